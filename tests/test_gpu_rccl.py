@@ -50,7 +50,7 @@ def test_bench_runs_its_collective_through_rccl_with_one_rank(extra):
     barrier and the max-over-ranks all-reduce; the oracle check of the last step still gates the run.  Also BASELINE's presets: --config 5 (streamed
     UZH-FPV replay, 256 pairs, the streamed step gathers) and --config 4 (MC samples over the ranks)."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-collective", "--steps", "5", "--warmup", "2",
-           "--no-cpu-baseline", "--no-latency", "--no-extras"] + extra
+           "--full", "--no-cpu-baseline", "--no-latency", "--no-extras"] + extra
     r = subprocess.run(cmd, env=_env(), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     res = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

@@ -1,7 +1,7 @@
 import json,sys,subprocess,os
 def run(env):
     e=dict(os.environ); e.update(env)
-    r=subprocess.run([sys.executable,"bench.py","--no-cpu-baseline","--no-extras","--steps","5","--warmup","2"],env=e,capture_output=True,text=True)
+    r=subprocess.run([sys.executable,"bench.py","--full","--no-cpu-baseline","--no-extras","--steps","5","--warmup","2"],env=e,capture_output=True,text=True)
     d=json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     l=d["latency_batch1_ms"]
     return l["p50"], {x["launch"]:x["us"] for x in l["per_launch_us"]}
