@@ -29,6 +29,9 @@ SYMBOLS = [
     "hnet_op_block4_fused", "hnet_op_block3_fused", "hnet_op_block42_fused", "hnet_precision", "hnet_overflow_flag",
     "hnet_create_group", "hnet_create_group_from_memory", "hnet_destroy_group", "hnet_group_size", "hnet_group_context", "hnet_group_stream",
     "hnet_group_last_error", "hnet_group_infer_batch_packed_device", "hnet_group_join", "hnet_group_synchronize", "hnet_group_overflow_flag",
+    "hnet_create_sessions", "hnet_destroy_sessions", "hnet_sessions_push", "hnet_sessions_add_camera", "hnet_sessions_bind_camera",
+    "hnet_sessions_push_raw", "hnet_sessions_infer", "hnet_sessions_image_count", "hnet_sessions_latest_time", "hnet_sessions_set_seq",
+    "hnet_sessions_seq", "hnet_sessions_reset", "hnet_sessions_get_frame", "hnet_sessions_last_timing", "hnet_infer_batch_seqs_packed_device",
 ]
 
 
@@ -136,6 +139,24 @@ def lib():
     L.hnet_group_join.argtypes = [vp, vp]
     L.hnet_group_synchronize.argtypes = [vp]
     L.hnet_group_overflow_flag.argtypes = [vp, C.POINTER(C.c_int)]
+    L.hnet_create_sessions.argtypes = [vp, C.c_int, C.POINTER(vp)]
+    L.hnet_destroy_sessions.argtypes = [vp]
+    L.hnet_destroy_sessions.restype = None
+    L.hnet_sessions_push.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_size_t, vp]
+    L.hnet_sessions_add_camera.argtypes = [vp, C.POINTER(Camera), C.POINTER(C.c_int)]
+    L.hnet_sessions_bind_camera.argtypes = [vp, C.c_int, C.c_int]
+    L.hnet_sessions_push_raw.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_size_t, vp]
+    L.hnet_sessions_infer.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
+    L.hnet_sessions_image_count.argtypes = [vp, C.c_int]
+    L.hnet_sessions_latest_time.argtypes = [vp, C.c_int]
+    L.hnet_sessions_latest_time.restype = C.c_double
+    L.hnet_sessions_set_seq.argtypes = [vp, C.c_int, C.c_uint64]
+    L.hnet_sessions_seq.argtypes = [vp, C.c_int]
+    L.hnet_sessions_seq.restype = C.c_uint64
+    L.hnet_sessions_reset.argtypes = [vp, C.c_int]
+    L.hnet_sessions_get_frame.argtypes = [vp, C.c_int, C.c_int, vp]
+    L.hnet_sessions_last_timing.argtypes = [vp, C.POINTER(Timing)]
+    L.hnet_infer_batch_seqs_packed_device.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp]
     for name in SYMBOLS:
         getattr(L, name)   # AttributeError here = the library does not export what include/hnet.h declares
     _lib = L

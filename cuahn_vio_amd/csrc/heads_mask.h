@@ -10,11 +10,18 @@
 
 namespace hnet {
 
+// The mask sequence number of pair b (the second half of its key, hnet_pair_key): seq_tab[b] when a per-pair table is given (hnet_infer_batch_seqs_packed_device,
+// hnet_sessions_infer: one independent count per camera), else pair_seq0 + the optional device-resident addend (graph replays) + b - every dropout site of the
+// forward forms its key here.
+__device__ __forceinline__ uint64_t pair_seq(const uint64_t* seq_tab, uint64_t pair_seq0, const uint64_t* seq_dev, uint32_t b) {
+    return seq_tab ? seq_tab[b] : pair_seq0 + (seq_dev ? *seq_dev : 0ull) + (uint64_t)b;
+}
+
 // vb: virtual block index; pre_row: three words of LDS.  Every thread of the 256-thread block must call it (one workgroup barrier inside).
 // A block's 1024 bytes span at most three rows (b, sample, head) of 640 bytes: the row's hash prefix (four hnet_mix32 and, with a run-time n_local, an integer
 // division) is formed by three threads and shared through LDS, and all index arithmetic is 32-bit.
-__device__ __forceinline__ void heads_mask_block(uint32_t vb, int batch, int n_local, int s_begin, uint32_t thr, uint64_t mc_seed, uint64_t pair_seq,
-                                                 uint8_t* __restrict__ mask, uint32_t* pre_row) {
+__device__ __forceinline__ void heads_mask_block(uint32_t vb, int batch, int n_local, int s_begin, uint32_t thr, uint64_t mc_seed, uint64_t pair_seq0,
+                                                 const uint64_t* seq_dev, const uint64_t* seq_tab, uint8_t* __restrict__ mask, uint32_t* pre_row) {
     const size_t nmask = (size_t)batch * n_local * 2 * 640;
     const size_t i = (size_t)vb * 256 + threadIdx.x;
     const uint32_t i0 = vb * 1024u, row0 = i0 / 640u, rem0 = i0 - row0 * 640u;
@@ -22,7 +29,7 @@ __device__ __forceinline__ void heads_mask_block(uint32_t vb, int batch, int n_l
         const uint32_t row = row0 + threadIdx.x;                      // rows beyond the end are never read
         const uint32_t head = row & 1u, t = row >> 1;
         const uint32_t b = t / (uint32_t)n_local, sm = t - b * (uint32_t)n_local;
-        pre_row[threadIdx.x] = hnet_mask_prefix(hnet_pair_key(mc_seed, pair_seq + (uint64_t)b), 2u * head, (uint32_t)s_begin + sm);
+        pre_row[threadIdx.x] = hnet_mask_prefix(hnet_pair_key(mc_seed, pair_seq(seq_tab, pair_seq0, seq_dev, b)), 2u * head, (uint32_t)s_begin + sm);
     }
     __syncthreads();
     if (4 * i >= nmask) return;                                       // nmask is a multiple of 640: the four bytes are all in or all out

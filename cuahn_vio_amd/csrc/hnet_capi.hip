@@ -383,6 +383,7 @@ struct FwdArgs {
     int pair0 = 0;            // first pair of this chunk inside the persistent buffers (caller arrays are pre-offset)
     bool use_ws = true;       // may use the context's split-K workspace (false for concurrent chunks)
     const uint64_t* seq_dev = nullptr;   // device addend to seq0 (graph replays)
+    const uint64_t* seq_tab = nullptr;   // device [batch]: the sequence number of every pair (replaces seq0 / seq_dev; hnet_sessions_infer, hnet_infer_batch_seqs_packed_device)
     int mean_stride = 8, cov_stride = 64;   // floats between consecutive pairs of `mean` / `cov` (72 / 72: the packed [B][72] record)
     uint32_t* flag = nullptr;               // where the kernels raise the overflow / timeout bits (nullptr: the context's device word; hnet_infer's graph: a word of its pinned block)
 };
@@ -450,7 +451,7 @@ int forward_chunk(hnet_ctx* c, const FwdArgs& a, hipStream_t s) {
                     pend.mask = c->head_mask + P0 * c->n_local * 2 * 640;
                     pend.mask_blocks = (int)(((size_t)B * c->n_local * 2 * 160 + 255) / 256);
                     pend.n_local = c->n_local; pend.s_begin = c->s_begin; pend.thr = hnet_drop_threshold(g.dropout_p);
-                    pend.mc_seed = g.mc_seed; pend.pair_seq0 = a.seq0; pend.seq_dev = a.seq_dev;
+                    pend.mc_seed = g.mc_seed; pend.pair_seq0 = a.seq0; pend.seq_dev = a.seq_dev; pend.seq_tab = a.seq_tab;
                     mask_ready = true;
                 }
                 STAGE(launch_prep_fc(a.prev, a.curr, a.pix_fmt, pend, 8 >> blk, x, B, s, x16, c->x16_plane, c->n_planes, c->warp_exact));
@@ -560,14 +561,14 @@ int forward_chunk(hnet_ctx* c, const FwdArgs& a, hipStream_t s) {
         LatIO lat_h = {nullptr, 1, small && c->lat_tail && c->n_planes == 2, mask_ready};
         STAGE(launch_heads_fc1_s3(feat, B, c->n_local, c->s_begin, g.dropout_p, g.mc_seed, a.seq0, c->w1_16, c->b1, hidden,
                                   c->feat16 + P0 * 5120, (size_t)g.max_batch * 5120, c->head_mask + P0 * c->n_local * 2 * 640, s, ws, wsn, a.seq_dev, c->n_planes,
-                                  c->s3_tile, &lat_h));
+                                  c->s3_tile, &lat_h, a.seq_tab));
         set_kernels(lat_h.kernels);
     }
     else
-        STAGE(launch_heads_fc1(feat, B, c->n_local, c->s_begin, g.dropout_p, g.mc_seed, a.seq0, c->w1, c->b1, hidden, s, ws, wsn, a.seq_dev));
+        STAGE(launch_heads_fc1(feat, B, c->n_local, c->s_begin, g.dropout_p, g.mc_seed, a.seq0, c->w1, c->b1, hidden, s, ws, wsn, a.seq_dev, a.seq_tab));
     if (a.partial) {
         STAGE(launch_heads_fc2(hidden, B, c->n_local, c->s_begin, g.dropout_p, g.mc_seed, a.seq0, c->w2, c->b2,
-                               a.mean_s, a.logvar_s, s, a.seq_dev, flagp));
+                               a.mean_s, a.logvar_s, s, a.seq_dev, flagp, a.seq_tab));
         if (a.h_part1) {
             hipError_t e = hipMemcpyAsync(a.h_part1, Hm, (size_t)B * 9 * sizeof(float), hipMemcpyDeviceToDevice, s);
             if (e != hipSuccess) return fail(c, HNET_ERR_DEVICE, "copy H_part1");
@@ -578,9 +579,9 @@ int forward_chunk(hnet_ctx* c, const FwdArgs& a, hipStream_t s) {
     float* lv = c->logvar_s + P0 * c->n_local * 8;
     if (small && c->n_local <= HEADS_FC2_FINISH_MAX_N) {
         STAGE(launch_heads_fc2_finish(hidden, B, c->n_local, c->s_begin, g.dropout_p, g.mc_seed, a.seq0, c->w2, c->b2, Hm, a.mean, a.cov, Htot, s,
-                                      a.seq_dev, flagp, a.mean_stride, a.cov_stride));
+                                      a.seq_dev, flagp, a.mean_stride, a.cov_stride, a.seq_tab));
     } else {
-        STAGE(launch_heads_fc2(hidden, B, c->n_local, c->s_begin, g.dropout_p, g.mc_seed, a.seq0, c->w2, c->b2, ms, lv, s, a.seq_dev));
+        STAGE(launch_heads_fc2(hidden, B, c->n_local, c->s_begin, g.dropout_p, g.mc_seed, a.seq0, c->w2, c->b2, ms, lv, s, a.seq_dev, nullptr, a.seq_tab));
         STAGE(launch_mc_finish(ms, lv, c->n_local, Hm, B, a.mean, a.cov, Htot, s, flagp, a.mean_stride, a.cov_stride));
     }
     if (g.emit_error_map && (a.err || a.err_u8))                                     // :319-327
@@ -1341,12 +1342,13 @@ int hnet_set_undistort_maps(hnet_ctx* c, const float* map_x, const float* map_y,
     return HNET_OK;
 }
 
-int hnet_set_camera(hnet_ctx* c, const hnet_camera* cam) {
-    if (!c || !cam) return HNET_ERR_INVALID_ARG;
+// initialize_undist_map[_fisheye] (CamBase.h:165-180): the maps of `cam` (hnet_set_camera, hnet_sessions_add_camera)
+static void build_undistort_maps(const hnet_camera* cam, std::vector<float>& mx, std::vector<float>& my) {
     // the virtual camera every frame is resampled to: 90 deg horizontal field of view on 320 px (CamBase.h:166-169)
     const double f = (IMG_W - 1.0) / 2.0 / std::tan(45.0 / 180.0 * (2.0 * std::acos(0.0)));
     const double cx = (IMG_W - 1.0) / 2.0, cy = (IMG_H - 1.0) / 2.0;
-    std::vector<float> mx(NPIX), my(NPIX);
+    mx.assign(NPIX, 0.0f);
+    my.assign(NPIX, 0.0f);
     for (int v = 0; v < IMG_H; v++)
         for (int u = 0; u < IMG_W; u++) {
             const double x = (u - cx) / f, y = (v - cy) / f;          // R = I: the pixel's ray in the virtual camera
@@ -1364,6 +1366,12 @@ int hnet_set_camera(hnet_ctx* c, const hnet_camera* cam) {
             mx[v * IMG_W + u] = (float)(cam->k[0] * xd + cam->k[2]);
             my[v * IMG_W + u] = (float)(cam->k[1] * yd + cam->k[3]);
         }
+}
+
+int hnet_set_camera(hnet_ctx* c, const hnet_camera* cam) {
+    if (!c || !cam) return HNET_ERR_INVALID_ARG;
+    std::vector<float> mx, my;
+    build_undistort_maps(cam, mx, my);
     return hnet_set_undistort_maps(c, mx.data(), my.data(), cam->raw_rows, cam->raw_cols);
 }
 
@@ -2043,6 +2051,344 @@ int hnet_debug_h_part1(hnet_ctx* c, int pair, float* out9) {
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(out9, (c->H_last ? c->H_last : c->Hm) + (size_t)pair * 9, 36, hipMemcpyDeviceToHost));
+    return HNET_OK;
+}
+
+int hnet_infer_batch_seqs_packed_device(hnet_ctx* c, const void* d_prev, const void* d_curr, int pix_fmt, const float* d_prior, int batch,
+                                        const uint64_t* d_pair_seq, float* d_out72, float* d_err_map, void* stream) {
+    if (!c || !d_prev || !d_curr || !d_pair_seq || !d_out72) return HNET_ERR_INVALID_ARG;
+    if (pix_fmt != HNET_PIX_U8 && pix_fmt != HNET_PIX_F32) return fail(c, HNET_ERR_INVALID_ARG, "pix_fmt");
+    if (d_err_map && !c->cfg.emit_error_map) return fail(c, HNET_ERR_INVALID_ARG, "context was created without emit_error_map");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    FwdArgs a = {d_prev, d_curr, pix_fmt, d_prior, batch, 0, d_out72, d_out72 + 8, d_err_map, nullptr, nullptr, nullptr, nullptr, false};
+    a.mean_stride = a.cov_stride = HNET_PACKED_FLOATS;
+    a.seq_tab = d_pair_seq;
+    return forward(c, a, stream ? (hipStream_t)stream : c->stream);
+}
+
+// ---- sessions: many camera streams on one context (include/hnet.h).  Per session: image count, ring orientation, time stamp, mask sequence number and camera, all
+// on the host; the frames live in a device ring of 2 slots per session (slot 2 id + k).  Every device step runs on the context's stream.
+struct hnet_sessions {
+    hnet_ctx* ctx = nullptr;
+    int n = 0;
+    uint8_t* ring = nullptr;                   // device [n][2][NPIX]
+    struct Sess { int count = 0, curr = 0, cam = -1; double t = -1.0; uint64_t seq = 0; };
+    std::vector<Sess> st;
+    std::vector<uint8_t> mark;                 // id validation scratch (repeats within one call)
+    struct Cam { float* map[2]; int rows, cols; };
+    std::vector<Cam> cams;
+    const float** d_maps = nullptr;            // device [cams][2]: the map pointers session_remap_kernel reads
+    // push: two pinned blocks used in turn (the ev_img pattern of hnet_push_image), each {slot table [n] i32, camera table [n] i32 | frames}, and one device slab
+    uint8_t* pin[2] = {nullptr, nullptr};
+    size_t pin_cap[2] = {0, 0};
+    hipEvent_t ev_pin[2] = {nullptr, nullptr};
+    int pin_next = 0;
+    uint8_t* slab = nullptr;
+    size_t slab_cap = 0;
+    // infer: ONE pinned block {priors [n][8] f32 | seq table [n] u64 | pair table [n][2] i32} and its device copy, sized for max_batch
+    uint8_t* pin_tab = nullptr;
+    uint8_t* d_tab = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hnet_timing timing = {};
+};
+
+static constexpr int HNET_SESSIONS_MAX = 1 << 16;
+static size_t sessions_header(int n) { return ((size_t)n * 8 + 255) & ~(size_t)255; }      // slot + camera tables, 256-byte aligned frames behind them
+
+// n distinct ids in range, n within the context's capacity
+static int sessions_check_ids(hnet_sessions* s, int n, const int32_t* ids) {
+    hnet_ctx* c = s->ctx;
+    if (!ids || n < 1) return fail(c, HNET_ERR_INVALID_ARG, "sessions: n < 1 or no ids");
+    if (n > c->cfg.max_batch) return fail(c, HNET_ERR_CAPACITY, "sessions: n exceeds max_batch");
+    int rc = HNET_OK;
+    int i = 0;
+    for (; i < n; i++) {
+        if (ids[i] < 0 || ids[i] >= s->n) { rc = fail(c, HNET_ERR_INVALID_ARG, "sessions: id out of range"); break; }
+        if (s->mark[ids[i]]) { rc = fail(c, HNET_ERR_INVALID_ARG, "sessions: id repeated in one call"); break; }
+        s->mark[ids[i]] = 1;
+    }
+    for (int j = 0; j < i; j++) s->mark[ids[j]] = 0;
+    return rc;
+}
+
+// pinned block of the next push with room for `bytes` (its previous upload has completed) and a device slab as large
+static int sessions_stage(hnet_sessions* s, size_t bytes, uint8_t** pin) {
+    hnet_ctx* c = s->ctx;
+    const int k = s->pin_next;
+    HIPCHK(c, hipEventSynchronize(s->ev_pin[k]));
+    if (s->pin_cap[k] < bytes) {
+        if (s->pin[k]) HIPCHK(c, hipHostFree(s->pin[k]));
+        s->pin[k] = nullptr;
+        s->pin_cap[k] = 0;
+        HIPCHK(c, hipHostMalloc((void**)&s->pin[k], bytes, hipHostMallocDefault));
+        s->pin_cap[k] = bytes;
+    }
+    if (s->slab_cap < bytes) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));               // (earlier scatters may still read it)
+        if (s->slab) HIPCHK(c, hipFree(s->slab));
+        s->slab = nullptr;
+        s->slab_cap = 0;
+        HIPCHK(c, hipMalloc((void**)&s->slab, bytes));
+        s->slab_cap = bytes;
+    }
+    *pin = s->pin[k];
+    return HNET_OK;
+}
+
+// after a push was enqueued: the slot each session wrote, its count and time stamp (hnet_push_image, :134-148)
+static void sessions_commit_push(hnet_sessions* s, int n, const int32_t* ids, const double* t) {
+    for (int i = 0; i < n; i++) {
+        hnet_sessions::Sess& e = s->st[ids[i]];
+        e.curr = e.count == 0 ? 0 : (e.curr ^ 1);
+        e.count++;
+        if (e.count >= 2 && t) e.t = t[i];
+    }
+    s->pin_next ^= 1;
+}
+static int sessions_slot(const hnet_sessions* s, int id) { const hnet_sessions::Sess& e = s->st[id]; return 2 * id + (e.count == 0 ? 0 : (e.curr ^ 1)); }
+
+void hnet_destroy_sessions(hnet_sessions* s) {
+    if (!s) return;
+    hnet_ctx* c = s->ctx;
+    (void)hipSetDevice(c->cfg.device_id);
+    (void)hipStreamSynchronize(c->stream);
+    auto fr = [](void* p) { if (p) (void)hipFree(p); };
+    fr(s->ring); fr(s->slab); fr(s->d_tab); fr((void*)s->d_maps);
+    for (auto& k : s->cams) { fr(k.map[0]); fr(k.map[1]); }
+    for (int i = 0; i < 2; i++) {
+        if (s->pin[i]) (void)hipHostFree(s->pin[i]);
+        if (s->ev_pin[i]) (void)hipEventDestroy(s->ev_pin[i]);
+    }
+    if (s->pin_tab) (void)hipHostFree(s->pin_tab);
+    if (s->ev0) (void)hipEventDestroy(s->ev0);
+    if (s->ev1) (void)hipEventDestroy(s->ev1);
+    delete s;
+}
+
+int hnet_create_sessions(hnet_ctx* c, int n_sessions, hnet_sessions** out) {
+    if (!c || !out) return HNET_ERR_INVALID_ARG;
+    if (n_sessions < 1 || n_sessions > HNET_SESSIONS_MAX) return fail(c, HNET_ERR_INVALID_ARG, "hnet_create_sessions: n_sessions outside 1 .. 65536");
+    if (c->s_begin != 0 || c->n_local != c->cfg.mc_samples) return fail(c, HNET_ERR_UNSUPPORTED, "hnet_create_sessions: the context evaluates a sample shard");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    hnet_sessions* s = new hnet_sessions();
+    s->ctx = c;
+    s->n = n_sessions;
+    s->st.resize(n_sessions);
+    s->mark.assign(n_sessions, 0);
+    const size_t tab = (size_t)c->cfg.max_batch * (8 + 32 + 8);
+    hipError_t e = hipMalloc((void**)&s->ring, (size_t)n_sessions * 2 * NPIX);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&s->pin_tab, tab, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipMalloc((void**)&s->d_tab, tab);
+    for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipEventCreateWithFlags(&s->ev_pin[i], hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreate(&s->ev0);
+    if (e == hipSuccess) e = hipEventCreate(&s->ev1);
+    if (e != hipSuccess) {
+        hnet_destroy_sessions(s);
+        return fail(c, HNET_ERR_DEVICE, std::string("hnet_create_sessions: ") + hipGetErrorString(e));
+    }
+    *out = s;
+    return HNET_OK;
+}
+
+int hnet_sessions_push(hnet_sessions* s, int n, const int32_t* ids, const uint8_t* frames, int row_stride, size_t frame_stride, const double* t) {
+    if (!s) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = s->ctx;
+    if (!frames || row_stride < IMG_W || (n > 1 && frame_stride < (size_t)(IMG_H - 1) * row_stride + IMG_W))
+        return fail(c, HNET_ERR_INVALID_ARG, "hnet_sessions_push: frames must be 224x320 8-bit, row_stride >= 320, frames apart by frame_stride");
+    int rc = sessions_check_ids(s, n, ids);
+    if (rc != HNET_OK) return rc;
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    const size_t hdr = sessions_header(n), bytes = hdr + (size_t)n * NPIX;
+    uint8_t* pin = nullptr;
+    if ((rc = sessions_stage(s, bytes, &pin)) != HNET_OK) return rc;
+    int32_t* dst = reinterpret_cast<int32_t*>(pin);
+    for (int i = 0; i < n; i++) {
+        dst[i] = sessions_slot(s, ids[i]);
+        const uint8_t* f = frames + (size_t)i * frame_stride;
+        uint8_t* o = pin + hdr + (size_t)i * NPIX;
+        if (row_stride == IMG_W) memcpy(o, f, NPIX);
+        else for (int r = 0; r < IMG_H; r++) memcpy(o + (size_t)r * IMG_W, f + (size_t)r * row_stride, IMG_W);
+    }
+    HIPCHK(c, hipMemcpyAsync(s->slab, pin, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, launch_session_scatter(s->slab + hdr, reinterpret_cast<const int32_t*>(s->slab), n, 2 * s->n, s->ring, c->stream));
+    HIPCHK(c, hipEventRecord(s->ev_pin[s->pin_next], c->stream));
+    sessions_commit_push(s, n, ids, t);
+    return HNET_OK;
+}
+
+int hnet_sessions_add_camera(hnet_sessions* s, const hnet_camera* cam, int* cam_id) {
+    if (!s) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = s->ctx;
+    if (!cam || !cam_id || cam->raw_rows < 1 || cam->raw_cols < 1 || cam->raw_rows > 16384 || cam->raw_cols > 16384)
+        return fail(c, HNET_ERR_INVALID_ARG, "hnet_sessions_add_camera: camera");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    std::vector<float> mx, my;
+    build_undistort_maps(cam, mx, my);
+    hnet_sessions::Cam k = {{nullptr, nullptr}, cam->raw_rows, cam->raw_cols};
+    DevTemps tmp;                                                  // (freed unless the camera is committed below)
+    HIPCHK(c, tmp.alloc(&k.map[0], (size_t)NPIX));
+    HIPCHK(c, tmp.alloc(&k.map[1], (size_t)NPIX));
+    HIPCHK(c, hipMemcpy(k.map[0], mx.data(), NPIX * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(k.map[1], my.data(), NPIX * 4, hipMemcpyHostToDevice));
+    std::vector<const float*> tab;
+    for (auto& q : s->cams) { tab.push_back(q.map[0]); tab.push_back(q.map[1]); }
+    tab.push_back(k.map[0]);
+    tab.push_back(k.map[1]);
+    const float** d_maps = nullptr;
+    HIPCHK(c, tmp.alloc(&d_maps, tab.size()));
+    HIPCHK(c, hipMemcpy(d_maps, tab.data(), tab.size() * sizeof(float*), hipMemcpyHostToDevice));
+    HIPCHK(c, hipStreamSynchronize(c->stream));                    // enqueued remaps read the old table
+    tmp.ptrs.clear();
+    if (s->d_maps) (void)hipFree((void*)s->d_maps);
+    s->d_maps = d_maps;
+    s->cams.push_back(k);
+    *cam_id = (int)s->cams.size() - 1;
+    return HNET_OK;
+}
+
+int hnet_sessions_bind_camera(hnet_sessions* s, int id, int cam_id) {
+    if (!s) return HNET_ERR_INVALID_ARG;
+    if (id < 0 || id >= s->n || cam_id < 0 || cam_id >= (int)s->cams.size()) return fail(s->ctx, HNET_ERR_INVALID_ARG, "hnet_sessions_bind_camera: id or camera");
+    s->st[id].cam = cam_id;
+    return HNET_OK;
+}
+
+int hnet_sessions_push_raw(hnet_sessions* s, int n, const int32_t* ids, const uint8_t* raw, int rows, int cols, int row_stride, size_t frame_stride,
+                           const double* t) {
+    if (!s) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = s->ctx;
+    if (!raw || rows < 1 || cols < 1 || row_stride < cols || (n > 1 && frame_stride < (size_t)(rows - 1) * row_stride + cols))
+        return fail(c, HNET_ERR_INVALID_ARG, "hnet_sessions_push_raw: raw frame geometry");
+    int rc = sessions_check_ids(s, n, ids);
+    if (rc != HNET_OK) return rc;
+    for (int i = 0; i < n; i++) {
+        const int k = s->st[ids[i]].cam;
+        if (k < 0) return fail(c, HNET_ERR_INVALID_ARG, "hnet_sessions_push_raw: session without a camera (hnet_sessions_bind_camera)");
+        if (s->cams[k].rows != rows || s->cams[k].cols != cols) return fail(c, HNET_ERR_INVALID_ARG, "hnet_sessions_push_raw: raw image size differs from the camera's");
+    }
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    const size_t frame = ((size_t)rows * cols + 15) & ~(size_t)15;
+    const size_t hdr = sessions_header(n), bytes = hdr + (size_t)n * frame;
+    uint8_t* pin = nullptr;
+    if ((rc = sessions_stage(s, bytes, &pin)) != HNET_OK) return rc;
+    int32_t* dst = reinterpret_cast<int32_t*>(pin);
+    for (int i = 0; i < n; i++) {
+        dst[i] = sessions_slot(s, ids[i]);
+        dst[n + i] = s->st[ids[i]].cam;
+        const uint8_t* f = raw + (size_t)i * frame_stride;
+        uint8_t* o = pin + hdr + (size_t)i * frame;
+        for (int r = 0; r < rows; r++) memcpy(o + (size_t)r * cols, f + (size_t)r * row_stride, cols);
+    }
+    HIPCHK(c, hipMemcpyAsync(s->slab, pin, bytes, hipMemcpyHostToDevice, c->stream));
+    const int32_t* d_dst = reinterpret_cast<const int32_t*>(s->slab);
+    HIPCHK(c, launch_session_remap(s->slab + hdr, frame, rows, cols, d_dst, d_dst + n, s->d_maps, (int)s->cams.size(), n, 2 * s->n, s->ring, c->stream));
+    HIPCHK(c, hipEventRecord(s->ev_pin[s->pin_next], c->stream));
+    sessions_commit_push(s, n, ids, t);
+    return HNET_OK;
+}
+
+int hnet_sessions_infer(hnet_sessions* s, int n, const int32_t* ids, const double* prior_px, float* mean, float* cov, uint8_t* err_map) {
+    if (!s) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = s->ctx;
+    if (!mean || !cov) return fail(c, HNET_ERR_INVALID_ARG, "hnet_sessions_infer: mean / cov");
+    int rc = sessions_check_ids(s, n, ids);
+    if (rc != HNET_OK) return rc;
+    if (err_map && !c->cfg.emit_error_map) return fail(c, HNET_ERR_INVALID_ARG, "context was created without emit_error_map");
+    if (c->cfg.use_prior && !prior_px) return fail(c, HNET_ERR_INVALID_ARG, "prior required");
+    for (int i = 0; i < n; i++)
+        if (s->st[ids[i]].count < 2) return fail(c, HNET_ERR_NOT_READY, "HNet cannot inference! Only has one image!");   // :155-158, per session
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    auto t0 = std::chrono::steady_clock::now();
+    // ONE pinned block, ONE upload: the sequence numbers, the priors (:160-165 toType(kFloat)) and the (prev, curr) ring slots of every pair
+    float* pr = reinterpret_cast<float*>(s->pin_tab);
+    uint64_t* seq = reinterpret_cast<uint64_t*>(pr + (size_t)8 * n);
+    int32_t* pairs = reinterpret_cast<int32_t*>(seq + n);
+    for (int i = 0; i < n; i++) {
+        const hnet_sessions::Sess& e = s->st[ids[i]];
+        seq[i] = e.seq;
+        for (int k = 0; k < 8; k++) pr[8 * i + k] = c->cfg.use_prior ? (float)prior_px[8 * i + k] : 0.0f;
+        pairs[2 * i] = 2 * ids[i] + (e.curr ^ 1);
+        pairs[2 * i + 1] = 2 * ids[i] + e.curr;
+    }
+    const size_t bytes = (size_t)n * (8 + 32 + 8);
+    const float* d_pr = reinterpret_cast<const float*>(s->d_tab);
+    const uint64_t* d_seq = reinterpret_cast<const uint64_t*>(d_pr + (size_t)8 * n);
+    const int32_t* d_pairs = reinterpret_cast<const int32_t*>(d_seq + n);
+    hipStream_t st = c->stream;
+    FwdArgs a = {c->stage_prev, c->stage_curr, HNET_PIX_U8, c->cfg.use_prior ? d_pr : nullptr, n, 0, c->d_mean, c->d_cov, nullptr,
+                 err_map ? c->d_err_u8 : nullptr, nullptr, nullptr, nullptr, false};
+    a.seq_tab = d_seq;
+    uint32_t flag_now = 0;
+    auto enqueue = [&]() -> int {
+        HIPCHK(c, hipMemcpyAsync(s->d_tab, s->pin_tab, bytes, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipEventRecord(s->ev0, st));
+        HIPCHK(c, launch_session_gather(s->ring, 2 * s->n, d_pairs, n, (uint8_t*)c->stage_prev, (uint8_t*)c->stage_curr, st));
+        const int r = forward(c, a, st);
+        if (r != HNET_OK) return r;
+        HIPCHK(c, hipEventRecord(s->ev1, st));
+        HIPCHK(c, hipMemcpyAsync(mean, c->d_mean, (size_t)n * 8 * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(cov, c->d_cov, (size_t)n * 64 * sizeof(float), hipMemcpyDeviceToHost, st));
+        if (err_map) HIPCHK(c, hipMemcpyAsync(err_map, c->d_err_u8, (size_t)n * NPIX, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(&flag_now, c->d_flag, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemsetAsync(c->d_flag, 0, 4, st));          // host results are inspected below (as in hnet_infer_batch)
+        HIPCHK(c, hipStreamSynchronize(st));
+        return HNET_OK;
+    };
+    rc = enqueue();
+    if (rc != HNET_OK) { (void)hipStreamSynchronize(st); return rc; }      // (the pinned table may still be read by the copy)
+    // the repeats of hnet_infer_batch (:1656-1665): same table, the counts advance once
+    if (flag_now & CH_FLAG_TIMEOUT) {
+        if ((rc = chain_gave_up(c)) != HNET_OK || (rc = enqueue()) != HNET_OK) { (void)hipStreamSynchronize(st); return rc; }
+    }
+    if (c->n_planes == 2 && !(all_finite(mean, (size_t)n * 8) && all_finite(cov, (size_t)n * 64)) && prior_finite(c->cfg.use_prior ? prior_px : nullptr, (size_t)n * 8)) {
+        if ((rc = demote_to_bf16x3(c)) != HNET_OK || (rc = enqueue()) != HNET_OK) { (void)hipStreamSynchronize(st); return rc; }
+    }
+    for (int i = 0; i < n; i++) s->st[ids[i]].seq++;                  // n_inferences of each session's dedicated context (:1540, 1561)
+    float ms = 0;
+    HIPCHK(c, hipEventElapsedTime(&ms, s->ev0, s->ev1));
+    s->timing.device_ms = ms;
+    s->timing.host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    s->timing.n_inferences++;
+    s->timing.n_main_inferences++;
+    if (s->timing.n_main_inferences > 100) s->timing.sum_device_ms_after_100 += ms;
+    return HNET_OK;
+}
+
+int hnet_sessions_image_count(const hnet_sessions* s, int id) { return (s && id >= 0 && id < s->n) ? s->st[id].count : -1; }
+double hnet_sessions_latest_time(const hnet_sessions* s, int id) { return (s && id >= 0 && id < s->n) ? s->st[id].t : -1.0; }
+uint64_t hnet_sessions_seq(const hnet_sessions* s, int id) { return (s && id >= 0 && id < s->n) ? s->st[id].seq : 0; }
+
+int hnet_sessions_set_seq(hnet_sessions* s, int id, uint64_t seq) {
+    if (!s) return HNET_ERR_INVALID_ARG;
+    if (id < 0 || id >= s->n) return fail(s->ctx, HNET_ERR_INVALID_ARG, "sessions: id out of range");
+    s->st[id].seq = seq;
+    return HNET_OK;
+}
+
+int hnet_sessions_reset(hnet_sessions* s, int id) {
+    if (!s) return HNET_ERR_INVALID_ARG;
+    if (id < 0 || id >= s->n) return fail(s->ctx, HNET_ERR_INVALID_ARG, "sessions: id out of range");
+    s->st[id].count = 0;
+    s->st[id].curr = 0;
+    s->st[id].t = -1.0;
+    return HNET_OK;
+}
+
+int hnet_sessions_get_frame(hnet_sessions* s, int id, int which, uint8_t* out) {
+    if (!s) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = s->ctx;
+    if (!out || id < 0 || id >= s->n || (which != 0 && which != 1)) return fail(c, HNET_ERR_INVALID_ARG, "hnet_sessions_get_frame: id / which / out");
+    const hnet_sessions::Sess& e = s->st[id];
+    if (e.count < (which == 0 ? 2 : 1)) return fail(c, HNET_ERR_NOT_READY, "hnet_sessions_get_frame: no such frame yet");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    HIPCHK(c, hipMemcpyAsync(out, s->ring + (size_t)(2 * id + (which == 1 ? e.curr : e.curr ^ 1)) * NPIX, NPIX, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return HNET_OK;
+}
+
+int hnet_sessions_last_timing(const hnet_sessions* s, hnet_timing* out) {
+    if (!s || !out) return HNET_ERR_INVALID_ARG;
+    *out = s->timing;
     return HNET_OK;
 }
 

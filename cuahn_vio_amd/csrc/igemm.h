@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/hnet_rng.h"
+#include "heads_mask.h"
 
 namespace hnet {
 
@@ -45,6 +46,7 @@ struct IgemmParams {
     float scale;          // 1/(1-p)
     uint64_t mc_seed, pair_seq0;
     const uint64_t* seq_dev;   // optional device-resident addend to pair_seq0 (lets a captured hipGraph be replayed with a new sequence number)
+    const uint64_t* seq_tab;   // optional per-pair sequence numbers [B] (replace pair_seq0 / seq_dev: heads_mask.h pair_seq)
     // split-K (small-M launches): gridDim.z = k_split slices of the K loop, raw partial sums go to
     // partial[z][M][N]; splitk_reduce_kernel adds them in z order (deterministic) and applies bias + LeakyReLU
     int k_split;
@@ -156,7 +158,7 @@ struct HeadLoader {
         int s = p.s_begin + (mm - b * p.n_local);
         int head = n0 >> 8;     // columns 0..255 = mean head, 256..511 = uncertainty head
         r.feat = p.A + (size_t)b * 5120;
-        const uint64_t seq = p.pair_seq0 + (p.seq_dev ? *p.seq_dev : 0ull) + (uint64_t)b;
+        const uint64_t seq = pair_seq(p.seq_tab, p.pair_seq0, p.seq_dev, (uint32_t)b);
         r.prefix = hnet_mask_prefix(hnet_pair_key(p.mc_seed, seq), (uint32_t)(2 * head), (uint32_t)s);
         return r;
     }

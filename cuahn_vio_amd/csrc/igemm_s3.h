@@ -1126,7 +1126,7 @@ __global__ __launch_bounds__(512, 2) void igemm_s3_lean8_kernel(S3Params p) {
 // reference's NCHW flatten index c*20 + pix (include/hnet_rng.h); stream 0 = mean head, 2 = uncertainty head.
 static __global__ __launch_bounds__(256) void heads_prep_kernel(const float* __restrict__ feat, int batch, int n_local, int s_begin,
                                                          uint32_t thr, float scale, uint64_t mc_seed, uint64_t pair_seq0,
-                                                         const uint64_t* __restrict__ seq_dev,
+                                                         const uint64_t* __restrict__ seq_dev, const uint64_t* __restrict__ seq_tab,
                                                          uint16_t* __restrict__ feat16, size_t f_plane, uint8_t* __restrict__ mask, int np, int ktile_layout) {
     // (plain-bf16 mode reads plane 0 only; writing all three costs nothing measurable here)
     const size_t nfeat = (size_t)batch * 5120;
@@ -1147,7 +1147,7 @@ static __global__ __launch_bounds__(256) void heads_prep_kernel(const float* __r
     // halves of consecutive ROWS of one K-tile (coalesced 4-byte stores), every thread forms its own row prefix.
     __shared__ uint32_t pre_row[3];
     if (!ktile_layout) {                                              // (uniform) the row-major layout: heads_mask.h
-        heads_mask_block(blockIdx.x, batch, n_local, s_begin, thr, mc_seed, pair_seq0 + (seq_dev ? *seq_dev : 0ull), mask, pre_row);
+        heads_mask_block(blockIdx.x, batch, n_local, s_begin, thr, mc_seed, pair_seq0, seq_dev, seq_tab, mask, pre_row);
         return;
     }
     if (4 * i < nmask) {                                              // nmask is a multiple of 640: the four bytes are all in or all out
@@ -1157,7 +1157,7 @@ static __global__ __launch_bounds__(256) void heads_prep_kernel(const float* __r
             const uint32_t M = (uint32_t)batch * (uint32_t)n_local, g = (uint32_t)i, half = g & 1u, t = g >> 1;
             const uint32_t q = t / M, m = t - q * M, head = q / 80u, it = q - head * 80u;
             const uint32_t b = m / (uint32_t)n_local, sm = m - b * (uint32_t)n_local;
-            pre = hnet_mask_prefix(hnet_pair_key(mc_seed, pair_seq0 + (seq_dev ? *seq_dev : 0ull) + (uint64_t)b), 2u * head, (uint32_t)s_begin + sm);
+            pre = hnet_mask_prefix(hnet_pair_key(mc_seed, pair_seq(seq_tab, pair_seq0, seq_dev, b)), 2u * head, (uint32_t)s_begin + sm);
             chunk = (int)(it * 8u + half * 4u);
             oidx = (q * M + m) * 2u + half;
         }

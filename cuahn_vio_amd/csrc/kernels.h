@@ -81,14 +81,15 @@ hipError_t launch_heads_fc1_s3(const float* feat, int batch, int n_local, int s_
                                uint64_t pair_seq0, const uint16_t* w1planes, const float* b1, float* hidden,
                                uint16_t* feat16, size_t f_plane, uint8_t* mask, hipStream_t s,
                                float* ws = nullptr, size_t ws_floats = 0, const uint64_t* seq_dev = nullptr, int n_planes = 3, int tile = 0,
-                               LatIO* lat = nullptr /* lat->heads_one_launch, fp16-plane mode, batch <= 8, n_local <= 64: the one-launch kernel of heads_lat.h */);
+                               LatIO* lat = nullptr /* lat->heads_one_launch, fp16-plane mode, batch <= 8, n_local <= 64: the one-launch kernel of heads_lat.h */,
+                               const uint64_t* seq_tab = nullptr /* per-pair sequence numbers [B] instead of pair_seq0 + b (heads_mask.h pair_seq) */);
 hipError_t launch_nchw_f32_to_nhwc_s3(const float* in, uint16_t* out, size_t o_plane, int batch, int c, int h, int w, hipStream_t s, int n_planes = 3);
 hipError_t launch_nhwc_s3_to_nchw_f32(const uint16_t* in, size_t i_plane, float* out, int batch, int c, int h, int w, hipStream_t s, int n_planes = 3);
 
 // first FC of both heads with MC-dropout on the input: feat [B][5120] (NHWC flatten) -> hidden [B*n_local][512]
 hipError_t launch_heads_fc1(const float* feat, int batch, int n_local, int s_begin, float p, uint64_t mc_seed,
                             uint64_t pair_seq0, const float* w1packed, const float* b1, float* hidden, hipStream_t s,
-                            float* ws = nullptr, size_t ws_floats = 0, const uint64_t* seq_dev = nullptr);
+                            float* ws = nullptr, size_t ws_floats = 0, const uint64_t* seq_dev = nullptr, const uint64_t* seq_tab = nullptr);
 
 // Input of the fused block-4 kernel (conv_b4_fused.h, DMA staging): cat(img1, warp(img2, H)) as bf16 planes with a zero border,
 // [plane][B][B4_HP][B4_WP] dwords (lo half = channel 0, hi half = channel 1), pixel (u, v) at row v + B4_PADY, column u + B4_PADX.
@@ -136,6 +137,7 @@ struct FcArgs {
     uint32_t thr;           // hnet_drop_threshold(p)
     uint64_t mc_seed, pair_seq0;
     const uint64_t* seq_dev;
+    const uint64_t* seq_tab;   // per-pair sequence numbers [B] or nullptr (heads_mask.h pair_seq)
     // round 6: the FC as 32 partial sums per pair, written by the one-XCD tail chain of the previous block (chain_lat.h): [B][32][8]; feat is then not read
     const float* fc_part;
 };
@@ -148,6 +150,13 @@ hipError_t launch_s3pad_to_f32_nhwc(const uint32_t* in, size_t s3_plane, float* 
 // |warp(img2,H) - img1| * 255 -> float [B][224][320]  (and optional u8 clamp copy)
 hipError_t launch_undistort(const uint8_t* raw, int rows, int cols, int stride, const float* map_x, const float* map_y, uint8_t* out,
                             hipStream_t s);
+// hnet_sessions (kernels_sessions.hip): a ring of n_slots 224 x 320 u8 frames (16-byte aligned), one slot per (session, ring side)
+//   scatter: staged [n][NPIX] -> ring slot dst_slot[i];  gather: prev[b] / curr[b] <- ring slots pair_slot[2 b] / [2 b + 1];
+//   remap: raw frame i (packed rows x cols, raw_frame bytes apart) through camera cam[i]'s maps (maps[2 k], maps[2 k + 1]: device x / y) -> ring slot dst_slot[i]
+hipError_t launch_session_scatter(const uint8_t* staged, const int32_t* dst_slot, int n, int n_slots, uint8_t* ring, hipStream_t s);
+hipError_t launch_session_gather(const uint8_t* ring, int n_slots, const int32_t* pair_slot, int n, uint8_t* prev, uint8_t* curr, hipStream_t s);
+hipError_t launch_session_remap(const uint8_t* raw, size_t raw_frame, int rows, int cols, const int32_t* dst_slot, const int32_t* cam, const float* const* maps,
+                                int n_cams, int n, int n_slots, uint8_t* ring, hipStream_t s);
 hipError_t launch_errmap(const void* img1, const void* img2, int pix_fmt, const float* H, float* out,
                          uint8_t* out_u8, int batch, hipStream_t s);
 
@@ -167,7 +176,8 @@ hipError_t launch_block_fc_dlt(const float* feat, const float* wfc, const float*
 //   hidden [B*n_local][512]
 hipError_t launch_heads_fc2(const float* hidden, int batch, int n_local, int s_begin, float p, uint64_t mc_seed,
                             uint64_t pair_seq0, const float* w2, const float* b2, float* mean_s, float* logvar_s,
-                            hipStream_t s, const uint64_t* seq_dev = nullptr, uint32_t* flag = nullptr /* bit 0 is ORed when an output is not finite */);
+                            hipStream_t s, const uint64_t* seq_dev = nullptr, uint32_t* flag = nullptr /* bit 0 is ORed when an output is not finite */,
+                            const uint64_t* seq_tab = nullptr);
 
 // ensemble/transfer from gathered per-sample outputs [B][n][8]
 hipError_t launch_mc_finish(const float* mean_s, const float* logvar_s, int n, const float* H1, int batch,
@@ -179,7 +189,8 @@ hipError_t launch_mc_finish(const float* mean_s, const float* logvar_s, int n, c
 constexpr int HEADS_FC2_FINISH_MAX_N = 64;
 hipError_t launch_heads_fc2_finish(const float* hidden, int batch, int n_local, int s_begin, float p, uint64_t mc_seed, uint64_t pair_seq0, const float* w2,
                                    const float* b2, const float* H1, float* mean, float* cov, float* Htot, hipStream_t s,
-                                   const uint64_t* seq_dev = nullptr, uint32_t* flag = nullptr, int mean_stride = 8, int cov_stride = 64);
+                                   const uint64_t* seq_dev = nullptr, uint32_t* flag = nullptr, int mean_stride = 8, int cov_stride = 64,
+                                   const uint64_t* seq_tab = nullptr);
 
 // layout helpers for the operator-level entry points
 hipError_t launch_nchw_to_nhwc(const float* in, float* out, int batch, int c, int h, int w, hipStream_t s);

@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include "kernels.h"
 #include "heads_mask.h"
+#include "undistort_dev.h"
 #include "geom.h"
 #include "warp_dev.h"
 #include "s3_format.h"
@@ -297,7 +298,7 @@ __global__ __launch_bounds__(256) void prep_warp_tiled_kernel(const PIX* __restr
         if (fc.mask) {      // the surplus workgroups of the grid: keep bits of the heads (FcArgs::mask)
             n_main -= (unsigned)fc.mask_blocks;
             if (blockIdx.x >= n_main) {
-                heads_mask_block(blockIdx.x - n_main, (int)(n_main / (TX * TY)), fc.n_local, fc.s_begin, fc.thr, fc.mc_seed, fc.pair_seq0 + (fc.seq_dev ? *fc.seq_dev : 0ull),
+                heads_mask_block(blockIdx.x - n_main, (int)(n_main / (TX * TY)), fc.n_local, fc.s_begin, fc.thr, fc.mc_seed, fc.pair_seq0, fc.seq_dev, fc.seq_tab,
                                  fc.mask, reinterpret_cast<uint32_t*>(reg));
                 return;
             }
@@ -692,25 +693,16 @@ hipError_t launch_errmap(const void* img1, const void* img2, int pix_fmt, const 
 }
 
 // ---------------------------------------------------------------------------------------------
-// undistort + resize (CamBase::undistort_and_resize_img = cv::remap(INTER_LINEAR, BORDER_CONSTANT 0), CamBase.h:182-186):
-// out(v, u) = bilinear(raw, map_x(v, u), map_y(v, u)).  Sample positions are quantised to 1/32 px as cv::remap does
-// (INTER_BITS = 5, round half to even), the blend is exact integer arithmetic: weights (32-ax)(32-ay) ... sum 1024,
-// result (sum + 512) >> 10.  71 680 output pixels per frame: a latency-bound gather, one pixel per thread.
+// undistort + resize (CamBase::undistort_and_resize_img = cv::remap(INTER_LINEAR, BORDER_CONSTANT 0), CamBase.h:182-186): the per-pixel
+// body is undistort_pixel (undistort_dev.h, shared with the sessions' batched remap).  71 680 output pixels per frame: a latency-bound gather,
+// one pixel per thread.
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void undistort_kernel(const uint8_t* __restrict__ raw, int rows, int cols, int stride,
                                                         const float* __restrict__ map_x, const float* __restrict__ map_y,
                                                         uint8_t* __restrict__ out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= NPIX) return;
-    const float fx = map_x[i] * 32.0f, fy = map_y[i] * 32.0f;
-    // saturate like cv::saturate_cast<short> of the integer part does, and keep NaN / huge positions out of the image
-    const bool sane = fabsf(fx) < 1.0e9f && fabsf(fy) < 1.0e9f;
-    const int sx = sane ? __float2int_rn(fx) : -(1 << 20), sy = sane ? __float2int_rn(fy) : -(1 << 20);
-    const int x0 = sx >> 5, y0 = sy >> 5, ax = sx & 31, ay = sy & 31;
-    auto tap = [&](int y, int x) -> int { return ((unsigned)y < (unsigned)rows && (unsigned)x < (unsigned)cols) ? (int)raw[(size_t)y * stride + x] : 0; };
-    const int v = tap(y0, x0) * (32 - ax) * (32 - ay) + tap(y0, x0 + 1) * ax * (32 - ay) + tap(y0 + 1, x0) * (32 - ax) * ay +
-                  tap(y0 + 1, x0 + 1) * ax * ay;
-    out[i] = (uint8_t)((v + 512) >> 10);
+    out[i] = undistort_pixel(raw, rows, cols, stride, map_x, map_y, i);
 }
 
 hipError_t launch_undistort(const uint8_t* raw, int rows, int cols, int stride, const float* map_x, const float* map_y, uint8_t* out,
@@ -848,7 +840,8 @@ __device__ __forceinline__ void heads_fc2_chunk(const float* __restrict__ hidden
 __global__ __launch_bounds__(256) void heads_fc2_kernel(const float* __restrict__ hidden, int n_local, int s_begin,
                                                         uint32_t thr, float scale, uint64_t mc_seed, uint64_t pair_seq0,
                                                         const uint64_t* __restrict__ seq_dev, const float* __restrict__ w2, const float* __restrict__ b2,
-                                                        float* __restrict__ mean_s, float* __restrict__ logvar_s, uint32_t* __restrict__ flag) {
+                                                        float* __restrict__ mean_s, float* __restrict__ logvar_s, uint32_t* __restrict__ flag,
+                                                        const uint64_t* __restrict__ seq_tab) {
     __shared__ __attribute__((aligned(16))) float w2s[4096];                  // [2][8][256]
     __shared__ __attribute__((aligned(16))) float hid[FC2_CHUNK * 512];       // after dropout
     __shared__ uint32_t pre_row[FC2_CHUNK * 2];
@@ -857,18 +850,18 @@ __global__ __launch_bounds__(256) void heads_fc2_kernel(const float* __restrict_
     const int nc = min(FC2_CHUNK, n_local - c0);
     const int tid = threadIdx.x;
     for (int i = tid; i < 4096; i += 256) w2s[i] = w2[i];
-    const uint64_t key = hnet_pair_key(mc_seed, pair_seq0 + (seq_dev ? *seq_dev : 0ull) + (uint64_t)b);
+    const uint64_t key = hnet_pair_key(mc_seed, pair_seq(seq_tab, pair_seq0, seq_dev, (uint32_t)b));
     heads_fc2_chunk(hidden + (size_t)b * n_local * 512, n_local, s_begin, c0, nc, tid, thr, scale, key, w2s, b2, hid, pre_row,
                     mean_s + (size_t)b * n_local * 8, logvar_s + (size_t)b * n_local * 8, flag);
 }
 
 hipError_t launch_heads_fc2(const float* hidden, int batch, int n_local, int s_begin, float p, uint64_t mc_seed,
                             uint64_t pair_seq0, const float* w2, const float* b2, float* mean_s, float* logvar_s,
-                            hipStream_t s, const uint64_t* seq_dev, uint32_t* flag) {
+                            hipStream_t s, const uint64_t* seq_dev, uint32_t* flag, const uint64_t* seq_tab) {
     if (n_local < 1 || !mean_s || !logvar_s) return hipErrorInvalidValue;
     const int n_chunks = (n_local + FC2_CHUNK - 1) / FC2_CHUNK;
     hipLaunchKernelGGL(heads_fc2_kernel, dim3((unsigned)(batch * n_chunks)), dim3(256), 0, s, hidden, n_local, s_begin,
-                       hnet_drop_threshold(p), 1.0f / (1.0f - p), mc_seed, pair_seq0, seq_dev, w2, b2, mean_s, logvar_s, flag);
+                       hnet_drop_threshold(p), 1.0f / (1.0f - p), mc_seed, pair_seq0, seq_dev, w2, b2, mean_s, logvar_s, flag, seq_tab);
     return hipGetLastError();
 }
 
@@ -963,7 +956,8 @@ __global__ __launch_bounds__(1024) void heads_fc2_finish_kernel(const float* __r
                                                                 uint64_t mc_seed, uint64_t pair_seq0, const uint64_t* __restrict__ seq_dev,
                                                                 const float* __restrict__ w2, const float* __restrict__ b2,
                                                                 const float* __restrict__ H1, float* __restrict__ mean, float* __restrict__ cov,
-                                                                float* __restrict__ Htot, uint32_t* __restrict__ flag, int mean_stride, int cov_stride) {
+                                                                float* __restrict__ Htot, uint32_t* __restrict__ flag, int mean_stride, int cov_stride,
+                                                                const uint64_t* __restrict__ seq_tab) {
     __shared__ __attribute__((aligned(16))) float w2s[4096];
     __shared__ __attribute__((aligned(16))) float hid[4][FC2_CHUNK * 512];
     __shared__ uint32_t pre_row[4][FC2_CHUNK * 2];
@@ -975,7 +969,7 @@ __global__ __launch_bounds__(1024) void heads_fc2_finish_kernel(const float* __r
     // (15.3 -> ... us at batch 1; same values, same arithmetic)
     const float* hidden_b = hidden + (size_t)b * n_local * 512;
     const int n_chunks = (n_local + FC2_CHUNK - 1) / FC2_CHUNK;
-    const uint64_t seqv = seq_dev ? *seq_dev : 0ull;
+    const uint64_t seqv = pair_seq(seq_tab, pair_seq0, seq_dev, (uint32_t)b);
     float w2r[4], hpre[2][FC2_CHUNK * 512 / 256];
 #pragma unroll
     for (int k = 0; k < 4; k++) w2r[k] = w2[tid + 1024 * k];
@@ -991,7 +985,7 @@ __global__ __launch_bounds__(1024) void heads_fc2_finish_kernel(const float* __r
     if (tid < 9) h1_l[tid] = H1[b * 9 + tid];
 #pragma unroll
     for (int k = 0; k < 4; k++) w2s[tid + 1024 * k] = w2r[k];
-    const uint64_t key = hnet_pair_key(mc_seed, pair_seq0 + seqv + (uint64_t)b);
+    const uint64_t key = hnet_pair_key(mc_seed, seqv);
     // (the first barrier inside heads_fc2_chunk also covers the w2s / h1_l fill)
     heads_fc2_chunk(hidden_b, n_local, s_begin, grp * FC2_CHUNK, min(FC2_CHUNK, n_local - grp * FC2_CHUNK), t, thr, scale, key, w2s, b2, hid[grp],
                     pre_row[grp], ms_l, lv_l, nullptr, hpre[0]);
@@ -1008,10 +1002,10 @@ __global__ __launch_bounds__(1024) void heads_fc2_finish_kernel(const float* __r
 }
 hipError_t launch_heads_fc2_finish(const float* hidden, int batch, int n_local, int s_begin, float p, uint64_t mc_seed, uint64_t pair_seq0, const float* w2,
                                    const float* b2, const float* H1, float* mean, float* cov, float* Htot, hipStream_t s, const uint64_t* seq_dev,
-                                   uint32_t* flag, int mean_stride, int cov_stride) {
+                                   uint32_t* flag, int mean_stride, int cov_stride, const uint64_t* seq_tab) {
     if (n_local < 1 || n_local > FC2M_MAX_N) return hipErrorInvalidValue;
     hipLaunchKernelGGL(heads_fc2_finish_kernel, dim3((unsigned)batch), dim3(1024), 0, s, hidden, n_local, s_begin, hnet_drop_threshold(p), 1.0f / (1.0f - p),
-                       mc_seed, pair_seq0, seq_dev, w2, b2, H1, mean, cov, Htot, flag, mean_stride, cov_stride);
+                       mc_seed, pair_seq0, seq_dev, w2, b2, H1, mean, cov, Htot, flag, mean_stride, cov_stride, seq_tab);
     return hipGetLastError();
 }
 

@@ -175,6 +175,11 @@ class HnetEngine:
         """the same forward with the packed [batch, 72] record (mean | cov) as output: the message of the multi-GPU gather, written by the ensemble kernel"""
         check(self._h, self._L.hnet_infer_batch_packed_device(self._h, d_prev, d_curr, fmt, d_prior, batch, pair_seq0, d_out72, d_err, self._stream(stream)))
 
+    def infer_batch_seqs_packed_device(self, d_prev, d_curr, fmt, d_prior, batch, d_pair_seq, d_out72, d_err=None, stream=None):
+        """infer_batch_packed_device with one mask sequence number per pair: d_pair_seq = device uint64 [batch] (pair b's key; [s0, s0 + 1, ...] = pair_seq0 s0)"""
+        check(self._h, self._L.hnet_infer_batch_seqs_packed_device(self._h, d_prev, d_curr, fmt, d_prior, batch, d_pair_seq, d_out72, d_err,
+                                                                   self._stream(stream)))
+
     def mc_finish_packed_device(self, d_mean_s, d_logvar_s, n_total, d_h1, batch, d_out72, stream=None):
         check(self._h, self._L.hnet_mc_finish_packed_device(self._h, d_mean_s, d_logvar_s, n_total, d_h1, batch, d_out72, self._stream(stream)))
 
@@ -399,6 +404,120 @@ class HnetGroup:
                 m.close()
             self._L.hnet_destroy_group(self._g)
             self._g = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class HnetSessions:
+    """hnet_sessions (include/hnet.h): n_sessions camera streams on ONE context - per session its own frame ring, image count, time stamp, mask sequence
+    number and undistort camera; infer() runs the current pairs of any subset as one batched forward.  Session i's result is that of a dedicated context
+    driven by push_image / push_raw_image + infer.  Holds a reference to `engine`, so the context outlives the sessions."""
+
+    def __init__(self, engine, n_sessions):
+        self.engine, self._L, self.n = engine, engine._L, int(n_sessions)
+        self._s = C.c_void_p()
+        check(engine.handle, self._L.hnet_create_sessions(engine.handle, self.n, C.byref(self._s)))
+        self.emit_error_map = bool(engine.config().emit_error_map)
+
+    def _check(self, rc):
+        check(self.engine.handle, rc)
+
+    @staticmethod
+    def _ids(ids):
+        ids = np.ascontiguousarray(np.atleast_1d(ids), dtype=np.int32)
+        return ids, len(ids)
+
+    @staticmethod
+    def _times(t, n):
+        if t is None:
+            return None
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(t, dtype=np.float64), (n,)))
+
+    def push(self, ids, frames, t=None):
+        """frames [n, 224, 320] uint8 (any row / frame stride with unit pixel stride) -> sessions ids; t: n time stamps or None"""
+        ids, n = self._ids(ids)
+        f = np.asarray(frames)
+        if f.ndim == 2:
+            f = f[None]
+        if f.dtype != np.uint8 or f.shape[1:] != (IMG_H, IMG_W) or f.shape[0] != n:
+            raise ValueError("expected frames of shape [n, 224, 320] uint8")
+        if f.strides[2] != 1:
+            f = np.ascontiguousarray(f)
+        tt = self._times(t, n)
+        self._check(self._L.hnet_sessions_push(self._s, n, ids.ctypes.data, f.ctypes.data, f.strides[1], f.strides[0],
+                                               tt.ctypes.data if tt is not None else None))
+
+    def add_camera(self, k, d, raw_rows, raw_cols, fisheye=True):
+        """one more undistort camera (maps as HnetEngine.set_camera builds them); returns its index"""
+        cam = _capi.Camera(int(bool(fisheye)), int(raw_rows), int(raw_cols), (C.c_double * 4)(*[float(x) for x in k]),
+                           (C.c_double * 4)(*[float(x) for x in d]))
+        out = C.c_int(-1)
+        self._check(self._L.hnet_sessions_add_camera(self._s, C.byref(cam), C.byref(out)))
+        return int(out.value)
+
+    def bind_camera(self, id, cam):
+        self._check(self._L.hnet_sessions_bind_camera(self._s, int(id), int(cam)))
+
+    def push_raw(self, ids, raw, t=None):
+        """raw [n, rows, cols] uint8: remapped with each session's camera into its ring"""
+        ids, n = self._ids(ids)
+        r = np.asarray(raw)
+        if r.ndim == 2:
+            r = r[None]
+        if r.dtype != np.uint8 or r.ndim != 3 or r.shape[0] != n:
+            raise ValueError("expected raw frames of shape [n, rows, cols] uint8")
+        if r.strides[2] != 1:
+            r = np.ascontiguousarray(r)
+        tt = self._times(t, n)
+        self._check(self._L.hnet_sessions_push_raw(self._s, n, ids.ctypes.data, r.ctypes.data, r.shape[1], r.shape[2], r.strides[1], r.strides[0],
+                                                   tt.ctypes.data if tt is not None else None))
+
+    def infer(self, ids, prior=None, want_err=False):
+        """-> (mean [n, 8], cov [n, 8, 8][, err [n, 224, 320] uint8]); prior [n, 8] pixels (float64 as the C ABI takes it)"""
+        ids, n = self._ids(ids)
+        mean = np.zeros((n, 8), np.float32)
+        cov = np.zeros((n, 8, 8), np.float32)
+        err = np.zeros((n, IMG_H, IMG_W), np.uint8) if want_err else None
+        pr = None if prior is None else np.ascontiguousarray(prior, dtype=np.float64).reshape(n, 8)
+        self._check(self._L.hnet_sessions_infer(self._s, n, ids.ctypes.data, pr.ctypes.data if pr is not None else None, mean.ctypes.data,
+                                                cov.ctypes.data, err.ctypes.data if want_err else None))
+        return (mean, cov, err) if want_err else (mean, cov)
+
+    def image_count(self, id):
+        return int(self._L.hnet_sessions_image_count(self._s, int(id)))
+
+    def latest_time(self, id):
+        return float(self._L.hnet_sessions_latest_time(self._s, int(id)))
+
+    def set_seq(self, id, seq):
+        self._check(self._L.hnet_sessions_set_seq(self._s, int(id), int(seq)))
+
+    def seq(self, id):
+        return int(self._L.hnet_sessions_seq(self._s, int(id)))
+
+    def reset(self, id):
+        self._check(self._L.hnet_sessions_reset(self._s, int(id)))
+
+    def frame(self, id, which):
+        """the session's previous (0) or current (1) 224 x 320 frame as the ring holds it"""
+        out = np.zeros((IMG_H, IMG_W), np.uint8)
+        self._check(self._L.hnet_sessions_get_frame(self._s, int(id), int(which), out.ctypes.data))
+        return out
+
+    def last_timing(self):
+        t = Timing()
+        self._check(self._L.hnet_sessions_last_timing(self._s, C.byref(t)))
+        return {"device_ms": t.device_ms, "host_ms": t.host_ms, "n_inferences": t.n_inferences,
+                "sum_device_ms_after_100": t.sum_device_ms_after_100, "n_main_inferences": t.n_main_inferences}
+
+    def close(self):
+        if getattr(self, "_s", None):
+            self._L.hnet_destroy_sessions(self._s)
+            self._s = None
 
     def __del__(self):
         try:

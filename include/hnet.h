@@ -274,6 +274,46 @@ int hnet_group_join(hnet_group* group, void* stream);
 int hnet_group_synchronize(hnet_group* group);
 int hnet_group_overflow_flag(hnet_group* group, int* flags);   /* hnet_overflow_flag of every member, ORed; synchronises the members */
 
+/* ---- sessions: many camera streams on ONE context ----------------------------------------------------------------------------------
+ * The reference runs one HomographyNet object per camera: one frame ring (load_current_img, HomographyNet.cpp:127-151), one mask sequence count (the
+ * forward's call count, :153-252) and one undistort camera (CamBase.h:165-186) each.  A sessions object keeps that state for n_sessions cameras on one context
+ * and runs the pairs of any subset of them as ONE batched forward: session i's result is what a dedicated context with the same blob and config gives when
+ * driven by hnet_push_image / hnet_push_raw_image + hnet_infer (pair b's mask key = its session's own count: hnet_infer_batch_seqs_packed_device).
+ * Device ring: n_sessions x 2 frames.  `ctx` must outlive the sessions; errors go to hnet_last_error(ctx); a failed call changes no state.
+ * Session calls never touch the context's own image ring, counters or timing (hnet_infer on the same context keeps its sequence).
+ * ids: n distinct session indices.  HNET_ERR_INVALID_ARG: an id out of range or repeated, an unbound camera, a raw size other than the bound camera's, an error
+ * map without emit_error_map; HNET_ERR_NOT_READY: a listed session holds fewer than two images; HNET_ERR_CAPACITY: n > max_batch; HNET_ERR_UNSUPPORTED
+ * (hnet_create_sessions): a context that evaluates a sample shard (mc_sample_begin / end != 0, 0).  Not thread-safe (one caller thread, like a context). */
+typedef struct hnet_sessions hnet_sessions;
+int  hnet_create_sessions(hnet_ctx* ctx, int n_sessions, hnet_sessions** out);
+void hnet_destroy_sessions(hnet_sessions* s);
+/* load_current_img (HomographyNet.cpp:127-151) for n sessions at once: frame i = 224 x 320 u8 at frames + i frame_stride (row_stride bytes per row) goes to
+ * session ids[i]; prev <- curr, counts, t[i] recorded from the second image on (t NULL: times not recorded).  The frames are copied into pinned staging
+ * (double-buffered, not retained), uploaded with one copy and scattered into the ring by one launch; no synchronisation. */
+int  hnet_sessions_push(hnet_sessions* s, int n, const int32_t* ids, const uint8_t* frames, int row_stride, size_t frame_stride, const double* t);
+/* initialize_undist_map[_fisheye] (CamBase.h:165-180) for one more camera; maps built exactly as hnet_set_camera builds them.  *cam_id receives its index */
+int  hnet_sessions_add_camera(hnet_sessions* s, const hnet_camera* cam, int* cam_id);
+int  hnet_sessions_bind_camera(hnet_sessions* s, int id, int cam_id);
+/* undistort_and_resize_img (CamBase.h:182-186) + load_current_img for n sessions: raw frame i (rows x cols u8, row_stride bytes per row) at raw + i frame_stride
+ * remapped with session ids[i]'s camera straight into its ring slot (the bits of hnet_push_raw_image); one upload, one launch, no synchronisation */
+int  hnet_sessions_push_raw(hnet_sessions* s, int n, const int32_t* ids, const uint8_t* raw, int rows, int cols, int row_stride, size_t frame_stride,
+                            const double* t);
+/* network_inference (HomographyNet.cpp:153-252) on the current pair of each listed session, as one batched forward: prior_px [n][8] doubles (pixels; required
+ * with use_prior), mean [n][8], cov [n][64], err_map [n][224][320] u8 or NULL.  Each listed session's sequence number advances by one (an IEKF re-run is
+ * another call with the new priors).  One synchronisation; the F16X2 overflow repeat of hnet_infer_batch applies (same keys, counts advance once). */
+int  hnet_sessions_infer(hnet_sessions* s, int n, const int32_t* ids, const double* prior_px, float* mean, float* cov, uint8_t* err_map);
+int  hnet_sessions_image_count(const hnet_sessions* s, int id);           /* img_counter (HomographyNet.h:33) of session id; -1 for a bad id */
+double hnet_sessions_latest_time(const hnet_sessions* s, int id);         /* get_latest_inference_time() (HomographyNet.h:31); -1 before the second image */
+int  hnet_sessions_set_seq(hnet_sessions* s, int id, uint64_t seq);       /* next mask sequence number of session id (default 0) */
+uint64_t hnet_sessions_seq(const hnet_sessions* s, int id);
+int  hnet_sessions_reset(hnet_sessions* s, int id);                       /* camera restarted: image count 0, time -1, sequence number kept */
+int  hnet_sessions_get_frame(hnet_sessions* s, int id, int which /* 0 prev, 1 curr */, uint8_t* out);   /* operator level (tests): 224 x 320 bytes */
+int  hnet_sessions_last_timing(const hnet_sessions* s, hnet_timing* out); /* the sessions' own: last infer's device / host ms, infer calls so far */
+/* hnet_infer_batch_packed_device with one mask sequence number per pair: d_pair_seq [batch] uint64 in device memory (pair b's key = d_pair_seq[b] instead of
+ * pair_seq0 + b).  The table [s0, s0 + 1, ...] gives the bits of pair_seq0 = s0. */
+int  hnet_infer_batch_seqs_packed_device(hnet_ctx* ctx, const void* d_prev, const void* d_curr, int pix_fmt, const float* d_prior, int batch,
+                                         const uint64_t* d_pair_seq, float* d_out72, float* d_err_map, void* stream);
+
 int hnet_synchronize(hnet_ctx* ctx, void* stream);
 int hnet_last_timing(const hnet_ctx* ctx, hnet_timing* out);
 
