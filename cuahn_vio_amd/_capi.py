@@ -7,6 +7,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import numpy as _np
+
 _PKG = os.path.dirname(os.path.abspath(__file__))
 # HNET_LIB_PATH: another build of the SAME library (same-box A/B of two source states with tools/ab_bench.py); never a fallback
 LIB_PATH = os.environ.get("HNET_LIB_PATH") or os.path.join(_PKG, "libhnet_hip.so")
@@ -32,6 +34,8 @@ SYMBOLS = [
     "hnet_create_sessions", "hnet_destroy_sessions", "hnet_sessions_push", "hnet_sessions_add_camera", "hnet_sessions_bind_camera",
     "hnet_sessions_push_raw", "hnet_sessions_infer", "hnet_sessions_image_count", "hnet_sessions_latest_time", "hnet_sessions_set_seq",
     "hnet_sessions_seq", "hnet_sessions_reset", "hnet_sessions_get_frame", "hnet_sessions_last_timing", "hnet_infer_batch_seqs_packed_device",
+    "hnet_filter_default_params", "hnet_create_filters", "hnet_destroy_filters", "hnet_filters_set_params", "hnet_filters_set_state",
+    "hnet_filters_get_state", "hnet_filters_step", "hnet_filters_last_priors", "hnet_filters_last_timing",
 ]
 
 
@@ -51,6 +55,20 @@ class Camera(C.Structure):
 class Timing(C.Structure):
     _fields_ = [("device_ms", C.c_double), ("host_ms", C.c_double), ("n_inferences", C.c_int64),
                 ("sum_device_ms_after_100", C.c_double), ("n_main_inferences", C.c_int64)]
+
+
+class FilterParams(C.Structure):
+    """hnet_filter_params: extrinsics, noise densities, gravity, network covariance scale, camera-IMU time offset, IMU averaging"""
+    _fields_ = [("c_R_i", C.c_double * 9), ("i_t_i2c", C.c_double * 3), ("sigma_w", C.c_double), ("sigma_a", C.c_double),
+                ("sigma_wb", C.c_double), ("sigma_ab", C.c_double), ("gravity_mag", C.c_double), ("k_net_cov", C.c_double),
+                ("cam_imu_dt", C.c_double), ("imu_avg", C.c_int32)]
+
+
+# hnet_filter_state / hnet_imu as numpy records (the C structs are packed doubles)
+
+FILTER_STATE_DTYPE = _np.dtype([("t", "<f8"), ("p", "<f8", 3), ("q", "<f8", 4), ("v", "<f8", 3), ("ba", "<f8", 3), ("bg", "<f8", 3),
+                                ("offset", "<f8", (4, 3)), ("cov", "<f8", (27, 27))])
+IMU_DTYPE = _np.dtype([("t", "<f8"), ("wm", "<f8", 3), ("am", "<f8", 3)])
 
 
 class HnetError(RuntimeError):
@@ -157,6 +175,17 @@ def lib():
     L.hnet_sessions_get_frame.argtypes = [vp, C.c_int, C.c_int, vp]
     L.hnet_sessions_last_timing.argtypes = [vp, C.POINTER(Timing)]
     L.hnet_infer_batch_seqs_packed_device.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp]
+    L.hnet_filter_default_params.argtypes = [C.POINTER(FilterParams)]
+    L.hnet_filter_default_params.restype = None
+    L.hnet_create_filters.argtypes = [vp, C.c_int, C.POINTER(vp)]
+    L.hnet_destroy_filters.argtypes = [vp]
+    L.hnet_destroy_filters.restype = None
+    L.hnet_filters_set_params.argtypes = [vp, C.c_int, C.POINTER(FilterParams)]
+    L.hnet_filters_set_state.argtypes = [vp, C.c_int, vp]
+    L.hnet_filters_get_state.argtypes = [vp, C.c_int, vp, vp]
+    L.hnet_filters_step.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]
+    L.hnet_filters_last_priors.argtypes = [vp, C.c_int, vp]
+    L.hnet_filters_last_timing.argtypes = [vp, C.POINTER(Timing)]
     for name in SYMBOLS:
         getattr(L, name)   # AttributeError here = the library does not export what include/hnet.h declares
     _lib = L

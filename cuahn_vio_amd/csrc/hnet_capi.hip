@@ -7,6 +7,7 @@
 #include "../../include/hnet_rng.h"
 #include "geom.h"
 #include "kernels.h"
+#include "filters_dev.h"
 #include "chain_args.h"
 #include "s3_format.h"
 
@@ -2389,6 +2390,310 @@ int hnet_sessions_get_frame(hnet_sessions* s, int id, int which, uint8_t* out) {
 int hnet_sessions_last_timing(const hnet_sessions* s, hnet_timing* out) {
     if (!s || !out) return HNET_ERR_INVALID_ARG;
     *out = s->timing;
+    return HNET_OK;
+}
+
+// ---- filters: one 27-state filter per session of a sessions object (include/hnet.h).  Device: the states [n_sessions], the parameters [n_sessions] and
+// the step's buffers sized for max_batch; host: each state's time (the t_frame check) and camera-IMU offset (the selection window).  A step works on a
+// copy of the listed states (work) and scatters it back only once its forwards are accepted: an overflow / timeout repeat starts from the untouched states.
+struct hnet_filters {
+    hnet_sessions* s = nullptr;
+    int iters = 1;
+    FilterRec* d_state = nullptr;              // [n_sessions]
+    FilterParams* d_params = nullptr;          // [n_sessions]
+    std::vector<double> t, cam_imu_dt;         // host mirror of state t / the offset of each session
+    std::vector<int> imu_avg;
+    // step outputs, ONE device block {net [iters][B][72] f32 | prior_px [iters][B][8] f32 | updates [B] i32 | work [B] FilterRec} and its pinned copy
+    uint8_t* d_out = nullptr;
+    uint8_t* pin_out = nullptr;
+    size_t off_prior = 0, off_upd = 0, off_work = 0, out_bytes = 0;
+    double* d_prior_cam = nullptr;             // [B][8]
+    // step inputs, ONE pinned block and its device copy (grown on demand): {readings [R] | t_frame [n] | seq [iters][n] | ids [n] | gate [n] | pairs [n][2] | rd_off [n + 1]}
+    uint8_t* pin_in = nullptr;
+    uint8_t* d_in = nullptr;
+    size_t in_cap = 0;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hnet_timing timing = {};
+    int last_n = 0;                            // sessions of the last accepted step (hnet_filters_last_priors)
+};
+
+static size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+void hnet_filter_default_params(hnet_filter_params* p) {
+    if (!p) return;
+    memset(p, 0, sizeof *p);
+    static const double T[12] = {-0.027256691772188965, -0.9996260641688061, 0.0021919370477445077, 0.02422852666805565,
+                                 -0.7139206120417471, 0.017931469899155242, -0.6999970157716363, 0.008974432843748055,
+                                 0.6996959571525168, -0.020644471939022302, -0.714142404092339, -0.000638971731537894};
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) p->c_R_i[i * 3 + j] = T[i * 4 + j];
+    for (int i = 0; i < 3; i++) p->i_t_i2c[i] = -(p->c_R_i[i] * T[3] + p->c_R_i[3 + i] * T[7] + p->c_R_i[6 + i] * T[11]);
+    p->sigma_w = 0.00559017;
+    p->sigma_wb = 8.94427e-04;
+    p->sigma_a = 0.01118034;
+    p->sigma_ab = 0.04472136;
+    p->gravity_mag = 9.81;
+    p->k_net_cov = 10.0;
+    p->cam_imu_dt = 0.0;
+    p->imu_avg = 1;
+}
+
+static FilterParams filter_params_dev(const hnet_filter_params& p) {
+    FilterParams d;
+    memset(&d, 0, sizeof d);
+    memcpy(d.ext.c_R_i, p.c_R_i, sizeof d.ext.c_R_i);
+    memcpy(d.ext.i_t_i2c, p.i_t_i2c, sizeof d.ext.i_t_i2c);
+    hnet_ekf::noise_q_diag(p.sigma_w, p.sigma_a, p.sigma_wb, p.sigma_ab, d.q);
+    d.gravity_mag = p.gravity_mag;
+    d.k_net_cov = p.k_net_cov;
+    d.imu_avg = p.imu_avg ? 1 : 0;
+    return d;
+}
+
+void hnet_destroy_filters(hnet_filters* f) {
+    if (!f) return;
+    hnet_ctx* c = f->s->ctx;
+    (void)hipSetDevice(c->cfg.device_id);
+    (void)hipStreamSynchronize(c->stream);
+    auto fr = [](void* p) { if (p) (void)hipFree(p); };
+    fr(f->d_state); fr(f->d_params); fr(f->d_out); fr(f->d_prior_cam); fr(f->d_in);
+    if (f->pin_out) (void)hipHostFree(f->pin_out);
+    if (f->pin_in) (void)hipHostFree(f->pin_in);
+    if (f->ev0) (void)hipEventDestroy(f->ev0);
+    if (f->ev1) (void)hipEventDestroy(f->ev1);
+    delete f;
+}
+
+int hnet_create_filters(hnet_sessions* s, int max_iekf_iteration, hnet_filters** out) {
+    if (!s || !out) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = s->ctx;
+    if (max_iekf_iteration < 1 || max_iekf_iteration > 64) return fail(c, HNET_ERR_INVALID_ARG, "hnet_create_filters: max_iekf_iteration outside 1 .. 64");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    hnet_filters* f = new hnet_filters();
+    f->s = s;
+    f->iters = max_iekf_iteration;
+    const int N = s->n, B = c->cfg.max_batch;
+    hnet_filter_params dp;
+    hnet_filter_default_params(&dp);
+    f->t.assign(N, 0.0);
+    f->cam_imu_dt.assign(N, dp.cam_imu_dt);
+    f->imu_avg.assign(N, dp.imu_avg);
+    f->off_prior = al256((size_t)f->iters * B * 72 * sizeof(float));
+    f->off_upd = f->off_prior + al256((size_t)f->iters * B * 8 * sizeof(float));
+    f->off_work = f->off_upd + al256((size_t)B * sizeof(int32_t));
+    f->out_bytes = f->off_work + (size_t)B * sizeof(FilterRec);
+    std::vector<FilterRec> st(N);
+    memset(st.data(), 0, st.size() * sizeof(FilterRec));
+    for (auto& r : st) r.s.q[0] = 1.0;
+    std::vector<FilterParams> pr(N, filter_params_dev(dp));
+    hipError_t e = hipMalloc((void**)&f->d_state, (size_t)N * sizeof(FilterRec));
+    if (e == hipSuccess) e = hipMalloc((void**)&f->d_params, (size_t)N * sizeof(FilterParams));
+    if (e == hipSuccess) e = hipMalloc((void**)&f->d_out, f->out_bytes);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&f->pin_out, f->out_bytes, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipMalloc((void**)&f->d_prior_cam, (size_t)B * 8 * sizeof(double));
+    if (e == hipSuccess) e = hipEventCreate(&f->ev0);
+    if (e == hipSuccess) e = hipEventCreate(&f->ev1);
+    if (e == hipSuccess) e = hipMemcpyAsync(f->d_state, st.data(), (size_t)N * sizeof(FilterRec), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(f->d_params, pr.data(), (size_t)N * sizeof(FilterParams), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        hnet_destroy_filters(f);
+        return fail(c, HNET_ERR_DEVICE, std::string("hnet_create_filters: ") + hipGetErrorString(e));
+    }
+    *out = f;
+    return HNET_OK;
+}
+
+int hnet_filters_set_params(hnet_filters* f, int id, const hnet_filter_params* p) {
+    if (!f) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = f->s->ctx;
+    if (!p || id < 0 || id >= f->s->n) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_set_params: id or params");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    const FilterParams d = filter_params_dev(*p);
+    HIPCHK(c, hipMemcpyAsync(f->d_params + id, &d, sizeof d, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    f->cam_imu_dt[id] = p->cam_imu_dt;
+    f->imu_avg[id] = p->imu_avg ? 1 : 0;
+    return HNET_OK;
+}
+
+static_assert(sizeof(hnet_filter_state) == sizeof(FilterRec), "hnet_filter_state is the FilterRec layout");
+
+int hnet_filters_set_state(hnet_filters* f, int id, const hnet_filter_state* st) {
+    if (!f) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = f->s->ctx;
+    if (!st || id < 0 || id >= f->s->n) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_set_state: id or state");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    HIPCHK(c, hipMemcpyAsync(f->d_state + id, st, sizeof(FilterRec), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    f->t[id] = st->t;
+    return HNET_OK;
+}
+
+int hnet_filters_get_state(hnet_filters* f, int n, const int32_t* ids, hnet_filter_state* out) {
+    if (!f) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = f->s->ctx;
+    if (!ids || !out || n < 1) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_get_state: ids / out");
+    for (int i = 0; i < n; i++)
+        if (ids[i] < 0 || ids[i] >= f->s->n) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_get_state: id out of range");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    for (int i = 0; i < n; i++) HIPCHK(c, hipMemcpyAsync(out + i, f->d_state + ids[i], sizeof(FilterRec), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return HNET_OK;
+}
+
+int hnet_filters_step(hnet_filters* f, int n, const int32_t* ids, const double* t_frame, const hnet_imu* imu, const int64_t* imu_off,
+                      hnet_filter_state* state_out, float* net_out, int32_t* updates) {
+    if (!f) return HNET_ERR_INVALID_ARG;
+    hnet_sessions* s = f->s;
+    hnet_ctx* c = s->ctx;
+    if (!t_frame || !imu_off) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_step: t_frame / imu_off");
+    int rc = sessions_check_ids(s, n, ids);
+    if (rc != HNET_OK) return rc;
+    for (int i = 0; i < n; i++)
+        if (s->st[ids[i]].count < 2) return fail(c, HNET_ERR_NOT_READY, "HNet cannot inference! Only has one image!");
+    for (int i = 0; i < n; i++) {
+        if (!(t_frame[i] > f->t[ids[i]]) || !std::isfinite(t_frame[i]))
+            return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_step: t_frame must be later than the state's time (Propagator.cpp:32-43)");
+        if (imu_off[i] < 0 || imu_off[i + 1] < imu_off[i] || (imu_off[i + 1] > imu_off[i] && !imu))
+            return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_step: imu / imu_off");
+    }
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    auto t0 = std::chrono::steady_clock::now();
+    const int I = f->iters;
+    // selection on the host (hnet_ekf::select_imu_readings: the window [state t, t_frame] + the session's offset) into the input block
+    static_assert(sizeof(hnet_imu) == sizeof(hnet_ekf::ImuData), "hnet_imu is hnet_ekf::ImuData");
+    int64_t total = 0;
+    for (int i = 0; i < n; i++) total += imu_off[i + 1] - imu_off[i] + 2;
+    const size_t o_t = al256((size_t)total * sizeof(hnet_ekf::ImuData)), o_seq = o_t + al256((size_t)n * 8), o_ids = o_seq + al256((size_t)I * n * 8);
+    const size_t o_gate = o_ids + al256((size_t)n * 4), o_pairs = o_gate + al256((size_t)n * 4), o_off = o_pairs + al256((size_t)n * 8);
+    const size_t in_bytes = o_off + al256((size_t)(n + 1) * 4);
+    if (f->in_cap < in_bytes) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (f->pin_in) HIPCHK(c, hipHostFree(f->pin_in));
+        if (f->d_in) HIPCHK(c, hipFree(f->d_in));
+        f->pin_in = f->d_in = nullptr;
+        f->in_cap = 0;
+        HIPCHK(c, hipHostMalloc((void**)&f->pin_in, in_bytes, hipHostMallocDefault));
+        HIPCHK(c, hipMalloc((void**)&f->d_in, in_bytes));
+        f->in_cap = in_bytes;
+    }
+    hnet_ekf::ImuData* rd = reinterpret_cast<hnet_ekf::ImuData*>(f->pin_in);
+    double* tf = reinterpret_cast<double*>(f->pin_in + o_t);
+    uint64_t* seq = reinterpret_cast<uint64_t*>(f->pin_in + o_seq);
+    int32_t* hid = reinterpret_cast<int32_t*>(f->pin_in + o_ids);
+    int32_t* gate = reinterpret_cast<int32_t*>(f->pin_in + o_gate);
+    int32_t* pairs = reinterpret_cast<int32_t*>(f->pin_in + o_pairs);
+    int32_t* roff = reinterpret_cast<int32_t*>(f->pin_in + o_off);
+    int R = 0;
+    for (int i = 0; i < n; i++) {
+        const int id = ids[i];
+        const hnet_sessions::Sess& e = s->st[id];
+        const int64_t m = imu_off[i + 1] - imu_off[i];
+        const double dt = f->cam_imu_dt[id];
+        roff[i] = R;
+        R += hnet_ekf::select_imu_readings(reinterpret_cast<const hnet_ekf::ImuData*>(imu) + imu_off[i], (int)m, f->t[id] + dt, t_frame[i] + dt, rd + R);
+        tf[i] = t_frame[i];
+        for (int it = 0; it < I; it++) seq[(size_t)it * n + i] = e.seq + (uint64_t)it;
+        hid[i] = id;
+        gate[i] = (e.t == t_frame[i] && e.count > 10) ? 1 : 0;                      // VioManager.cpp:257
+        pairs[2 * i] = 2 * id + (e.curr ^ 1);
+        pairs[2 * i + 1] = 2 * id + e.curr;
+    }
+    roff[n] = R;
+    const hnet_ekf::ImuData* d_rd = reinterpret_cast<const hnet_ekf::ImuData*>(f->d_in);
+    const double* d_tf = reinterpret_cast<const double*>(f->d_in + o_t);
+    const uint64_t* d_seq = reinterpret_cast<const uint64_t*>(f->d_in + o_seq);
+    const int32_t* d_ids = reinterpret_cast<const int32_t*>(f->d_in + o_ids);
+    const int32_t* d_gate = reinterpret_cast<const int32_t*>(f->d_in + o_gate);
+    const int32_t* d_pairs = reinterpret_cast<const int32_t*>(f->d_in + o_pairs);
+    const int32_t* d_roff = reinterpret_cast<const int32_t*>(f->d_in + o_off);
+    float* d_net = reinterpret_cast<float*>(f->d_out);
+    float* d_prior = reinterpret_cast<float*>(f->d_out + f->off_prior);
+    int32_t* d_upd = reinterpret_cast<int32_t*>(f->d_out + f->off_upd);
+    FilterRec* d_work = reinterpret_cast<FilterRec*>(f->d_out + f->off_work);
+    const float* h_net = reinterpret_cast<const float*>(f->pin_out);
+    const float* h_prior = reinterpret_cast<const float*>(f->pin_out + f->off_prior);
+    // the output block is laid out for max_batch: download the used parts of each section in one copy up to the last one needed
+    const size_t down = state_out ? f->off_work + (size_t)n * sizeof(FilterRec) : f->off_upd + (size_t)n * sizeof(int32_t);
+    hipStream_t st = c->stream;
+    const size_t up = o_off + (size_t)(n + 1) * 4;
+    uint32_t flag_now = 0;
+    auto enqueue = [&]() -> int {
+        HIPCHK(c, hipMemcpyAsync(f->d_in, f->pin_in, up, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemsetAsync(d_upd, 0, (size_t)n * sizeof(int32_t), st));
+        HIPCHK(c, hipEventRecord(f->ev0, st));
+        HIPCHK(c, launch_session_gather(s->ring, 2 * s->n, d_pairs, n, (uint8_t*)c->stage_prev, (uint8_t*)c->stage_curr, st));
+        HIPCHK(c, launch_filter_propagate(d_ids, n, s->n, f->d_state, f->d_params, d_rd, d_roff, d_tf, d_work, st));
+        for (int it = 0; it < I; it++) {
+            float* pr_it = d_prior + (size_t)it * c->cfg.max_batch * 8;
+            float* net_it = d_net + (size_t)it * c->cfg.max_batch * 72;
+            HIPCHK(c, launch_filter_prior(d_work, n, pr_it, f->d_prior_cam, st));
+            FwdArgs a = {c->stage_prev, c->stage_curr, HNET_PIX_U8, c->cfg.use_prior ? pr_it : nullptr, n, 0, net_it, net_it + 8, nullptr, nullptr,
+                         nullptr, nullptr, nullptr, false};
+            a.mean_stride = a.cov_stride = HNET_PACKED_FLOATS;
+            a.seq_tab = d_seq + (size_t)it * n;
+            const int r = forward(c, a, st);
+            if (r != HNET_OK) return r;
+            HIPCHK(c, launch_filter_update(d_ids, n, s->n, f->d_params, net_it, f->d_prior_cam, d_gate, it != I - 1, it == I - 1, d_work, d_upd, st));
+        }
+        HIPCHK(c, hipEventRecord(f->ev1, st));
+        HIPCHK(c, hipMemcpyAsync(f->pin_out, f->d_out, down, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(&flag_now, c->d_flag, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemsetAsync(c->d_flag, 0, 4, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        return HNET_OK;
+    };
+    // an overflow of the fp16 planes: the first forward with a non-finite output had finite inputs (its fp32 priors; later priors follow from it)
+    auto overflowed = [&]() -> bool {
+        if (c->n_planes != 2) return false;
+        for (int it = 0; it < I; it++)
+            if (!all_finite(h_net + (size_t)it * c->cfg.max_batch * 72, (size_t)n * 72))
+                return !c->cfg.use_prior || all_finite(h_prior + (size_t)it * c->cfg.max_batch * 8, (size_t)n * 8);
+        return false;
+    };
+    rc = enqueue();
+    if (rc != HNET_OK) { (void)hipStreamSynchronize(st); return rc; }
+    if (flag_now & CH_FLAG_TIMEOUT) {
+        if ((rc = chain_gave_up(c)) != HNET_OK || (rc = enqueue()) != HNET_OK) { (void)hipStreamSynchronize(st); return rc; }
+    }
+    if (overflowed()) {
+        if ((rc = demote_to_bf16x3(c)) != HNET_OK || (rc = enqueue()) != HNET_OK) { (void)hipStreamSynchronize(st); return rc; }
+    }
+    // accepted: the listed states take the step's result (stream order: later calls see it), the bookkeeping advances
+    HIPCHK(c, launch_filter_scatter(d_work, d_ids, n, s->n, f->d_state, st));
+    for (int i = 0; i < n; i++) {
+        f->t[ids[i]] = t_frame[i];
+        s->st[ids[i]].seq += (uint64_t)I;
+    }
+    if (net_out)
+        for (int it = 0; it < I; it++) memcpy(net_out + (size_t)it * n * 72, h_net + (size_t)it * c->cfg.max_batch * 72, (size_t)n * 72 * sizeof(float));
+    if (updates) memcpy(updates, f->pin_out + f->off_upd, (size_t)n * sizeof(int32_t));
+    if (state_out) memcpy(state_out, f->pin_out + f->off_work, (size_t)n * sizeof(FilterRec));
+    f->last_n = n;
+    float ms = 0;
+    HIPCHK(c, hipEventElapsedTime(&ms, f->ev0, f->ev1));
+    f->timing.device_ms = ms;
+    f->timing.host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    f->timing.n_inferences += I;
+    f->timing.n_main_inferences++;
+    if (f->timing.n_main_inferences > 100) f->timing.sum_device_ms_after_100 += ms;
+    return HNET_OK;
+}
+
+int hnet_filters_last_priors(const hnet_filters* f, int n, float* out) {
+    if (!f || !out) return HNET_ERR_INVALID_ARG;
+    if (f->last_n < 1) return fail(f->s->ctx, HNET_ERR_NOT_READY, "hnet_filters_last_priors: no step yet");
+    if (n != f->last_n) return fail(f->s->ctx, HNET_ERR_INVALID_ARG, "hnet_filters_last_priors: n differs from the last step's");
+    const int B = f->s->ctx->cfg.max_batch;
+    const float* h_prior = reinterpret_cast<const float*>(f->pin_out + f->off_prior);
+    for (int it = 0; it < f->iters; it++) memcpy(out + (size_t)it * f->last_n * 8, h_prior + (size_t)it * B * 8, (size_t)f->last_n * 8 * sizeof(float));
+    return HNET_OK;
+}
+
+int hnet_filters_last_timing(const hnet_filters* f, hnet_timing* out) {
+    if (!f || !out) return HNET_ERR_INVALID_ARG;
+    *out = f->timing;
     return HNET_OK;
 }
 

@@ -526,6 +526,81 @@ class HnetSessions:
             pass
 
 
+class HnetFilters:
+    """hnet_filters (include/hnet.h): one 27-state filter per session of `sessions`, stepped on the device.  step() runs, for any subset of the
+    sessions, the IMU propagation, max_iekf_iteration batched forwards each followed by the filter update under the reference's gate, and the
+    offsets reset, with one synchronisation; each session's result is hnet_ekf::propagate_with_imu + iterated_update around a dedicated context.
+    States are numpy records of _capi.FILTER_STATE_DTYPE, IMU readings of _capi.IMU_DTYPE.  Holds a reference to `sessions`."""
+
+    def __init__(self, sessions, max_iekf_iteration=1):
+        self.sessions, self._L, self.iters = sessions, sessions._L, int(max_iekf_iteration)
+        self._f = C.c_void_p()
+        check(sessions.engine.handle, self._L.hnet_create_filters(sessions._s, self.iters, C.byref(self._f)))
+
+    def _check(self, rc):
+        check(self.sessions.engine.handle, rc)
+
+    @staticmethod
+    def default_params():
+        p = _capi.FilterParams()
+        _capi.lib().hnet_filter_default_params(C.byref(p))
+        return p
+
+    def set_params(self, id, params):
+        self._check(self._L.hnet_filters_set_params(self._f, int(id), C.byref(params)))
+
+    def set_state(self, id, state):
+        st = np.ascontiguousarray(np.asarray(state, dtype=_capi.FILTER_STATE_DTYPE).reshape(()))
+        self._check(self._L.hnet_filters_set_state(self._f, int(id), st.ctypes.data))
+
+    def get_state(self, ids):
+        ids = np.ascontiguousarray(np.atleast_1d(ids), dtype=np.int32)
+        out = np.zeros(len(ids), _capi.FILTER_STATE_DTYPE)
+        self._check(self._L.hnet_filters_get_state(self._f, len(ids), ids.ctypes.data, out.ctypes.data))
+        return out
+
+    def step(self, ids, t_frame, imu):
+        """ids [n]; t_frame [n]; imu: n arrays of IMU_DTYPE readings (session ids[i]'s window, time ordered).
+        -> (states [n] FILTER_STATE_DTYPE, net [iters, n, 72] float32 (mean | cov of every forward), updates [n] int32)"""
+        ids = np.ascontiguousarray(np.atleast_1d(ids), dtype=np.int32)
+        n = len(ids)
+        tf = np.ascontiguousarray(np.broadcast_to(np.asarray(t_frame, dtype=np.float64), (n,)))
+        if len(imu) != n:
+            raise ValueError("one IMU array per session")
+        parts = [np.asarray(r, dtype=_capi.IMU_DTYPE).reshape(-1) for r in imu]
+        off = np.zeros(n + 1, np.int64)
+        off[1:] = np.cumsum([len(r) for r in parts])
+        rd = np.ascontiguousarray(np.concatenate(parts) if off[-1] else np.zeros(1, _capi.IMU_DTYPE))
+        states = np.zeros(n, _capi.FILTER_STATE_DTYPE)
+        net = np.zeros((self.iters, n, 72), np.float32)
+        upd = np.zeros(n, np.int32)
+        self._check(self._L.hnet_filters_step(self._f, n, ids.ctypes.data, tf.ctypes.data, rd.ctypes.data, off.ctypes.data, states.ctypes.data,
+                                              net.ctypes.data, upd.ctypes.data))
+        return states, net, upd
+
+    def last_priors(self, n):
+        """the fp32 priors [iters, n, 8] the forwards of the last step (of n sessions; another n is refused) read"""
+        out = np.zeros((self.iters, int(n), 8), np.float32)
+        self._check(self._L.hnet_filters_last_priors(self._f, int(n), out.ctypes.data))
+        return out
+
+    def last_timing(self):
+        t = Timing()
+        self._check(self._L.hnet_filters_last_timing(self._f, C.byref(t)))
+        return {"device_ms": t.device_ms, "host_ms": t.host_ms, "n_inferences": t.n_inferences, "n_steps": t.n_main_inferences}
+
+    def close(self):
+        if getattr(self, "_f", None):
+            self._L.hnet_destroy_filters(self._f)
+            self._f = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class HomographyNet:
     """Mirror of ``pytorch::HomographyNet`` (HomographyNet.h:23-67).
 

@@ -314,6 +314,50 @@ int  hnet_sessions_last_timing(const hnet_sessions* s, hnet_timing* out); /* the
 int  hnet_infer_batch_seqs_packed_device(hnet_ctx* ctx, const void* d_prev, const void* d_curr, int pix_fmt, const float* d_prior, int batch,
                                          const uint64_t* d_pair_seq, float* d_out72, float* d_err_map, void* stream);
 
+/* ---- filters: one 27-state filter per session, stepped on the device ------------------------------------------------------------------
+ * The per-frame filter work of VioManager.cpp:188-275 for any subset of a sessions object's cameras, on the context's stream, with ONE host synchronisation:
+ * IMU propagation of mean and covariance (Propagator.cpp:28-76), the prior (:230-234), max_iekf_iteration batched forwards each followed by
+ * UpdaterHNet::update under the reference's gate (:257: latest time == t_frame and image count > 10), then State::reset_4pt_offset (:275).
+ * For every listed session a step equals hnet_ekf::propagate_with_imu + hnet_ekf::iterated_update (include/hnet_ekf.h) around a dedicated context; each
+ * forward advances the session's mask sequence number by one, as max_iekf_iteration calls of hnet_sessions_infer do.  Unlisted sessions are untouched.
+ * The IMU readings are selected on the host (hnet_ekf::select_imu_readings), everything else runs on the device.  The one difference to the host loop:
+ * a singular innovation covariance leaves that session's state as it was before that update and skips its later updates in the step (updates[i] < 0),
+ * where hnet_ekf::iterated_update stops iterating; the device still runs the later batched forwards for it, so its sequence number advances once per
+ * iteration either way.  Errors (the hnet_sessions codes: a bad or repeated id, n > max_batch, a session with fewer than two images, t_frame <= state t)
+ * change no state.  The F16X2 overflow and chain-timeout repeats of hnet_sessions_infer apply to the whole step (the listed states are restored first).
+ * The filters must be destroyed before their sessions. */
+typedef struct hnet_imu { double t, wm[3], am[3]; } hnet_imu;
+/* defaults (hnet_filter_default_params): uzhfpv.launch - indoor T_ItoCmono (:84-89; i_t_i2c = -c_R_i^T t, State.cpp:95-96), noise densities
+ * (:69-72), gravity (:48), up_linear_K_HNet_Cov 10 (:65), imu_avg (use_imuavg, :37).  cam_imu_dt: the fixed camera-IMU time offset (t_imu = t_cam + dt);
+ * its default 0 is NOT the launch value (uzhfpv.launch:43 sets calib_camimu_dt = -0.0148489, applied as a fixed offset): set it for that setup */
+typedef struct hnet_filter_params {
+    double c_R_i[9], i_t_i2c[3];
+    double sigma_w, sigma_a, sigma_wb, sigma_ab, gravity_mag, k_net_cov, cam_imu_dt;
+    int32_t imu_avg;
+} hnet_filter_params;
+/* t: time of the state (camera clock); p, q (Hamilton w, x, y, z), v, ba, bg, offset (ul, bl, br, ur; x, y, z each), cov 27 x 27 row major
+ * (the hnet_ekf::State layout behind t).  A new filter: t = 0, q = identity, everything else 0. */
+typedef struct hnet_filter_state { double t, p[3], q[4], v[3], ba[3], bg[3], offset[12], cov[729]; } hnet_filter_state;
+typedef struct hnet_filters hnet_filters;
+
+void hnet_filter_default_params(hnet_filter_params* p);
+/* one filter per session of `s`, all with the default parameters; max_iekf_iteration forwards per step, 1 .. 64 (HNET_ERR_INVALID_ARG otherwise;
+ * uzhfpv.launch:67: 1) */
+int  hnet_create_filters(hnet_sessions* s, int max_iekf_iteration, hnet_filters** out);
+void hnet_destroy_filters(hnet_filters* f);
+int  hnet_filters_set_params(hnet_filters* f, int id, const hnet_filter_params* p);
+int  hnet_filters_set_state(hnet_filters* f, int id, const hnet_filter_state* st);
+int  hnet_filters_get_state(hnet_filters* f, int n, const int32_t* ids, hnet_filter_state* out);
+/* one frame for n sessions: t_frame [n] (camera clock, > each state's t); session ids[i]'s readings are imu[imu_off[i] .. imu_off[i + 1]) in time order (a window
+ * around [state t, t_frame], as VioManager's imu_data).  state_out [n] (the states after the step), net_out [max_iekf_iteration][n][72] (packed mean | cov of
+ * every forward) and updates [n] (updates applied; -1 - applied when a singular S stopped them) may be NULL. */
+int  hnet_filters_step(hnet_filters* f, int n, const int32_t* ids, const double* t_frame, const hnet_imu* imu, const int64_t* imu_off,
+                       hnet_filter_state* state_out, float* net_out, int32_t* updates);
+/* the fp32 priors [max_iekf_iteration][n][8] the forwards of the last step read (whether or not use_prior let them); n must be that step's n
+ * (HNET_ERR_INVALID_ARG otherwise, nothing written) (tests, tools) */
+int  hnet_filters_last_priors(const hnet_filters* f, int n, float* out);
+int  hnet_filters_last_timing(const hnet_filters* f, hnet_timing* out);   /* last step: device ms (upload end .. last update), host ms; steps so far */
+
 int hnet_synchronize(hnet_ctx* ctx, void* stream);
 int hnet_last_timing(const hnet_ctx* ctx, hnet_timing* out);
 

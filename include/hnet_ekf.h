@@ -459,5 +459,89 @@ inline int iterated_update(State& s, Net& net, int max_iekf_iteration, double k_
     return done;
 }
 
+/* ---- IMU propagation over one camera interval: what Propagator::propagate_with_imu (Propagator.cpp:28-76) does with the
+ * buffered IMU readings.  The device filters (hnet_filters, include/hnet.h) select the readings with these functions on the host and run the
+ * intervals on the device; tests/test_filters_cpu.py checks them against a numpy restatement. */
+struct ImuData {
+    double t;                          /* time stamp (IMU clock) */
+    double wm[3];                      /* measured angular velocity */
+    double am[3];                      /* measured specific force */
+};
+
+/* Propagator.h:179-190: linear interpolation of two readings at time t */
+inline ImuData interpolate_data(const ImuData& a, const ImuData& b, double t) {
+    const double lambda = (t - a.t) / (b.t - a.t);
+    ImuData d;
+    d.t = t;
+    for (int i = 0; i < 3; i++) {
+        d.am[i] = (1 - lambda) * a.am[i] + lambda * b.am[i];
+        d.wm[i] = (1 - lambda) * a.wm[i] + lambda * b.wm[i];
+    }
+    return d;
+}
+
+/* Propagator::select_imu_readings (Propagator.cpp:81-175): the readings that cover [t0, t1] out of readings[0 .. n), split at both ends,
+ * zero-dt readings (< 1e-12) removed.  `out` has room for n + 2 entries; returns how many were written (fewer than two: nothing to
+ * integrate, as the reference's warning cases). */
+inline int select_imu_readings(const ImuData* readings, int n, double t0, double t1, ImuData* out) {
+    int m = 0;
+    if (n <= 0) return 0;
+    for (int i = 0; i < n - 1; i++) {
+        if (readings[i + 1].t > t0 && readings[i].t < t0) {                          /* start of the period: split */
+            out[m++] = interpolate_data(readings[i], readings[i + 1], t0);
+            continue;
+        }
+        if (readings[i].t >= t0 && readings[i + 1].t <= t1) {                        /* middle: the whole reading */
+            out[m++] = readings[i];
+            continue;
+        }
+        if (readings[i + 1].t > t1) {                                                /* end of the period */
+            if (readings[i].t > t1 && i == 0) break;                                 /* IMU slower than the camera, nothing before t0 */
+            else if (readings[i].t > t1) out[m++] = interpolate_data(readings[i - 1], readings[i], t1);
+            else out[m++] = readings[i];
+            if (out[m - 1].t != t1) out[m++] = interpolate_data(readings[i], readings[i + 1], t1);
+            break;
+        }
+    }
+    if (m == 0) return 0;
+    for (int i = 0; i < m - 1; i++)                                                  /* zero dt: drop the earlier reading */
+        if (std::fabs(out[i + 1].t - out[i].t) < 1e-12) {
+            for (int j = i; j < m - 1; j++) out[j] = out[j + 1];
+            m--;
+            i--;
+        }
+    return m;
+}
+
+/* Propagator::predict_and_compute (Propagator.cpp:186-204): the corrected inputs of the interval a -> b with the state's current biases,
+ * the average of both ends with imu_avg (StateOptions.h:39, true by default), the later reading otherwise; returns dt */
+inline double imu_interval_inputs(const State& s, const ImuData& a, const ImuData& b, bool imu_avg, double w_hat[3], double a_hat[3]) {
+    for (int i = 0; i < 3; i++) {
+        const double w1 = a.wm[i] - s.bg[i], a1 = a.am[i] - s.ba[i];
+        const double w2 = b.wm[i] - s.bg[i], a2 = b.am[i] - s.ba[i];
+        w_hat[i] = imu_avg ? .5 * (w1 + w2) : w2;
+        a_hat[i] = imu_avg ? .5 * (a1 + a2) : a2;
+    }
+    return b.t - a.t;
+}
+
+/* Propagator::propagate_with_imu (Propagator.cpp:28-76) with a fixed camera-IMU time offset cam_imu_dt (t_imu = t_cam + cam_imu_dt;
+ * calib_cam_timeoffset is false in uzhfpv.launch:42).  t_state / t_frame: camera clock.  Refuses t_frame <= t_state (the reference exits,
+ * :32-43) and returns -1; otherwise runs one propagate() per selected interval and returns their number.  With fewer than two selected
+ * readings no interval runs, and the state time still becomes t_frame (:75): the caller records it.  `scratch` has room for n + 2 readings. */
+inline int propagate_with_imu(State& s, const Extrinsics& e, double t_state, double t_frame, const ImuData* readings, int n,
+                              const double q[NW], double gravity_mag, bool imu_avg, double cam_imu_dt, ImuData* scratch) {
+    if (!(t_frame > t_state)) return -1;
+    const int m = select_imu_readings(readings, n, t_state + cam_imu_dt, t_frame + cam_imu_dt, scratch);
+    int done = 0;
+    for (int i = 0; i + 1 < m; i++) {
+        double w_hat[3], a_hat[3];
+        const double dt = imu_interval_inputs(s, scratch[i], scratch[i + 1], imu_avg, w_hat, a_hat);
+        propagate(s, e, dt, w_hat, a_hat, q, gravity_mag);
+        done++;
+    }
+    return done;
+}
+
 }  // namespace hnet_ekf
 #endif  /* HNET_EKF_H */

@@ -1,0 +1,125 @@
+#!/usr/bin/env python3
+"""Device filters (hnet_filters, include/hnet.h) against the host loop of INTEGRATION.md §6, in one process, over the replay fixture.
+Per tick every one of K sessions pushes one frame and gets 16 IMU intervals of 2 ms; then
+  device: one hnet_filters_step (propagation, max_iekf_iteration forwards + updates, reset; one synchronisation),
+  host:   hnet_ekf::propagate_with_imu on T threads, then per iteration the priors, hnet_sessions_infer and hnet_ekf::update on T threads, then the
+          reset (tests/cpp/filters_ref.cpp, built here with g++ -O2), on a second sessions object of the same blob.
+One JSON line per (K, iterations): ticks/s and ms per tick of both (median, p10, p90 over the ticks), the step's device ms (upload .. last
+update, HIP events).
+   python tools/filters_bench.py [--k 1,8,64,256] [--iters 1,3] [--ticks 20] [--warmup 3] [--threads 1,16]"""
+import argparse
+import ctypes as C
+import json
+import os
+import subprocess
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def build_ref():
+    so = os.path.join(tempfile.mkdtemp(prefix="filters_ref_"), "filters_ref.so")
+    subprocess.run(["g++", "-std=c++17", "-O2", "-shared", "-fPIC", "-pthread", "-I", os.path.join(ROOT, "include"),
+                    os.path.join(ROOT, "tests", "cpp", "filters_ref.cpp"), "-o", so], check=True)
+    return C.CDLL(so)
+
+
+def imu_window(rng, t0, n_int=16, dt=0.002):
+    r = np.zeros(n_int + 2, np.dtype([("t", "<f8"), ("wm", "<f8", 3), ("am", "<f8", 3)]))
+    r["t"] = t0 - 0.0005 + dt * np.arange(n_int + 2)
+    r["wm"] = rng.standard_normal((n_int + 2, 3)) * 0.2
+    r["am"] = rng.standard_normal((n_int + 2, 3)) * 0.3 + [0, 0, 9.81]
+    return r
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--k", default="1,8,64,256")
+    ap.add_argument("--iters", default="1,3")
+    ap.add_argument("--ticks", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--threads", default="1,16")
+    a = ap.parse_args()
+    from cuahn_vio_amd import _capi, replay, weights
+    from cuahn_vio_amd.homography_net import HnetEngine, HnetFilters, HnetSessions
+    ref = build_ref()
+    blob = weights.pack_state_dict(weights.synthetic_state(0))
+    fx = replay.load_fixture("indoor_forward_7")
+    pool = np.stack([replay.render_frame(fx, 100 + j) for j in range(16)])
+    threads = [int(x) for x in a.threads.split(",")]
+    kw = dict(variant="prior3", mc_samples=16, dropout_p=0.05, mc_seed=1)
+    for K in [int(x) for x in a.k.split(",")]:
+        for iters in [int(x) for x in a.iters.split(",")]:
+            e1, e2 = HnetEngine(blob, max_batch=K, **kw), HnetEngine(blob, max_batch=K, **kw)
+            s1, s2 = HnetSessions(e1, K), HnetSessions(e2, K)
+            f = HnetFilters(s1, iters)
+            p = HnetFilters.default_params()
+            params = (_capi.FilterParams * K)(*([p] * K))
+            ids = np.arange(K, dtype=np.int32)
+            st0 = np.zeros(1, _capi.FILTER_STATE_DTYPE)
+            st0["q"] = [1, 0, 0, 0]
+            st0["p"] = [0, 0, -1.0]
+            st0["cov"] = np.diag(np.r_[np.full(15, 1e-3), np.full(12, 1e-6)])
+            for i in range(K):
+                f.set_state(i, st0[0])
+            hosts = {T: np.repeat(st0, K) for T in threads}
+            rng = np.random.default_rng(K)
+            dev_ms, dev_dev, host_ms = [], [], {T: [] for T in threads}
+            t = 0.0
+            for tick in range(a.warmup + a.ticks):
+                t_new = t + 0.0325
+                fr = np.repeat(pool[tick % len(pool)][None], K, 0)
+                for s in (s1, s2):
+                    s.push(ids, fr, t=[t_new] * K)
+                win = imu_window(rng, t)
+                if tick == 0:                                   # one image per session so far: nothing to step
+                    t = t_new
+                    continue
+                t0 = time.perf_counter()
+                f.step(ids, [t_new] * K, [win] * K)
+                d = (time.perf_counter() - t0) * 1e3
+                if tick > a.warmup:
+                    dev_ms.append(d)
+                    dev_dev.append(f.last_timing()["device_ms"])
+                imu = np.ascontiguousarray(np.tile(win, K))
+                off = (np.arange(K + 1) * len(win)).astype(np.int64)
+                tf = np.full(K, t_new)
+                for T in threads:
+                    h = hosts[T]
+                    t0 = time.perf_counter()
+                    ref.ref_propagate_batch(C.c_void_p(h.ctypes.data), params, K, C.c_void_p(tf.ctypes.data), C.c_void_p(imu.ctypes.data),
+                                            C.c_void_p(off.ctypes.data), T)
+                    gate = np.array([int(s2.latest_time(j) == t_new and s2.image_count(j) > 10) for j in range(K)], np.int32)
+                    for it in range(iters):
+                        prior_px = h["offset"][:, :, :2].reshape(K, 8) * 159.5
+                        prior_cam = np.ascontiguousarray(h["offset"][:, :, :2].reshape(K, 8))
+                        mean, cov = s2.infer(ids, prior_px)
+                        ref.ref_update_batch(C.c_void_p(h.ctypes.data), params, K, C.c_void_p(mean.ctypes.data), C.c_void_p(cov.ctypes.data),
+                                             C.c_void_p(prior_cam.ctypes.data), C.c_void_p(gate.ctypes.data), int(it != iters - 1), T)
+                    ref.ref_reset_batch(C.c_void_p(h.ctypes.data), K)
+                    if tick > a.warmup:
+                        host_ms[T].append((time.perf_counter() - t0) * 1e3)
+                t = t_new
+            def pct(x, q):
+                return round(float(np.percentile(x, q)), 3)
+            rec = {"K": K, "max_iekf_iteration": iters, "intervals": 16, "ticks": len(dev_ms),
+                   "device_step_ms_p50": pct(dev_ms, 50), "device_step_ms_p10": pct(dev_ms, 10), "device_step_ms_p90": pct(dev_ms, 90),
+                   "device_step_ticks_per_s": round(1e3 / float(np.median(dev_ms)), 1),
+                   "device_step_event_ms_p50": pct(dev_dev, 50), "device_step_event_ms_p10": pct(dev_dev, 10), "device_step_event_ms_p90": pct(dev_dev, 90)}
+            for T in threads:
+                m = float(np.median(host_ms[T]))
+                rec[f"host_loop_{T}t_ms_p50"] = round(m, 3)
+                rec[f"host_loop_{T}t_ms_p10"] = pct(host_ms[T], 10)
+                rec[f"host_loop_{T}t_ms_p90"] = pct(host_ms[T], 90)
+                rec[f"host_loop_{T}t_ticks_per_s"] = round(1e3 / m, 1)
+            print(json.dumps(rec), flush=True)
+            f.close(); s1.close(); s2.close(); e1.close(); e2.close()
+
+
+if __name__ == "__main__":
+    main()
