@@ -1,0 +1,612 @@
+// capi_sessions.hip — hnet_sessions_* (many camera streams on one context) and hnet_filters_* (one device filter per session) of include/hnet.h.
+#include "capi_internal.h"
+
+using namespace hnet;
+using namespace capi;
+
+extern "C" {
+
+// ---- sessions: many camera streams on one context (include/hnet.h).  Per session: image count, ring orientation, time stamp, mask sequence number and camera, all
+// on the host; the frames live in a device ring of 2 slots per session (slot 2 id + k).  Every device step runs on the context's stream.
+struct hnet_sessions {
+    hnet_ctx* ctx = nullptr;
+    int n = 0;
+    uint8_t* ring = nullptr;                   // device [n][2][NPIX]
+    struct Sess { int count = 0, curr = 0, cam = -1; double t = -1.0; uint64_t seq = 0; };
+    std::vector<Sess> st;
+    std::vector<uint8_t> mark;                 // id validation scratch (repeats within one call)
+    struct Cam { float* map[2]; int rows, cols; };
+    std::vector<Cam> cams;
+    const float** d_maps = nullptr;            // device [cams][2]: the map pointers session_remap_kernel reads
+    // push: two pinned blocks used in turn (the ev_img pattern of hnet_push_image), each {slot table [n] i32, camera table [n] i32 | frames}, and one device slab
+    uint8_t* pin[2] = {nullptr, nullptr};
+    size_t pin_cap[2] = {0, 0};
+    hipEvent_t ev_pin[2] = {nullptr, nullptr};
+    int pin_next = 0;
+    uint8_t* slab = nullptr;
+    size_t slab_cap = 0;
+    // infer: ONE pinned block {priors [n][8] f32 | seq table [n] u64 | pair table [n][2] i32} and its device copy, sized for max_batch
+    uint8_t* pin_tab = nullptr;
+    uint8_t* d_tab = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hnet_timing timing = {};
+};
+
+static constexpr int HNET_SESSIONS_MAX = 1 << 16;
+static size_t sessions_header(int n) { return ((size_t)n * 8 + 255) & ~(size_t)255; }      // slot + camera tables, 256-byte aligned frames behind them
+
+// n distinct ids in range, n within the context's capacity
+static int sessions_check_ids(hnet_sessions* s, int n, const int32_t* ids) {
+    hnet_ctx* c = s->ctx;
+    if (!ids || n < 1) return fail(c, HNET_ERR_INVALID_ARG, "sessions: n < 1 or no ids");
+    if (n > c->cfg.max_batch) return fail(c, HNET_ERR_CAPACITY, "sessions: n exceeds max_batch");
+    int rc = HNET_OK;
+    int i = 0;
+    for (; i < n; i++) {
+        if (ids[i] < 0 || ids[i] >= s->n) { rc = fail(c, HNET_ERR_INVALID_ARG, "sessions: id out of range"); break; }
+        if (s->mark[ids[i]]) { rc = fail(c, HNET_ERR_INVALID_ARG, "sessions: id repeated in one call"); break; }
+        s->mark[ids[i]] = 1;
+    }
+    for (int j = 0; j < i; j++) s->mark[ids[j]] = 0;
+    return rc;
+}
+
+// (on the context's device) pinned block of the next push with room for `bytes` (its previous upload has completed) and a device slab as large
+static int sessions_stage(hnet_sessions* s, size_t bytes, uint8_t** pin) {
+    hnet_ctx* c = s->ctx;
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    const int k = s->pin_next;
+    HIPCHK(c, hipEventSynchronize(s->ev_pin[k]));
+    if (s->pin_cap[k] < bytes) {
+        if (s->pin[k]) HIPCHK(c, hipHostFree(s->pin[k]));
+        s->pin[k] = nullptr;
+        s->pin_cap[k] = 0;
+        HIPCHK(c, hipHostMalloc((void**)&s->pin[k], bytes, hipHostMallocDefault));
+        s->pin_cap[k] = bytes;
+    }
+    if (s->slab_cap < bytes) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));               // (earlier scatters may still read it)
+        if (s->slab) HIPCHK(c, hipFree(s->slab));
+        s->slab = nullptr;
+        s->slab_cap = 0;
+        HIPCHK(c, hipMalloc((void**)&s->slab, bytes));
+        s->slab_cap = bytes;
+    }
+    *pin = s->pin[k];
+    return HNET_OK;
+}
+
+// after a push was enqueued: the slot each session wrote, its count and time stamp (hnet_push_image, :134-148)
+static int sessions_commit_push(hnet_sessions* s, int n, const int32_t* ids, const double* t) {
+    hnet_ctx* c = s->ctx;
+    HIPCHK(c, hipEventRecord(s->ev_pin[s->pin_next], c->stream));
+    for (int i = 0; i < n; i++) {
+        hnet_sessions::Sess& e = s->st[ids[i]];
+        e.curr = e.count == 0 ? 0 : (e.curr ^ 1);
+        e.count++;
+        if (e.count >= 2 && t) e.t = t[i];
+    }
+    s->pin_next ^= 1;
+    return HNET_OK;
+}
+static int sessions_slot(const hnet_sessions* s, int id) { const hnet_sessions::Sess& e = s->st[id]; return 2 * id + (e.count == 0 ? 0 : (e.curr ^ 1)); }
+// the (prev, curr) ring slots of session `id`'s pair, as launch_session_gather reads them
+static void sessions_pair(const hnet_sessions* s, int id, int32_t* pair) { pair[0] = 2 * id + (s->st[id].curr ^ 1); pair[1] = 2 * id + s->st[id].curr; }
+
+void hnet_destroy_sessions(hnet_sessions* s) {
+    if (!s) return;
+    hnet_ctx* c = s->ctx;
+    (void)hipSetDevice(c->cfg.device_id);
+    (void)hipStreamSynchronize(c->stream);
+    auto fr = [](void* p) { if (p) (void)hipFree(p); };
+    fr(s->ring); fr(s->slab); fr(s->d_tab); fr((void*)s->d_maps);
+    for (auto& k : s->cams) { fr(k.map[0]); fr(k.map[1]); }
+    for (int i = 0; i < 2; i++) {
+        if (s->pin[i]) (void)hipHostFree(s->pin[i]);
+        if (s->ev_pin[i]) (void)hipEventDestroy(s->ev_pin[i]);
+    }
+    if (s->pin_tab) (void)hipHostFree(s->pin_tab);
+    if (s->ev0) (void)hipEventDestroy(s->ev0);
+    if (s->ev1) (void)hipEventDestroy(s->ev1);
+    delete s;
+}
+
+int hnet_create_sessions(hnet_ctx* c, int n_sessions, hnet_sessions** out) {
+    if (!c || !out) return HNET_ERR_INVALID_ARG;
+    if (n_sessions < 1 || n_sessions > HNET_SESSIONS_MAX) return fail(c, HNET_ERR_INVALID_ARG, "hnet_create_sessions: n_sessions outside 1 .. 65536");
+    if (c->s_begin != 0 || c->n_local != c->cfg.mc_samples) return fail(c, HNET_ERR_UNSUPPORTED, "hnet_create_sessions: the context evaluates a sample shard");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    hnet_sessions* s = new hnet_sessions();
+    s->ctx = c;
+    s->n = n_sessions;
+    s->st.resize(n_sessions);
+    s->mark.assign(n_sessions, 0);
+    const size_t tab = (size_t)c->cfg.max_batch * (8 + 32 + 8);
+    hipError_t e = hipMalloc((void**)&s->ring, (size_t)n_sessions * 2 * NPIX);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&s->pin_tab, tab, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipMalloc((void**)&s->d_tab, tab);
+    for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipEventCreateWithFlags(&s->ev_pin[i], hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreate(&s->ev0);
+    if (e == hipSuccess) e = hipEventCreate(&s->ev1);
+    if (e != hipSuccess) {
+        hnet_destroy_sessions(s);
+        return fail(c, HNET_ERR_DEVICE, std::string("hnet_create_sessions: ") + hipGetErrorString(e));
+    }
+    *out = s;
+    return HNET_OK;
+}
+
+int hnet_sessions_push(hnet_sessions* s, int n, const int32_t* ids, const uint8_t* frames, int row_stride, size_t frame_stride, const double* t) {
+    if (!s) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = s->ctx;
+    if (!frames || row_stride < IMG_W || (n > 1 && frame_stride < (size_t)(IMG_H - 1) * row_stride + IMG_W))
+        return fail(c, HNET_ERR_INVALID_ARG, "hnet_sessions_push: frames must be 224x320 8-bit, row_stride >= 320, frames apart by frame_stride");
+    int rc = sessions_check_ids(s, n, ids);
+    if (rc != HNET_OK) return rc;
+    const size_t hdr = sessions_header(n), bytes = hdr + (size_t)n * NPIX;
+    uint8_t* pin = nullptr;
+    if ((rc = sessions_stage(s, bytes, &pin)) != HNET_OK) return rc;
+    int32_t* dst = reinterpret_cast<int32_t*>(pin);
+    for (int i = 0; i < n; i++) {
+        dst[i] = sessions_slot(s, ids[i]);
+        const uint8_t* f = frames + (size_t)i * frame_stride;
+        uint8_t* o = pin + hdr + (size_t)i * NPIX;
+        if (row_stride == IMG_W) memcpy(o, f, NPIX);
+        else for (int r = 0; r < IMG_H; r++) memcpy(o + (size_t)r * IMG_W, f + (size_t)r * row_stride, IMG_W);
+    }
+    HIPCHK(c, hipMemcpyAsync(s->slab, pin, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, launch_session_scatter(s->slab + hdr, reinterpret_cast<const int32_t*>(s->slab), n, 2 * s->n, s->ring, c->stream));
+    return sessions_commit_push(s, n, ids, t);
+}
+
+int hnet_sessions_add_camera(hnet_sessions* s, const hnet_camera* cam, int* cam_id) {
+    if (!s) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = s->ctx;
+    if (!cam || !cam_id || cam->raw_rows < 1 || cam->raw_cols < 1 || cam->raw_rows > 16384 || cam->raw_cols > 16384)
+        return fail(c, HNET_ERR_INVALID_ARG, "hnet_sessions_add_camera: camera");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    std::vector<float> mx, my;
+    build_undistort_maps(cam, mx, my);
+    hnet_sessions::Cam k = {{nullptr, nullptr}, cam->raw_rows, cam->raw_cols};
+    DevTemps tmp;                                                  // (freed unless the camera is committed below)
+    HIPCHK(c, tmp.alloc(&k.map[0], (size_t)NPIX));
+    HIPCHK(c, tmp.alloc(&k.map[1], (size_t)NPIX));
+    HIPCHK(c, hipMemcpy(k.map[0], mx.data(), NPIX * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(k.map[1], my.data(), NPIX * 4, hipMemcpyHostToDevice));
+    std::vector<const float*> tab;
+    for (auto& q : s->cams) { tab.push_back(q.map[0]); tab.push_back(q.map[1]); }
+    tab.push_back(k.map[0]);
+    tab.push_back(k.map[1]);
+    const float** d_maps = nullptr;
+    HIPCHK(c, tmp.alloc(&d_maps, tab.size()));
+    HIPCHK(c, hipMemcpy(d_maps, tab.data(), tab.size() * sizeof(float*), hipMemcpyHostToDevice));
+    HIPCHK(c, hipStreamSynchronize(c->stream));                    // enqueued remaps read the old table
+    tmp.ptrs.clear();
+    if (s->d_maps) (void)hipFree((void*)s->d_maps);
+    s->d_maps = d_maps;
+    s->cams.push_back(k);
+    *cam_id = (int)s->cams.size() - 1;
+    return HNET_OK;
+}
+
+int hnet_sessions_bind_camera(hnet_sessions* s, int id, int cam_id) {
+    if (!s) return HNET_ERR_INVALID_ARG;
+    if (id < 0 || id >= s->n || cam_id < 0 || cam_id >= (int)s->cams.size()) return fail(s->ctx, HNET_ERR_INVALID_ARG, "hnet_sessions_bind_camera: id or camera");
+    s->st[id].cam = cam_id;
+    return HNET_OK;
+}
+
+int hnet_sessions_push_raw(hnet_sessions* s, int n, const int32_t* ids, const uint8_t* raw, int rows, int cols, int row_stride, size_t frame_stride,
+                           const double* t) {
+    if (!s) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = s->ctx;
+    if (!raw || rows < 1 || cols < 1 || row_stride < cols || (n > 1 && frame_stride < (size_t)(rows - 1) * row_stride + cols))
+        return fail(c, HNET_ERR_INVALID_ARG, "hnet_sessions_push_raw: raw frame geometry");
+    int rc = sessions_check_ids(s, n, ids);
+    if (rc != HNET_OK) return rc;
+    for (int i = 0; i < n; i++) {
+        const int k = s->st[ids[i]].cam;
+        if (k < 0) return fail(c, HNET_ERR_INVALID_ARG, "hnet_sessions_push_raw: session without a camera (hnet_sessions_bind_camera)");
+        if (s->cams[k].rows != rows || s->cams[k].cols != cols) return fail(c, HNET_ERR_INVALID_ARG, "hnet_sessions_push_raw: raw image size differs from the camera's");
+    }
+    const size_t frame = ((size_t)rows * cols + 15) & ~(size_t)15;
+    const size_t hdr = sessions_header(n), bytes = hdr + (size_t)n * frame;
+    uint8_t* pin = nullptr;
+    if ((rc = sessions_stage(s, bytes, &pin)) != HNET_OK) return rc;
+    int32_t* dst = reinterpret_cast<int32_t*>(pin);
+    for (int i = 0; i < n; i++) {
+        dst[i] = sessions_slot(s, ids[i]);
+        dst[n + i] = s->st[ids[i]].cam;
+        const uint8_t* f = raw + (size_t)i * frame_stride;
+        uint8_t* o = pin + hdr + (size_t)i * frame;
+        for (int r = 0; r < rows; r++) memcpy(o + (size_t)r * cols, f + (size_t)r * row_stride, cols);
+    }
+    HIPCHK(c, hipMemcpyAsync(s->slab, pin, bytes, hipMemcpyHostToDevice, c->stream));
+    const int32_t* d_dst = reinterpret_cast<const int32_t*>(s->slab);
+    HIPCHK(c, launch_session_remap(s->slab + hdr, frame, rows, cols, d_dst, d_dst + n, s->d_maps, (int)s->cams.size(), n, 2 * s->n, s->ring, c->stream));
+    return sessions_commit_push(s, n, ids, t);
+}
+
+int hnet_sessions_infer(hnet_sessions* s, int n, const int32_t* ids, const double* prior_px, float* mean, float* cov, uint8_t* err_map) {
+    if (!s) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = s->ctx;
+    if (!mean || !cov) return fail(c, HNET_ERR_INVALID_ARG, "hnet_sessions_infer: mean / cov");
+    int rc = sessions_check_ids(s, n, ids);
+    if (rc != HNET_OK) return rc;
+    if (err_map && !c->cfg.emit_error_map) return fail(c, HNET_ERR_INVALID_ARG, "context was created without emit_error_map");
+    if (c->cfg.use_prior && !prior_px) return fail(c, HNET_ERR_INVALID_ARG, "prior required");
+    for (int i = 0; i < n; i++)
+        if (s->st[ids[i]].count < 2) return fail(c, HNET_ERR_NOT_READY, "HNet cannot inference! Only has one image!");   // :155-158, per session
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    auto t0 = std::chrono::steady_clock::now();
+    // ONE pinned block, ONE upload: the sequence numbers, the priors (:160-165 toType(kFloat)) and the (prev, curr) ring slots of every pair
+    float* pr = reinterpret_cast<float*>(s->pin_tab);
+    uint64_t* seq = reinterpret_cast<uint64_t*>(pr + (size_t)8 * n);
+    int32_t* pairs = reinterpret_cast<int32_t*>(seq + n);
+    for (int i = 0; i < n; i++) {
+        const hnet_sessions::Sess& e = s->st[ids[i]];
+        seq[i] = e.seq;
+        for (int k = 0; k < 8; k++) pr[8 * i + k] = c->cfg.use_prior ? (float)prior_px[8 * i + k] : 0.0f;
+        sessions_pair(s, ids[i], pairs + 2 * i);
+    }
+    const size_t bytes = (size_t)n * (8 + 32 + 8);
+    const float* d_pr = reinterpret_cast<const float*>(s->d_tab);
+    const uint64_t* d_seq = reinterpret_cast<const uint64_t*>(d_pr + (size_t)8 * n);
+    const int32_t* d_pairs = reinterpret_cast<const int32_t*>(d_seq + n);
+    hipStream_t st = c->stream;
+    const FwdArgs a{.prev = c->stage_prev, .curr = c->stage_curr, .prior = c->cfg.use_prior ? d_pr : nullptr, .batch = n, .mean = c->d_mean, .cov = c->d_cov,
+                    .err_u8 = err_map ? c->d_err_u8 : nullptr, .seq_tab = d_seq};
+    auto enqueue = [&](uint32_t& flag_now) -> int {
+        HIPCHK(c, hipMemcpyAsync(s->d_tab, s->pin_tab, bytes, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipEventRecord(s->ev0, st));
+        HIPCHK(c, launch_session_gather(s->ring, 2 * s->n, d_pairs, n, (uint8_t*)c->stage_prev, (uint8_t*)c->stage_curr, st));
+        const int r = forward(c, a, st);
+        if (r != HNET_OK) return r;
+        HIPCHK(c, hipEventRecord(s->ev1, st));
+        HIPCHK(c, hipMemcpyAsync(mean, c->d_mean, (size_t)n * 8 * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(cov, c->d_cov, (size_t)n * 64 * sizeof(float), hipMemcpyDeviceToHost, st));
+        if (err_map) HIPCHK(c, hipMemcpyAsync(err_map, c->d_err_u8, (size_t)n * NPIX, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(&flag_now, c->d_flag, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemsetAsync(c->d_flag, 0, 4, st));          // host results are inspected by run_host_call (as in hnet_infer_batch)
+        HIPCHK(c, hipStreamSynchronize(st));
+        return HNET_OK;
+    };
+    // a repeat reuses the same table: the counts advance once
+    rc = run_host_call(c, enqueue, [&] {
+        return !(all_finite(mean, (size_t)n * 8) && all_finite(cov, (size_t)n * 64)) && all_finite(c->cfg.use_prior ? prior_px : nullptr, (size_t)n * 8);
+    });
+    if (rc != HNET_OK) return rc;
+    for (int i = 0; i < n; i++) s->st[ids[i]].seq++;                  // n_inferences of each session's dedicated context
+    float ms = 0;
+    HIPCHK(c, hipEventElapsedTime(&ms, s->ev0, s->ev1));
+    record_timing(s->timing, ms, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), 1, true);
+    return HNET_OK;
+}
+
+int hnet_sessions_image_count(const hnet_sessions* s, int id) { return (s && id >= 0 && id < s->n) ? s->st[id].count : -1; }
+double hnet_sessions_latest_time(const hnet_sessions* s, int id) { return (s && id >= 0 && id < s->n) ? s->st[id].t : -1.0; }
+uint64_t hnet_sessions_seq(const hnet_sessions* s, int id) { return (s && id >= 0 && id < s->n) ? s->st[id].seq : 0; }
+
+int hnet_sessions_set_seq(hnet_sessions* s, int id, uint64_t seq) {
+    if (!s) return HNET_ERR_INVALID_ARG;
+    if (id < 0 || id >= s->n) return fail(s->ctx, HNET_ERR_INVALID_ARG, "sessions: id out of range");
+    s->st[id].seq = seq;
+    return HNET_OK;
+}
+
+int hnet_sessions_reset(hnet_sessions* s, int id) {
+    if (!s) return HNET_ERR_INVALID_ARG;
+    if (id < 0 || id >= s->n) return fail(s->ctx, HNET_ERR_INVALID_ARG, "sessions: id out of range");
+    s->st[id].count = 0;
+    s->st[id].curr = 0;
+    s->st[id].t = -1.0;
+    return HNET_OK;
+}
+
+int hnet_sessions_get_frame(hnet_sessions* s, int id, int which, uint8_t* out) {
+    if (!s) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = s->ctx;
+    if (!out || id < 0 || id >= s->n || (which != 0 && which != 1)) return fail(c, HNET_ERR_INVALID_ARG, "hnet_sessions_get_frame: id / which / out");
+    const hnet_sessions::Sess& e = s->st[id];
+    if (e.count < (which == 0 ? 2 : 1)) return fail(c, HNET_ERR_NOT_READY, "hnet_sessions_get_frame: no such frame yet");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    HIPCHK(c, hipMemcpyAsync(out, s->ring + (size_t)(2 * id + (which == 1 ? e.curr : e.curr ^ 1)) * NPIX, NPIX, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return HNET_OK;
+}
+
+int hnet_sessions_last_timing(const hnet_sessions* s, hnet_timing* out) {
+    if (!s || !out) return HNET_ERR_INVALID_ARG;
+    *out = s->timing;
+    return HNET_OK;
+}
+
+// ---- filters: one 27-state filter per session of a sessions object (include/hnet.h).  Device: the states [n_sessions], the parameters [n_sessions] and
+// the step's buffers sized for max_batch; host: each state's time (the t_frame check) and camera-IMU offset (the selection window).  A step works on a
+// copy of the listed states (work) and scatters it back only once its forwards are accepted: an overflow / timeout repeat starts from the untouched states.
+struct hnet_filters {
+    hnet_sessions* s = nullptr;
+    int iters = 1;
+    FilterRec* d_state = nullptr;              // [n_sessions]
+    FilterParams* d_params = nullptr;          // [n_sessions]
+    std::vector<double> t, cam_imu_dt;         // host mirror of state t / the offset of each session
+    std::vector<int> imu_avg;
+    // step outputs, ONE device block {net [iters][B][72] f32 | prior_px [iters][B][8] f32 | updates [B] i32 | work [B] FilterRec} and its pinned copy
+    uint8_t* d_out = nullptr;
+    uint8_t* pin_out = nullptr;
+    size_t off_prior = 0, off_upd = 0, off_work = 0, out_bytes = 0;
+    double* d_prior_cam = nullptr;             // [B][8]
+    // step inputs, ONE pinned block and its device copy (grown on demand): {readings [R] | t_frame [n] | seq [iters][n] | ids [n] | gate [n] | pairs [n][2] | rd_off [n + 1]}
+    uint8_t* pin_in = nullptr;
+    uint8_t* d_in = nullptr;
+    size_t in_cap = 0;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hnet_timing timing = {};
+    int last_n = 0;                            // sessions of the last accepted step (hnet_filters_last_priors)
+};
+
+static size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+void hnet_filter_default_params(hnet_filter_params* p) {
+    if (!p) return;
+    memset(p, 0, sizeof *p);
+    static const double T[12] = {-0.027256691772188965, -0.9996260641688061, 0.0021919370477445077, 0.02422852666805565,
+                                 -0.7139206120417471, 0.017931469899155242, -0.6999970157716363, 0.008974432843748055,
+                                 0.6996959571525168, -0.020644471939022302, -0.714142404092339, -0.000638971731537894};
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) p->c_R_i[i * 3 + j] = T[i * 4 + j];
+    for (int i = 0; i < 3; i++) p->i_t_i2c[i] = -(p->c_R_i[i] * T[3] + p->c_R_i[3 + i] * T[7] + p->c_R_i[6 + i] * T[11]);
+    p->sigma_w = 0.00559017;
+    p->sigma_wb = 8.94427e-04;
+    p->sigma_a = 0.01118034;
+    p->sigma_ab = 0.04472136;
+    p->gravity_mag = 9.81;
+    p->k_net_cov = 10.0;
+    p->cam_imu_dt = 0.0;
+    p->imu_avg = 1;
+}
+
+static FilterParams filter_params_dev(const hnet_filter_params& p) {
+    FilterParams d;
+    memset(&d, 0, sizeof d);
+    memcpy(d.ext.c_R_i, p.c_R_i, sizeof d.ext.c_R_i);
+    memcpy(d.ext.i_t_i2c, p.i_t_i2c, sizeof d.ext.i_t_i2c);
+    hnet_ekf::noise_q_diag(p.sigma_w, p.sigma_a, p.sigma_wb, p.sigma_ab, d.q);
+    d.gravity_mag = p.gravity_mag;
+    d.k_net_cov = p.k_net_cov;
+    d.imu_avg = p.imu_avg ? 1 : 0;
+    return d;
+}
+
+void hnet_destroy_filters(hnet_filters* f) {
+    if (!f) return;
+    hnet_ctx* c = f->s->ctx;
+    (void)hipSetDevice(c->cfg.device_id);
+    (void)hipStreamSynchronize(c->stream);
+    auto fr = [](void* p) { if (p) (void)hipFree(p); };
+    fr(f->d_state); fr(f->d_params); fr(f->d_out); fr(f->d_prior_cam); fr(f->d_in);
+    if (f->pin_out) (void)hipHostFree(f->pin_out);
+    if (f->pin_in) (void)hipHostFree(f->pin_in);
+    if (f->ev0) (void)hipEventDestroy(f->ev0);
+    if (f->ev1) (void)hipEventDestroy(f->ev1);
+    delete f;
+}
+
+int hnet_create_filters(hnet_sessions* s, int max_iekf_iteration, hnet_filters** out) {
+    if (!s || !out) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = s->ctx;
+    if (max_iekf_iteration < 1 || max_iekf_iteration > 64) return fail(c, HNET_ERR_INVALID_ARG, "hnet_create_filters: max_iekf_iteration outside 1 .. 64");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    hnet_filters* f = new hnet_filters();
+    f->s = s;
+    f->iters = max_iekf_iteration;
+    const int N = s->n, B = c->cfg.max_batch;
+    hnet_filter_params dp;
+    hnet_filter_default_params(&dp);
+    f->t.assign(N, 0.0);
+    f->cam_imu_dt.assign(N, dp.cam_imu_dt);
+    f->imu_avg.assign(N, dp.imu_avg);
+    f->off_prior = al256((size_t)f->iters * B * 72 * sizeof(float));
+    f->off_upd = f->off_prior + al256((size_t)f->iters * B * 8 * sizeof(float));
+    f->off_work = f->off_upd + al256((size_t)B * sizeof(int32_t));
+    f->out_bytes = f->off_work + (size_t)B * sizeof(FilterRec);
+    std::vector<FilterRec> st(N);
+    memset(st.data(), 0, st.size() * sizeof(FilterRec));
+    for (auto& r : st) r.s.q[0] = 1.0;
+    std::vector<FilterParams> pr(N, filter_params_dev(dp));
+    hipError_t e = hipMalloc((void**)&f->d_state, (size_t)N * sizeof(FilterRec));
+    if (e == hipSuccess) e = hipMalloc((void**)&f->d_params, (size_t)N * sizeof(FilterParams));
+    if (e == hipSuccess) e = hipMalloc((void**)&f->d_out, f->out_bytes);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&f->pin_out, f->out_bytes, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipMalloc((void**)&f->d_prior_cam, (size_t)B * 8 * sizeof(double));
+    if (e == hipSuccess) e = hipEventCreate(&f->ev0);
+    if (e == hipSuccess) e = hipEventCreate(&f->ev1);
+    if (e == hipSuccess) e = hipMemcpyAsync(f->d_state, st.data(), (size_t)N * sizeof(FilterRec), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(f->d_params, pr.data(), (size_t)N * sizeof(FilterParams), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        hnet_destroy_filters(f);
+        return fail(c, HNET_ERR_DEVICE, std::string("hnet_create_filters: ") + hipGetErrorString(e));
+    }
+    *out = f;
+    return HNET_OK;
+}
+
+int hnet_filters_set_params(hnet_filters* f, int id, const hnet_filter_params* p) {
+    if (!f) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = f->s->ctx;
+    if (!p || id < 0 || id >= f->s->n) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_set_params: id or params");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    const FilterParams d = filter_params_dev(*p);
+    HIPCHK(c, hipMemcpyAsync(f->d_params + id, &d, sizeof d, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    f->cam_imu_dt[id] = p->cam_imu_dt;
+    f->imu_avg[id] = p->imu_avg ? 1 : 0;
+    return HNET_OK;
+}
+
+static_assert(sizeof(hnet_filter_state) == sizeof(FilterRec), "hnet_filter_state is the FilterRec layout");
+
+int hnet_filters_set_state(hnet_filters* f, int id, const hnet_filter_state* st) {
+    if (!f) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = f->s->ctx;
+    if (!st || id < 0 || id >= f->s->n) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_set_state: id or state");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    HIPCHK(c, hipMemcpyAsync(f->d_state + id, st, sizeof(FilterRec), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    f->t[id] = st->t;
+    return HNET_OK;
+}
+
+int hnet_filters_get_state(hnet_filters* f, int n, const int32_t* ids, hnet_filter_state* out) {
+    if (!f) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = f->s->ctx;
+    if (!ids || !out || n < 1) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_get_state: ids / out");
+    for (int i = 0; i < n; i++)
+        if (ids[i] < 0 || ids[i] >= f->s->n) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_get_state: id out of range");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    for (int i = 0; i < n; i++) HIPCHK(c, hipMemcpyAsync(out + i, f->d_state + ids[i], sizeof(FilterRec), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return HNET_OK;
+}
+
+int hnet_filters_step(hnet_filters* f, int n, const int32_t* ids, const double* t_frame, const hnet_imu* imu, const int64_t* imu_off,
+                      hnet_filter_state* state_out, float* net_out, int32_t* updates) {
+    if (!f) return HNET_ERR_INVALID_ARG;
+    hnet_sessions* s = f->s;
+    hnet_ctx* c = s->ctx;
+    if (!t_frame || !imu_off) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_step: t_frame / imu_off");
+    int rc = sessions_check_ids(s, n, ids);
+    if (rc != HNET_OK) return rc;
+    for (int i = 0; i < n; i++)
+        if (s->st[ids[i]].count < 2) return fail(c, HNET_ERR_NOT_READY, "HNet cannot inference! Only has one image!");
+    for (int i = 0; i < n; i++) {
+        if (!(t_frame[i] > f->t[ids[i]]) || !std::isfinite(t_frame[i]))
+            return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_step: t_frame must be later than the state's time (Propagator.cpp:32-43)");
+        if (imu_off[i] < 0 || imu_off[i + 1] < imu_off[i] || (imu_off[i + 1] > imu_off[i] && !imu))
+            return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_step: imu / imu_off");
+    }
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    auto t0 = std::chrono::steady_clock::now();
+    const int I = f->iters;
+    // selection on the host (hnet_ekf::select_imu_readings: the window [state t, t_frame] + the session's offset) into the input block
+    static_assert(sizeof(hnet_imu) == sizeof(hnet_ekf::ImuData), "hnet_imu is hnet_ekf::ImuData");
+    int64_t total = 0;
+    for (int i = 0; i < n; i++) total += imu_off[i + 1] - imu_off[i] + 2;
+    const size_t o_t = al256((size_t)total * sizeof(hnet_ekf::ImuData)), o_seq = o_t + al256((size_t)n * 8), o_ids = o_seq + al256((size_t)I * n * 8);
+    const size_t o_gate = o_ids + al256((size_t)n * 4), o_pairs = o_gate + al256((size_t)n * 4), o_off = o_pairs + al256((size_t)n * 8);
+    const size_t in_bytes = o_off + al256((size_t)(n + 1) * 4);
+    if (f->in_cap < in_bytes) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (f->pin_in) HIPCHK(c, hipHostFree(f->pin_in));
+        if (f->d_in) HIPCHK(c, hipFree(f->d_in));
+        f->pin_in = f->d_in = nullptr;
+        f->in_cap = 0;
+        HIPCHK(c, hipHostMalloc((void**)&f->pin_in, in_bytes, hipHostMallocDefault));
+        HIPCHK(c, hipMalloc((void**)&f->d_in, in_bytes));
+        f->in_cap = in_bytes;
+    }
+    hnet_ekf::ImuData* rd = reinterpret_cast<hnet_ekf::ImuData*>(f->pin_in);
+    double* tf = reinterpret_cast<double*>(f->pin_in + o_t);
+    uint64_t* seq = reinterpret_cast<uint64_t*>(f->pin_in + o_seq);
+    int32_t* hid = reinterpret_cast<int32_t*>(f->pin_in + o_ids);
+    int32_t* gate = reinterpret_cast<int32_t*>(f->pin_in + o_gate);
+    int32_t* pairs = reinterpret_cast<int32_t*>(f->pin_in + o_pairs);
+    int32_t* roff = reinterpret_cast<int32_t*>(f->pin_in + o_off);
+    int R = 0;
+    for (int i = 0; i < n; i++) {
+        const int id = ids[i];
+        const hnet_sessions::Sess& e = s->st[id];
+        const int64_t m = imu_off[i + 1] - imu_off[i];
+        const double dt = f->cam_imu_dt[id];
+        roff[i] = R;
+        R += hnet_ekf::select_imu_readings(reinterpret_cast<const hnet_ekf::ImuData*>(imu) + imu_off[i], (int)m, f->t[id] + dt, t_frame[i] + dt, rd + R);
+        tf[i] = t_frame[i];
+        for (int it = 0; it < I; it++) seq[(size_t)it * n + i] = e.seq + (uint64_t)it;
+        hid[i] = id;
+        gate[i] = (e.t == t_frame[i] && e.count > 10) ? 1 : 0;                      // VioManager.cpp:257
+        sessions_pair(s, id, pairs + 2 * i);
+    }
+    roff[n] = R;
+    const hnet_ekf::ImuData* d_rd = reinterpret_cast<const hnet_ekf::ImuData*>(f->d_in);
+    const double* d_tf = reinterpret_cast<const double*>(f->d_in + o_t);
+    const uint64_t* d_seq = reinterpret_cast<const uint64_t*>(f->d_in + o_seq);
+    const int32_t* d_ids = reinterpret_cast<const int32_t*>(f->d_in + o_ids);
+    const int32_t* d_gate = reinterpret_cast<const int32_t*>(f->d_in + o_gate);
+    const int32_t* d_pairs = reinterpret_cast<const int32_t*>(f->d_in + o_pairs);
+    const int32_t* d_roff = reinterpret_cast<const int32_t*>(f->d_in + o_off);
+    float* d_net = reinterpret_cast<float*>(f->d_out);
+    float* d_prior = reinterpret_cast<float*>(f->d_out + f->off_prior);
+    int32_t* d_upd = reinterpret_cast<int32_t*>(f->d_out + f->off_upd);
+    FilterRec* d_work = reinterpret_cast<FilterRec*>(f->d_out + f->off_work);
+    const float* h_net = reinterpret_cast<const float*>(f->pin_out);
+    const float* h_prior = reinterpret_cast<const float*>(f->pin_out + f->off_prior);
+    // the output block is laid out for max_batch: download the used parts of each section in one copy up to the last one needed
+    const size_t down = state_out ? f->off_work + (size_t)n * sizeof(FilterRec) : f->off_upd + (size_t)n * sizeof(int32_t);
+    hipStream_t st = c->stream;
+    const size_t up = o_off + (size_t)(n + 1) * 4;
+    auto enqueue = [&](uint32_t& flag_now) -> int {
+        HIPCHK(c, hipMemcpyAsync(f->d_in, f->pin_in, up, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemsetAsync(d_upd, 0, (size_t)n * sizeof(int32_t), st));
+        HIPCHK(c, hipEventRecord(f->ev0, st));
+        HIPCHK(c, launch_session_gather(s->ring, 2 * s->n, d_pairs, n, (uint8_t*)c->stage_prev, (uint8_t*)c->stage_curr, st));
+        HIPCHK(c, launch_filter_propagate(d_ids, n, s->n, f->d_state, f->d_params, d_rd, d_roff, d_tf, d_work, st));
+        for (int it = 0; it < I; it++) {
+            float* pr_it = d_prior + (size_t)it * c->cfg.max_batch * 8;
+            float* net_it = d_net + (size_t)it * c->cfg.max_batch * 72;
+            HIPCHK(c, launch_filter_prior(d_work, n, pr_it, f->d_prior_cam, st));
+            const FwdArgs a{.prev = c->stage_prev, .curr = c->stage_curr, .prior = c->cfg.use_prior ? pr_it : nullptr, .batch = n, .mean = net_it, .cov = net_it + 8,
+                            .seq_tab = d_seq + (size_t)it * n, .mean_stride = HNET_PACKED_FLOATS, .cov_stride = HNET_PACKED_FLOATS};
+            const int r = forward(c, a, st);
+            if (r != HNET_OK) return r;
+            HIPCHK(c, launch_filter_update(d_ids, n, s->n, f->d_params, net_it, f->d_prior_cam, d_gate, it != I - 1, it == I - 1, d_work, d_upd, st));
+        }
+        HIPCHK(c, hipEventRecord(f->ev1, st));
+        HIPCHK(c, hipMemcpyAsync(f->pin_out, f->d_out, down, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(&flag_now, c->d_flag, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemsetAsync(c->d_flag, 0, 4, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        return HNET_OK;
+    };
+    // an overflow of the fp16 planes: the first forward with a non-finite output had finite inputs (its fp32 priors; later priors follow from it)
+    auto overflowed = [&]() -> bool {
+        for (int it = 0; it < I; it++)
+            if (!all_finite(h_net + (size_t)it * c->cfg.max_batch * 72, (size_t)n * 72))
+                return !c->cfg.use_prior || all_finite(h_prior + (size_t)it * c->cfg.max_batch * 8, (size_t)n * 8);
+        return false;
+    };
+    if ((rc = run_host_call(c, enqueue, overflowed)) != HNET_OK) return rc;
+    // accepted: the listed states take the step's result (stream order: later calls see it), the bookkeeping advances
+    HIPCHK(c, launch_filter_scatter(d_work, d_ids, n, s->n, f->d_state, st));
+    for (int i = 0; i < n; i++) {
+        f->t[ids[i]] = t_frame[i];
+        s->st[ids[i]].seq += (uint64_t)I;
+    }
+    if (net_out)
+        for (int it = 0; it < I; it++) memcpy(net_out + (size_t)it * n * 72, h_net + (size_t)it * c->cfg.max_batch * 72, (size_t)n * 72 * sizeof(float));
+    if (updates) memcpy(updates, f->pin_out + f->off_upd, (size_t)n * sizeof(int32_t));
+    if (state_out) memcpy(state_out, f->pin_out + f->off_work, (size_t)n * sizeof(FilterRec));
+    f->last_n = n;
+    float ms = 0;
+    HIPCHK(c, hipEventElapsedTime(&ms, f->ev0, f->ev1));
+    record_timing(f->timing, ms, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), I, true);
+    return HNET_OK;
+}
+
+int hnet_filters_last_priors(const hnet_filters* f, int n, float* out) {
+    if (!f || !out) return HNET_ERR_INVALID_ARG;
+    if (f->last_n < 1) return fail(f->s->ctx, HNET_ERR_NOT_READY, "hnet_filters_last_priors: no step yet");
+    if (n != f->last_n) return fail(f->s->ctx, HNET_ERR_INVALID_ARG, "hnet_filters_last_priors: n differs from the last step's");
+    const int B = f->s->ctx->cfg.max_batch;
+    const float* h_prior = reinterpret_cast<const float*>(f->pin_out + f->off_prior);
+    for (int it = 0; it < f->iters; it++) memcpy(out + (size_t)it * f->last_n * 8, h_prior + (size_t)it * B * 8, (size_t)f->last_n * 8 * sizeof(float));
+    return HNET_OK;
+}
+
+int hnet_filters_last_timing(const hnet_filters* f, hnet_timing* out) {
+    if (!f || !out) return HNET_ERR_INVALID_ARG;
+    *out = f->timing;
+    return HNET_OK;
+}
+
+}  // extern "C"

@@ -22,7 +22,7 @@
 //    two 16-chunk windows that would have to start at the same bank).  Now each lane reads its 16-byte chunk as two
 //    ds_read_b64, even groups low half first, odd groups high half first: the 32 lanes of a b64 access then cover all 64
 //    banks exactly once for ANY chunk-aligned tap offsets.  Odd groups so get channels (4..7, 0..3); their weight
-//    fragments are packed in that channel order (hnet_capi.hip), the MFMA sums over K and does not care.
+//    fragments are packed in that channel order (capi_weights.hip), the MFMA sums over K and does not care.
 //  * geometry is a template: <TH1 = 8, 512 threads> is the round-1 shape (85 KB of LDS, one workgroup per CU: staging,
 //    phase 1 and phase 2 of the ONE resident workgroup never overlap); <TH1 = 7, 256 threads> needs 76.5 KB, so TWO
 //    independent workgroups share a CU (one wave of each per SIMD) and one's staging / epilogue / stores run under the

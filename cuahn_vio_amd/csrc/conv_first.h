@@ -28,7 +28,7 @@ template <> struct FirstCfg<16> {
     static constexpr int NFRAG = 56;                // 7 rows x 8 k-steps (32x32x2)
 };
 
-// wfrag: [NFRAG][64] floats, fragment t of lane l (host-packed, see pack_first_weights in hnet_capi.hip)
+// wfrag: [NFRAG][64] floats, fragment t of lane l (host-packed, see pack_first_weights in capi_weights.hip)
 // out16 != nullptr: the output is written as three bf16 planes (S3, igemm_s3.h) instead of fp32
 template <int COUT>
 __global__ __launch_bounds__(256) void conv7_c2_s1_kernel(const float* __restrict__ in, const float* __restrict__ wfrag,
@@ -193,7 +193,7 @@ __global__ __launch_bounds__(256) void conv7_c2_s1_kernel(const float* __restric
 // sixteenth of the rate.  The MFMA is issued with the weights as A operand (transposed tile, conv_b4_fused.h): a lane
 // holds 4 x 4 consecutive channels of its pixel pair and writes them as 8-byte pieces of the S3 planes.
 // wfrag: [7 kernel rows][3 planes][64 lanes] x 16 B; lane (n = l&31 = (dx, co), hh = l>>5) holds kk = 8hh .. 8hh+7 of
-// W'[kh][kk = 2 kw' + ci][n] = W[co][ci][kh][kw' - dx] (pack in hnet_capi.hip).
+// W'[kh][kk = 2 kw' + ci][n] = W[co][ci][kh][kw' - dx] (pack in capi_weights.hip).
 // ---------------------------------------------------------------------------------------------
 // NP = number of bf16 planes (3 = split-bf16, 1 = plain bf16 operands)
 template <int NP>
@@ -342,7 +342,7 @@ __global__ __launch_bounds__(256) void conv7_c2_s1_s3_kernel(const float* __rest
 //   32-deep step, four steps (row 7 zero): lane group g reads row 2 st + (g>>1), taps 4 (g&1) .. + 3 = 16 contiguous bytes
 //   of the patch (8-byte aligned: the first tap of output column ox is input column 2 ox);
 //   N = 16 output channels per MFMA, weights as A operand (transposed tile: a lane holds 4 channels of one pixel).
-// wfrag: [COUT / 16 n-tiles][4 steps][3 planes][64 lanes] x 16 B (pack in hnet_capi.hip).  out16: S3 planes [B][HO][WO][COUT].
+// wfrag: [COUT / 16 n-tiles][4 steps][3 planes][64 lanes] x 16 B (pack in capi_weights.hip).  out16: S3 planes [B][HO][WO][COUT].
 // ---------------------------------------------------------------------------------------------
 template <int COUT, int HO, int WO, int TH, int NP>
 __global__ __launch_bounds__(256) void conv7_c2_s2_s3_kernel(const float* __restrict__ in, const u32x4* __restrict__ wfrag,

@@ -11,7 +11,7 @@
 //             result is non-finite and is DETECTED (hnet_overflow_flag / demotion), never silently wrong; from 65520 on A0 overflows as well
 //             (tests/cpp/s3_format_check.cpp walks both bands exhaustively); fp16 subnormals are not flushed by the gfx950 MFMAs
 //             (tools/f16x2_probe.hip), so small values only lose ABSOLUTE precision below 2^-37.
-// Host + device helpers shared by the kernels (igemm_s3.h) and the weight packer (hnet_capi.hip).
+// Host + device helpers shared by the kernels (igemm_s3.h) and the weight packer (capi_weights.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
