@@ -36,7 +36,11 @@ SYMBOLS = [
     "hnet_sessions_seq", "hnet_sessions_reset", "hnet_sessions_get_frame", "hnet_sessions_last_timing", "hnet_infer_batch_seqs_packed_device",
     "hnet_filter_default_params", "hnet_create_filters", "hnet_destroy_filters", "hnet_filters_set_params", "hnet_filters_set_state",
     "hnet_filters_get_state", "hnet_filters_step", "hnet_filters_last_priors", "hnet_filters_last_timing",
+    "hnet_filter_default_init_params", "hnet_filters_enable_feed", "hnet_filters_set_init_params", "hnet_filters_feed_imu", "hnet_filters_initialized",
+    "hnet_filters_uninitialize", "hnet_filters_advance", "hnet_filters_last_selection",
 ]
+# hnet_filters_advance's status per listed session (include/hnet.h HNET_ADV_*)
+ADV_STEPPED, ADV_WAIT_IMU, ADV_WAIT_INIT, ADV_INITIALIZED, ADV_PROPAGATED, ADV_NO_FRAME = range(6)
 
 
 class Config(C.Structure):
@@ -62,6 +66,11 @@ class FilterParams(C.Structure):
     _fields_ = [("c_R_i", C.c_double * 9), ("i_t_i2c", C.c_double * 3), ("sigma_w", C.c_double), ("sigma_a", C.c_double),
                 ("sigma_wb", C.c_double), ("sigma_ab", C.c_double), ("gravity_mag", C.c_double), ("k_net_cov", C.c_double),
                 ("cam_imu_dt", C.c_double), ("imu_avg", C.c_int32)]
+
+
+class InitParams(C.Structure):
+    """hnet_init_params: the static initialiser's window length, excitation threshold, initial height and wait_for_jerk"""
+    _fields_ = [("window_time", C.c_double), ("imu_thresh", C.c_double), ("init_height", C.c_double), ("wait_for_jerk", C.c_int32)]
 
 
 # hnet_filter_state / hnet_imu as numpy records (the C structs are packed doubles)
@@ -186,6 +195,15 @@ def lib():
     L.hnet_filters_step.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]
     L.hnet_filters_last_priors.argtypes = [vp, C.c_int, vp]
     L.hnet_filters_last_timing.argtypes = [vp, C.POINTER(Timing)]
+    L.hnet_filter_default_init_params.argtypes = [C.POINTER(InitParams)]
+    L.hnet_filter_default_init_params.restype = None
+    L.hnet_filters_enable_feed.argtypes = [vp, C.c_int]
+    L.hnet_filters_set_init_params.argtypes = [vp, C.c_int, C.POINTER(InitParams)]
+    L.hnet_filters_feed_imu.argtypes = [vp, C.c_int, vp, vp, vp]
+    L.hnet_filters_initialized.argtypes = [vp, C.c_int]
+    L.hnet_filters_uninitialize.argtypes = [vp, C.c_int]
+    L.hnet_filters_advance.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
+    L.hnet_filters_last_selection.argtypes = [vp, C.c_int, vp, C.c_int, C.POINTER(C.c_int)]
     for name in SYMBOLS:
         getattr(L, name)   # AttributeError here = the library does not export what include/hnet.h declares
     _lib = L

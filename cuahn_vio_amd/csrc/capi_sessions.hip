@@ -12,7 +12,8 @@ struct hnet_sessions {
     hnet_ctx* ctx = nullptr;
     int n = 0;
     uint8_t* ring = nullptr;                   // device [n][2][NPIX]
-    struct Sess { int count = 0, curr = 0, cam = -1; double t = -1.0; uint64_t seq = 0; };
+    // t_push: the stamp of the latest push, whatever the count (NaN: none given; hnet_filters_advance's t_frame)
+    struct Sess { int count = 0, curr = 0, cam = -1; double t = -1.0; uint64_t seq = 0; double t_push = NAN; };
     std::vector<Sess> st;
     std::vector<uint8_t> mark;                 // id validation scratch (repeats within one call)
     struct Cam { float* map[2]; int rows, cols; };
@@ -85,6 +86,7 @@ static int sessions_commit_push(hnet_sessions* s, int n, const int32_t* ids, con
         e.curr = e.count == 0 ? 0 : (e.curr ^ 1);
         e.count++;
         if (e.count >= 2 && t) e.t = t[i];
+        e.t_push = t ? t[i] : NAN;
     }
     s->pin_next ^= 1;
     return HNET_OK;
@@ -300,6 +302,7 @@ int hnet_sessions_reset(hnet_sessions* s, int id) {
     s->st[id].count = 0;
     s->st[id].curr = 0;
     s->st[id].t = -1.0;
+    s->st[id].t_push = NAN;
     return HNET_OK;
 }
 
@@ -343,6 +346,27 @@ struct hnet_filters {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hnet_timing timing = {};
     int last_n = 0;                            // sessions of the last accepted step (hnet_filters_last_priors)
+    // ---- the IMU feed (hnet_filters_enable_feed): per session a device ring of `cap` readings, its head / count mirrored here, the newest reading's time,
+    // whether the filter has a state (set_state or the initialiser) and, while it has none, the stamp of the last frame the initialiser dropped
+    int cap = 0;
+    hnet_ekf::ImuData* d_ring = nullptr;       // [n_sessions][cap]
+    ImuRingMeta* d_meta = nullptr;             // [n_sessions]
+    InitParams* d_ip = nullptr;                // [n_sessions]
+    hnet_ekf::ImuData* d_sel = nullptr;        // [B][2 (cap + 2)]: filter_select_kernel's span and selection
+    std::vector<ImuRingMeta> meta;
+    std::vector<double> imu_newest, t_seen;
+    std::vector<uint8_t> inited;
+    std::vector<hnet_init_params> ip;
+    std::vector<int> last_slot;                // session -> its workgroup in the last advance, -1 if none (hnet_filters_last_selection)
+    // feed_imu: ONE pinned block {segments [n] | readings} and its device copy (grown on demand); ev_feed: the pinned block's last upload
+    uint8_t* pin_feed = nullptr;
+    uint8_t* d_feed = nullptr;
+    size_t feed_cap = 0;
+    hipEvent_t ev_feed = nullptr;
+    // advance: ONE pinned block {jobs [B] | seq [iters][B] | gate [B] | ids [B] | pairs [B][2]} and its device copy; the results [B] behind the step's output block
+    uint8_t* pin_adv = nullptr;
+    uint8_t* d_adv = nullptr;
+    size_t off_res = 0;
 };
 
 static size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -385,6 +409,10 @@ void hnet_destroy_filters(hnet_filters* f) {
     (void)hipStreamSynchronize(c->stream);
     auto fr = [](void* p) { if (p) (void)hipFree(p); };
     fr(f->d_state); fr(f->d_params); fr(f->d_out); fr(f->d_prior_cam); fr(f->d_in);
+    fr(f->d_ring); fr(f->d_meta); fr(f->d_ip); fr(f->d_sel); fr(f->d_feed); fr(f->d_adv);
+    if (f->pin_feed) (void)hipHostFree(f->pin_feed);
+    if (f->pin_adv) (void)hipHostFree(f->pin_adv);
+    if (f->ev_feed) (void)hipEventDestroy(f->ev_feed);
     if (f->pin_out) (void)hipHostFree(f->pin_out);
     if (f->pin_in) (void)hipHostFree(f->pin_in);
     if (f->ev0) (void)hipEventDestroy(f->ev0);
@@ -409,7 +437,14 @@ int hnet_create_filters(hnet_sessions* s, int max_iekf_iteration, hnet_filters**
     f->off_prior = al256((size_t)f->iters * B * 72 * sizeof(float));
     f->off_upd = f->off_prior + al256((size_t)f->iters * B * 8 * sizeof(float));
     f->off_work = f->off_upd + al256((size_t)B * sizeof(int32_t));
-    f->out_bytes = f->off_work + (size_t)B * sizeof(FilterRec);
+    f->off_res = f->off_work + al256((size_t)B * sizeof(FilterRec));
+    f->out_bytes = f->off_res + (size_t)B * sizeof(AdvanceResult);
+    f->t_seen.assign(N, -INFINITY);
+    f->inited.assign(N, 0);
+    f->last_slot.assign(N, -1);
+    hnet_init_params ip0;
+    hnet_filter_default_init_params(&ip0);
+    f->ip.assign(N, ip0);
     std::vector<FilterRec> st(N);
     memset(st.data(), 0, st.size() * sizeof(FilterRec));
     for (auto& r : st) r.s.q[0] = 1.0;
@@ -455,6 +490,7 @@ int hnet_filters_set_state(hnet_filters* f, int id, const hnet_filter_state* st)
     HIPCHK(c, hipMemcpyAsync(f->d_state + id, st, sizeof(FilterRec), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     f->t[id] = st->t;
+    f->inited[id] = 1;
     return HNET_OK;
 }
 
@@ -606,6 +642,313 @@ int hnet_filters_last_priors(const hnet_filters* f, int n, float* out) {
 int hnet_filters_last_timing(const hnet_filters* f, hnet_timing* out) {
     if (!f || !out) return HNET_ERR_INVALID_ARG;
     *out = f->timing;
+    return HNET_OK;
+}
+
+// ---- filters, fed (include/hnet.h): the IMU rings, the initialiser and hnet_filters_advance ----
+
+void hnet_filter_default_init_params(hnet_init_params* p) {
+    if (!p) return;
+    memset(p, 0, sizeof *p);
+    p->window_time = 1.0;
+    p->imu_thresh = 0.5;
+    p->init_height = 0.1;
+    p->wait_for_jerk = 1;
+}
+
+static InitParams init_params_dev(const hnet_init_params& p) { return InitParams{p.window_time, p.imu_thresh, p.init_height, p.wait_for_jerk ? 1 : 0, 0}; }
+// the advance input block for n sessions: jobs | seq [iters][n] | gate | ids | pairs
+struct AdvLayout {
+    size_t o_seq, o_gate, o_ids, o_pairs, bytes;
+    AdvLayout(int n, int iters) {
+        o_seq = al256((size_t)n * sizeof(AdvanceJob));
+        o_gate = o_seq + al256((size_t)iters * n * 8);
+        o_ids = o_gate + al256((size_t)n * 4);
+        o_pairs = o_ids + al256((size_t)n * 4);
+        bytes = o_pairs + al256((size_t)n * 8);
+    }
+};
+
+int hnet_filters_enable_feed(hnet_filters* f, int imu_capacity) {
+    if (!f) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = f->s->ctx;
+    if (f->cap) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_enable_feed: already enabled");
+    if (imu_capacity < 2 || imu_capacity > (1 << 20)) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_enable_feed: imu_capacity outside 2 .. 1048576");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    const int N = f->s->n, B = c->cfg.max_batch;
+    const size_t adv = AdvLayout(B, f->iters).bytes;
+    std::vector<InitParams> ipd(N);
+    for (int i = 0; i < N; i++) ipd[i] = init_params_dev(f->ip[i]);
+    hipError_t e = hipMalloc((void**)&f->d_ring, (size_t)N * imu_capacity * sizeof(hnet_ekf::ImuData));
+    if (e == hipSuccess) e = hipMalloc((void**)&f->d_meta, (size_t)N * sizeof(ImuRingMeta));
+    if (e == hipSuccess) e = hipMalloc((void**)&f->d_ip, (size_t)N * sizeof(InitParams));
+    if (e == hipSuccess) e = hipMalloc((void**)&f->d_sel, (size_t)B * 2 * (imu_capacity + 2) * sizeof(hnet_ekf::ImuData));
+    if (e == hipSuccess) e = hipMalloc((void**)&f->d_adv, adv);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&f->pin_adv, adv, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&f->ev_feed, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipMemsetAsync(f->d_meta, 0, (size_t)N * sizeof(ImuRingMeta), c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(f->d_ip, ipd.data(), (size_t)N * sizeof(InitParams), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        auto fr = [](void* q) { if (q) (void)hipFree(q); };
+        fr(f->d_ring); fr(f->d_meta); fr(f->d_ip); fr(f->d_sel); fr(f->d_adv);
+        if (f->pin_adv) (void)hipHostFree(f->pin_adv);
+        if (f->ev_feed) (void)hipEventDestroy(f->ev_feed);
+        f->d_ring = nullptr; f->d_meta = nullptr; f->d_ip = nullptr; f->d_sel = nullptr; f->d_adv = nullptr; f->pin_adv = nullptr; f->ev_feed = nullptr;
+        return fail(c, HNET_ERR_DEVICE, std::string("hnet_filters_enable_feed: ") + hipGetErrorString(e));
+    }
+    f->meta.assign(N, ImuRingMeta{0, 0});
+    f->imu_newest.assign(N, -INFINITY);
+    f->cap = imu_capacity;
+    return HNET_OK;
+}
+
+int hnet_filters_set_init_params(hnet_filters* f, int id, const hnet_init_params* p) {
+    if (!f) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = f->s->ctx;
+    if (!p || id < 0 || id >= f->s->n || !(p->window_time > 0.0) || !std::isfinite(p->window_time) || !std::isfinite(p->imu_thresh) || !std::isfinite(p->init_height))
+        return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_set_init_params: id or params");
+    if (f->cap) {
+        HIPCHK(c, hipSetDevice(c->cfg.device_id));
+        const InitParams d = init_params_dev(*p);
+        HIPCHK(c, hipMemcpyAsync(f->d_ip + id, &d, sizeof d, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    f->ip[id] = *p;
+    return HNET_OK;
+}
+
+int hnet_filters_feed_imu(hnet_filters* f, int n, const int32_t* ids, const hnet_imu* imu, const int64_t* imu_off) {
+    if (!f) return HNET_ERR_INVALID_ARG;
+    hnet_sessions* s = f->s;
+    hnet_ctx* c = s->ctx;
+    if (!f->cap) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_feed_imu: feed not enabled (hnet_filters_enable_feed)");
+    if (!ids || !imu_off || n < 1 || n > s->n) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_feed_imu: ids / imu_off / n");
+    if (imu_off[0] < 0) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_feed_imu: imu_off");
+    // validation first: nothing is appended unless every listed session's readings are in order
+    int rc = HNET_OK, marked = 0;
+    for (int i = 0; i < n && rc == HNET_OK; i++) {
+        const int id = ids[i];
+        if (id < 0 || id >= s->n) { rc = fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_feed_imu: id out of range"); break; }
+        if (s->mark[id]) { rc = fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_feed_imu: id repeated in one call"); break; }
+        s->mark[id] = 1;
+        marked = i + 1;
+        if (imu_off[i + 1] < imu_off[i] || imu_off[i + 1] > INT32_MAX || (imu_off[i + 1] > imu_off[i] && !imu)) { rc = fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_feed_imu: imu / imu_off"); break; }
+        double last = f->imu_newest[id];
+        for (int64_t k = imu_off[i]; k < imu_off[i + 1]; k++) {
+            if (!std::isfinite(imu[k].t) || imu[k].t < last) { rc = fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_feed_imu: readings must be finite and in non-decreasing time"); break; }
+            last = imu[k].t;
+        }
+    }
+    for (int j = 0; j < marked; j++) s->mark[ids[j]] = 0;
+    if (rc != HNET_OK) return rc;
+    const int64_t base = imu_off[0], total = imu_off[n] - base;
+    if (total == 0) return HNET_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    const size_t o_rd = al256((size_t)n * sizeof(ImuFeedSeg)), bytes = o_rd + (size_t)total * sizeof(hnet_ekf::ImuData);
+    HIPCHK(c, hipEventSynchronize(f->ev_feed));                    // the pinned block's last upload has left it
+    if (f->feed_cap < bytes) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (f->pin_feed) HIPCHK(c, hipHostFree(f->pin_feed));
+        if (f->d_feed) HIPCHK(c, hipFree(f->d_feed));
+        f->pin_feed = f->d_feed = nullptr;
+        f->feed_cap = 0;
+        const size_t want = std::max(bytes, (size_t)1 << 16);
+        HIPCHK(c, hipHostMalloc((void**)&f->pin_feed, want, hipHostMallocDefault));
+        HIPCHK(c, hipMalloc((void**)&f->d_feed, want));
+        f->feed_cap = want;
+    }
+    static_assert(sizeof(hnet_imu) == sizeof(hnet_ekf::ImuData), "hnet_imu is hnet_ekf::ImuData");
+    ImuFeedSeg* seg = reinterpret_cast<ImuFeedSeg*>(f->pin_feed);
+    memcpy(f->pin_feed + o_rd, imu + base, (size_t)total * sizeof(hnet_imu));
+    std::vector<ImuRingMeta> next(n);
+    int longest = 0;
+    for (int i = 0; i < n; i++) {
+        const ImuRingMeta m = f->meta[ids[i]];
+        const int64_t have = imu_off[i + 1] - imu_off[i];
+        const int take = (int)std::min<int64_t>(have, f->cap);      // more than a ring's worth: only the newest `cap` can stay
+        const int count = std::min(f->cap, m.count + take);
+        const int head = (int)(((int64_t)m.head + m.count + take - count) % f->cap);
+        next[i] = ImuRingMeta{head, count};
+        seg[i] = ImuFeedSeg{ids[i], (int32_t)(imu_off[i] - base + (have - take)), take, (int32_t)(((int64_t)m.head + m.count) % f->cap), head, count};
+        longest = std::max(longest, take);
+    }
+    HIPCHK(c, hipMemcpyAsync(f->d_feed, f->pin_feed, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipEventRecord(f->ev_feed, c->stream));
+    HIPCHK(c, launch_imu_append(reinterpret_cast<const ImuFeedSeg*>(f->d_feed), n, longest, reinterpret_cast<const hnet_ekf::ImuData*>(f->d_feed + o_rd), (int)total,
+                                s->n, f->cap, f->d_ring, f->d_meta, c->stream));
+    for (int i = 0; i < n; i++) {
+        f->meta[ids[i]] = next[i];
+        if (imu_off[i + 1] > imu_off[i]) f->imu_newest[ids[i]] = imu[imu_off[i + 1] - 1].t;
+    }
+    return HNET_OK;
+}
+
+int hnet_filters_initialized(const hnet_filters* f, int id) { return (f && id >= 0 && id < f->s->n) ? (int)f->inited[id] : -1; }
+
+int hnet_filters_uninitialize(hnet_filters* f, int id) {
+    if (!f) return HNET_ERR_INVALID_ARG;
+    if (id < 0 || id >= f->s->n) return fail(f->s->ctx, HNET_ERR_INVALID_ARG, "hnet_filters_uninitialize: id out of range");
+    f->inited[id] = 0;
+    f->t_seen[id] = -INFINITY;
+    return hnet_sessions_reset(f->s, id);
+}
+
+int hnet_filters_advance(hnet_filters* f, int n, const int32_t* ids, hnet_filter_state* state_out, float* net_out, int32_t* updates, int32_t* status) {
+    if (!f) return HNET_ERR_INVALID_ARG;
+    hnet_sessions* s = f->s;
+    hnet_ctx* c = s->ctx;
+    if (!f->cap) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_advance: feed not enabled (hnet_filters_enable_feed)");
+    if (!status) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_advance: status");
+    int rc = sessions_check_ids(s, n, ids);
+    if (rc != HNET_OK) return rc;
+    auto t_begin = std::chrono::steady_clock::now();
+    const int I = f->iters, B = c->cfg.max_batch;
+    // what each listed session does (VioManager.cpp:122-162); the sessions that step come first on the device, the propagate-only ones behind them
+    std::vector<int> order;                                        // listed index of workgroup j
+    order.reserve(n);
+    for (int pass = 0; pass < 2; pass++)
+        for (int i = 0; i < n; i++) {
+            const int id = ids[i];
+            const hnet_sessions::Sess& e = s->st[id];
+            int st;
+            if (e.count < 1 || !(e.t_push > (f->inited[id] ? f->t[id] : f->t_seen[id]))) st = HNET_ADV_NO_FRAME;
+            else if (!(e.t_push < f->imu_newest[id] - f->cam_imu_dt[id])) st = HNET_ADV_WAIT_IMU;
+            else if (!f->inited[id]) st = HNET_ADV_WAIT_INIT;      // (INITIALIZED if the device's initialiser accepts)
+            else st = e.count < 2 ? HNET_ADV_PROPAGATED : HNET_ADV_STEPPED;
+            if (pass == 0) status[i] = st;
+            if ((pass == 0 && st == HNET_ADV_STEPPED) || (pass == 1 && (st == HNET_ADV_PROPAGATED || st == HNET_ADV_WAIT_INIT))) order.push_back(i);
+        }
+    const int n_a = (int)order.size();
+    int n_s = 0;
+    for (int i = 0; i < n; i++) n_s += status[i] == HNET_ADV_STEPPED;
+    if (net_out) memset(net_out, 0, (size_t)I * n * 72 * sizeof(float));
+    if (updates) memset(updates, 0, (size_t)n * sizeof(int32_t));
+    std::fill(f->last_slot.begin(), f->last_slot.end(), -1);
+    if (n_a == 0) return HNET_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    const AdvLayout L(n_a, I);
+    AdvanceJob* job = reinterpret_cast<AdvanceJob*>(f->pin_adv);
+    uint64_t* seq = reinterpret_cast<uint64_t*>(f->pin_adv + L.o_seq);
+    int32_t* gate = reinterpret_cast<int32_t*>(f->pin_adv + L.o_gate);
+    int32_t* hid = reinterpret_cast<int32_t*>(f->pin_adv + L.o_ids);
+    int32_t* pairs = reinterpret_cast<int32_t*>(f->pin_adv + L.o_pairs);
+    bool any_init = false;
+    for (int j = 0; j < n_a; j++) {
+        const int i = order[j], id = ids[i];
+        const hnet_sessions::Sess& e = s->st[id];
+        const bool init = status[i] == HNET_ADV_WAIT_INIT;
+        any_init |= init;
+        job[j] = AdvanceJob{e.t_push, f->cam_imu_dt[id], id, init ? 1 : 0, j >= n_s ? 1 : 0, 0};
+        for (int it = 0; it < I; it++) seq[(size_t)it * n_a + j] = e.seq + (uint64_t)it;
+        gate[j] = (j < n_s && e.t == e.t_push && e.count > 10) ? 1 : 0;             // VioManager.cpp:257
+        hid[j] = id;
+        sessions_pair(s, id, pairs + 2 * j);
+    }
+    const AdvanceJob* d_job = reinterpret_cast<const AdvanceJob*>(f->d_adv);
+    const uint64_t* d_seq = reinterpret_cast<const uint64_t*>(f->d_adv + L.o_seq);
+    const int32_t* d_gate = reinterpret_cast<const int32_t*>(f->d_adv + L.o_gate);
+    const int32_t* d_ids = reinterpret_cast<const int32_t*>(f->d_adv + L.o_ids);
+    const int32_t* d_pairs = reinterpret_cast<const int32_t*>(f->d_adv + L.o_pairs);
+    float* d_net = reinterpret_cast<float*>(f->d_out);
+    float* d_prior = reinterpret_cast<float*>(f->d_out + f->off_prior);
+    int32_t* d_upd = reinterpret_cast<int32_t*>(f->d_out + f->off_upd);
+    FilterRec* d_work = reinterpret_cast<FilterRec*>(f->d_out + f->off_work);
+    AdvanceResult* d_res = reinterpret_cast<AdvanceResult*>(f->d_out + f->off_res);
+    const float* h_net = reinterpret_cast<const float*>(f->pin_out);
+    const float* h_prior = reinterpret_cast<const float*>(f->pin_out + f->off_prior);
+    const AdvanceResult* h_res = reinterpret_cast<const AdvanceResult*>(f->pin_out + f->off_res);
+    hipStream_t st = c->stream;
+    auto enqueue = [&](uint32_t& flag_now) -> int {
+        HIPCHK(c, hipMemcpyAsync(f->d_adv, f->pin_adv, L.bytes, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemsetAsync(d_upd, 0, (size_t)n_a * sizeof(int32_t), st));
+        HIPCHK(c, hipEventRecord(f->ev0, st));
+        if (any_init)                                              // (the sessions without a state are among the propagate-only ones)
+            HIPCHK(c, launch_filter_init(d_job + n_s, n_a - n_s, s->n, f->cap, f->d_ring, f->d_meta, f->d_ip, f->d_params, d_work + n_s, d_res + n_s, st));
+        HIPCHK(c, launch_filter_select(d_job, n_a, s->n, f->cap, f->d_ring, f->d_meta, f->d_state, d_work, f->d_sel, d_res, st));
+        if (n_s) HIPCHK(c, launch_session_gather(s->ring, 2 * s->n, d_pairs, n_s, (uint8_t*)c->stage_prev, (uint8_t*)c->stage_curr, st));
+        HIPCHK(c, launch_filter_propagate_adv(d_job, n_a, s->n, f->cap, f->d_state, f->d_params, f->d_sel, d_res, d_work, st));
+        for (int it = 0; it < I && n_s; it++) {
+            float* pr_it = d_prior + (size_t)it * B * 8;
+            float* net_it = d_net + (size_t)it * B * 72;
+            HIPCHK(c, launch_filter_prior(d_work, n_s, pr_it, f->d_prior_cam, st));
+            const FwdArgs a{.prev = c->stage_prev, .curr = c->stage_curr, .prior = c->cfg.use_prior ? pr_it : nullptr, .batch = n_s, .mean = net_it, .cov = net_it + 8,
+                            .seq_tab = d_seq + (size_t)it * n_a, .mean_stride = HNET_PACKED_FLOATS, .cov_stride = HNET_PACKED_FLOATS};
+            const int r = forward(c, a, st);
+            if (r != HNET_OK) return r;
+            HIPCHK(c, launch_filter_update(d_ids, n_s, s->n, f->d_params, net_it, f->d_prior_cam, d_gate, it != I - 1, it == I - 1, d_work, d_upd, st));
+        }
+        HIPCHK(c, hipEventRecord(f->ev1, st));
+        if (n_s) HIPCHK(c, hipMemcpyAsync(f->pin_out, f->d_out, f->off_upd + (size_t)n_s * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        if (state_out) HIPCHK(c, hipMemcpyAsync(f->pin_out + f->off_work, d_work, (size_t)n_a * sizeof(FilterRec), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(f->pin_out + f->off_res, d_res, (size_t)n_a * sizeof(AdvanceResult), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(&flag_now, c->d_flag, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemsetAsync(c->d_flag, 0, 4, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        return HNET_OK;
+    };
+    auto overflowed = [&]() -> bool {                              // as hnet_filters_step, over the sessions that step
+        for (int it = 0; it < I && n_s; it++)
+            if (!all_finite(h_net + (size_t)it * B * 72, (size_t)n_s * 72)) return !c->cfg.use_prior || all_finite(h_prior + (size_t)it * B * 8, (size_t)n_s * 8);
+        return false;
+    };
+    if ((rc = run_host_call(c, enqueue, overflowed)) != HNET_OK) return rc;
+    // accepted: the states take the results (not those the initialiser refused), the bookkeeping advances
+    HIPCHK(c, launch_filter_scatter_ok(d_work, d_job, d_res, n_a, s->n, f->d_state, st));
+    const int32_t* h_upd = reinterpret_cast<const int32_t*>(f->pin_out + f->off_upd);
+    for (int j = 0; j < n_a; j++) {
+        const int i = order[j], id = ids[i];
+        hnet_sessions::Sess& e = s->st[id];
+        f->last_slot[id] = j;
+        if (status[i] == HNET_ADV_WAIT_INIT) {
+            if (!h_res[j].ok) {                                    // the frame is dropped: the session starts over (VioManager.cpp:158-162)
+                f->t_seen[id] = e.t_push;
+                e.count = 0;
+                e.curr = 0;
+                e.t = -1.0;
+                continue;
+            }
+            status[i] = HNET_ADV_INITIALIZED;
+            f->inited[id] = 1;
+            f->t[id] = h_res[j].time0 > e.t_push ? h_res[j].time0 : e.t_push;
+            e.count = 1;                                           // this frame is the session's first image; its ring slot stays the current one
+            e.t = -1.0;
+        } else {
+            f->t[id] = e.t_push;
+            if (j < n_s) {
+                e.seq += (uint64_t)I;
+                if (updates) updates[i] = h_upd[j];
+                if (net_out)
+                    for (int it = 0; it < I; it++) memcpy(net_out + ((size_t)it * n + i) * 72, h_net + ((size_t)it * B + j) * 72, 72 * sizeof(float));
+            }
+        }
+        if (state_out) memcpy(state_out + i, f->pin_out + f->off_work + (size_t)j * sizeof(FilterRec), sizeof(FilterRec));
+    }
+    f->last_n = n_s;
+    float ms = 0;
+    HIPCHK(c, hipEventElapsedTime(&ms, f->ev0, f->ev1));
+    record_timing(f->timing, ms, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(), n_s ? I : 0, true);
+    return HNET_OK;
+}
+
+int hnet_filters_last_selection(hnet_filters* f, int id, hnet_imu* out, int cap, int* count) {
+    if (!f) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = f->s->ctx;
+    if (!f->cap) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_last_selection: feed not enabled");
+    if (!count || id < 0 || id >= f->s->n || cap < 0 || (cap > 0 && !out)) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_last_selection: id / out / count");
+    *count = 0;
+    const int j = f->last_slot[id];
+    if (j < 0) return HNET_OK;
+    const AdvanceResult* h_res = reinterpret_cast<const AdvanceResult*>(f->pin_out + f->off_res);
+    const int m = h_res[j].ok ? h_res[j].n_sel : 0;
+    if (m < 0 || m > f->cap + 2) return fail(c, HNET_ERR_DEVICE, "hnet_filters_last_selection: selection count out of range");
+    *count = m;
+    const int k = std::min(m, cap);
+    if (k > 0) {
+        HIPCHK(c, hipSetDevice(c->cfg.device_id));
+        HIPCHK(c, hipMemcpyAsync(out, f->d_sel + (size_t)j * 2 * (f->cap + 2) + (f->cap + 2), (size_t)k * sizeof(hnet_imu), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
     return HNET_OK;
 }
 

@@ -42,5 +42,35 @@ hipError_t launch_filter_update(const int32_t* ids, int n, int n_sessions, const
                                 const int32_t* gate, int update_offset, int last, FilterRec* work, int32_t* updates, hipStream_t s);
 hipError_t launch_filter_scatter(const FilterRec* work, const int32_t* ids, int n, int n_sessions, FilterRec* state, hipStream_t s);
 
+
+// ---- the IMU feed (hnet_filters_enable_feed .. hnet_filters_advance).  Per session a ring of `cap` readings, ring[id * cap + (head + j) % cap] the
+// j-th oldest of `count`; head / count live in ImuRingMeta on the device (the kernels read them) and are mirrored on the host (it computes them).
+struct ImuRingMeta { int32_t head, count; };
+// one session's segment of a feed call: readings fed[src0 .. src0 + n) go to ring positions (wpos + k) % cap; the ring's head / count afterwards
+struct ImuFeedSeg { int32_t id, src0, n, wpos, head, count; };
+// the initialiser's settings per session (hnet_init_params)
+struct InitParams { double window_time, imu_thresh, init_height; int32_t wait_for_jerk, pad; };
+// what hnet_filters_advance asks for one listed session (one workgroup of the init / select / propagate kernels each)
+struct AdvanceJob {
+    double t_frame, cam_imu_dt;
+    int32_t id;
+    int32_t init;                      // 1: the state comes from the initialiser in this call (work[b], when ok[b]); 0: from state[id]
+    int32_t reset;                     // 1: State::reset_4pt_offset after the propagation (a session that takes no part in the forwards)
+    int32_t pad;
+};
+// per listed session, written by the kernels: ok (init == 0: 1; init == 1: the initialiser's decision), the readings selected, the initialiser's time0
+struct AdvanceResult { double time0; int32_t ok, n_sel; };
+
+hipError_t launch_imu_append(const ImuFeedSeg* seg, int n_seg, int max_seg_len, const hnet_ekf::ImuData* fed, int n_fed, int n_sessions, int cap,
+                             hnet_ekf::ImuData* ring, ImuRingMeta* meta, hipStream_t s);
+hipError_t launch_filter_init(const AdvanceJob* job, int n, int n_sessions, int cap, const hnet_ekf::ImuData* ring, const ImuRingMeta* meta,
+                              const InitParams* ip, const FilterParams* params, FilterRec* work, AdvanceResult* res, hipStream_t s);
+// sel: [n][2 * (cap + 2)] readings (the span copied out of the ring, then the selected readings behind it)
+hipError_t launch_filter_select(const AdvanceJob* job, int n, int n_sessions, int cap, const hnet_ekf::ImuData* ring, const ImuRingMeta* meta,
+                                const FilterRec* state, const FilterRec* work, hnet_ekf::ImuData* sel, AdvanceResult* res, hipStream_t s);
+hipError_t launch_filter_propagate_adv(const AdvanceJob* job, int n, int n_sessions, int cap, const FilterRec* state, const FilterParams* params,
+                                       const hnet_ekf::ImuData* sel, const AdvanceResult* res, FilterRec* work, hipStream_t s);
+hipError_t launch_filter_scatter_ok(const FilterRec* work, const AdvanceJob* job, const AdvanceResult* res, int n, int n_sessions, FilterRec* state, hipStream_t s);
+
 }  // namespace hnet
 #endif  // HNET_FILTERS_DEV_H

@@ -28,21 +28,39 @@ __device__ inline void store_rec(FilterRec& dst, const FilterRec& src) {
 __device__ inline int sel(int j) { return 15 + 3 * (j >> 1) + (j & 1); }
 }  // namespace
 
-// IMU propagation of session ids[b] over its selected readings rd[rd_off[b] .. rd_off[b + 1]) (hnet_ekf::propagate_with_imu's loop):
-// per interval the corrected inputs with the current biases, the Jacobians and the mean on lane 0, then P <- F P F^T + Fw diag(q) Fw^T
-// by all lanes.  The result goes to work[b] with time t_frame[b].
+// IMU propagation of one listed session per workgroup over its selected readings (hnet_ekf::propagate_with_imu's loop): per interval the corrected
+// inputs with the current biases, the Jacobians and the mean on lane 0, then P <- F P F^T + Fw diag(q) Fw^T by all lanes.  The result goes to work[b].
+// ADV = false (hnet_filters_step): session ids[b], readings rd[rd_off[b] .. rd_off[b + 1]) selected on the host, time t_frame[b].
+// ADV = true (hnet_filters_advance): session job[b].id, readings rd + b * 2 * (cap + 2) + (cap + 2) .. + res[b].n_sel from filter_select_kernel; the state
+// comes from state[id] or, after the initialiser, from work[b]; a session the initialiser refused is skipped, one initialised after its frame keeps the
+// initial state; job.reset: State::reset_4pt_offset afterwards (a session with fewer than two images: no forward follows).
+template <bool ADV>
 __global__ __launch_bounds__(FILTER_THREADS) void filter_propagate_kernel(const int32_t* __restrict__ ids, int n_sessions, const FilterRec* __restrict__ state,
                                                                           const FilterParams* __restrict__ params, const hnet_ekf::ImuData* __restrict__ rd,
                                                                           const int32_t* __restrict__ rd_off, const double* __restrict__ t_frame,
-                                                                          FilterRec* __restrict__ work) {
+                                                                          FilterRec* work, const AdvanceJob* __restrict__ job, int cap,
+                                                                          const AdvanceResult* __restrict__ res) {
     __shared__ FilterRec S;
     __shared__ double F[NE], Fw[NS * NW], T[NE];
-    const int b = blockIdx.x, id = ids[b];
+    const int b = blockIdx.x, id = ADV ? job[b].id : ids[b];
     if (id < 0 || id >= n_sessions) return;                   // (host-validated)
     const FilterParams& pr = params[id];
-    load_rec(S, state[id]);
-    const int k0 = rd_off[b], k1 = rd_off[b + 1];
+    int k0, k1;
+    if constexpr (ADV) {
+        const AdvanceResult r = res[b];
+        if (job[b].init && !r.ok) return;                      // (uniform over the workgroup, as the returns below)
+        if (r.n_sel < 0 || r.n_sel > cap + 2) return;
+        load_rec(S, job[b].init ? work[b] : state[id]);
+        k0 = 0;
+        k1 = r.n_sel;
+        rd += (size_t)b * 2 * (cap + 2) + (cap + 2);
+    } else {
+        load_rec(S, state[id]);
+        k0 = rd_off[b], k1 = rd_off[b + 1];
+    }
     __syncthreads();
+    if constexpr (ADV)
+        if (job[b].init && S.t > job[b].t_frame) return;       // VioManager.cpp:203-206: work[b] holds the initial state
     for (int k = k0; k + 1 < k1; k++) {
         if (threadIdx.x == 0) {
             double w_hat[3], a_hat[3];
@@ -74,7 +92,14 @@ __global__ __launch_bounds__(FILTER_THREADS) void filter_propagate_kernel(const 
         }
         __syncthreads();
     }
-    if (threadIdx.x == 0) S.t = t_frame[b];
+    if constexpr (ADV) {
+        if (job[b].reset) {                                    // hnet_ekf::reset_4pt_offset
+            for (int e = threadIdx.x; e < NE; e += FILTER_THREADS)
+                if (e / NS >= 15 || e % NS >= 15) S.s.cov[e] = 0.0;
+            if (threadIdx.x < 12) (&S.s.offset[0][0])[threadIdx.x] = 0.0;
+        }
+    }
+    if (threadIdx.x == 0) S.t = ADV ? job[b].t_frame : t_frame[b];
     __syncthreads();
     store_rec(work[b], S);
 }
@@ -204,10 +229,191 @@ __global__ __launch_bounds__(FILTER_THREADS) void filter_scatter_kernel(const Fi
     store_rec(state[id], work[b]);
 }
 
+// ---- the IMU feed and the cold start (hnet_filters_feed_imu / hnet_filters_advance) ----
+
+namespace {
+__device__ inline const hnet_ekf::ImuData& ring_at(const hnet_ekf::ImuData* rg, int head, int cap, int j) { return rg[(head + j) % cap]; }
+// a session's ring is usable when its meta is consistent (the host wrote it; checked again because the kernels index with it)
+__device__ inline bool ring_ok(const ImuRingMeta& m, int cap) { return m.head >= 0 && m.head < cap && m.count >= 0 && m.count <= cap; }
+}  // namespace
+
+// feed: segment blockIdx.y's readings fed[src0 .. src0 + n) -> ring positions (wpos + k) % cap of session id; one lane records the ring's new head / count
+__global__ __launch_bounds__(256) void imu_append_kernel(const ImuFeedSeg* __restrict__ seg, int n_fed, const hnet_ekf::ImuData* __restrict__ fed, int n_sessions,
+                                                         int cap, hnet_ekf::ImuData* __restrict__ ring, ImuRingMeta* __restrict__ meta) {
+    const ImuFeedSeg g = seg[blockIdx.y];
+    if (g.id < 0 || g.id >= n_sessions || g.n < 0 || g.n > cap || g.wpos < 0 || g.wpos >= cap || g.src0 < 0 || g.src0 + g.n > n_fed) return;   // (host-validated)
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k < g.n) ring[(size_t)g.id * cap + (g.wpos + k) % cap] = fed[g.src0 + k];
+    if (k == 0 && g.head >= 0 && g.head < cap && g.count >= 0 && g.count <= cap) meta[g.id] = ImuRingMeta{g.head, g.count};
+}
+
+// The initialiser (hnet_ekf::initialize_with_imu + initialize_cov) for the listed sessions with job.init, one workgroup each, on the ring's readings
+// not older than three windows behind the newest (hnet_ekf::trim_imu_init).  The window sums are reductions: every lane adds its readings (every
+// 256th, in time order), then a fixed tree over the lanes; the decision and the mean come from the header's init_decide / init_from_stats on lane 0.
+// Accepted: work[b] = {time0, mean, zero offsets, initialize_cov}, res[b] = {time0, ok 1}; refused: res[b].ok = 0 and work[b] is not written.
+__global__ __launch_bounds__(FILTER_THREADS) void filter_init_kernel(const AdvanceJob* __restrict__ job, int n_sessions, int cap, const hnet_ekf::ImuData* __restrict__ ring,
+                                                                     const ImuRingMeta* __restrict__ meta, const InitParams* __restrict__ ip,
+                                                                     const FilterParams* __restrict__ params, FilterRec* __restrict__ work,
+                                                                     AdvanceResult* __restrict__ res) {
+    __shared__ FilterRec S;
+    __shared__ double red[9][FILTER_THREADS];
+    __shared__ int cnt[4];
+    const int b = blockIdx.x, t = threadIdx.x;
+    const AdvanceJob jb = job[b];
+    if (!jb.init) return;
+    const int id = jb.id;
+    if (id < 0 || id >= n_sessions) return;
+    const ImuRingMeta m = meta[id];
+    const hnet_ekf::ImuData* rg = ring + (size_t)id * cap;
+    const InitParams P = ip[id];
+    const double w = P.window_time;
+    bool refuse = !ring_ok(m, cap) || m.count < 2;                          // (uniform over the workgroup, as every test below)
+    double newest = 0.0;
+    int c3 = 0;
+    if (!refuse) {
+        newest = ring_at(rg, m.head, cap, m.count - 1).t;
+        if (t < 4) cnt[t] = 0;
+        __syncthreads();
+        int c = 0;
+        for (int j = t; j < m.count; j += FILTER_THREADS) c += ring_at(rg, m.head, cap, j).t < newest - 3 * w ? 1 : 0;   // trim_imu_init (time order: a prefix)
+        if (c) atomicAdd(&cnt[0], c);
+        __syncthreads();
+        c3 = cnt[0];
+        refuse = m.count - c3 < 2 || newest - ring_at(rg, m.head, cap, c3).t < 2 * w;
+    }
+    int n1 = 0, n2 = 0, last2 = -1;
+    double avg[9];                                                           // a_avg_1to0, a_avg_2to1, w_avg_2to1
+    if (!refuse) {
+        double a[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+        int c1 = 0, c2 = 0, l2 = -1;
+        for (int j = c3 + t; j < m.count; j += FILTER_THREADS) {
+            const hnet_ekf::ImuData& d = ring_at(rg, m.head, cap, j);
+            if (d.t > newest - 1 * w && d.t <= newest - 0 * w) {
+                for (int i = 0; i < 3; i++) a[i] += d.am[i];
+                c1++;
+            }
+            if (d.t > newest - 2 * w && d.t <= newest - 1 * w) {
+                for (int i = 0; i < 3; i++) { a[3 + i] += d.am[i]; a[6 + i] += d.wm[i]; }
+                c2++;
+                l2 = j;
+            }
+        }
+        for (int i = 0; i < 9; i++) red[i][t] = a[i];
+        if (c1) atomicAdd(&cnt[1], c1);
+        if (c2) atomicAdd(&cnt[2], c2);
+        if (l2 >= 0) atomicMax(&cnt[3], l2 + 1);
+        __syncthreads();
+        for (int st = FILTER_THREADS / 2; st > 0; st >>= 1) {
+            if (t < st)
+                for (int i = 0; i < 9; i++) red[i][t] += red[i][t + st];
+            __syncthreads();
+        }
+        n1 = cnt[1]; n2 = cnt[2]; last2 = cnt[3] - 1;
+        refuse = n1 == 0 || n2 == 0;
+        if (!refuse) {
+            for (int i = 0; i < 3; i++) { avg[i] = red[i][0] / n1; avg[3 + i] = red[3 + i][0] / n2; avg[6 + i] = red[6 + i][0] / n2; }
+        }
+        __syncthreads();
+    }
+    if (!refuse) {
+        double v1 = 0.0, v2 = 0.0;
+        for (int j = c3 + t; j < m.count; j += FILTER_THREADS) {
+            const hnet_ekf::ImuData& d = ring_at(rg, m.head, cap, j);
+            if (d.t > newest - 1 * w && d.t <= newest - 0 * w) {
+                const double e[3] = {d.am[0] - avg[0], d.am[1] - avg[1], d.am[2] - avg[2]};
+                v1 += hnet_ekf::m3::dot(e, e);
+            }
+            if (d.t > newest - 2 * w && d.t <= newest - 1 * w) {
+                const double e[3] = {d.am[0] - avg[3], d.am[1] - avg[4], d.am[2] - avg[5]};
+                v2 += hnet_ekf::m3::dot(e, e);
+            }
+        }
+        red[0][t] = v1;
+        red[1][t] = v2;
+        __syncthreads();
+        for (int st = FILTER_THREADS / 2; st > 0; st >>= 1) {
+            if (t < st) { red[0][t] += red[0][t + st]; red[1][t] += red[1][t + st]; }
+            __syncthreads();
+        }
+        const double d1 = sqrt(red[0][0] / (n1 - 1)), d2 = sqrt(red[1][0] / (n2 - 1));        // (one reading: 0 / 0 = NaN, hnet_ekf::init_decide)
+        refuse = !hnet_ekf::init_decide(d1, d2, P.imu_thresh, P.wait_for_jerk != 0);
+    }
+    if (refuse) {
+        if (t == 0) res[b] = AdvanceResult{0.0, 0, 0};
+        return;
+    }
+    double* sd = reinterpret_cast<double*>(&S);
+    for (int i = t; i < FILTER_REC_DOUBLES; i += FILTER_THREADS) sd[i] = 0.0;        // a new State: zero offsets, zero covariance (State.cpp:79)
+    __syncthreads();
+    if (t == 0) {
+        hnet_ekf::init_from_stats(avg + 3, avg + 6, P.init_height, params[id].gravity_mag, S.s);
+        hnet_ekf::initialize_cov(S.s);
+        S.t = ring_at(rg, m.head, cap, last2).t;
+        res[b] = AdvanceResult{S.t, 1, 0};
+    }
+    __syncthreads();
+    store_rec(work[b], S);
+}
+
+// Selection (hnet_ekf::select_imu_readings) for the listed sessions straight from the ring, one workgroup each: window [state t, t_frame] + cam_imu_dt,
+// the state's time read from state[id] (work[b] after the initialiser).  All lanes count the readings more than 10 s behind the newest (never used:
+// hnet_ekf::trim_imu_prop), those before the window's start and those up to its end; hnet_ekf::select_span turns the counts into the span the
+// header's loop can touch; the span is copied out of the ring (it may wrap) and lane 0 runs the header's function on it.
+// sel + b * 2 * (cap + 2): the span [cap + 2], then the selected readings [cap + 2]; res[b].n_sel their number.
+__global__ __launch_bounds__(FILTER_THREADS) void filter_select_kernel(const AdvanceJob* __restrict__ job, int n_sessions, int cap, const hnet_ekf::ImuData* __restrict__ ring,
+                                                                       const ImuRingMeta* __restrict__ meta, const FilterRec* __restrict__ state,
+                                                                       const FilterRec* __restrict__ work, hnet_ekf::ImuData* __restrict__ sel,
+                                                                       AdvanceResult* __restrict__ res) {
+    __shared__ int cnt[3];
+    const int b = blockIdx.x, t = threadIdx.x;
+    const AdvanceJob jb = job[b];
+    const int id = jb.id;
+    if (id < 0 || id >= n_sessions) return;
+    if (jb.init && !res[b].ok) return;                                       // refused by the initialiser (n_sel is 0 already)
+    if (!jb.init && t == 0) { res[b].time0 = 0.0; res[b].ok = 1; res[b].n_sel = 0; }
+    const double t_state = jb.init ? work[b].t : state[id].t;
+    if (!(jb.t_frame > t_state)) return;                                     // initialised later than this frame (VioManager.cpp:203-206) or at it: nothing to select
+    const ImuRingMeta m = meta[id];
+    if (!ring_ok(m, cap) || m.count < 1) return;
+    const hnet_ekf::ImuData* rg = ring + (size_t)id * cap;
+    const double t0 = t_state + jb.cam_imu_dt, t1 = jb.t_frame + jb.cam_imu_dt;
+    const double newest = ring_at(rg, m.head, cap, m.count - 1).t;
+    if (t < 3) cnt[t] = 0;
+    __syncthreads();
+    int c_old = 0, c_lt = 0, c_le = 0;
+    for (int j = t; j < m.count; j += FILTER_THREADS) {
+        const double tt = ring_at(rg, m.head, cap, j).t;
+        if (newest - tt > 10) c_old++;
+        else { c_lt += tt < t0 ? 1 : 0; c_le += tt <= t1 ? 1 : 0; }
+    }
+    if (c_old) atomicAdd(&cnt[0], c_old);
+    if (c_lt) atomicAdd(&cnt[1], c_lt);
+    if (c_le) atomicAdd(&cnt[2], c_le);
+    __syncthreads();
+    int first = 0;
+    const int n_u = m.count - cnt[0];
+    const int len = hnet_ekf::select_span(n_u, cnt[1], cnt[2], &first);
+    if (len < 1 || len > cap || first < 0 || cnt[0] + first + len > m.count) return;
+    hnet_ekf::ImuData* lin = sel + (size_t)b * 2 * (cap + 2);
+    hnet_ekf::ImuData* out = lin + (cap + 2);
+    for (int k = t; k < len; k += FILTER_THREADS) lin[k] = ring_at(rg, m.head, cap, cnt[0] + first + k);
+    __syncthreads();
+    if (t == 0) res[b].n_sel = hnet_ekf::select_imu_readings(lin, len, t0, t1, out);          // writes at most len + 2 readings
+}
+
+// filter_scatter_kernel for hnet_filters_advance: work[b] -> state[id] unless the initialiser refused the session
+__global__ __launch_bounds__(FILTER_THREADS) void filter_scatter_ok_kernel(const FilterRec* __restrict__ work, const AdvanceJob* __restrict__ job,
+                                                                           const AdvanceResult* __restrict__ res, int n_sessions, FilterRec* __restrict__ state) {
+    const int b = blockIdx.x, id = job[b].id;
+    if (id < 0 || id >= n_sessions || !res[b].ok) return;
+    store_rec(state[id], work[b]);
+}
+
 hipError_t launch_filter_propagate(const int32_t* ids, int n, int n_sessions, const FilterRec* state, const FilterParams* params, const hnet_ekf::ImuData* rd,
                                    const int32_t* rd_off, const double* t_frame, FilterRec* work, hipStream_t s) {
     if (n < 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(filter_propagate_kernel, dim3((unsigned)n), dim3(FILTER_THREADS), 0, s, ids, n_sessions, state, params, rd, rd_off, t_frame, work);
+    hipLaunchKernelGGL(filter_propagate_kernel<false>, dim3((unsigned)n), dim3(FILTER_THREADS), 0, s, ids, n_sessions, state, params, rd, rd_off, t_frame, work,
+                       (const AdvanceJob*)nullptr, 0, (const AdvanceResult*)nullptr);
     return hipGetLastError();
 }
 
@@ -228,6 +434,41 @@ hipError_t launch_filter_update(const int32_t* ids, int n, int n_sessions, const
 hipError_t launch_filter_scatter(const FilterRec* work, const int32_t* ids, int n, int n_sessions, FilterRec* state, hipStream_t s) {
     if (n < 1) return hipErrorInvalidValue;
     hipLaunchKernelGGL(filter_scatter_kernel, dim3((unsigned)n), dim3(FILTER_THREADS), 0, s, work, ids, n_sessions, state);
+    return hipGetLastError();
+}
+
+hipError_t launch_imu_append(const ImuFeedSeg* seg, int n_seg, int max_seg_len, const hnet_ekf::ImuData* fed, int n_fed, int n_sessions, int cap,
+                             hnet_ekf::ImuData* ring, ImuRingMeta* meta, hipStream_t s) {
+    if (n_seg < 1 || n_seg > 65535 || max_seg_len < 1 || cap < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(imu_append_kernel, dim3((unsigned)((max_seg_len + 255) / 256), (unsigned)n_seg), dim3(256), 0, s, seg, n_fed, fed, n_sessions, cap, ring, meta);
+    return hipGetLastError();
+}
+
+hipError_t launch_filter_init(const AdvanceJob* job, int n, int n_sessions, int cap, const hnet_ekf::ImuData* ring, const ImuRingMeta* meta, const InitParams* ip,
+                              const FilterParams* params, FilterRec* work, AdvanceResult* res, hipStream_t s) {
+    if (n < 1 || cap < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(filter_init_kernel, dim3((unsigned)n), dim3(FILTER_THREADS), 0, s, job, n_sessions, cap, ring, meta, ip, params, work, res);
+    return hipGetLastError();
+}
+
+hipError_t launch_filter_select(const AdvanceJob* job, int n, int n_sessions, int cap, const hnet_ekf::ImuData* ring, const ImuRingMeta* meta,
+                                const FilterRec* state, const FilterRec* work, hnet_ekf::ImuData* sel, AdvanceResult* res, hipStream_t s) {
+    if (n < 1 || cap < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(filter_select_kernel, dim3((unsigned)n), dim3(FILTER_THREADS), 0, s, job, n_sessions, cap, ring, meta, state, work, sel, res);
+    return hipGetLastError();
+}
+
+hipError_t launch_filter_propagate_adv(const AdvanceJob* job, int n, int n_sessions, int cap, const FilterRec* state, const FilterParams* params,
+                                       const hnet_ekf::ImuData* sel, const AdvanceResult* res, FilterRec* work, hipStream_t s) {
+    if (n < 1 || cap < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(filter_propagate_kernel<true>, dim3((unsigned)n), dim3(FILTER_THREADS), 0, s, (const int32_t*)nullptr, n_sessions, state, params, sel,
+                       (const int32_t*)nullptr, (const double*)nullptr, work, job, cap, res);
+    return hipGetLastError();
+}
+
+hipError_t launch_filter_scatter_ok(const FilterRec* work, const AdvanceJob* job, const AdvanceResult* res, int n, int n_sessions, FilterRec* state, hipStream_t s) {
+    if (n < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(filter_scatter_ok_kernel, dim3((unsigned)n), dim3(FILTER_THREADS), 0, s, work, job, res, n_sessions, state);
     return hipGetLastError();
 }
 

@@ -578,6 +578,59 @@ class HnetFilters:
                                               net.ctypes.data, upd.ctypes.data))
         return states, net, upd
 
+    # ---- the fed interface: device IMU rings, the static initialiser, one call that advances every camera that is ready ----
+    @staticmethod
+    def default_init_params():
+        p = _capi.InitParams()
+        _capi.lib().hnet_filter_default_init_params(C.byref(p))
+        return p
+
+    def enable_feed(self, imu_capacity):
+        """allocates one device ring of imu_capacity readings per session (once)"""
+        self._check(self._L.hnet_filters_enable_feed(self._f, int(imu_capacity)))
+
+    def set_init_params(self, id, params):
+        self._check(self._L.hnet_filters_set_init_params(self._f, int(id), C.byref(params)))
+
+    def feed_imu(self, ids, imu):
+        """ids [n]; imu: n arrays of IMU_DTYPE readings, each in non-decreasing time and not older than what the session was fed before.
+        One upload, one kernel, no synchronisation."""
+        ids = np.ascontiguousarray(np.atleast_1d(ids), dtype=np.int32)
+        if len(imu) != len(ids):
+            raise ValueError("one IMU array per session")
+        parts = [np.asarray(r, dtype=_capi.IMU_DTYPE).reshape(-1) for r in imu]
+        off = np.zeros(len(ids) + 1, np.int64)
+        off[1:] = np.cumsum([len(r) for r in parts])
+        rd = np.ascontiguousarray(np.concatenate(parts) if off[-1] else np.zeros(1, _capi.IMU_DTYPE))
+        self._check(self._L.hnet_filters_feed_imu(self._f, len(ids), ids.ctypes.data, rd.ctypes.data, off.ctypes.data))
+
+    def initialized(self, id):
+        return self._L.hnet_filters_initialized(self._f, int(id)) == 1
+
+    def uninitialize(self, id):
+        self._check(self._L.hnet_filters_uninitialize(self._f, int(id)))
+
+    def advance(self, ids):
+        """track_image_and_update for the listed sessions, on each one's latest pushed frame, with one synchronisation.
+        -> (states [n] FILTER_STATE_DTYPE (rows of sessions that did not move stay zero), net [iters, n, 72] float32 (rows of STEPPED sessions),
+            updates [n] int32, status [n] int32 of _capi.ADV_*)"""
+        ids = np.ascontiguousarray(np.atleast_1d(ids), dtype=np.int32)
+        n = len(ids)
+        states = np.zeros(n, _capi.FILTER_STATE_DTYPE)
+        net = np.zeros((self.iters, n, 72), np.float32)
+        upd = np.zeros(n, np.int32)
+        status = np.zeros(n, np.int32)
+        self._check(self._L.hnet_filters_advance(self._f, n, ids.ctypes.data, states.ctypes.data, net.ctypes.data, upd.ctypes.data, status.ctypes.data))
+        return states, net, upd, status
+
+    def last_selection(self, id):
+        """the readings the last advance selected for session id (IMU_DTYPE), as hnet_ekf::select_imu_readings writes them"""
+        cnt = C.c_int(0)
+        self._check(self._L.hnet_filters_last_selection(self._f, int(id), None, 0, C.byref(cnt)))
+        out = np.zeros(max(cnt.value, 1), _capi.IMU_DTYPE)
+        self._check(self._L.hnet_filters_last_selection(self._f, int(id), out.ctypes.data, cnt.value, C.byref(cnt)))
+        return out[:cnt.value]
+
     def last_priors(self, n):
         """the fp32 priors [iters, n, 8] the forwards of the last step (of n sessions; another n is refused) read"""
         out = np.zeros((self.iters, int(n), 8), np.float32)

@@ -358,6 +358,49 @@ int  hnet_filters_step(hnet_filters* f, int n, const int32_t* ids, const double*
 int  hnet_filters_last_priors(const hnet_filters* f, int n, float* out);
 int  hnet_filters_last_timing(const hnet_filters* f, hnet_timing* out);   /* last step: device ms (upload end .. last update), host ms; steps so far */
 
+/* ---- filters, fed: device IMU rings, the static initialiser, one call that advances every camera that is ready ----------------------------
+ * The front half of VioManager for the filters above: readings are handed over once (feed_measurement_imu), kept in a device ring per session, and
+ * hnet_filters_advance is track_image_and_update (VioManager.cpp:155-275) for the listed sessions with ONE host synchronisation: the window selection
+ * (Propagator.cpp:81-175), the initialiser (InertialInitializer.cpp:163-279 + StateHelper.cpp:35-61; hnet_ekf::initialize_with_imu / initialize_cov) and
+ * the propagation run on the device, the forwards of the sessions that step run as one batch.  hnet_filters_step stays usable next to these calls and
+ * ignores the rings.
+ * Per listed session, t_frame is the stamp of its latest hnet_sessions_push[_raw] (a push without stamps leaves it without a frame):
+ *   HNET_ADV_NO_FRAME     no frame newer than the state's time (or than the last frame the initialiser dropped).  Nothing changes.
+ *   HNET_ADV_WAIT_IMU     no reading newer than the frame yet: newest reading's t - cam_imu_dt <= t_frame (VioManager.cpp:148-149).  Nothing changes.
+ *   HNET_ADV_WAIT_INIT    not initialised and the initialiser refuses the ring's readings.  The frame is dropped (the reference returns before
+ *                         load_current_img, :158-162): the session's image count restarts at 0, the filter's state is untouched.
+ *   HNET_ADV_INITIALIZED  the initialiser accepted: state = time0 / the initial mean / initialize_cov, this frame is image 1 of the session, and the
+ *                         state is propagated from time0 to t_frame with the offsets reset (no forward).  time0 is an IMU-clock time that the
+ *                         reference uses as the state's camera-clock time (:341); so do we.  If time0 > t_frame the frame is out of order
+ *                         (:203-206): the state stays at time0 and later frames up to time0 report NO_FRAME.
+ *   HNET_ADV_PROPAGATED   initialised, fewer than two images: propagated, offsets reset, no forward (HomographyNet.cpp:155-158; the mask sequence
+ *                         number does not advance).
+ *   HNET_ADV_STEPPED      what hnet_filters_step does for this session with the host-selected window, gate and repeats included.
+ * Readings more than 10 s behind a ring's newest are never used (Propagator.h:110-124), whatever the capacity; the initialiser reads those not older
+ * than three windows behind the newest (InertialInitializer.cpp:28-38).  A window that reaches further back than the ring is propagated with what is there.
+ * Errors (a bad or repeated id, n > max_batch, feed not enabled, unordered readings) change no state. */
+typedef struct hnet_init_params { double window_time, imu_thresh, init_height; int32_t wait_for_jerk; } hnet_init_params;
+/* defaults: uzhfpv.launch:18-19,66 (init_window_time 1.0, init_imu_thresh 0.5, init_height 0.1), wait_for_jerk 1 (VioManager.cpp:322) */
+void hnet_filter_default_init_params(hnet_init_params* p);
+/* allocates the rings, imu_capacity readings (56 bytes) per session, 2 .. 1 << 20; once per filters object (HNET_ERR_INVALID_ARG on a second call) */
+int  hnet_filters_enable_feed(hnet_filters* f, int imu_capacity);
+int  hnet_filters_set_init_params(hnet_filters* f, int id, const hnet_init_params* p);
+/* readings imu[imu_off[i] .. imu_off[i + 1]) for session ids[i] (n distinct sessions, any number of them), appended to its ring by one kernel from one
+ * upload; no synchronisation.  Times must be finite and not decrease, within the call and against the ring's newest reading (HNET_ERR_INVALID_ARG,
+ * nothing appended for any session).  A full ring drops its oldest readings. */
+int  hnet_filters_feed_imu(hnet_filters* f, int n, const int32_t* ids, const hnet_imu* imu, const int64_t* imu_off);
+int  hnet_filters_initialized(const hnet_filters* f, int id);             /* 1 after set_state or a successful initialisation, 0 before, -1 for a bad id */
+/* camera restarted: the next advance initialises again from the ring; the session's image count restarts (hnet_sessions_reset), the state stays readable */
+int  hnet_filters_uninitialize(hnet_filters* f, int id);
+enum { HNET_ADV_STEPPED = 0, HNET_ADV_WAIT_IMU = 1, HNET_ADV_WAIT_INIT = 2, HNET_ADV_INITIALIZED = 3, HNET_ADV_PROPAGATED = 4, HNET_ADV_NO_FRAME = 5 };
+/* status [n] is required.  state_out [n] (written for STEPPED / PROPAGATED / INITIALIZED sessions), net_out [max_iekf_iteration][n][72] (rows of STEPPED
+ * sessions; the others are zero) and updates [n] (as hnet_filters_step; 0 unless STEPPED) may be NULL.  hnet_filters_last_priors afterwards describes the
+ * STEPPED sessions, in the order listed. */
+int  hnet_filters_advance(hnet_filters* f, int n, const int32_t* ids, hnet_filter_state* state_out, float* net_out, int32_t* updates, int32_t* status);
+/* the readings the last advance selected for session id, as hnet_ekf::select_imu_readings writes them: up to cap entries to out, their number to count
+ * (0 for a session that advance did not propagate) (tests) */
+int  hnet_filters_last_selection(hnet_filters* f, int id, hnet_imu* out, int cap, int* count);
+
 int hnet_synchronize(hnet_ctx* ctx, void* stream);
 int hnet_last_timing(const hnet_ctx* ctx, hnet_timing* out);
 

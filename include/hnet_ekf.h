@@ -543,5 +543,154 @@ inline int propagate_with_imu(State& s, const Extrinsics& e, double t_state, dou
     return done;
 }
 
+/* ---- initialisation from a standing start: what VioManager::try_to_initialize (VioManager.cpp:312-363) does with the buffered IMU
+ * readings: InertialInitializer::initialize_with_imu_CUAHN (ov_core/src/init/InertialInitializer.cpp:163-279) for the mean and
+ * StateHelper::initialize_Cov (StateHelper.cpp:35-61) for the covariance.  The device filters (hnet_filters_advance, include/hnet.h) form the window
+ * sums as reductions and run init_decide / init_from_stats / initialize_cov below on them; tests/test_filters_feed_cpu.py checks every function
+ * against a numpy restatement. */
+
+/* the two retention rules of the reference's IMU buffers, for readings[0 .. n) in time order: the index of the first reading that is kept.
+ * The initialiser drops from the front while a reading is older than three windows behind the newest (InertialInitializer.cpp:28-38); the propagator
+ * drops every reading more than 10 s behind the newest (Propagator.h:110-124; a prefix, the readings being in time order). */
+inline int trim_imu_init(const ImuData* readings, int n, double newest_t, double window_time) {
+    int k = 0;
+    while (k < n && readings[k].t < newest_t - 3 * window_time) k++;
+    return k;
+}
+inline int trim_imu_prop(const ImuData* readings, int n, double newest_t) {
+    int k = 0;
+    while (k < n && newest_t - readings[k].t > 10) k++;
+    return k;
+}
+
+/* The part of readings[0 .. n) (time order) that select_imu_readings(readings, n, t0, t1, .) can touch, from two counts: n_lt readings with
+ * t < t0 and n_le readings with t <= t1.  Every pair before the reading just below t0 fails all three tests of the loop, and the loop ends at the
+ * first pair whose later reading is past t1 or, when that pair opened the window (IMU slower than the camera), one pair later; so
+ * select_imu_readings(readings + first, len, t0, t1, .) writes what the whole history gives.  (Its `i == 0` test needs a reading past t1 at the
+ * start of the span, which only a span that starts at reading 0 can have.)  Returns len; the device filters find the counts in parallel. */
+inline int select_span(int n, int n_lt, int n_le, int* first) {
+    *first = 0;
+    if (n <= 0) return 0;
+    const int lo = n_lt > 0 ? n_lt - 1 : 0;
+    const int hi = n_le + 1 < n - 1 ? n_le + 1 : n - 1;
+    *first = lo;
+    return hi >= lo ? hi - lo + 1 : 0;
+}
+
+/* InertialInitializer.cpp:216-229: the two refusals on the windows' sample deviations (wait_for_jerk: VioManager.cpp:322, always true there).
+ * dev_1to0: newest window, dev_2to1: the window before it.  A window of ONE reading has a deviation of 0 / (1 - 1) = NaN (:197, :212 divide by
+ * size - 1); both comparisons are then false and the window passes, as in the reference: written with the reference's `<` and `>` so that it stays so. */
+inline bool init_decide(double dev_1to0, double dev_2to1, double imu_thresh, bool wait_for_jerk) {
+    if (dev_1to0 < imu_thresh && wait_for_jerk) return false;              /* no excitation yet */
+    if (dev_2to1 > imu_thresh && wait_for_jerk) return false;              /* started up moving: wait for a stationary period */
+    return true;
+}
+
+/* InertialInitializer.cpp:231-270: the mean from the older window's average specific force a_avg and angular velocity w_avg.  z axis along a_avg,
+ * e_1 made perpendicular to it, y = z x x, Ro = [x y z]; q = rot_2_Ham_quat(Ro^T) (quat_ops.h:558-571, Hamilton w, x, y, z, no sign convention
+ * applied), ba = a_avg - Ro (0, 0, g), bg = w_avg, p = Ro (0, 0, init_height), v = 0.  Offsets and covariance of `s` are not touched. */
+inline void init_from_stats(const double a_avg[3], const double w_avg[3], double init_height, double gravity_mag, State& s) {
+    const double an = std::sqrt(m3::dot(a_avg, a_avg));
+    const double z[3] = {a_avg[0] / an, a_avg[1] / an, a_avg[2] / an};
+    const double e1[3] = {1.0, 0.0, 0.0};
+    double zz[9], zze[3], x[3], y[3];
+    m3::outer(z, z, zz);
+    mat3_vec(zz, e1, zze);                                                 /* z z^T e_1 (:238) */
+    for (int i = 0; i < 3; i++) x[i] = e1[i] - zze[i];
+    const double xn = std::sqrt(m3::dot(x, x));
+    for (int i = 0; i < 3; i++) x[i] = x[i] / xn;
+    cross(z, x, y);                                                        /* skew_x(z) x (:242) */
+    const double Ro[9] = {x[0], y[0], z[0], x[1], y[1], z[1], x[2], y[2], z[2]};
+    /* rot_2_Ham_quat(Ro^T): rot(i, j) = Ro[j * 3 + i] */
+    const double T = Ro[0] + Ro[4] + Ro[8];
+    double q[4];
+    q[0] = 0.5 * std::sqrt(1 + T);
+    q[1] = (Ro[1 * 3 + 2] - Ro[2 * 3 + 1]) / (4 * q[0]);
+    q[2] = (Ro[2 * 3 + 0] - Ro[0 * 3 + 2]) / (4 * q[0]);
+    q[3] = (Ro[0 * 3 + 1] - Ro[1 * 3 + 0]) / (4 * q[0]);
+    const double qn = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    for (int i = 0; i < 4; i++) s.q[i] = q[i] / qn;
+    const double grav[3] = {0.0, 0.0, gravity_mag}, wp[3] = {0.0, 0.0, init_height};
+    double Rg[3];
+    mat3_vec(Ro, grav, Rg);
+    mat3_vec(Ro, wp, s.p);
+    for (int i = 0; i < 3; i++) { s.ba[i] = a_avg[i] - Rg[i]; s.bg[i] = w_avg[i]; s.v[i] = 0.0; }
+}
+
+/* InertialInitializer::initialize_with_imu_CUAHN on readings[0 .. n) (time order; the caller has applied trim_imu_init, as feed_imu does).
+ * Windows (newest - 2w, newest - w] and (newest - w, newest]; refuses (false, nothing written) fewer than two readings, a span below 2 w, an
+ * empty window, and what init_decide refuses.  The deviations are sqrt(sum |a - a_avg|^2 / (size - 1)) (see init_decide for size 1).
+ * On success the mean of `s` is set (init_from_stats) and time0 is the time of the LAST reading of the OLDER window (:259). */
+inline bool initialize_with_imu(const ImuData* readings, int n, double window_time, double imu_thresh, double init_height, bool wait_for_jerk,
+                                double gravity_mag, double& time0, State& s) {
+    if (n < 2) return false;
+    const double newest = readings[n - 1].t, oldest = readings[0].t;
+    if (newest - oldest < 2 * window_time) return false;
+    int n1 = 0, n2 = 0, last2 = -1;
+    double a1[3] = {0, 0, 0}, a2[3] = {0, 0, 0}, w2[3] = {0, 0, 0};
+    for (int k = 0; k < n; k++) {
+        const ImuData& d = readings[k];
+        if (d.t > newest - 1 * window_time && d.t <= newest - 0 * window_time) {
+            for (int i = 0; i < 3; i++) a1[i] += d.am[i];
+            n1++;
+        }
+        if (d.t > newest - 2 * window_time && d.t <= newest - 1 * window_time) {
+            for (int i = 0; i < 3; i++) { a2[i] += d.am[i]; w2[i] += d.wm[i]; }
+            n2++;
+            last2 = k;
+        }
+    }
+    if (n1 == 0 || n2 == 0) return false;
+    for (int i = 0; i < 3; i++) { a1[i] /= n1; a2[i] = a2[i] / n2; w2[i] = w2[i] / n2; }
+    double v1 = 0, v2 = 0;
+    for (int k = 0; k < n; k++) {
+        const ImuData& d = readings[k];
+        if (d.t > newest - 1 * window_time && d.t <= newest - 0 * window_time) {
+            const double e[3] = {d.am[0] - a1[0], d.am[1] - a1[1], d.am[2] - a1[2]};
+            v1 += m3::dot(e, e);
+        }
+        if (d.t > newest - 2 * window_time && d.t <= newest - 1 * window_time) {
+            const double e[3] = {d.am[0] - a2[0], d.am[1] - a2[1], d.am[2] - a2[2]};
+            v2 += m3::dot(e, e);
+        }
+    }
+    v1 = std::sqrt(v1 / (n1 - 1));
+    v2 = std::sqrt(v2 / (n2 - 1));
+    if (!init_decide(v1, v2, imu_thresh, wait_for_jerk)) return false;
+    init_from_stats(a2, w2, init_height, gravity_mag, s);
+    time0 = readings[last2].t;
+    return true;
+}
+
+/* StateHelper::initialize_Cov (StateHelper.cpp:35-61) on s.cov with s.q: zero x / y position variance (the 2 x 2 block), z 0.005^2; roll / pitch
+ * (0.5 / 180 * 3.14159265)^2 with the reference's literal, yaw 0; ba 0.005^2 I, bg 0; then the p and q blocks go into the local frame,
+ * w_R_i^T B w_R_i.  Like the reference it overwrites those entries only: it is meant for the all-zero covariance of a new State (State.cpp:79). */
+inline void initialize_cov(State& s) {
+    double* P = s.cov;
+    for (int i = 0; i < 2; i++)
+        for (int j = 0; j < 2; j++) P[i * NS + j] = 0.0;
+    P[2 * NS + 2] = 0.005 * 0.005;
+    const double std_degree = 0.5;
+    P[3 * NS + 3] = (std_degree / 180.0 * 3.14159265) * (std_degree / 180.0 * 3.14159265);
+    P[4 * NS + 4] = (std_degree / 180.0 * 3.14159265) * (std_degree / 180.0 * 3.14159265);
+    P[5 * NS + 5] = 0.0;
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) {
+            P[(9 + i) * NS + 9 + j] = (i == j ? 1.0 : 0.0) * 0.005 * 0.005;
+            P[(12 + i) * NS + 12 + j] = (i == j ? 1.0 : 0.0) * 0.0000 * 0.0000;
+        }
+    double R[9], Rt[9];
+    quat_to_rot(s.q, R);
+    m3::transpose(R, Rt);
+    for (int b = 0; b < 6; b += 3) {
+        double B[9], t[9];
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) B[i * 3 + j] = P[(b + i) * NS + b + j];
+        m3::mul(Rt, B, t);
+        m3::mul(t, R, B);
+        set_block(P, NS, b, b, B);
+    }
+}
+
 }  // namespace hnet_ekf
 #endif  /* HNET_EKF_H */

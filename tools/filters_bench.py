@@ -6,7 +6,10 @@ Per tick every one of K sessions pushes one frame and gets 16 IMU intervals of 2
           reset (tests/cpp/filters_ref.cpp, built here with g++ -O2), on a second sessions object of the same blob.
 One JSON line per (K, iterations): ticks/s and ms per tick of both (median, p10, p90 over the ticks), the step's device ms (upload .. last
 update, HIP events).
-   python tools/filters_bench.py [--k 1,8,64,256] [--iters 1,3] [--ticks 20] [--warmup 3] [--threads 1,16]"""
+--feed adds a third filters object on its own context that runs the same ticks through hnet_filters_feed_imu + hnet_filters_advance (rings of 256
+readings): per tick the readings newer than the ring's newest are handed over once and one advance steps all K sessions; reported are the feed
+call, the advance call and their sum, next to the step column of the same process and inputs (the step call's time includes packing K windows).
+   python tools/filters_bench.py [--k 1,8,64,256] [--iters 1,3] [--ticks 20] [--warmup 3] [--threads 1,16] [--feed]"""
 import argparse
 import ctypes as C
 import json
@@ -44,6 +47,7 @@ def main():
     ap.add_argument("--ticks", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--threads", default="1,16")
+    ap.add_argument("--feed", action="store_true")
     a = ap.parse_args()
     from cuahn_vio_amd import _capi, replay, weights
     from cuahn_vio_amd.homography_net import HnetEngine, HnetFilters, HnetSessions
@@ -68,6 +72,14 @@ def main():
             for i in range(K):
                 f.set_state(i, st0[0])
             hosts = {T: np.repeat(st0, K) for T in threads}
+            if a.feed:
+                e3 = HnetEngine(blob, max_batch=K, **kw)
+                s3 = HnetSessions(e3, K)
+                f3 = HnetFilters(s3, iters)
+                f3.enable_feed(256)
+                for i in range(K):
+                    f3.set_state(i, st0[0])
+                newest, feed_ms, adv_ms, adv_dev = -np.inf, [], [], []
             rng = np.random.default_rng(K)
             dev_ms, dev_dev, host_ms = [], [], {T: [] for T in threads}
             t = 0.0
@@ -77,6 +89,21 @@ def main():
                 for s in (s1, s2):
                     s.push(ids, fr, t=[t_new] * K)
                 win = imu_window(rng, t)
+                if a.feed:
+                    s3.push(ids, fr, t=[t_new] * K)
+                    new = win[win["t"] > newest]                # the windows of consecutive ticks overlap: a reading is handed over once
+                    newest = float(new["t"][-1])
+                    t0 = time.perf_counter()
+                    f3.feed_imu(ids, [new] * K)
+                    t1 = time.perf_counter()
+                    if tick > 0:
+                        _, _, _, status = f3.advance(ids)
+                        t2 = time.perf_counter()
+                        assert (status == _capi.ADV_STEPPED).all(), status
+                        if tick > a.warmup:
+                            feed_ms.append((t1 - t0) * 1e3)
+                            adv_ms.append((t2 - t1) * 1e3)
+                            adv_dev.append(f3.last_timing()["device_ms"])
                 if tick == 0:                                   # one image per session so far: nothing to step
                     t = t_new
                     continue
@@ -117,6 +144,12 @@ def main():
                 rec[f"host_loop_{T}t_ms_p10"] = pct(host_ms[T], 10)
                 rec[f"host_loop_{T}t_ms_p90"] = pct(host_ms[T], 90)
                 rec[f"host_loop_{T}t_ticks_per_s"] = round(1e3 / m, 1)
+            if a.feed:
+                tot = [x + y for x, y in zip(feed_ms, adv_ms)]
+                for name, v in (("feed_imu_ms", feed_ms), ("advance_ms", adv_ms), ("feed_tick_ms", tot), ("advance_event_ms", adv_dev)):
+                    rec[f"{name}_p50"], rec[f"{name}_p10"], rec[f"{name}_p90"] = pct(v, 50), pct(v, 10), pct(v, 90)
+                rec["feed_tick_over_step"] = round(float(np.median(tot)) / float(np.median(dev_ms)), 3)
+                f3.close(); s3.close(); e3.close()
             print(json.dumps(rec), flush=True)
             f.close(); s1.close(); s2.close(); e1.close(); e2.close()
 
