@@ -38,6 +38,7 @@ SYMBOLS = [
     "hnet_filters_get_state", "hnet_filters_step", "hnet_filters_last_priors", "hnet_filters_last_timing",
     "hnet_filter_default_init_params", "hnet_filters_enable_feed", "hnet_filters_set_init_params", "hnet_filters_feed_imu", "hnet_filters_initialized",
     "hnet_filters_uninitialize", "hnet_filters_advance", "hnet_filters_last_selection",
+    "hnet_sessions_set_iterative_model", "hnet_sessions_infer_iter",
 ]
 # hnet_filters_advance's status per listed session (include/hnet.h HNET_ADV_*)
 ADV_STEPPED, ADV_WAIT_IMU, ADV_WAIT_INIT, ADV_INITIALIZED, ADV_PROPAGATED, ADV_NO_FRAME = range(6)
@@ -174,6 +175,8 @@ def lib():
     L.hnet_sessions_bind_camera.argtypes = [vp, C.c_int, C.c_int]
     L.hnet_sessions_push_raw.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_size_t, vp]
     L.hnet_sessions_infer.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
+    L.hnet_sessions_set_iterative_model.argtypes = [vp, vp]
+    L.hnet_sessions_infer_iter.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
     L.hnet_sessions_image_count.argtypes = [vp, C.c_int]
     L.hnet_sessions_latest_time.argtypes = [vp, C.c_int]
     L.hnet_sessions_latest_time.restype = C.c_double

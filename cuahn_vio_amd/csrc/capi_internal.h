@@ -207,7 +207,12 @@ int upload_weights(hnet_ctx* c, const Blob& b);          // weights -> device in
 void build_stages(hnet_ctx* c, int batch, const void* prev = nullptr, const void* curr = nullptr, int pix_fmt = HNET_PIX_U8);   // capi_forward.hip
 int forward(hnet_ctx* c, const FwdArgs& a, hipStream_t s);
 void record_timing(hnet_timing& t, float dev_ms, double host_ms, int n_inferences, bool main_model);      // hnet_capi.hip
-int run_host_call(hnet_ctx* c, const std::function<int(uint32_t& flag)>& enqueue, const std::function<bool()>& overflowed);
+int run_host_call(hnet_ctx* const ctx[2], const std::function<int(uint32_t* flag)>& enqueue, const std::function<int()>& overflowed);
+// ... for a call that runs forwards on one context
+inline int run_host_call(hnet_ctx* c, const std::function<int(uint32_t& flag)>& enqueue, const std::function<bool()>& overflowed) {
+    hnet_ctx* const ctx[2] = {c, nullptr};
+    return run_host_call(ctx, [&](uint32_t* flag) { return enqueue(flag[0]); }, [&] { return overflowed() ? 0 : -1; });
+}
 void build_undistort_maps(const hnet_camera* cam, std::vector<float>& mx, std::vector<float>& my);
 
 }  // namespace capi

@@ -10,6 +10,7 @@ extern "C" {
 // on the host; the frames live in a device ring of 2 slots per session (slot 2 id + k).  Every device step runs on the context's stream.
 struct hnet_sessions {
     hnet_ctx* ctx = nullptr;
+    hnet_ctx* iter = nullptr;                  // the iterative model's context (hnet_sessions_set_iterative_model) or null: forwards of iteration > 0, on ctx's stream
     int n = 0;
     uint8_t* ring = nullptr;                   // device [n][2][NPIX]
     // t_push: the stamp of the latest push, whatever the count (NaN: none given; hnet_filters_advance's t_frame)
@@ -229,13 +230,34 @@ int hnet_sessions_push_raw(hnet_sessions* s, int n, const int32_t* ids, const ui
     return sessions_commit_push(s, n, ids, t);
 }
 
+int hnet_sessions_set_iterative_model(hnet_sessions* s, hnet_ctx* it) {
+    if (!s) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = s->ctx;
+    if (it) {                                                      // (the adapter's require_prior_agrees; the forwards read the main context's staging)
+        if (it == c) return fail(c, HNET_ERR_INVALID_ARG, "hnet_sessions_set_iterative_model: the sessions' own context");
+        if (it->cfg.device_id != c->cfg.device_id) return fail(c, HNET_ERR_INVALID_ARG, "hnet_sessions_set_iterative_model: both contexts must live on one device");
+        if (it->s_begin != 0 || it->n_local != it->cfg.mc_samples) return fail(c, HNET_ERR_UNSUPPORTED, "hnet_sessions_set_iterative_model: the context evaluates a sample shard");
+        if (!it->cfg.use_prior != !c->cfg.use_prior) return fail(c, HNET_ERR_INVALID_ARG, "hnet_sessions_set_iterative_model: use_prior differs from the main model's");
+        if (it->cfg.max_batch < c->cfg.max_batch) return fail(c, HNET_ERR_INVALID_ARG, "hnet_sessions_set_iterative_model: max_batch below the main context's");
+    }
+    s->iter = it;
+    return HNET_OK;
+}
+
 int hnet_sessions_infer(hnet_sessions* s, int n, const int32_t* ids, const double* prior_px, float* mean, float* cov, uint8_t* err_map) {
+    return hnet_sessions_infer_iter(s, 0, n, ids, prior_px, mean, cov, err_map);
+}
+
+int hnet_sessions_infer_iter(hnet_sessions* s, int iteration, int n, const int32_t* ids, const double* prior_px, float* mean, float* cov, uint8_t* err_map) {
     if (!s) return HNET_ERR_INVALID_ARG;
     hnet_ctx* c = s->ctx;
     if (!mean || !cov) return fail(c, HNET_ERR_INVALID_ARG, "hnet_sessions_infer: mean / cov");
+    if (iteration < 0) return fail(c, HNET_ERR_INVALID_ARG, "hnet_sessions_infer_iter: iteration < 0");
     int rc = sessions_check_ids(s, n, ids);
     if (rc != HNET_OK) return rc;
-    if (err_map && !c->cfg.emit_error_map) return fail(c, HNET_ERR_INVALID_ARG, "context was created without emit_error_map");
+    hnet_ctx* m = iteration > 0 && s->iter ? s->iter : c;         // the model that runs (HomographyNet.cpp:183, :211); its forward is enqueued on c's stream
+    hnet_ctx* const ctx[2] = {c, m != c ? m : nullptr};
+    if (err_map && !m->cfg.emit_error_map) return fail(c, HNET_ERR_INVALID_ARG, "context was created without emit_error_map");
     if (c->cfg.use_prior && !prior_px) return fail(c, HNET_ERR_INVALID_ARG, "prior required");
     for (int i = 0; i < n; i++)
         if (s->st[ids[i]].count < 2) return fail(c, HNET_ERR_NOT_READY, "HNet cannot inference! Only has one image!");   // :155-158, per session
@@ -256,32 +278,34 @@ int hnet_sessions_infer(hnet_sessions* s, int n, const int32_t* ids, const doubl
     const uint64_t* d_seq = reinterpret_cast<const uint64_t*>(d_pr + (size_t)8 * n);
     const int32_t* d_pairs = reinterpret_cast<const int32_t*>(d_seq + n);
     hipStream_t st = c->stream;
-    const FwdArgs a{.prev = c->stage_prev, .curr = c->stage_curr, .prior = c->cfg.use_prior ? d_pr : nullptr, .batch = n, .mean = c->d_mean, .cov = c->d_cov,
-                    .err_u8 = err_map ? c->d_err_u8 : nullptr, .seq_tab = d_seq};
-    auto enqueue = [&](uint32_t& flag_now) -> int {
+    // (the frame pair is gathered into c's staging whichever model reads it; an attached context's max_batch covers n)
+    const FwdArgs a{.prev = c->stage_prev, .curr = c->stage_curr, .prior = c->cfg.use_prior ? d_pr : nullptr, .batch = n, .mean = m->d_mean, .cov = m->d_cov,
+                    .err_u8 = err_map ? m->d_err_u8 : nullptr, .seq_tab = d_seq};
+    auto enqueue = [&](uint32_t* flag_now) -> int {
         HIPCHK(c, hipMemcpyAsync(s->d_tab, s->pin_tab, bytes, hipMemcpyHostToDevice, st));
         HIPCHK(c, hipEventRecord(s->ev0, st));
         HIPCHK(c, launch_session_gather(s->ring, 2 * s->n, d_pairs, n, (uint8_t*)c->stage_prev, (uint8_t*)c->stage_curr, st));
-        const int r = forward(c, a, st);
-        if (r != HNET_OK) return r;
+        const int r = forward(m, a, st);
+        if (r != HNET_OK) return m == c ? r : fail(c, r, "iterative model: " + m->err);
         HIPCHK(c, hipEventRecord(s->ev1, st));
-        HIPCHK(c, hipMemcpyAsync(mean, c->d_mean, (size_t)n * 8 * sizeof(float), hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipMemcpyAsync(cov, c->d_cov, (size_t)n * 64 * sizeof(float), hipMemcpyDeviceToHost, st));
-        if (err_map) HIPCHK(c, hipMemcpyAsync(err_map, c->d_err_u8, (size_t)n * NPIX, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipMemcpyAsync(&flag_now, c->d_flag, 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipMemsetAsync(c->d_flag, 0, 4, st));          // host results are inspected by run_host_call (as in hnet_infer_batch)
+        HIPCHK(c, hipMemcpyAsync(mean, m->d_mean, (size_t)n * 8 * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(cov, m->d_cov, (size_t)n * 64 * sizeof(float), hipMemcpyDeviceToHost, st));
+        if (err_map) HIPCHK(c, hipMemcpyAsync(err_map, m->d_err_u8, (size_t)n * NPIX, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(&flag_now[m == c ? 0 : 1], m->d_flag, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemsetAsync(m->d_flag, 0, 4, st));          // host results are inspected by run_host_call (as in hnet_infer_batch)
         HIPCHK(c, hipStreamSynchronize(st));
         return HNET_OK;
     };
     // a repeat reuses the same table: the counts advance once
-    rc = run_host_call(c, enqueue, [&] {
-        return !(all_finite(mean, (size_t)n * 8) && all_finite(cov, (size_t)n * 64)) && all_finite(c->cfg.use_prior ? prior_px : nullptr, (size_t)n * 8);
+    rc = run_host_call(ctx, enqueue, [&] {
+        const bool o = !(all_finite(mean, (size_t)n * 8) && all_finite(cov, (size_t)n * 64)) && all_finite(c->cfg.use_prior ? prior_px : nullptr, (size_t)n * 8);
+        return o ? (m == c ? 0 : 1) : -1;
     });
     if (rc != HNET_OK) return rc;
-    for (int i = 0; i < n; i++) s->st[ids[i]].seq++;                  // n_inferences of each session's dedicated context
+    for (int i = 0; i < n; i++) s->st[ids[i]].seq++;                  // n_inferences of each session's dedicated context (one count for both models)
     float ms = 0;
     HIPCHK(c, hipEventElapsedTime(&ms, s->ev0, s->ev1));
-    record_timing(s->timing, ms, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), 1, true);
+    record_timing(s->timing, ms, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), 1, iteration == 0);
     return HNET_OK;
 }
 
@@ -370,6 +394,26 @@ struct hnet_filters {
 };
 
 static size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// the context of forwards 1 .. iters - 1 of a step when the sessions have an iterative model (hnet_sessions_set_iterative_model), else null
+static hnet_ctx* filters_iter_ctx(const hnet_filters* f) { return f->iters > 1 ? f->s->iter : nullptr; }
+// forward `it` of a step: 0 on the main context ctx[0], later ones on ctx[1] if there is one; both read the pairs gathered into ctx[0]'s staging
+static int filters_forward(hnet_ctx* const ctx[2], int it, const FwdArgs& a, hipStream_t st) {
+    hnet_ctx* m = it > 0 && ctx[1] ? ctx[1] : ctx[0];
+    const int r = forward(m, a, st);
+    return r == HNET_OK || m == ctx[0] ? r : fail(ctx[0], r, "iterative model: " + m->err);
+}
+// the end of a step's attempt: the flag word of every context that ran downloaded and cleared (run_host_call), the one synchronisation
+static int filters_flags(hnet_ctx* const ctx[2], uint32_t* flag, hipStream_t st) {
+    hnet_ctx* c = ctx[0];
+    for (int k = 0; k < 2; k++)
+        if (ctx[k]) {
+            HIPCHK(c, hipMemcpyAsync(&flag[k], ctx[k]->d_flag, 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(c, hipMemsetAsync(ctx[k]->d_flag, 0, 4, st));
+        }
+    HIPCHK(c, hipStreamSynchronize(st));
+    return HNET_OK;
+}
 
 void hnet_filter_default_params(hnet_filter_params* p) {
     if (!p) return;
@@ -581,7 +625,8 @@ int hnet_filters_step(hnet_filters* f, int n, const int32_t* ids, const double* 
     const size_t down = state_out ? f->off_work + (size_t)n * sizeof(FilterRec) : f->off_upd + (size_t)n * sizeof(int32_t);
     hipStream_t st = c->stream;
     const size_t up = o_off + (size_t)(n + 1) * 4;
-    auto enqueue = [&](uint32_t& flag_now) -> int {
+    hnet_ctx* const ctx[2] = {c, filters_iter_ctx(f)};
+    auto enqueue = [&](uint32_t* flag_now) -> int {
         HIPCHK(c, hipMemcpyAsync(f->d_in, f->pin_in, up, hipMemcpyHostToDevice, st));
         HIPCHK(c, hipMemsetAsync(d_upd, 0, (size_t)n * sizeof(int32_t), st));
         HIPCHK(c, hipEventRecord(f->ev0, st));
@@ -593,25 +638,21 @@ int hnet_filters_step(hnet_filters* f, int n, const int32_t* ids, const double* 
             HIPCHK(c, launch_filter_prior(d_work, n, pr_it, f->d_prior_cam, st));
             const FwdArgs a{.prev = c->stage_prev, .curr = c->stage_curr, .prior = c->cfg.use_prior ? pr_it : nullptr, .batch = n, .mean = net_it, .cov = net_it + 8,
                             .seq_tab = d_seq + (size_t)it * n, .mean_stride = HNET_PACKED_FLOATS, .cov_stride = HNET_PACKED_FLOATS};
-            const int r = forward(c, a, st);
-            if (r != HNET_OK) return r;
+            if (const int r = filters_forward(ctx, it, a, st); r != HNET_OK) return r;
             HIPCHK(c, launch_filter_update(d_ids, n, s->n, f->d_params, net_it, f->d_prior_cam, d_gate, it != I - 1, it == I - 1, d_work, d_upd, st));
         }
         HIPCHK(c, hipEventRecord(f->ev1, st));
         HIPCHK(c, hipMemcpyAsync(f->pin_out, f->d_out, down, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipMemcpyAsync(&flag_now, c->d_flag, 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipMemsetAsync(c->d_flag, 0, 4, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-        return HNET_OK;
+        return filters_flags(ctx, flag_now, st);
     };
     // an overflow of the fp16 planes: the first forward with a non-finite output had finite inputs (its fp32 priors; later priors follow from it)
-    auto overflowed = [&]() -> bool {
+    auto overflowed = [&]() -> int {
         for (int it = 0; it < I; it++)
             if (!all_finite(h_net + (size_t)it * c->cfg.max_batch * 72, (size_t)n * 72))
-                return !c->cfg.use_prior || all_finite(h_prior + (size_t)it * c->cfg.max_batch * 8, (size_t)n * 8);
-        return false;
+                return !c->cfg.use_prior || all_finite(h_prior + (size_t)it * c->cfg.max_batch * 8, (size_t)n * 8) ? (it > 0 && ctx[1] ? 1 : 0) : -1;
+        return -1;
     };
-    if ((rc = run_host_call(c, enqueue, overflowed)) != HNET_OK) return rc;
+    if ((rc = run_host_call(ctx, enqueue, overflowed)) != HNET_OK) return rc;
     // accepted: the listed states take the step's result (stream order: later calls see it), the bookkeeping advances
     HIPCHK(c, launch_filter_scatter(d_work, d_ids, n, s->n, f->d_state, st));
     for (int i = 0; i < n; i++) {
@@ -859,7 +900,8 @@ int hnet_filters_advance(hnet_filters* f, int n, const int32_t* ids, hnet_filter
     const float* h_prior = reinterpret_cast<const float*>(f->pin_out + f->off_prior);
     const AdvanceResult* h_res = reinterpret_cast<const AdvanceResult*>(f->pin_out + f->off_res);
     hipStream_t st = c->stream;
-    auto enqueue = [&](uint32_t& flag_now) -> int {
+    hnet_ctx* const ctx[2] = {c, n_s ? filters_iter_ctx(f) : nullptr};
+    auto enqueue = [&](uint32_t* flag_now) -> int {
         HIPCHK(c, hipMemcpyAsync(f->d_adv, f->pin_adv, L.bytes, hipMemcpyHostToDevice, st));
         HIPCHK(c, hipMemsetAsync(d_upd, 0, (size_t)n_a * sizeof(int32_t), st));
         HIPCHK(c, hipEventRecord(f->ev0, st));
@@ -874,25 +916,22 @@ int hnet_filters_advance(hnet_filters* f, int n, const int32_t* ids, hnet_filter
             HIPCHK(c, launch_filter_prior(d_work, n_s, pr_it, f->d_prior_cam, st));
             const FwdArgs a{.prev = c->stage_prev, .curr = c->stage_curr, .prior = c->cfg.use_prior ? pr_it : nullptr, .batch = n_s, .mean = net_it, .cov = net_it + 8,
                             .seq_tab = d_seq + (size_t)it * n_a, .mean_stride = HNET_PACKED_FLOATS, .cov_stride = HNET_PACKED_FLOATS};
-            const int r = forward(c, a, st);
-            if (r != HNET_OK) return r;
+            if (const int r = filters_forward(ctx, it, a, st); r != HNET_OK) return r;
             HIPCHK(c, launch_filter_update(d_ids, n_s, s->n, f->d_params, net_it, f->d_prior_cam, d_gate, it != I - 1, it == I - 1, d_work, d_upd, st));
         }
         HIPCHK(c, hipEventRecord(f->ev1, st));
         if (n_s) HIPCHK(c, hipMemcpyAsync(f->pin_out, f->d_out, f->off_upd + (size_t)n_s * sizeof(int32_t), hipMemcpyDeviceToHost, st));
         if (state_out) HIPCHK(c, hipMemcpyAsync(f->pin_out + f->off_work, d_work, (size_t)n_a * sizeof(FilterRec), hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipMemcpyAsync(f->pin_out + f->off_res, d_res, (size_t)n_a * sizeof(AdvanceResult), hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipMemcpyAsync(&flag_now, c->d_flag, 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipMemsetAsync(c->d_flag, 0, 4, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-        return HNET_OK;
+        return filters_flags(ctx, flag_now, st);
     };
-    auto overflowed = [&]() -> bool {                              // as hnet_filters_step, over the sessions that step
+    auto overflowed = [&]() -> int {                               // as hnet_filters_step, over the sessions that step
         for (int it = 0; it < I && n_s; it++)
-            if (!all_finite(h_net + (size_t)it * B * 72, (size_t)n_s * 72)) return !c->cfg.use_prior || all_finite(h_prior + (size_t)it * B * 8, (size_t)n_s * 8);
-        return false;
+            if (!all_finite(h_net + (size_t)it * B * 72, (size_t)n_s * 72))
+                return !c->cfg.use_prior || all_finite(h_prior + (size_t)it * B * 8, (size_t)n_s * 8) ? (it > 0 && ctx[1] ? 1 : 0) : -1;
+        return -1;
     };
-    if ((rc = run_host_call(c, enqueue, overflowed)) != HNET_OK) return rc;
+    if ((rc = run_host_call(ctx, enqueue, overflowed)) != HNET_OK) return rc;
     // accepted: the states take the results (not those the initialiser refused), the bookkeeping advances
     HIPCHK(c, launch_filter_scatter_ok(d_work, d_job, d_res, n_a, s->n, f->d_state, st));
     const int32_t* h_upd = reinterpret_cast<const int32_t*>(f->pin_out + f->off_upd);

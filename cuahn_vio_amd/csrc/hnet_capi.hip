@@ -348,18 +348,25 @@ static int chain_gave_up(hnet_ctx* c) {
     return HNET_OK;
 }
 
-// The policy of every entry point that returns its results to the host (hnet_infer, hnet_infer_batch, hnet_sessions_infer, hnet_filters_step).
-// `enqueue` runs one complete attempt: its work, the download of the results and of the flag word, the reset of that word, the synchronisation.
-// A tail chain that timed out sends the context back to the launches and the attempt runs again; then, on the latest results, an fp16-plane
-// overflow (`overflowed`: non-finite outputs of finite inputs, the entry point's own test) demotes the context and the attempt runs again.
-// The caller advances its counters once, after an accepted call.  A failed attempt may leave copies from pinned buffers in flight: the stream
-// is drained before the error returns.
-int run_host_call(hnet_ctx* c, const std::function<int(uint32_t& flag)>& enqueue, const std::function<bool()>& overflowed) {
-    uint32_t flag = 0;
+// The policy of every entry point that returns its results to the host (hnet_infer, hnet_infer_batch, hnet_sessions_infer[_iter], hnet_filters_step,
+// hnet_filters_advance).  ctx[0] is the call's context (its stream carries the work), ctx[1] a second context whose forwards the same attempt enqueues
+// on that stream (the sessions' iterative model), or null.  `enqueue` runs one complete attempt: its work, the download of the results and of the flag
+// word of every context that ran (flag[k] of ctx[k]; 0 for one that did not), the reset of those words, the synchronisation.  A tail chain that timed
+// out sends the context that flagged it back to the launches and the attempt runs again; then, on the latest results, an fp16-plane overflow
+// (`overflowed`: the index of the context whose forward gave non-finite outputs of finite inputs, -1 for none; the entry point's own test) demotes
+// that context and the attempt runs again - a context demotes once, so two contexts repeat twice at the most.  The caller advances its counters once,
+// after an accepted call.  A failed attempt may leave copies from pinned buffers in flight: the stream is drained before the error returns.
+int run_host_call(hnet_ctx* const ctx[2], const std::function<int(uint32_t* flag)>& enqueue, const std::function<int()>& overflowed) {
+    uint32_t flag[2] = {0, 0};
     int rc = enqueue(flag);
-    if (rc == HNET_OK && (flag & CH_FLAG_TIMEOUT) && (rc = chain_gave_up(c)) == HNET_OK) rc = enqueue(flag);
-    if (rc == HNET_OK && c->n_planes == 2 && overflowed() && (rc = demote_to_bf16x3(c)) == HNET_OK) rc = enqueue(flag);
-    if (rc != HNET_OK) (void)hipStreamSynchronize(c->stream);
+    bool again = false;
+    for (int k = 0; k < 2 && rc == HNET_OK; k++)
+        if (ctx[k] && (flag[k] & CH_FLAG_TIMEOUT) && (rc = chain_gave_up(ctx[k])) == HNET_OK) again = true;
+    if (rc == HNET_OK && again) rc = enqueue(flag);
+    auto f16 = [&](int k) { return k >= 0 && ctx[k] && ctx[k]->n_planes == 2; };
+    for (int k; rc == HNET_OK && (f16(0) || f16(1)) && f16(k = overflowed());)
+        if ((rc = demote_to_bf16x3(ctx[k])) == HNET_OK) rc = enqueue(flag);
+    if (rc != HNET_OK) (void)hipStreamSynchronize(ctx[0]->stream);
     return rc;
 }
 

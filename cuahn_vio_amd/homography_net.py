@@ -419,6 +419,7 @@ class HnetSessions:
 
     def __init__(self, engine, n_sessions):
         self.engine, self._L, self.n = engine, engine._L, int(n_sessions)
+        self.iter_engine = None
         self._s = C.c_void_p()
         check(engine.handle, self._L.hnet_create_sessions(engine.handle, self.n, C.byref(self._s)))
         self.emit_error_map = bool(engine.config().emit_error_map)
@@ -476,15 +477,29 @@ class HnetSessions:
         self._check(self._L.hnet_sessions_push_raw(self._s, n, ids.ctypes.data, r.ctypes.data, r.shape[1], r.shape[2], r.strides[1], r.strides[0],
                                                    tt.ctypes.data if tt is not None else None))
 
-    def infer(self, ids, prior=None, want_err=False):
-        """-> (mean [n, 8], cov [n, 8, 8][, err [n, 224, 320] uint8]); prior [n, 8] pixels (float64 as the C ABI takes it)"""
+    def set_iterative_model(self, engine):
+        """hnet_sessions_set_iterative_model: `engine` (an HnetEngine of the iterative weight file) runs IEKF iterations > 0 of infer() and of the
+        filters' steps, on this object's frames; None detaches.  A reference to the engine is held while it is attached."""
+        if engine is not None and not isinstance(engine, HnetEngine):
+            raise TypeError("set_iterative_model expects an HnetEngine or None")
+        self._check(self._L.hnet_sessions_set_iterative_model(self._s, engine.handle if engine is not None else None))
+        self.iter_engine = engine
+
+    def infer(self, ids, prior=None, want_err=False, iteration=0):
+        """-> (mean [n, 8], cov [n, 8, 8][, err [n, 224, 320] uint8]); prior [n, 8] pixels (float64 as the C ABI takes it).
+        iteration > 0: the IEKF re-run, on the iterative model if one is attached (hnet_sessions_infer_iter)"""
+        if isinstance(iteration, bool) or not isinstance(iteration, (int, np.integer)) or iteration < 0:
+            raise ValueError("iteration must be an integer >= 0")
         ids, n = self._ids(ids)
         mean = np.zeros((n, 8), np.float32)
         cov = np.zeros((n, 8, 8), np.float32)
         err = np.zeros((n, IMG_H, IMG_W), np.uint8) if want_err else None
         pr = None if prior is None else np.ascontiguousarray(prior, dtype=np.float64).reshape(n, 8)
-        self._check(self._L.hnet_sessions_infer(self._s, n, ids.ctypes.data, pr.ctypes.data if pr is not None else None, mean.ctypes.data,
-                                                cov.ctypes.data, err.ctypes.data if want_err else None))
+        args = (n, ids.ctypes.data, pr.ctypes.data if pr is not None else None, mean.ctypes.data, cov.ctypes.data, err.ctypes.data if want_err else None)
+        if iteration == 0:
+            self._check(self._L.hnet_sessions_infer(self._s, *args))
+        else:
+            self._check(self._L.hnet_sessions_infer_iter(self._s, int(iteration), *args))
         return (mean, cov, err) if want_err else (mean, cov)
 
     def image_count(self, id):

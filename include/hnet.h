@@ -302,6 +302,16 @@ int  hnet_sessions_push_raw(hnet_sessions* s, int n, const int32_t* ids, const u
  * with use_prior), mean [n][8], cov [n][64], err_map [n][224][320] u8 or NULL.  Each listed session's sequence number advances by one (an IEKF re-run is
  * another call with the new priors).  One synchronisation; the F16X2 overflow repeat of hnet_infer_batch applies (same keys, counts advance once). */
 int  hnet_sessions_infer(hnet_sessions* s, int n, const int32_t* ids, const double* prior_px, float* mean, float* cov, uint8_t* err_map);
+/* The IEKF's second model (network_model_iterative_path, HomographyNet.cpp:20-24,104-124,209-219; hnet_attach_images for one camera) for every session:
+ * `iter` is a context created from the iterative weight file (it may be another variant, e.g. prior-1, N = 8, p = 0.1); it needs no frames of its own - its
+ * forwards read the pairs the sessions' ring holds - and while attached it is dedicated to these sessions: its forwards are enqueued on the sessions'
+ * context's stream.  iter = NULL detaches.  `iter` must outlive the attachment.  HNET_ERR_INVALID_ARG (nothing changes): iter is the sessions' own context,
+ * lives on another device, has another use_prior than the main model, or a smaller max_batch; HNET_ERR_UNSUPPORTED: iter evaluates a sample shard. */
+int  hnet_sessions_set_iterative_model(hnet_sessions* s, hnet_ctx* iter);
+/* hnet_sessions_infer for IEKF iteration `iteration` (>= 0): iteration 0 is exactly hnet_sessions_infer; iteration > 0 runs the attached iterative model, or
+ * the main model when none is attached (as hnet_infer accepts the index).  Each listed session's sequence number advances by one whichever model ran: the
+ * adapter's one shared count.  err_map needs emit_error_map on the context that runs.  An F16X2 overflow demotes that context. */
+int  hnet_sessions_infer_iter(hnet_sessions* s, int iteration, int n, const int32_t* ids, const double* prior_px, float* mean, float* cov, uint8_t* err_map);
 int  hnet_sessions_image_count(const hnet_sessions* s, int id);           /* img_counter (HomographyNet.h:33) of session id; -1 for a bad id */
 double hnet_sessions_latest_time(const hnet_sessions* s, int id);         /* get_latest_inference_time() (HomographyNet.h:31); -1 before the second image */
 int  hnet_sessions_set_seq(hnet_sessions* s, int id, uint64_t seq);       /* next mask sequence number of session id (default 0) */
@@ -325,6 +335,12 @@ int  hnet_infer_batch_seqs_packed_device(hnet_ctx* ctx, const void* d_prev, cons
  * where hnet_ekf::iterated_update stops iterating; the device still runs the later batched forwards for it, so its sequence number advances once per
  * iteration either way.  Errors (the hnet_sessions codes: a bad or repeated id, n > max_batch, a session with fewer than two images, t_frame <= state t)
  * change no state.  The F16X2 overflow and chain-timeout repeats of hnet_sessions_infer apply to the whole step (the listed states are restored first).
+ * Iteration routing: with an iterative model attached to the sessions (hnet_sessions_set_iterative_model) and max_iekf_iteration > 1, forward 0 of a step
+ * runs on the main context and forwards 1 .. max_iekf_iteration - 1 on the iterative one, as hnet_sessions_infer_iter would route them; still one upload,
+ * one download and one synchronisation, and the frame pairs are gathered once.  A repeat then acts on the context that asked for it: a chain time-out sends
+ * the context that flagged it back to the launches, an overflow demotes the context whose forward overflowed (the first forward with non-finite outputs
+ * of finite priors: forward 0 -> main, later -> iterative), and the whole step reruns from the untouched states; sequence numbers advance once per accepted
+ * step.  With max_iekf_iteration = 1 or nothing attached a step is what it is without the attachment, bit for bit.
  * The filters must be destroyed before their sessions. */
 typedef struct hnet_imu { double t, wm[3], am[3]; } hnet_imu;
 /* defaults (hnet_filter_default_params): uzhfpv.launch - indoor T_ItoCmono (:84-89; i_t_i2c = -c_R_i^T t, State.cpp:95-96), noise densities

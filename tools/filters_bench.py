@@ -9,7 +9,12 @@ update, HIP events).
 --feed adds a third filters object on its own context that runs the same ticks through hnet_filters_feed_imu + hnet_filters_advance (rings of 256
 readings): per tick the readings newer than the ring's newest are handed over once and one advance steps all K sessions; reported are the feed
 call, the advance call and their sum, next to the step column of the same process and inputs (the step call's time includes packing K windows).
-   python tools/filters_bench.py [--k 1,8,64,256] [--iters 1,3] [--ticks 20] [--warmup 3] [--threads 1,16] [--feed]"""
+--iter-variant V (with --iter-mc N, --iter-p P) adds the IEKF's second model (hnet_sessions_set_iterative_model): a fourth filters object on its own
+context whose sessions have an iterative engine of variant V attached, so its forwards 1 .. I-1 run on that model ("iter_step" columns, and
+iter_over_main = its median over the device step's, which runs every iteration on the main model); the host loop then runs iterations > 0 through
+hnet_sessions_infer_iter on an iterative engine attached to its sessions.
+   python tools/filters_bench.py [--k 1,8,64,256] [--iters 1,3] [--ticks 20] [--warmup 3] [--threads 1,16] [--feed]
+                                 [--iter-variant prior1 --iter-mc 8 --iter-p 0.1]"""
 import argparse
 import ctypes as C
 import json
@@ -48,6 +53,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--threads", default="1,16")
     ap.add_argument("--feed", action="store_true")
+    ap.add_argument("--iter-variant", default=None)
+    ap.add_argument("--iter-mc", type=int, default=8)
+    ap.add_argument("--iter-p", type=float, default=0.1)
     a = ap.parse_args()
     from cuahn_vio_amd import _capi, replay, weights
     from cuahn_vio_amd.homography_net import HnetEngine, HnetFilters, HnetSessions
@@ -72,6 +80,16 @@ def main():
             for i in range(K):
                 f.set_state(i, st0[0])
             hosts = {T: np.repeat(st0, K) for T in threads}
+            if a.iter_variant:
+                ikw = dict(variant=a.iter_variant, mc_samples=a.iter_mc, dropout_p=a.iter_p, mc_seed=kw["mc_seed"], max_batch=K)
+                e4, ei4, ei2 = HnetEngine(blob, max_batch=K, **kw), HnetEngine(blob, **ikw), HnetEngine(blob, **ikw)
+                s4 = HnetSessions(e4, K)
+                s4.set_iterative_model(ei4)
+                s2.set_iterative_model(ei2)
+                f4 = HnetFilters(s4, iters)
+                for i in range(K):
+                    f4.set_state(i, st0[0])
+                it_ms, it_dev = [], []
             if a.feed:
                 e3 = HnetEngine(blob, max_batch=K, **kw)
                 s3 = HnetSessions(e3, K)
@@ -86,7 +104,7 @@ def main():
             for tick in range(a.warmup + a.ticks):
                 t_new = t + 0.0325
                 fr = np.repeat(pool[tick % len(pool)][None], K, 0)
-                for s in (s1, s2):
+                for s in (s1, s2) + ((s4,) if a.iter_variant else ()):
                     s.push(ids, fr, t=[t_new] * K)
                 win = imu_window(rng, t)
                 if a.feed:
@@ -113,6 +131,13 @@ def main():
                 if tick > a.warmup:
                     dev_ms.append(d)
                     dev_dev.append(f.last_timing()["device_ms"])
+                if a.iter_variant:
+                    t0 = time.perf_counter()
+                    f4.step(ids, [t_new] * K, [win] * K)
+                    d = (time.perf_counter() - t0) * 1e3
+                    if tick > a.warmup:
+                        it_ms.append(d)
+                        it_dev.append(f4.last_timing()["device_ms"])
                 imu = np.ascontiguousarray(np.tile(win, K))
                 off = (np.arange(K + 1) * len(win)).astype(np.int64)
                 tf = np.full(K, t_new)
@@ -125,7 +150,7 @@ def main():
                     for it in range(iters):
                         prior_px = h["offset"][:, :, :2].reshape(K, 8) * 159.5
                         prior_cam = np.ascontiguousarray(h["offset"][:, :, :2].reshape(K, 8))
-                        mean, cov = s2.infer(ids, prior_px)
+                        mean, cov = s2.infer(ids, prior_px, iteration=it) if a.iter_variant else s2.infer(ids, prior_px)
                         ref.ref_update_batch(C.c_void_p(h.ctypes.data), params, K, C.c_void_p(mean.ctypes.data), C.c_void_p(cov.ctypes.data),
                                              C.c_void_p(prior_cam.ctypes.data), C.c_void_p(gate.ctypes.data), int(it != iters - 1), T)
                     ref.ref_reset_batch(C.c_void_p(h.ctypes.data), K)
@@ -144,6 +169,12 @@ def main():
                 rec[f"host_loop_{T}t_ms_p10"] = pct(host_ms[T], 10)
                 rec[f"host_loop_{T}t_ms_p90"] = pct(host_ms[T], 90)
                 rec[f"host_loop_{T}t_ticks_per_s"] = round(1e3 / m, 1)
+            if a.iter_variant:
+                rec["iter_model"] = f"{a.iter_variant} N={a.iter_mc} p={a.iter_p:g}"
+                for name, v in (("iter_step_ms", it_ms), ("iter_step_event_ms", it_dev)):
+                    rec[f"{name}_p50"], rec[f"{name}_p10"], rec[f"{name}_p90"] = pct(v, 50), pct(v, 10), pct(v, 90)
+                rec["iter_over_main"] = round(float(np.median(it_ms)) / float(np.median(dev_ms)), 3)
+                f4.close(); s4.close(); ei4.close(); e4.close()
             if a.feed:
                 tot = [x + y for x, y in zip(feed_ms, adv_ms)]
                 for name, v in (("feed_imu_ms", feed_ms), ("advance_ms", adv_ms), ("feed_tick_ms", tot), ("advance_event_ms", adv_dev)):
@@ -152,6 +183,8 @@ def main():
                 f3.close(); s3.close(); e3.close()
             print(json.dumps(rec), flush=True)
             f.close(); s1.close(); s2.close(); e1.close(); e2.close()
+            if a.iter_variant:
+                ei2.close()
 
 
 if __name__ == "__main__":
