@@ -126,12 +126,21 @@ def synthetic_state(seed: int = 0, offset_gain: float = 30.0, offset_bias: float
     return state
 
 
-def variant_state(seed: int = 0, conv_gain: float = 1.0) -> "OrderedDict[str, np.ndarray]":
+UNC_HEAD_OUT = "model_last_block_list.0.fc_block_4_uncertainty.4"      # Linear(256, 8) of the uncertainty head: its output x 1e-3 is the log-variance
+
+
+def variant_state(seed: int = 0, conv_gain: float = 1.0, unc_gain: float = 1.0) -> "OrderedDict[str, np.ndarray]":
     """synthetic_state(seed) with every trunk convolution scaled by `conv_gain` (activations of O(gain^depth)) and the
     5120-input FC layers scaled back so the corner offsets stay at O(1-10) px.  gain 4 drives activations to O(10^3),
     gain 0.5 drives the features to O(0.1): the two ends of the fp16-plane format's range that the golden vectors pin
-    (tools/gen_golden.py `weights_seed` / `conv_gain`)."""
+    (tools/gen_golden.py `weights_seed` / `conv_gain`).
+    `unc_gain` multiplies weight and bias of the uncertainty head's last layer.  At PyTorch's default initialisation that head gives
+    log-variances of +-4e-5 (exp = 1 to 4e-5: the ensemble's aleatoric term is the identity); unc_gain = 1e5 spreads them over about
+    [-5, 5], variances over 0.007 ... 200 (tests/golden/heads_range, tests/test_gpu_heads_range.py)."""
     st = synthetic_state(seed)
+    if unc_gain != 1.0:
+        for k in (UNC_HEAD_OUT + ".weight", UNC_HEAD_OUT + ".bias"):
+            st[k] = (st[k] * np.float32(unc_gain)).astype(np.float32)
     if conv_gain != 1.0:
         g = np.float32(conv_gain)
         for k in st:

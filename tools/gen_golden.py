@@ -13,7 +13,11 @@ Recipe follows SURVEY.md Appendix B:
     are replaced by a module multiplying with keep_mask/(1-p) from include/hnet_rng.h
   - prior variants via `blocks_to_run` (model_to_trace.py:72,129-193)
 
-usage: python tools/gen_golden.py [--out tests/golden]
+A second group, `--group heads_range`, writes tests/golden/heads_range/*.npz: the same recipe on weights whose uncertainty head is
+scaled by unc_gain = 1e5 (weights.variant_state), so that the per-sample log-variances span about [-5, 5] instead of +-4e-5, plus the
+reference's per-sample head outputs (`mean_s`, `logvar_s` [N][8] of the fp64 run, `mean_s32`, `logvar_s32` of the fp32 run).  It leaves every other file alone.
+
+usage: python tools/gen_golden.py [--out tests/golden] [--group forward|heads_range]
 """
 import argparse
 import os
@@ -82,11 +86,16 @@ def layer_stats(t):
     return np.concatenate([[a.sum(), np.sqrt((a * a).sum()), float(n)], a[idx.astype(np.int64)]])
 
 
-def run_case(m, p1, lb, img1, img2, prior, blocks_to_run, dtype=torch.float32):
-    """returns dict of outputs + per-layer stats + recorded DLT calls"""
+def run_case(m, p1, lb, img1, img2, prior, blocks_to_run, dtype=torch.float32, per_sample=False):
+    """returns dict of outputs + per-layer stats + recorded DLT calls (per_sample: + the two heads' outputs of every MC sample)"""
     rec = {"dlt_dst": [], "dlt_H": []}
     stats = {}
     hooks = []
+    heads = {}
+    if per_sample:      # run_fc (model_to_trace.py:252-256): [N, 8] per head, the log-variance is the uncertainty head x 1e-3
+        hooks.append(lb.fc_block_4_mean.register_forward_hook(lambda _m, _i, o: heads.__setitem__("mean_s", o.detach().double().numpy().reshape(-1, 8).copy())))
+        hooks.append(lb.fc_block_4_uncertainty.register_forward_hook(
+            lambda _m, _i, o: heads.__setitem__("logvar_s", (o.detach() * 1e-03).double().numpy().reshape(-1, 8).copy())))
     for name, mod in list(p1.named_children()) + list(lb.named_children()):
         if name.startswith("block_") or name.startswith("fc_block_"):
             hooks.append(mod.register_forward_hook(lambda _m, _i, o, name=name: stats.__setitem__(name, layer_stats(o))))
@@ -128,6 +137,7 @@ def run_case(m, p1, lb, img1, img2, prior, blocks_to_run, dtype=torch.float32):
     }
     for k, v in stats.items():
         out["L_" + k] = v
+    out.update(heads)
     return out
 
 
@@ -147,6 +157,8 @@ WARP_H = {
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(REPO, "tests", "golden"))
+    ap.add_argument("--group", choices=("forward", "heads_range"), default="forward",
+                    help="forward: the cases of tests/golden/*.npz and the operator vectors; heads_range: tests/golden/heads_range/*.npz only")
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
     torch.manual_seed(0)
@@ -155,7 +167,7 @@ def main():
     states = {}
 
     def state_of(c):
-        key = (c.get("wseed", 0), c.get("gain", 1.0))
+        key = (c.get("wseed", 0), c.get("gain", 1.0), c.get("unc_gain", 1.0))
         if key not in states:
             states[key] = weights.variant_state(*key)
         return states[key]
@@ -196,6 +208,14 @@ def main():
     for k in (40, 200, 333, 500):
         cases.append(dict(name=f"traj_pair{k}_prior3", kind="replay", seed=k, variant="prior3", p=0.05, n_mc=16, pair_seq=k))
 
+    if args.group == "heads_range":
+        # --- the uncertainty head away from its initialisation (unc_gain = 1e5: log-variances over about [-5, 5], covariance diagonals 0.04 ... 80):
+        # both finish paths' sample counts (16; 5 = a ragged chunk of 4, fewer than 8) and, at p = 0.5, an epistemic term the size of the aleatoric one
+        cases = [dict(name="heads_range/full_mask16_u1e5_s12", kind="pair", seed=12, variant="full", p=0.05, n_mc=16, pair_seq=12, unc_gain=1e5),
+                 dict(name="heads_range/full_mask5_p50_u1e5_s13", kind="pair", seed=13, variant="full", p=0.5, n_mc=5, pair_seq=13, unc_gain=1e5),
+                 dict(name="heads_range/prior3_pm15_u1e5_s14", kind="pair", seed=14, variant="prior3", p=0.05, n_mc=16, pair_seq=14, prior_amp=15.0,
+                      unc_gain=1e5)]
+        os.makedirs(os.path.join(args.out, "heads_range"), exist_ok=True)
     btr = {"full": 3, "prior3": 3, "prior2": 2, "prior1": 1}
     floor = []
     for c in cases:
@@ -231,7 +251,9 @@ def main():
         else:
             m, p1, lb = m0, p1_0, lb_0
             lb.MC_dropout_num = c["n_mc"]
-        out = run_case(m, p1, lb, f1, f2, prior, btr[c["variant"]])
+        out = run_case(m, p1, lb, f1, f2, prior, btr[c["variant"]], per_sample="unc_gain" in c)
+        if "unc_gain" in c:
+            meta.update(unc_gain=np.float64(c["unc_gain"]), mean_s32=out.pop("mean_s"), logvar_s32=out.pop("logvar_s"))
         out.update(meta)
         out.update(variant=c["variant"], p=np.float32(c["p"]), n_mc=c["n_mc"], kind=c["kind"],
                    seed=c.get("seed", -1), weights_seed=c.get("wseed", 0), conv_gain=np.float64(c.get("gain", 1.0)))
@@ -245,16 +267,20 @@ def main():
         if c["p"] > 0:
             inject_masks(l64, c["pair_seq"], c["n_mc"], c["p"])
         o64 = run_case(m64, p64, l64, f1.astype(np.float64), f2.astype(np.float64),
-                       None if prior is None else prior.astype(np.float64), btr[c["variant"]], torch.float64)
+                       None if prior is None else prior.astype(np.float64), btr[c["variant"]], torch.float64, per_sample="unc_gain" in c)
         d = np.abs(o64["mean"] - out["mean"]).max()
         dc = np.abs(o64["cov"] - out["cov"]).max() / np.abs(o64["cov"]).max()
         floor.append(d)
         msg += f" | fp32-vs-fp64: mean {d:.2e} px, cov rel {dc:.2e}"
         extra = {"mean64": o64["mean"], "cov64": o64["cov"], "H_part1_64": o64["H_part1"], "dlt_dst64": o64["dlt_dst"],
                  "err_stats64": o64["err_stats"]}
+        if "unc_gain" in c:      # the reference's per-sample head outputs (fp64 run, the injected masks; `mean_s32` / `logvar_s32`: its fp32 run)
+            extra.update(mean_s=o64["mean_s"], logvar_s=o64["logvar_s"])
         np.savez_compressed(os.path.join(args.out, c["name"] + ".npz"), **out, **extra)
         print(msg, flush=True)
 
+    if args.group != "forward":
+        return
     # --- standalone warp vectors (warp.py:60-79)
     i1, i2, _ = synth.make_pair(11)
     f2 = u8_to_f32(i2)
