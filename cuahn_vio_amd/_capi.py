@@ -39,9 +39,12 @@ SYMBOLS = [
     "hnet_filter_default_init_params", "hnet_filters_enable_feed", "hnet_filters_set_init_params", "hnet_filters_feed_imu", "hnet_filters_initialized",
     "hnet_filters_uninitialize", "hnet_filters_advance", "hnet_filters_last_selection",
     "hnet_sessions_set_iterative_model", "hnet_sessions_infer_iter",
+    "hnet_filters_predict", "hnet_filters_newest_imu_time", "hnet_filters_last_predict_device_ms",
 ]
 # hnet_filters_advance's status per listed session (include/hnet.h HNET_ADV_*)
 ADV_STEPPED, ADV_WAIT_IMU, ADV_WAIT_INIT, ADV_INITIALIZED, ADV_PROPAGATED, ADV_NO_FRAME = range(6)
+# hnet_filters_predict's status per listed session (include/hnet.h HNET_PRED_*)
+PRED_OK, PRED_NO_STATE, PRED_WAIT_IMU, PRED_AT_STATE = range(4)
 
 
 class Config(C.Structure):
@@ -79,6 +82,10 @@ class InitParams(C.Structure):
 FILTER_STATE_DTYPE = _np.dtype([("t", "<f8"), ("p", "<f8", 3), ("q", "<f8", 4), ("v", "<f8", 3), ("ba", "<f8", 3), ("bg", "<f8", 3),
                                 ("offset", "<f8", (4, 3)), ("cov", "<f8", (27, 27))])
 IMU_DTYPE = _np.dtype([("t", "<f8"), ("wm", "<f8", 3), ("am", "<f8", 3)])
+# hnet_odometry: what hnet_filters_predict writes per listed session
+ODOMETRY_DTYPE = _np.dtype([("t_cam", "<f8"), ("t_imu", "<f8"), ("p", "<f8", 3), ("q", "<f8", 4), ("v", "<f8", 3), ("w_pos", "<f8", 3),
+                            ("rpy", "<f8", 3), ("body_pos", "<f8", 3), ("body_vel", "<f8", 3), ("prior_px", "<f8", 8),
+                            ("intervals", "<i4"), ("status", "<i4")])
 
 
 class HnetError(RuntimeError):
@@ -207,6 +214,11 @@ def lib():
     L.hnet_filters_uninitialize.argtypes = [vp, C.c_int]
     L.hnet_filters_advance.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
     L.hnet_filters_last_selection.argtypes = [vp, C.c_int, vp, C.c_int, C.POINTER(C.c_int)]
+    L.hnet_filters_predict.argtypes = [vp, C.c_int, vp, vp, vp]
+    L.hnet_filters_newest_imu_time.argtypes = [vp, C.c_int]
+    L.hnet_filters_newest_imu_time.restype = C.c_double
+    L.hnet_filters_last_predict_device_ms.argtypes = [vp]
+    L.hnet_filters_last_predict_device_ms.restype = C.c_double
     for name in SYMBOLS:
         getattr(L, name)   # AttributeError here = the library does not export what include/hnet.h declares
     _lib = L

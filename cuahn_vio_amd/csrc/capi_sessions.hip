@@ -391,6 +391,14 @@ struct hnet_filters {
     uint8_t* pin_adv = nullptr;
     uint8_t* d_adv = nullptr;
     size_t off_res = 0;
+    // predict (hnet_filters_predict), allocated by its first call: ONE block {jobs [B] | records [B]}, its pinned copy, and the kernel's own scratch
+    uint8_t* pin_pred = nullptr;
+    uint8_t* d_pred = nullptr;
+    hnet_ekf::ImuData* d_pred_sel = nullptr;   // [B][2 (cap + 2)]
+    size_t off_pred_out = 0;
+    hipEvent_t ev_p0 = nullptr, ev_p1 = nullptr;
+    bool pred_timed = false;                   // set by the first hnet_filters_last_predict_device_ms: only then a predict records its two events
+    double pred_ms = NAN;
 };
 
 static size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -453,7 +461,10 @@ void hnet_destroy_filters(hnet_filters* f) {
     (void)hipStreamSynchronize(c->stream);
     auto fr = [](void* p) { if (p) (void)hipFree(p); };
     fr(f->d_state); fr(f->d_params); fr(f->d_out); fr(f->d_prior_cam); fr(f->d_in);
-    fr(f->d_ring); fr(f->d_meta); fr(f->d_ip); fr(f->d_sel); fr(f->d_feed); fr(f->d_adv);
+    fr(f->d_ring); fr(f->d_meta); fr(f->d_ip); fr(f->d_sel); fr(f->d_feed); fr(f->d_adv); fr(f->d_pred); fr(f->d_pred_sel);
+    if (f->pin_pred) (void)hipHostFree(f->pin_pred);
+    if (f->ev_p0) (void)hipEventDestroy(f->ev_p0);
+    if (f->ev_p1) (void)hipEventDestroy(f->ev_p1);
     if (f->pin_feed) (void)hipHostFree(f->pin_feed);
     if (f->pin_adv) (void)hipHostFree(f->pin_adv);
     if (f->ev_feed) (void)hipEventDestroy(f->ev_feed);
@@ -989,6 +1000,85 @@ int hnet_filters_last_selection(hnet_filters* f, int id, hnet_imu* out, int cap,
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     return HNET_OK;
+}
+
+// ---- filters, between frames (include/hnet.h): hnet_filters_predict.  Read-only: nothing of the filters' or the sessions' bookkeeping is written.
+
+static_assert(sizeof(hnet_odometry) == sizeof(PredictOut), "hnet_odometry is the PredictOut layout");
+static_assert(HNET_PRED_OK == PRED_OK && HNET_PRED_NO_STATE == PRED_NO_STATE && HNET_PRED_WAIT_IMU == PRED_WAIT_IMU && HNET_PRED_AT_STATE == PRED_AT_STATE,
+              "HNET_PRED_* are the kernel's codes");
+
+// the call's buffers, made once: the kernel's scratch is its own, so that hnet_filters_last_selection keeps describing the last advance
+static int predict_buffers(hnet_filters* f) {
+    if (f->d_pred) return HNET_OK;
+    hnet_ctx* c = f->s->ctx;
+    const int B = c->cfg.max_batch;
+    f->off_pred_out = al256((size_t)B * sizeof(PredictJob));
+    const size_t bytes = f->off_pred_out + (size_t)B * sizeof(PredictOut);
+    hipError_t e = hipMalloc((void**)&f->d_pred_sel, (size_t)B * 2 * (f->cap + 2) * sizeof(hnet_ekf::ImuData));
+    if (e == hipSuccess) e = hipHostMalloc((void**)&f->pin_pred, bytes, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipEventCreate(&f->ev_p0);
+    if (e == hipSuccess) e = hipEventCreate(&f->ev_p1);
+    if (e == hipSuccess) e = hipMalloc((void**)&f->d_pred, bytes);
+    if (e != hipSuccess) {
+        if (f->d_pred_sel) (void)hipFree(f->d_pred_sel);
+        if (f->pin_pred) (void)hipHostFree(f->pin_pred);
+        if (f->ev_p0) (void)hipEventDestroy(f->ev_p0);
+        if (f->ev_p1) (void)hipEventDestroy(f->ev_p1);
+        f->d_pred_sel = nullptr; f->pin_pred = nullptr; f->ev_p0 = f->ev_p1 = nullptr; f->d_pred = nullptr;
+        return fail(c, HNET_ERR_DEVICE, std::string("hnet_filters_predict: ") + hipGetErrorString(e));
+    }
+    return HNET_OK;
+}
+
+int hnet_filters_predict(hnet_filters* f, int n, const int32_t* ids, const double* t_query, hnet_odometry* out) {
+    if (!f) return HNET_ERR_INVALID_ARG;
+    hnet_sessions* s = f->s;
+    hnet_ctx* c = s->ctx;
+    if (!f->cap) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_predict: feed not enabled (hnet_filters_enable_feed)");
+    if (!t_query || !out) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_predict: t_query / out");
+    int rc = sessions_check_ids(s, n, ids);
+    if (rc != HNET_OK) return rc;
+    for (int i = 0; i < n; i++)
+        if (!std::isfinite(t_query[i])) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_predict: t_query must be finite");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    if ((rc = predict_buffers(f)) != HNET_OK) return rc;
+    PredictJob* job = reinterpret_cast<PredictJob*>(f->pin_pred);
+    for (int i = 0; i < n; i++) {
+        const int id = ids[i];
+        const double dt = f->cam_imu_dt[id];
+        int st = PRED_OK;                                          // (the kernel reports AT_STATE from the device's own state time)
+        if (!f->inited[id]) st = PRED_NO_STATE;
+        else if (t_query[i] > f->t[id] && !(t_query[i] < f->imu_newest[id] - dt)) st = PRED_WAIT_IMU;
+        job[i] = PredictJob{t_query[i], dt, id, st};
+    }
+    hipStream_t st = c->stream;
+    PredictOut* d_out = reinterpret_cast<PredictOut*>(f->d_pred + f->off_pred_out);
+    HIPCHK(c, hipMemcpyAsync(f->d_pred, f->pin_pred, (size_t)n * sizeof(PredictJob), hipMemcpyHostToDevice, st));
+    if (f->pred_timed) HIPCHK(c, hipEventRecord(f->ev_p0, st));
+    HIPCHK(c, launch_filter_predict(reinterpret_cast<const PredictJob*>(f->d_pred), n, s->n, f->cap, f->d_ring, f->d_meta, f->d_state, f->d_params, f->d_pred_sel,
+                                    d_out, st));
+    if (f->pred_timed) HIPCHK(c, hipEventRecord(f->ev_p1, st));
+    HIPCHK(c, hipMemcpyAsync(f->pin_pred + f->off_pred_out, d_out, (size_t)n * sizeof(PredictOut), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    memcpy(out, f->pin_pred + f->off_pred_out, (size_t)n * sizeof(PredictOut));
+    if (f->pred_timed) {
+        float ms = 0;
+        HIPCHK(c, hipEventElapsedTime(&ms, f->ev_p0, f->ev_p1));
+        f->pred_ms = ms;
+    }
+    return HNET_OK;
+}
+
+double hnet_filters_newest_imu_time(const hnet_filters* f, int id) {
+    if (!f || !f->cap || id < 0 || id >= f->s->n || !std::isfinite(f->imu_newest[id])) return NAN;
+    return f->imu_newest[id];
+}
+
+double hnet_filters_last_predict_device_ms(hnet_filters* f) {
+    if (!f) return NAN;
+    f->pred_timed = true;
+    return f->pred_ms;
 }
 
 }  // extern "C"

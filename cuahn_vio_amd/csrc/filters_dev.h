@@ -72,5 +72,26 @@ hipError_t launch_filter_propagate_adv(const AdvanceJob* job, int n, int n_sessi
                                        const hnet_ekf::ImuData* sel, const AdvanceResult* res, FilterRec* work, hipStream_t s);
 hipError_t launch_filter_scatter_ok(const FilterRec* work, const AdvanceJob* job, const AdvanceResult* res, int n, int n_sessions, FilterRec* state, hipStream_t s);
 
+// ---- prediction between frames (hnet_filters_predict): read-only over the states and the rings.
+// what the call asks for one listed session: status is HNET_PRED_OK (the kernel predicts, or reports AT_STATE when t_query <= the state's t) or the
+// host's refusal (NO_STATE / WAIT_IMU: the record is zero apart from it)
+struct PredictJob {
+    double t_query, cam_imu_dt;
+    int32_t id, status;
+};
+constexpr int PRED_OK = 0, PRED_NO_STATE = 1, PRED_WAIT_IMU = 2, PRED_AT_STATE = 3;      // include/hnet.h HNET_PRED_*
+// the layout of hnet_odometry: hnet_ekf::Odometry, the pixel prior, intervals and status
+struct PredictOut {
+    hnet_ekf::Odometry o;
+    double prior_px[8];
+    int32_t intervals, status;
+};
+constexpr int PREDICT_OUT_DOUBLES = (int)(sizeof(PredictOut) / sizeof(double));     // 33
+static_assert(sizeof(PredictOut) == 33 * sizeof(double), "PredictOut must be 32 packed doubles and two ints");
+constexpr int PREDICT_THREADS = 64;
+// scratch: [n][2 * (cap + 2)] readings of the call's own (the span, then the selection), never the advance's sel
+hipError_t launch_filter_predict(const PredictJob* job, int n, int n_sessions, int cap, const hnet_ekf::ImuData* ring, const ImuRingMeta* meta,
+                                 const FilterRec* state, const FilterParams* params, hnet_ekf::ImuData* scratch, PredictOut* out, hipStream_t s);
+
 }  // namespace hnet
 #endif  // HNET_FILTERS_DEV_H

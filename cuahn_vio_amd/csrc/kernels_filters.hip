@@ -409,6 +409,93 @@ __global__ __launch_bounds__(FILTER_THREADS) void filter_scatter_ok_kernel(const
     store_rec(state[id], work[b]);
 }
 
+// ---- prediction between frames (hnet_filters_predict) ----
+
+namespace {
+constexpr int REC_MEAN_DOUBLES = 29;                                          // t, then p q v ba bg offset: everything of a FilterRec before cov
+static_assert(offsetof(FilterRec, s) + offsetof(hnet_ekf::State, cov) == REC_MEAN_DOUBLES * sizeof(double), "t and the mean are the record's first 29 doubles");
+}  // namespace
+
+// The mean of each listed session at job[b].t_query and what the reference's publishers form from it (hnet_ekf::propagate_mean_with_imu +
+// odometry_from_state + prior_pixels), one wavefront per session: the chain of mean updates is serial, the parallelism is across the sessions.  Of
+// state[id] only t and the mean are read: S has room for the covariance only because propagate_mean takes a State&, S.s.cov is never loaded and
+// nothing here may read it.  The ring is counted and the span copied as filter_select_kernel does, restated here and not shared with it, so that the
+// advance's kernel stays textually as it was and keeps its code; lane 0 then runs the header's selection and mean loop on it.  Reads state / ring / meta / params, writes out[b] and
+// scratch + b * 2 * (cap + 2) (the span [cap + 2], then the selection [cap + 2]) only.  A job the host refused (NO_STATE / WAIT_IMU) gets a zero
+// record with that status, as does a ring the kernel finds empty or inconsistent (WAIT_IMU); t_query <= the state's t gives the state as it is
+// (AT_STATE, 0 intervals).
+__global__ __launch_bounds__(PREDICT_THREADS) void filter_predict_kernel(const PredictJob* __restrict__ job, int n_sessions, int cap,
+                                                                         const hnet_ekf::ImuData* __restrict__ ring, const ImuRingMeta* __restrict__ meta,
+                                                                         const FilterRec* __restrict__ state, const FilterParams* __restrict__ params,
+                                                                         hnet_ekf::ImuData* __restrict__ scratch, PredictOut* __restrict__ out) {
+    __shared__ FilterRec S;
+    __shared__ PredictOut R;
+    __shared__ int cnt[3];
+    const int b = blockIdx.x, t = threadIdx.x;
+    const PredictJob jb = job[b];
+    const int id = jb.id;
+    double* rw = reinterpret_cast<double*>(&R);
+    for (int i = t; i < PREDICT_OUT_DOUBLES; i += PREDICT_THREADS) rw[i] = 0.0;          // (all-zero bits: intervals and status too)
+    if (t < 3) cnt[t] = 0;
+    __syncthreads();
+    int status = (id >= 0 && id < n_sessions) ? jb.status : PRED_NO_STATE;                // (host-validated; uniform over the workgroup, as every test below)
+    if (status == PRED_OK) {
+        const double* src = reinterpret_cast<const double*>(state + id);
+        double* dst = reinterpret_cast<double*>(&S);
+        for (int i = t; i < REC_MEAN_DOUBLES; i += PREDICT_THREADS) dst[i] = src[i];
+        __syncthreads();
+        const double t_state = S.t;
+        hnet_ekf::ImuData* lin = scratch + (size_t)b * 2 * (cap + 2);
+        int len = 0;
+        if (!(jb.t_query > t_state)) status = PRED_AT_STATE;
+        else {
+            const ImuRingMeta m = meta[id];
+            if (!ring_ok(m, cap) || m.count < 1) status = PRED_WAIT_IMU;          // (the host's mirror says so first: an empty ring has no reading past the query)
+            else {
+                const hnet_ekf::ImuData* rg = ring + (size_t)id * cap;
+                const double t0 = t_state + jb.cam_imu_dt, t1 = jb.t_query + jb.cam_imu_dt;
+                const double newest = ring_at(rg, m.head, cap, m.count - 1).t;
+                int c_old = 0, c_lt = 0, c_le = 0;
+                for (int j = t; j < m.count; j += PREDICT_THREADS) {
+                    const double tt = ring_at(rg, m.head, cap, j).t;
+                    if (newest - tt > 10) c_old++;
+                    else { c_lt += tt < t0 ? 1 : 0; c_le += tt <= t1 ? 1 : 0; }
+                }
+                if (c_old) atomicAdd(&cnt[0], c_old);
+                if (c_lt) atomicAdd(&cnt[1], c_lt);
+                if (c_le) atomicAdd(&cnt[2], c_le);
+                __syncthreads();
+                int first = 0;
+                len = hnet_ekf::select_span(m.count - cnt[0], cnt[1], cnt[2], &first);
+                if (len < 1 || len > cap || first < 0 || cnt[0] + first + len > m.count) len = 0;
+                for (int k = t; k < len; k += PREDICT_THREADS) lin[k] = ring_at(rg, m.head, cap, cnt[0] + first + k);
+                __syncthreads();
+            }
+        }
+        if (t == 0 && status != PRED_WAIT_IMU) {
+            const FilterParams& pr = params[id];
+            int done = 0;
+            if (status == PRED_OK)                                                      // the selection writes at most len + 2 readings
+                done = hnet_ekf::propagate_mean_with_imu(S.s, pr.ext, t_state, jb.t_query, lin, len, pr.gravity_mag, pr.imu_avg != 0, jb.cam_imu_dt, lin + (cap + 2));
+            hnet_ekf::odometry_from_state(S.s, status == PRED_OK ? jb.t_query : t_state, jb.cam_imu_dt, R.o);
+            double prior_cam[8];
+            hnet_ekf::prior_pixels(S.s, R.prior_px, prior_cam);
+            R.intervals = done;
+        }
+    }
+    if (t == 0) R.status = status;
+    __syncthreads();
+    double* ow = reinterpret_cast<double*>(out + b);
+    for (int i = t; i < PREDICT_OUT_DOUBLES; i += PREDICT_THREADS) ow[i] = rw[i];
+}
+
+hipError_t launch_filter_predict(const PredictJob* job, int n, int n_sessions, int cap, const hnet_ekf::ImuData* ring, const ImuRingMeta* meta,
+                                 const FilterRec* state, const FilterParams* params, hnet_ekf::ImuData* scratch, PredictOut* out, hipStream_t s) {
+    if (n < 1 || cap < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(filter_predict_kernel, dim3((unsigned)n), dim3(PREDICT_THREADS), 0, s, job, n_sessions, cap, ring, meta, state, params, scratch, out);
+    return hipGetLastError();
+}
+
 hipError_t launch_filter_propagate(const int32_t* ids, int n, int n_sessions, const FilterRec* state, const FilterParams* params, const hnet_ekf::ImuData* rd,
                                    const int32_t* rd_off, const double* t_frame, FilterRec* work, hipStream_t s) {
     if (n < 1) return hipErrorInvalidValue;

@@ -646,6 +646,24 @@ class HnetFilters:
         self._check(self._L.hnet_filters_last_selection(self._f, int(id), out.ctypes.data, cnt.value, C.byref(cnt)))
         return out[:cnt.value]
 
+    def predict(self, ids, t_query):
+        """the listed sessions' states predicted to t_query [n] (camera clock) from the device's IMU rings, read-only, with one launch and one
+        synchronisation -> [n] records of _capi.ODOMETRY_DTYPE (status: _capi.PRED_*)"""
+        ids = np.ascontiguousarray(np.atleast_1d(ids), dtype=np.int32)
+        n = len(ids)
+        tq = np.ascontiguousarray(np.broadcast_to(np.asarray(t_query, dtype=np.float64), (n,)))
+        out = np.zeros(n, _capi.ODOMETRY_DTYPE)
+        self._check(self._L.hnet_filters_predict(self._f, n, ids.ctypes.data, tq.ctypes.data, out.ctypes.data))
+        return out
+
+    def newest_imu_time(self, id):
+        """the time (IMU clock) of the newest reading session id was fed; NaN for an empty ring"""
+        return float(self._L.hnet_filters_newest_imu_time(self._f, int(id)))
+
+    def last_predict_device_ms(self):
+        """event time of the last timed predict's launch; the first call switches the timing on (NaN until a timed predict has run)"""
+        return float(self._L.hnet_filters_last_predict_device_ms(self._f))
+
     def last_priors(self, n):
         """the fp32 priors [iters, n, 8] the forwards of the last step (of n sessions; another n is refused) read"""
         out = np.zeros((self.iters, int(n), 8), np.float32)

@@ -417,6 +417,41 @@ int  hnet_filters_advance(hnet_filters* f, int n, const int32_t* ids, hnet_filte
  * (0 for a session that advance did not propagate) (tests) */
 int  hnet_filters_last_selection(hnet_filters* f, int id, hnet_imu* out, int cap, int* count);
 
+/* ---- filters, between frames: the state predicted to a query time from the IMU rings, read-only ---------------------------------------------
+ * A filter's state is the state at its last camera frame.  A control loop wants the pose and velocity NOW, 10 - 30 ms later, at IMU rate: the
+ * reference node publishes RosVisualizer::visualize_odometry from its IMU callback (ros_subscribe_cuahn.cpp:134), and OpenVINS' fast_state_propagate
+ * (Propagator.h:151, commented out in the reference) carried the state on to the newest reading for it.  hnet_filters_predict does that for the listed
+ * sessions from the readings hnet_filters_feed_imu left on the device: the mean of hnet_ekf::propagate_mean_with_imu (the loop of an advance without the
+ * covariance) from the state's time to t_query[i] (camera clock), then what the reference's two publishers form from a state
+ * (hnet_ekf::odometry_from_state) and the pixel prior a forward at t_query would receive.  p, q, v and prior_px are, bit for bit, what an advance to a
+ * frame stamped t_query computes before its forward (tests/test_gpu_filters_predict.py).  The covariance is not predicted: a caller who needs it advances.
+ * One upload, one launch, one download and one synchronisation on the context's stream, so the call is ordered behind earlier feed_imu / advance calls.
+ * No call changes any state: filter states, rings, image counts, mask sequence numbers, hnet_filters_last_timing / _last_selection / _last_priors and
+ * the steps so far are as before; sessions with any number of images may be listed.  Per listed session:
+ *   HNET_PRED_NO_STATE  the session is not initialised (hnet_filters_initialized).  The record is zero apart from the status.
+ *   HNET_PRED_AT_STATE  t_query <= the state's t: the record describes the state as it is, at the state's time, with 0 intervals (no reading is needed
+ *                       for that, so this is tested before WAIT_IMU).
+ *   HNET_PRED_WAIT_IMU  the newest reading's t - cam_imu_dt <= t_query (the rule of VioManager.cpp:148-149 and of HNET_ADV_WAIT_IMU: the selection closes
+ *                       a window only with a reading beyond it).  The record is zero apart from the status.  For the furthest prediction ask just
+ *                       below hnet_filters_newest_imu_time(id) - cam_imu_dt.
+ *   HNET_PRED_OK        predicted to t_query.  A window that reaches further back than the ring is propagated with what is there, as in the advance.
+ * Errors (a bad or repeated id, n > max_batch, feed not enabled, a t_query that is not finite) write nothing.  The first call allocates the call's own
+ * scratch (as large as the advance's selection buffer). */
+typedef struct hnet_odometry {
+    double t_cam, t_imu;            /* the query time (AT_STATE: the state's); + cam_imu_dt, the stamp of the reference's messages */
+    double p[3], q[4], v[3];        /* the predicted mean, hnet_filter_state layout */
+    double w_pos[3];                /* Rot() * p (publish_state, RosVisualizer.cpp:171) */
+    double rpy[3], body_pos[3], body_vel[3];   /* visualize_odometry (RosVisualizer.cpp:121-144): roll / pitch / yaw, front-right-down position and velocity */
+    double prior_px[8];             /* what a forward at t_cam would receive as its prior (offsets x 159.5, VioManager.cpp:230-234) */
+    int32_t intervals, status;      /* IMU intervals integrated; HNET_PRED_* */
+} hnet_odometry;
+enum { HNET_PRED_OK = 0, HNET_PRED_NO_STATE = 1, HNET_PRED_WAIT_IMU = 2, HNET_PRED_AT_STATE = 3 };
+int    hnet_filters_predict(hnet_filters* f, int n, const int32_t* ids, const double* t_query, hnet_odometry* out);
+double hnet_filters_newest_imu_time(const hnet_filters* f, int id);   /* the host mirror's value (IMU clock); NaN: empty ring, feed not enabled or bad id */
+/* tools: the launch of the last timed predict, HIP events, ms.  A predict records no events until this has been called once, so a caller at IMU rate
+ * never pays for them; the first call switches the timing on and returns NaN, as does every call before a timed predict */
+double hnet_filters_last_predict_device_ms(hnet_filters* f);
+
 int hnet_synchronize(hnet_ctx* ctx, void* stream);
 int hnet_last_timing(const hnet_ctx* ctx, hnet_timing* out);
 

@@ -543,6 +543,70 @@ inline int propagate_with_imu(State& s, const Extrinsics& e, double t_state, dou
     return done;
 }
 
+/* ---- prediction between frames: the mean at a query time past the state's, and what the reference's publishers form from it.
+ * OpenVINS' fast_state_propagate, which carried the state on to the newest inertial reading for the odometry message, is still in the reference,
+ * commented out (Propagator.h:151); its node publishes visualize_odometry from the IMU callback "for onboard feedback control"
+ * (ros_subscribe_cuahn.cpp:134).  hnet_filters_predict (include/hnet.h) runs these on the device's IMU rings; tests/test_filters_predict_cpu.py. */
+
+/* The loop of propagate_with_imu without propagate_jacobians and propagate_cov: the same select_imu_readings, imu_interval_inputs and propagate_mean
+ * in the same order, so p, q, v, ba, bg and the offsets come out as propagate_with_imu leaves them; s.cov is neither read nor written.  t_state /
+ * t_query: camera clock.  Returns the number of intervals, or -1 for t_query <= t_state (nothing written).  `scratch` has room for n + 2 readings. */
+inline int propagate_mean_with_imu(State& s, const Extrinsics& e, double t_state, double t_query, const ImuData* readings, int n,
+                                   double gravity_mag, bool imu_avg, double cam_imu_dt, ImuData* scratch) {
+    if (!(t_query > t_state)) return -1;
+    const int m = select_imu_readings(readings, n, t_state + cam_imu_dt, t_query + cam_imu_dt, scratch);
+    int done = 0;
+    for (int i = 0; i + 1 < m; i++) {
+        double w_hat[3], a_hat[3];
+        const double dt = imu_interval_inputs(s, scratch[i], scratch[i + 1], imu_avg, w_hat, a_hat);
+        propagate_mean(s, e, dt, w_hat, a_hat, gravity_mag);
+        done++;
+    }
+    return done;
+}
+
+/* What RosVisualizer::publish_state (RosVisualizer.cpp:157-174) and RosVisualizer::visualize_odometry (:113-144) form from a state: 24 packed doubles,
+ * the head of hnet_odometry (include/hnet.h). */
+struct Odometry {
+    double t_cam, t_imu;               /* the state's time; + cam_imu_dt, the stamp of both messages (:157-158, :113-114) */
+    double p[3], q[4], v[3];           /* the mean as it is (State layout); q is published as it is (:165-168) */
+    double w_pos[3];                   /* Rot() * pos (:171, :132) */
+    double rpy[3];                     /* roll, pitch, yaw of b_R_w (:123-128) */
+    double body_pos[3], body_vel[3];   /* front-right-down: (-w_pos[1], -w_pos[0], -w_pos[2]) (:134-136), (-v[1], -v[0], -v[2]) (:141-144) */
+};
+
+/* RosVisualizer::Rot2Euler (RosVisualizer.cpp:303-315) of a row-major 3 x 3 matrix, the sy < 1e-6 branch (pitch near 90 degrees) included */
+inline void rot_to_euler(const double R[9], double& roll, double& pitch, double& yaw) {
+    const double sy = std::sqrt(R[1 * 3 + 2] * R[1 * 3 + 2] + R[2 * 3 + 2] * R[2 * 3 + 2]);
+    if (sy < 1e-6) {
+        yaw = 0.0;
+        roll = std::atan2(-R[2 * 3 + 1], R[1 * 3 + 1]);
+    } else {
+        yaw = std::atan2(R[0 * 3 + 1], R[0 * 3 + 0]);
+        roll = std::atan2(R[1 * 3 + 2], R[2 * 3 + 2]);
+    }
+    pitch = std::atan2(-R[0 * 3 + 2], sy);
+}
+
+/* Rot() of the reference's pose (PoseCUAHN.h:119 -> HamQuat.h:80,104) is Ham_quat_2_Rot of the state's quaternion (quat_ops.h:546-550): quat_to_rot above.
+ * b_R_w = i0_R_w^T Rot()^T i0_R_w (:123) with i0_R_w = [0 -1 0; -1 0 0; 0 0 -1] (:64), multiplied left to right as Eigen evaluates it. */
+inline void odometry_from_state(const State& s, double t_cam, double cam_imu_dt, Odometry& o) {
+    o.t_cam = t_cam;
+    o.t_imu = t_cam + cam_imu_dt;
+    for (int i = 0; i < 3; i++) { o.p[i] = s.p[i]; o.v[i] = s.v[i]; }
+    for (int i = 0; i < 4; i++) o.q[i] = s.q[i];
+    double R[9], Rt[9], A[9], B[9];
+    quat_to_rot(s.q, R);
+    mat3_vec(R, s.p, o.w_pos);
+    const double i0_R_w[9] = {0.0, -1.0, 0.0, -1.0, 0.0, 0.0, 0.0, 0.0, -1.0};      /* symmetric: its own transpose */
+    m3::transpose(R, Rt);
+    m3::mul(i0_R_w, Rt, A);
+    m3::mul(A, i0_R_w, B);
+    rot_to_euler(B, o.rpy[0], o.rpy[1], o.rpy[2]);
+    o.body_pos[0] = -o.w_pos[1]; o.body_pos[1] = -o.w_pos[0]; o.body_pos[2] = -o.w_pos[2];
+    o.body_vel[0] = -s.v[1]; o.body_vel[1] = -s.v[0]; o.body_vel[2] = -s.v[2];
+}
+
 /* ---- initialisation from a standing start: what VioManager::try_to_initialize (VioManager.cpp:312-363) does with the buffered IMU
  * readings: InertialInitializer::initialize_with_imu_CUAHN (ov_core/src/init/InertialInitializer.cpp:163-279) for the mean and
  * StateHelper::initialize_Cov (StateHelper.cpp:35-61) for the covariance.  The device filters (hnet_filters_advance, include/hnet.h) form the window

@@ -13,8 +13,13 @@ call, the advance call and their sum, next to the step column of the same proces
 context whose sessions have an iterative engine of variant V attached, so its forwards 1 .. I-1 run on that model ("iter_step" columns, and
 iter_over_main = its median over the device step's, which runs every iteration on the main model); the host loop then runs iterations > 0 through
 hnet_sessions_infer_iter on an iterative engine attached to its sessions.
+--predict is a mode of its own (hnet_filters_predict): one fed filters object per K with the same 16-interval ticks; per tick, once the
+frame is pushed and the readings are fed, one predict of all K sessions to the frame's time (wall time of the call and the event time of its launch),
+the host alternative on the same inputs (hnet_filters_get_state of the K sessions + hnet_ekf::propagate_mean_with_imu / odometry_from_state over a
+host copy of the histories, tests/cpp/filters_predict_ref.cpp, on T threads), then the advance of the same sessions, which is the reference point.
    python tools/filters_bench.py [--k 1,8,64,256] [--iters 1,3] [--ticks 20] [--warmup 3] [--threads 1,16] [--feed]
-                                 [--iter-variant prior1 --iter-mc 8 --iter-p 0.1]"""
+                                 [--iter-variant prior1 --iter-mc 8 --iter-p 0.1]
+   python tools/filters_bench.py --predict [--k 1,8,64,256] [--ticks 20] [--warmup 3] [--threads 1,16]"""
 import argparse
 import ctypes as C
 import json
@@ -45,6 +50,91 @@ def imu_window(rng, t0, n_int=16, dt=0.002):
     return r
 
 
+def predict_mode(a):
+    from cuahn_vio_amd import _capi, replay, weights
+    from cuahn_vio_amd.homography_net import HnetEngine, HnetFilters, HnetSessions
+    so = os.path.join(tempfile.mkdtemp(prefix="filters_predict_ref_"), "filters_predict_ref.so")
+    subprocess.run(["g++", "-std=c++17", "-O2", "-shared", "-fPIC", "-pthread", "-I", os.path.join(ROOT, "include"),
+                    os.path.join(ROOT, "tests", "cpp", "filters_predict_ref.cpp"), "-o", so], check=True)
+    ref = C.CDLL(so)
+    ref.pred_ref_predict_batch.restype = None
+    blob = weights.pack_state_dict(weights.synthetic_state(0))
+    fx = replay.load_fixture("indoor_forward_7")
+    pool = np.stack([replay.render_frame(fx, 100 + j) for j in range(16)])
+    threads = [int(x) for x in a.threads.split(",")]
+
+    def pct(x, q):
+        return round(float(np.percentile(x, q)), 3)
+
+    for K in [int(x) for x in a.k.split(",")]:
+        e = HnetEngine(blob, max_batch=K, variant="prior3", mc_samples=16, dropout_p=0.05, mc_seed=1)
+        s = HnetSessions(e, K)
+        f = HnetFilters(s, 1)
+        f.enable_feed(256)
+        f.last_predict_device_ms()                               # switches the predict's event timing on
+        p = HnetFilters.default_params()
+        params = (_capi.FilterParams * K)(*([p] * K))
+        ids = np.arange(K, dtype=np.int32)
+        st0 = np.zeros(1, _capi.FILTER_STATE_DTYPE)
+        st0["q"] = [1, 0, 0, 0]
+        st0["p"] = [0, 0, -1.0]
+        st0["cov"] = np.diag(np.r_[np.full(15, 1e-3), np.full(12, 1e-6)])
+        for i in range(K):
+            f.set_state(i, st0[0])
+        rng = np.random.default_rng(K)
+        hist = np.zeros(0, _capi.IMU_DTYPE)                      # the host alternative's copy of one session's history (all K are fed the same)
+        newest, t = -np.inf, 0.0
+        pred_ms, pred_dev, adv_ms, adv_dev, host_ms = [], [], [], [], {T: [] for T in threads}
+        for tick in range(a.warmup + a.ticks + 1):
+            t_new = t + 0.0325
+            s.push(ids, np.repeat(pool[tick % len(pool)][None], K, 0), t=[t_new] * K)
+            win = imu_window(rng, t)
+            new = win[win["t"] > newest]
+            newest = float(new["t"][-1])
+            f.feed_imu(ids, [new] * K)
+            hist = np.concatenate([hist, new])[-256:]
+            tq = np.full(K, t_new)
+            t0 = time.perf_counter()
+            o = f.predict(ids, tq)
+            d = (time.perf_counter() - t0) * 1e3
+            assert (o["status"] == _capi.PRED_OK).all() and (o["intervals"] == o["intervals"][0]).all(), (o["status"], o["intervals"])
+            keep = tick > a.warmup
+            if keep:
+                pred_ms.append(d)
+                pred_dev.append(f.last_predict_device_ms())
+            imu = np.ascontiguousarray(np.tile(hist, K))
+            off = (np.arange(K + 1) * len(hist)).astype(np.int64)
+            for T in threads:
+                out = np.zeros(K, _capi.ODOMETRY_DTYPE)
+                t0 = time.perf_counter()
+                st = f.get_state(ids)
+                ref.pred_ref_predict_batch(C.c_void_p(st.ctypes.data), params, K, C.c_void_p(tq.ctypes.data), C.c_void_p(imu.ctypes.data),
+                                           C.c_void_p(off.ctypes.data), T, C.c_void_p(out.ctypes.data))
+                if keep:
+                    host_ms[T].append((time.perf_counter() - t0) * 1e3)
+                assert np.abs(out["p"] - o["p"]).max() < 1e-9 and (out["intervals"] == o["intervals"]).all()
+            if tick > 0:                                          # (one image per session at tick 0: that advance propagates only)
+                t0 = time.perf_counter()
+                _, _, _, status = f.advance(ids)
+                d = (time.perf_counter() - t0) * 1e3
+                assert (status == _capi.ADV_STEPPED).all(), status
+                if keep:
+                    adv_ms.append(d)
+                    adv_dev.append(f.last_timing()["device_ms"])
+            else:
+                f.advance(ids)
+            t = t_new
+        rec = {"K": K, "intervals": int(o["intervals"][0]), "ticks": len(pred_ms)}
+        for name, v in (("predict_ms", pred_ms), ("predict_event_ms", pred_dev), ("advance_ms", adv_ms), ("advance_event_ms", adv_dev)):
+            rec[f"{name}_p50"], rec[f"{name}_p10"], rec[f"{name}_p90"] = pct(v, 50), pct(v, 10), pct(v, 90)
+        for T in threads:
+            rec[f"host_predict_{T}t_ms_p50"], rec[f"host_predict_{T}t_ms_p10"], rec[f"host_predict_{T}t_ms_p90"] = (pct(host_ms[T], 50), pct(host_ms[T], 10),
+                                                                                                               pct(host_ms[T], 90))
+        rec["predict_over_advance"] = round(float(np.median(pred_ms)) / float(np.median(adv_ms)), 4)
+        print(json.dumps(rec), flush=True)
+        f.close(); s.close(); e.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--k", default="1,8,64,256")
@@ -53,10 +143,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--threads", default="1,16")
     ap.add_argument("--feed", action="store_true")
+    ap.add_argument("--predict", action="store_true")
     ap.add_argument("--iter-variant", default=None)
     ap.add_argument("--iter-mc", type=int, default=8)
     ap.add_argument("--iter-p", type=float, default=0.1)
     a = ap.parse_args()
+    if a.predict:
+        return predict_mode(a)
     from cuahn_vio_amd import _capi, replay, weights
     from cuahn_vio_amd.homography_net import HnetEngine, HnetFilters, HnetSessions
     ref = build_ref()
