@@ -40,11 +40,15 @@ SYMBOLS = [
     "hnet_filters_uninitialize", "hnet_filters_advance", "hnet_filters_last_selection",
     "hnet_sessions_set_iterative_model", "hnet_sessions_infer_iter",
     "hnet_filters_predict", "hnet_filters_newest_imu_time", "hnet_filters_last_predict_device_ms",
+    "hnet_filters_enable_innovations", "hnet_filters_set_nis_gate", "hnet_filters_last_innovations", "hnet_filters_innovation_stats",
+    "hnet_filters_reset_innovation_stats",
 ]
 # hnet_filters_advance's status per listed session (include/hnet.h HNET_ADV_*)
 ADV_STEPPED, ADV_WAIT_IMU, ADV_WAIT_INIT, ADV_INITIALIZED, ADV_PROPAGATED, ADV_NO_FRAME = range(6)
 # hnet_filters_predict's status per listed session (include/hnet.h HNET_PRED_*)
 PRED_OK, PRED_NO_STATE, PRED_WAIT_IMU, PRED_AT_STATE = range(4)
+# an innovation record's flag (include/hnet.h HNET_INNOV_*)
+INNOV_NONE, INNOV_USED, INNOV_REJECTED, INNOV_SINGULAR, INNOV_SKIPPED = range(5)
 
 
 class Config(C.Structure):
@@ -72,6 +76,11 @@ class FilterParams(C.Structure):
                 ("cam_imu_dt", C.c_double), ("imu_avg", C.c_int32)]
 
 
+class InnovationStats(C.Structure):
+    """hnet_innovation_stats: records by flag, the sum of the NIS over the USED records, the largest NIS seen"""
+    _fields_ = [("used", C.c_int64), ("rejected", C.c_int64), ("singular", C.c_int64), ("sum_nis", C.c_double), ("max_nis", C.c_double)]
+
+
 class InitParams(C.Structure):
     """hnet_init_params: the static initialiser's window length, excitation threshold, initial height and wait_for_jerk"""
     _fields_ = [("window_time", C.c_double), ("imu_thresh", C.c_double), ("init_height", C.c_double), ("wait_for_jerk", C.c_int32)]
@@ -86,6 +95,8 @@ IMU_DTYPE = _np.dtype([("t", "<f8"), ("wm", "<f8", 3), ("am", "<f8", 3)])
 ODOMETRY_DTYPE = _np.dtype([("t_cam", "<f8"), ("t_imu", "<f8"), ("p", "<f8", 3), ("q", "<f8", 4), ("v", "<f8", 3), ("w_pos", "<f8", 3),
                             ("rpy", "<f8", 3), ("body_pos", "<f8", 3), ("body_vel", "<f8", 3), ("prior_px", "<f8", 8),
                             ("intervals", "<i4"), ("status", "<i4")])
+# hnet_innovation: one record per IEKF iteration and stepping session (hnet_filters_last_innovations)
+INNOVATION_DTYPE = _np.dtype([("r", "<f8", 8), ("s_diag", "<f8", 8), ("nis", "<f8"), ("iteration", "<i4"), ("flag", "<i4")])
 
 
 class HnetError(RuntimeError):
@@ -219,6 +230,11 @@ def lib():
     L.hnet_filters_newest_imu_time.restype = C.c_double
     L.hnet_filters_last_predict_device_ms.argtypes = [vp]
     L.hnet_filters_last_predict_device_ms.restype = C.c_double
+    L.hnet_filters_enable_innovations.argtypes = [vp]
+    L.hnet_filters_set_nis_gate.argtypes = [vp, C.c_int, C.c_double]
+    L.hnet_filters_last_innovations.argtypes = [vp, C.c_int, vp]
+    L.hnet_filters_innovation_stats.argtypes = [vp, C.c_int, C.POINTER(InnovationStats)]
+    L.hnet_filters_reset_innovation_stats.argtypes = [vp, C.c_int]
     for name in SYMBOLS:
         getattr(L, name)   # AttributeError here = the library does not export what include/hnet.h declares
     _lib = L

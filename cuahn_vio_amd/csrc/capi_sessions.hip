@@ -399,9 +399,39 @@ struct hnet_filters {
     hipEvent_t ev_p0 = nullptr, ev_p1 = nullptr;
     bool pred_timed = false;                   // set by the first hnet_filters_last_predict_device_ms: only then a predict records its two events
     double pred_ms = NAN;
+    // innovations (hnet_filters_enable_innovations): the output block then is {net | prior_px | updates | innov [iters][n] InnovRec, dense | work | results},
+    // so that the records lie inside the one download; the per-session gates; the statistics, accumulated from the records of accepted steps
+    bool innov = false;
+    size_t off_innov = 0;
+    double* d_max_nis = nullptr;               // [n_sessions], 0 = no gate
+    std::vector<hnet_innovation_stats> innov_stats;
+    int last_innov_n = 0;                      // sessions the last accepted step has records for; 0: it ran with innovations off
 };
 
 static size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// the offsets of the step's output block for max_batch B, with or without room for the innovation records behind the updates
+static void filters_out_layout(hnet_filters* f, int B, bool innov) {
+    f->off_prior = al256((size_t)f->iters * B * 72 * sizeof(float));
+    f->off_upd = f->off_prior + al256((size_t)f->iters * B * 8 * sizeof(float));
+    f->off_innov = f->off_upd + al256((size_t)B * sizeof(int32_t));
+    f->off_work = f->off_innov + (innov ? al256((size_t)f->iters * B * sizeof(InnovRec)) : 0);
+    f->off_res = f->off_work + al256((size_t)B * sizeof(FilterRec));
+    f->out_bytes = f->off_res + (size_t)B * sizeof(AdvanceResult);
+}
+// after an accepted step with innovations on: the records [iters][n] of the sessions ids[0 .. n) go into their statistics
+static void filters_count_innovations(hnet_filters* f, int n, const int32_t* ids) {
+    const InnovRec* rec = reinterpret_cast<const InnovRec*>(f->pin_out + f->off_innov);
+    for (int it = 0; it < f->iters; it++)
+        for (int j = 0; j < n; j++) {
+            const InnovRec& r = rec[(size_t)it * n + j];
+            hnet_innovation_stats& a = f->innov_stats[ids[j]];
+            if (r.flag == HNET_INNOV_USED) { a.used++; a.sum_nis += r.nis; }
+            else if (r.flag == HNET_INNOV_REJECTED) a.rejected++;
+            else if (r.flag == HNET_INNOV_SINGULAR) a.singular++;
+            if ((r.flag == HNET_INNOV_USED || r.flag == HNET_INNOV_REJECTED) && r.nis > a.max_nis) a.max_nis = r.nis;
+        }
+}
 
 // the context of forwards 1 .. iters - 1 of a step when the sessions have an iterative model (hnet_sessions_set_iterative_model), else null
 static hnet_ctx* filters_iter_ctx(const hnet_filters* f) { return f->iters > 1 ? f->s->iter : nullptr; }
@@ -461,7 +491,7 @@ void hnet_destroy_filters(hnet_filters* f) {
     (void)hipStreamSynchronize(c->stream);
     auto fr = [](void* p) { if (p) (void)hipFree(p); };
     fr(f->d_state); fr(f->d_params); fr(f->d_out); fr(f->d_prior_cam); fr(f->d_in);
-    fr(f->d_ring); fr(f->d_meta); fr(f->d_ip); fr(f->d_sel); fr(f->d_feed); fr(f->d_adv); fr(f->d_pred); fr(f->d_pred_sel);
+    fr(f->d_ring); fr(f->d_meta); fr(f->d_ip); fr(f->d_sel); fr(f->d_feed); fr(f->d_adv); fr(f->d_pred); fr(f->d_pred_sel); fr(f->d_max_nis);
     if (f->pin_pred) (void)hipHostFree(f->pin_pred);
     if (f->ev_p0) (void)hipEventDestroy(f->ev_p0);
     if (f->ev_p1) (void)hipEventDestroy(f->ev_p1);
@@ -489,11 +519,7 @@ int hnet_create_filters(hnet_sessions* s, int max_iekf_iteration, hnet_filters**
     f->t.assign(N, 0.0);
     f->cam_imu_dt.assign(N, dp.cam_imu_dt);
     f->imu_avg.assign(N, dp.imu_avg);
-    f->off_prior = al256((size_t)f->iters * B * 72 * sizeof(float));
-    f->off_upd = f->off_prior + al256((size_t)f->iters * B * 8 * sizeof(float));
-    f->off_work = f->off_upd + al256((size_t)B * sizeof(int32_t));
-    f->off_res = f->off_work + al256((size_t)B * sizeof(FilterRec));
-    f->out_bytes = f->off_res + (size_t)B * sizeof(AdvanceResult);
+    filters_out_layout(f, B, false);
     f->t_seen.assign(N, -INFINITY);
     f->inited.assign(N, 0);
     f->last_slot.assign(N, -1);
@@ -623,7 +649,7 @@ int hnet_filters_step(hnet_filters* f, int n, const int32_t* ids, const double* 
     const double* d_tf = reinterpret_cast<const double*>(f->d_in + o_t);
     const uint64_t* d_seq = reinterpret_cast<const uint64_t*>(f->d_in + o_seq);
     const int32_t* d_ids = reinterpret_cast<const int32_t*>(f->d_in + o_ids);
-    const int32_t* d_gate = reinterpret_cast<const int32_t*>(f->d_in + o_gate);
+    int32_t* d_gate = reinterpret_cast<int32_t*>(f->d_in + o_gate);             // (filter_innovation_kernel closes the gate of a session it rejects; every attempt uploads it again)
     const int32_t* d_pairs = reinterpret_cast<const int32_t*>(f->d_in + o_pairs);
     const int32_t* d_roff = reinterpret_cast<const int32_t*>(f->d_in + o_off);
     float* d_net = reinterpret_cast<float*>(f->d_out);
@@ -633,7 +659,9 @@ int hnet_filters_step(hnet_filters* f, int n, const int32_t* ids, const double* 
     const float* h_net = reinterpret_cast<const float*>(f->pin_out);
     const float* h_prior = reinterpret_cast<const float*>(f->pin_out + f->off_prior);
     // the output block is laid out for max_batch: download the used parts of each section in one copy up to the last one needed
-    const size_t down = state_out ? f->off_work + (size_t)n * sizeof(FilterRec) : f->off_upd + (size_t)n * sizeof(int32_t);
+    const size_t down = state_out ? f->off_work + (size_t)n * sizeof(FilterRec)
+                                  : f->innov ? f->off_innov + (size_t)I * n * sizeof(InnovRec) : f->off_upd + (size_t)n * sizeof(int32_t);
+    InnovRec* d_innov = reinterpret_cast<InnovRec*>(f->d_out + f->off_innov);
     hipStream_t st = c->stream;
     const size_t up = o_off + (size_t)(n + 1) * 4;
     hnet_ctx* const ctx[2] = {c, filters_iter_ctx(f)};
@@ -650,6 +678,7 @@ int hnet_filters_step(hnet_filters* f, int n, const int32_t* ids, const double* 
             const FwdArgs a{.prev = c->stage_prev, .curr = c->stage_curr, .prior = c->cfg.use_prior ? pr_it : nullptr, .batch = n, .mean = net_it, .cov = net_it + 8,
                             .seq_tab = d_seq + (size_t)it * n, .mean_stride = HNET_PACKED_FLOATS, .cov_stride = HNET_PACKED_FLOATS};
             if (const int r = filters_forward(ctx, it, a, st); r != HNET_OK) return r;
+            if (f->innov) HIPCHK(c, launch_filter_innovation(d_ids, n, s->n, f->d_params, d_work, net_it, f->d_prior_cam, f->d_max_nis, d_gate, d_upd, it, d_innov, st));
             HIPCHK(c, launch_filter_update(d_ids, n, s->n, f->d_params, net_it, f->d_prior_cam, d_gate, it != I - 1, it == I - 1, d_work, d_upd, st));
         }
         HIPCHK(c, hipEventRecord(f->ev1, st));
@@ -675,6 +704,8 @@ int hnet_filters_step(hnet_filters* f, int n, const int32_t* ids, const double* 
     if (updates) memcpy(updates, f->pin_out + f->off_upd, (size_t)n * sizeof(int32_t));
     if (state_out) memcpy(state_out, f->pin_out + f->off_work, (size_t)n * sizeof(FilterRec));
     f->last_n = n;
+    f->last_innov_n = f->innov ? n : 0;
+    if (f->innov) filters_count_innovations(f, n, ids);
     float ms = 0;
     HIPCHK(c, hipEventElapsedTime(&ms, f->ev0, f->ev1));
     record_timing(f->timing, ms, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), I, true);
@@ -899,7 +930,7 @@ int hnet_filters_advance(hnet_filters* f, int n, const int32_t* ids, hnet_filter
     }
     const AdvanceJob* d_job = reinterpret_cast<const AdvanceJob*>(f->d_adv);
     const uint64_t* d_seq = reinterpret_cast<const uint64_t*>(f->d_adv + L.o_seq);
-    const int32_t* d_gate = reinterpret_cast<const int32_t*>(f->d_adv + L.o_gate);
+    int32_t* d_gate = reinterpret_cast<int32_t*>(f->d_adv + L.o_gate);          // (as in hnet_filters_step)
     const int32_t* d_ids = reinterpret_cast<const int32_t*>(f->d_adv + L.o_ids);
     const int32_t* d_pairs = reinterpret_cast<const int32_t*>(f->d_adv + L.o_pairs);
     float* d_net = reinterpret_cast<float*>(f->d_out);
@@ -907,6 +938,7 @@ int hnet_filters_advance(hnet_filters* f, int n, const int32_t* ids, hnet_filter
     int32_t* d_upd = reinterpret_cast<int32_t*>(f->d_out + f->off_upd);
     FilterRec* d_work = reinterpret_cast<FilterRec*>(f->d_out + f->off_work);
     AdvanceResult* d_res = reinterpret_cast<AdvanceResult*>(f->d_out + f->off_res);
+    InnovRec* d_innov = reinterpret_cast<InnovRec*>(f->d_out + f->off_innov);
     const float* h_net = reinterpret_cast<const float*>(f->pin_out);
     const float* h_prior = reinterpret_cast<const float*>(f->pin_out + f->off_prior);
     const AdvanceResult* h_res = reinterpret_cast<const AdvanceResult*>(f->pin_out + f->off_res);
@@ -928,10 +960,12 @@ int hnet_filters_advance(hnet_filters* f, int n, const int32_t* ids, hnet_filter
             const FwdArgs a{.prev = c->stage_prev, .curr = c->stage_curr, .prior = c->cfg.use_prior ? pr_it : nullptr, .batch = n_s, .mean = net_it, .cov = net_it + 8,
                             .seq_tab = d_seq + (size_t)it * n_a, .mean_stride = HNET_PACKED_FLOATS, .cov_stride = HNET_PACKED_FLOATS};
             if (const int r = filters_forward(ctx, it, a, st); r != HNET_OK) return r;
+            if (f->innov) HIPCHK(c, launch_filter_innovation(d_ids, n_s, s->n, f->d_params, d_work, net_it, f->d_prior_cam, f->d_max_nis, d_gate, d_upd, it, d_innov, st));
             HIPCHK(c, launch_filter_update(d_ids, n_s, s->n, f->d_params, net_it, f->d_prior_cam, d_gate, it != I - 1, it == I - 1, d_work, d_upd, st));
         }
         HIPCHK(c, hipEventRecord(f->ev1, st));
-        if (n_s) HIPCHK(c, hipMemcpyAsync(f->pin_out, f->d_out, f->off_upd + (size_t)n_s * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        if (n_s) HIPCHK(c, hipMemcpyAsync(f->pin_out, f->d_out, f->innov ? f->off_innov + (size_t)I * n_s * sizeof(InnovRec) : f->off_upd + (size_t)n_s * sizeof(int32_t),
+                                          hipMemcpyDeviceToHost, st));
         if (state_out) HIPCHK(c, hipMemcpyAsync(f->pin_out + f->off_work, d_work, (size_t)n_a * sizeof(FilterRec), hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipMemcpyAsync(f->pin_out + f->off_res, d_res, (size_t)n_a * sizeof(AdvanceResult), hipMemcpyDeviceToHost, st));
         return filters_flags(ctx, flag_now, st);
@@ -975,6 +1009,8 @@ int hnet_filters_advance(hnet_filters* f, int n, const int32_t* ids, hnet_filter
         if (state_out) memcpy(state_out + i, f->pin_out + f->off_work + (size_t)j * sizeof(FilterRec), sizeof(FilterRec));
     }
     f->last_n = n_s;
+    f->last_innov_n = f->innov ? n_s : 0;
+    if (f->innov && n_s) filters_count_innovations(f, n_s, hid);             // (the stepping sessions are the first n_s of the call's id table)
     float ms = 0;
     HIPCHK(c, hipEventElapsedTime(&ms, f->ev0, f->ev1));
     record_timing(f->timing, ms, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(), n_s ? I : 0, true);
@@ -999,6 +1035,81 @@ int hnet_filters_last_selection(hnet_filters* f, int id, hnet_imu* out, int cap,
         HIPCHK(c, hipMemcpyAsync(out, f->d_sel + (size_t)j * 2 * (f->cap + 2) + (f->cap + 2), (size_t)k * sizeof(hnet_imu), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
+    return HNET_OK;
+}
+
+// ---- filters, innovation records (include/hnet.h): the records themselves come from filter_innovation_kernel inside hnet_filters_step / _advance ----
+
+static_assert(sizeof(hnet_innovation) == sizeof(InnovRec), "hnet_innovation is the InnovRec layout");
+static_assert((int)HNET_INNOV_NONE == (int)hnet_ekf::INNOV_NONE && (int)HNET_INNOV_USED == (int)hnet_ekf::INNOV_USED && (int)HNET_INNOV_REJECTED == (int)hnet_ekf::INNOV_REJECTED &&
+              (int)HNET_INNOV_SINGULAR == (int)hnet_ekf::INNOV_SINGULAR && (int)HNET_INNOV_SKIPPED == (int)hnet_ekf::INNOV_SKIPPED, "HNET_INNOV_* are the header's flags");
+
+int hnet_filters_enable_innovations(hnet_filters* f) {
+    if (!f) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = f->s->ctx;
+    if (f->innov) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_enable_innovations: already enabled");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    HIPCHK(c, hipStreamSynchronize(c->stream));                    // (nothing enqueued reads the old output block any more)
+    const int N = f->s->n, B = c->cfg.max_batch;
+    // the output block with room for the records: a new block, and the old one freed only when everything is there
+    filters_out_layout(f, B, true);
+    uint8_t *d_out = nullptr, *pin_out = nullptr;
+    double* d_max = nullptr;
+    hipError_t e = hipMalloc((void**)&d_out, f->out_bytes);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&pin_out, f->out_bytes, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_max, (size_t)N * sizeof(double));
+    if (e == hipSuccess) e = hipMemsetAsync(d_max, 0, (size_t)N * sizeof(double), c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        if (d_out) (void)hipFree(d_out);
+        if (pin_out) (void)hipHostFree(pin_out);
+        if (d_max) (void)hipFree(d_max);
+        filters_out_layout(f, B, false);
+        return fail(c, HNET_ERR_DEVICE, std::string("hnet_filters_enable_innovations: ") + hipGetErrorString(e));
+    }
+    (void)hipFree(f->d_out);
+    (void)hipHostFree(f->pin_out);
+    f->d_out = d_out;
+    f->pin_out = pin_out;
+    f->d_max_nis = d_max;
+    f->innov_stats.assign(N, hnet_innovation_stats{0, 0, 0, 0.0, 0.0});
+    f->last_n = 0;                                                 // what last_priors / last_selection described went with the old block
+    f->last_innov_n = 0;
+    std::fill(f->last_slot.begin(), f->last_slot.end(), -1);
+    f->innov = true;
+    return HNET_OK;
+}
+
+int hnet_filters_set_nis_gate(hnet_filters* f, int id, double max_nis) {
+    if (!f) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = f->s->ctx;
+    if (!f->innov) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_set_nis_gate: innovations not enabled (hnet_filters_enable_innovations)");
+    if (id < 0 || id >= f->s->n || !(max_nis >= 0.0)) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_set_nis_gate: id out of range, or max_nis negative or NaN");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    HIPCHK(c, hipMemcpyAsync(f->d_max_nis + id, &max_nis, sizeof max_nis, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return HNET_OK;
+}
+
+int hnet_filters_last_innovations(const hnet_filters* f, int n, hnet_innovation* out) {
+    if (!f || !out) return HNET_ERR_INVALID_ARG;
+    if (!f->innov || f->last_innov_n < 1) return fail(f->s->ctx, HNET_ERR_INVALID_ARG, "hnet_filters_last_innovations: the last step ran without innovations");
+    if (n != f->last_innov_n) return fail(f->s->ctx, HNET_ERR_INVALID_ARG, "hnet_filters_last_innovations: n differs from the last step's");
+    memcpy(out, f->pin_out + f->off_innov, (size_t)f->iters * n * sizeof(InnovRec));
+    return HNET_OK;
+}
+
+int hnet_filters_innovation_stats(const hnet_filters* f, int id, hnet_innovation_stats* out) {
+    if (!f || !out) return HNET_ERR_INVALID_ARG;
+    if (!f->innov || id < 0 || id >= f->s->n) return fail(f->s->ctx, HNET_ERR_INVALID_ARG, "hnet_filters_innovation_stats: innovations not enabled or id out of range");
+    *out = f->innov_stats[id];
+    return HNET_OK;
+}
+
+int hnet_filters_reset_innovation_stats(hnet_filters* f, int id) {
+    if (!f) return HNET_ERR_INVALID_ARG;
+    if (!f->innov || id < 0 || id >= f->s->n) return fail(f->s->ctx, HNET_ERR_INVALID_ARG, "hnet_filters_reset_innovation_stats: innovations not enabled or id out of range");
+    f->innov_stats[id] = hnet_innovation_stats{0, 0, 0, 0.0, 0.0};
     return HNET_OK;
 }
 

@@ -93,5 +93,20 @@ constexpr int PREDICT_THREADS = 64;
 hipError_t launch_filter_predict(const PredictJob* job, int n, int n_sessions, int cap, const hnet_ekf::ImuData* ring, const ImuRingMeta* meta,
                                  const FilterRec* state, const FilterParams* params, hnet_ekf::ImuData* scratch, PredictOut* out, hipStream_t s);
 
+// ---- innovation records and the NIS gate (hnet_filters_enable_innovations).
+// the layout of hnet_innovation: hnet_ekf::Innovation's r, s_diag and nis, then the iteration and the flag (hnet_ekf::INNOV_*)
+struct InnovRec {
+    double r[8], s_diag[8], nis;
+    int32_t iteration, flag;
+};
+constexpr int INNOV_REC_DOUBLES = (int)(sizeof(InnovRec) / sizeof(double));       // 18
+static_assert(sizeof(InnovRec) == 18 * sizeof(double), "InnovRec must be 17 packed doubles and two ints");
+constexpr int INNOV_THREADS = 64;
+// iteration `it` of a step of n sessions, between its forward and its filter_update_kernel: writes innov[it * n + b] and, on a rejection, 0 to gate[b]
+// (the step's device copy, uploaded again by every attempt).  max_nis: [n_sessions], <= 0 = no gate.  Reads innov[(it - 1) * n + b] for it > 0.
+hipError_t launch_filter_innovation(const int32_t* ids, int n, int n_sessions, const FilterParams* params, const FilterRec* work, const float* net72,
+                                    const double* prior_cam, const double* max_nis, int32_t* gate, const int32_t* updates, int it, InnovRec* innov,
+                                    hipStream_t s);
+
 }  // namespace hnet
 #endif  // HNET_FILTERS_DEV_H

@@ -489,6 +489,108 @@ __global__ __launch_bounds__(PREDICT_THREADS) void filter_predict_kernel(const P
     for (int i = t; i < PREDICT_OUT_DOUBLES; i += PREDICT_THREADS) ow[i] = rw[i];
 }
 
+// ---- innovation records and the NIS gate (hnet_filters_enable_innovations) ----
+
+static_assert(offsetof(InnovRec, nis) == 16 * sizeof(double) && offsetof(InnovRec, iteration) == 17 * sizeof(double), "InnovRec: r, s_diag, nis, then the two ints");
+
+// hnet_ekf::innovation for the measurement filter_update_kernel is about to apply in iteration `it`, one wavefront per listed session, and the gate
+// rule of hnet_ekf::iterated_update_gated.  Of work[b] only the 64 covariance elements cov[sel(i)][sel(j)] are read.  S, r and the Gauss-Jordan inverse
+// are the update kernel's (the header's operations in the header's order, one matrix element per lane); y = S^-1 r by lanes 0 .. 7 and the NIS as a
+// serial sum in the header's order.  Flags: a session whose earlier update of this step found S singular (updates[b] < 0), or whose earlier record is
+// REJECTED / SKIPPED, is SKIPPED; a closed reference gate otherwise gives NONE; both leave r, s_diag and nis zero.  A rejection writes 0 to gate[b],
+// which is what makes filter_update_kernel skip this and the later updates and still do the last iteration's reset.  Writes innov[it * n + b] and
+// gate[b] only.
+__global__ __launch_bounds__(INNOV_THREADS) void filter_innovation_kernel(const int32_t* __restrict__ ids, int n, int n_sessions, const FilterParams* __restrict__ params,
+                                                                          const FilterRec* __restrict__ work, const float* __restrict__ net72,
+                                                                          const double* __restrict__ prior_cam, const double* __restrict__ max_nis,
+                                                                          int32_t* gate, const int32_t* __restrict__ updates, int it, InnovRec* innov) {
+    __shared__ double A[64], V[64], r[8], sd[8], y[8];
+    const int b = blockIdx.x, t = threadIdx.x;
+    if (b >= n) return;
+    const int id = ids[b];
+    if (id < 0 || id >= n_sessions) return;                                    // (host-validated; uniform over the workgroup, as every test below)
+    InnovRec* out = innov + (size_t)it * n + b;
+    double* ow = reinterpret_cast<double*>(out);
+    int flag = hnet_ekf::INNOV_USED;
+    if (updates[b] < 0) flag = hnet_ekf::INNOV_SKIPPED;
+    else if (gate[b] == 0) {
+        const int prev = it > 0 ? innov[(size_t)(it - 1) * n + b].flag : hnet_ekf::INNOV_NONE;
+        flag = prev == hnet_ekf::INNOV_REJECTED || prev == hnet_ekf::INNOV_SKIPPED ? hnet_ekf::INNOV_SKIPPED : hnet_ekf::INNOV_NONE;
+    }
+    if (flag != hnet_ekf::INNOV_USED) {
+        if (t < 17) ow[t] = 0.0;
+        if (t == 0) { out->iteration = it; out->flag = flag; }
+        return;
+    }
+    const double kc = params[id].k_net_cov;
+    const float* nm = net72 + (size_t)b * 72;
+    const int i = t >> 3, j = t & 7;
+    A[t] = work[b].s.cov[sel(i) * NS + sel(j)] + kc * (double)nm[8 + t] / (hnet_ekf::F_PIX * hnet_ekf::F_PIX);
+    V[t] = i == j ? 1.0 : 0.0;
+    if (t < 8) r[t] = (double)nm[t] / hnet_ekf::F_PIX - prior_cam[(size_t)b * 8 + t];
+    __syncthreads();
+    if (t < 8) sd[t] = A[t * 9];
+    // hnet_ekf::invert(A, 8) as in filter_update_kernel: lane t holds element (i, j) of both A and V
+    bool singular = false;
+    for (int col = 0; col < 8; col++) {
+        int piv = col;
+        for (int q = col + 1; q < 8; q++)
+            if (fabs(A[q * 8 + col]) > fabs(A[piv * 8 + col])) piv = q;
+        if (A[piv * 8 + col] == 0.0) { singular = true; break; }                 // (every lane sees the same LDS values)
+        __syncthreads();
+        if (piv != col && t < 16) {
+            double* X = t < 8 ? A : V;
+            const double tmp = X[col * 8 + j];
+            X[col * 8 + j] = X[piv * 8 + j];
+            X[piv * 8 + j] = tmp;
+        }
+        __syncthreads();
+        const double d = 1.0 / A[col * 8 + col];
+        __syncthreads();
+        if (t < 16) (t < 8 ? A : V)[col * 8 + j] *= d;
+        __syncthreads();
+        const double f = A[i * 8 + col];
+        __syncthreads();
+        if (i != col && f != 0.0) {
+            A[t] -= f * A[col * 8 + j];
+            V[t] -= f * V[col * 8 + j];
+        }
+        __syncthreads();
+    }
+    double nis = (double)NAN;
+    if (singular) flag = hnet_ekf::INNOV_SINGULAR;
+    else {
+        if (t < 8) {
+            double a = 0.0;
+            for (int q = 0; q < 8; q++) a += V[t * 8 + q] * r[q];
+            y[t] = a;
+        }
+        __syncthreads();
+        nis = 0.0;
+        for (int q = 0; q < 8; q++) nis += r[q] * y[q];
+        const double mx = max_nis[id];
+        if (mx > 0.0 && nis > mx) flag = hnet_ekf::INNOV_REJECTED;               // (a NaN NIS does not reject)
+    }
+    __syncthreads();                                                           // (sd: a matrix singular in column 0 passed no barrier since it was written)
+    if (t < 8) ow[t] = r[t];
+    else if (t < 16) ow[t] = sd[t - 8];
+    else if (t == 16) ow[16] = nis;
+    if (t == 0) {
+        out->iteration = it;
+        out->flag = flag;
+        if (flag == hnet_ekf::INNOV_REJECTED) gate[b] = 0;
+    }
+}
+
+hipError_t launch_filter_innovation(const int32_t* ids, int n, int n_sessions, const FilterParams* params, const FilterRec* work, const float* net72,
+                                    const double* prior_cam, const double* max_nis, int32_t* gate, const int32_t* updates, int it, InnovRec* innov,
+                                    hipStream_t s) {
+    if (n < 1 || it < 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(filter_innovation_kernel, dim3((unsigned)n), dim3(INNOV_THREADS), 0, s, ids, n, n_sessions, params, work, net72, prior_cam, max_nis, gate,
+                       updates, it, innov);
+    return hipGetLastError();
+}
+
 hipError_t launch_filter_predict(const PredictJob* job, int n, int n_sessions, int cap, const hnet_ekf::ImuData* ring, const ImuRingMeta* meta,
                                  const FilterRec* state, const FilterParams* params, hnet_ekf::ImuData* scratch, PredictOut* out, hipStream_t s) {
     if (n < 1 || cap < 1) return hipErrorInvalidValue;

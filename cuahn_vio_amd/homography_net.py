@@ -664,6 +664,30 @@ class HnetFilters:
         """event time of the last timed predict's launch; the first call switches the timing on (NaN until a timed predict has run)"""
         return float(self._L.hnet_filters_last_predict_device_ms(self._f))
 
+    # ---- innovation records and the NIS gate ----
+    def enable_innovations(self):
+        """from now on every step / advance also returns one innovation record per iteration and stepping session (once per object)"""
+        self._check(self._L.hnet_filters_enable_innovations(self._f))
+
+    def set_nis_gate(self, id, max_nis):
+        """session id's gate on the normalised innovation squared; 0 = off.  chi-squared with 8 degrees of freedom: 15.507 (95 %), 20.090 (99 %),
+        26.124 (99.9 %)"""
+        self._check(self._L.hnet_filters_set_nis_gate(self._f, int(id), float(max_nis)))
+
+    def last_innovations(self, n):
+        """the records [iters, n] of _capi.INNOVATION_DTYPE of the last step (of n sessions; another n is refused)"""
+        out = np.zeros((self.iters, int(n)), _capi.INNOVATION_DTYPE)
+        self._check(self._L.hnet_filters_last_innovations(self._f, int(n), out.ctypes.data))
+        return out
+
+    def innovation_stats(self, id):
+        st = _capi.InnovationStats()
+        self._check(self._L.hnet_filters_innovation_stats(self._f, int(id), C.byref(st)))
+        return {"used": st.used, "rejected": st.rejected, "singular": st.singular, "sum_nis": st.sum_nis, "max_nis": st.max_nis}
+
+    def reset_innovation_stats(self, id):
+        self._check(self._L.hnet_filters_reset_innovation_stats(self._f, int(id)))
+
     def last_priors(self, n):
         """the fp32 priors [iters, n, 8] the forwards of the last step (of n sessions; another n is refused) read"""
         out = np.zeros((self.iters, int(n), 8), np.float32)

@@ -452,6 +452,41 @@ double hnet_filters_newest_imu_time(const hnet_filters* f, int id);   /* the hos
  * never pays for them; the first call switches the timing on and returns NaN, as does every call before a timed predict */
 double hnet_filters_last_predict_device_ms(hnet_filters* f);
 
+/* ---- filters, innovation records: how well each measurement agreed with the filter, and an opt-in gate on it --------------------------------
+ * The update weighs the network's covariance with one hand-set scale, k_net_cov, and the reference applies every measurement (it dropped OpenVINS'
+ * chi-squared test, UpdaterHNet.cpp:28-61).  With innovations enabled every step / advance also returns, per IEKF iteration and stepping session, the
+ * innovation r = mean / 159.5 - prior, the diagonal of S = H P H^T + k_net_cov C / 159.5^2 and the normalised innovation squared NIS = r^T S^-1 r
+ * (hnet_ekf::innovation), formed on the device from the state each update is about to change: one more launch per iteration, the records in the call's
+ * download, still one upload, one download and one synchronisation.  For a consistent filter the NIS is chi-squared with 8 degrees of freedom: mean 8,
+ * quantiles 15.507 (95 %), 20.090 (99 %), 26.124 (99.9 %).
+ * The gate (hnet_filters_set_nis_gate; off by default) follows hnet_ekf::iterated_update_gated: at an iteration whose reference gate is open and
+ * whose NIS exceeds max_nis, that update and all later updates of the step are skipped for that session; updates already applied stay, every forward
+ * still runs (the sequence number advances as always) and the offsets are reset.  A NaN NIS does not reject.  updates[i] keeps its meaning (the number
+ * applied, -1 - applied for a singular S): a rejection shows in the records only.  Flags per (iteration, session):
+ *   HNET_INNOV_NONE      the reference's gate was closed (VioManager.cpp:257).  r, s_diag and nis are zero.
+ *   HNET_INNOV_USED      the update was applied.
+ *   HNET_INNOV_REJECTED  the NIS exceeded the session's gate.
+ *   HNET_INNOV_SINGULAR  S was singular (nis is NaN).
+ *   HNET_INNOV_SKIPPED   after an earlier rejection or singular S in the same step.  r, s_diag and nis are zero.
+ * Without hnet_filters_enable_innovations a step and an advance launch exactly what they launched before, and with it and no gate set they compute
+ * the same states, priors, network outputs and updates, bit for bit. */
+typedef struct hnet_innovation { double r[8], s_diag[8], nis; int32_t iteration, flag; } hnet_innovation;
+enum { HNET_INNOV_NONE = 0, HNET_INNOV_USED = 1, HNET_INNOV_REJECTED = 2, HNET_INNOV_SINGULAR = 3, HNET_INNOV_SKIPPED = 4 };
+/* per session, accumulated on the host from the records of every accepted step (a repeated attempt never counts twice): records by flag, the sum
+ * of the NIS over the USED records (sum_nis / used estimates the mean NIS of what the filter absorbed) and the largest NIS seen, USED or REJECTED */
+typedef struct hnet_innovation_stats { int64_t used, rejected, singular; double sum_nis, max_nis; } hnet_innovation_stats;
+/* once per filters object (HNET_ERR_INVALID_ARG on a second call): room for [max_iekf_iteration][max_batch] records in the step's output block.
+ * hnet_filters_last_priors has nothing to describe until the next step. */
+int  hnet_filters_enable_innovations(hnet_filters* f);
+/* session id's gate: max_nis = 0 is off (the default), e.g. 20.090 rejects what a consistent filter produces once in 100 frames.  A negative or NaN
+ * max_nis, a bad id or a call before hnet_filters_enable_innovations: HNET_ERR_INVALID_ARG */
+int  hnet_filters_set_nis_gate(hnet_filters* f, int id, double max_nis);
+/* the records [max_iekf_iteration][n] of the last step (n: its n) or advance (n: its STEPPED sessions, in the order listed), as hnet_filters_last_priors.
+ * A wrong n, or a last call that ran with innovations off: HNET_ERR_INVALID_ARG, nothing written */
+int  hnet_filters_last_innovations(const hnet_filters* f, int n, hnet_innovation* out);
+int  hnet_filters_innovation_stats(const hnet_filters* f, int id, hnet_innovation_stats* out);
+int  hnet_filters_reset_innovation_stats(hnet_filters* f, int id);
+
 int hnet_synchronize(hnet_ctx* ctx, void* stream);
 int hnet_last_timing(const hnet_ctx* ctx, hnet_timing* out);
 

@@ -459,6 +459,98 @@ inline int iterated_update(State& s, Net& net, int max_iekf_iteration, double k_
     return done;
 }
 
+/* ---- innovation records, the normalised innovation squared and an opt-in gate on it.  The reference dropped OpenVINS' chi-squared test when
+ * UpdaterHNet replaced the feature updaters (UpdaterHNet.cpp:28-61 applies every measurement); these are additions next to update() and
+ * iterated_update(), which stay as they are.  NIS = r^T S^-1 r with r and S as update() forms them; for a consistent filter it is chi-squared
+ * with 8 degrees of freedom (mean 8; quantiles 15.507 at 95 %, 20.090 at 99 %, 26.124 at 99.9 %).  The device filters (hnet_filters_enable_innovations,
+ * include/hnet.h) restate innovation() in filter_innovation_kernel; tests/test_filters_innov_cpu.py checks it against numpy. */
+enum { INNOV_NONE = 0,                 /* the reference's gate (VioManager.cpp:257) was closed: nothing measured */
+       INNOV_USED = 1,                 /* the update was applied */
+       INNOV_REJECTED = 2,             /* the NIS exceeded max_nis: this update and the step's later ones are skipped */
+       INNOV_SINGULAR = 3,             /* S was singular: update() refuses it */
+       INNOV_SKIPPED = 4 };            /* after an earlier rejection or singular S in the same step */
+/* r: the innovation mean / 159.5 - prior; s_diag: the diagonal of S = H P H^T + k_net_cov C / 159.5^2; nis: NaN when S is singular.
+ * A NONE or SKIPPED record holds zeros in r, s_diag and nis: nothing was formed for it. */
+struct Innovation {
+    double r[8], s_diag[8], nis;
+    int flag;
+};
+
+/* r, the diagonal of S and the NIS of the measurement update() would apply to `s`: the same expressions for S and the innovation, the same
+ * invert(), then nis = sum_i r_i (sum_j Sinv_ij r_j) in that order.  Returns false on a singular S (nis = NaN, flag SINGULAR), else flag USED;
+ * `s` is not written. */
+inline bool innovation(const State& s, const double net_mean_px[8], const double net_cov_px[64], const double propagated[8], double k_net_cov,
+                       Innovation& o) {
+    int sel[8];
+    for (int c = 0; c < 4; c++) { sel[2 * c] = 15 + 3 * c; sel[2 * c + 1] = 16 + 3 * c; }
+    double S[64];
+    for (int i = 0; i < 8; i++)
+        for (int j = 0; j < 8; j++) S[i * 8 + j] = s.cov[sel[i] * NS + sel[j]] + k_net_cov * net_cov_px[i * 8 + j] / (F_PIX * F_PIX);
+    for (int i = 0; i < 8; i++) {
+        o.s_diag[i] = S[i * 8 + i];
+        o.r[i] = net_mean_px[i] / F_PIX - propagated[i];
+    }
+    if (!invert(S, 8)) {
+        o.nis = (double)NAN;
+        o.flag = INNOV_SINGULAR;
+        return false;
+    }
+    double nis = 0.0;
+    for (int i = 0; i < 8; i++) {
+        double a = 0.0;
+        for (int j = 0; j < 8; j++) a += S[i * 8 + j] * o.r[j];
+        nis += o.r[i] * a;
+    }
+    o.nis = nis;
+    o.flag = INNOV_USED;
+    return true;
+}
+
+/* iterated_update with one Innovation per iteration in rec[max_iekf_iteration] and a gate on the NIS.  max_nis <= 0: no gate, and state,
+ * return value and the calls made to `net` are iterated_update's, bit for bit.  With a gate: at an iteration whose reference gate is open and whose
+ * NIS exceeds max_nis, that update and every later update of the call are skipped (REJECTED, then SKIPPED); updates already applied stay, the
+ * network still runs in every iteration and the offsets are reset as always.  A NaN NIS does not reject (update()'s singular path handles a
+ * singular S: SINGULAR, the loop ends as iterated_update's does and the iterations it never ran are SKIPPED). */
+template <class Net, class Vec8>
+inline int iterated_update_gated(State& s, Net& net, int max_iekf_iteration, double k_net_cov, Vec8& prior_px_vec, double time_stamp, double max_nis,
+                                 Innovation* rec) {
+    int done = 0;
+    bool skip = false;
+    for (int it = 0; it < max_iekf_iteration; it++) {
+        std::memset(&rec[it], 0, sizeof rec[it]);
+        rec[it].flag = INNOV_NONE;
+    }
+    for (int it = 0; it < max_iekf_iteration; it++) {
+        double prior_px[8], prior_cam[8];
+        prior_pixels(s, prior_px, prior_cam);
+        for (int i = 0; i < 8; i++) prior_px_vec[i] = prior_px[i];
+        net.network_inference(prior_px_vec, it);
+        if (net.get_latest_inference_time() == time_stamp && net.img_counter > 10) {
+            if (skip) { rec[it].flag = INNOV_SKIPPED; continue; }
+            const auto m = net.get_pred_mean();
+            const auto C = net.get_pred_Cov();
+            double mean[8], cov[64];
+            for (int i = 0; i < 8; i++) {
+                mean[i] = m(i, 0);
+                for (int j = 0; j < 8; j++) cov[i * 8 + j] = C(i, j);
+            }
+            innovation(s, mean, cov, prior_cam, k_net_cov, rec[it]);
+            if (max_nis > 0.0 && rec[it].nis > max_nis) {
+                rec[it].flag = INNOV_REJECTED;
+                skip = true;
+                continue;
+            }
+            if (!update(s, mean, cov, prior_cam, k_net_cov, it != max_iekf_iteration - 1)) {
+                for (int k = it + 1; k < max_iekf_iteration; k++) rec[k].flag = INNOV_SKIPPED;
+                break;
+            }
+            done++;
+        }
+    }
+    reset_4pt_offset(s);
+    return done;
+}
+
 /* ---- IMU propagation over one camera interval: what Propagator::propagate_with_imu (Propagator.cpp:28-76) does with the
  * buffered IMU readings.  The device filters (hnet_filters, include/hnet.h) select the readings with these functions on the host and run the
  * intervals on the device; tests/test_filters_cpu.py checks them against a numpy restatement. */

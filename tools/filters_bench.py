@@ -17,9 +17,15 @@ hnet_sessions_infer_iter on an iterative engine attached to its sessions.
 frame is pushed and the readings are fed, one predict of all K sessions to the frame's time (wall time of the call and the event time of its launch),
 the host alternative on the same inputs (hnet_filters_get_state of the K sessions + hnet_ekf::propagate_mean_with_imu / odometry_from_state over a
 host copy of the histories, tests/cpp/filters_predict_ref.cpp, on T threads), then the advance of the same sessions, which is the reference point.
+--innov is a mode of its own (innovation records and the NIS gate): per (K, iterations) three filters objects for hnet_filters_step and three
+fed ones for hnet_filters_advance, each on its own context, with innovations off, on, and on with a gate that never rejects (1e300); every tick runs the
+same inputs through all six in turn (the order rotates with the tick), reported are the wall time of the call and its event time.  "host_gated" is the host
+path on one thread: filters_ref's propagation, then hnet_ekf::iterated_update_gated (tests/cpp/filters_innov_ref.cpp) around
+hnet_sessions_infer, the prior of forward `it` being the one the header hands its network after the first `it` outputs.
    python tools/filters_bench.py [--k 1,8,64,256] [--iters 1,3] [--ticks 20] [--warmup 3] [--threads 1,16] [--feed]
                                  [--iter-variant prior1 --iter-mc 8 --iter-p 0.1]
-   python tools/filters_bench.py --predict [--k 1,8,64,256] [--ticks 20] [--warmup 3] [--threads 1,16]"""
+   python tools/filters_bench.py --predict [--k 1,8,64,256] [--ticks 20] [--warmup 3] [--threads 1,16]
+   python tools/filters_bench.py --innov [--k 1,8,64,256] [--iters 1,3] [--ticks 20] [--warmup 3]"""
 import argparse
 import ctypes as C
 import json
@@ -135,6 +141,127 @@ def predict_mode(a):
         f.close(); s.close(); e.close()
 
 
+def innov_mode(a):
+    from cuahn_vio_amd import _capi, replay, weights
+    from cuahn_vio_amd.homography_net import HnetEngine, HnetFilters, HnetSessions
+    ref = build_ref()
+    so = os.path.join(tempfile.mkdtemp(prefix="filters_innov_ref_"), "filters_innov_ref.so")
+    subprocess.run(["g++", "-std=c++17", "-O2", "-shared", "-fPIC", "-pthread", "-I", os.path.join(ROOT, "include"),
+                    os.path.join(ROOT, "tests", "cpp", "filters_innov_ref.cpp"), "-o", so], check=True)
+    iref = C.CDLL(so)
+    iref.innov_ref_step.restype = None
+    blob = weights.pack_state_dict(weights.synthetic_state(0))
+    fx = replay.load_fixture("indoor_forward_7")
+    pool = np.stack([replay.render_frame(fx, 100 + j) for j in range(16)])
+    kw = dict(variant="prior3", mc_samples=16, dropout_p=0.05, mc_seed=1)
+    modes = ("off", "on", "gate")
+
+    def pct(x, q):
+        return round(float(np.percentile(x, q)), 3)
+
+    for K in [int(x) for x in a.k.split(",")]:
+        for iters in [int(x) for x in a.iters.split(",")]:
+            p = HnetFilters.default_params()
+            params = (_capi.FilterParams * K)(*([p] * K))
+            ids = np.arange(K, dtype=np.int32)
+            st0 = np.zeros(1, _capi.FILTER_STATE_DTYPE)
+            st0["q"] = [1, 0, 0, 0]
+            st0["p"] = [0, 0, -1.0]
+            st0["cov"] = np.diag(np.r_[np.full(15, 1e-3), np.full(12, 1e-6)])
+            objs = {}
+            for kind in ("step", "advance"):
+                for m in modes:
+                    e = HnetEngine(blob, max_batch=K, **kw)
+                    s = HnetSessions(e, K)
+                    f = HnetFilters(s, iters)
+                    if m != "off":
+                        f.enable_innovations()
+                    if kind == "advance":
+                        f.enable_feed(256)
+                    for i in range(K):
+                        f.set_state(i, st0[0])
+                        if m == "gate":
+                            f.set_nis_gate(i, 1e300)
+                    objs[kind, m] = (e, s, f)
+            eh = HnetEngine(blob, max_batch=K, **kw)
+            sh = HnetSessions(eh, K)
+            host = np.repeat(st0, K)
+            rng = np.random.default_rng(K)
+            wall = {k: [] for k in objs}
+            event = {k: [] for k in objs}
+            host_ms, rejected, nis = [], 0, []
+            newest, t = -np.inf, 0.0
+            order = list(objs)
+            for tick in range(a.warmup + a.ticks):
+                t_new = t + 0.0325
+                fr = np.repeat(pool[tick % len(pool)][None], K, 0)
+                for (_, s, _) in list(objs.values()) + [(None, sh, None)]:
+                    s.push(ids, fr, t=[t_new] * K)
+                win = imu_window(rng, t)
+                new = win[win["t"] > newest]
+                newest = float(new["t"][-1])
+                for m in modes:
+                    objs["advance", m][2].feed_imu(ids, [new] * K)
+                keep = tick > a.warmup
+                for key in order[tick % len(order):] + order[:tick % len(order)]:
+                    f = objs[key][2]
+                    if key[0] == "step" and tick == 0:              # one image per session so far: nothing to step
+                        continue
+                    t0 = time.perf_counter()
+                    if key[0] == "step":
+                        f.step(ids, [t_new] * K, [win] * K)
+                    else:
+                        status = f.advance(ids)[3]
+                    d = (time.perf_counter() - t0) * 1e3
+                    if key[0] == "advance" and tick > 0:
+                        assert (status == _capi.ADV_STEPPED).all(), status
+                    if keep:
+                        wall[key].append(d)
+                        event[key].append(f.last_timing()["device_ms"])
+                    if keep and key == ("step", "gate"):
+                        r = f.last_innovations(K)
+                        rejected += int((r["flag"] == _capi.INNOV_REJECTED).sum())
+                        nis += [float(x) for x in r["nis"][r["flag"] == _capi.INNOV_USED]]
+                if tick > 0:
+                    imu = np.ascontiguousarray(np.tile(win, K))
+                    off = (np.arange(K + 1) * len(win)).astype(np.int64)
+                    tf = np.full(K, t_new)
+                    t0 = time.perf_counter()
+                    ref.ref_propagate_batch(C.c_void_p(host.ctypes.data), params, K, C.c_void_p(tf.ctypes.data), C.c_void_p(imu.ctypes.data),
+                                            C.c_void_p(off.ctypes.data), 1)
+                    gate = np.array([int(sh.latest_time(j) == t_new and sh.image_count(j) > 10) for j in range(K)], np.int32)
+                    mx = np.full(K, 1e300)
+                    net = np.zeros((iters, K, 72), np.float32)
+                    rec = np.zeros((iters, K), _capi.INNOVATION_DTYPE)
+                    upd = np.zeros(K, np.int32)
+                    pri = np.zeros((iters, K, 8))
+                    for it in range(iters + 1):                     # pass `it` < iters yields the prior of forward `it`; the last pass commits
+                        iref.innov_ref_step(C.c_void_p(host.ctypes.data), params, K, iters, C.c_void_p(net.ctypes.data), C.c_void_p(gate.ctypes.data),
+                                            C.c_void_p(mx.ctypes.data), C.c_void_p(rec.ctypes.data), C.c_void_p(upd.ctypes.data),
+                                            C.c_void_p(pri.ctypes.data), int(it == iters))
+                        if it < iters:
+                            mean, cov = sh.infer(ids, np.ascontiguousarray(pri[it]))
+                            net[it, :, :8], net[it, :, 8:] = mean, cov.reshape(K, 64)
+                    if keep:
+                        host_ms.append((time.perf_counter() - t0) * 1e3)
+                t = t_new
+            out = {"K": K, "max_iekf_iteration": iters, "intervals": 16, "ticks": len(wall["step", "off"]),
+                   "record_bytes_per_call": _capi.INNOVATION_DTYPE.itemsize * iters * K}
+            for (kind, m), v in wall.items():
+                out[f"{kind}_{m}_ms_p50"], out[f"{kind}_{m}_ms_p10"], out[f"{kind}_{m}_ms_p90"] = pct(v, 50), pct(v, 10), pct(v, 90)
+                ev = event[kind, m]
+                out[f"{kind}_{m}_event_ms_p50"], out[f"{kind}_{m}_event_ms_p10"], out[f"{kind}_{m}_event_ms_p90"] = pct(ev, 50), pct(ev, 10), pct(ev, 90)
+            for kind in ("step", "advance"):
+                for m in ("on", "gate"):
+                    out[f"{kind}_{m}_minus_off_event_us"] = round(1e3 * (float(np.median(event[kind, m])) - float(np.median(event[kind, "off"]))), 1)
+            out["host_gated_1t_ms_p50"], out["host_gated_1t_ms_p10"], out["host_gated_1t_ms_p90"] = pct(host_ms, 50), pct(host_ms, 10), pct(host_ms, 90)
+            out["rejected"], out["mean_nis_used"] = rejected, (round(float(np.mean(nis)), 4) if nis else None)
+            print(json.dumps(out), flush=True)
+            for (e, s, f) in objs.values():
+                f.close(); s.close(); e.close()
+            sh.close(); eh.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--k", default="1,8,64,256")
@@ -144,12 +271,15 @@ def main():
     ap.add_argument("--threads", default="1,16")
     ap.add_argument("--feed", action="store_true")
     ap.add_argument("--predict", action="store_true")
+    ap.add_argument("--innov", action="store_true")
     ap.add_argument("--iter-variant", default=None)
     ap.add_argument("--iter-mc", type=int, default=8)
     ap.add_argument("--iter-p", type=float, default=0.1)
     a = ap.parse_args()
     if a.predict:
         return predict_mode(a)
+    if a.innov:
+        return innov_mode(a)
     from cuahn_vio_amd import _capi, replay, weights
     from cuahn_vio_amd.homography_net import HnetEngine, HnetFilters, HnetSessions
     ref = build_ref()
