@@ -42,6 +42,7 @@ SYMBOLS = [
     "hnet_filters_predict", "hnet_filters_newest_imu_time", "hnet_filters_last_predict_device_ms",
     "hnet_filters_enable_innovations", "hnet_filters_set_nis_gate", "hnet_filters_last_innovations", "hnet_filters_innovation_stats",
     "hnet_filters_reset_innovation_stats",
+    "hnet_op_photo_residual", "hnet_sessions_photo_residual", "hnet_filters_enable_photometric", "hnet_filters_last_photometric",
 ]
 # hnet_filters_advance's status per listed session (include/hnet.h HNET_ADV_*)
 ADV_STEPPED, ADV_WAIT_IMU, ADV_WAIT_INIT, ADV_INITIALIZED, ADV_PROPAGATED, ADV_NO_FRAME = range(6)
@@ -97,6 +98,12 @@ ODOMETRY_DTYPE = _np.dtype([("t_cam", "<f8"), ("t_imu", "<f8"), ("p", "<f8", 3),
                             ("intervals", "<i4"), ("status", "<i4")])
 # hnet_innovation: one record per IEKF iteration and stepping session (hnet_filters_last_innovations)
 INNOVATION_DTYPE = _np.dtype([("r", "<f8", 8), ("s_diag", "<f8", 8), ("nis", "<f8"), ("iteration", "<i4"), ("flag", "<i4")])
+
+
+# hnet_photo_residual: one record per (frame pair, candidate offsets); flags: PHOTO_DEGENERATE (include/hnet.h HNET_PHOTO_*)
+PHOTO_RESIDUAL_DTYPE = _np.dtype([("sum", "<f8"), ("sum_inside", "<f8"), ("n_inside", "<i4"), ("flags", "<i4")])
+PHOTO_DEGENERATE = 1
+PHOTO_MAX_CANDIDATES = 66
 
 
 class HnetError(RuntimeError):
@@ -235,6 +242,10 @@ def lib():
     L.hnet_filters_last_innovations.argtypes = [vp, C.c_int, vp]
     L.hnet_filters_innovation_stats.argtypes = [vp, C.c_int, C.POINTER(InnovationStats)]
     L.hnet_filters_reset_innovation_stats.argtypes = [vp, C.c_int]
+    L.hnet_op_photo_residual.argtypes = [vp, vp, vp, C.c_int, fp, C.c_int, vp, vp]
+    L.hnet_sessions_photo_residual.argtypes = [vp, C.c_int, vp, fp, C.c_int, vp]
+    L.hnet_filters_enable_photometric.argtypes = [vp]
+    L.hnet_filters_last_photometric.argtypes = [vp, C.c_int, vp]
     for name in SYMBOLS:
         getattr(L, name)   # AttributeError here = the library does not export what include/hnet.h declares
     _lib = L

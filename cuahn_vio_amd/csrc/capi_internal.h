@@ -8,6 +8,7 @@
 #include "geom.h"
 #include "kernels.h"
 #include "filters_dev.h"
+#include "photo_dev.h"
 #include "chain_args.h"
 #include "s3_format.h"
 

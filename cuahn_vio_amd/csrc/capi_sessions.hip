@@ -406,18 +406,38 @@ struct hnet_filters {
     double* d_max_nis = nullptr;               // [n_sessions], 0 = no gate
     std::vector<hnet_innovation_stats> innov_stats;
     int last_innov_n = 0;                      // sessions the last accepted step has records for; 0: it ran with innovations off
+    // photometric residual records (hnet_filters_enable_photometric): the output block then also holds {photo [n][2 + iters] PhotoRec, dense} behind the
+    // innovation records (if any), inside the one download; the slice partials of kernels_photo.hip are device scratch
+    bool photo = false;
+    size_t off_photo = 0;
+    PhotoRec* d_photo_part = nullptr;          // [B][2 + iters][PHOTO_SLICES]
+    int last_photo_n = 0;                      // as last_innov_n
 };
 
 static size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-// the offsets of the step's output block for max_batch B, with or without room for the innovation records behind the updates
-static void filters_out_layout(hnet_filters* f, int B, bool innov) {
+// the offsets of the step's output block for max_batch B: {net | prior_px | updates | innov (if enabled) | photo (if enabled) | work | results}
+static void filters_out_layout(hnet_filters* f, int B, bool innov, bool photo) {
     f->off_prior = al256((size_t)f->iters * B * 72 * sizeof(float));
     f->off_upd = f->off_prior + al256((size_t)f->iters * B * 8 * sizeof(float));
     f->off_innov = f->off_upd + al256((size_t)B * sizeof(int32_t));
-    f->off_work = f->off_innov + (innov ? al256((size_t)f->iters * B * sizeof(InnovRec)) : 0);
+    f->off_photo = f->off_innov + (innov ? al256((size_t)f->iters * B * sizeof(InnovRec)) : 0);
+    f->off_work = f->off_photo + (photo ? al256((size_t)(2 + f->iters) * B * sizeof(PhotoRec)) : 0);
     f->off_res = f->off_work + al256((size_t)B * sizeof(FilterRec));
     f->out_bytes = f->off_res + (size_t)B * sizeof(AdvanceResult);
+}
+// what a step of n stepping sessions downloads in one copy from the start of the output block when the states are not wanted: up to the last record section in use
+static size_t filters_down_head(const hnet_filters* f, int n) {
+    if (f->photo) return f->off_photo + (size_t)n * (2 + f->iters) * sizeof(PhotoRec);
+    if (f->innov) return f->off_innov + (size_t)f->iters * n * sizeof(InnovRec);
+    return f->off_upd + (size_t)n * sizeof(int32_t);
+}
+// (photometric enabled) the records of the step's n pairs in the context's staging: candidates zero | prior of iteration 0 | packed mean of every forward
+static hipError_t filters_launch_photo(hnet_filters* f, int n, hipStream_t st) {
+    hnet_ctx* c = f->s->ctx;
+    const PhotoCands cands{nullptr, reinterpret_cast<const float*>(f->d_out + f->off_prior), reinterpret_cast<const float*>(f->d_out), (size_t)c->cfg.max_batch * 72};
+    return launch_photo_residual((const uint8_t*)c->stage_prev, (const uint8_t*)c->stage_curr, n, cands, 2 + f->iters, f->d_photo_part,
+                                 reinterpret_cast<PhotoRec*>(f->d_out + f->off_photo), nullptr, st);
 }
 // after an accepted step with innovations on: the records [iters][n] of the sessions ids[0 .. n) go into their statistics
 static void filters_count_innovations(hnet_filters* f, int n, const int32_t* ids) {
@@ -491,7 +511,7 @@ void hnet_destroy_filters(hnet_filters* f) {
     (void)hipStreamSynchronize(c->stream);
     auto fr = [](void* p) { if (p) (void)hipFree(p); };
     fr(f->d_state); fr(f->d_params); fr(f->d_out); fr(f->d_prior_cam); fr(f->d_in);
-    fr(f->d_ring); fr(f->d_meta); fr(f->d_ip); fr(f->d_sel); fr(f->d_feed); fr(f->d_adv); fr(f->d_pred); fr(f->d_pred_sel); fr(f->d_max_nis);
+    fr(f->d_ring); fr(f->d_meta); fr(f->d_ip); fr(f->d_sel); fr(f->d_feed); fr(f->d_adv); fr(f->d_pred); fr(f->d_pred_sel); fr(f->d_max_nis); fr(f->d_photo_part);
     if (f->pin_pred) (void)hipHostFree(f->pin_pred);
     if (f->ev_p0) (void)hipEventDestroy(f->ev_p0);
     if (f->ev_p1) (void)hipEventDestroy(f->ev_p1);
@@ -519,7 +539,7 @@ int hnet_create_filters(hnet_sessions* s, int max_iekf_iteration, hnet_filters**
     f->t.assign(N, 0.0);
     f->cam_imu_dt.assign(N, dp.cam_imu_dt);
     f->imu_avg.assign(N, dp.imu_avg);
-    filters_out_layout(f, B, false);
+    filters_out_layout(f, B, false, false);
     f->t_seen.assign(N, -INFINITY);
     f->inited.assign(N, 0);
     f->last_slot.assign(N, -1);
@@ -659,8 +679,7 @@ int hnet_filters_step(hnet_filters* f, int n, const int32_t* ids, const double* 
     const float* h_net = reinterpret_cast<const float*>(f->pin_out);
     const float* h_prior = reinterpret_cast<const float*>(f->pin_out + f->off_prior);
     // the output block is laid out for max_batch: download the used parts of each section in one copy up to the last one needed
-    const size_t down = state_out ? f->off_work + (size_t)n * sizeof(FilterRec)
-                                  : f->innov ? f->off_innov + (size_t)I * n * sizeof(InnovRec) : f->off_upd + (size_t)n * sizeof(int32_t);
+    const size_t down = state_out ? f->off_work + (size_t)n * sizeof(FilterRec) : filters_down_head(f, n);
     InnovRec* d_innov = reinterpret_cast<InnovRec*>(f->d_out + f->off_innov);
     hipStream_t st = c->stream;
     const size_t up = o_off + (size_t)(n + 1) * 4;
@@ -682,6 +701,7 @@ int hnet_filters_step(hnet_filters* f, int n, const int32_t* ids, const double* 
             HIPCHK(c, launch_filter_update(d_ids, n, s->n, f->d_params, net_it, f->d_prior_cam, d_gate, it != I - 1, it == I - 1, d_work, d_upd, st));
         }
         HIPCHK(c, hipEventRecord(f->ev1, st));
+        if (f->photo) HIPCHK(c, filters_launch_photo(f, n, st));   // (behind ev1: hnet_filters_last_timing keeps its meaning; inside the attempt: a repeat recomputes the records)
         HIPCHK(c, hipMemcpyAsync(f->pin_out, f->d_out, down, hipMemcpyDeviceToHost, st));
         return filters_flags(ctx, flag_now, st);
     };
@@ -705,6 +725,7 @@ int hnet_filters_step(hnet_filters* f, int n, const int32_t* ids, const double* 
     if (state_out) memcpy(state_out, f->pin_out + f->off_work, (size_t)n * sizeof(FilterRec));
     f->last_n = n;
     f->last_innov_n = f->innov ? n : 0;
+    f->last_photo_n = f->photo ? n : 0;
     if (f->innov) filters_count_innovations(f, n, ids);
     float ms = 0;
     HIPCHK(c, hipEventElapsedTime(&ms, f->ev0, f->ev1));
@@ -908,6 +929,7 @@ int hnet_filters_advance(hnet_filters* f, int n, const int32_t* ids, hnet_filter
     if (net_out) memset(net_out, 0, (size_t)I * n * 72 * sizeof(float));
     if (updates) memset(updates, 0, (size_t)n * sizeof(int32_t));
     std::fill(f->last_slot.begin(), f->last_slot.end(), -1);
+    f->last_photo_n = 0;                                           // (a call in which nothing steps has no photometric records, whatever the call before it left)
     if (n_a == 0) return HNET_OK;
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
     const AdvLayout L(n_a, I);
@@ -964,8 +986,8 @@ int hnet_filters_advance(hnet_filters* f, int n, const int32_t* ids, hnet_filter
             HIPCHK(c, launch_filter_update(d_ids, n_s, s->n, f->d_params, net_it, f->d_prior_cam, d_gate, it != I - 1, it == I - 1, d_work, d_upd, st));
         }
         HIPCHK(c, hipEventRecord(f->ev1, st));
-        if (n_s) HIPCHK(c, hipMemcpyAsync(f->pin_out, f->d_out, f->innov ? f->off_innov + (size_t)I * n_s * sizeof(InnovRec) : f->off_upd + (size_t)n_s * sizeof(int32_t),
-                                          hipMemcpyDeviceToHost, st));
+        if (f->photo && n_s) HIPCHK(c, filters_launch_photo(f, n_s, st));          // (as in hnet_filters_step)
+        if (n_s) HIPCHK(c, hipMemcpyAsync(f->pin_out, f->d_out, filters_down_head(f, n_s), hipMemcpyDeviceToHost, st));
         if (state_out) HIPCHK(c, hipMemcpyAsync(f->pin_out + f->off_work, d_work, (size_t)n_a * sizeof(FilterRec), hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipMemcpyAsync(f->pin_out + f->off_res, d_res, (size_t)n_a * sizeof(AdvanceResult), hipMemcpyDeviceToHost, st));
         return filters_flags(ctx, flag_now, st);
@@ -1010,6 +1032,7 @@ int hnet_filters_advance(hnet_filters* f, int n, const int32_t* ids, hnet_filter
     }
     f->last_n = n_s;
     f->last_innov_n = f->innov ? n_s : 0;
+    f->last_photo_n = f->photo ? n_s : 0;
     if (f->innov && n_s) filters_count_innovations(f, n_s, hid);             // (the stepping sessions are the first n_s of the call's id table)
     float ms = 0;
     HIPCHK(c, hipEventElapsedTime(&ms, f->ev0, f->ev1));
@@ -1052,7 +1075,7 @@ int hnet_filters_enable_innovations(hnet_filters* f) {
     HIPCHK(c, hipStreamSynchronize(c->stream));                    // (nothing enqueued reads the old output block any more)
     const int N = f->s->n, B = c->cfg.max_batch;
     // the output block with room for the records: a new block, and the old one freed only when everything is there
-    filters_out_layout(f, B, true);
+    filters_out_layout(f, B, true, f->photo);
     uint8_t *d_out = nullptr, *pin_out = nullptr;
     double* d_max = nullptr;
     hipError_t e = hipMalloc((void**)&d_out, f->out_bytes);
@@ -1064,7 +1087,7 @@ int hnet_filters_enable_innovations(hnet_filters* f) {
         if (d_out) (void)hipFree(d_out);
         if (pin_out) (void)hipHostFree(pin_out);
         if (d_max) (void)hipFree(d_max);
-        filters_out_layout(f, B, false);
+        filters_out_layout(f, B, false, f->photo);
         return fail(c, HNET_ERR_DEVICE, std::string("hnet_filters_enable_innovations: ") + hipGetErrorString(e));
     }
     (void)hipFree(f->d_out);
@@ -1075,6 +1098,7 @@ int hnet_filters_enable_innovations(hnet_filters* f) {
     f->innov_stats.assign(N, hnet_innovation_stats{0, 0, 0, 0.0, 0.0});
     f->last_n = 0;                                                 // what last_priors / last_selection described went with the old block
     f->last_innov_n = 0;
+    f->last_photo_n = 0;
     std::fill(f->last_slot.begin(), f->last_slot.end(), -1);
     f->innov = true;
     return HNET_OK;
@@ -1110,6 +1134,81 @@ int hnet_filters_reset_innovation_stats(hnet_filters* f, int id) {
     if (!f) return HNET_ERR_INVALID_ARG;
     if (!f->innov || id < 0 || id >= f->s->n) return fail(f->s->ctx, HNET_ERR_INVALID_ARG, "hnet_filters_reset_innovation_stats: innovations not enabled or id out of range");
     f->innov_stats[id] = hnet_innovation_stats{0, 0, 0, 0.0, 0.0};
+    return HNET_OK;
+}
+
+// ---- photometric residual records (include/hnet.h): csrc/kernels_photo.hip on the sessions' current pairs and inside hnet_filters_step / _advance ----
+
+int hnet_sessions_photo_residual(hnet_sessions* s, int n, const int32_t* ids, const float* offsets_px, int m, hnet_photo_residual* out) {
+    if (!s) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = s->ctx;
+    if (!offsets_px || !out || m < 1 || m > PHOTO_MAX_CAND) return fail(c, HNET_ERR_INVALID_ARG, "hnet_sessions_photo_residual: offsets / out, 1 <= m <= 66");
+    int rc = sessions_check_ids(s, n, ids);
+    if (rc != HNET_OK) return rc;
+    for (int i = 0; i < n; i++)
+        if (s->st[ids[i]].count < 2) return fail(c, HNET_ERR_NOT_READY, "HNet cannot inference! Only has one image!");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    // ONE upload {offsets [n][m][8] f32 | pair table [n][2] i32}; nothing of the sessions' own tables, events or bookkeeping is touched
+    const size_t off_bytes = (size_t)n * m * 8 * sizeof(float), up = off_bytes + (size_t)n * 8, rec_bytes = (size_t)n * m * sizeof(PhotoRec);
+    std::vector<uint8_t> h_in(up), h_out(rec_bytes);
+    memcpy(h_in.data(), offsets_px, off_bytes);
+    for (int i = 0; i < n; i++) sessions_pair(s, ids[i], reinterpret_cast<int32_t*>(h_in.data() + off_bytes) + 2 * i);
+    DevTemps t;
+    uint8_t* d_in = nullptr;
+    PhotoRec *d_part = nullptr, *d_rec = nullptr;
+    HIPCHK(c, t.alloc(&d_in, up));
+    HIPCHK(c, t.alloc(&d_part, photo_partial_count(n, m)));
+    HIPCHK(c, t.alloc(&d_rec, (size_t)n * m));
+    hipStream_t st = c->stream;
+    HIPCHK(c, hipMemcpyAsync(d_in, h_in.data(), up, hipMemcpyHostToDevice, st));
+    HIPCHK(c, launch_session_gather(s->ring, 2 * s->n, reinterpret_cast<const int32_t*>(d_in + off_bytes), n, (uint8_t*)c->stage_prev, (uint8_t*)c->stage_curr, st));
+    const PhotoCands cands{reinterpret_cast<const float*>(d_in), nullptr, nullptr, 0};
+    HIPCHK(c, launch_photo_residual((const uint8_t*)c->stage_prev, (const uint8_t*)c->stage_curr, n, cands, m, d_part, d_rec, nullptr, st));
+    HIPCHK(c, hipMemcpyAsync(h_out.data(), d_rec, rec_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    memcpy(out, h_out.data(), rec_bytes);
+    return HNET_OK;
+}
+
+int hnet_filters_enable_photometric(hnet_filters* f) {
+    if (!f) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = f->s->ctx;
+    if (f->photo) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_enable_photometric: already enabled");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    HIPCHK(c, hipStreamSynchronize(c->stream));                    // (nothing enqueued reads the old output block any more)
+    const int B = c->cfg.max_batch;
+    // as hnet_filters_enable_innovations: a new output block with room for the records, the old one freed only when everything is there
+    filters_out_layout(f, B, f->innov, true);
+    uint8_t *d_out = nullptr, *pin_out = nullptr;
+    PhotoRec* d_part = nullptr;
+    hipError_t e = hipMalloc((void**)&d_out, f->out_bytes);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&pin_out, f->out_bytes, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_part, photo_partial_count(B, 2 + f->iters) * sizeof(PhotoRec));
+    if (e != hipSuccess) {
+        if (d_out) (void)hipFree(d_out);
+        if (pin_out) (void)hipHostFree(pin_out);
+        if (d_part) (void)hipFree(d_part);
+        filters_out_layout(f, B, f->innov, false);
+        return fail(c, HNET_ERR_DEVICE, std::string("hnet_filters_enable_photometric: ") + hipGetErrorString(e));
+    }
+    (void)hipFree(f->d_out);
+    (void)hipHostFree(f->pin_out);
+    f->d_out = d_out;
+    f->pin_out = pin_out;
+    f->d_photo_part = d_part;
+    f->last_n = 0;                                                 // what last_priors / last_selection / last_innovations described went with the old block
+    f->last_innov_n = 0;
+    f->last_photo_n = 0;
+    std::fill(f->last_slot.begin(), f->last_slot.end(), -1);
+    f->photo = true;
+    return HNET_OK;
+}
+
+int hnet_filters_last_photometric(const hnet_filters* f, int n, hnet_photo_residual* out) {
+    if (!f || !out) return HNET_ERR_INVALID_ARG;
+    if (!f->photo || f->last_photo_n < 1) return fail(f->s->ctx, HNET_ERR_INVALID_ARG, "hnet_filters_last_photometric: the last step ran without photometric records");
+    if (n != f->last_photo_n) return fail(f->s->ctx, HNET_ERR_INVALID_ARG, "hnet_filters_last_photometric: n differs from the last step's");
+    memcpy(out, f->pin_out + f->off_photo, (size_t)n * (2 + f->iters) * sizeof(PhotoRec));
     return HNET_OK;
 }
 

@@ -167,6 +167,7 @@ int create_impl(const hnet_config* cfg_in, const uint8_t* blob, size_t len, hnet
     CK(hipSetDevice(g.device_id));
     CK(conv_kernels_init_device());      // dynamic-LDS limits of the patch / fused kernels: per device, so set at every create
     CK(chain_init_device());
+    CK(photo_init_device());
     if (preset_stream) { c->stream = preset_stream; c->owns_stream = false; }      // a group member: the group created its streams first, each on a priority level / hardware queue of its own
     else CK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     CK(hipEventCreate(&c->ev0));
@@ -980,6 +981,38 @@ int hnet_op_dlt(hnet_ctx* c, const float* dst, int n, float* H) {
     HIPCHK(c, launch_dlt(d_d, d_h, n, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(H, d_h, (size_t)n * 36, hipMemcpyDeviceToHost));
+    return HNET_OK;
+}
+
+static_assert(sizeof(hnet_photo_residual) == sizeof(PhotoRec) && (int)HNET_PHOTO_DEGENERATE == PHOTO_DEGENERATE && (int)HNET_PHOTO_MAX_CANDIDATES == PHOTO_MAX_CAND,
+              "hnet_photo_residual is the PhotoRec layout");
+
+// photometric residual records of n host frame pairs under m candidate offset vectors each (csrc/kernels_photo.hip): ONE upload {img1 | img2 | offsets},
+// the kernel and its slice sum, ONE download {records | map}, one synchronisation
+int hnet_op_photo_residual(hnet_ctx* c, const uint8_t* img1, const uint8_t* img2, int n, const float* offsets_px, int m, hnet_photo_residual* out, float* map_out) {
+    if (!c) return HNET_ERR_INVALID_ARG;
+    if (!img1 || !img2 || !offsets_px || !out || n < 1 || m < 1 || m > PHOTO_MAX_CAND) return fail(c, HNET_ERR_INVALID_ARG, "hnet_op_photo_residual: frames / offsets / out, n >= 1, 1 <= m <= 66");
+    if (n > c->cfg.max_batch) return fail(c, HNET_ERR_CAPACITY, "hnet_op_photo_residual: n exceeds max_batch");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    const size_t img = (size_t)n * NPIX, off_bytes = (size_t)n * m * 8 * sizeof(float), up = 2 * img + off_bytes;            // (NPIX is a multiple of 16: every section stays aligned)
+    const size_t rec_bytes = ((size_t)n * m * sizeof(PhotoRec) + 15) & ~(size_t)15, map_bytes = map_out ? (size_t)n * m * NPIX * sizeof(float) : 0;
+    DevTemps t;
+    uint8_t *d_in = nullptr, *d_res = nullptr;
+    PhotoRec* d_part = nullptr;
+    HIPCHK(c, t.alloc(&d_in, up));
+    HIPCHK(c, t.alloc(&d_res, rec_bytes + map_bytes));
+    HIPCHK(c, t.alloc(&d_part, photo_partial_count(n, m)));
+    std::vector<uint8_t> h_in(up), h_res(rec_bytes + map_bytes);
+    memcpy(h_in.data(), img1, img);
+    memcpy(h_in.data() + img, img2, img);
+    memcpy(h_in.data() + 2 * img, offsets_px, off_bytes);
+    HIPCHK(c, hipMemcpyAsync(d_in, h_in.data(), up, hipMemcpyHostToDevice, c->stream));
+    const PhotoCands cands{reinterpret_cast<const float*>(d_in + 2 * img), nullptr, nullptr, 0};
+    HIPCHK(c, launch_photo_residual(d_in, d_in + img, n, cands, m, d_part, reinterpret_cast<PhotoRec*>(d_res), map_out ? reinterpret_cast<float*>(d_res + rec_bytes) : nullptr, c->stream));
+    HIPCHK(c, hipMemcpyAsync(h_res.data(), d_res, rec_bytes + map_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    memcpy(out, h_res.data(), (size_t)n * m * sizeof(PhotoRec));
+    if (map_out) memcpy(map_out, h_res.data() + rec_bytes, map_bytes);
     return HNET_OK;
 }
 

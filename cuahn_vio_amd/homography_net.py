@@ -247,6 +247,22 @@ class HnetEngine:
         check(self._h, self._L.hnet_op_dlt(self._h, _fp(d), d.shape[0], _fp(out)))
         return out
 
+    def op_photo_residual(self, img1, img2, offsets, want_map=False):
+        """photometric residual records (hnet_op_photo_residual): img1 / img2 uint8 [n, 224, 320], offsets [n, m, 8] pixels ->
+        records [n, m] of _capi.PHOTO_RESIDUAL_DTYPE (, the error map itself [n, m, 224, 320] float32)"""
+        a = np.ascontiguousarray(img1, dtype=np.uint8).reshape(-1, IMG_H, IMG_W)
+        b = np.ascontiguousarray(img2, dtype=np.uint8).reshape(-1, IMG_H, IMG_W)
+        n = a.shape[0]
+        if b.shape[0] != n:
+            raise ValueError("img1 and img2 must hold the same number of frames")
+        off = np.ascontiguousarray(offsets, dtype=np.float32).reshape(n, -1, 8)
+        m = off.shape[1]
+        out = np.zeros((n, m), _capi.PHOTO_RESIDUAL_DTYPE)
+        emap = np.zeros((n, m, IMG_H, IMG_W), np.float32) if want_map else None
+        check(self._h, self._L.hnet_op_photo_residual(self._h, a.ctypes.data, b.ctypes.data, n, _fp(off), m, out.ctypes.data,
+                                                      emap.ctypes.data if want_map else None))
+        return (out, emap) if want_map else out
+
     def op_conv(self, layer, x):
         from .weights import CONV_LAYERS
         x = np.ascontiguousarray(x, dtype=np.float32)
@@ -502,6 +518,15 @@ class HnetSessions:
             self._check(self._L.hnet_sessions_infer_iter(self._s, int(iteration), *args))
         return (mean, cov, err) if want_err else (mean, cov)
 
+    def photo_residual(self, ids, offsets):
+        """photometric residual records of the listed sessions' current pairs under offsets [n, m, 8] pixels -> [n, m] of _capi.PHOTO_RESIDUAL_DTYPE;
+        read-only (hnet_sessions_photo_residual)"""
+        ids, n = self._ids(ids)
+        off = np.ascontiguousarray(offsets, dtype=np.float32).reshape(n, -1, 8)
+        out = np.zeros((n, off.shape[1]), _capi.PHOTO_RESIDUAL_DTYPE)
+        self._check(self._L.hnet_sessions_photo_residual(self._s, n, ids.ctypes.data, _fp(off), off.shape[1], out.ctypes.data))
+        return out
+
     def image_count(self, id):
         return int(self._L.hnet_sessions_image_count(self._s, int(id)))
 
@@ -687,6 +712,18 @@ class HnetFilters:
 
     def reset_innovation_stats(self, id):
         self._check(self._L.hnet_filters_reset_innovation_stats(self._f, int(id)))
+
+    # ---- photometric residual records ----
+    def enable_photometric(self):
+        """from now on every step / advance also returns 2 + iters photometric residual records per stepping session (once per object)"""
+        self._check(self._L.hnet_filters_enable_photometric(self._f))
+
+    def last_photometric(self, n):
+        """the records [n, 2 + iters] of _capi.PHOTO_RESIDUAL_DTYPE of the last step (of n sessions; another n is refused): identity, the prior of
+        iteration 0, the packed mean of every forward"""
+        out = np.zeros((int(n), 2 + self.iters), _capi.PHOTO_RESIDUAL_DTYPE)
+        self._check(self._L.hnet_filters_last_photometric(self._f, int(n), out.ctypes.data))
+        return out
 
     def last_priors(self, n):
         """the fp32 priors [iters, n, 8] the forwards of the last step (of n sessions; another n is refused) read"""

@@ -487,6 +487,42 @@ int  hnet_filters_last_innovations(const hnet_filters* f, int n, hnet_innovation
 int  hnet_filters_innovation_stats(const hnet_filters* f, int id, hnet_innovation_stats* out);
 int  hnet_filters_reset_innovation_stats(hnet_filters* f, int id);
 
+/* ---- photometric residual records: how well a homography agreed with the IMAGES -------------------------------------------------------------
+ * The reference's instrument is the error map |warp(img2, H_total) - img1| * 255 (model_to_trace.py:319-327); what an operator of many cameras reads
+ * is its mean.  A record is that map summed on the device (csrc/kernels_photo.hip) for H = (float) dlt_solve(p4 + offsets), offsets being 8 floats in
+ * pixels, ul, bl, br, ur: for the network's packed mean this is the reference's H_total up to scale.  Every pixel's value has the bits of the err_map
+ * paths for the same H; the sums are taken in double in a fixed order (a record depends on its pair and offsets alone, never on the batch or the run).
+ * A pixel is "inside" when its sampling position (ix, iy) in img2 has -0.5 < ix < 319.5 and -0.5 < iy < 223.5; sum_inside / n_inside is the residual
+ * to watch, because `sum` also holds the pixels that merely left the image (zeros padding).  "estimate << prior ~ identity" means the network is
+ * working; "estimate ~ identity" on a moving camera means its output has gone bad, which a consistent NIS cannot show.  No emit_error_map needed. */
+typedef struct hnet_photo_residual {
+    double  sum;          /* sum over all 71 680 pixels of e = |warp(img2, H)(u, v) - img1(u, v)| * 255, zeros padding: the reference's map, summed */
+    double  sum_inside;   /* sum of e over the pixels whose sampling position lies inside img2 */
+    int32_t n_inside;     /* their number */
+    int32_t flags;        /* HNET_PHOTO_DEGENERATE: H has a non-finite entry (every sample is 0, n_inside = 0) */
+} hnet_photo_residual;
+enum { HNET_PHOTO_DEGENERATE = 1 };
+enum { HNET_PHOTO_MAX_CANDIDATES = 66 };
+/* operator call, host pointers: img1 / img2 u8 [n][224][320], offsets_px [n][m][8], out [n][m]; map_out NULL or float [n][m][224][320] (the map itself).
+ * 1 <= n <= max_batch, 1 <= m <= 66 (HNET_ERR_CAPACITY / HNET_ERR_INVALID_ARG otherwise; an error writes nothing).  One upload, one download, one
+ * synchronisation on the context's stream. */
+int  hnet_op_photo_residual(hnet_ctx* ctx, const uint8_t* img1, const uint8_t* img2, int n, const float* offsets_px, int m, hnet_photo_residual* out,
+                            float* map_out);
+/* the same on the current pair of each listed session (img1 / img2 = the frames a forward receives as prev / curr), for any hypothesis, e.g.
+ * hnet_odometry.prior_px of a predict at the frame's time.  Read-only: counts, sequence numbers, times and hnet_sessions_last_timing stay as they were.
+ * Errors as hnet_sessions_infer: a bad or repeated id (HNET_ERR_INVALID_ARG), fewer than two images (HNET_ERR_NOT_READY), n > max_batch (HNET_ERR_CAPACITY) */
+int  hnet_sessions_photo_residual(hnet_sessions* s, int n, const int32_t* ids, const float* offsets_px, int m, hnet_photo_residual* out);
+/* once per filters object (HNET_ERR_INVALID_ARG on a second call; works with hnet_filters_enable_innovations in either order): from now on every step
+ * and advance also produces, per stepping session, 2 + max_iekf_iteration records on the step's own frame pair - [0] zero offsets (no motion), [1] the
+ * fp32 prior of iteration 0 (what hnet_filters_last_priors reports, whether or not use_prior let the forward read it), [2 + it] the packed mean of
+ * forward `it` - inside the call's one download, two launches after the last update.  Nothing is gated on them, and the states, priors, network
+ * outputs, updates, innovation records and sequence numbers are what they are without the call, bit for bit.  hnet_filters_last_priors has nothing
+ * to describe until the next step. */
+int  hnet_filters_enable_photometric(hnet_filters* f);
+/* the records [n][2 + max_iekf_iteration] of the last step (n: its n) or advance (n: its STEPPED sessions, in the order listed).  A wrong n, or a last
+ * call that ran without hnet_filters_enable_photometric (or in which nothing stepped): HNET_ERR_INVALID_ARG, nothing written */
+int  hnet_filters_last_photometric(const hnet_filters* f, int n, hnet_photo_residual* out);
+
 int hnet_synchronize(hnet_ctx* ctx, void* stream);
 int hnet_last_timing(const hnet_ctx* ctx, hnet_timing* out);
 

@@ -25,7 +25,9 @@ hnet_sessions_infer, the prior of forward `it` being the one the header hands it
    python tools/filters_bench.py [--k 1,8,64,256] [--iters 1,3] [--ticks 20] [--warmup 3] [--threads 1,16] [--feed]
                                  [--iter-variant prior1 --iter-mc 8 --iter-p 0.1]
    python tools/filters_bench.py --predict [--k 1,8,64,256] [--ticks 20] [--warmup 3] [--threads 1,16]
-   python tools/filters_bench.py --innov [--k 1,8,64,256] [--iters 1,3] [--ticks 20] [--warmup 3]"""
+   python tools/filters_bench.py --innov [--k 1,8,64,256] [--iters 1,3] [--ticks 20] [--warmup 3]
+--photo is a mode of its own (photometric residual records): step and advance with the records off and on, in one process on the same inputs.
+   python tools/filters_bench.py --photo [--k 1,8,64,256] [--iters 1,3] [--ticks 20] [--warmup 3]"""
 import argparse
 import ctypes as C
 import json
@@ -262,6 +264,92 @@ def innov_mode(a):
             sh.close(); eh.close()
 
 
+def photo_mode(a):
+    """photometric residual records: per (K, iterations) two filters objects for hnet_filters_step and two fed ones for hnet_filters_advance, each
+    on its own context, with the records off and on; every tick runs all four on the same frames and IMU window, in rotating order.  The records are
+    launched behind the event that closes hnet_filters_last_timing's window, so the wall time of the call (it ends in the call's synchronisation) is the
+    figure that contains them; the event time shows that the window itself did not move."""
+    from cuahn_vio_amd import _capi, replay, weights
+    from cuahn_vio_amd.homography_net import HnetEngine, HnetFilters, HnetSessions
+    blob = weights.pack_state_dict(weights.synthetic_state(0))
+    fx = replay.load_fixture("indoor_forward_7")
+    pool = np.stack([replay.render_frame(fx, 100 + j) for j in range(16)])
+    kw = dict(variant="prior3", mc_samples=16, dropout_p=0.05, mc_seed=1)
+    modes = ("off", "on")
+
+    def pct(x, q):
+        return round(float(np.percentile(x, q)), 3)
+
+    for K in [int(x) for x in a.k.split(",")]:
+        for iters in [int(x) for x in a.iters.split(",")]:
+            ids = np.arange(K, dtype=np.int32)
+            st0 = np.zeros(1, _capi.FILTER_STATE_DTYPE)
+            st0["q"] = [1, 0, 0, 0]
+            st0["p"] = [0, 0, -1.0]
+            st0["cov"] = np.diag(np.r_[np.full(15, 1e-3), np.full(12, 1e-6)])
+            objs = {}
+            for kind in ("step", "advance"):
+                for m in modes:
+                    e = HnetEngine(blob, max_batch=K, **kw)
+                    s = HnetSessions(e, K)
+                    f = HnetFilters(s, iters)
+                    if m == "on":
+                        f.enable_photometric()
+                    if kind == "advance":
+                        f.enable_feed(256)
+                    for i in range(K):
+                        f.set_state(i, st0[0])
+                    objs[kind, m] = (e, s, f)
+            rng = np.random.default_rng(K)
+            wall = {k: [] for k in objs}
+            event = {k: [] for k in objs}
+            res = []
+            newest, t = -np.inf, 0.0
+            order = list(objs)
+            for tick in range(a.warmup + a.ticks):
+                t_new = t + 0.0325
+                fr = np.repeat(pool[tick % len(pool)][None], K, 0)
+                for (_, s, _) in objs.values():
+                    s.push(ids, fr, t=[t_new] * K)
+                win = imu_window(rng, t)
+                new = win[win["t"] > newest]
+                newest = float(new["t"][-1])
+                for m in modes:
+                    objs["advance", m][2].feed_imu(ids, [new] * K)
+                keep = tick > a.warmup
+                for key in order[tick % len(order):] + order[:tick % len(order)]:
+                    f = objs[key][2]
+                    if key[0] == "step" and tick == 0:              # one image per session so far: nothing to step
+                        continue
+                    t0 = time.perf_counter()
+                    if key[0] == "step":
+                        f.step(ids, [t_new] * K, [win] * K)
+                    else:
+                        status = f.advance(ids)[3]
+                    d = (time.perf_counter() - t0) * 1e3
+                    if key[0] == "advance" and tick > 0:
+                        assert (status == _capi.ADV_STEPPED).all(), status
+                    if keep:
+                        wall[key].append(d)
+                        event[key].append(f.last_timing()["device_ms"])
+                    if keep and key == ("step", "on"):
+                        r = f.last_photometric(K)
+                        res.append((r["sum_inside"] / np.maximum(r["n_inside"], 1)).mean(axis=0))
+                t = t_new
+            out = {"K": K, "max_iekf_iteration": iters, "intervals": 16, "ticks": len(wall["step", "off"]), "candidates": 2 + iters,
+                   "record_bytes_per_call": _capi.PHOTO_RESIDUAL_DTYPE.itemsize * (2 + iters) * K}
+            for (kind, m), v in wall.items():
+                out[f"{kind}_{m}_ms_p50"], out[f"{kind}_{m}_ms_p10"], out[f"{kind}_{m}_ms_p90"] = pct(v, 50), pct(v, 10), pct(v, 90)
+                ev = event[kind, m]
+                out[f"{kind}_{m}_event_ms_p50"], out[f"{kind}_{m}_event_ms_p10"], out[f"{kind}_{m}_event_ms_p90"] = pct(ev, 50), pct(ev, 10), pct(ev, 90)
+            for kind in ("step", "advance"):
+                out[f"{kind}_on_minus_off_wall_us"] = round(1e3 * (float(np.median(wall[kind, "on"])) - float(np.median(wall[kind, "off"]))), 1)
+            out["mean_inside_residual_identity_prior_estimates"] = [round(float(x), 3) for x in np.mean(res, axis=0)]
+            print(json.dumps(out), flush=True)
+            for (e, s, f) in objs.values():
+                f.close(); s.close(); e.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--k", default="1,8,64,256")
@@ -272,6 +360,7 @@ def main():
     ap.add_argument("--feed", action="store_true")
     ap.add_argument("--predict", action="store_true")
     ap.add_argument("--innov", action="store_true")
+    ap.add_argument("--photo", action="store_true")
     ap.add_argument("--iter-variant", default=None)
     ap.add_argument("--iter-mc", type=int, default=8)
     ap.add_argument("--iter-p", type=float, default=0.1)
@@ -280,6 +369,8 @@ def main():
         return predict_mode(a)
     if a.innov:
         return innov_mode(a)
+    if a.photo:
+        return photo_mode(a)
     from cuahn_vio_amd import _capi, replay, weights
     from cuahn_vio_amd.homography_net import HnetEngine, HnetFilters, HnetSessions
     ref = build_ref()
