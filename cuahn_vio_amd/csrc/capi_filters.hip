@@ -1,0 +1,887 @@
+// capi_filters.hip — hnet_filters_* and hnet_filter_default_* of include/hnet.h: one device filter per session of a sessions object (sessions_internal.h).
+// hnet_filters_step and hnet_filters_advance differ in how a call's states get their readings (the host's windows / the device's IMU rings and the
+// initialiser); the IEKF iterations of an attempt, the overflow test and the bookkeeping of an accepted call are one piece of code each, below.
+#include "sessions_internal.h"
+
+using namespace hnet;
+using namespace capi;
+
+// ---- filters: one 27-state filter per session of a sessions object (include/hnet.h).  Device: the states [n_sessions], the parameters [n_sessions] and
+// the step's buffers sized for max_batch; host: each state's time (the t_frame check) and camera-IMU offset (the selection window).  A step works on a
+// copy of the listed states (work) and scatters it back only once its forwards are accepted: an overflow / timeout repeat starts from the untouched states.
+struct hnet_filters {
+    hnet_sessions* s = nullptr;
+    int iters = 1;
+    FilterRec* d_state = nullptr;              // [n_sessions]
+    FilterParams* d_params = nullptr;          // [n_sessions]
+    std::vector<double> t, cam_imu_dt;         // host mirror of state t / the offset of each session
+    std::vector<int> imu_avg;
+    // step outputs, ONE device block {net [iters][B][72] f32 | prior_px [iters][B][8] f32 | updates [B] i32 | work [B] FilterRec} and its pinned copy
+    uint8_t* d_out = nullptr;
+    uint8_t* pin_out = nullptr;
+    size_t off_prior = 0, off_upd = 0, off_work = 0, out_bytes = 0;
+    double* d_prior_cam = nullptr;             // [B][8]
+    // step inputs, ONE pinned block and its device copy (grown on demand): {readings [R] | t_frame [n] | seq [iters][n] | ids [n] | gate [n] | pairs [n][2] | rd_off [n + 1]}
+    uint8_t* pin_in = nullptr;
+    uint8_t* d_in = nullptr;
+    size_t in_cap = 0;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hnet_timing timing = {};
+    int last_n = 0;                            // sessions of the last accepted step (hnet_filters_last_priors)
+    // ---- the IMU feed (hnet_filters_enable_feed): per session a device ring of `cap` readings, its head / count mirrored here, the newest reading's time,
+    // whether the filter has a state (set_state or the initialiser) and, while it has none, the stamp of the last frame the initialiser dropped
+    int cap = 0;
+    hnet_ekf::ImuData* d_ring = nullptr;       // [n_sessions][cap]
+    ImuRingMeta* d_meta = nullptr;             // [n_sessions]
+    InitParams* d_ip = nullptr;                // [n_sessions]
+    hnet_ekf::ImuData* d_sel = nullptr;        // [B][2 (cap + 2)]: filter_select_kernel's span and selection
+    std::vector<ImuRingMeta> meta;
+    std::vector<double> imu_newest, t_seen;
+    std::vector<uint8_t> inited;
+    std::vector<hnet_init_params> ip;
+    std::vector<int> last_slot;                // session -> its workgroup in the last advance, -1 if none (hnet_filters_last_selection)
+    // feed_imu: ONE pinned block {segments [n] | readings} and its device copy (grown on demand); ev_feed: the pinned block's last upload
+    uint8_t* pin_feed = nullptr;
+    uint8_t* d_feed = nullptr;
+    size_t feed_cap = 0;
+    hipEvent_t ev_feed = nullptr;
+    // advance: ONE pinned block {jobs [B] | seq [iters][B] | gate [B] | ids [B] | pairs [B][2]} and its device copy; the results [B] behind the step's output block
+    uint8_t* pin_adv = nullptr;
+    uint8_t* d_adv = nullptr;
+    size_t off_res = 0;
+    // predict (hnet_filters_predict), allocated by its first call: ONE block {jobs [B] | records [B]}, its pinned copy, and the kernel's own scratch
+    uint8_t* pin_pred = nullptr;
+    uint8_t* d_pred = nullptr;
+    hnet_ekf::ImuData* d_pred_sel = nullptr;   // [B][2 (cap + 2)]
+    size_t off_pred_out = 0;
+    hipEvent_t ev_p0 = nullptr, ev_p1 = nullptr;
+    bool pred_timed = false;                   // set by the first hnet_filters_last_predict_device_ms: only then a predict records its two events
+    double pred_ms = NAN;
+    // innovations (hnet_filters_enable_innovations): the output block then is {net | prior_px | updates | innov [iters][n] InnovRec, dense | work | results},
+    // so that the records lie inside the one download; the per-session gates; the statistics, accumulated from the records of accepted steps
+    bool innov = false;
+    size_t off_innov = 0;
+    double* d_max_nis = nullptr;               // [n_sessions], 0 = no gate
+    std::vector<hnet_innovation_stats> innov_stats;
+    int last_innov_n = 0;                      // sessions the last accepted step has records for; 0: it ran with innovations off
+    // photometric residual records (hnet_filters_enable_photometric): the output block then also holds {photo [n][2 + iters] PhotoRec, dense} behind the
+    // innovation records (if any), inside the one download; the slice partials of kernels_photo.hip are device scratch
+    bool photo = false;
+    size_t off_photo = 0;
+    PhotoRec* d_photo_part = nullptr;          // [B][2 + iters][PHOTO_SLICES]
+    int last_photo_n = 0;                      // as last_innov_n
+};
+
+static size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// grows a pinned block and its device copy to `want` bytes; the stream is drained first (enqueued work may still read either)
+static int grow_block(hnet_ctx* c, uint8_t** pin, uint8_t** dev, size_t* cap, size_t want) {
+    if (*cap >= want) return HNET_OK;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (*pin) HIPCHK(c, hipHostFree(*pin));
+    if (*dev) HIPCHK(c, hipFree(*dev));
+    *pin = *dev = nullptr;
+    *cap = 0;
+    HIPCHK(c, hipHostMalloc((void**)pin, want, hipHostMallocDefault));
+    HIPCHK(c, hipMalloc((void**)dev, want));
+    *cap = want;
+    return HNET_OK;
+}
+// free and forget: what a failed enable / first call gives back is what hnet_destroy_filters gives back
+template <typename T> static void drop_dev(T*& p) { if (p) (void)hipFree((void*)p); p = nullptr; }
+static void drop_pin(uint8_t*& p) { if (p) (void)hipHostFree(p); p = nullptr; }
+static void drop_event(hipEvent_t& e) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+static void filters_drop_feed(hnet_filters* f) {                  // hnet_filters_enable_feed
+    drop_dev(f->d_ring); drop_dev(f->d_meta); drop_dev(f->d_ip); drop_dev(f->d_sel); drop_dev(f->d_adv);
+    drop_pin(f->pin_adv);
+    drop_event(f->ev_feed);
+}
+static void filters_drop_predict(hnet_filters* f) {               // predict_buffers
+    drop_dev(f->d_pred_sel); drop_dev(f->d_pred);
+    drop_pin(f->pin_pred);
+    drop_event(f->ev_p0); drop_event(f->ev_p1);
+}
+
+extern "C" {
+
+// the offsets of the step's output block for max_batch B: {net | prior_px | updates | innov (if enabled) | photo (if enabled) | work | results}
+static void filters_out_layout(hnet_filters* f, int B, bool innov, bool photo) {
+    f->off_prior = al256((size_t)f->iters * B * 72 * sizeof(float));
+    f->off_upd = f->off_prior + al256((size_t)f->iters * B * 8 * sizeof(float));
+    f->off_innov = f->off_upd + al256((size_t)B * sizeof(int32_t));
+    f->off_photo = f->off_innov + (innov ? al256((size_t)f->iters * B * sizeof(InnovRec)) : 0);
+    f->off_work = f->off_photo + (photo ? al256((size_t)(2 + f->iters) * B * sizeof(PhotoRec)) : 0);
+    f->off_res = f->off_work + al256((size_t)B * sizeof(FilterRec));
+    f->out_bytes = f->off_res + (size_t)B * sizeof(AdvanceResult);
+}
+// the sections of the output block as typed pointers, on the device (d) and in the pinned copy (h)
+struct OutView { float *net, *prior; int32_t* upd; InnovRec* innov; PhotoRec* photo; FilterRec* work; AdvanceResult* res; };
+struct OutViews { OutView d, h; };
+static OutView filters_out_view(const hnet_filters* f, uint8_t* b) {
+    return OutView{reinterpret_cast<float*>(b), reinterpret_cast<float*>(b + f->off_prior), reinterpret_cast<int32_t*>(b + f->off_upd), reinterpret_cast<InnovRec*>(b + f->off_innov),
+                   reinterpret_cast<PhotoRec*>(b + f->off_photo), reinterpret_cast<FilterRec*>(b + f->off_work), reinterpret_cast<AdvanceResult*>(b + f->off_res)};
+}
+static OutViews filters_out_views(const hnet_filters* f) { return OutViews{filters_out_view(f, f->d_out), filters_out_view(f, f->pin_out)}; }
+// what a step of n stepping sessions downloads in one copy from the start of the output block when the states are not wanted: up to the last record section in use
+static size_t filters_down_head(const hnet_filters* f, int n) {
+    if (f->photo) return f->off_photo + (size_t)n * (2 + f->iters) * sizeof(PhotoRec);
+    if (f->innov) return f->off_innov + (size_t)f->iters * n * sizeof(InnovRec);
+    return f->off_upd + (size_t)n * sizeof(int32_t);
+}
+// (photometric enabled) the records of the step's n pairs in the context's staging: candidates zero | prior of iteration 0 | packed mean of every forward
+static hipError_t filters_launch_photo(hnet_filters* f, const OutView& d, int n, hipStream_t st) {
+    hnet_ctx* c = f->s->ctx;
+    const PhotoCands cands{nullptr, d.prior, d.net, (size_t)c->cfg.max_batch * 72};
+    return launch_photo_residual((const uint8_t*)c->stage_prev, (const uint8_t*)c->stage_curr, n, cands, 2 + f->iters, f->d_photo_part, d.photo, nullptr, st);
+}
+// after an accepted step with innovations on: the records [iters][n] of the sessions ids[0 .. n) go into their statistics
+static void filters_count_innovations(hnet_filters* f, int n, const int32_t* ids) {
+    const InnovRec* rec = filters_out_view(f, f->pin_out).innov;
+    for (int it = 0; it < f->iters; it++)
+        for (int j = 0; j < n; j++) {
+            const InnovRec& r = rec[(size_t)it * n + j];
+            hnet_innovation_stats& a = f->innov_stats[ids[j]];
+            if (r.flag == HNET_INNOV_USED) { a.used++; a.sum_nis += r.nis; }
+            else if (r.flag == HNET_INNOV_REJECTED) a.rejected++;
+            else if (r.flag == HNET_INNOV_SINGULAR) a.singular++;
+            if ((r.flag == HNET_INNOV_USED || r.flag == HNET_INNOV_REJECTED) && r.nis > a.max_nis) a.max_nis = r.nis;
+        }
+}
+
+// the context of forwards 1 .. iters - 1 of a step when the sessions have an iterative model (hnet_sessions_set_iterative_model), else null
+static hnet_ctx* filters_iter_ctx(const hnet_filters* f) { return f->iters > 1 ? f->s->iter : nullptr; }
+// forward `it` of a step: 0 on the main context ctx[0], later ones on ctx[1] if there is one; both read the pairs gathered into ctx[0]'s staging
+static int filters_forward(hnet_ctx* const ctx[2], int it, const FwdArgs& a, hipStream_t st) {
+    hnet_ctx* m = it > 0 && ctx[1] ? ctx[1] : ctx[0];
+    const int r = forward(m, a, st);
+    return r == HNET_OK || m == ctx[0] ? r : fail(ctx[0], r, "iterative model: " + m->err);
+}
+// the end of a step's attempt: the flag word of every context that ran downloaded and cleared (run_host_call), the one synchronisation
+static int filters_flags(hnet_ctx* const ctx[2], uint32_t* flag, hipStream_t st) {
+    hnet_ctx* c = ctx[0];
+    for (int k = 0; k < 2; k++)
+        if (ctx[k]) {
+            HIPCHK(c, hipMemcpyAsync(&flag[k], ctx[k]->d_flag, 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(c, hipMemsetAsync(ctx[k]->d_flag, 0, 4, st));
+        }
+    HIPCHK(c, hipStreamSynchronize(st));
+    return HNET_OK;
+}
+// the IEKF iterations of one attempt for the first n workgroups of d.work (n = 0: none), whose pairs lie gathered in ctx[0]'s staging: per iteration the
+// prior, the forward, the innovation record (if enabled) and the update; then ev1 and, behind it, the photometric records (hnet_filters_last_timing keeps
+// its meaning; inside the attempt: a repeat recomputes the records).  d_seq is [iters][seq_stride]; filter_innovation_kernel closes the d_gate entry of a
+// session it rejects, so every attempt uploads the gates again.
+static int filters_enqueue_iekf(hnet_filters* f, hnet_ctx* const ctx[2], const OutView& d, int n, const int32_t* d_ids, int32_t* d_gate, const uint64_t* d_seq,
+                                int seq_stride, hipStream_t st) {
+    hnet_ctx* c = ctx[0];
+    const int I = f->iters, B = c->cfg.max_batch, N = f->s->n;
+    for (int it = 0; it < I && n; it++) {
+        float* pr_it = d.prior + (size_t)it * B * 8;
+        float* net_it = d.net + (size_t)it * B * 72;
+        HIPCHK(c, launch_filter_prior(d.work, n, pr_it, f->d_prior_cam, st));
+        const FwdArgs a{.prev = c->stage_prev, .curr = c->stage_curr, .prior = c->cfg.use_prior ? pr_it : nullptr, .batch = n, .mean = net_it, .cov = net_it + 8,
+                        .seq_tab = d_seq + (size_t)it * seq_stride, .mean_stride = HNET_PACKED_FLOATS, .cov_stride = HNET_PACKED_FLOATS};
+        if (const int r = filters_forward(ctx, it, a, st); r != HNET_OK) return r;
+        if (f->innov) HIPCHK(c, launch_filter_innovation(d_ids, n, N, f->d_params, d.work, net_it, f->d_prior_cam, f->d_max_nis, d_gate, d.upd, it, d.innov, st));
+        HIPCHK(c, launch_filter_update(d_ids, n, N, f->d_params, net_it, f->d_prior_cam, d_gate, it != I - 1, it == I - 1, d.work, d.upd, st));
+    }
+    HIPCHK(c, hipEventRecord(f->ev1, st));
+    if (f->photo && n) HIPCHK(c, filters_launch_photo(f, d, n, st));
+    return HNET_OK;
+}
+// an overflow of the fp16 planes among the downloaded outputs of n stepping sessions: the first forward with a non-finite output had finite inputs (its
+// fp32 priors; later priors follow from it).  -> the index in ctx of the context to repair, -1: none
+static int filters_overflowed(const hnet_filters* f, hnet_ctx* const ctx[2], const OutView& h, int n) {
+    const hnet_ctx* c = ctx[0];
+    const size_t B = (size_t)c->cfg.max_batch;
+    for (int it = 0; it < f->iters && n; it++)
+        if (!all_finite(h.net + it * B * 72, (size_t)n * 72))
+            return !c->cfg.use_prior || all_finite(h.prior + it * B * 8, (size_t)n * 8) ? (it > 0 && ctx[1] ? 1 : 0) : -1;
+    return -1;
+}
+// the bookkeeping of an accepted call in which the sessions ids[0 .. n) stepped: what the last_* calls describe, the innovation statistics, the timing
+static int filters_accepted(hnet_filters* f, int n, const int32_t* ids, std::chrono::steady_clock::time_point t0, int n_inferences) {
+    f->last_n = n;
+    f->last_innov_n = f->innov ? n : 0;
+    f->last_photo_n = f->photo ? n : 0;
+    if (f->innov) filters_count_innovations(f, n, ids);
+    float ms = 0;
+    HIPCHK(f->s->ctx, hipEventElapsedTime(&ms, f->ev0, f->ev1));
+    record_timing(f->timing, ms, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), n_inferences, true);
+    return HNET_OK;
+}
+
+void hnet_filter_default_params(hnet_filter_params* p) {
+    if (!p) return;
+    memset(p, 0, sizeof *p);
+    static const double T[12] = {-0.027256691772188965, -0.9996260641688061, 0.0021919370477445077, 0.02422852666805565,
+                                 -0.7139206120417471, 0.017931469899155242, -0.6999970157716363, 0.008974432843748055,
+                                 0.6996959571525168, -0.020644471939022302, -0.714142404092339, -0.000638971731537894};
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) p->c_R_i[i * 3 + j] = T[i * 4 + j];
+    for (int i = 0; i < 3; i++) p->i_t_i2c[i] = -(p->c_R_i[i] * T[3] + p->c_R_i[3 + i] * T[7] + p->c_R_i[6 + i] * T[11]);
+    p->sigma_w = 0.00559017;
+    p->sigma_wb = 8.94427e-04;
+    p->sigma_a = 0.01118034;
+    p->sigma_ab = 0.04472136;
+    p->gravity_mag = 9.81;
+    p->k_net_cov = 10.0;
+    p->cam_imu_dt = 0.0;
+    p->imu_avg = 1;
+}
+
+static FilterParams filter_params_dev(const hnet_filter_params& p) {
+    FilterParams d;
+    memset(&d, 0, sizeof d);
+    memcpy(d.ext.c_R_i, p.c_R_i, sizeof d.ext.c_R_i);
+    memcpy(d.ext.i_t_i2c, p.i_t_i2c, sizeof d.ext.i_t_i2c);
+    hnet_ekf::noise_q_diag(p.sigma_w, p.sigma_a, p.sigma_wb, p.sigma_ab, d.q);
+    d.gravity_mag = p.gravity_mag;
+    d.k_net_cov = p.k_net_cov;
+    d.imu_avg = p.imu_avg ? 1 : 0;
+    return d;
+}
+
+void hnet_destroy_filters(hnet_filters* f) {
+    if (!f) return;
+    hnet_ctx* c = f->s->ctx;
+    (void)hipSetDevice(c->cfg.device_id);
+    (void)hipStreamSynchronize(c->stream);
+    drop_dev(f->d_state); drop_dev(f->d_params); drop_dev(f->d_out); drop_dev(f->d_prior_cam); drop_dev(f->d_in); drop_dev(f->d_feed); drop_dev(f->d_max_nis); drop_dev(f->d_photo_part);
+    drop_pin(f->pin_feed); drop_pin(f->pin_out); drop_pin(f->pin_in);
+    drop_event(f->ev0); drop_event(f->ev1);
+    filters_drop_feed(f);
+    filters_drop_predict(f);
+    delete f;
+}
+
+int hnet_create_filters(hnet_sessions* s, int max_iekf_iteration, hnet_filters** out) {
+    if (!s || !out) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = s->ctx;
+    if (max_iekf_iteration < 1 || max_iekf_iteration > 64) return fail(c, HNET_ERR_INVALID_ARG, "hnet_create_filters: max_iekf_iteration outside 1 .. 64");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    hnet_filters* f = new hnet_filters();
+    f->s = s;
+    f->iters = max_iekf_iteration;
+    const int N = s->n, B = c->cfg.max_batch;
+    hnet_filter_params dp;
+    hnet_filter_default_params(&dp);
+    f->t.assign(N, 0.0);
+    f->cam_imu_dt.assign(N, dp.cam_imu_dt);
+    f->imu_avg.assign(N, dp.imu_avg);
+    filters_out_layout(f, B, false, false);
+    f->t_seen.assign(N, -INFINITY);
+    f->inited.assign(N, 0);
+    f->last_slot.assign(N, -1);
+    hnet_init_params ip0;
+    hnet_filter_default_init_params(&ip0);
+    f->ip.assign(N, ip0);
+    std::vector<FilterRec> st(N);
+    memset(st.data(), 0, st.size() * sizeof(FilterRec));
+    for (auto& r : st) r.s.q[0] = 1.0;
+    std::vector<FilterParams> pr(N, filter_params_dev(dp));
+    hipError_t e = hipMalloc((void**)&f->d_state, (size_t)N * sizeof(FilterRec));
+    if (e == hipSuccess) e = hipMalloc((void**)&f->d_params, (size_t)N * sizeof(FilterParams));
+    if (e == hipSuccess) e = hipMalloc((void**)&f->d_out, f->out_bytes);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&f->pin_out, f->out_bytes, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipMalloc((void**)&f->d_prior_cam, (size_t)B * 8 * sizeof(double));
+    if (e == hipSuccess) e = hipEventCreate(&f->ev0);
+    if (e == hipSuccess) e = hipEventCreate(&f->ev1);
+    if (e == hipSuccess) e = hipMemcpyAsync(f->d_state, st.data(), (size_t)N * sizeof(FilterRec), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(f->d_params, pr.data(), (size_t)N * sizeof(FilterParams), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        hnet_destroy_filters(f);
+        return fail(c, HNET_ERR_DEVICE, std::string("hnet_create_filters: ") + hipGetErrorString(e));
+    }
+    *out = f;
+    return HNET_OK;
+}
+
+int hnet_filters_set_params(hnet_filters* f, int id, const hnet_filter_params* p) {
+    if (!f) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = f->s->ctx;
+    if (!p || id < 0 || id >= f->s->n) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_set_params: id or params");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    const FilterParams d = filter_params_dev(*p);
+    HIPCHK(c, hipMemcpyAsync(f->d_params + id, &d, sizeof d, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    f->cam_imu_dt[id] = p->cam_imu_dt;
+    f->imu_avg[id] = p->imu_avg ? 1 : 0;
+    return HNET_OK;
+}
+
+static_assert(sizeof(hnet_filter_state) == sizeof(FilterRec), "hnet_filter_state is the FilterRec layout");
+
+int hnet_filters_set_state(hnet_filters* f, int id, const hnet_filter_state* st) {
+    if (!f) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = f->s->ctx;
+    if (!st || id < 0 || id >= f->s->n) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_set_state: id or state");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    HIPCHK(c, hipMemcpyAsync(f->d_state + id, st, sizeof(FilterRec), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    f->t[id] = st->t;
+    f->inited[id] = 1;
+    return HNET_OK;
+}
+
+int hnet_filters_get_state(hnet_filters* f, int n, const int32_t* ids, hnet_filter_state* out) {
+    if (!f) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = f->s->ctx;
+    if (!ids || !out || n < 1) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_get_state: ids / out");
+    for (int i = 0; i < n; i++)
+        if (ids[i] < 0 || ids[i] >= f->s->n) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_get_state: id out of range");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    for (int i = 0; i < n; i++) HIPCHK(c, hipMemcpyAsync(out + i, f->d_state + ids[i], sizeof(FilterRec), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return HNET_OK;
+}
+
+int hnet_filters_step(hnet_filters* f, int n, const int32_t* ids, const double* t_frame, const hnet_imu* imu, const int64_t* imu_off,
+                      hnet_filter_state* state_out, float* net_out, int32_t* updates) {
+    if (!f) return HNET_ERR_INVALID_ARG;
+    hnet_sessions* s = f->s;
+    hnet_ctx* c = s->ctx;
+    if (!t_frame || !imu_off) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_step: t_frame / imu_off");
+    int rc = sessions_check_ids(s, n, ids);
+    if (rc == HNET_OK) rc = sessions_check_pairs(s, n, ids);
+    if (rc != HNET_OK) return rc;
+    for (int i = 0; i < n; i++) {
+        if (!(t_frame[i] > f->t[ids[i]]) || !std::isfinite(t_frame[i]))
+            return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_step: t_frame must be later than the state's time (Propagator.cpp:32-43)");
+        if (imu_off[i] < 0 || imu_off[i + 1] < imu_off[i] || (imu_off[i + 1] > imu_off[i] && !imu))
+            return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_step: imu / imu_off");
+    }
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    auto t0 = std::chrono::steady_clock::now();
+    const int I = f->iters;
+    // selection on the host (hnet_ekf::select_imu_readings: the window [state t, t_frame] + the session's offset) into the input block
+    static_assert(sizeof(hnet_imu) == sizeof(hnet_ekf::ImuData), "hnet_imu is hnet_ekf::ImuData");
+    int64_t total = 0;
+    for (int i = 0; i < n; i++) total += imu_off[i + 1] - imu_off[i] + 2;
+    const size_t o_t = al256((size_t)total * sizeof(hnet_ekf::ImuData)), o_seq = o_t + al256((size_t)n * 8), o_ids = o_seq + al256((size_t)I * n * 8);
+    const size_t o_gate = o_ids + al256((size_t)n * 4), o_pairs = o_gate + al256((size_t)n * 4), o_off = o_pairs + al256((size_t)n * 8);
+    const size_t in_bytes = o_off + al256((size_t)(n + 1) * 4);
+    if ((rc = grow_block(c, &f->pin_in, &f->d_in, &f->in_cap, in_bytes)) != HNET_OK) return rc;
+    hnet_ekf::ImuData* rd = reinterpret_cast<hnet_ekf::ImuData*>(f->pin_in);
+    double* tf = reinterpret_cast<double*>(f->pin_in + o_t);
+    uint64_t* seq = reinterpret_cast<uint64_t*>(f->pin_in + o_seq);
+    int32_t* hid = reinterpret_cast<int32_t*>(f->pin_in + o_ids);
+    int32_t* gate = reinterpret_cast<int32_t*>(f->pin_in + o_gate);
+    int32_t* pairs = reinterpret_cast<int32_t*>(f->pin_in + o_pairs);
+    int32_t* roff = reinterpret_cast<int32_t*>(f->pin_in + o_off);
+    int R = 0;
+    for (int i = 0; i < n; i++) {
+        const int id = ids[i];
+        const hnet_sessions::Sess& e = s->st[id];
+        const int64_t m = imu_off[i + 1] - imu_off[i];
+        const double dt = f->cam_imu_dt[id];
+        roff[i] = R;
+        R += hnet_ekf::select_imu_readings(reinterpret_cast<const hnet_ekf::ImuData*>(imu) + imu_off[i], (int)m, f->t[id] + dt, t_frame[i] + dt, rd + R);
+        tf[i] = t_frame[i];
+        for (int it = 0; it < I; it++) seq[(size_t)it * n + i] = e.seq + (uint64_t)it;
+        hid[i] = id;
+        gate[i] = (e.t == t_frame[i] && e.count > 10) ? 1 : 0;                      // VioManager.cpp:257
+        sessions_pair(s, id, pairs + 2 * i);
+    }
+    roff[n] = R;
+    const hnet_ekf::ImuData* d_rd = reinterpret_cast<const hnet_ekf::ImuData*>(f->d_in);
+    const double* d_tf = reinterpret_cast<const double*>(f->d_in + o_t);
+    const uint64_t* d_seq = reinterpret_cast<const uint64_t*>(f->d_in + o_seq);
+    const int32_t* d_ids = reinterpret_cast<const int32_t*>(f->d_in + o_ids);
+    int32_t* d_gate = reinterpret_cast<int32_t*>(f->d_in + o_gate);
+    const int32_t* d_pairs = reinterpret_cast<const int32_t*>(f->d_in + o_pairs);
+    const int32_t* d_roff = reinterpret_cast<const int32_t*>(f->d_in + o_off);
+    const OutViews o = filters_out_views(f);
+    // the output block is laid out for max_batch: download the used parts of each section in one copy up to the last one needed
+    const size_t down = state_out ? f->off_work + (size_t)n * sizeof(FilterRec) : filters_down_head(f, n);
+    hipStream_t st = c->stream;
+    const size_t up = o_off + (size_t)(n + 1) * 4;
+    hnet_ctx* const ctx[2] = {c, filters_iter_ctx(f)};
+    auto enqueue = [&](uint32_t* flag_now) -> int {
+        HIPCHK(c, hipMemcpyAsync(f->d_in, f->pin_in, up, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemsetAsync(o.d.upd, 0, (size_t)n * sizeof(int32_t), st));
+        HIPCHK(c, hipEventRecord(f->ev0, st));
+        HIPCHK(c, launch_session_gather(s->ring, 2 * s->n, d_pairs, n, (uint8_t*)c->stage_prev, (uint8_t*)c->stage_curr, st));
+        HIPCHK(c, launch_filter_propagate(d_ids, n, s->n, f->d_state, f->d_params, d_rd, d_roff, d_tf, o.d.work, st));
+        if (const int r = filters_enqueue_iekf(f, ctx, o.d, n, d_ids, d_gate, d_seq, n, st); r != HNET_OK) return r;
+        HIPCHK(c, hipMemcpyAsync(f->pin_out, f->d_out, down, hipMemcpyDeviceToHost, st));
+        return filters_flags(ctx, flag_now, st);
+    };
+    if ((rc = run_host_call(ctx, enqueue, [&] { return filters_overflowed(f, ctx, o.h, n); })) != HNET_OK) return rc;
+    // accepted: the listed states take the step's result (stream order: later calls see it), the bookkeeping advances
+    HIPCHK(c, launch_filter_scatter(o.d.work, d_ids, n, s->n, f->d_state, st));
+    for (int i = 0; i < n; i++) {
+        f->t[ids[i]] = t_frame[i];
+        s->st[ids[i]].seq += (uint64_t)I;
+    }
+    if (net_out)
+        for (int it = 0; it < I; it++) memcpy(net_out + (size_t)it * n * 72, o.h.net + (size_t)it * c->cfg.max_batch * 72, (size_t)n * 72 * sizeof(float));
+    if (updates) memcpy(updates, o.h.upd, (size_t)n * sizeof(int32_t));
+    if (state_out) memcpy(state_out, o.h.work, (size_t)n * sizeof(FilterRec));
+    return filters_accepted(f, n, ids, t0, I);
+}
+
+int hnet_filters_last_priors(const hnet_filters* f, int n, float* out) {
+    if (!f || !out) return HNET_ERR_INVALID_ARG;
+    if (f->last_n < 1) return fail(f->s->ctx, HNET_ERR_NOT_READY, "hnet_filters_last_priors: no step yet");
+    if (n != f->last_n) return fail(f->s->ctx, HNET_ERR_INVALID_ARG, "hnet_filters_last_priors: n differs from the last step's");
+    const int B = f->s->ctx->cfg.max_batch;
+    const float* h_prior = filters_out_view(f, f->pin_out).prior;
+    for (int it = 0; it < f->iters; it++) memcpy(out + (size_t)it * f->last_n * 8, h_prior + (size_t)it * B * 8, (size_t)f->last_n * 8 * sizeof(float));
+    return HNET_OK;
+}
+
+int hnet_filters_last_timing(const hnet_filters* f, hnet_timing* out) {
+    if (!f || !out) return HNET_ERR_INVALID_ARG;
+    *out = f->timing;
+    return HNET_OK;
+}
+
+// ---- filters, fed (include/hnet.h): the IMU rings, the initialiser and hnet_filters_advance ----
+
+void hnet_filter_default_init_params(hnet_init_params* p) {
+    if (!p) return;
+    memset(p, 0, sizeof *p);
+    p->window_time = 1.0;
+    p->imu_thresh = 0.5;
+    p->init_height = 0.1;
+    p->wait_for_jerk = 1;
+}
+
+static InitParams init_params_dev(const hnet_init_params& p) { return InitParams{p.window_time, p.imu_thresh, p.init_height, p.wait_for_jerk ? 1 : 0, 0}; }
+// the advance input block for n sessions: jobs | seq [iters][n] | gate | ids | pairs
+struct AdvLayout {
+    size_t o_seq, o_gate, o_ids, o_pairs, bytes;
+    AdvLayout(int n, int iters) {
+        o_seq = al256((size_t)n * sizeof(AdvanceJob));
+        o_gate = o_seq + al256((size_t)iters * n * 8);
+        o_ids = o_gate + al256((size_t)n * 4);
+        o_pairs = o_ids + al256((size_t)n * 4);
+        bytes = o_pairs + al256((size_t)n * 8);
+    }
+};
+
+int hnet_filters_enable_feed(hnet_filters* f, int imu_capacity) {
+    if (!f) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = f->s->ctx;
+    if (f->cap) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_enable_feed: already enabled");
+    if (imu_capacity < 2 || imu_capacity > (1 << 20)) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_enable_feed: imu_capacity outside 2 .. 1048576");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    const int N = f->s->n, B = c->cfg.max_batch;
+    const size_t adv = AdvLayout(B, f->iters).bytes;
+    std::vector<InitParams> ipd(N);
+    for (int i = 0; i < N; i++) ipd[i] = init_params_dev(f->ip[i]);
+    hipError_t e = hipMalloc((void**)&f->d_ring, (size_t)N * imu_capacity * sizeof(hnet_ekf::ImuData));
+    if (e == hipSuccess) e = hipMalloc((void**)&f->d_meta, (size_t)N * sizeof(ImuRingMeta));
+    if (e == hipSuccess) e = hipMalloc((void**)&f->d_ip, (size_t)N * sizeof(InitParams));
+    if (e == hipSuccess) e = hipMalloc((void**)&f->d_sel, (size_t)B * 2 * (imu_capacity + 2) * sizeof(hnet_ekf::ImuData));
+    if (e == hipSuccess) e = hipMalloc((void**)&f->d_adv, adv);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&f->pin_adv, adv, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&f->ev_feed, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipMemsetAsync(f->d_meta, 0, (size_t)N * sizeof(ImuRingMeta), c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(f->d_ip, ipd.data(), (size_t)N * sizeof(InitParams), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        filters_drop_feed(f);
+        return fail(c, HNET_ERR_DEVICE, std::string("hnet_filters_enable_feed: ") + hipGetErrorString(e));
+    }
+    f->meta.assign(N, ImuRingMeta{0, 0});
+    f->imu_newest.assign(N, -INFINITY);
+    f->cap = imu_capacity;
+    return HNET_OK;
+}
+
+int hnet_filters_set_init_params(hnet_filters* f, int id, const hnet_init_params* p) {
+    if (!f) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = f->s->ctx;
+    if (!p || id < 0 || id >= f->s->n || !(p->window_time > 0.0) || !std::isfinite(p->window_time) || !std::isfinite(p->imu_thresh) || !std::isfinite(p->init_height))
+        return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_set_init_params: id or params");
+    if (f->cap) {
+        HIPCHK(c, hipSetDevice(c->cfg.device_id));
+        const InitParams d = init_params_dev(*p);
+        HIPCHK(c, hipMemcpyAsync(f->d_ip + id, &d, sizeof d, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    f->ip[id] = *p;
+    return HNET_OK;
+}
+
+int hnet_filters_feed_imu(hnet_filters* f, int n, const int32_t* ids, const hnet_imu* imu, const int64_t* imu_off) {
+    if (!f) return HNET_ERR_INVALID_ARG;
+    hnet_sessions* s = f->s;
+    hnet_ctx* c = s->ctx;
+    if (!f->cap) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_feed_imu: feed not enabled (hnet_filters_enable_feed)");
+    if (!ids || !imu_off || n < 1 || n > s->n) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_feed_imu: ids / imu_off / n");
+    if (imu_off[0] < 0) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_feed_imu: imu_off");
+    // validation first: nothing is appended unless every listed session's readings are in order
+    int rc = HNET_OK, marked = 0;
+    for (int i = 0; i < n && rc == HNET_OK; i++) {
+        const int id = ids[i];
+        if (id < 0 || id >= s->n) { rc = fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_feed_imu: id out of range"); break; }
+        if (s->mark[id]) { rc = fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_feed_imu: id repeated in one call"); break; }
+        s->mark[id] = 1;
+        marked = i + 1;
+        if (imu_off[i + 1] < imu_off[i] || imu_off[i + 1] > INT32_MAX || (imu_off[i + 1] > imu_off[i] && !imu)) { rc = fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_feed_imu: imu / imu_off"); break; }
+        double last = f->imu_newest[id];
+        for (int64_t k = imu_off[i]; k < imu_off[i + 1]; k++) {
+            if (!std::isfinite(imu[k].t) || imu[k].t < last) { rc = fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_feed_imu: readings must be finite and in non-decreasing time"); break; }
+            last = imu[k].t;
+        }
+    }
+    for (int j = 0; j < marked; j++) s->mark[ids[j]] = 0;
+    if (rc != HNET_OK) return rc;
+    const int64_t base = imu_off[0], total = imu_off[n] - base;
+    if (total == 0) return HNET_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    const size_t o_rd = al256((size_t)n * sizeof(ImuFeedSeg)), bytes = o_rd + (size_t)total * sizeof(hnet_ekf::ImuData);
+    HIPCHK(c, hipEventSynchronize(f->ev_feed));                    // the pinned block's last upload has left it
+    if (rc = grow_block(c, &f->pin_feed, &f->d_feed, &f->feed_cap, std::max(bytes, (size_t)1 << 16)); rc != HNET_OK) return rc;
+    static_assert(sizeof(hnet_imu) == sizeof(hnet_ekf::ImuData), "hnet_imu is hnet_ekf::ImuData");
+    ImuFeedSeg* seg = reinterpret_cast<ImuFeedSeg*>(f->pin_feed);
+    memcpy(f->pin_feed + o_rd, imu + base, (size_t)total * sizeof(hnet_imu));
+    std::vector<ImuRingMeta> next(n);
+    int longest = 0;
+    for (int i = 0; i < n; i++) {
+        const ImuRingMeta m = f->meta[ids[i]];
+        const int64_t have = imu_off[i + 1] - imu_off[i];
+        const int take = (int)std::min<int64_t>(have, f->cap);      // more than a ring's worth: only the newest `cap` can stay
+        const int count = std::min(f->cap, m.count + take);
+        const int head = (int)(((int64_t)m.head + m.count + take - count) % f->cap);
+        next[i] = ImuRingMeta{head, count};
+        seg[i] = ImuFeedSeg{ids[i], (int32_t)(imu_off[i] - base + (have - take)), take, (int32_t)(((int64_t)m.head + m.count) % f->cap), head, count};
+        longest = std::max(longest, take);
+    }
+    HIPCHK(c, hipMemcpyAsync(f->d_feed, f->pin_feed, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipEventRecord(f->ev_feed, c->stream));
+    HIPCHK(c, launch_imu_append(reinterpret_cast<const ImuFeedSeg*>(f->d_feed), n, longest, reinterpret_cast<const hnet_ekf::ImuData*>(f->d_feed + o_rd), (int)total,
+                                s->n, f->cap, f->d_ring, f->d_meta, c->stream));
+    for (int i = 0; i < n; i++) {
+        f->meta[ids[i]] = next[i];
+        if (imu_off[i + 1] > imu_off[i]) f->imu_newest[ids[i]] = imu[imu_off[i + 1] - 1].t;
+    }
+    return HNET_OK;
+}
+
+int hnet_filters_initialized(const hnet_filters* f, int id) { return (f && id >= 0 && id < f->s->n) ? (int)f->inited[id] : -1; }
+
+int hnet_filters_uninitialize(hnet_filters* f, int id) {
+    if (!f) return HNET_ERR_INVALID_ARG;
+    if (id < 0 || id >= f->s->n) return fail(f->s->ctx, HNET_ERR_INVALID_ARG, "hnet_filters_uninitialize: id out of range");
+    f->inited[id] = 0;
+    f->t_seen[id] = -INFINITY;
+    return hnet_sessions_reset(f->s, id);
+}
+
+int hnet_filters_advance(hnet_filters* f, int n, const int32_t* ids, hnet_filter_state* state_out, float* net_out, int32_t* updates, int32_t* status) {
+    if (!f) return HNET_ERR_INVALID_ARG;
+    hnet_sessions* s = f->s;
+    hnet_ctx* c = s->ctx;
+    if (!f->cap) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_advance: feed not enabled (hnet_filters_enable_feed)");
+    if (!status) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_advance: status");
+    int rc = sessions_check_ids(s, n, ids);
+    if (rc != HNET_OK) return rc;
+    auto t_begin = std::chrono::steady_clock::now();
+    const int I = f->iters, B = c->cfg.max_batch;
+    // what each listed session does (VioManager.cpp:122-162); the sessions that step come first on the device, the propagate-only ones behind them
+    std::vector<int> order;                                        // listed index of workgroup j
+    order.reserve(n);
+    for (int pass = 0; pass < 2; pass++)
+        for (int i = 0; i < n; i++) {
+            const int id = ids[i];
+            const hnet_sessions::Sess& e = s->st[id];
+            int st;
+            if (e.count < 1 || !(e.t_push > (f->inited[id] ? f->t[id] : f->t_seen[id]))) st = HNET_ADV_NO_FRAME;
+            else if (!(e.t_push < f->imu_newest[id] - f->cam_imu_dt[id])) st = HNET_ADV_WAIT_IMU;
+            else if (!f->inited[id]) st = HNET_ADV_WAIT_INIT;      // (INITIALIZED if the device's initialiser accepts)
+            else st = e.count < 2 ? HNET_ADV_PROPAGATED : HNET_ADV_STEPPED;
+            if (pass == 0) status[i] = st;
+            if ((pass == 0 && st == HNET_ADV_STEPPED) || (pass == 1 && (st == HNET_ADV_PROPAGATED || st == HNET_ADV_WAIT_INIT))) order.push_back(i);
+        }
+    const int n_a = (int)order.size();
+    int n_s = 0;
+    for (int i = 0; i < n; i++) n_s += status[i] == HNET_ADV_STEPPED;
+    if (net_out) memset(net_out, 0, (size_t)I * n * 72 * sizeof(float));
+    if (updates) memset(updates, 0, (size_t)n * sizeof(int32_t));
+    std::fill(f->last_slot.begin(), f->last_slot.end(), -1);
+    f->last_photo_n = 0;                                           // (a call in which nothing steps has no photometric records, whatever the call before it left)
+    if (n_a == 0) return HNET_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    const AdvLayout L(n_a, I);
+    AdvanceJob* job = reinterpret_cast<AdvanceJob*>(f->pin_adv);
+    uint64_t* seq = reinterpret_cast<uint64_t*>(f->pin_adv + L.o_seq);
+    int32_t* gate = reinterpret_cast<int32_t*>(f->pin_adv + L.o_gate);
+    int32_t* hid = reinterpret_cast<int32_t*>(f->pin_adv + L.o_ids);
+    int32_t* pairs = reinterpret_cast<int32_t*>(f->pin_adv + L.o_pairs);
+    bool any_init = false;
+    for (int j = 0; j < n_a; j++) {
+        const int i = order[j], id = ids[i];
+        const hnet_sessions::Sess& e = s->st[id];
+        const bool init = status[i] == HNET_ADV_WAIT_INIT;
+        any_init |= init;
+        job[j] = AdvanceJob{e.t_push, f->cam_imu_dt[id], id, init ? 1 : 0, j >= n_s ? 1 : 0, 0};
+        for (int it = 0; it < I; it++) seq[(size_t)it * n_a + j] = e.seq + (uint64_t)it;
+        gate[j] = (j < n_s && e.t == e.t_push && e.count > 10) ? 1 : 0;             // VioManager.cpp:257
+        hid[j] = id;
+        sessions_pair(s, id, pairs + 2 * j);
+    }
+    const AdvanceJob* d_job = reinterpret_cast<const AdvanceJob*>(f->d_adv);
+    const uint64_t* d_seq = reinterpret_cast<const uint64_t*>(f->d_adv + L.o_seq);
+    int32_t* d_gate = reinterpret_cast<int32_t*>(f->d_adv + L.o_gate);
+    const int32_t* d_ids = reinterpret_cast<const int32_t*>(f->d_adv + L.o_ids);
+    const int32_t* d_pairs = reinterpret_cast<const int32_t*>(f->d_adv + L.o_pairs);
+    const OutViews o = filters_out_views(f);
+    FilterRec* d_work = o.d.work;
+    AdvanceResult* d_res = o.d.res;
+    hipStream_t st = c->stream;
+    hnet_ctx* const ctx[2] = {c, n_s ? filters_iter_ctx(f) : nullptr};
+    auto enqueue = [&](uint32_t* flag_now) -> int {
+        HIPCHK(c, hipMemcpyAsync(f->d_adv, f->pin_adv, L.bytes, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemsetAsync(o.d.upd, 0, (size_t)n_a * sizeof(int32_t), st));
+        HIPCHK(c, hipEventRecord(f->ev0, st));
+        if (any_init)                                              // (the sessions without a state are among the propagate-only ones)
+            HIPCHK(c, launch_filter_init(d_job + n_s, n_a - n_s, s->n, f->cap, f->d_ring, f->d_meta, f->d_ip, f->d_params, d_work + n_s, d_res + n_s, st));
+        HIPCHK(c, launch_filter_select(d_job, n_a, s->n, f->cap, f->d_ring, f->d_meta, f->d_state, d_work, f->d_sel, d_res, st));
+        if (n_s) HIPCHK(c, launch_session_gather(s->ring, 2 * s->n, d_pairs, n_s, (uint8_t*)c->stage_prev, (uint8_t*)c->stage_curr, st));
+        HIPCHK(c, launch_filter_propagate_adv(d_job, n_a, s->n, f->cap, f->d_state, f->d_params, f->d_sel, d_res, d_work, st));
+        if (const int r = filters_enqueue_iekf(f, ctx, o.d, n_s, d_ids, d_gate, d_seq, n_a, st); r != HNET_OK) return r;     // (the sequence table has a row of n_a per iteration)
+        if (n_s) HIPCHK(c, hipMemcpyAsync(f->pin_out, f->d_out, filters_down_head(f, n_s), hipMemcpyDeviceToHost, st));
+        if (state_out) HIPCHK(c, hipMemcpyAsync(f->pin_out + f->off_work, d_work, (size_t)n_a * sizeof(FilterRec), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(f->pin_out + f->off_res, d_res, (size_t)n_a * sizeof(AdvanceResult), hipMemcpyDeviceToHost, st));
+        return filters_flags(ctx, flag_now, st);
+    };
+    if ((rc = run_host_call(ctx, enqueue, [&] { return filters_overflowed(f, ctx, o.h, n_s); })) != HNET_OK) return rc;
+    // accepted: the states take the results (not those the initialiser refused), the bookkeeping advances
+    HIPCHK(c, launch_filter_scatter_ok(d_work, d_job, d_res, n_a, s->n, f->d_state, st));
+    const AdvanceResult* h_res = o.h.res;
+    for (int j = 0; j < n_a; j++) {
+        const int i = order[j], id = ids[i];
+        hnet_sessions::Sess& e = s->st[id];
+        f->last_slot[id] = j;
+        if (status[i] == HNET_ADV_WAIT_INIT) {
+            if (!h_res[j].ok) {                                    // the frame is dropped: the session starts over (VioManager.cpp:158-162)
+                f->t_seen[id] = e.t_push;
+                e.count = 0;
+                e.curr = 0;
+                e.t = -1.0;
+                continue;
+            }
+            status[i] = HNET_ADV_INITIALIZED;
+            f->inited[id] = 1;
+            f->t[id] = h_res[j].time0 > e.t_push ? h_res[j].time0 : e.t_push;
+            e.count = 1;                                           // this frame is the session's first image; its ring slot stays the current one
+            e.t = -1.0;
+        } else {
+            f->t[id] = e.t_push;
+            if (j < n_s) {
+                e.seq += (uint64_t)I;
+                if (updates) updates[i] = o.h.upd[j];
+                if (net_out)
+                    for (int it = 0; it < I; it++) memcpy(net_out + ((size_t)it * n + i) * 72, o.h.net + ((size_t)it * B + j) * 72, 72 * sizeof(float));
+            }
+        }
+        if (state_out) memcpy(state_out + i, o.h.work + j, sizeof(FilterRec));
+    }
+    return filters_accepted(f, n_s, hid, t_begin, n_s ? I : 0);     // (the stepping sessions are the first n_s of the call's id table)
+}
+
+int hnet_filters_last_selection(hnet_filters* f, int id, hnet_imu* out, int cap, int* count) {
+    if (!f) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = f->s->ctx;
+    if (!f->cap) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_last_selection: feed not enabled");
+    if (!count || id < 0 || id >= f->s->n || cap < 0 || (cap > 0 && !out)) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_last_selection: id / out / count");
+    *count = 0;
+    const int j = f->last_slot[id];
+    if (j < 0) return HNET_OK;
+    const AdvanceResult* h_res = filters_out_view(f, f->pin_out).res;
+    const int m = h_res[j].ok ? h_res[j].n_sel : 0;
+    if (m < 0 || m > f->cap + 2) return fail(c, HNET_ERR_DEVICE, "hnet_filters_last_selection: selection count out of range");
+    *count = m;
+    const int k = std::min(m, cap);
+    if (k > 0) {
+        HIPCHK(c, hipSetDevice(c->cfg.device_id));
+        HIPCHK(c, hipMemcpyAsync(out, f->d_sel + (size_t)j * 2 * (f->cap + 2) + (f->cap + 2), (size_t)k * sizeof(hnet_imu), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return HNET_OK;
+}
+
+// ---- filters, innovation records (include/hnet.h): the records themselves come from filter_innovation_kernel inside hnet_filters_step / _advance ----
+
+static_assert(sizeof(hnet_innovation) == sizeof(InnovRec), "hnet_innovation is the InnovRec layout");
+static_assert((int)HNET_INNOV_NONE == (int)hnet_ekf::INNOV_NONE && (int)HNET_INNOV_USED == (int)hnet_ekf::INNOV_USED && (int)HNET_INNOV_REJECTED == (int)hnet_ekf::INNOV_REJECTED &&
+              (int)HNET_INNOV_SINGULAR == (int)hnet_ekf::INNOV_SINGULAR && (int)HNET_INNOV_SKIPPED == (int)hnet_ekf::INNOV_SKIPPED, "HNET_INNOV_* are the header's flags");
+
+// The output block with room for another kind of record: a new device block and pinned copy laid out for (innov, photo) and `extra_bytes` of zeroed device
+// memory (*extra: the gates start open; the partials are scratch), the old blocks freed only when everything is there.  On failure the layout is the old
+// one again and nothing of the object has changed.
+static int filters_relayout(hnet_filters* f, bool innov, bool photo, const char* who, void** extra, size_t extra_bytes) {
+    hnet_ctx* c = f->s->ctx;
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    HIPCHK(c, hipStreamSynchronize(c->stream));                    // (nothing enqueued reads the old output block any more)
+    const int B = c->cfg.max_batch;
+    filters_out_layout(f, B, innov, photo);
+    uint8_t *d_out = nullptr, *pin_out = nullptr;
+    void* d_extra = nullptr;
+    hipError_t e = hipMalloc((void**)&d_out, f->out_bytes);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&pin_out, f->out_bytes, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipMalloc(&d_extra, extra_bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(d_extra, 0, extra_bytes, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        drop_dev(d_out); drop_pin(pin_out); drop_dev(d_extra);
+        filters_out_layout(f, B, f->innov, f->photo);
+        return fail(c, HNET_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    }
+    (void)hipFree(f->d_out);
+    (void)hipHostFree(f->pin_out);
+    f->d_out = d_out;
+    f->pin_out = pin_out;
+    *extra = d_extra;
+    f->last_n = 0;                                                 // what last_priors / last_selection / last_innovations / last_photometric described went with the old block
+    f->last_innov_n = 0;
+    f->last_photo_n = 0;
+    std::fill(f->last_slot.begin(), f->last_slot.end(), -1);
+    return HNET_OK;
+}
+
+int hnet_filters_enable_innovations(hnet_filters* f) {
+    if (!f) return HNET_ERR_INVALID_ARG;
+    if (f->innov) return fail(f->s->ctx, HNET_ERR_INVALID_ARG, "hnet_filters_enable_innovations: already enabled");
+    const int N = f->s->n;
+    const int rc = filters_relayout(f, true, f->photo, "hnet_filters_enable_innovations", (void**)&f->d_max_nis, (size_t)N * sizeof(double));
+    if (rc != HNET_OK) return rc;
+    f->innov_stats.assign(N, hnet_innovation_stats{0, 0, 0, 0.0, 0.0});
+    f->innov = true;
+    return HNET_OK;
+}
+
+int hnet_filters_set_nis_gate(hnet_filters* f, int id, double max_nis) {
+    if (!f) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = f->s->ctx;
+    if (!f->innov) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_set_nis_gate: innovations not enabled (hnet_filters_enable_innovations)");
+    if (id < 0 || id >= f->s->n || !(max_nis >= 0.0)) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_set_nis_gate: id out of range, or max_nis negative or NaN");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    HIPCHK(c, hipMemcpyAsync(f->d_max_nis + id, &max_nis, sizeof max_nis, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return HNET_OK;
+}
+
+int hnet_filters_last_innovations(const hnet_filters* f, int n, hnet_innovation* out) {
+    if (!f || !out) return HNET_ERR_INVALID_ARG;
+    if (!f->innov || f->last_innov_n < 1) return fail(f->s->ctx, HNET_ERR_INVALID_ARG, "hnet_filters_last_innovations: the last step ran without innovations");
+    if (n != f->last_innov_n) return fail(f->s->ctx, HNET_ERR_INVALID_ARG, "hnet_filters_last_innovations: n differs from the last step's");
+    memcpy(out, filters_out_view(f, f->pin_out).innov, (size_t)f->iters * n * sizeof(InnovRec));
+    return HNET_OK;
+}
+
+int hnet_filters_innovation_stats(const hnet_filters* f, int id, hnet_innovation_stats* out) {
+    if (!f || !out) return HNET_ERR_INVALID_ARG;
+    if (!f->innov || id < 0 || id >= f->s->n) return fail(f->s->ctx, HNET_ERR_INVALID_ARG, "hnet_filters_innovation_stats: innovations not enabled or id out of range");
+    *out = f->innov_stats[id];
+    return HNET_OK;
+}
+
+int hnet_filters_reset_innovation_stats(hnet_filters* f, int id) {
+    if (!f) return HNET_ERR_INVALID_ARG;
+    if (!f->innov || id < 0 || id >= f->s->n) return fail(f->s->ctx, HNET_ERR_INVALID_ARG, "hnet_filters_reset_innovation_stats: innovations not enabled or id out of range");
+    f->innov_stats[id] = hnet_innovation_stats{0, 0, 0, 0.0, 0.0};
+    return HNET_OK;
+}
+
+// ---- filters, photometric residual records (include/hnet.h): csrc/kernels_photo.hip on the step's pairs, inside hnet_filters_step / _advance ----
+
+int hnet_filters_enable_photometric(hnet_filters* f) {
+    if (!f) return HNET_ERR_INVALID_ARG;
+    if (f->photo) return fail(f->s->ctx, HNET_ERR_INVALID_ARG, "hnet_filters_enable_photometric: already enabled");
+    const size_t part = photo_partial_count(f->s->ctx->cfg.max_batch, 2 + f->iters) * sizeof(PhotoRec);
+    const int rc = filters_relayout(f, f->innov, true, "hnet_filters_enable_photometric", (void**)&f->d_photo_part, part);
+    if (rc != HNET_OK) return rc;
+    f->photo = true;
+    return HNET_OK;
+}
+
+int hnet_filters_last_photometric(const hnet_filters* f, int n, hnet_photo_residual* out) {
+    if (!f || !out) return HNET_ERR_INVALID_ARG;
+    if (!f->photo || f->last_photo_n < 1) return fail(f->s->ctx, HNET_ERR_INVALID_ARG, "hnet_filters_last_photometric: the last step ran without photometric records");
+    if (n != f->last_photo_n) return fail(f->s->ctx, HNET_ERR_INVALID_ARG, "hnet_filters_last_photometric: n differs from the last step's");
+    memcpy(out, filters_out_view(f, f->pin_out).photo, (size_t)n * (2 + f->iters) * sizeof(PhotoRec));
+    return HNET_OK;
+}
+
+// ---- filters, between frames (include/hnet.h): hnet_filters_predict.  Read-only: nothing of the filters' or the sessions' bookkeeping is written.
+
+static_assert(sizeof(hnet_odometry) == sizeof(PredictOut), "hnet_odometry is the PredictOut layout");
+static_assert(HNET_PRED_OK == PRED_OK && HNET_PRED_NO_STATE == PRED_NO_STATE && HNET_PRED_WAIT_IMU == PRED_WAIT_IMU && HNET_PRED_AT_STATE == PRED_AT_STATE,
+              "HNET_PRED_* are the kernel's codes");
+
+// the call's buffers, made once: the kernel's scratch is its own, so that hnet_filters_last_selection keeps describing the last advance
+static int predict_buffers(hnet_filters* f) {
+    if (f->d_pred) return HNET_OK;
+    hnet_ctx* c = f->s->ctx;
+    const int B = c->cfg.max_batch;
+    f->off_pred_out = al256((size_t)B * sizeof(PredictJob));
+    const size_t bytes = f->off_pred_out + (size_t)B * sizeof(PredictOut);
+    hipError_t e = hipMalloc((void**)&f->d_pred_sel, (size_t)B * 2 * (f->cap + 2) * sizeof(hnet_ekf::ImuData));
+    if (e == hipSuccess) e = hipHostMalloc((void**)&f->pin_pred, bytes, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipEventCreate(&f->ev_p0);
+    if (e == hipSuccess) e = hipEventCreate(&f->ev_p1);
+    if (e == hipSuccess) e = hipMalloc((void**)&f->d_pred, bytes);
+    if (e != hipSuccess) {
+        filters_drop_predict(f);
+        return fail(c, HNET_ERR_DEVICE, std::string("hnet_filters_predict: ") + hipGetErrorString(e));
+    }
+    return HNET_OK;
+}
+
+int hnet_filters_predict(hnet_filters* f, int n, const int32_t* ids, const double* t_query, hnet_odometry* out) {
+    if (!f) return HNET_ERR_INVALID_ARG;
+    hnet_sessions* s = f->s;
+    hnet_ctx* c = s->ctx;
+    if (!f->cap) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_predict: feed not enabled (hnet_filters_enable_feed)");
+    if (!t_query || !out) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_predict: t_query / out");
+    int rc = sessions_check_ids(s, n, ids);
+    if (rc != HNET_OK) return rc;
+    for (int i = 0; i < n; i++)
+        if (!std::isfinite(t_query[i])) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_predict: t_query must be finite");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    if ((rc = predict_buffers(f)) != HNET_OK) return rc;
+    PredictJob* job = reinterpret_cast<PredictJob*>(f->pin_pred);
+    for (int i = 0; i < n; i++) {
+        const int id = ids[i];
+        const double dt = f->cam_imu_dt[id];
+        int st = PRED_OK;                                          // (the kernel reports AT_STATE from the device's own state time)
+        if (!f->inited[id]) st = PRED_NO_STATE;
+        else if (t_query[i] > f->t[id] && !(t_query[i] < f->imu_newest[id] - dt)) st = PRED_WAIT_IMU;
+        job[i] = PredictJob{t_query[i], dt, id, st};
+    }
+    hipStream_t st = c->stream;
+    PredictOut* d_out = reinterpret_cast<PredictOut*>(f->d_pred + f->off_pred_out);
+    HIPCHK(c, hipMemcpyAsync(f->d_pred, f->pin_pred, (size_t)n * sizeof(PredictJob), hipMemcpyHostToDevice, st));
+    if (f->pred_timed) HIPCHK(c, hipEventRecord(f->ev_p0, st));
+    HIPCHK(c, launch_filter_predict(reinterpret_cast<const PredictJob*>(f->d_pred), n, s->n, f->cap, f->d_ring, f->d_meta, f->d_state, f->d_params, f->d_pred_sel,
+                                    d_out, st));
+    if (f->pred_timed) HIPCHK(c, hipEventRecord(f->ev_p1, st));
+    HIPCHK(c, hipMemcpyAsync(f->pin_pred + f->off_pred_out, d_out, (size_t)n * sizeof(PredictOut), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    memcpy(out, f->pin_pred + f->off_pred_out, (size_t)n * sizeof(PredictOut));
+    if (f->pred_timed) {
+        float ms = 0;
+        HIPCHK(c, hipEventElapsedTime(&ms, f->ev_p0, f->ev_p1));
+        f->pred_ms = ms;
+    }
+    return HNET_OK;
+}
+
+double hnet_filters_newest_imu_time(const hnet_filters* f, int id) {
+    if (!f || !f->cap || id < 0 || id >= f->s->n || !std::isfinite(f->imu_newest[id])) return NAN;
+    return f->imu_newest[id];
+}
+
+double hnet_filters_last_predict_device_ms(hnet_filters* f) {
+    if (!f) return NAN;
+    f->pred_timed = true;
+    return f->pred_ms;
+}
+
+}  // extern "C"

@@ -1,7 +1,7 @@
 // capi_internal.h — what the host translation units of libhnet_hip.so share: the context, the forward's argument block and the functions
 // that more than one of them calls.  hnet_capi.hip: contexts, images, the inference entry points and their repair policy, groups, operator and
 // debug entry points; capi_weights.hip: the HNETW001 blob and the weight layouts; capi_forward.hip: the launch sequence of one forward;
-// capi_sessions.hip: hnet_sessions_* and hnet_filters_*.  Nothing here is part of the C ABI.
+// capi_sessions.hip: hnet_sessions_*; capi_filters.hip: hnet_filters_* (what it reads of the sessions: sessions_internal.h).  Nothing here is part of the C ABI.
 #pragma once
 #include "../../include/hnet.h"
 #include "../../include/hnet_rng.h"

@@ -1,4 +1,4 @@
-// filters_dev.h — what the device filters (hnet_filters, include/hnet.h) and their host orchestration in capi_sessions.hip share.
+// filters_dev.h — what the device filters (hnet_filters, include/hnet.h) and their host orchestration in capi_filters.hip share.
 // The device compiles the host reference include/hnet_ekf.h itself (host + device functions) so that the Jacobians, the mean
 // propagation and the quaternion update are the very functions tests/test_filters_cpu.py pins against numpy; the parallel parts
 // (covariance products, the 8 x 8 inverse, the gain) are restated in kernels_filters.hip in the host's summation order.

@@ -4,7 +4,7 @@
 // (filters_dev.h); the products run one output element per thread with the k-loop in the host's order.  The Makefile builds this file
 // with -ffp-contract=off (a per-target flag: the pragma form would only cover code after the include of include/hnet_ekf.h), so the header's
 // serial code and the products round every multiply and add as the host's x86-64 build does; device and host then differ only where the
-// device library's sin / cos / sqrt / division do.
+// device library's sin / cos / sqrt / division do.  The host side that enqueues these kernels is capi_filters.hip.
 #include "filters_dev.h"
 
 namespace hnet {

@@ -135,6 +135,77 @@ def test_feed_equals_step(blob, ref, fref, iters):
         o.close()
 
 
+def test_feed_equals_step_with_every_layer_and_a_propagate_only_session(blob, ref):
+    """Everything a step's attempt can contain at once, on both paths: max_batch 4, 4 sessions, 8 samples, 3 IEKF iterations, an iterative model attached,
+    innovation and photometric records on.  Sessions 0 - 2 step for three ticks, through hnet_filters_step on one filters object and through feed_imu +
+    advance on another; the advance also lists session 3, whose camera restarts before every frame, so it has one image and only propagates: the call's
+    tables then are wider (4) than its forwards (3).  Bytes are compared for the stepping sessions, session 3 against the host header's propagation."""
+    _capi, HnetEngine, HnetSessions, HnetFilters = tg._mods()
+    iters, n = 3, 3
+    objs = []
+    for _ in range(2):
+        e = HnetEngine(blob, variant="prior3", mc_samples=8, dropout_p=0.05, mc_seed=9, max_batch=4)
+        ie = HnetEngine(blob, variant="prior1", mc_samples=8, dropout_p=0.1, mc_seed=9, max_batch=4)
+        s = HnetSessions(e, 4)
+        s.set_iterative_model(ie)
+        f = HnetFilters(s, iters)
+        f.enable_innovations()
+        f.enable_photometric()
+        objs.append((e, ie, s, f))
+    (ea, ia, sa, fa), (eb, ib, sb, fb) = objs
+    fa.enable_feed(64)
+    rng = np.random.default_rng(77)
+    fr = tg._frames(rng, 15)
+    every = np.arange(4, dtype=np.int32)
+    ids = every[:n]
+    for k in range(12):                                                                 # 12 images each: the reference's gate is open (count > 10)
+        for s in (sa, sb):
+            s.push(every, np.stack([np.roll(fr[k], 5 * i, axis=0) for i in range(4)]), t=[1.0 + 0.1 * k] * 4)
+    counts = [16, 3, 40, 7]
+    t_frame = np.full(4, 1.0 + 0.1 * 11)
+    ps, hist, fed = [], [], [0] * 4
+    for i in range(4):
+        p = tg._params(HnetFilters, rng, i)
+        st = tg._state(_capi, rng, t_frame[i])
+        for f in (fa, fb):
+            f.set_params(i, p)
+            f.set_state(i, st)
+        ps.append(p)
+        ts = t_frame[i] + p.cam_imu_dt - 0.0007 + 0.002 * np.arange(3 * 42 + 4)
+        r = np.zeros(len(ts), _capi.IMU_DTYPE)
+        r["t"], r["wm"], r["am"] = ts, rng.standard_normal((len(ts), 3)) * 0.3, rng.standard_normal((len(ts), 3)) * 0.5 + [0, 0, 9.81]
+        hist.append(r)
+    for tick in range(3):
+        t_frame = t_frame + 0.002 * np.array(counts) + 0.0004
+        frames = np.stack([np.roll(fr[12 + tick], 5 * i, axis=0) for i in range(4)])
+        sa.reset(3)                                                                     # (the filter keeps its state: PROPAGATED, as in test_cold_start_to_flight)
+        sa.push(every, frames, t=list(t_frame))
+        sb.push(ids, frames[:n], t=list(t_frame[:n]))
+        chunks = []
+        for i in range(4):
+            upto = int(np.searchsorted(hist[i]["t"], t_frame[i] + ps[i].cam_imu_dt, side="right")) + 1
+            chunks.append(hist[i][fed[i]:upto])
+            fed[i] = upto
+        fa.feed_imu(every, chunks)
+        before3, seq3 = fa.get_state([3]), sa.seq(3)
+        sta, neta, upda, status = fa.advance(every)
+        assert list(status) == [_capi.ADV_STEPPED] * n + [_capi.ADV_PROPAGATED]
+        stb, netb, updb = fb.step(ids, list(t_frame[:n]), [hist[i][:fed[i]] for i in range(n)])
+        assert list(upda[:n]) == list(updb) == [iters] * n and upda[3] == 0
+        assert sta[:n].tobytes() == stb.tobytes(), tick
+        assert np.ascontiguousarray(neta[:, :n]).tobytes() == netb.tobytes() and np.isfinite(netb).all() and not neta[:, 3].any(), tick
+        assert fa.last_priors(n).tobytes() == fb.last_priors(n).tobytes(), tick
+        assert fa.last_innovations(n).tobytes() == fb.last_innovations(n).tobytes(), tick
+        assert fa.last_photometric(n).tobytes() == fb.last_photometric(n).tobytes(), tick
+        assert fa.get_state(every).tobytes() == sta.tobytes()
+        assert [sa.seq(i) for i in ids] == [sb.seq(i) for i in ids] and sa.seq(3) == seq3
+        assert sta[3]["t"] == t_frame[3]
+        tg._close(sta[3], _host_propagate(ref, before3, ps[3], t_frame[3], hist[3][:fed[3]])[0])
+    for group in objs:
+        for o in reversed(group):
+            o.close()
+
+
 SELECT_CASES = ["inside", "split_both_ends", "reading_on_t1", "reading_on_t0", "imu_slower_than_camera", "all_after_t1", "duplicated_stamps",
                 "near_duplicate_at_t0"]
 
