@@ -67,6 +67,31 @@ int ref_propagate_with_imu(hnet_filter_state* st, const hnet_filter_params* p, d
     return k;
 }
 
+// ref_propagate_with_imu's loop, interval by interval (the header's select_imu_readings, imu_interval_inputs and propagate in its order), with the
+// quaternion after every interval in q_trace [n + 1][4] (may be null) and the largest |w_hat| dt in *max_angle (may be null): what the input
+// qualifications of tests/filters_edges.py read.  The state it leaves is ref_propagate_with_imu's, bit for bit (tests/test_filters_edges_cpu.py).
+int ref_propagate_trace(hnet_filter_state* st, const hnet_filter_params* p, double t_frame, const hnet_imu* r, int n, double* q_trace, double* max_angle) {
+    if (!(t_frame > st->t)) return -1;
+    State s = load(*st);
+    double q[hnet_ekf::NW];
+    hnet_ekf::noise_q_diag(p->sigma_w, p->sigma_a, p->sigma_wb, p->sigma_ab, q);
+    std::vector<ImuData> sel(n + 2);
+    const int m = hnet_ekf::select_imu_readings(reinterpret_cast<const ImuData*>(r), n, st->t + p->cam_imu_dt, t_frame + p->cam_imu_dt, sel.data());
+    int done = 0;
+    if (max_angle) *max_angle = 0.0;
+    for (int i = 0; i + 1 < m; i++) {
+        double w_hat[3], a_hat[3];
+        const double dt = hnet_ekf::imu_interval_inputs(s, sel[i], sel[i + 1], p->imu_avg != 0, w_hat, a_hat);
+        hnet_ekf::propagate(s, ext(*p), dt, w_hat, a_hat, q, p->gravity_mag);
+        if (q_trace) std::memcpy(q_trace + 4 * done, s.q, sizeof s.q);
+        if (max_angle) *max_angle = std::max(*max_angle, std::sqrt(hnet_ekf::m3::dot(w_hat, w_hat)) * dt);
+        done++;
+    }
+    save(s, *st);
+    st->t = t_frame;
+    return done;
+}
+
 // the fp32 prior a forward reads: (float)(offset x 159.5)
 void ref_prior(const hnet_filter_state* st, float* prior_px) {
     double px[8], cam[8];
