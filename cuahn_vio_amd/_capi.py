@@ -26,7 +26,7 @@ SYMBOLS = [
     "hnet_mc_finish_packed_device", "hnet_mc_finish_gathered_device",
     "hnet_synchronize", "hnet_last_timing", "hnet_time_batch_device", "hnet_stage_count", "hnet_stage_name",
     "hnet_stage_flops_per_pair", "hnet_stage_kernels", "hnet_get_config", "hnet_profile_batch_device", "hnet_op_warp", "hnet_op_dlt", "hnet_op_conv",
-    "hnet_op_prep", "hnet_op_prep_u8", "hnet_debug_layer_output", "hnet_debug_h_part1",
+    "hnet_op_prep", "hnet_op_prep_u8", "hnet_op_prep_batch", "hnet_debug_layer_output", "hnet_debug_h_part1",
     "hnet_set_camera", "hnet_set_undistort_maps", "hnet_get_undistort_maps", "hnet_push_raw_image", "hnet_op_undistort",
     "hnet_op_block4_fused", "hnet_op_block3_fused", "hnet_op_block42_fused", "hnet_precision", "hnet_overflow_flag",
     "hnet_create_group", "hnet_create_group_from_memory", "hnet_destroy_group", "hnet_group_size", "hnet_group_context", "hnet_group_stream",
@@ -105,6 +105,11 @@ PHOTO_RESIDUAL_DTYPE = _np.dtype([("sum", "<f8"), ("sum_inside", "<f8"), ("n_ins
 PHOTO_DEGENERATE = 1
 PHOTO_MAX_CANDIDATES = 66
 
+# the block-4 input planes (csrc/kernels.h B4_*): [plane][pair][B4_HP][B4_WP] dwords, pixel (u, v) at row v + B4_PADY, column u + B4_PADX
+# (tests/cpp/b41_tap_check.cpp pins these numbers to the header)
+B4_HP, B4_WP, B4_PADX, B4_PADY = 235, 336, 5, 5
+B4_SENTINEL = 0xA5A5A5A5      # what hnet_op_prep_batch fills its plane buffer with before the launch
+
 
 class HnetError(RuntimeError):
     def __init__(self, status, msg):
@@ -175,6 +180,7 @@ def lib():
     L.hnet_op_block42_fused.argtypes = [vp, fp, C.c_int, fp]
     L.hnet_op_prep.argtypes = [vp, fp, fp, fp, C.c_int, fp]
     L.hnet_op_prep_u8.argtypes = [vp, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), fp, C.c_int, fp]
+    L.hnet_op_prep_batch.argtypes = [vp, vp, vp, C.c_int, fp, C.c_int, C.c_int, C.c_int, fp, vp]
     L.hnet_debug_layer_output.argtypes = [vp, C.c_int, C.c_int, fp, C.c_size_t]
     L.hnet_debug_h_part1.argtypes = [vp, C.c_int, fp]
     L.hnet_create_group.argtypes = [C.POINTER(Config), C.c_char_p, C.c_int, C.POINTER(vp)]

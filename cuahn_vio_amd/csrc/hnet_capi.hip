@@ -1160,6 +1160,43 @@ int hnet_op_prep_u8(hnet_ctx* c, const uint8_t* img1, const uint8_t* img2, const
     return op_prep_impl(c, img1, img2, HNET_PIX_U8, H, k, out);
 }
 
+// A batch of pairs through ONE launch_prep, as the forward issues it (batch = n, the context's sampler, optionally the block-4 planes): the frames are
+// uploaded align_off bytes past a 16-byte boundary, so that the tiled kernels (16-byte aligned frames) and the direct-gather routes can both be reached.
+int hnet_op_prep_batch(hnet_ctx* c, const void* img1, const void* img2, int pix_fmt, const float* H, int n, int k, int align_off, float* out, uint32_t* planes) {
+    if (!c) return HNET_ERR_INVALID_ARG;
+    if (!img1 || !img2 || !out || n < 1 || n > 4096 || (k != 1 && k != 2 && k != 4 && k != 8) || (pix_fmt != HNET_PIX_U8 && pix_fmt != HNET_PIX_F32) ||
+        align_off < 0 || align_off > 15)
+        return fail(c, HNET_ERR_INVALID_ARG, "hnet_op_prep_batch: frames / out, 1 <= n <= 4096, k in {1, 2, 4, 8}, a pixel format, 0 <= align_off <= 15");
+    if (pix_fmt == HNET_PIX_F32 && (align_off & 3)) return fail(c, HNET_ERR_INVALID_ARG, "hnet_op_prep_batch: float frames need an align_off that is a multiple of 4");
+    if (planes && (k != 1 || !H)) return fail(c, HNET_ERR_INVALID_ARG, "hnet_op_prep_batch: the block-4 planes exist for k = 1 with a homography only");
+    if (planes && !c->x16_b4) return fail(c, HNET_ERR_UNSUPPORTED, "hnet_op_prep_batch: this context's forward has no block-4 plane input");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    const int ho = IMG_H / k, wo = IMG_W / k;
+    const size_t px = pix_fmt == HNET_PIX_U8 ? 1 : 4, img_bytes = (size_t)n * NPIX * px, n_out = (size_t)n * 2 * ho * wo;
+    const size_t plane = (size_t)n * B4_HP * B4_WP;                         // dwords per plane
+    DevTemps t;
+    uint8_t *d_1 = nullptr, *d_2 = nullptr;
+    float *d_h = nullptr, *d_o = nullptr, *d_t = nullptr;
+    uint32_t* d_p = nullptr;
+    HIPCHK(c, t.alloc(&d_1, img_bytes + 16)); HIPCHK(c, t.alloc(&d_2, img_bytes + 16)); HIPCHK(c, t.alloc(&d_h, (size_t)n * 9));
+    HIPCHK(c, t.alloc(&d_o, n_out)); HIPCHK(c, t.alloc(&d_t, n_out));
+    if ((((uintptr_t)d_1 | (uintptr_t)d_2) & 15) != 0) return fail(c, HNET_ERR_DEVICE, "hnet_op_prep_batch: a device allocation is not 16-byte aligned");
+    HIPCHK(c, hipMemcpy(d_1 + align_off, img1, img_bytes, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_2 + align_off, img2, img_bytes, hipMemcpyHostToDevice));
+    if (H) HIPCHK(c, hipMemcpy(d_h, H, (size_t)n * 36, hipMemcpyHostToDevice));
+    if (planes) {                                                           // sentinel everywhere: what the launch leaves of it is the border it must not touch
+        HIPCHK(c, t.alloc(&d_p, (size_t)c->n_planes * plane));
+        HIPCHK(c, hipMemsetAsync(d_p, 0xA5, (size_t)c->n_planes * plane * 4, c->stream));
+    }
+    HIPCHK(c, launch_prep(d_1 + align_off, d_2 + align_off, pix_fmt, H ? d_h : nullptr, k, d_o, n, c->stream, d_p, d_p ? plane : 0, d_p ? c->n_planes : 3, c->warp_exact));
+    if (d_p) HIPCHK(c, launch_s3pad_to_f32_nhwc(d_p, plane, d_o, n, c->n_planes, c->stream));
+    HIPCHK(c, launch_nhwc_to_nchw(d_o, d_t, n, 2, ho, wo, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out, d_t, n_out * 4, hipMemcpyDeviceToHost));
+    if (d_p) HIPCHK(c, hipMemcpy(planes, d_p, (size_t)c->n_planes * plane * 4, hipMemcpyDeviceToHost));
+    return HNET_OK;
+}
+
 int hnet_debug_layer_output(hnet_ctx* c, int layer, int pair, float* out, size_t cap) {
     if (!c || !out || layer < 0 || layer >= 20 || pair < 0 || pair >= c->cfg.max_batch) return HNET_ERR_INVALID_ARG;
     HIPCHK(c, hipSetDevice(c->cfg.device_id));

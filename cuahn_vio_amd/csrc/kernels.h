@@ -117,7 +117,7 @@ constexpr int b41_tap(int st, int g) {
 // cat(img1, warp(img2,H)) -> AvgPool(k) -> NHWC [B][224/k][320/k][2]; H == nullptr: no warp
 // out_s3 != nullptr (k = 1 only): write the padded bf16 planes above instead (s3_plane = dwords per plane)
 //   exact = true: sampling positions bit-identical to grid_sample (IEEE divisions, the normalise / un-normalise round trip of warp.py:70);
-//   false (the library default, HNET_WARP_EXACT=0): shared reciprocal + Newton step, no round trip (positions within 6e-5 px; kernels.hip)
+//   false (the library default, HNET_WARP_EXACT=0): shared reciprocal + Newton step, no round trip (positions within 1.3e-4 px, measured; kernels.hip)
 hipError_t launch_prep(const void* img1, const void* img2, int pix_fmt, const float* H, int k, float* out,
                        int batch, hipStream_t s, uint32_t* out_s3 = nullptr, size_t s3_plane = 0, int n_planes = 3, bool exact = true);
 // Small-batch form of launch_prep (latency path, batch <= 8): the block-tail launch (Linear(5120,8) + DLT + composition, launch_block_fc_dlt)

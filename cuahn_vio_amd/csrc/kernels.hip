@@ -167,7 +167,13 @@ __device__ __forceinline__ float warp_sample_box(const float* h, int u, int v, c
 //     zero padding exactly (position -1 or W: the only tap with a non-zero weight is a stored zero), elsewhere it never acts,
 //   * weights come from v_fract_f32, the LDS address from one FMA + one conversion.
 // ~30 vector instructions per pixel instead of ~85.  Used only for tiles with a staged box and Z safely away from 0 (the others take the
-// exact path).  Measured position difference to the exact path: < 6e-5 px; outputs: same golden gates (tests/test_gpu_parity.py).
+// exact path).  Measured position difference to the exact path: up to 1.22e-4 px in x (four ulps of a coordinate in [256, 320)) and 6.1e-5 px in y,
+// on 1-px stripes of 0 / 255 away from the zero padding, where the intensity difference IS the position difference across the stripes
+// (tests/test_gpu_frontend_batch.py; worst under the warp_s11 `persp` homography).  The 6e-5 px stated here before covers the quotient (1.5 ulp) and
+// the skipped round trip only, not the rounding of X, Y, Z themselves (summed here in another order than in warp_coords) nor the exact path's own
+// distance to the true position.  Intensities: at most 1.22e-4 measured on the steepest 8-bit textures (1-px checkerboard and stripes, a saturated
+// frame against the zero padding) under every homography of the tests, gated at 2e-4 (tests/test_gpu_parity.py, tests/test_gpu_frontend_batch.py);
+// outputs: same golden gates.
 struct WarpFast { float bx_lo, bx_hi, by_lo, by_hi, fpitch; int ibase; };
 __device__ __forceinline__ WarpFast warp_fast_setup(const WarpBox& bx) {
     WarpFast f;

@@ -350,6 +350,29 @@ class HnetEngine:
                                                _fp(hm) if hm is not None else None, k, _fp(out)))
         return out
 
+    def op_prep_batch(self, img1, img2, h, k, align_off=0, want_planes=False):
+        """hnet_op_prep_batch: n pairs through one launch with the context's sampler.  img1 / img2 [n, 224, 320], both uint8 or both float32; h [n, 3, 3] or
+        None; the frames sit align_off bytes past a 16-byte boundary on the device -> out [n, 2, 224 / k, 320 / k].  want_planes (k = 1 with h):
+        -> (out, planes) with planes [n_planes, n, B4_HP, B4_WP] uint32, the block-4 input as the launch wrote it into a buffer of _capi.B4_SENTINEL,
+        and out the values the planes join to"""
+        i1, i2 = np.ascontiguousarray(img1), np.ascontiguousarray(img2)
+        if i1.dtype != i2.dtype or i1.dtype not in (np.uint8, np.float32):
+            raise TypeError("images must both be uint8 or float32")
+        fmt = PIX_U8 if i1.dtype == np.uint8 else PIX_F32
+        i1, i2 = i1.reshape(-1, IMG_H, IMG_W), i2.reshape(-1, IMG_H, IMG_W)
+        n = i1.shape[0]
+        if i2.shape[0] != n:
+            raise ValueError("img1 and img2 must hold the same number of frames")
+        hm = None if h is None else np.ascontiguousarray(h, dtype=np.float32).reshape(n, 9)
+        out = np.zeros((n, 2, IMG_H // k, IMG_W // k), np.float32)
+        planes = None
+        if want_planes:
+            n_planes = {_capi.PREC_BF16: 1, _capi.PREC_F16X2: 2}.get(self.precision(), 3)
+            planes = np.zeros((n_planes, n, _capi.B4_HP, _capi.B4_WP), np.uint32)
+        check(self._h, self._L.hnet_op_prep_batch(self._h, i1.ctypes.data, i2.ctypes.data, fmt, _fp(hm) if hm is not None else None, n, k, int(align_off),
+                                                  _fp(out), planes.ctypes.data if want_planes else None))
+        return (out, planes) if want_planes else out
+
     def debug_layer_output(self, layer, pair=0):
         """[Cout, Ho, Wo] output of conv layer `layer` from the last forward"""
         from .weights import CONV_LAYERS

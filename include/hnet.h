@@ -78,7 +78,7 @@ typedef struct hnet_config {
     /* Kernel selection (round 4: the library reads no environment variable; 0 everywhere = the measured defaults = what hnet_default_config sets).
      * These fields replace the HNET_* switches that rounds 1 - 3 read with getenv at hnet_create: a stray variable in a deployment can no longer
      * change kernels or summation order.  The tests and tools/ab_bench.py set them explicitly (the Python mirror maps its own environment onto them). */
-    int32_t  warp_exact;       /* 1: the warp keeps grid_sample's sampling positions bit for bit (warp.py:70); 0: fast sampler, positions within 6e-5 px */
+    int32_t  warp_exact;       /* 1: the warp keeps grid_sample's sampling positions bit for bit (warp.py:70); 0: fast sampler, positions within 1.3e-4 px (measured) */
     int32_t  graph;            /* HNET_GRAPH_*: hipGraph replay of the batch-1 forward of hnet_infer */
     uint32_t variant;          /* HNET_VARIANT_*: reference kernels for in-process A/B measurements and the bitwise cross-kernel tests */
 } hnet_config;
@@ -569,6 +569,15 @@ int hnet_op_block42_fused(hnet_ctx* ctx, const float* in, int batch, float* out)
 int hnet_op_prep(hnet_ctx* ctx, const float* img1, const float* img2, const float* H, int k, float* out);
 /* the same on u8 images as load_current_img receives them (u8 -> f32 / 255.0, HomographyNet.cpp:139-146) */
 int hnet_op_prep_u8(hnet_ctx* ctx, const uint8_t* img1, const uint8_t* img2, const float* H, int k, float* out);
+/* the same for n pairs in ONE launch, as the forward issues it: img1, img2 [n][224][320] of pix_fmt (HNET_PIX_*), H [n][9] or NULL, the context's sampler
+ * (hnet_config.warp_exact) -> out [n][2][224/k][320/k].  The frames are uploaded to device addresses align_off bytes (0 .. 15; a multiple of 4 for float
+ * frames) past a 16-byte boundary: 0 takes the tiled kernels, anything else the routes of frames that are not 16-byte aligned.
+ * planes != NULL (k = 1 with H; HNET_ERR_UNSUPPORTED on a context whose forward has no block-4 plane input): the launch writes the block-4 input as the
+ * forward's 16-bit planes (two fp16 planes in HNET_PREC_F16X2, three bf16 planes in HNET_PREC_BF16X3, one in HNET_PREC_BF16) into a buffer filled with
+ * 0xA5A5A5A5; planes receives its dwords [n_planes][n][235][336] (pixel (u, v) at row v + 5, column u + 5; low half img1, high half the warped img2) and
+ * out the values the planes join to. */
+int hnet_op_prep_batch(hnet_ctx* ctx, const void* img1, const void* img2, int pix_fmt, const float* H, int n, int k, int align_off, float* out,
+                       uint32_t* planes);
 /* after a forward: copies the output of layer `layer` (0..19 convs) of pair `pair` as [Cout][Ho][Wo] */
 int hnet_debug_layer_output(hnet_ctx* ctx, int layer, int pair, float* out, size_t capacity_floats);
 /* after a forward: part-1 homography of pair `pair`, 9 floats */

@@ -20,4 +20,6 @@ constexpr bool table_ok() {
 static_assert(table_ok(), "b41_tap: every tap once, shared reads within one kernel column");
 static_assert(B42_HP >= 112 + B42_PADY && B42_WP >= 160 + B42_PADX + 1, "the bordered block_4_1 map holds the image and the patch of the last tile (pixel 35 of its rows)");
 static_assert((B42_WP * 32) % 128 == 0, "rows of the bordered map start on 128-byte lines");
+// the block-4 input planes as cuahn_vio_amd/_capi.py exports them to the tests (B4_HP, B4_WP, B4_PADX, B4_PADY)
+static_assert(B4_HP == 235 && B4_WP == 336 && B4_PADX == 5 && B4_PADY == 5, "the B4_* constants of _capi.py are those of kernels.h");
 int main() { return 0; }

@@ -8,6 +8,7 @@ import pytest
 
 from conftest import (GOLDEN_DIR, TOL_COV_REL, TOL_PX_VS_ORACLE, TOL_PX_VS_REF32, TOL_PX_VS_REF64, case_oracle, case_weights, tol_px_vs_oracle,
                       golden_cases, load_case)
+from warp_cases import nasty_homographies as _nasty_homographies, pool_like_kernel as _pool_like_kernel
 
 pytestmark = pytest.mark.gpu
 
@@ -94,31 +95,6 @@ def test_op_prep(eng_full, k):
         ref = pyoracle.avgpool(np.stack([f1, w]), k)
         assert np.abs(got - ref).max() < 2e-4 / k
     assert np.abs(eng_full.op_prep(f1, f2, None, k)[0] - pyoracle.avgpool(f1[None], k)[0]).max() < 1e-6
-
-
-def _nasty_homographies():
-    g = np.load(os.path.join(GOLDEN_DIR, "warp_s11.npz"))
-    hs = {n: g["H_" + n].astype(np.float32) for n in ("identity", "shift", "oob", "persp")}
-    hs["z_zero"] = np.array([[1, 0, 0], [0, 1, 0], [0, 0, 0]], np.float32)                  # NaN coordinates everywhere
-    hs["z_sign_change"] = np.array([[1, 0, 0], [0, 1, 0], [-1 / 160.0, 0, 1]], np.float32)   # Z = 0 on the column u = 160
-    hs["zoom_out_3x"] = np.array([[3, 0, -300], [0, 3, -200], [0, 0, 1]], np.float32)       # source box of a tile > staging buffer
-    hs["rot90"] = np.array([[0, -1, 270], [1, 0, -50], [0, 0, 1]], np.float32)
-    hs["shrink"] = np.array([[0.05, 0, 100], [0, 0.05, 100], [0, 0, 1]], np.float32)        # whole tile inside 4 x 2 source pixels
-    hs["far_shift"] = np.array([[1, 0, 5000], [0, 1, 0], [0, 0, 1]], np.float32)
-    hs["edge_minus_half"] = np.array([[1, 0, -0.5], [0, 1, -0.5], [0, 0, 1]], np.float32)   # taps at -1 on the first row / column
-    return hs
-
-
-def _pool_like_kernel(x, k):
-    """AvgPool in the summation order of prep_warp_tiled_kernel: rows of a window sequentially, then a pairwise tree over its columns"""
-    h, w = x.shape
-    cols = np.zeros((h // k, w), np.float32)
-    for i in range(k):
-        cols = (cols + x[i::k]).astype(np.float32)
-    parts = [cols[:, j::k] for j in range(k)]
-    while len(parts) > 1:
-        parts = [(parts[2 * j] + parts[2 * j + 1]).astype(np.float32) for j in range(len(parts) // 2)]
-    return (parts[0] * np.float32(1.0 / (k * k))).astype(np.float32)
 
 
 @pytest.mark.parametrize("k", [1, 2, 4, 8])
