@@ -40,6 +40,7 @@ SYMBOLS = [
     "hnet_filters_uninitialize", "hnet_filters_advance", "hnet_filters_last_selection",
     "hnet_sessions_set_iterative_model", "hnet_sessions_infer_iter",
     "hnet_filters_predict", "hnet_filters_newest_imu_time", "hnet_filters_last_predict_device_ms",
+    "hnet_filters_predict_cov", "hnet_filters_last_predict_cov_device_ms",
     "hnet_filters_enable_innovations", "hnet_filters_set_nis_gate", "hnet_filters_last_innovations", "hnet_filters_innovation_stats",
     "hnet_filters_reset_innovation_stats",
     "hnet_op_photo_residual", "hnet_sessions_photo_residual", "hnet_filters_enable_photometric", "hnet_filters_last_photometric",
@@ -96,6 +97,8 @@ IMU_DTYPE = _np.dtype([("t", "<f8"), ("wm", "<f8", 3), ("am", "<f8", 3)])
 ODOMETRY_DTYPE = _np.dtype([("t_cam", "<f8"), ("t_imu", "<f8"), ("p", "<f8", 3), ("q", "<f8", 4), ("v", "<f8", 3), ("w_pos", "<f8", 3),
                             ("rpy", "<f8", 3), ("body_pos", "<f8", 3), ("body_vel", "<f8", 3), ("prior_px", "<f8", 8),
                             ("intervals", "<i4"), ("status", "<i4")])
+# hnet_odometry_cov: what hnet_filters_predict_cov writes per listed session next to its hnet_odometry
+ODOMETRY_COV_DTYPE = _np.dtype([("pose_cov", "<f8", (6, 6)), ("body_pos_cov", "<f8", (3, 3)), ("body_vel_cov", "<f8", (3, 3)), ("prior_cov_px", "<f8", (8, 8))])
 # hnet_innovation: one record per IEKF iteration and stepping session (hnet_filters_last_innovations)
 INNOVATION_DTYPE = _np.dtype([("r", "<f8", 8), ("s_diag", "<f8", 8), ("nis", "<f8"), ("iteration", "<i4"), ("flag", "<i4")])
 
@@ -243,6 +246,9 @@ def lib():
     L.hnet_filters_newest_imu_time.restype = C.c_double
     L.hnet_filters_last_predict_device_ms.argtypes = [vp]
     L.hnet_filters_last_predict_device_ms.restype = C.c_double
+    L.hnet_filters_predict_cov.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
+    L.hnet_filters_last_predict_cov_device_ms.argtypes = [vp]
+    L.hnet_filters_last_predict_cov_device_ms.restype = C.c_double
     L.hnet_filters_enable_innovations.argtypes = [vp]
     L.hnet_filters_set_nis_gate.argtypes = [vp, C.c_int, C.c_double]
     L.hnet_filters_last_innovations.argtypes = [vp, C.c_int, vp]

@@ -57,6 +57,14 @@ struct hnet_filters {
     hipEvent_t ev_p0 = nullptr, ev_p1 = nullptr;
     bool pred_timed = false;                   // set by the first hnet_filters_last_predict_device_ms: only then a predict records its two events
     double pred_ms = NAN;
+    // predict_cov (hnet_filters_predict_cov), allocated by its first call: ONE block {jobs [B] | records [n] | covariance records [n] | full [n][729]} (the
+    // three output sections dense for the call's n, so that one copy downloads what was asked for) and its pinned copy; the scratch is the predict's
+    uint8_t* pin_pcov = nullptr;
+    uint8_t* d_pcov = nullptr;
+    size_t off_pcov_out = 0;
+    hipEvent_t ev_c0 = nullptr, ev_c1 = nullptr;
+    bool pcov_timed = false;                   // as pred_timed, set by hnet_filters_last_predict_cov_device_ms
+    double pcov_ms = NAN;
     // innovations (hnet_filters_enable_innovations): the output block then is {net | prior_px | updates | innov [iters][n] InnovRec, dense | work | results},
     // so that the records lie inside the one download; the per-session gates; the statistics, accumulated from the records of accepted steps
     bool innov = false;
@@ -100,6 +108,11 @@ static void filters_drop_predict(hnet_filters* f) {               // predict_buf
     drop_dev(f->d_pred_sel); drop_dev(f->d_pred);
     drop_pin(f->pin_pred);
     drop_event(f->ev_p0); drop_event(f->ev_p1);
+}
+static void filters_drop_predict_cov(hnet_filters* f) {           // predict_cov_buffers
+    drop_dev(f->d_pcov);
+    drop_pin(f->pin_pcov);
+    drop_event(f->ev_c0); drop_event(f->ev_c1);
 }
 
 extern "C" {
@@ -252,6 +265,7 @@ void hnet_destroy_filters(hnet_filters* f) {
     drop_event(f->ev0); drop_event(f->ev1);
     filters_drop_feed(f);
     filters_drop_predict(f);
+    filters_drop_predict_cov(f);
     delete f;
 }
 
@@ -871,6 +885,78 @@ int hnet_filters_predict(hnet_filters* f, int n, const int32_t* ids, const doubl
         f->pred_ms = ms;
     }
     return HNET_OK;
+}
+
+// ---- hnet_filters_predict_cov: the predict's record with the covariance at the query time.  Read-only in the same sense.
+
+static_assert(sizeof(hnet_odometry_cov) == sizeof(PredictCovOut), "hnet_odometry_cov is the PredictCovOut layout");
+
+// the call's own job / output block, made once for max_batch sessions with the full covariances; the scratch is the predict's (predict_buffers)
+static int predict_cov_buffers(hnet_filters* f) {
+    if (f->d_pcov) return HNET_OK;
+    hnet_ctx* c = f->s->ctx;
+    const int B = c->cfg.max_batch;
+    f->off_pcov_out = al256((size_t)B * sizeof(PredictJob));
+    const size_t bytes = f->off_pcov_out + (size_t)B * (sizeof(PredictOut) + sizeof(PredictCovOut) + (size_t)hnet_ekf::NS * hnet_ekf::NS * sizeof(double));
+    hipError_t e = hipHostMalloc((void**)&f->pin_pcov, bytes, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipEventCreate(&f->ev_c0);
+    if (e == hipSuccess) e = hipEventCreate(&f->ev_c1);
+    if (e == hipSuccess) e = hipMalloc((void**)&f->d_pcov, bytes);
+    if (e != hipSuccess) {
+        filters_drop_predict_cov(f);
+        return fail(c, HNET_ERR_DEVICE, std::string("hnet_filters_predict_cov: ") + hipGetErrorString(e));
+    }
+    return HNET_OK;
+}
+
+int hnet_filters_predict_cov(hnet_filters* f, int n, const int32_t* ids, const double* t_query, hnet_odometry* out, hnet_odometry_cov* cov_out, double* full_cov) {
+    if (!f) return HNET_ERR_INVALID_ARG;
+    hnet_sessions* s = f->s;
+    hnet_ctx* c = s->ctx;
+    if (!f->cap) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_predict_cov: feed not enabled (hnet_filters_enable_feed)");
+    if (!t_query || !out || !cov_out) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_predict_cov: t_query / out / cov_out");
+    int rc = sessions_check_ids(s, n, ids);
+    if (rc != HNET_OK) return rc;
+    for (int i = 0; i < n; i++)
+        if (!std::isfinite(t_query[i])) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_predict_cov: t_query must be finite");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    if ((rc = predict_buffers(f)) != HNET_OK) return rc;
+    if ((rc = predict_cov_buffers(f)) != HNET_OK) return rc;
+    PredictJob* job = reinterpret_cast<PredictJob*>(f->pin_pcov);
+    for (int i = 0; i < n; i++) {                                  // hnet_filters_predict's rules in its order
+        const int id = ids[i];
+        const double dt = f->cam_imu_dt[id];
+        int st = PRED_OK;
+        if (!f->inited[id]) st = PRED_NO_STATE;
+        else if (t_query[i] > f->t[id] && !(t_query[i] < f->imu_newest[id] - dt)) st = PRED_WAIT_IMU;
+        job[i] = PredictJob{t_query[i], dt, id, st};
+    }
+    hipStream_t st = c->stream;
+    const size_t off_cov = f->off_pcov_out + (size_t)n * sizeof(PredictOut), off_full = off_cov + (size_t)n * sizeof(PredictCovOut);
+    const size_t full_bytes = full_cov ? (size_t)n * hnet_ekf::NS * hnet_ekf::NS * sizeof(double) : 0;
+    HIPCHK(c, hipMemcpyAsync(f->d_pcov, f->pin_pcov, (size_t)n * sizeof(PredictJob), hipMemcpyHostToDevice, st));
+    if (f->pcov_timed) HIPCHK(c, hipEventRecord(f->ev_c0, st));
+    HIPCHK(c, launch_filter_predict_cov(reinterpret_cast<const PredictJob*>(f->d_pcov), n, s->n, f->cap, f->d_ring, f->d_meta, f->d_state, f->d_params, f->d_pred_sel,
+                                        reinterpret_cast<PredictOut*>(f->d_pcov + f->off_pcov_out), reinterpret_cast<PredictCovOut*>(f->d_pcov + off_cov),
+                                        full_cov ? reinterpret_cast<double*>(f->d_pcov + off_full) : nullptr, st));
+    if (f->pcov_timed) HIPCHK(c, hipEventRecord(f->ev_c1, st));
+    HIPCHK(c, hipMemcpyAsync(f->pin_pcov + f->off_pcov_out, f->d_pcov + f->off_pcov_out, off_full + full_bytes - f->off_pcov_out, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    memcpy(out, f->pin_pcov + f->off_pcov_out, (size_t)n * sizeof(PredictOut));
+    memcpy(cov_out, f->pin_pcov + off_cov, (size_t)n * sizeof(PredictCovOut));
+    if (full_cov) memcpy(full_cov, f->pin_pcov + off_full, full_bytes);
+    if (f->pcov_timed) {
+        float ms = 0;
+        HIPCHK(c, hipEventElapsedTime(&ms, f->ev_c0, f->ev_c1));
+        f->pcov_ms = ms;
+    }
+    return HNET_OK;
+}
+
+double hnet_filters_last_predict_cov_device_ms(hnet_filters* f) {
+    if (!f) return NAN;
+    f->pcov_timed = true;
+    return f->pcov_ms;
 }
 
 double hnet_filters_newest_imu_time(const hnet_filters* f, int id) {

@@ -93,6 +93,18 @@ constexpr int PREDICT_THREADS = 64;
 hipError_t launch_filter_predict(const PredictJob* job, int n, int n_sessions, int cap, const hnet_ekf::ImuData* ring, const ImuRingMeta* meta,
                                  const FilterRec* state, const FilterParams* params, hnet_ekf::ImuData* scratch, PredictOut* out, hipStream_t s);
 
+// ---- prediction between frames with the covariance (hnet_filters_predict_cov): the record of the predict plus the covariance
+// hnet_ekf::propagate_with_imu gives at the query time and hnet_ekf::odometry_cov_from_state's blocks of it; read-only like the predict.
+// the layout of hnet_odometry_cov: hnet_ekf::OdometryCov
+struct PredictCovOut { hnet_ekf::OdometryCov c; };
+constexpr int PREDICT_COV_DOUBLES = (int)(sizeof(PredictCovOut) / sizeof(double));  // 118
+static_assert(sizeof(PredictCovOut) == 118 * sizeof(double), "PredictCovOut must be 118 packed doubles");
+// one workgroup of FILTER_THREADS per job.  scratch as launch_filter_predict's (the two calls are ordered on one stream and may share it);
+// out [n], cov_out [n]; full: null or [n][729], the propagated covariance itself
+hipError_t launch_filter_predict_cov(const PredictJob* job, int n, int n_sessions, int cap, const hnet_ekf::ImuData* ring, const ImuRingMeta* meta,
+                                     const FilterRec* state, const FilterParams* params, hnet_ekf::ImuData* scratch, PredictOut* out,
+                                     PredictCovOut* cov_out, double* full, hipStream_t s);
+
 // ---- innovation records and the NIS gate (hnet_filters_enable_innovations).
 // the layout of hnet_innovation: hnet_ekf::Innovation's r, s_diag and nis, then the iteration and the flag (hnet_ekf::INNOV_*)
 struct InnovRec {

@@ -489,6 +489,144 @@ __global__ __launch_bounds__(PREDICT_THREADS) void filter_predict_kernel(const P
     for (int i = t; i < PREDICT_OUT_DOUBLES; i += PREDICT_THREADS) ow[i] = rw[i];
 }
 
+// ---- prediction between frames with the covariance (hnet_filters_predict_cov) ----
+
+// filter_predict_kernel's record plus the covariance at the query time, one workgroup of FILTER_THREADS per listed session; read-only.
+// Status, ring count and span copy are filter_predict_kernel's, restated (that kernel and filter_select_kernel keep their text and their code); lane 0
+// runs the header's select_imu_readings on the span.  The intervals then run as in filter_propagate_kernel, every operation in that kernel's order, so
+// mean and covariance are the advance's bit for bit before its reset: per interval lane 0 forms the inputs, the Jacobians and the mean, all lanes
+// T = F P and T F^T + Fw diag(q) Fw^T.  One difference that costs no bit: F and Fw are zeroed ONCE by all lanes and lane 0 calls the header's
+// propagate_jacobians_fill, which writes the same entries in every interval, where propagate_jacobians clears both per interval on one lane.
+// Then lane 0 forms the record as filter_predict_kernel does (the same header calls in the same order) and the 6 x 6 pose Jacobian; the derived
+// blocks of hnet_ekf::odometry_cov_from_state go one element per lane through the header's element functions.  AT_STATE: the state's covariance as
+// it is and its blocks; NO_STATE / WAIT_IMU: zero records and a zero row of `full`.  Reads state / ring / meta / params, writes out[b], cov_out[b],
+// full + b * 729 (if given) and scratch + b * 2 * (cap + 2) only.
+__global__ __launch_bounds__(FILTER_THREADS) void filter_predict_cov_kernel(const PredictJob* __restrict__ job, int n_sessions, int cap,
+                                                                            const hnet_ekf::ImuData* __restrict__ ring, const ImuRingMeta* __restrict__ meta,
+                                                                            const FilterRec* __restrict__ state, const FilterParams* __restrict__ params,
+                                                                            hnet_ekf::ImuData* __restrict__ scratch, PredictOut* __restrict__ out,
+                                                                            PredictCovOut* __restrict__ cov_out, double* __restrict__ full) {
+    __shared__ FilterRec S;
+    __shared__ double F[NE], Fw[NS * NW], T[NE];
+    __shared__ PredictOut R;
+    __shared__ double J[36], TJ[36];
+    __shared__ int cnt[4];                                                              // the three counts, then the number of selected readings
+    const int b = blockIdx.x, t = threadIdx.x;
+    const PredictJob jb = job[b];
+    const int id = jb.id;
+    double* rw = reinterpret_cast<double*>(&R);
+    for (int i = t; i < PREDICT_OUT_DOUBLES; i += FILTER_THREADS) rw[i] = 0.0;          // (all-zero bits: intervals and status too)
+    for (int i = t; i < NE; i += FILTER_THREADS) F[i] = 0.0;
+    for (int i = t; i < NS * NW; i += FILTER_THREADS) Fw[i] = 0.0;
+    if (t < 4) cnt[t] = 0;
+    __syncthreads();
+    int status = (id >= 0 && id < n_sessions) ? jb.status : PRED_NO_STATE;              // (host-validated; uniform over the workgroup, as every test below)
+    if (status == PRED_OK) {
+        load_rec(S, state[id]);
+        __syncthreads();
+        const FilterParams& pr = params[id];
+        const double t_state = S.t;
+        hnet_ekf::ImuData* lin = scratch + (size_t)b * 2 * (cap + 2);
+        hnet_ekf::ImuData* rd = lin + (cap + 2);
+        int len = 0;
+        if (!(jb.t_query > t_state)) status = PRED_AT_STATE;
+        else {
+            const ImuRingMeta m = meta[id];
+            if (!ring_ok(m, cap) || m.count < 1) status = PRED_WAIT_IMU;
+            else {
+                const hnet_ekf::ImuData* rg = ring + (size_t)id * cap;
+                const double t0 = t_state + jb.cam_imu_dt, t1 = jb.t_query + jb.cam_imu_dt;
+                const double newest = ring_at(rg, m.head, cap, m.count - 1).t;
+                int c_old = 0, c_lt = 0, c_le = 0;
+                for (int j = t; j < m.count; j += FILTER_THREADS) {
+                    const double tt = ring_at(rg, m.head, cap, j).t;
+                    if (newest - tt > 10) c_old++;
+                    else { c_lt += tt < t0 ? 1 : 0; c_le += tt <= t1 ? 1 : 0; }
+                }
+                if (c_old) atomicAdd(&cnt[0], c_old);
+                if (c_lt) atomicAdd(&cnt[1], c_lt);
+                if (c_le) atomicAdd(&cnt[2], c_le);
+                __syncthreads();
+                int first = 0;
+                len = hnet_ekf::select_span(m.count - cnt[0], cnt[1], cnt[2], &first);
+                if (len < 1 || len > cap || first < 0 || cnt[0] + first + len > m.count) len = 0;
+                for (int k = t; k < len; k += FILTER_THREADS) lin[k] = ring_at(rg, m.head, cap, cnt[0] + first + k);
+                __syncthreads();
+                if (t == 0) cnt[3] = hnet_ekf::select_imu_readings(lin, len, t0, t1, rd);    // writes at most len + 2 readings
+                __syncthreads();
+            }
+        }
+        int done = 0;
+        if (status == PRED_OK) {
+            int n_sel = cnt[3];
+            if (n_sel < 0 || n_sel > cap + 2) n_sel = 0;
+            for (int k = 0; k + 1 < n_sel; k++) {                                        // filter_propagate_kernel's interval, F and Fw zeroed above
+                if (t == 0) {
+                    double w_hat[3], a_hat[3];
+                    const double dt = hnet_ekf::imu_interval_inputs(S.s, rd[k], rd[k + 1], pr.imu_avg != 0, w_hat, a_hat);
+                    hnet_ekf::propagate_jacobians_fill(S.s, pr.ext, dt, w_hat, F, Fw, pr.gravity_mag);
+                    hnet_ekf::propagate_mean(S.s, pr.ext, dt, w_hat, a_hat, pr.gravity_mag);
+                }
+                __syncthreads();
+                for (int e = t; e < NE; e += FILTER_THREADS) {                           // T = F P
+                    const int i = e / NS, j = e % NS;
+                    double a = 0.0;
+                    for (int q = 0; q < NS; q++) a += F[i * NS + q] * S.s.cov[q * NS + j];
+                    T[e] = a;
+                }
+                __syncthreads();
+                double o[EPT];
+                for (int r = 0; r < EPT; r++) {                                          // T F^T + Fw diag(q) Fw^T
+                    const int e = t + r * FILTER_THREADS;
+                    if (e >= NE) break;
+                    const int i = e / NS, j = e % NS;
+                    double a = 0.0;
+                    for (int q = 0; q < NS; q++) a += T[i * NS + q] * F[j * NS + q];
+                    for (int q = 0; q < NW; q++) a += Fw[i * NW + q] * pr.q[q] * Fw[j * NW + q];
+                    o[r] = a;
+                }
+                for (int r = 0; r < EPT; r++) {
+                    const int e = t + r * FILTER_THREADS;
+                    if (e < NE) S.s.cov[e] = o[r];
+                }
+                __syncthreads();
+                done++;
+            }
+        }
+        if (status != PRED_WAIT_IMU) {
+            if (t == 0) {                                                                // filter_predict_kernel's record
+                hnet_ekf::odometry_from_state(S.s, status == PRED_OK ? jb.t_query : t_state, jb.cam_imu_dt, R.o);
+                double prior_cam[8];
+                hnet_ekf::prior_pixels(S.s, R.prior_px, prior_cam);
+                R.intervals = done;
+                hnet_ekf::pose_cov_jacobian(S.s, J);
+            }
+            __syncthreads();
+            if (t < 36) TJ[t] = hnet_ekf::pose_cov_left(J, S.s.cov, t / 6, t % 6);
+        }
+    }
+    if (t == 0) R.status = status;
+    __syncthreads();
+    const bool live = status == PRED_OK || status == PRED_AT_STATE;
+    double* ow = reinterpret_cast<double*>(out + b);
+    for (int i = t; i < PREDICT_OUT_DOUBLES; i += FILTER_THREADS) ow[i] = rw[i];
+    static_assert(PREDICT_COV_DOUBLES <= FILTER_THREADS && offsetof(hnet_ekf::OdometryCov, body_pos_cov) == 36 * sizeof(double) &&
+                  offsetof(hnet_ekf::OdometryCov, body_vel_cov) == 45 * sizeof(double) && offsetof(hnet_ekf::OdometryCov, prior_cov_px) == 54 * sizeof(double),
+                  "OdometryCov: pose 36, body position 9, body velocity 9, prior 64, one element per lane");
+    if (t < PREDICT_COV_DOUBLES) {                                                       // hnet_ekf::odometry_cov_from_state, one element per lane
+        double v = 0.0;
+        if (live) {
+            if (t < 36) v = hnet_ekf::pose_cov_elem(TJ, J, t / 6, t % 6);
+            else if (t < 45) v = hnet_ekf::pose_cov_elem(TJ, J, hnet_ekf::frd_src((t - 36) / 3), hnet_ekf::frd_src((t - 36) % 3));
+            else if (t < 54) v = hnet_ekf::body_vel_cov_elem(S.s.cov, (t - 45) / 3, (t - 45) % 3);
+            else v = hnet_ekf::prior_cov_px_elem(S.s.cov, (t - 54) >> 3, (t - 54) & 7);
+        }
+        reinterpret_cast<double*>(cov_out + b)[t] = v;
+    }
+    if (full)
+        for (int e = t; e < NE; e += FILTER_THREADS) full[(size_t)b * NE + e] = live ? S.s.cov[e] : 0.0;
+}
+
 // ---- innovation records and the NIS gate (hnet_filters_enable_innovations) ----
 
 static_assert(offsetof(InnovRec, nis) == 16 * sizeof(double) && offsetof(InnovRec, iteration) == 17 * sizeof(double), "InnovRec: r, s_diag, nis, then the two ints");
@@ -595,6 +733,15 @@ hipError_t launch_filter_predict(const PredictJob* job, int n, int n_sessions, i
                                  const FilterRec* state, const FilterParams* params, hnet_ekf::ImuData* scratch, PredictOut* out, hipStream_t s) {
     if (n < 1 || cap < 1) return hipErrorInvalidValue;
     hipLaunchKernelGGL(filter_predict_kernel, dim3((unsigned)n), dim3(PREDICT_THREADS), 0, s, job, n_sessions, cap, ring, meta, state, params, scratch, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_filter_predict_cov(const PredictJob* job, int n, int n_sessions, int cap, const hnet_ekf::ImuData* ring, const ImuRingMeta* meta,
+                                     const FilterRec* state, const FilterParams* params, hnet_ekf::ImuData* scratch, PredictOut* out,
+                                     PredictCovOut* cov_out, double* full, hipStream_t s) {
+    if (n < 1 || cap < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(filter_predict_cov_kernel, dim3((unsigned)n), dim3(FILTER_THREADS), 0, s, job, n_sessions, cap, ring, meta, state, params, scratch, out,
+                       cov_out, full);
     return hipGetLastError();
 }
 

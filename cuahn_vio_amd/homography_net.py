@@ -704,6 +704,23 @@ class HnetFilters:
         self._check(self._L.hnet_filters_predict(self._f, n, ids.ctypes.data, tq.ctypes.data, out.ctypes.data))
         return out
 
+    def predict_cov(self, ids, t_query, full=False):
+        """predict() with the covariance at the query time, read-only -> (records of _capi.ODOMETRY_DTYPE [n], records of _capi.ODOMETRY_COV_DTYPE [n])
+        and, with full, the propagated 27 x 27 covariances [n, 27, 27] as a third item"""
+        ids = np.ascontiguousarray(np.atleast_1d(ids), dtype=np.int32)
+        n = len(ids)
+        tq = np.ascontiguousarray(np.broadcast_to(np.asarray(t_query, dtype=np.float64), (n,)))
+        out = np.zeros(n, _capi.ODOMETRY_DTYPE)
+        cov = np.zeros(n, _capi.ODOMETRY_COV_DTYPE)
+        P = np.zeros((n, 27, 27)) if full else None
+        self._check(self._L.hnet_filters_predict_cov(self._f, n, ids.ctypes.data, tq.ctypes.data, out.ctypes.data, cov.ctypes.data,
+                                                     P.ctypes.data if full else None))
+        return (out, cov, P) if full else (out, cov)
+
+    def last_predict_cov_device_ms(self):
+        """as last_predict_device_ms, for predict_cov"""
+        return float(self._L.hnet_filters_last_predict_cov_device_ms(self._f))
+
     def newest_imu_time(self, id):
         """the time (IMU clock) of the newest reading session id was fed; NaN for an empty ring"""
         return float(self._L.hnet_filters_newest_imu_time(self._f, int(id)))

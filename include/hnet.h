@@ -424,7 +424,7 @@ int  hnet_filters_last_selection(hnet_filters* f, int id, hnet_imu* out, int cap
  * sessions from the readings hnet_filters_feed_imu left on the device: the mean of hnet_ekf::propagate_mean_with_imu (the loop of an advance without the
  * covariance) from the state's time to t_query[i] (camera clock), then what the reference's two publishers form from a state
  * (hnet_ekf::odometry_from_state) and the pixel prior a forward at t_query would receive.  p, q, v and prior_px are, bit for bit, what an advance to a
- * frame stamped t_query computes before its forward (tests/test_gpu_filters_predict.py).  The covariance is not predicted: a caller who needs it advances.
+ * frame stamped t_query computes before its forward (tests/test_gpu_filters_predict.py).  The covariance is not predicted here: hnet_filters_predict_cov below returns it.
  * One upload, one launch, one download and one synchronisation on the context's stream, so the call is ordered behind earlier feed_imu / advance calls.
  * No call changes any state: filter states, rings, image counts, mask sequence numbers, hnet_filters_last_timing / _last_selection / _last_priors and
  * the steps so far are as before; sessions with any number of images may be listed.  Per listed session:
@@ -451,6 +451,34 @@ double hnet_filters_newest_imu_time(const hnet_filters* f, int id);   /* the hos
 /* tools: the launch of the last timed predict, HIP events, ms.  A predict records no events until this has been called once, so a caller at IMU rate
  * never pays for them; the first call switches the timing on and returns NaN, as does every call before a timed predict */
 double hnet_filters_last_predict_device_ms(hnet_filters* f);
+
+/* ---- filters, between frames: the predict's record WITH the covariance at the query time, read-only ------------------------------------------
+ * hnet_filters_predict gives no uncertainty, and an advance is no substitute for a caller who wants one between frames: it needs a pushed frame,
+ * changes the filter, resets the offset block and costs a forward.  hnet_filters_predict_cov returns, for the listed sessions, out[i] = what
+ * hnet_filters_predict returns for the same query, byte for byte, and in cov_out[i] the covariance of that record: the 27 x 27 covariance of
+ * hnet_ekf::propagate_with_imu at t_query[i], BEFORE any reset (for HNET_PRED_OK bit for bit what the advance to a frame stamped t_query computes before
+ * its forward: rows and columns 0 .. 14 are those of its state_out, tests/test_gpu_filters_predict_cov.py), carried to the record's quantities by
+ * hnet_ekf::odometry_cov_from_state.  The error state perturbs the attitude on the right (q <- q (x) dq(dtheta)) and p in the IMU frame, so with
+ * R = Rot() and P6 = cov[0:6, 0:6]:
+ *   pose_cov      J P6 J^T, J = [[R, -R skew(p)], [0, R]]: the covariance of (w_pos, rotation vector about the fixed axes of the frame `global`) in the
+ *                 order of a geometry_msgs::PoseWithCovariance (x, y, z, rotation about x, y, z), which publish_state leaves empty (RosVisualizer.cpp:161-176)
+ *   body_pos_cov  of body_pos: the signed permutation (-y, -x, -z) applied to pose_cov[0:3, 0:3]
+ *   body_vel_cov  of body_vel: the same permutation applied to cov[6:9, 6:9]
+ *   prior_cov_px  of prior_px: 159.5^2 cov[sel(i)][sel(j)], sel(j) = 15 + 3 (j >> 1) + (j & 1): the filter's part of the S an update at t_query would form
+ *                 (hnet_innovation.s_diag minus the network's share), in px^2
+ * There is no roll / pitch / yaw covariance (the Euler Jacobian is singular where Rot2Euler branches); pose_cov[3:6, 3:6] is the attitude's.
+ * full_cov: NULL, or [n][729]: the propagated covariance itself, row major in the error-state order of hnet_filter_state.cov (5.8 KB per session, so
+ * it is downloaded only when asked for).  Statuses as hnet_filters_predict, decided by the same rules in the same order:
+ *   HNET_PRED_OK        the covariance at t_query        HNET_PRED_AT_STATE  the state's covariance as it is, and its blocks
+ *   HNET_PRED_NO_STATE / HNET_PRED_WAIT_IMU  zero records and a zero row of full_cov
+ * Errors (those of hnet_filters_predict, and a NULL out / cov_out) write nothing.  One upload, one launch, one download and one synchronisation on the
+ * context's stream; nothing of the filters' or the sessions' state or bookkeeping is written.  The first call allocates its own job / output block and
+ * shares the predict's scratch. */
+typedef struct hnet_odometry_cov { double pose_cov[36], body_pos_cov[9], body_vel_cov[9], prior_cov_px[64]; } hnet_odometry_cov;   /* 118 doubles */
+int    hnet_filters_predict_cov(hnet_filters* f, int n, const int32_t* ids, const double* t_query, hnet_odometry* out, hnet_odometry_cov* cov_out,
+                                double* full_cov);
+/* tools: as hnet_filters_last_predict_device_ms, for the launch of the last timed predict_cov */
+double hnet_filters_last_predict_cov_device_ms(hnet_filters* f);
 
 /* ---- filters, innovation records: how well each measurement agreed with the filter, and an opt-in gate on it --------------------------------
  * The update weighs the network's covariance with one hand-set scale, k_net_cov, and the reference applies every measurement (it dropped OpenVINS'

@@ -218,11 +218,12 @@ inline void set_block(double* M, int ld, int r0, int c0, const double* B, double
         for (int j = 0; j < 3; j++) M[(r0 + i) * ld + c0 + j] = scale * B[i * 3 + j];
 }
 
-/* F [27 x 27], Fw [27 x 15], row major, evaluated at `s` BEFORE the mean is advanced (Propagator.cpp:211-220, :222-333) */
-inline void propagate_jacobians(const State& s, const Extrinsics& e, double dt, const double w_hat[3], double* F, double* Fw,
-                                double gravity_mag = 9.81) {
-    std::memset(F, 0, sizeof(double) * NS * NS);
-    std::memset(Fw, 0, sizeof(double) * NS * NW);
+/* The body of propagate_jacobians below: every entry of F [27 x 27] and Fw [27 x 15] (row major) that can be non-zero is WRITTEN, none is read before
+ * it is written and no other entry is touched; which entries those are does not depend on the arguments.  A caller that zeroed both once may therefore
+ * call this for one interval after another (filter_predict_cov_kernel zeroes them once with all lanes); tests/test_filters_predict_cov_cpu.py compares
+ * zeroed buffers + this with the body as it stood before the split, byte for byte. */
+inline void propagate_jacobians_fill(const State& s, const Extrinsics& e, double dt, const double w_hat[3], double* F, double* Fw,
+                                     double gravity_mag = 9.81) {
     const double I3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
     double R[9], Rt[9];
     quat_to_rot(s.q, R);
@@ -339,6 +340,14 @@ inline void propagate_jacobians(const State& s, const Extrinsics& e, double dt, 
     copy_block(BA, 6, P_, V_, 1.0);
     copy_block(BG, 9, P_, V_, 1.0);
     for (int c = 0; c < 4; c++) copy_block(15 + 3 * c, 0, 15 + 3 * c, BG, -1.0);
+}
+
+/* F [27 x 27], Fw [27 x 15], row major, evaluated at `s` BEFORE the mean is advanced (Propagator.cpp:211-220, :222-333) */
+inline void propagate_jacobians(const State& s, const Extrinsics& e, double dt, const double w_hat[3], double* F, double* Fw,
+                                double gravity_mag = 9.81) {
+    std::memset(F, 0, sizeof(double) * NS * NS);
+    std::memset(Fw, 0, sizeof(double) * NS * NW);
+    propagate_jacobians_fill(s, e, dt, w_hat, F, Fw, gravity_mag);
 }
 
 /* Propagator.h:86-96: diagonal of Q, order gyro, accel, accel random walk, gyro random walk, 4pt */
@@ -697,6 +706,70 @@ inline void odometry_from_state(const State& s, double t_cam, double cam_imu_dt,
     rot_to_euler(B, o.rpy[0], o.rpy[1], o.rpy[2]);
     o.body_pos[0] = -o.w_pos[1]; o.body_pos[1] = -o.w_pos[0]; o.body_pos[2] = -o.w_pos[2];
     o.body_vel[0] = -s.v[1]; o.body_vel[1] = -s.v[0]; o.body_vel[2] = -s.v[2];
+}
+
+/* ---- the covariance of what odometry_from_state and prior_pixels form (hnet_filters_predict_cov, include/hnet.h).  The reference publishes
+ * geometry_msgs::PoseWithCovarianceStamped from publish_state and never fills its covariance (RosVisualizer.cpp:161-176).
+ * The error state perturbs the attitude on the RIGHT: update() applies q <- q (x) dq(dtheta) through quat_apply_rotvec, so Rot() <- R Exp(dtheta) with
+ * R = quat_to_rot(q) (J_dc_q = -ez^T R skew(p + t) in propagate_jacobians_fill says the same), and p is additive in the IMU frame.  With
+ * w_pos = R p:  d w_pos = R dp - R skew(p) dtheta, and R Exp(dtheta) = Exp(R dtheta) R: the rotation vector about the FIXED axes of the frame
+ * `global` is R dtheta.  Hence J = [[R, -R skew(p)], [0, R]] on (dp, dtheta) = error states 0 .. 5, and pose_cov = J P6 J^T in the order of a ROS
+ * PoseWithCovariance (x, y, z, rotation about x, y, z).  tests/test_filters_predict_cov_cpu.py pins J against central differences of update()'s own
+ * perturbation.  There is no roll / pitch / yaw covariance: the Euler Jacobian is singular at rot_to_euler's sy < 1e-6 branch. */
+struct OdometryCov {
+    double pose_cov[36];               /* (w_pos, rotation vector about the axes of `global`), row major 6 x 6 */
+    double body_pos_cov[9];            /* of Odometry::body_pos: the signed permutation (-y, -x, -z) applied to pose_cov[0:3, 0:3] */
+    double body_vel_cov[9];            /* of Odometry::body_vel: the same permutation applied to cov[6:9, 6:9] */
+    double prior_cov_px[64];           /* of prior_pixels' prior_px: 159.5^2 cov[sel(i)][sel(j)], row major 8 x 8 */
+};
+
+/* the error state that measurement component j selects (update(), innovation(): 15 + 3 c + k) */
+inline int meas_row(int j) { return 15 + 3 * (j >> 1) + (j & 1); }
+/* (-y, -x, -z): component i of body_pos / body_vel is minus component frd_src(i); the two signs of a covariance element cancel */
+inline int frd_src(int i) { return i == 0 ? 1 : i == 1 ? 0 : 2; }
+
+/* J [6 x 6], row major */
+inline void pose_cov_jacobian(const State& s, double J[36]) {
+    double R[9], Sp[9], RS[9];
+    quat_to_rot(s.q, R);
+    m3::skew(s.p, Sp);
+    m3::mul(R, Sp, RS);
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) {
+            J[i * 6 + j] = R[i * 3 + j];
+            J[i * 6 + 3 + j] = -RS[i * 3 + j];
+            J[(3 + i) * 6 + j] = 0.0;
+            J[(3 + i) * 6 + 3 + j] = R[i * 3 + j];
+        }
+}
+/* element (i, j) of T = J P6 and of T J^T, the inner index ascending (the style of propagate_cov: the device forms one element per lane with these) */
+inline double pose_cov_left(const double J[36], const double* cov, int i, int j) {
+    double a = 0.0;
+    for (int k = 0; k < 6; k++) a += J[i * 6 + k] * cov[k * NS + j];
+    return a;
+}
+inline double pose_cov_elem(const double T[36], const double J[36], int i, int j) {
+    double a = 0.0;
+    for (int k = 0; k < 6; k++) a += T[i * 6 + k] * J[j * 6 + k];
+    return a;
+}
+inline double body_vel_cov_elem(const double* cov, int i, int j) { return cov[(6 + frd_src(i)) * NS + 6 + frd_src(j)]; }
+inline double prior_cov_px_elem(const double* cov, int i, int j) { return (F_PIX * F_PIX) * cov[meas_row(i) * NS + meas_row(j)]; }
+
+inline void odometry_cov_from_state(const State& s, OdometryCov& c) {
+    double J[36], T[36];
+    pose_cov_jacobian(s, J);
+    for (int i = 0; i < 6; i++)
+        for (int j = 0; j < 6; j++) T[i * 6 + j] = pose_cov_left(J, s.cov, i, j);
+    for (int i = 0; i < 6; i++)
+        for (int j = 0; j < 6; j++) c.pose_cov[i * 6 + j] = pose_cov_elem(T, J, i, j);
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) {
+            c.body_pos_cov[i * 3 + j] = c.pose_cov[frd_src(i) * 6 + frd_src(j)];
+            c.body_vel_cov[i * 3 + j] = body_vel_cov_elem(s.cov, i, j);
+        }
+    for (int i = 0; i < 8; i++)
+        for (int j = 0; j < 8; j++) c.prior_cov_px[i * 8 + j] = prior_cov_px_elem(s.cov, i, j);
 }
 
 /* ---- initialisation from a standing start: what VioManager::try_to_initialize (VioManager.cpp:312-363) does with the buffered IMU

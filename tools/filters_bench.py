@@ -17,6 +17,10 @@ hnet_sessions_infer_iter on an iterative engine attached to its sessions.
 frame is pushed and the readings are fed, one predict of all K sessions to the frame's time (wall time of the call and the event time of its launch),
 the host alternative on the same inputs (hnet_filters_get_state of the K sessions + hnet_ekf::propagate_mean_with_imu / odometry_from_state over a
 host copy of the histories, tests/cpp/filters_predict_ref.cpp, on T threads), then the advance of the same sessions, which is the reference point.
+--predict-cov is a mode beside --predict (hnet_filters_predict_cov) with the same ticks: per tick, once the frame is pushed and the readings
+are fed, one predict_cov of all K sessions to the frame's time without and one with the full covariances (wall time of each call, event time of each
+launch), one predict, the host alternative (hnet_filters_get_state + hnet_ekf::propagate_with_imu / odometry_from_state / odometry_cov_from_state over a
+host copy of the histories, tests/cpp/filters_predict_cov_ref.cpp, on T threads), then the advance of the same sessions.
 --innov is a mode of its own (innovation records and the NIS gate): per (K, iterations) three filters objects for hnet_filters_step and three
 fed ones for hnet_filters_advance, each on its own context, with innovations off, on, and on with a gate that never rejects (1e300); every tick runs the
 same inputs through all six in turn (the order rotates with the tick), reported are the wall time of the call and its event time.  "host_gated" is the host
@@ -25,6 +29,7 @@ hnet_sessions_infer, the prior of forward `it` being the one the header hands it
    python tools/filters_bench.py [--k 1,8,64,256] [--iters 1,3] [--ticks 20] [--warmup 3] [--threads 1,16] [--feed]
                                  [--iter-variant prior1 --iter-mc 8 --iter-p 0.1]
    python tools/filters_bench.py --predict [--k 1,8,64,256] [--ticks 20] [--warmup 3] [--threads 1,16]
+   python tools/filters_bench.py --predict-cov [--k 1,8,64,256] [--ticks 20] [--warmup 3] [--threads 1,16]
    python tools/filters_bench.py --innov [--k 1,8,64,256] [--iters 1,3] [--ticks 20] [--warmup 3]
 --photo is a mode of its own (photometric residual records): step and advance with the records off and on, in one process on the same inputs.
    python tools/filters_bench.py --photo [--k 1,8,64,256] [--iters 1,3] [--ticks 20] [--warmup 3]"""
@@ -139,6 +144,109 @@ def predict_mode(a):
             rec[f"host_predict_{T}t_ms_p50"], rec[f"host_predict_{T}t_ms_p10"], rec[f"host_predict_{T}t_ms_p90"] = (pct(host_ms[T], 50), pct(host_ms[T], 10),
                                                                                                                pct(host_ms[T], 90))
         rec["predict_over_advance"] = round(float(np.median(pred_ms)) / float(np.median(adv_ms)), 4)
+        print(json.dumps(rec), flush=True)
+        f.close(); s.close(); e.close()
+
+
+def predict_cov_mode(a):
+    from cuahn_vio_amd import _capi, replay, weights
+    from cuahn_vio_amd.homography_net import HnetEngine, HnetFilters, HnetSessions
+    so = os.path.join(tempfile.mkdtemp(prefix="filters_predict_cov_ref_"), "filters_predict_cov_ref.so")
+    subprocess.run(["g++", "-std=c++17", "-O2", "-shared", "-fPIC", "-pthread", "-I", os.path.join(ROOT, "include"),
+                    os.path.join(ROOT, "tests", "cpp", "filters_predict_cov_ref.cpp"), "-o", so], check=True)
+    ref = C.CDLL(so)
+    ref.pcov_ref_predict_batch.restype = None
+    blob = weights.pack_state_dict(weights.synthetic_state(0))
+    fx = replay.load_fixture("indoor_forward_7")
+    pool = np.stack([replay.render_frame(fx, 100 + j) for j in range(16)])
+    threads = [int(x) for x in a.threads.split(",")]
+
+    def pct(x, q):
+        return round(float(np.percentile(x, q)), 3)
+
+    for K in [int(x) for x in a.k.split(",")]:
+        e = HnetEngine(blob, max_batch=K, variant="prior3", mc_samples=16, dropout_p=0.05, mc_seed=1)
+        s = HnetSessions(e, K)
+        f = HnetFilters(s, 1)
+        f.enable_feed(256)
+        f.last_predict_device_ms()                               # switches the event timing of both calls on
+        f.last_predict_cov_device_ms()
+        p = HnetFilters.default_params()
+        params = (_capi.FilterParams * K)(*([p] * K))
+        ids = np.arange(K, dtype=np.int32)
+        st0 = np.zeros(1, _capi.FILTER_STATE_DTYPE)
+        st0["q"] = [1, 0, 0, 0]
+        st0["p"] = [0, 0, -1.0]
+        st0["cov"] = np.diag(np.r_[np.full(15, 1e-3), np.full(12, 1e-6)])
+        for i in range(K):
+            f.set_state(i, st0[0])
+        rng = np.random.default_rng(K)
+        hist = np.zeros(0, _capi.IMU_DTYPE)                      # the host alternative's copy of one session's history (all K are fed the same)
+        newest, t = -np.inf, 0.0
+        names = ("predict_cov_ms", "predict_cov_event_ms", "predict_cov_full_ms", "predict_cov_full_event_ms", "predict_ms", "predict_event_ms", "advance_ms",
+                 "advance_event_ms")
+        v = {k: [] for k in names}
+        host_ms = {T: [] for T in threads}
+        for tick in range(a.warmup + a.ticks + 1):
+            t_new = t + 0.0325
+            s.push(ids, np.repeat(pool[tick % len(pool)][None], K, 0), t=[t_new] * K)
+            win = imu_window(rng, t)
+            new = win[win["t"] > newest]
+            newest = float(new["t"][-1])
+            f.feed_imu(ids, [new] * K)
+            hist = np.concatenate([hist, new])[-256:]
+            tq = np.full(K, t_new)
+            keep = tick > a.warmup
+            t0 = time.perf_counter()
+            o, oc = f.predict_cov(ids, tq)
+            d = (time.perf_counter() - t0) * 1e3
+            d_ev = f.last_predict_cov_device_ms()
+            t0 = time.perf_counter()
+            o2, oc2, full = f.predict_cov(ids, tq, full=True)
+            d_full = (time.perf_counter() - t0) * 1e3
+            d_full_ev = f.last_predict_cov_device_ms()
+            t0 = time.perf_counter()
+            o3 = f.predict(ids, tq)
+            d_pred = (time.perf_counter() - t0) * 1e3
+            assert (o["status"] == _capi.PRED_OK).all() and (o["intervals"] == o["intervals"][0]).all(), (o["status"], o["intervals"])
+            assert o.tobytes() == o2.tobytes() == o3.tobytes() and oc.tobytes() == oc2.tobytes()
+            if keep:
+                for k, x in zip(names[:6], (d, d_ev, d_full, d_full_ev, d_pred, f.last_predict_device_ms())):
+                    v[k].append(x)
+            imu = np.ascontiguousarray(np.tile(hist, K))
+            off = (np.arange(K + 1) * len(hist)).astype(np.int64)
+            for T in threads:
+                out, cov, hfull = np.zeros(K, _capi.ODOMETRY_DTYPE), np.zeros(K, _capi.ODOMETRY_COV_DTYPE), np.zeros((K, 27, 27))
+                t0 = time.perf_counter()
+                st = f.get_state(ids)
+                ref.pcov_ref_predict_batch(C.c_void_p(st.ctypes.data), params, K, C.c_void_p(tq.ctypes.data), C.c_void_p(imu.ctypes.data),
+                                           C.c_void_p(off.ctypes.data), T, C.c_void_p(out.ctypes.data), C.c_void_p(cov.ctypes.data), C.c_void_p(hfull.ctypes.data))
+                if keep:
+                    host_ms[T].append((time.perf_counter() - t0) * 1e3)
+                assert np.abs(out["p"] - o["p"]).max() < 1e-9 and (out["intervals"] == o["intervals"]).all()
+                assert np.abs(hfull - full).max() <= 1e-10 * np.abs(hfull).max()
+            if tick > 0:                                          # (one image per session at tick 0: that advance propagates only)
+                t0 = time.perf_counter()
+                sta, _, _, status = f.advance(ids)
+                d = (time.perf_counter() - t0) * 1e3
+                assert (status == _capi.ADV_STEPPED).all(), status
+                if keep:
+                    v["advance_ms"].append(d)
+                    v["advance_event_ms"].append(f.last_timing()["device_ms"])
+            else:
+                f.advance(ids)
+            t = t_new
+        rec = {"K": K, "intervals": int(o["intervals"][0]), "ticks": len(v["predict_ms"])}
+        for name in names:
+            rec[f"{name}_p50"], rec[f"{name}_p10"], rec[f"{name}_p90"] = pct(v[name], 50), pct(v[name], 10), pct(v[name], 90)
+        for T in threads:
+            rec[f"host_predict_cov_{T}t_ms_p50"], rec[f"host_predict_cov_{T}t_ms_p10"], rec[f"host_predict_cov_{T}t_ms_p90"] = (
+                pct(host_ms[T], 50), pct(host_ms[T], 10), pct(host_ms[T], 90))
+        med = {k: float(np.median(x)) for k, x in v.items()}
+        rec["predict_cov_over_predict"] = round(med["predict_cov_ms"] / med["predict_ms"], 4)
+        rec["predict_cov_over_advance"] = round(med["predict_cov_ms"] / med["advance_ms"], 4)
+        rec["predict_cov_full_over_advance"] = round(med["predict_cov_full_ms"] / med["advance_ms"], 4)
+        rec["predict_cov_event_us_per_interval"] = round(1e3 * med["predict_cov_event_ms"] / max(rec["intervals"], 1), 3)
         print(json.dumps(rec), flush=True)
         f.close(); s.close(); e.close()
 
@@ -359,6 +467,7 @@ def main():
     ap.add_argument("--threads", default="1,16")
     ap.add_argument("--feed", action="store_true")
     ap.add_argument("--predict", action="store_true")
+    ap.add_argument("--predict-cov", action="store_true")
     ap.add_argument("--innov", action="store_true")
     ap.add_argument("--photo", action="store_true")
     ap.add_argument("--iter-variant", default=None)
@@ -367,6 +476,8 @@ def main():
     a = ap.parse_args()
     if a.predict:
         return predict_mode(a)
+    if a.predict_cov:
+        return predict_cov_mode(a)
     if a.innov:
         return innov_mode(a)
     if a.photo:
