@@ -44,6 +44,7 @@ SYMBOLS = [
     "hnet_filters_enable_innovations", "hnet_filters_set_nis_gate", "hnet_filters_last_innovations", "hnet_filters_innovation_stats",
     "hnet_filters_reset_innovation_stats",
     "hnet_op_photo_residual", "hnet_sessions_photo_residual", "hnet_filters_enable_photometric", "hnet_filters_last_photometric",
+    "hnet_filters_set_photo_gate", "hnet_filters_photo_stats", "hnet_filters_reset_photo_stats", "hnet_filters_set_photo_gate_taps",
 ]
 # hnet_filters_advance's status per listed session (include/hnet.h HNET_ADV_*)
 ADV_STEPPED, ADV_WAIT_IMU, ADV_WAIT_INIT, ADV_INITIALIZED, ADV_PROPAGATED, ADV_NO_FRAME = range(6)
@@ -83,6 +84,11 @@ class InnovationStats(C.Structure):
     _fields_ = [("used", C.c_int64), ("rejected", C.c_int64), ("singular", C.c_int64), ("sum_nis", C.c_double), ("max_nis", C.c_double)]
 
 
+class PhotoStats(C.Structure):
+    """hnet_photo_stats: estimate records judged, those rejected / degenerate among them, sum and maximum of the estimate / prior residual ratio"""
+    _fields_ = [("judged", C.c_int64), ("rejected", C.c_int64), ("degenerate", C.c_int64), ("sum_ratio", C.c_double), ("max_ratio", C.c_double)]
+
+
 class InitParams(C.Structure):
     """hnet_init_params: the static initialiser's window length, excitation threshold, initial height and wait_for_jerk"""
     _fields_ = [("window_time", C.c_double), ("imu_thresh", C.c_double), ("init_height", C.c_double), ("wait_for_jerk", C.c_int32)]
@@ -103,9 +109,10 @@ ODOMETRY_COV_DTYPE = _np.dtype([("pose_cov", "<f8", (6, 6)), ("body_pos_cov", "<
 INNOVATION_DTYPE = _np.dtype([("r", "<f8", 8), ("s_diag", "<f8", 8), ("nis", "<f8"), ("iteration", "<i4"), ("flag", "<i4")])
 
 
-# hnet_photo_residual: one record per (frame pair, candidate offsets); flags: PHOTO_DEGENERATE (include/hnet.h HNET_PHOTO_*)
+# hnet_photo_residual: one record per (frame pair, candidate offsets); flags: PHOTO_DEGENERATE, PHOTO_REJECTED (include/hnet.h HNET_PHOTO_*)
 PHOTO_RESIDUAL_DTYPE = _np.dtype([("sum", "<f8"), ("sum_inside", "<f8"), ("n_inside", "<i4"), ("flags", "<i4")])
 PHOTO_DEGENERATE = 1
+PHOTO_REJECTED = 2
 PHOTO_MAX_CANDIDATES = 66
 
 # the block-4 input planes (csrc/kernels.h B4_*): [plane][pair][B4_HP][B4_WP] dwords, pixel (u, v) at row v + B4_PADY, column u + B4_PADX
@@ -258,6 +265,10 @@ def lib():
     L.hnet_sessions_photo_residual.argtypes = [vp, C.c_int, vp, fp, C.c_int, vp]
     L.hnet_filters_enable_photometric.argtypes = [vp]
     L.hnet_filters_last_photometric.argtypes = [vp, C.c_int, vp]
+    L.hnet_filters_set_photo_gate.argtypes = [vp, C.c_int, C.c_double, C.c_int32]
+    L.hnet_filters_photo_stats.argtypes = [vp, C.c_int, C.POINTER(PhotoStats)]
+    L.hnet_filters_reset_photo_stats.argtypes = [vp, C.c_int]
+    L.hnet_filters_set_photo_gate_taps.argtypes = [vp, C.c_int]
     for name in SYMBOLS:
         getattr(L, name)   # AttributeError here = the library does not export what include/hnet.h declares
     _lib = L

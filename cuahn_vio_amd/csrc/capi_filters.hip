@@ -78,6 +78,13 @@ struct hnet_filters {
     size_t off_photo = 0;
     PhotoRec* d_photo_part = nullptr;          // [B][2 + iters][PHOTO_SLICES]
     int last_photo_n = 0;                      // as last_innov_n
+    // the photometric gate (hnet_filters_set_photo_gate): the per-session gates on the device and their host mirror (which decides whether a call
+    // forms its records per iteration), the per-slot verdict words of photo_gate_kernel, the statistics, where the single-candidate launch takes its taps from
+    PhotoGate* d_photo_gate = nullptr;         // [n_sessions], max_ratio 0 = no gate
+    int32_t* d_photo_verdict = nullptr;        // [B]
+    std::vector<PhotoGate> photo_gate;
+    std::vector<hnet_photo_stats> photo_stats;
+    bool photo_taps_global = false;
 };
 
 static size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -161,6 +168,47 @@ static void filters_count_innovations(hnet_filters* f, int n, const int32_t* ids
         }
 }
 
+// whether one of the sessions ids[0 .. n) has a photometric gate: the call then forms its photometric records per iteration (filters_enqueue_iekf)
+static bool filters_photo_gated(const hnet_filters* f, int n, const int32_t* ids) {
+    if (!f->photo) return false;
+    for (int j = 0; j < n; j++)
+        if (f->photo_gate[ids[j]].max_ratio > 0.0) return true;
+    return false;
+}
+// after an accepted call with photometric records: the records [n][2 + iters] of the sessions ids[0 .. n) go into their statistics (include/hnet.h
+// hnet_photo_stats).  ref_gate: the reference gates as the call uploaded them (the pinned input block: the device's copy is the one the kernels close).
+// An iteration is reached unrejected when no earlier iteration of the step has a photometric rejection, a NIS rejection or a singular S (updates[j] =
+// -1 - applied: with nothing skipped before it, `applied` is the iteration that found it).
+static void filters_count_photo(hnet_filters* f, int n, const int32_t* ids, const int32_t* ref_gate) {
+    const OutView h = filters_out_view(f, f->pin_out);
+    const int I = f->iters;
+    for (int j = 0; j < n; j++) {
+        if (!ref_gate[j]) continue;
+        hnet_photo_stats& a = f->photo_stats[ids[j]];
+        const PhotoRec* rec = h.photo + (size_t)j * (2 + I);
+        const PhotoRec& pr = rec[1];
+        for (int it = 0; it < I; it++) {
+            const PhotoRec& e = rec[2 + it];
+            a.judged++;
+            if (e.flags & PHOTO_REJECTED) a.rejected++;
+            if (e.flags & PHOTO_DEGENERATE) a.degenerate++;
+            if (!((pr.flags | e.flags) & PHOTO_DEGENERATE) && pr.n_inside >= 1 && e.n_inside >= 1) {
+                const double ratio = (e.sum_inside / e.n_inside) / (pr.sum_inside / pr.n_inside);
+                if (std::isfinite(ratio)) {
+                    a.sum_ratio += ratio;
+                    if (ratio > a.max_ratio) a.max_ratio = ratio;
+                }
+            }
+            bool stop = (e.flags & PHOTO_REJECTED) != 0 || (h.upd[j] < 0 && -1 - h.upd[j] == it);
+            if (f->innov) {
+                const int fl = h.innov[(size_t)it * n + j].flag;
+                stop = stop || fl == HNET_INNOV_REJECTED || fl == HNET_INNOV_SINGULAR;
+            }
+            if (stop) break;
+        }
+    }
+}
+
 // the context of forwards 1 .. iters - 1 of a step when the sessions have an iterative model (hnet_sessions_set_iterative_model), else null
 static hnet_ctx* filters_iter_ctx(const hnet_filters* f) { return f->iters > 1 ? f->s->iter : nullptr; }
 // forward `it` of a step: 0 on the main context ctx[0], later ones on ctx[1] if there is one; both read the pairs gathered into ctx[0]'s staging
@@ -184,8 +232,11 @@ static int filters_flags(hnet_ctx* const ctx[2], uint32_t* flag, hipStream_t st)
 // prior, the forward, the innovation record (if enabled) and the update; then ev1 and, behind it, the photometric records (hnet_filters_last_timing keeps
 // its meaning; inside the attempt: a repeat recomputes the records).  d_seq is [iters][seq_stride]; filter_innovation_kernel closes the d_gate entry of a
 // session it rejects, so every attempt uploads the gates again.
+// photo_gated (one of the n sessions has a photometric gate): the photometric records are formed per iteration instead, between the forward and the
+// innovation kernel - photo_iter_kernel and photo_gate_kernel, which closes d_gate and sets the slot's verdict word on a rejection (iteration 0 writes
+// every verdict word: a repeat re-forms them) - and nothing runs behind ev1.
 static int filters_enqueue_iekf(hnet_filters* f, hnet_ctx* const ctx[2], const OutView& d, int n, const int32_t* d_ids, int32_t* d_gate, const uint64_t* d_seq,
-                                int seq_stride, hipStream_t st) {
+                                int seq_stride, bool photo_gated, hipStream_t st) {
     hnet_ctx* c = ctx[0];
     const int I = f->iters, B = c->cfg.max_batch, N = f->s->n;
     for (int it = 0; it < I && n; it++) {
@@ -195,11 +246,18 @@ static int filters_enqueue_iekf(hnet_filters* f, hnet_ctx* const ctx[2], const O
         const FwdArgs a{.prev = c->stage_prev, .curr = c->stage_curr, .prior = c->cfg.use_prior ? pr_it : nullptr, .batch = n, .mean = net_it, .cov = net_it + 8,
                         .seq_tab = d_seq + (size_t)it * seq_stride, .mean_stride = HNET_PACKED_FLOATS, .cov_stride = HNET_PACKED_FLOATS};
         if (const int r = filters_forward(ctx, it, a, st); r != HNET_OK) return r;
-        if (f->innov) HIPCHK(c, launch_filter_innovation(d_ids, n, N, f->d_params, d.work, net_it, f->d_prior_cam, f->d_max_nis, d_gate, d.upd, it, d.innov, st));
+        if (photo_gated) {
+            const PhotoCands cands{nullptr, d.prior, d.net, (size_t)B * 72};
+            HIPCHK(c, launch_photo_iteration((const uint8_t*)c->stage_prev, (const uint8_t*)c->stage_curr, n, cands, it, I, !f->photo_taps_global, f->d_photo_part,
+                                             d_ids, N, f->d_photo_gate, d.upd, d_gate, f->d_photo_verdict, d.photo, st));
+        }
+        if (f->innov)
+            HIPCHK(c, launch_filter_innovation(d_ids, n, N, f->d_params, d.work, net_it, f->d_prior_cam, f->d_max_nis, d_gate, d.upd, it, d.innov,
+                                               photo_gated ? f->d_photo_verdict : nullptr, st));
         HIPCHK(c, launch_filter_update(d_ids, n, N, f->d_params, net_it, f->d_prior_cam, d_gate, it != I - 1, it == I - 1, d.work, d.upd, st));
     }
     HIPCHK(c, hipEventRecord(f->ev1, st));
-    if (f->photo && n) HIPCHK(c, filters_launch_photo(f, d, n, st));
+    if (f->photo && n && !photo_gated) HIPCHK(c, filters_launch_photo(f, d, n, st));
     return HNET_OK;
 }
 // an overflow of the fp16 planes among the downloaded outputs of n stepping sessions: the first forward with a non-finite output had finite inputs (its
@@ -213,11 +271,12 @@ static int filters_overflowed(const hnet_filters* f, hnet_ctx* const ctx[2], con
     return -1;
 }
 // the bookkeeping of an accepted call in which the sessions ids[0 .. n) stepped: what the last_* calls describe, the innovation statistics, the timing
-static int filters_accepted(hnet_filters* f, int n, const int32_t* ids, std::chrono::steady_clock::time_point t0, int n_inferences) {
+static int filters_accepted(hnet_filters* f, int n, const int32_t* ids, const int32_t* ref_gate, std::chrono::steady_clock::time_point t0, int n_inferences) {
     f->last_n = n;
     f->last_innov_n = f->innov ? n : 0;
     f->last_photo_n = f->photo ? n : 0;
     if (f->innov) filters_count_innovations(f, n, ids);
+    if (f->photo) filters_count_photo(f, n, ids, ref_gate);
     float ms = 0;
     HIPCHK(f->s->ctx, hipEventElapsedTime(&ms, f->ev0, f->ev1));
     record_timing(f->timing, ms, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), n_inferences, true);
@@ -260,7 +319,7 @@ void hnet_destroy_filters(hnet_filters* f) {
     hnet_ctx* c = f->s->ctx;
     (void)hipSetDevice(c->cfg.device_id);
     (void)hipStreamSynchronize(c->stream);
-    drop_dev(f->d_state); drop_dev(f->d_params); drop_dev(f->d_out); drop_dev(f->d_prior_cam); drop_dev(f->d_in); drop_dev(f->d_feed); drop_dev(f->d_max_nis); drop_dev(f->d_photo_part);
+    drop_dev(f->d_state); drop_dev(f->d_params); drop_dev(f->d_out); drop_dev(f->d_prior_cam); drop_dev(f->d_in); drop_dev(f->d_feed); drop_dev(f->d_max_nis); drop_dev(f->d_photo_part); drop_dev(f->d_photo_gate); drop_dev(f->d_photo_verdict);
     drop_pin(f->pin_feed); drop_pin(f->pin_out); drop_pin(f->pin_in);
     drop_event(f->ev0); drop_event(f->ev1);
     filters_drop_feed(f);
@@ -412,13 +471,14 @@ int hnet_filters_step(hnet_filters* f, int n, const int32_t* ids, const double* 
     hipStream_t st = c->stream;
     const size_t up = o_off + (size_t)(n + 1) * 4;
     hnet_ctx* const ctx[2] = {c, filters_iter_ctx(f)};
+    const bool photo_gated = filters_photo_gated(f, n, ids);
     auto enqueue = [&](uint32_t* flag_now) -> int {
         HIPCHK(c, hipMemcpyAsync(f->d_in, f->pin_in, up, hipMemcpyHostToDevice, st));
         HIPCHK(c, hipMemsetAsync(o.d.upd, 0, (size_t)n * sizeof(int32_t), st));
         HIPCHK(c, hipEventRecord(f->ev0, st));
         HIPCHK(c, launch_session_gather(s->ring, 2 * s->n, d_pairs, n, (uint8_t*)c->stage_prev, (uint8_t*)c->stage_curr, st));
         HIPCHK(c, launch_filter_propagate(d_ids, n, s->n, f->d_state, f->d_params, d_rd, d_roff, d_tf, o.d.work, st));
-        if (const int r = filters_enqueue_iekf(f, ctx, o.d, n, d_ids, d_gate, d_seq, n, st); r != HNET_OK) return r;
+        if (const int r = filters_enqueue_iekf(f, ctx, o.d, n, d_ids, d_gate, d_seq, n, photo_gated, st); r != HNET_OK) return r;
         HIPCHK(c, hipMemcpyAsync(f->pin_out, f->d_out, down, hipMemcpyDeviceToHost, st));
         return filters_flags(ctx, flag_now, st);
     };
@@ -433,7 +493,7 @@ int hnet_filters_step(hnet_filters* f, int n, const int32_t* ids, const double* 
         for (int it = 0; it < I; it++) memcpy(net_out + (size_t)it * n * 72, o.h.net + (size_t)it * c->cfg.max_batch * 72, (size_t)n * 72 * sizeof(float));
     if (updates) memcpy(updates, o.h.upd, (size_t)n * sizeof(int32_t));
     if (state_out) memcpy(state_out, o.h.work, (size_t)n * sizeof(FilterRec));
-    return filters_accepted(f, n, ids, t0, I);
+    return filters_accepted(f, n, ids, gate, t0, I);
 }
 
 int hnet_filters_last_priors(const hnet_filters* f, int n, float* out) {
@@ -649,6 +709,7 @@ int hnet_filters_advance(hnet_filters* f, int n, const int32_t* ids, hnet_filter
     AdvanceResult* d_res = o.d.res;
     hipStream_t st = c->stream;
     hnet_ctx* const ctx[2] = {c, n_s ? filters_iter_ctx(f) : nullptr};
+    const bool photo_gated = filters_photo_gated(f, n_s, hid);
     auto enqueue = [&](uint32_t* flag_now) -> int {
         HIPCHK(c, hipMemcpyAsync(f->d_adv, f->pin_adv, L.bytes, hipMemcpyHostToDevice, st));
         HIPCHK(c, hipMemsetAsync(o.d.upd, 0, (size_t)n_a * sizeof(int32_t), st));
@@ -658,7 +719,7 @@ int hnet_filters_advance(hnet_filters* f, int n, const int32_t* ids, hnet_filter
         HIPCHK(c, launch_filter_select(d_job, n_a, s->n, f->cap, f->d_ring, f->d_meta, f->d_state, d_work, f->d_sel, d_res, st));
         if (n_s) HIPCHK(c, launch_session_gather(s->ring, 2 * s->n, d_pairs, n_s, (uint8_t*)c->stage_prev, (uint8_t*)c->stage_curr, st));
         HIPCHK(c, launch_filter_propagate_adv(d_job, n_a, s->n, f->cap, f->d_state, f->d_params, f->d_sel, d_res, d_work, st));
-        if (const int r = filters_enqueue_iekf(f, ctx, o.d, n_s, d_ids, d_gate, d_seq, n_a, st); r != HNET_OK) return r;     // (the sequence table has a row of n_a per iteration)
+        if (const int r = filters_enqueue_iekf(f, ctx, o.d, n_s, d_ids, d_gate, d_seq, n_a, photo_gated, st); r != HNET_OK) return r;     // (the sequence table has a row of n_a per iteration)
         if (n_s) HIPCHK(c, hipMemcpyAsync(f->pin_out, f->d_out, filters_down_head(f, n_s), hipMemcpyDeviceToHost, st));
         if (state_out) HIPCHK(c, hipMemcpyAsync(f->pin_out + f->off_work, d_work, (size_t)n_a * sizeof(FilterRec), hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipMemcpyAsync(f->pin_out + f->off_res, d_res, (size_t)n_a * sizeof(AdvanceResult), hipMemcpyDeviceToHost, st));
@@ -696,7 +757,7 @@ int hnet_filters_advance(hnet_filters* f, int n, const int32_t* ids, hnet_filter
         }
         if (state_out) memcpy(state_out + i, o.h.work + j, sizeof(FilterRec));
     }
-    return filters_accepted(f, n_s, hid, t_begin, n_s ? I : 0);     // (the stepping sessions are the first n_s of the call's id table)
+    return filters_accepted(f, n_s, hid, gate, t_begin, n_s ? I : 0);     // (the stepping sessions are the first n_s of the call's id table)
 }
 
 int hnet_filters_last_selection(hnet_filters* f, int id, hnet_imu* out, int cap, int* count) {
@@ -807,11 +868,62 @@ int hnet_filters_reset_innovation_stats(hnet_filters* f, int id) {
 
 int hnet_filters_enable_photometric(hnet_filters* f) {
     if (!f) return HNET_ERR_INVALID_ARG;
-    if (f->photo) return fail(f->s->ctx, HNET_ERR_INVALID_ARG, "hnet_filters_enable_photometric: already enabled");
-    const size_t part = photo_partial_count(f->s->ctx->cfg.max_batch, 2 + f->iters) * sizeof(PhotoRec);
-    const int rc = filters_relayout(f, f->innov, true, "hnet_filters_enable_photometric", (void**)&f->d_photo_part, part);
-    if (rc != HNET_OK) return rc;
+    hnet_ctx* c = f->s->ctx;
+    if (f->photo) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_enable_photometric: already enabled");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    // first the gates (none set) and the verdict words of the photometric gate: small, and made here so that hnet_filters_set_photo_gate only writes
+    const int N = f->s->n, B = c->cfg.max_batch;
+    hipError_t e = hipMalloc((void**)&f->d_photo_gate, (size_t)N * sizeof(PhotoGate));
+    if (e == hipSuccess) e = hipMalloc((void**)&f->d_photo_verdict, (size_t)B * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMemsetAsync(f->d_photo_gate, 0, (size_t)N * sizeof(PhotoGate), c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(f->d_photo_verdict, 0, (size_t)B * sizeof(int32_t), c->stream);
+    int rc = e == hipSuccess ? HNET_OK : fail(c, HNET_ERR_DEVICE, std::string("hnet_filters_enable_photometric: ") + hipGetErrorString(e));
+    const size_t part = photo_partial_count(B, 2 + f->iters) * sizeof(PhotoRec);
+    if (rc == HNET_OK) rc = filters_relayout(f, f->innov, true, "hnet_filters_enable_photometric", (void**)&f->d_photo_part, part);      // (synchronises)
+    if (rc != HNET_OK) {
+        drop_dev(f->d_photo_gate); drop_dev(f->d_photo_verdict);
+        return rc;
+    }
+    f->photo_gate.assign(N, PhotoGate{0.0, 0, 0});
+    f->photo_stats.assign(N, hnet_photo_stats{0, 0, 0, 0.0, 0.0});
     f->photo = true;
+    return HNET_OK;
+}
+
+static_assert(sizeof(hnet_photo_residual) == sizeof(PhotoRec) && (int)HNET_PHOTO_DEGENERATE == PHOTO_DEGENERATE && (int)HNET_PHOTO_REJECTED == PHOTO_REJECTED,
+              "hnet_photo_residual is the PhotoRec layout");
+
+int hnet_filters_set_photo_gate(hnet_filters* f, int id, double max_ratio, int32_t min_inside) {
+    if (!f) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = f->s->ctx;
+    if (!f->photo) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_set_photo_gate: photometric records not enabled (hnet_filters_enable_photometric)");
+    if (id < 0 || id >= f->s->n || !(max_ratio >= 0.0) || min_inside < 0 || min_inside > NPIX)
+        return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_set_photo_gate: id out of range, max_ratio negative or NaN, or min_inside outside 0 .. 71680");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    const PhotoGate g{max_ratio, min_inside, 0};
+    HIPCHK(c, hipMemcpyAsync(f->d_photo_gate + id, &g, sizeof g, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    f->photo_gate[id] = g;
+    return HNET_OK;
+}
+
+int hnet_filters_photo_stats(const hnet_filters* f, int id, hnet_photo_stats* out) {
+    if (!f || !out) return HNET_ERR_INVALID_ARG;
+    if (!f->photo || id < 0 || id >= f->s->n) return fail(f->s->ctx, HNET_ERR_INVALID_ARG, "hnet_filters_photo_stats: photometric records not enabled or id out of range");
+    *out = f->photo_stats[id];
+    return HNET_OK;
+}
+
+int hnet_filters_reset_photo_stats(hnet_filters* f, int id) {
+    if (!f) return HNET_ERR_INVALID_ARG;
+    if (!f->photo || id < 0 || id >= f->s->n) return fail(f->s->ctx, HNET_ERR_INVALID_ARG, "hnet_filters_reset_photo_stats: photometric records not enabled or id out of range");
+    f->photo_stats[id] = hnet_photo_stats{0, 0, 0, 0.0, 0.0};
+    return HNET_OK;
+}
+
+int hnet_filters_set_photo_gate_taps(hnet_filters* f, int from_global) {
+    if (!f) return HNET_ERR_INVALID_ARG;
+    f->photo_taps_global = from_global != 0;
     return HNET_OK;
 }
 

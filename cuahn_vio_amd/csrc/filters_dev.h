@@ -116,9 +116,10 @@ static_assert(sizeof(InnovRec) == 18 * sizeof(double), "InnovRec must be 17 pack
 constexpr int INNOV_THREADS = 64;
 // iteration `it` of a step of n sessions, between its forward and its filter_update_kernel: writes innov[it * n + b] and, on a rejection, 0 to gate[b]
 // (the step's device copy, uploaded again by every attempt).  max_nis: [n_sessions], <= 0 = no gate.  Reads innov[(it - 1) * n + b] for it > 0.
+// photo_verdict: null, or the [n] verdict words of photo_gate_kernel (photo_dev.h) in a step with a photometric gate: non-zero -> SKIPPED.
 hipError_t launch_filter_innovation(const int32_t* ids, int n, int n_sessions, const FilterParams* params, const FilterRec* work, const float* net72,
                                     const double* prior_cam, const double* max_nis, int32_t* gate, const int32_t* updates, int it, InnovRec* innov,
-                                    hipStream_t s);
+                                    const int32_t* photo_verdict, hipStream_t s);
 
 }  // namespace hnet
 #endif  // HNET_FILTERS_DEV_H

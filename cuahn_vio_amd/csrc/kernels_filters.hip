@@ -637,11 +637,14 @@ static_assert(offsetof(InnovRec, nis) == 16 * sizeof(double) && offsetof(InnovRe
 // serial sum in the header's order.  Flags: a session whose earlier update of this step found S singular (updates[b] < 0), or whose earlier record is
 // REJECTED / SKIPPED, is SKIPPED; a closed reference gate otherwise gives NONE; both leave r, s_diag and nis zero.  A rejection writes 0 to gate[b],
 // which is what makes filter_update_kernel skip this and the later updates and still do the last iteration's reset.  Writes innov[it * n + b] and
-// gate[b] only.
+// gate[b] only.  PHOTO (a step with a photometric gate): verdict[b] != 0 says photo_gate_kernel refused the estimate of this or an earlier
+// iteration, and the record is SKIPPED whatever the record before it says; without PHOTO the pointer is not read and the kernel is what it was.
+template <bool PHOTO>
 __global__ __launch_bounds__(INNOV_THREADS) void filter_innovation_kernel(const int32_t* __restrict__ ids, int n, int n_sessions, const FilterParams* __restrict__ params,
                                                                           const FilterRec* __restrict__ work, const float* __restrict__ net72,
                                                                           const double* __restrict__ prior_cam, const double* __restrict__ max_nis,
-                                                                          int32_t* gate, const int32_t* __restrict__ updates, int it, InnovRec* innov) {
+                                                                          int32_t* gate, const int32_t* __restrict__ updates, int it, InnovRec* innov,
+                                                                          const int32_t* __restrict__ verdict) {
     __shared__ double A[64], V[64], r[8], sd[8], y[8];
     const int b = blockIdx.x, t = threadIdx.x;
     if (b >= n) return;
@@ -651,6 +654,7 @@ __global__ __launch_bounds__(INNOV_THREADS) void filter_innovation_kernel(const 
     double* ow = reinterpret_cast<double*>(out);
     int flag = hnet_ekf::INNOV_USED;
     if (updates[b] < 0) flag = hnet_ekf::INNOV_SKIPPED;
+    else if (PHOTO && verdict[b] != 0) flag = hnet_ekf::INNOV_SKIPPED;
     else if (gate[b] == 0) {
         const int prev = it > 0 ? innov[(size_t)(it - 1) * n + b].flag : hnet_ekf::INNOV_NONE;
         flag = prev == hnet_ekf::INNOV_REJECTED || prev == hnet_ekf::INNOV_SKIPPED ? hnet_ekf::INNOV_SKIPPED : hnet_ekf::INNOV_NONE;
@@ -722,10 +726,14 @@ __global__ __launch_bounds__(INNOV_THREADS) void filter_innovation_kernel(const 
 
 hipError_t launch_filter_innovation(const int32_t* ids, int n, int n_sessions, const FilterParams* params, const FilterRec* work, const float* net72,
                                     const double* prior_cam, const double* max_nis, int32_t* gate, const int32_t* updates, int it, InnovRec* innov,
-                                    hipStream_t s) {
+                                    const int32_t* photo_verdict, hipStream_t s) {
     if (n < 1 || it < 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(filter_innovation_kernel, dim3((unsigned)n), dim3(INNOV_THREADS), 0, s, ids, n, n_sessions, params, work, net72, prior_cam, max_nis, gate,
-                       updates, it, innov);
+    if (photo_verdict)
+        hipLaunchKernelGGL(filter_innovation_kernel<true>, dim3((unsigned)n), dim3(INNOV_THREADS), 0, s, ids, n, n_sessions, params, work, net72, prior_cam, max_nis,
+                           gate, updates, it, innov, photo_verdict);
+    else
+        hipLaunchKernelGGL(filter_innovation_kernel<false>, dim3((unsigned)n), dim3(INNOV_THREADS), 0, s, ids, n, n_sessions, params, work, net72, prior_cam, max_nis,
+                           gate, updates, it, innov, photo_verdict);
     return hipGetLastError();
 }
 

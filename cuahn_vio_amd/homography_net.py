@@ -765,6 +765,23 @@ class HnetFilters:
         self._check(self._L.hnet_filters_last_photometric(self._f, int(n), out.ctypes.data))
         return out
 
+    def set_photo_gate(self, id, max_ratio, min_inside=0):
+        """session id's photometric gate (needs enable_photometric): an update is refused when its estimate's mean residual inside the image exceeds
+        max_ratio times the prior's, or the estimate is degenerate or has fewer than max(min_inside, 1) pixels inside; 0 = off"""
+        self._check(self._L.hnet_filters_set_photo_gate(self._f, int(id), float(max_ratio), int(min_inside)))
+
+    def photo_stats(self, id):
+        st = _capi.PhotoStats()
+        self._check(self._L.hnet_filters_photo_stats(self._f, int(id), C.byref(st)))
+        return {"judged": st.judged, "rejected": st.rejected, "degenerate": st.degenerate, "sum_ratio": st.sum_ratio, "max_ratio": st.max_ratio}
+
+    def reset_photo_stats(self, id):
+        self._check(self._L.hnet_filters_reset_photo_stats(self._f, int(id)))
+
+    def set_photo_gate_taps(self, from_global):
+        """tools: the single-candidate launches of a gated step read img2 from global memory (True) or stage it in LDS (False); same records"""
+        self._check(self._L.hnet_filters_set_photo_gate_taps(self._f, 1 if from_global else 0))
+
     def last_priors(self, n):
         """the fp32 priors [iters, n, 8] the forwards of the last step (of n sessions; another n is refused) read"""
         out = np.zeros((self.iters, int(n), 8), np.float32)

@@ -495,7 +495,8 @@ double hnet_filters_last_predict_cov_device_ms(hnet_filters* f);
  *   HNET_INNOV_USED      the update was applied.
  *   HNET_INNOV_REJECTED  the NIS exceeded the session's gate.
  *   HNET_INNOV_SINGULAR  S was singular (nis is NaN).
- *   HNET_INNOV_SKIPPED   after an earlier rejection or singular S in the same step.  r, s_diag and nis are zero.
+ *   HNET_INNOV_SKIPPED   after an earlier rejection or singular S in the same step, or a photometric rejection at this or an earlier iteration
+ *                        (hnet_filters_set_photo_gate).  r, s_diag and nis are zero.
  * Without hnet_filters_enable_innovations a step and an advance launch exactly what they launched before, and with it and no gate set they compute
  * the same states, priors, network outputs and updates, bit for bit. */
 typedef struct hnet_innovation { double r[8], s_diag[8], nis; int32_t iteration, flag; } hnet_innovation;
@@ -527,9 +528,10 @@ typedef struct hnet_photo_residual {
     double  sum;          /* sum over all 71 680 pixels of e = |warp(img2, H)(u, v) - img1(u, v)| * 255, zeros padding: the reference's map, summed */
     double  sum_inside;   /* sum of e over the pixels whose sampling position lies inside img2 */
     int32_t n_inside;     /* their number */
-    int32_t flags;        /* HNET_PHOTO_DEGENERATE: H has a non-finite entry (every sample is 0, n_inside = 0) */
+    int32_t flags;        /* HNET_PHOTO_DEGENERATE: H has a non-finite entry (every sample is 0, n_inside = 0); HNET_PHOTO_REJECTED: the session's
+                           * photometric gate refused this estimate (a filters step only, hnet_filters_set_photo_gate) */
 } hnet_photo_residual;
-enum { HNET_PHOTO_DEGENERATE = 1 };
+enum { HNET_PHOTO_DEGENERATE = 1, HNET_PHOTO_REJECTED = 2 };
 enum { HNET_PHOTO_MAX_CANDIDATES = 66 };
 /* operator call, host pointers: img1 / img2 u8 [n][224][320], offsets_px [n][m][8], out [n][m]; map_out NULL or float [n][m][224][320] (the map itself).
  * 1 <= n <= max_batch, 1 <= m <= 66 (HNET_ERR_CAPACITY / HNET_ERR_INVALID_ARG otherwise; an error writes nothing).  One upload, one download, one
@@ -543,13 +545,41 @@ int  hnet_sessions_photo_residual(hnet_sessions* s, int n, const int32_t* ids, c
 /* once per filters object (HNET_ERR_INVALID_ARG on a second call; works with hnet_filters_enable_innovations in either order): from now on every step
  * and advance also produces, per stepping session, 2 + max_iekf_iteration records on the step's own frame pair - [0] zero offsets (no motion), [1] the
  * fp32 prior of iteration 0 (what hnet_filters_last_priors reports, whether or not use_prior let the forward read it), [2 + it] the packed mean of
- * forward `it` - inside the call's one download, two launches after the last update.  Nothing is gated on them, and the states, priors, network
- * outputs, updates, innovation records and sequence numbers are what they are without the call, bit for bit.  hnet_filters_last_priors has nothing
- * to describe until the next step. */
+ * forward `it` - inside the call's one download, two launches after the last update.  Unless a photometric gate is set (hnet_filters_set_photo_gate,
+ * below) nothing is gated on them, and the states, priors, network outputs, updates, innovation records and sequence numbers are what they are
+ * without the call, bit for bit.  hnet_filters_last_priors has nothing to describe until the next step. */
 int  hnet_filters_enable_photometric(hnet_filters* f);
 /* the records [n][2 + max_iekf_iteration] of the last step (n: its n) or advance (n: its STEPPED sessions, in the order listed).  A wrong n, or a last
  * call that ran without hnet_filters_enable_photometric (or in which nothing stepped): HNET_ERR_INVALID_ARG, nothing written */
 int  hnet_filters_last_photometric(const hnet_filters* f, int n, hnet_photo_residual* out);
+/* The photometric gate, per session and off by default: refuse an update whose estimate explains the frame pair WORSE than the IMU prior did, before it
+ * is absorbed.  The rule is hnet_ekf::photo_reject and the loop hnet_ekf::iterated_update_photo_gated (include/hnet_ekf.h): at every iteration whose
+ * reference gate is open (VioManager.cpp:257) and that no singular S, NIS rejection or photometric rejection of the step precedes, record [2 + it] is
+ * judged against record [1].  Refused: an estimate that is DEGENERATE or has fewer than max(min_inside, 1) pixels inside; otherwise, given a prior record
+ * that is not DEGENERATE and has that many pixels inside, an estimate with
+ *   est.sum_inside * prior.n_inside > (max_ratio * prior.sum_inside) * est.n_inside          (a NaN on either side does not refuse).
+ * A refusal sets HNET_PHOTO_REJECTED in record [2 + it]; that update and all later updates of the step are skipped for that session, updates already
+ * applied stay, every forward still runs (the sequence number advances as always), the offsets are reset, updates[i] counts what was applied, and the
+ * innovation records from that iteration on are HNET_INNOV_SKIPPED.  The photometric gate comes before the NIS gate: a refused estimate has no NIS.
+ * A step or advance in which at least one STEPPING session has a gate forms the records per iteration, between the forward and the update they guard
+ * (two launches per iteration; img2 is read once per iteration) instead of after the last update, for all its stepping sessions: the records have the
+ * same bits either way, and so have the states, outputs and records of the sessions without a gate.  hnet_filters_last_timing's device window then
+ * includes the photometric launches, which without a gate lie behind it.  Still one upload, one download and one synchronisation; an overflow or
+ * chain-timeout repeat forms every verdict again.
+ * max_ratio = 0 is off.  HNET_ERR_INVALID_ARG, nothing changed: a negative or NaN max_ratio, min_inside outside 0 .. 71 680, a bad id, a call before
+ * hnet_filters_enable_photometric. */
+int  hnet_filters_set_photo_gate(hnet_filters* f, int id, double max_ratio, int32_t min_inside);
+/* per session, accumulated on the host from the records of every accepted step or advance with photometric records, gated or not (a repeated attempt
+ * never counts twice).  judged: the estimate records [2 + it] of iterations whose reference gate was open and that no singular S, NIS rejection or
+ * photometric rejection preceded; rejected, degenerate: those among them with HNET_PHOTO_REJECTED, HNET_PHOTO_DEGENERATE.  sum_ratio, max_ratio: over
+ * the judged records for which ratio = (est.sum_inside / est.n_inside) / (prior.sum_inside / prior.n_inside) is defined and finite (neither record
+ * DEGENERATE, both n_inside >= 1), in host arithmetic. */
+typedef struct hnet_photo_stats { int64_t judged, rejected, degenerate; double sum_ratio, max_ratio; } hnet_photo_stats;
+int  hnet_filters_photo_stats(const hnet_filters* f, int id, hnet_photo_stats* out);
+int  hnet_filters_reset_photo_stats(hnet_filters* f, int id);
+/* tools: where the single-candidate launch of iterations 1 .. of a gated step takes its taps of img2 from: 0 LDS (the pair staged per workgroup), 1 global
+ * memory.  The records do not depend on it (tests/test_gpu_filters_photo_gate.py); the default is the one DESIGN 7j measured as faster. */
+int  hnet_filters_set_photo_gate_taps(hnet_filters* f, int from_global);
 
 int hnet_synchronize(hnet_ctx* ctx, void* stream);
 int hnet_last_timing(const hnet_ctx* ctx, hnet_timing* out);

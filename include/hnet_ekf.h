@@ -477,7 +477,7 @@ enum { INNOV_NONE = 0,                 /* the reference's gate (VioManager.cpp:2
        INNOV_USED = 1,                 /* the update was applied */
        INNOV_REJECTED = 2,             /* the NIS exceeded max_nis: this update and the step's later ones are skipped */
        INNOV_SINGULAR = 3,             /* S was singular: update() refuses it */
-       INNOV_SKIPPED = 4 };            /* after an earlier rejection or singular S in the same step */
+       INNOV_SKIPPED = 4 };            /* after an earlier rejection or singular S in the same step, or a photometric rejection at this or an earlier iteration */
 /* r: the innovation mean / 159.5 - prior; s_diag: the diagonal of S = H P H^T + k_net_cov C / 159.5^2; nis: NaN when S is singular.
  * A NONE or SKIPPED record holds zeros in r, s_diag and nis: nothing was formed for it. */
 struct Innovation {
@@ -542,6 +542,96 @@ inline int iterated_update_gated(State& s, Net& net, int max_iekf_iteration, dou
             for (int i = 0; i < 8; i++) {
                 mean[i] = m(i, 0);
                 for (int j = 0; j < 8; j++) cov[i * 8 + j] = C(i, j);
+            }
+            innovation(s, mean, cov, prior_cam, k_net_cov, rec[it]);
+            if (max_nis > 0.0 && rec[it].nis > max_nis) {
+                rec[it].flag = INNOV_REJECTED;
+                skip = true;
+                continue;
+            }
+            if (!update(s, mean, cov, prior_cam, k_net_cov, it != max_iekf_iteration - 1)) {
+                for (int k = it + 1; k < max_iekf_iteration; k++) rec[k].flag = INNOV_SKIPPED;
+                break;
+            }
+            done++;
+        }
+    }
+    reset_4pt_offset(s);
+    return done;
+}
+
+/* ---- an opt-in photometric gate: refuse an update whose estimate explains the frame pair worse than the IMU prior did.  A record is the reference's
+ * error map |warp(img2, H) - img1| * 255 (model_to_trace.py:319-327) summed for H = (float) dlt_solve(p4 + offsets): `sum` over all pixels,
+ * `sum_inside` / `n_inside` over the pixels that sample inside img2 (include/hnet.h hnet_photo_residual; the device forms them in csrc/kernels_photo.hip).
+ * The reference has no such test (UpdaterHNet.cpp:28-61 applies every measurement); like the NIS gate these are additions. */
+enum { PHOTO_DEGENERATE = 1,           /* H has a non-finite entry: every sample is 0, n_inside = 0 */
+       PHOTO_REJECTED = 2 };           /* photo_reject refused this estimate: its update and the call's later ones are skipped */
+struct PhotoRecord {
+    double sum, sum_inside;
+    int n_inside, flags;
+};
+
+/* The rule.  max_ratio <= 0 (or NaN): never.  An estimate that is DEGENERATE or has fewer than max(min_inside, 1) pixels inside is refused; otherwise a
+ * prior that is DEGENERATE or has fewer than that inside gives nothing to compare with: accepted.  Otherwise refused iff the estimate's mean residual
+ * inside exceeds max_ratio times the prior's, compared on products, est.sum_inside * prior.n_inside > (max_ratio * prior.sum_inside) * est.n_inside:
+ * no quotient and no addition, so host and device round it identically whatever the contraction setting.  A NaN on either side does not refuse (as a
+ * NaN NIS does not). */
+inline bool photo_reject(const PhotoRecord& prior, const PhotoRecord& est, double max_ratio, int min_inside) {
+    if (!(max_ratio > 0.0)) return false;
+    const int need = min_inside > 1 ? min_inside : 1;
+    if ((est.flags & PHOTO_DEGENERATE) || est.n_inside < need) return true;
+    if ((prior.flags & PHOTO_DEGENERATE) || prior.n_inside < need) return false;
+    const double lhs = est.sum_inside * (double)prior.n_inside;
+    const double rhs = (max_ratio * prior.sum_inside) * (double)est.n_inside;
+    return lhs > rhs;
+}
+
+/* iterated_update_gated with the photometric gate in front of the NIS gate.  photo(off_px): the PhotoRecord of 8 corner offsets in pixels (the fp32
+ * values the device works on, widened) on the current frame pair.  prec[1 + max_iekf_iteration]: prec[0] the record of iteration 0's fp32 prior,
+ * prec[1 + it] the record of forward it's mean where it was judged; records never formed are zeros.  max_ratio <= 0: `photo` is never called, prec is
+ * zeros, and state, return value, rec and the calls made to `net` are iterated_update_gated's, bit for bit.  With a gate: at every iteration whose
+ * reference gate is open and that no earlier singular S, NIS rejection or photometric rejection of the call precedes, the estimate's record is formed
+ * and photo_reject applied against prec[0]; on rejection the record takes PHOTO_REJECTED, this update and every later one of the call are skipped
+ * (rec[it] and the later open iterations SKIPPED), updates already applied stay, the network still runs in every iteration and the offsets are reset
+ * as always.  Only an estimate that passes goes on to the NIS record, the NIS gate and the update. */
+template <class Net, class Vec8, class Photo>
+inline int iterated_update_photo_gated(State& s, Net& net, int max_iekf_iteration, double k_net_cov, Vec8& prior_px_vec, double time_stamp, double max_nis,
+                                       Innovation* rec, Photo& photo, double max_ratio, int min_inside, PhotoRecord* prec) {
+    int done = 0;
+    bool skip = false;
+    const bool gated = max_ratio > 0.0;
+    for (int it = 0; it < max_iekf_iteration; it++) {
+        std::memset(&rec[it], 0, sizeof rec[it]);
+        rec[it].flag = INNOV_NONE;
+    }
+    std::memset(prec, 0, sizeof(PhotoRecord) * (size_t)(1 + max_iekf_iteration));
+    for (int it = 0; it < max_iekf_iteration; it++) {
+        double prior_px[8], prior_cam[8];
+        prior_pixels(s, prior_px, prior_cam);
+        for (int i = 0; i < 8; i++) prior_px_vec[i] = prior_px[i];
+        if (gated && it == 0) {
+            double p32[8];
+            for (int i = 0; i < 8; i++) p32[i] = (double)(float)prior_px[i];
+            prec[0] = photo(p32);
+        }
+        net.network_inference(prior_px_vec, it);
+        if (net.get_latest_inference_time() == time_stamp && net.img_counter > 10) {
+            if (skip) { rec[it].flag = INNOV_SKIPPED; continue; }
+            const auto m = net.get_pred_mean();
+            const auto C = net.get_pred_Cov();
+            double mean[8], cov[64];
+            for (int i = 0; i < 8; i++) {
+                mean[i] = m(i, 0);
+                for (int j = 0; j < 8; j++) cov[i * 8 + j] = C(i, j);
+            }
+            if (gated) {
+                prec[1 + it] = photo(mean);
+                if (photo_reject(prec[0], prec[1 + it], max_ratio, min_inside)) {
+                    prec[1 + it].flags |= PHOTO_REJECTED;
+                    rec[it].flag = INNOV_SKIPPED;
+                    skip = true;
+                    continue;
+                }
             }
             innovation(s, mean, cov, prior_cam, k_net_cov, rec[it]);
             if (max_nis > 0.0 && rec[it].nis > max_nis) {

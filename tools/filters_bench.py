@@ -32,7 +32,10 @@ hnet_sessions_infer, the prior of forward `it` being the one the header hands it
    python tools/filters_bench.py --predict-cov [--k 1,8,64,256] [--ticks 20] [--warmup 3] [--threads 1,16]
    python tools/filters_bench.py --innov [--k 1,8,64,256] [--iters 1,3] [--ticks 20] [--warmup 3]
 --photo is a mode of its own (photometric residual records): step and advance with the records off and on, in one process on the same inputs.
-   python tools/filters_bench.py --photo [--k 1,8,64,256] [--iters 1,3] [--ticks 20] [--warmup 3]"""
+   python tools/filters_bench.py --photo [--k 1,8,64,256] [--iters 1,3] [--ticks 20] [--warmup 3]
+--photo-gate runs the same ticks with the photometric gate next to them: records off, records on, a gate that never rejects (max_ratio 1e30)
+with the single-candidate launches reading img2 through LDS (pass) and from global memory (pass_global), and a gate that rejects every update.
+   python tools/filters_bench.py --photo-gate [--k 1,8,64,256] [--iters 1,3] [--ticks 20] [--warmup 3]"""
 import argparse
 import ctypes as C
 import json
@@ -372,18 +375,21 @@ def innov_mode(a):
             sh.close(); eh.close()
 
 
-def photo_mode(a):
+def photo_mode(a, gate=False):
     """photometric residual records: per (K, iterations) two filters objects for hnet_filters_step and two fed ones for hnet_filters_advance, each
     on its own context, with the records off and on; every tick runs all four on the same frames and IMU window, in rotating order.  The records are
     launched behind the event that closes hnet_filters_last_timing's window, so the wall time of the call (it ends in the call's synchronisation) is the
-    figure that contains them; the event time shows that the window itself did not move."""
+    figure that contains them; the event time shows that the window itself did not move.
+    gate: three more objects per call - every session with a gate of max_ratio 1e30 (never rejects; the records are then formed per iteration,
+    inside the window) in both tap forms, and with a gate of 1e-30 (every estimate whose reference gate is open is refused at iteration 0)."""
     from cuahn_vio_amd import _capi, replay, weights
     from cuahn_vio_amd.homography_net import HnetEngine, HnetFilters, HnetSessions
     blob = weights.pack_state_dict(weights.synthetic_state(0))
     fx = replay.load_fixture("indoor_forward_7")
     pool = np.stack([replay.render_frame(fx, 100 + j) for j in range(16)])
     kw = dict(variant="prior3", mc_samples=16, dropout_p=0.05, mc_seed=1)
-    modes = ("off", "on")
+    modes = ("off", "on", "pass", "pass_global", "reject") if gate else ("off", "on")
+    ratio = {"pass": 1e30, "pass_global": 1e30, "reject": 1e-30}
 
     def pct(x, q):
         return round(float(np.percentile(x, q)), 3)
@@ -401,8 +407,12 @@ def photo_mode(a):
                     e = HnetEngine(blob, max_batch=K, **kw)
                     s = HnetSessions(e, K)
                     f = HnetFilters(s, iters)
-                    if m == "on":
+                    if m != "off":
                         f.enable_photometric()
+                    if m in ratio:
+                        f.set_photo_gate_taps(m == "pass_global")
+                        for i in range(K):
+                            f.set_photo_gate(i, ratio[m])
                     if kind == "advance":
                         f.enable_feed(256)
                     for i in range(K):
@@ -452,6 +462,13 @@ def photo_mode(a):
                 out[f"{kind}_{m}_event_ms_p50"], out[f"{kind}_{m}_event_ms_p10"], out[f"{kind}_{m}_event_ms_p90"] = pct(ev, 50), pct(ev, 10), pct(ev, 90)
             for kind in ("step", "advance"):
                 out[f"{kind}_on_minus_off_wall_us"] = round(1e3 * (float(np.median(wall[kind, "on"])) - float(np.median(wall[kind, "off"]))), 1)
+            if gate:
+                for kind in ("step", "advance"):
+                    on = float(np.median(wall[kind, "on"]))
+                    for m in ("pass", "pass_global", "reject"):
+                        out[f"{kind}_{m}_minus_on_wall_us"] = round(1e3 * (float(np.median(wall[kind, m])) - on), 1)
+                out["rejected_per_session"] = {m: objs["step", m][2].photo_stats(0)["rejected"] for m in ("on", "pass", "reject")}
+                out["judged_per_session"] = {m: objs["step", m][2].photo_stats(0)["judged"] for m in ("on", "pass", "reject")}
             out["mean_inside_residual_identity_prior_estimates"] = [round(float(x), 3) for x in np.mean(res, axis=0)]
             print(json.dumps(out), flush=True)
             for (e, s, f) in objs.values():
@@ -470,6 +487,7 @@ def main():
     ap.add_argument("--predict-cov", action="store_true")
     ap.add_argument("--innov", action="store_true")
     ap.add_argument("--photo", action="store_true")
+    ap.add_argument("--photo-gate", action="store_true")
     ap.add_argument("--iter-variant", default=None)
     ap.add_argument("--iter-mc", type=int, default=8)
     ap.add_argument("--iter-p", type=float, default=0.1)
@@ -480,8 +498,8 @@ def main():
         return predict_cov_mode(a)
     if a.innov:
         return innov_mode(a)
-    if a.photo:
-        return photo_mode(a)
+    if a.photo or a.photo_gate:
+        return photo_mode(a, gate=a.photo_gate)
     from cuahn_vio_amd import _capi, replay, weights
     from cuahn_vio_amd.homography_net import HnetEngine, HnetFilters, HnetSessions
     ref = build_ref()
