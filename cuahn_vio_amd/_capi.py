@@ -45,6 +45,7 @@ SYMBOLS = [
     "hnet_filters_reset_innovation_stats",
     "hnet_op_photo_residual", "hnet_sessions_photo_residual", "hnet_filters_enable_photometric", "hnet_filters_last_photometric",
     "hnet_filters_set_photo_gate", "hnet_filters_photo_stats", "hnet_filters_reset_photo_stats", "hnet_filters_set_photo_gate_taps",
+    "hnet_photo_align_default_opts", "hnet_op_photo_align", "hnet_sessions_photo_align", "hnet_last_photo_align_device_ms",
 ]
 # hnet_filters_advance's status per listed session (include/hnet.h HNET_ADV_*)
 ADV_STEPPED, ADV_WAIT_IMU, ADV_WAIT_INIT, ADV_INITIALIZED, ADV_PROPAGATED, ADV_NO_FRAME = range(6)
@@ -114,6 +115,30 @@ PHOTO_RESIDUAL_DTYPE = _np.dtype([("sum", "<f8"), ("sum_inside", "<f8"), ("n_ins
 PHOTO_DEGENERATE = 1
 PHOTO_REJECTED = 2
 PHOTO_MAX_CANDIDATES = 66
+
+# hnet_photo_align: one record per aligned frame pair; flags: ALIGN_* (include/hnet.h HNET_ALIGN_*)
+PHOTO_ALIGN_DTYPE = _np.dtype([("offsets_px", "<f4", 8), ("mse0", "<f8"), ("mse", "<f8"), ("n_valid0", "<i4"), ("n_valid", "<i4"), ("trials", "<i4"),
+                               ("accepted", "<i4"), ("flags", "<i4"), ("pad", "<i4"), ("lambda", "<f8"), ("grad", "<f8", 8), ("info", "<f8", (8, 8))])
+assert PHOTO_ALIGN_DTYPE.itemsize == 656      # (pad: the C struct's alignment gap, written as 0 - named, so that numpy copies it and records compare byte for byte)
+ALIGN_CONVERGED, ALIGN_SINGULAR, ALIGN_DEGENERATE, ALIGN_FEW_PIXELS = 1, 2, 4, 8
+ALIGN_MAX_ITERATIONS = 32
+
+
+class PhotoAlignOpts(C.Structure):
+    """hnet_photo_align_opts: trials at the most, valid pixels a point needs, initial damping, convergence threshold in pixels"""
+    _fields_ = [("max_iterations", C.c_int32), ("min_valid", C.c_int32), ("lambda0", C.c_double), ("eps_px", C.c_double)]
+
+
+def photo_align_opts(**kw):
+    """the defaults of hnet_photo_align_default_opts with the given fields replaced"""
+    o = PhotoAlignOpts()
+    lib().hnet_photo_align_default_opts(C.byref(o))
+    for k, v in kw.items():
+        if k not in ("max_iterations", "min_valid", "lambda0", "eps_px"):
+            raise TypeError(f"hnet_photo_align_opts has no field {k!r}")
+        setattr(o, k, v)
+    return o
+
 
 # the block-4 input planes (csrc/kernels.h B4_*): [plane][pair][B4_HP][B4_WP] dwords, pixel (u, v) at row v + B4_PADY, column u + B4_PADX
 # (tests/cpp/b41_tap_check.cpp pins these numbers to the header)
@@ -269,6 +294,12 @@ def lib():
     L.hnet_filters_photo_stats.argtypes = [vp, C.c_int, C.POINTER(PhotoStats)]
     L.hnet_filters_reset_photo_stats.argtypes = [vp, C.c_int]
     L.hnet_filters_set_photo_gate_taps.argtypes = [vp, C.c_int]
+    L.hnet_photo_align_default_opts.argtypes = [C.POINTER(PhotoAlignOpts)]
+    L.hnet_photo_align_default_opts.restype = None
+    L.hnet_op_photo_align.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp]
+    L.hnet_sessions_photo_align.argtypes = [vp, C.c_int, vp, vp, vp, vp]
+    L.hnet_last_photo_align_device_ms.argtypes = [vp]
+    L.hnet_last_photo_align_device_ms.restype = C.c_double
     for name in SYMBOLS:
         getattr(L, name)   # AttributeError here = the library does not export what include/hnet.h declares
     _lib = L

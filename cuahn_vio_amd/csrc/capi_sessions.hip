@@ -360,4 +360,29 @@ int hnet_sessions_photo_residual(hnet_sessions* s, int n, const int32_t* ids, co
     return HNET_OK;
 }
 
+// ---- photometric alignment (include/hnet.h hnet_photo_align) on the sessions' current pairs; read-only like the records above ----
+
+int hnet_sessions_photo_align(hnet_sessions* s, int n, const int32_t* ids, const float* offsets0_px, const hnet_photo_align_opts* opts, hnet_photo_align* out) {
+    if (!s) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = s->ctx;
+    if (!offsets0_px || !out) return fail(c, HNET_ERR_INVALID_ARG, "hnet_sessions_photo_align: offsets / out");
+    int rc = photo_align_check_opts(c, opts, "hnet_sessions_photo_align");
+    if (rc == HNET_OK) rc = sessions_check_ids(s, n, ids);
+    if (rc == HNET_OK) rc = sessions_check_pairs(s, n, ids);
+    if (rc != HNET_OK) return rc;
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    // ONE upload {offsets [n][8] f32 | pair table [n][2] i32}; nothing of the sessions' own tables, events or bookkeeping is touched
+    const size_t off_bytes = (size_t)n * 8 * sizeof(float), up = off_bytes + (size_t)n * 8;
+    std::vector<uint8_t> h_in(up);
+    memcpy(h_in.data(), offsets0_px, off_bytes);
+    for (int i = 0; i < n; i++) sessions_pair(s, ids[i], reinterpret_cast<int32_t*>(h_in.data() + off_bytes) + 2 * i);
+    DevTemps t;
+    uint8_t* d_in = nullptr;
+    HIPCHK(c, t.alloc(&d_in, up));
+    hipStream_t st = c->stream;
+    HIPCHK(c, hipMemcpyAsync(d_in, h_in.data(), up, hipMemcpyHostToDevice, st));
+    HIPCHK(c, launch_session_gather(s->ring, 2 * s->n, reinterpret_cast<const int32_t*>(d_in + off_bytes), n, (uint8_t*)c->stage_prev, (uint8_t*)c->stage_curr, st));
+    return photo_align_run(c, (const uint8_t*)c->stage_prev, (const uint8_t*)c->stage_curr, n, reinterpret_cast<const float*>(d_in), *opts, out);
+}
+
 }  // extern "C"

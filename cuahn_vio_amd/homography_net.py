@@ -263,6 +263,24 @@ class HnetEngine:
                                                       emap.ctypes.data if want_map else None))
         return (out, emap) if want_map else out
 
+    def op_photo_align(self, img1, img2, offsets0, **opts):
+        """photometric alignment (hnet_op_photo_align): img1 / img2 uint8 [n, 224, 320], start offsets [n, 8] pixels; opts: the fields of
+        hnet_photo_align_opts (max_iterations, min_valid, lambda0, eps_px) -> records [n] of _capi.PHOTO_ALIGN_DTYPE"""
+        a = np.ascontiguousarray(img1, dtype=np.uint8).reshape(-1, IMG_H, IMG_W)
+        b = np.ascontiguousarray(img2, dtype=np.uint8).reshape(-1, IMG_H, IMG_W)
+        n = a.shape[0]
+        if b.shape[0] != n:
+            raise ValueError("img1 and img2 must hold the same number of frames")
+        off = np.ascontiguousarray(offsets0, dtype=np.float32).reshape(n, 8)
+        o = _capi.photo_align_opts(**opts)
+        out = np.zeros(n, _capi.PHOTO_ALIGN_DTYPE)
+        check(self._h, self._L.hnet_op_photo_align(self._h, a.ctypes.data, b.ctypes.data, n, off.ctypes.data, C.addressof(o), out.ctypes.data))
+        return out
+
+    def last_photo_align_device_ms(self):
+        """device time of the launch sequence of the last alignment call on this context (operator or sessions), milliseconds"""
+        return float(self._L.hnet_last_photo_align_device_ms(self._h))
+
     def op_conv(self, layer, x):
         from .weights import CONV_LAYERS
         x = np.ascontiguousarray(x, dtype=np.float32)
@@ -548,6 +566,16 @@ class HnetSessions:
         off = np.ascontiguousarray(offsets, dtype=np.float32).reshape(n, -1, 8)
         out = np.zeros((n, off.shape[1]), _capi.PHOTO_RESIDUAL_DTYPE)
         self._check(self._L.hnet_sessions_photo_residual(self._s, n, ids.ctypes.data, _fp(off), off.shape[1], out.ctypes.data))
+        return out
+
+    def photo_align(self, ids, offsets0, **opts):
+        """photometric alignment of the listed sessions' current pairs from offsets0 [n, 8] pixels -> [n] of _capi.PHOTO_ALIGN_DTYPE; read-only
+        (hnet_sessions_photo_align); opts as HnetEngine.op_photo_align"""
+        ids, n = self._ids(ids)
+        off = np.ascontiguousarray(offsets0, dtype=np.float32).reshape(n, 8)
+        o = _capi.photo_align_opts(**opts)
+        out = np.zeros(n, _capi.PHOTO_ALIGN_DTYPE)
+        self._check(self._L.hnet_sessions_photo_align(self._s, n, ids.ctypes.data, off.ctypes.data, C.addressof(o), out.ctypes.data))
         return out
 
     def image_count(self, id):

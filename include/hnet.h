@@ -581,6 +581,54 @@ int  hnet_filters_reset_photo_stats(hnet_filters* f, int id);
  * memory.  The records do not depend on it (tests/test_gpu_filters_photo_gate.py); the default is the one DESIGN 7j measured as faster. */
 int  hnet_filters_set_photo_gate_taps(hnet_filters* f, int from_global);
 
+/* ---- photometric alignment: which way a homography is wrong, how strongly the frame pair constrains it, and a better one -----------------------------
+ * Forward-additive Lucas-Kanade / Levenberg-Marquardt on the eight corner offsets x (pixels, ul bl br ur), on the device (csrc/kernels_photo_align.hip),
+ * minimising the squared form of the residual hnet_photo_residual sums.  The quantity (the shared code is include/hnet_photo_align.h):
+ *   H(x) = (float) dlt_solve(p4 + x) as for the records; pixel (u, v) samples img2 at (ix, iy) = (X / Z, Y / Z), the records' exact sampler.
+ *   A pixel is VALID when 0 <= ix < 319 and 0 <= iy < 223, so that every one of its four bilinear taps is a pixel of img2.  This is deliberately stricter
+ *   than the records' "inside": the zero padding puts a false edge of full contrast around the image, which drags a minimiser away from the truth.
+ *   r = (w - img1 / 255) * 255 in grey levels, w the bilinear sample (|r| has the bits of the error map); with taps a b / c d and fractions fx, fy
+ *   gx = ((b - a)(1 - fy) + (d - c) fy) * 255, gy = ((c - a)(1 - fx) + (d - b) fx) * 255, q = gx ix + gy iy, and the row of dr / dvec(H) is
+ *   s = (gx u, gx v, gx, gy u, gy v, gy, -q u, -q v, -q) / Z.  Over the valid pixels: sum s s^T, sum s r, sum r^2, n_valid, summed in double in a
+ *   fixed order (a record depends on its pair, start offsets and options alone, never on the batch or the run).
+ *   D = dvec(H) / dx (9 x 8) is the analytic derivative of dlt_solve, in double.  info = A = D^T (sum s s^T) D in grey^2 / px^2, grad = g = D^T (sum s r),
+ *   mse = sum r^2 / n_valid.
+ * One step (hnet_align::step): dx = -(A + lambda diag(A))^-1 g by Cholesky in double; the trial x + dx (rounded to fp32) is accepted iff it has
+ * n_valid >= max(min_valid, 9) and a strictly smaller mse; lambda starts at lambda0, x 0.1 on accept, x 10 on reject.  A pair stops with
+ *   HNET_ALIGN_CONVERGED   after an accepted step with max |dx| < eps_px;
+ *   HNET_ALIGN_SINGULAR    when A at offsets_px has a Cholesky pivot <= 1e-12 max diag(A) or a non-finite one: the pair does not constrain all eight
+ *                          offsets (a constant img2: A = 0 exactly; stripes).  The offsets stay where they are.  Also reported with max_iterations = 0;
+ *   HNET_ALIGN_DEGENERATE  when the start offsets have no homography, HNET_ALIGN_FEW_PIXELS when they have fewer than max(min_valid, 9) valid pixels:
+ *                          the start offsets come back unchanged with info = grad = 0 (mse0 = mse = 0).
+ * No flag: max_iterations trials were made.  max_iterations = 0 is the linearisation alone (info, grad, mse at offsets0_px).
+ * `info` is an INFORMATION matrix, not a calibrated covariance: sigma^2 A^-1 with sigma^2 = mse understates the error of offsets_px severalfold (u8
+ * rounding and interpolation error are not white noise).  Its scaling is the caller's.
+ * The basin of convergence is the texture scale (no image pyramid): start within a few pixels of the truth on fine texture. */
+typedef struct hnet_photo_align_opts { int32_t max_iterations;  /* 0 .. 32 */  int32_t min_valid;  double lambda0, eps_px; } hnet_photo_align_opts;
+void hnet_photo_align_default_opts(hnet_photo_align_opts* o);      /* 6, 20000, 1e-3, 1e-3 */
+typedef struct hnet_photo_align {
+    float   offsets_px[8];         /* where the alignment ended (the start offsets for max_iterations = 0 or an early stop) */
+    double  mse0, mse;             /* mean squared residual over the valid pixels at the start and at offsets_px, grey levels^2 */
+    int32_t n_valid0, n_valid;     /* valid pixels at the start and at offsets_px */
+    int32_t trials, accepted;      /* steps tried (linearisations after the first) and accepted: accepted <= trials <= max_iterations */
+    int32_t flags;                 /* HNET_ALIGN_* (the alignment gap behind it is written as zero: records compare byte for byte) */
+    double  lambda, grad[8], info[64];   /* the damping reached; g and A = J^T J at offsets_px */
+} hnet_photo_align;
+enum { HNET_ALIGN_CONVERGED = 1, HNET_ALIGN_SINGULAR = 2, HNET_ALIGN_DEGENERATE = 4, HNET_ALIGN_FEW_PIXELS = 8 };
+enum { HNET_ALIGN_MAX_ITERATIONS = 32 };
+/* operator call, host pointers: img1 / img2 u8 [n][224][320], offsets0_px [n][8], out [n].  1 <= n <= max_batch (HNET_ERR_CAPACITY); a null pointer or
+ * options out of range (max_iterations outside 0 .. 32, min_valid < 0, lambda0 <= 0, eps_px < 0, a non-finite one): HNET_ERR_INVALID_ARG.  An error writes
+ * nothing.  One upload, max_iterations + 1 pairs of launches (iterations are separate launches; a stopped pair's workgroups return at once), one
+ * download and one synchronisation on the context's stream. */
+int  hnet_op_photo_align(hnet_ctx* ctx, const uint8_t* img1, const uint8_t* img2, int n, const float* offsets0_px, const hnet_photo_align_opts* opts,
+                         hnet_photo_align* out);
+/* the same on the current pair of each listed session, e.g. from hnet_odometry.prior_px of a predict at the frame's time, or from an estimate the
+ * photometric gate refused.  Read-only: counts, sequence numbers, times and hnet_sessions_last_timing stay as they were.  Errors as
+ * hnet_sessions_photo_residual. */
+int  hnet_sessions_photo_align(hnet_sessions* s, int n, const int32_t* ids, const float* offsets0_px, const hnet_photo_align_opts* opts, hnet_photo_align* out);
+/* device time of the launch sequence of the context's last alignment call (HIP events of its own around it), milliseconds */
+double hnet_last_photo_align_device_ms(hnet_ctx* ctx);
+
 int hnet_synchronize(hnet_ctx* ctx, void* stream);
 int hnet_last_timing(const hnet_ctx* ctx, hnet_timing* out);
 

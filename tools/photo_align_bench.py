@@ -1,0 +1,86 @@
+#!/usr/bin/env python3
+"""Device time of photometric alignment (hnet_op_photo_align) against its yardsticks, on a GPU:
+  python tools/photo_align_bench.py [--batches 1 8 64] [--reps 40] [--warmup 5]
+per batch n: hnet_last_photo_align_device_ms (HIP events around the launch sequence) at max_iterations 0 and 6, the host wall time of
+hnet_op_photo_residual with m = 1 (a call that ends in a synchronise; its kernels' own time comes from a kernel trace) and the device time of one
+forward of the same batch (hnet_sessions_last_timing).  Medians over --reps calls after --warmup; stock synthetic pairs started from the sigma = 1 prior.
+  python tools/photo_align_bench.py --summarize DIR
+prints, from the kernel trace a `rocprofv3 --kernel-trace --output-format csv -d DIR -- python tools/photo_align_bench.py ...` run left in DIR, the mean
+duration of every photometric kernel by grid size."""
+import argparse
+import collections
+import csv
+import glob
+import os
+import re
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def summarize(d):
+    files = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)
+    if not files:
+        sys.exit(f"no kernel trace under {d}")
+    acc = collections.defaultdict(list)
+    for r in csv.DictReader(open(files[0])):
+        k = re.sub(r"\(.*$", "", re.sub(r"hnet::", "", re.sub(r"^void ", "", r["Kernel_Name"])))
+        if "photo" in k:
+            acc[(k, int(r.get("Grid_Size") or r["Grid_Size_X"]))].append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1000.0)
+    for (k, g), v in sorted(acc.items()):
+        v = np.array(v)
+        print(f"{k:32s} grid {g:7d} ({g // 256 if 'accum' in k or 'residual' in k else g // 64:4d} workgroups)  x{len(v):5d}  mean {v.mean():8.2f} us  "
+              f"median {np.median(v):8.2f} us  min {v.min():8.2f} us")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", type=int, nargs="+", default=[1, 8, 64])
+    ap.add_argument("--reps", type=int, default=40)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--summarize")
+    a = ap.parse_args()
+    if a.summarize:
+        return summarize(a.summarize)
+    from cuahn_vio_amd import synth, weights
+    from cuahn_vio_amd.homography_net import HnetEngine, HnetSessions
+    blob = weights.pack_state_dict(weights.synthetic_state(0))
+    for n in a.batches:
+        pairs = [synth.make_pair(1 + i % 16, 12.0) for i in range(n)]
+        i1, i2 = np.stack([p[0] for p in pairs]), np.stack([p[1] for p in pairs])
+        start = np.stack([synth.make_prior(1 + i % 16, pairs[i][2], 1.0) for i in range(n)])
+        e = HnetEngine(blob, variant="prior3", mc_samples=16, dropout_p=0.05, mc_seed=9, max_batch=n)
+        s = HnetSessions(e, n)
+        ids = np.arange(n, dtype=np.int32)
+        s.push(ids, i1, t=[1.0] * n)
+        s.push(ids, i2, t=[2.0] * n)
+        row = {}
+        for K in (0, 6):
+            ms = []
+            for r in range(a.warmup + a.reps):
+                rec = e.op_photo_align(i1, i2, start, max_iterations=K)
+                ms.append(e.last_photo_align_device_ms())
+            ms = np.array(ms[a.warmup:])
+            row[K] = (float(np.median(ms)), float(ms.min()), float(rec["trials"].mean()), int((rec["flags"] & 1).sum()))
+        wall = []
+        for r in range(a.warmup + a.reps):
+            t0 = time.perf_counter()
+            e.op_photo_residual(i1, i2, start[:, None, :])
+            wall.append((time.perf_counter() - t0) * 1e3)
+        wall = np.array(wall[a.warmup:])
+        fwd = []
+        for r in range(a.warmup + a.reps // 2):
+            s.infer(ids, start.astype(np.float64))
+            fwd.append(s.last_timing()["device_ms"])
+        fwd = np.array(fwd[a.warmup:])
+        print(f"n = {n:3d}: align K=0 {row[0][0]:.4f} ms (min {row[0][1]:.4f}); align K=6 {row[6][0]:.4f} ms (min {row[6][1]:.4f}; {row[6][2]:.1f} trials per pair, "
+              f"{row[6][3]} converged); residual m=1 call (host wall, with its copies) {np.median(wall):.4f} ms; one forward {np.median(fwd):.4f} ms (device)", flush=True)
+        s.close()
+        e.close()
+
+
+if __name__ == "__main__":
+    main()
