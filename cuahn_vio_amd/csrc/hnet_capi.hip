@@ -1036,7 +1036,7 @@ int photo_align_check_opts(hnet_ctx* c, const hnet_photo_align_opts* opts, const
     AlignOpts o;
     if (opts) memcpy(&o, opts, sizeof o);
     if (!opts || !hnet_align::opts_valid(o))
-        return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": opts: 0 <= max_iterations <= 32, min_valid >= 0, lambda0 > 0, eps_px >= 0, all finite");
+        return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": opts: 0 <= max_iterations <= 32, min_valid >= 0, 0 < lambda0 <= 1e100, eps_px >= 0, all finite");
     return HNET_OK;
 }
 

@@ -595,7 +595,9 @@ int  hnet_filters_set_photo_gate_taps(hnet_filters* f, int from_global);
  *   mse = sum r^2 / n_valid.
  * One step (hnet_align::step): dx = -(A + lambda diag(A))^-1 g by Cholesky in double; the trial x + dx (rounded to fp32) is accepted iff it has
  * n_valid >= max(min_valid, 9) and a strictly smaller mse; lambda starts at lambda0, x 0.1 on accept, x 10 on reject.  A pair stops with
- *   HNET_ALIGN_CONVERGED   after an accepted step with max |dx| < eps_px;
+ *   HNET_ALIGN_CONVERGED   after an accepted step with max |dx| < eps_px.  The flag reports a small accepted STEP, not a small residual: after a run of
+ *                          refusals (accepted << trials, a large lambda) the damping alone makes the step small, so look at mse against mse0 and at lambda
+ *                          before reading it as "aligned";
  *   HNET_ALIGN_SINGULAR    when A at offsets_px has a Cholesky pivot <= 1e-12 max diag(A) or a non-finite one: the pair does not constrain all eight
  *                          offsets (a constant img2: A = 0 exactly; stripes).  The offsets stay where they are.  Also reported with max_iterations = 0;
  *   HNET_ALIGN_DEGENERATE  when the start offsets have no homography, HNET_ALIGN_FEW_PIXELS when they have fewer than max(min_valid, 9) valid pixels:
@@ -617,8 +619,9 @@ typedef struct hnet_photo_align {
 enum { HNET_ALIGN_CONVERGED = 1, HNET_ALIGN_SINGULAR = 2, HNET_ALIGN_DEGENERATE = 4, HNET_ALIGN_FEW_PIXELS = 8 };
 enum { HNET_ALIGN_MAX_ITERATIONS = 32 };
 /* operator call, host pointers: img1 / img2 u8 [n][224][320], offsets0_px [n][8], out [n].  1 <= n <= max_batch (HNET_ERR_CAPACITY); a null pointer or
- * options out of range (max_iterations outside 0 .. 32, min_valid < 0, lambda0 <= 0, eps_px < 0, a non-finite one): HNET_ERR_INVALID_ARG.  An error writes
- * nothing.  One upload, max_iterations + 1 pairs of launches (iterations are separate launches; a stopped pair's workgroups return at once), one
+ * options out of range (max_iterations outside 0 .. 32, min_valid < 0, lambda0 <= 0 or > 1e100, eps_px < 0, a non-finite one): HNET_ERR_INVALID_ARG.  lambda0 is
+ * capped so that lambda, x 10 per refusal, stays far from overflow (at most 1e132 after 32 refusals): HNET_ALIGN_SINGULAR is never an artefact of the damping.
+ * An error writes nothing.  One upload, max_iterations + 1 pairs of launches (iterations are separate launches; a stopped pair's workgroups return at once), one
  * download and one synchronisation on the context's stream. */
 int  hnet_op_photo_align(hnet_ctx* ctx, const uint8_t* img1, const uint8_t* img2, int n, const float* offsets0_px, const hnet_photo_align_opts* opts,
                          hnet_photo_align* out);

@@ -29,15 +29,20 @@ namespace hnet_align {
 
 constexpr int NH = 9, NX = 8, NSYM = 45;       /* entries of vec(H), offsets, unique entries of a symmetric 9 x 9 */
 constexpr int MAX_ITERATIONS = 32;
-enum { CONVERGED = 1,        /* an accepted step moved no offset by eps_px or more */
+enum { CONVERGED = 1,        /* an accepted step moved no offset by eps_px or more: a small STEP, not a small residual.  After a run of refusals (accepted << trials,
+                                a large lambda) the damping alone makes it small: read mse against mse0 and lambda before taking it for "aligned" */
        SINGULAR = 2,         /* A at offsets_px has a Cholesky pivot <= 1e-12 max diag(A) (or a non-finite one): the pair does not constrain the 8 offsets */
        DEGENERATE = 4,       /* the start offsets have no homography (a non-finite entry of H) */
        FEW_PIXELS = 8 };     /* fewer than max(min_valid, 9) valid pixels at the start offsets */
 
 struct Opts { int32_t max_iterations, min_valid; double lambda0, eps_px; };
 inline void default_opts(Opts& o) { o.max_iterations = 6; o.min_valid = 20000; o.lambda0 = 1e-3; o.eps_px = 1e-3; }
+/* lambda0 <= MAX_LAMBDA0: every refusal multiplies lambda by 10, so after MAX_ITERATIONS of them it is at most 1e132, and diag(A) on 8-bit frames is far
+ * below 1e100 (2.4e5 on a smooth pair): A[j][j] + lambda A[j][j] cannot overflow in cholesky, and a pair whose undamped A passes the pivot test can never
+ * stop SINGULAR because its DAMPED factorisation met an infinite pivot (lambda0 = 1e280 did, after 23 refusals) */
+constexpr double MAX_LAMBDA0 = 1e100;
 inline bool opts_valid(const Opts& o) {
-    return o.max_iterations >= 0 && o.max_iterations <= MAX_ITERATIONS && o.min_valid >= 0 && o.lambda0 > 0.0 && std::isfinite(o.lambda0) && o.eps_px >= 0.0 &&
+    return o.max_iterations >= 0 && o.max_iterations <= MAX_ITERATIONS && o.min_valid >= 0 && o.lambda0 > 0.0 && o.lambda0 <= MAX_LAMBDA0 && o.eps_px >= 0.0 &&
            std::isfinite(o.eps_px);
 }
 

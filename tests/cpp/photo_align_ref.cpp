@@ -145,6 +145,28 @@ void photo_align_ref_run(const uint8_t* img1, const uint8_t* img2, int n, const 
                                *static_cast<const photo_align_ref::pa::Opts*>(opts), static_cast<photo_align_ref::pa::Record*>(out)[b]);
 }
 
+// n_edge [n]: the pixels whose ix lies within 1e-3 px of 0 or 319 or whose iy lies within 1e-3 px of 0 or 223, the bounds of VALID, at offsets [n][8]: the
+// count by which a device whose positions differ in the last bits may differ in n_valid (the residual reference's n_edge for this quantity's bounds).
+// The frames take no part in it; they are in the signature so that it is called like photo_align_ref_sums.  0 where there is no homography.
+void photo_align_ref_edge(const uint8_t*, const uint8_t*, int n, const float* offsets, int32_t* n_edge) {
+    for (int b = 0; b < n; b++) {
+        float h[9];
+        n_edge[b] = 0;
+        if (!photo_ref::homography(offsets + b * 8, h)) continue;
+        for (int v = 0; v < photo_ref::IMG_H; v++)
+            for (int u = 0; u < photo_ref::IMG_W; u++) {
+                float ix, iy;
+                photo_ref::coords(h, u, v, ix, iy);
+                const bool ex = fabsf(ix) < 1e-3f || fabsf(ix - (float)(photo_ref::IMG_W - 1)) < 1e-3f;
+                const bool ey = fabsf(iy) < 1e-3f || fabsf(iy - (float)(photo_ref::IMG_H - 1)) < 1e-3f;
+                if (ex || ey) n_edge[b]++;
+            }
+    }
+}
+
+// whether the options are ones a call accepts (hnet_align::opts_valid: the C API answers HNET_ERR_INVALID_ARG otherwise)
+int photo_align_ref_opts_valid(const void* opts) { return photo_align_ref::pa::opts_valid(*static_cast<const photo_align_ref::pa::Opts*>(opts)) ? 1 : 0; }
+
 // csrc/geom.h's dlt_solve and its analytic Jacobian D [9][8] at the corners dst [8]
 void photo_align_ref_dlt(const double* dst, double* H, double* D) {
     hnet::dlt_solve(dst, H);

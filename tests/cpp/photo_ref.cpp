@@ -103,6 +103,11 @@ void photo_ref_records(const uint8_t* img1, const uint8_t* img2, int n, const fl
         }
 }
 
+// H [n][9] = photo_ref::homography of offsets [n][8] (all NaN where ok [n] is 0): what the device's matrices are held against bit for bit
+void photo_ref_homography(int n, const float* offsets, float* H, int32_t* ok) {
+    for (int b = 0; b < n; b++) ok[b] = photo_ref::homography(offsets + b * 8, H + b * 9) ? 1 : 0;
+}
+
 }  // extern "C"
 
 #ifdef PHOTO_REF_MAIN

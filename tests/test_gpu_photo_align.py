@@ -138,6 +138,7 @@ def test_shapes_and_batch_independence(eng, cases, dev_runs):
         return L.hnet_op_photo_align(eng.handle, img1, b.ctypes.data, n, x0.ctypes.data, C.addressof(o) if o is not None else None, outp)
     assert call(10, ok) == CAPACITY
     assert call(1, _capi.photo_align_opts(max_iterations=33)) == INVALID and call(1, _capi.photo_align_opts(min_valid=-1)) == INVALID
+    assert call(1, _capi.photo_align_opts(lambda0=1.0000001e100)) == INVALID                                    # (lambda0 is capped: lambda cannot overflow)
     assert call(1, ok, img1=None) == INVALID and call(1, None) == INVALID and call(1, ok, outp=None) == INVALID and call(0, ok) == INVALID
     assert out.tobytes() == keep.tobytes()
     assert call(1, _capi.photo_align_opts(max_iterations=32)) == 0 and out.tobytes() != keep.tobytes()          # (the largest K is legal)
