@@ -275,7 +275,7 @@ static int forward_chunk(hnet_ctx* c, const FwdArgs& a, hipStream_t s) {
         LatIO lat_h = {nullptr, 1, small && c->lat_tail && c->n_planes == 2, mask_ready};
         STAGE(launch_heads_fc1_s3(feat, B, c->n_local, c->s_begin, g.dropout_p, g.mc_seed, a.seq0, c->w1_16, c->b1, hidden,
                                   c->feat16 + P0 * 5120, (size_t)g.max_batch * 5120, c->head_mask + P0 * c->n_local * 2 * 640, s, ws, wsn, a.seq_dev, c->n_planes,
-                                  c->s3_tile, &lat_h, a.seq_tab));
+                                  c->s3_tile, &lat_h, a.seq_tab, c->w1_feat_scale));
         set_kernels(lat_h.kernels);
     }
     else

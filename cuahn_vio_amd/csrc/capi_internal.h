@@ -107,6 +107,7 @@ struct hnet_ctx {
     uint16_t* b40_frag = nullptr;      // block_4_0 weights as 16x16x32 B-fragments of the pixel-pair GEMM [4][3][64] x 16 B, + slot [4]: kernel row 6 as 16x16x16 fragments
     uint16_t* b41_frag = nullptr;      // block_4_1 weights as 16x16x32 B-fragments [7][3][64] x 16 B
     uint16_t* w1_16 = nullptr;         // heads Linear(5120,256) x2: [3][512][5120] 16-bit weight planes (fp16 / bf16 by mode)
+    float w1_feat_scale = 1.0f;        // fp16-plane mode, tiny head weights: w1_16 holds w / w1_feat_scale (a power of two), the feature is multiplied by it before its split (upload_weights)
     uint16_t* feat16 = nullptr;        // [planes][max_batch][5120] 16-bit planes: feat * 1/(1-p), split
     uint8_t* head_mask = nullptr;      // [max_batch][n_local][2][640] keep bits
     size_t act_count[20] = {};         // elements per pair of layer l's output

@@ -335,9 +335,22 @@ int upload_weights(hnet_ctx* c, const Blob& b) {
             b2.insert(b2.end(), tb2->data, tb2->data + 8);
         }
         CK(upload(&c->w1, w1)); CK(upload(&c->b1, b1)); CK(upload(&c->w2, w2)); CK(upload(&c->b2, b2));
+        c->w1_feat_scale = 1.0f;
         if (c->s3) {
+            // fp16 planes carry a value to 2^-37 ABSOLUTE (s3_format.h): head weights below 2^-15 - a network whose features are large, the heads scaled back -
+            // lose relative precision, and features of 24 000 turn that into 1e-4 px (tests/test_gpu_f16x2_kernel_range.py).  Such a file gets its planes from
+            // w 2^e, the largest weight in [2^-7, 2^-6) like PyTorch's default initialisation, and the feature is multiplied by 2^-e before ITS split
+            // (launch_heads_fc1_s3 feat_scale; both exact).  Ordinary files: e = 0, the same planes as ever.
+            int e = 0;
+            if (c->n_planes == 2) {
+                float m = 0.f;
+                for (float v : w1) m = std::max(m, std::fabs(v));
+                if (m > 0.f && m < 0x1p-15f) e = std::min(-7 - std::ilogb(m), 24);
+            }
+            const float up = std::ldexp(1.0f, e);
+            c->w1_feat_scale = std::ldexp(1.0f, -e);
             std::vector<uint16_t> pl(w1.size() * 3);
-            for (size_t i = 0; i < w1.size(); i++) wsplit_gemm(w1[i], c->n_planes, pl[i], pl[w1.size() + i], pl[2 * w1.size() + i]);
+            for (size_t i = 0; i < w1.size(); i++) wsplit_gemm(w1[i] * up, c->n_planes, pl[i], pl[w1.size() + i], pl[2 * w1.size() + i]);
             CK(upload(&c->w1_16, pl));
         }
     }

@@ -82,7 +82,8 @@ hipError_t launch_heads_fc1_s3(const float* feat, int batch, int n_local, int s_
                                uint16_t* feat16, size_t f_plane, uint8_t* mask, hipStream_t s,
                                float* ws = nullptr, size_t ws_floats = 0, const uint64_t* seq_dev = nullptr, int n_planes = 3, int tile = 0,
                                LatIO* lat = nullptr /* lat->heads_one_launch, fp16-plane mode, batch <= 8, n_local <= 64: the one-launch kernel of heads_lat.h */,
-                               const uint64_t* seq_tab = nullptr /* per-pair sequence numbers [B] instead of pair_seq0 + b (heads_mask.h pair_seq) */);
+                               const uint64_t* seq_tab = nullptr /* per-pair sequence numbers [B] instead of pair_seq0 + b (heads_mask.h pair_seq) */,
+                               float feat_scale = 1.0f /* the feature is multiplied by this power of two before it is split: w1planes hold w / feat_scale */);
 hipError_t launch_nchw_f32_to_nhwc_s3(const float* in, uint16_t* out, size_t o_plane, int batch, int c, int h, int w, hipStream_t s, int n_planes = 3);
 hipError_t launch_nhwc_s3_to_nchw_f32(const uint16_t* in, size_t i_plane, float* out, int batch, int c, int h, int w, hipStream_t s, int n_planes = 3);
 

@@ -170,9 +170,9 @@ hipError_t launch_conv_patch(int layer, const uint16_t* in, size_t i_plane, int 
 hipError_t launch_heads_fc1_s3(const float* feat, int batch, int n_local, int s_begin, float p_drop, uint64_t mc_seed,
                                uint64_t pair_seq0, const uint16_t* w1planes, const float* b1, float* hidden,
                                uint16_t* feat16, size_t f_plane, uint8_t* mask, hipStream_t s, float* ws, size_t wsn,
-                               const uint64_t* seq_dev, int n_planes, int tile, LatIO* lat, const uint64_t* seq_tab) {
+                               const uint64_t* seq_dev, int n_planes, int tile, LatIO* lat, const uint64_t* seq_tab, float feat_scale) {
     return HNET_NP(launch_heads_fc1_s3_np, feat, batch, n_local, s_begin, p_drop, mc_seed, pair_seq0, w1planes, b1, hidden, feat16, f_plane, mask, s, ws, wsn, seq_dev, tile, lat,
-                   seq_tab);
+                   seq_tab, feat_scale);
 }
 
 bool heads_fc1_one_launch(int batch, int n_local, int n_planes) { return n_planes == 2 && batch <= 8 && n_local <= 16 * HL_MAXG; }

@@ -316,7 +316,10 @@ template <int NP>
 hipError_t launch_heads_fc1_s3_np(const float* feat, int batch, int n_local, int s_begin, float p_drop, uint64_t mc_seed,
                                   uint64_t pair_seq0, const uint16_t* w1planes, const float* b1, float* hidden,
                                   uint16_t* feat16, size_t f_plane, uint8_t* mask, hipStream_t s, float* ws, size_t wsn,
-                                  const uint64_t* seq_dev, int tile, LatIO* lat, const uint64_t* seq_tab) {
+                                  const uint64_t* seq_dev, int tile, LatIO* lat, const uint64_t* seq_tab, float feat_scale) {
+    // feat_scale: the power of two hnet_create divided the weight planes' source by (capi_weights.hip: 1 unless the heads' weights are tiny); it rides on the
+    // dropout scale the feature is multiplied with before it is split into planes
+    const float fscale = feat_scale / (1.0f - p_drop);
     if constexpr (NP == 2) {
         // latency path (round 5): keep bits, then ONE launch that owns four hidden units per workgroup over the whole K (heads_lat.h) instead of
         // feature planes + split-K GEMM + reduce
@@ -325,16 +328,16 @@ hipError_t launch_heads_fc1_s3_np(const float* feat, int batch, int n_local, int
             if (!lat->mask_ready) {
                 const size_t nmw = (size_t)batch * n_local * 2 * 160;
                 hipLaunchKernelGGL(heads_prep_kernel, dim3((unsigned)((nmw + 255) / 256)), dim3(256), 0, s, feat, batch, n_local, s_begin,
-                                   hnet_drop_threshold(p_drop), 1.0f / (1.0f - p_drop), mc_seed, pair_seq0, seq_dev, seq_tab, (uint16_t*)nullptr, f_plane, mask, NP, 0);
+                                   hnet_drop_threshold(p_drop), fscale, mc_seed, pair_seq0, seq_dev, seq_tab, (uint16_t*)nullptr, f_plane, mask, NP, 0);
             }
             // pairs per workgroup: two y-groups of 128 workgroups = one round of the 256 CUs (this is a one-workgroup-per-CU kernel), the weights fetched once per workgroup
             const int ppw = (batch + 1) / 2, gy = (batch + ppw - 1) / ppw;
             if (n_local <= 32)
                 hipLaunchKernelGGL(heads_fc1_lat_kernel<2>, dim3(512 / HL_UN, (unsigned)gy), dim3(HL_NT), HL_LDS_BYTES, s, feat, w1planes, (size_t)512 * 5120, b1, mask,
-                                   n_local, 1.0f / (1.0f - p_drop), hidden, batch, ppw);
+                                   n_local, fscale, hidden, batch, ppw);
             else
                 hipLaunchKernelGGL(heads_fc1_lat_kernel<HL_MAXG>, dim3(512 / HL_UN, (unsigned)gy), dim3(HL_NT), HL_LDS_BYTES, s, feat, w1planes, (size_t)512 * 5120, b1, mask,
-                                   n_local, 1.0f / (1.0f - p_drop), hidden, batch, ppw);
+                                   n_local, fscale, hidden, batch, ppw);
             return hipGetLastError();
         }
     }
@@ -351,7 +354,7 @@ hipError_t launch_heads_fc1_s3_np(const float* feat, int batch, int n_local, int
     const bool one_per_cu = Mh >= 4096 && (t8h <= 256 || t8h % 256 == 0 || t8h % 256 >= 192) && tile != 13;
     const bool pipe = NP == 2 && one_per_cu && tile != 22;
     hipLaunchKernelGGL(heads_prep_kernel, dim3((unsigned)((nwork + 255) / 256)), dim3(256), 0, s, feat, batch, n_local, s_begin,
-                       hnet_drop_threshold(p_drop), 1.0f / (1.0f - p_drop), mc_seed, pair_seq0, seq_dev, seq_tab, feat16, f_plane, mask, NP, pipe ? 1 : 0);
+                       hnet_drop_threshold(p_drop), fscale, mc_seed, pair_seq0, seq_dev, seq_tab, feat16, f_plane, mask, NP, pipe ? 1 : 0);
     LatIO lat_count = {};                      // (feature planes + keep bits, the GEMM, its reduce launch if it splits K)
     if (!lat) lat = &lat_count;
     lat->tickets = nullptr;
@@ -460,7 +463,7 @@ hipError_t conv_kernels_init_device_np() {
                                                     size_t, hipStream_t, bool, int);                                                           \
     KW template hipError_t launch_heads_fc1_s3_np<NP>(const float*, int, int, int, float, uint64_t, uint64_t, const uint16_t*,           \
                                                       const float*, float*, uint16_t*, size_t, uint8_t*, hipStream_t, float*, size_t,    \
-                                                      const uint64_t*, int, LatIO*, const uint64_t*);                                    \
+                                                      const uint64_t*, int, LatIO*, const uint64_t*, float);                             \
     KW template hipError_t launch_conv_s3_np<NP>(int, const uint16_t*, size_t, int, int, int, const uint16_t*, size_t, const float*,     \
                                                  uint16_t*, size_t, float*, hipStream_t, float*, size_t, const uint16_t*, int, LatIO*);  \
     KW template hipError_t conv_kernels_init_device_np<NP>();

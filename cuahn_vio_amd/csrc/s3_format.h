@@ -10,7 +10,12 @@
 //             fp32 values (those within 2^-8 ulp of an fp16 rounding tie) scale their residual to >= 65520: the second plane becomes an infinity, the
 //             result is non-finite and is DETECTED (hnet_overflow_flag / demotion), never silently wrong; from 65520 on A0 overflows as well
 //             (tests/cpp/s3_format_check.cpp walks both bands exhaustively); fp16 subnormals are not flushed by the gfx950 MFMAs
-//             (tools/f16x2_probe.hip), so small values only lose ABSOLUTE precision below 2^-37.
+//             (tools/f16x2_probe.hip), so small values only lose ABSOLUTE precision below 2^-37.  That holds for WEIGHTS as well: one below 2^-15 is
+//             carried to 2^-37 absolute, no longer to 2^-22 relative; the heads' Linear(5120, 256), whose weights shrink as a network's features grow,
+//             is therefore packed from w 2^e with the feature scaled by 2^-e (capi_weights.hip).  The range is that of values IN PLANES: the last
+//             layer of a block writes fp32 for the block-tail FC and the heads, its outputs may pass 65520.  A kernel may read an input with a
+//             zero weight (the eighth tap of the pixel-pair GEMMs, conv_first.h): an infinite plane there gives a NaN, never a finite wrong value.
+//             tests/test_gpu_f16x2_kernel_range.py drives every kernel of the mode to these edges (table in DESIGN.md, section 3.0).
 // Host + device helpers shared by the kernels (igemm_s3.h) and the weight packer (capi_weights.hip).
 #pragma once
 #include <hip/hip_runtime.h>
