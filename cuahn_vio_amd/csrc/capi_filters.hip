@@ -6,6 +6,9 @@
 using namespace hnet;
 using namespace capi;
 
+// a launch with an opt-in device time: its two events are recorded only once the caller has asked for the time (`timed`); ms: the last timed launch's
+struct TimedLaunch { hipEvent_t ev0 = nullptr, ev1 = nullptr; bool timed = false; double ms = NAN; };
+
 // ---- filters: one 27-state filter per session of a sessions object (include/hnet.h).  Device: the states [n_sessions], the parameters [n_sessions] and
 // the step's buffers sized for max_batch; host: each state's time (the t_frame check) and camera-IMU offset (the selection window).  A step works on a
 // copy of the listed states (work) and scatters it back only once its forwards are accepted: an overflow / timeout repeat starts from the untouched states.
@@ -54,17 +57,13 @@ struct hnet_filters {
     uint8_t* d_pred = nullptr;
     hnet_ekf::ImuData* d_pred_sel = nullptr;   // [B][2 (cap + 2)]
     size_t off_pred_out = 0;
-    hipEvent_t ev_p0 = nullptr, ev_p1 = nullptr;
-    bool pred_timed = false;                   // set by the first hnet_filters_last_predict_device_ms: only then a predict records its two events
-    double pred_ms = NAN;
+    TimedLaunch pred_time;                     // hnet_filters_last_predict_device_ms
     // predict_cov (hnet_filters_predict_cov), allocated by its first call: ONE block {jobs [B] | records [n] | covariance records [n] | full [n][729]} (the
     // three output sections dense for the call's n, so that one copy downloads what was asked for) and its pinned copy; the scratch is the predict's
     uint8_t* pin_pcov = nullptr;
     uint8_t* d_pcov = nullptr;
     size_t off_pcov_out = 0;
-    hipEvent_t ev_c0 = nullptr, ev_c1 = nullptr;
-    bool pcov_timed = false;                   // as pred_timed, set by hnet_filters_last_predict_cov_device_ms
-    double pcov_ms = NAN;
+    TimedLaunch pcov_time;                     // hnet_filters_last_predict_cov_device_ms
     // innovations (hnet_filters_enable_innovations): the output block then is {net | prior_px | updates | innov [iters][n] InnovRec, dense | work | results},
     // so that the records lie inside the one download; the per-session gates; the statistics, accumulated from the records of accepted steps
     bool innov = false;
@@ -106,6 +105,7 @@ static int grow_block(hnet_ctx* c, uint8_t** pin, uint8_t** dev, size_t* cap, si
 template <typename T> static void drop_dev(T*& p) { if (p) (void)hipFree((void*)p); p = nullptr; }
 static void drop_pin(uint8_t*& p) { if (p) (void)hipHostFree(p); p = nullptr; }
 static void drop_event(hipEvent_t& e) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+static void drop_timed(TimedLaunch& t) { drop_event(t.ev0); drop_event(t.ev1); }
 static void filters_drop_feed(hnet_filters* f) {                  // hnet_filters_enable_feed
     drop_dev(f->d_ring); drop_dev(f->d_meta); drop_dev(f->d_ip); drop_dev(f->d_sel); drop_dev(f->d_adv);
     drop_pin(f->pin_adv);
@@ -114,12 +114,12 @@ static void filters_drop_feed(hnet_filters* f) {                  // hnet_filter
 static void filters_drop_predict(hnet_filters* f) {               // predict_buffers
     drop_dev(f->d_pred_sel); drop_dev(f->d_pred);
     drop_pin(f->pin_pred);
-    drop_event(f->ev_p0); drop_event(f->ev_p1);
+    drop_timed(f->pred_time);
 }
 static void filters_drop_predict_cov(hnet_filters* f) {           // predict_cov_buffers
     drop_dev(f->d_pcov);
     drop_pin(f->pin_pcov);
-    drop_event(f->ev_c0); drop_event(f->ev_c1);
+    drop_timed(f->pcov_time);
 }
 
 extern "C" {
@@ -950,8 +950,8 @@ static int predict_buffers(hnet_filters* f) {
     const size_t bytes = f->off_pred_out + (size_t)B * sizeof(PredictOut);
     hipError_t e = hipMalloc((void**)&f->d_pred_sel, (size_t)B * 2 * (f->cap + 2) * sizeof(hnet_ekf::ImuData));
     if (e == hipSuccess) e = hipHostMalloc((void**)&f->pin_pred, bytes, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipEventCreate(&f->ev_p0);
-    if (e == hipSuccess) e = hipEventCreate(&f->ev_p1);
+    if (e == hipSuccess) e = hipEventCreate(&f->pred_time.ev0);
+    if (e == hipSuccess) e = hipEventCreate(&f->pred_time.ev1);
     if (e == hipSuccess) e = hipMalloc((void**)&f->d_pred, bytes);
     if (e != hipSuccess) {
         filters_drop_predict(f);
@@ -960,42 +960,57 @@ static int predict_buffers(hnet_filters* f) {
     return HNET_OK;
 }
 
-int hnet_filters_predict(hnet_filters* f, int n, const int32_t* ids, const double* t_query, hnet_odometry* out) {
-    if (!f) return HNET_ERR_INVALID_ARG;
-    hnet_sessions* s = f->s;
-    hnet_ctx* c = s->ctx;
-    if (!f->cap) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_predict: feed not enabled (hnet_filters_enable_feed)");
-    if (!t_query || !out) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_predict: t_query / out");
-    int rc = sessions_check_ids(s, n, ids);
+// What hnet_filters_predict and hnet_filters_predict_cov (`who`, for the messages) do before they enqueue anything: the argument checks in their order
+// (`missing`: null, or the names of the caller's own pointers of which one is null), the device, the caller's buffers (`buffers`: made by its first call)
+// and the job of every listed session in `*job`, the caller's pinned job table, which exists once `buffers` has run.
+static int predict_prepare(hnet_filters* f, const char* who, const char* missing, int n, const int32_t* ids, const double* t_query, int (*buffers)(hnet_filters*),
+                           uint8_t* const* job) {
+    hnet_ctx* c = f->s->ctx;
+    if (!f->cap) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": feed not enabled (hnet_filters_enable_feed)");
+    if (missing) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": " + missing);
+    int rc = sessions_check_ids(f->s, n, ids);
     if (rc != HNET_OK) return rc;
     for (int i = 0; i < n; i++)
-        if (!std::isfinite(t_query[i])) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_predict: t_query must be finite");
+        if (!std::isfinite(t_query[i])) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": t_query must be finite");
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    if ((rc = predict_buffers(f)) != HNET_OK) return rc;
-    PredictJob* job = reinterpret_cast<PredictJob*>(f->pin_pred);
+    if ((rc = buffers(f)) != HNET_OK) return rc;
+    PredictJob* jb = reinterpret_cast<PredictJob*>(*job);
     for (int i = 0; i < n; i++) {
         const int id = ids[i];
         const double dt = f->cam_imu_dt[id];
         int st = PRED_OK;                                          // (the kernel reports AT_STATE from the device's own state time)
         if (!f->inited[id]) st = PRED_NO_STATE;
         else if (t_query[i] > f->t[id] && !(t_query[i] < f->imu_newest[id] - dt)) st = PRED_WAIT_IMU;
-        job[i] = PredictJob{t_query[i], dt, id, st};
+        jb[i] = PredictJob{t_query[i], dt, id, st};
     }
+    return HNET_OK;
+}
+// the two events of a timed launch, each recorded where the caller stands in the stream, and the time between them once the stream has been drained
+static hipError_t timed_record(const TimedLaunch& t, hipEvent_t ev, hipStream_t st) { return t.timed ? hipEventRecord(ev, st) : hipSuccess; }
+static hipError_t timed_read(TimedLaunch& t) {
+    float ms = 0;
+    const hipError_t e = t.timed ? hipEventElapsedTime(&ms, t.ev0, t.ev1) : hipSuccess;
+    if (t.timed && e == hipSuccess) t.ms = ms;
+    return e;
+}
+
+int hnet_filters_predict(hnet_filters* f, int n, const int32_t* ids, const double* t_query, hnet_odometry* out) {
+    if (!f) return HNET_ERR_INVALID_ARG;
+    hnet_sessions* s = f->s;
+    hnet_ctx* c = s->ctx;
+    const int rc = predict_prepare(f, "hnet_filters_predict", !t_query || !out ? "t_query / out" : nullptr, n, ids, t_query, predict_buffers, &f->pin_pred);
+    if (rc != HNET_OK) return rc;
     hipStream_t st = c->stream;
     PredictOut* d_out = reinterpret_cast<PredictOut*>(f->d_pred + f->off_pred_out);
     HIPCHK(c, hipMemcpyAsync(f->d_pred, f->pin_pred, (size_t)n * sizeof(PredictJob), hipMemcpyHostToDevice, st));
-    if (f->pred_timed) HIPCHK(c, hipEventRecord(f->ev_p0, st));
+    HIPCHK(c, timed_record(f->pred_time, f->pred_time.ev0, st));
     HIPCHK(c, launch_filter_predict(reinterpret_cast<const PredictJob*>(f->d_pred), n, s->n, f->cap, f->d_ring, f->d_meta, f->d_state, f->d_params, f->d_pred_sel,
                                     d_out, st));
-    if (f->pred_timed) HIPCHK(c, hipEventRecord(f->ev_p1, st));
+    HIPCHK(c, timed_record(f->pred_time, f->pred_time.ev1, st));
     HIPCHK(c, hipMemcpyAsync(f->pin_pred + f->off_pred_out, d_out, (size_t)n * sizeof(PredictOut), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     memcpy(out, f->pin_pred + f->off_pred_out, (size_t)n * sizeof(PredictOut));
-    if (f->pred_timed) {
-        float ms = 0;
-        HIPCHK(c, hipEventElapsedTime(&ms, f->ev_p0, f->ev_p1));
-        f->pred_ms = ms;
-    }
+    HIPCHK(c, timed_read(f->pred_time));
     return HNET_OK;
 }
 
@@ -1003,16 +1018,17 @@ int hnet_filters_predict(hnet_filters* f, int n, const int32_t* ids, const doubl
 
 static_assert(sizeof(hnet_odometry_cov) == sizeof(PredictCovOut), "hnet_odometry_cov is the PredictCovOut layout");
 
-// the call's own job / output block, made once for max_batch sessions with the full covariances; the scratch is the predict's (predict_buffers)
+// the call's own job / output block, made once for max_batch sessions with the full covariances; the scratch is the predict's (predict_buffers first)
 static int predict_cov_buffers(hnet_filters* f) {
+    if (const int rc = predict_buffers(f); rc != HNET_OK) return rc;
     if (f->d_pcov) return HNET_OK;
     hnet_ctx* c = f->s->ctx;
     const int B = c->cfg.max_batch;
     f->off_pcov_out = al256((size_t)B * sizeof(PredictJob));
     const size_t bytes = f->off_pcov_out + (size_t)B * (sizeof(PredictOut) + sizeof(PredictCovOut) + (size_t)hnet_ekf::NS * hnet_ekf::NS * sizeof(double));
     hipError_t e = hipHostMalloc((void**)&f->pin_pcov, bytes, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipEventCreate(&f->ev_c0);
-    if (e == hipSuccess) e = hipEventCreate(&f->ev_c1);
+    if (e == hipSuccess) e = hipEventCreate(&f->pcov_time.ev0);
+    if (e == hipSuccess) e = hipEventCreate(&f->pcov_time.ev1);
     if (e == hipSuccess) e = hipMalloc((void**)&f->d_pcov, bytes);
     if (e != hipSuccess) {
         filters_drop_predict_cov(f);
@@ -1025,50 +1041,31 @@ int hnet_filters_predict_cov(hnet_filters* f, int n, const int32_t* ids, const d
     if (!f) return HNET_ERR_INVALID_ARG;
     hnet_sessions* s = f->s;
     hnet_ctx* c = s->ctx;
-    if (!f->cap) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_predict_cov: feed not enabled (hnet_filters_enable_feed)");
-    if (!t_query || !out || !cov_out) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_predict_cov: t_query / out / cov_out");
-    int rc = sessions_check_ids(s, n, ids);
+    const int rc = predict_prepare(f, "hnet_filters_predict_cov", !t_query || !out || !cov_out ? "t_query / out / cov_out" : nullptr, n, ids, t_query,
+                                   predict_cov_buffers, &f->pin_pcov);
     if (rc != HNET_OK) return rc;
-    for (int i = 0; i < n; i++)
-        if (!std::isfinite(t_query[i])) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_predict_cov: t_query must be finite");
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    if ((rc = predict_buffers(f)) != HNET_OK) return rc;
-    if ((rc = predict_cov_buffers(f)) != HNET_OK) return rc;
-    PredictJob* job = reinterpret_cast<PredictJob*>(f->pin_pcov);
-    for (int i = 0; i < n; i++) {                                  // hnet_filters_predict's rules in its order
-        const int id = ids[i];
-        const double dt = f->cam_imu_dt[id];
-        int st = PRED_OK;
-        if (!f->inited[id]) st = PRED_NO_STATE;
-        else if (t_query[i] > f->t[id] && !(t_query[i] < f->imu_newest[id] - dt)) st = PRED_WAIT_IMU;
-        job[i] = PredictJob{t_query[i], dt, id, st};
-    }
     hipStream_t st = c->stream;
     const size_t off_cov = f->off_pcov_out + (size_t)n * sizeof(PredictOut), off_full = off_cov + (size_t)n * sizeof(PredictCovOut);
     const size_t full_bytes = full_cov ? (size_t)n * hnet_ekf::NS * hnet_ekf::NS * sizeof(double) : 0;
     HIPCHK(c, hipMemcpyAsync(f->d_pcov, f->pin_pcov, (size_t)n * sizeof(PredictJob), hipMemcpyHostToDevice, st));
-    if (f->pcov_timed) HIPCHK(c, hipEventRecord(f->ev_c0, st));
+    HIPCHK(c, timed_record(f->pcov_time, f->pcov_time.ev0, st));
     HIPCHK(c, launch_filter_predict_cov(reinterpret_cast<const PredictJob*>(f->d_pcov), n, s->n, f->cap, f->d_ring, f->d_meta, f->d_state, f->d_params, f->d_pred_sel,
                                         reinterpret_cast<PredictOut*>(f->d_pcov + f->off_pcov_out), reinterpret_cast<PredictCovOut*>(f->d_pcov + off_cov),
                                         full_cov ? reinterpret_cast<double*>(f->d_pcov + off_full) : nullptr, st));
-    if (f->pcov_timed) HIPCHK(c, hipEventRecord(f->ev_c1, st));
+    HIPCHK(c, timed_record(f->pcov_time, f->pcov_time.ev1, st));
     HIPCHK(c, hipMemcpyAsync(f->pin_pcov + f->off_pcov_out, f->d_pcov + f->off_pcov_out, off_full + full_bytes - f->off_pcov_out, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     memcpy(out, f->pin_pcov + f->off_pcov_out, (size_t)n * sizeof(PredictOut));
     memcpy(cov_out, f->pin_pcov + off_cov, (size_t)n * sizeof(PredictCovOut));
     if (full_cov) memcpy(full_cov, f->pin_pcov + off_full, full_bytes);
-    if (f->pcov_timed) {
-        float ms = 0;
-        HIPCHK(c, hipEventElapsedTime(&ms, f->ev_c0, f->ev_c1));
-        f->pcov_ms = ms;
-    }
+    HIPCHK(c, timed_read(f->pcov_time));
     return HNET_OK;
 }
 
 double hnet_filters_last_predict_cov_device_ms(hnet_filters* f) {
     if (!f) return NAN;
-    f->pcov_timed = true;
-    return f->pcov_ms;
+    f->pcov_time.timed = true;
+    return f->pcov_time.ms;
 }
 
 double hnet_filters_newest_imu_time(const hnet_filters* f, int id) {
@@ -1078,8 +1075,8 @@ double hnet_filters_newest_imu_time(const hnet_filters* f, int id) {
 
 double hnet_filters_last_predict_device_ms(hnet_filters* f) {
     if (!f) return NAN;
-    f->pred_timed = true;
-    return f->pred_ms;
+    f->pred_time.timed = true;
+    return f->pred_time.ms;
 }
 
 }  // extern "C"

@@ -14,22 +14,104 @@ constexpr int NS = hnet_ekf::NS, NW = hnet_ekf::NW;
 constexpr int NE = NS * NS;                                   // 729 covariance elements
 constexpr int EPT = (NE + FILTER_THREADS - 1) / FILTER_THREADS;   // 3 per thread
 
-__device__ inline void load_rec(FilterRec& dst, const FilterRec& src) {
-    const double* s = reinterpret_cast<const double*>(&src);
-    double* d = reinterpret_cast<double*>(&dst);
-    for (int i = threadIdx.x; i < FILTER_REC_DOUBLES; i += FILTER_THREADS) d[i] = s[i];
-}
-__device__ inline void store_rec(FilterRec& dst, const FilterRec& src) {
+// one record to another (global memory or LDS on either side) by the FILTER_THREADS lanes of a workgroup
+__device__ inline void copy_rec(FilterRec& dst, const FilterRec& src) {
     const double* s = reinterpret_cast<const double*>(&src);
     double* d = reinterpret_cast<double*>(&dst);
     for (int i = threadIdx.x; i < FILTER_REC_DOUBLES; i += FILTER_THREADS) d[i] = s[i];
 }
 // row of the state that measurement component j selects (update(): 15 + 3c + k)
 __device__ inline int sel(int j) { return 15 + 3 * (j >> 1) + (j & 1); }
+
+// hnet_ekf::reset_4pt_offset on the LDS-resident state by the FILTER_THREADS lanes (no barrier of its own: the caller's next one publishes it)
+__device__ inline void reset_offset_block(FilterRec& S) {
+    for (int e = threadIdx.x; e < NE; e += FILTER_THREADS)
+        if (e / NS >= 15 || e % NS >= 15) S.s.cov[e] = 0.0;
+    if (threadIdx.x < 12) (&S.s.offset[0][0])[threadIdx.x] = 0.0;
+}
+
+// F and Fw as cov_interval wants them before a launch's first interval: zeroed once by all lanes, published by the caller's next barrier
+__device__ inline void clear_jacobians(double* F, double* Fw) {
+    for (int i = threadIdx.x; i < NE; i += FILTER_THREADS) F[i] = 0.0;
+    for (int i = threadIdx.x; i < NS * NW; i += FILTER_THREADS) Fw[i] = 0.0;
+}
+// One IMU interval [r0, r1] of hnet_ekf::propagate_with_imu's loop on the LDS-resident state S with the LDS arrays F [729], Fw [27 * 15] and T [729], for a
+// workgroup of FILTER_THREADS: lane 0 forms the corrected inputs with the current biases, the Jacobians and the mean; all lanes then T = F P and
+// P <- T F^T + Fw diag(q) Fw^T, one output element per lane per pass with the k-loop in the host's order.  The Jacobians come from the header's
+// propagate_jacobians_fill, which writes the same entries in every interval and touches no other: clear_jacobians once per launch gives what
+// propagate_jacobians' per-interval clearing gives (include/hnet_ekf.h).  Contains barriers: every call is uniform over the workgroup; S is
+// published on entry (a barrier behind whatever wrote it) and on return.  filter_propagate_kernel calls it; filter_predict_cov_kernel restates the
+// body, because as this function it costs that kernel 3 %, and tests/test_gpu_filters_predict_cov.py pins the two bit for bit.
+__device__ __forceinline__ void cov_interval(FilterRec& S, const FilterParams& pr, const hnet_ekf::ImuData& r0, const hnet_ekf::ImuData& r1, double* F, double* Fw, double* T) {
+    if (threadIdx.x == 0) {
+        double w_hat[3], a_hat[3];
+        const double dt = hnet_ekf::imu_interval_inputs(S.s, r0, r1, pr.imu_avg != 0, w_hat, a_hat);
+        hnet_ekf::propagate_jacobians_fill(S.s, pr.ext, dt, w_hat, F, Fw, pr.gravity_mag);
+        hnet_ekf::propagate_mean(S.s, pr.ext, dt, w_hat, a_hat, pr.gravity_mag);
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < NE; e += FILTER_THREADS) {                  // T = F P
+        const int i = e / NS, j = e % NS;
+        double a = 0.0;
+        for (int q = 0; q < NS; q++) a += F[i * NS + q] * S.s.cov[q * NS + j];
+        T[e] = a;
+    }
+    __syncthreads();
+    double o[EPT];
+    for (int r = 0; r < EPT; r++) {                                             // T F^T + Fw diag(q) Fw^T
+        const int e = threadIdx.x + r * FILTER_THREADS;
+        if (e < NE) {                                                           // (not `break`: in a function that form costs 130 registers)
+            const int i = e / NS, j = e % NS;
+            double a = 0.0;
+            for (int q = 0; q < NS; q++) a += T[i * NS + q] * F[j * NS + q];
+            for (int q = 0; q < NW; q++) a += Fw[i * NW + q] * pr.q[q] * Fw[j * NW + q];
+            o[r] = a;
+        }
+    }
+    for (int r = 0; r < EPT; r++) {
+        const int e = threadIdx.x + r * FILTER_THREADS;
+        if (e < NE) S.s.cov[e] = o[r];
+    }
+    __syncthreads();
+}
+
+// hnet_ekf::invert(A, 8) on the LDS matrices A [64] and V [64] (V = I on entry, A^-1 on return): Gauss-Jordan with partial pivoting, the header's
+// operations in the header's order per element, lane t < 64 holding element (t >> 3, t & 7) of both.  Every thread of the workgroup takes the barriers
+// (lanes 64 and above do nothing else), so every call is uniform over the workgroup; A and V are published on entry.  -> singular: a pivot that is
+// exactly 0, A and V then hold the elimination as far as it went.
+__device__ inline bool invert8_lanes(double* A, double* V) {
+    const int t = threadIdx.x, i = t >> 3, j = t & 7;
+    for (int col = 0; col < 8; col++) {
+        int piv = col;
+        for (int r = col + 1; r < 8; r++)
+            if (fabs(A[r * 8 + col]) > fabs(A[piv * 8 + col])) piv = r;
+        if (A[piv * 8 + col] == 0.0) return true;                                // (every lane sees the same LDS values)
+        __syncthreads();
+        if (piv != col && t < 16) {
+            double* X = t < 8 ? A : V;
+            const double tmp = X[col * 8 + j];
+            X[col * 8 + j] = X[piv * 8 + j];
+            X[piv * 8 + j] = tmp;
+        }
+        __syncthreads();
+        const double d = 1.0 / A[col * 8 + col];
+        __syncthreads();
+        if (t < 16) (t < 8 ? A : V)[col * 8 + j] *= d;
+        __syncthreads();
+        const double f = t < 64 ? A[i * 8 + col] : 0.0;
+        __syncthreads();
+        if (t < 64 && i != col && f != 0.0) {
+            A[t] -= f * A[col * 8 + j];
+            V[t] -= f * V[col * 8 + j];
+        }
+        __syncthreads();
+    }
+    return false;
+}
 }  // namespace
 
-// IMU propagation of one listed session per workgroup over its selected readings (hnet_ekf::propagate_with_imu's loop): per interval the corrected
-// inputs with the current biases, the Jacobians and the mean on lane 0, then P <- F P F^T + Fw diag(q) Fw^T by all lanes.  The result goes to work[b].
+// IMU propagation of one listed session per workgroup over its selected readings (hnet_ekf::propagate_with_imu's loop), one cov_interval per pair of
+// readings.  The result goes to work[b].
 // ADV = false (hnet_filters_step): session ids[b], readings rd[rd_off[b] .. rd_off[b + 1]) selected on the host, time t_frame[b].
 // ADV = true (hnet_filters_advance): session job[b].id, readings rd + b * 2 * (cap + 2) + (cap + 2) .. + res[b].n_sel from filter_select_kernel; the state
 // comes from state[id] or, after the initialiser, from work[b]; a session the initialiser refused is skipped, one initialised after its frame keeps the
@@ -50,58 +132,24 @@ __global__ __launch_bounds__(FILTER_THREADS) void filter_propagate_kernel(const 
         const AdvanceResult r = res[b];
         if (job[b].init && !r.ok) return;                      // (uniform over the workgroup, as the returns below)
         if (r.n_sel < 0 || r.n_sel > cap + 2) return;
-        load_rec(S, job[b].init ? work[b] : state[id]);
+        copy_rec(S, job[b].init ? work[b] : state[id]);
         k0 = 0;
         k1 = r.n_sel;
         rd += (size_t)b * 2 * (cap + 2) + (cap + 2);
     } else {
-        load_rec(S, state[id]);
+        copy_rec(S, state[id]);
         k0 = rd_off[b], k1 = rd_off[b + 1];
     }
+    clear_jacobians(F, Fw);
     __syncthreads();
     if constexpr (ADV)
         if (job[b].init && S.t > job[b].t_frame) return;       // VioManager.cpp:203-206: work[b] holds the initial state
-    for (int k = k0; k + 1 < k1; k++) {
-        if (threadIdx.x == 0) {
-            double w_hat[3], a_hat[3];
-            const double dt = hnet_ekf::imu_interval_inputs(S.s, rd[k], rd[k + 1], pr.imu_avg != 0, w_hat, a_hat);
-            hnet_ekf::propagate_jacobians(S.s, pr.ext, dt, w_hat, F, Fw, pr.gravity_mag);
-            hnet_ekf::propagate_mean(S.s, pr.ext, dt, w_hat, a_hat, pr.gravity_mag);
-        }
-        __syncthreads();
-        for (int e = threadIdx.x; e < NE; e += FILTER_THREADS) {              // T = F P
-            const int i = e / NS, j = e % NS;
-            double a = 0.0;
-            for (int q = 0; q < NS; q++) a += F[i * NS + q] * S.s.cov[q * NS + j];
-            T[e] = a;
-        }
-        __syncthreads();
-        double o[EPT];
-        for (int r = 0; r < EPT; r++) {                                         // T F^T + Fw diag(q) Fw^T
-            const int e = threadIdx.x + r * FILTER_THREADS;
-            if (e >= NE) break;
-            const int i = e / NS, j = e % NS;
-            double a = 0.0;
-            for (int q = 0; q < NS; q++) a += T[i * NS + q] * F[j * NS + q];
-            for (int q = 0; q < NW; q++) a += Fw[i * NW + q] * pr.q[q] * Fw[j * NW + q];
-            o[r] = a;
-        }
-        for (int r = 0; r < EPT; r++) {
-            const int e = threadIdx.x + r * FILTER_THREADS;
-            if (e < NE) S.s.cov[e] = o[r];
-        }
-        __syncthreads();
-    }
-    if constexpr (ADV) {
-        if (job[b].reset) {                                    // hnet_ekf::reset_4pt_offset
-            for (int e = threadIdx.x; e < NE; e += FILTER_THREADS)
-                if (e / NS >= 15 || e % NS >= 15) S.s.cov[e] = 0.0;
-            if (threadIdx.x < 12) (&S.s.offset[0][0])[threadIdx.x] = 0.0;
-        }
-    }
+    for (int k = k0; k + 1 < k1; k++) cov_interval(S, pr, rd[k], rd[k + 1], F, Fw, T);
+    if constexpr (ADV)
+        if (job[b].reset) reset_offset_block(S);
     if (threadIdx.x == 0) S.t = ADV ? job[b].t_frame : t_frame[b];
     __syncthreads();
-    store_rec(work[b], S);
+    copy_rec(work[b], S);
 }
 
 // VioManager.cpp:230-234 + the (float) cast of hnet_sessions_infer: prior_px[b][k] = (float)(offset * 159.5), prior_cam[b][k] = offset
@@ -128,7 +176,7 @@ __global__ __launch_bounds__(FILTER_THREADS) void filter_update_kernel(const int
     const int done = updates[b];
     const bool run = gate[b] != 0 && done >= 0;
     if (!run && !last) return;                                                 // (uniform over the workgroup)
-    load_rec(S, work[b]);
+    copy_rec(S, work[b]);
     __syncthreads();
     const int t = threadIdx.x;
     if (run) {
@@ -142,33 +190,7 @@ __global__ __launch_bounds__(FILTER_THREADS) void filter_update_kernel(const int
         for (int e = t; e < NS * 8; e += FILTER_THREADS) PHt[e] = S.s.cov[(e >> 3) * NS + sel(e & 7)];
         if (t < 8) inno[t] = (double)nm[t] / hnet_ekf::F_PIX - prior_cam[(size_t)b * 8 + t];
         __syncthreads();
-        // hnet_ekf::invert(A, 8): Gauss-Jordan with partial pivoting, the same operations in the same order, rows / columns across lanes
-        bool singular = false;
-        for (int col = 0; col < 8; col++) {
-            int piv = col;
-            for (int r = col + 1; r < 8; r++)
-                if (fabs(A[r * 8 + col]) > fabs(A[piv * 8 + col])) piv = r;
-            if (A[piv * 8 + col] == 0.0) { singular = true; break; }             // (every lane sees the same LDS values)
-            __syncthreads();
-            if (piv != col && t < 16) {
-                double* X = t < 8 ? A : V;
-                const int j = t & 7;
-                const double tmp = X[col * 8 + j];
-                X[col * 8 + j] = X[piv * 8 + j];
-                X[piv * 8 + j] = tmp;
-            }
-            __syncthreads();
-            const double d = 1.0 / A[col * 8 + col];
-            __syncthreads();
-            if (t < 16) (t < 8 ? A : V)[col * 8 + (t & 7)] *= d;
-            __syncthreads();
-            const int r = t >> 4, j = t & 7;
-            double* X = (t & 8) ? V : A;
-            const double f = t < 128 ? A[r * 8 + col] : 0.0;
-            __syncthreads();
-            if (t < 128 && r != col && f != 0.0) X[r * 8 + j] -= f * X[col * 8 + j];
-            __syncthreads();
-        }
+        const bool singular = invert8_lanes(A, V);
         if (singular) {
             if (t == 0) updates[b] = -1 - done;
         } else {
@@ -212,13 +234,11 @@ __global__ __launch_bounds__(FILTER_THREADS) void filter_update_kernel(const int
         }
         __syncthreads();
     }
-    if (last) {                                                                // hnet_ekf::reset_4pt_offset
-        for (int e = t; e < NE; e += FILTER_THREADS)
-            if (e / NS >= 15 || e % NS >= 15) S.s.cov[e] = 0.0;
-        if (t < 12) (&S.s.offset[0][0])[t] = 0.0;
+    if (last) {
+        reset_offset_block(S);
         __syncthreads();
     }
-    store_rec(work[b], S);
+    copy_rec(work[b], S);
 }
 
 // the step's result work[b] -> state[ids[b]] (after the host accepted the step's forwards)
@@ -226,7 +246,7 @@ __global__ __launch_bounds__(FILTER_THREADS) void filter_scatter_kernel(const Fi
                                                                         FilterRec* __restrict__ state) {
     const int b = blockIdx.x, id = ids[b];
     if (id < 0 || id >= n_sessions) return;
-    store_rec(state[id], work[b]);
+    copy_rec(state[id], work[b]);
 }
 
 // ---- the IMU feed and the cold start (hnet_filters_feed_imu / hnet_filters_advance) ----
@@ -235,6 +255,36 @@ namespace {
 __device__ inline const hnet_ekf::ImuData& ring_at(const hnet_ekf::ImuData* rg, int head, int cap, int j) { return rg[(head + j) % cap]; }
 // a session's ring is usable when its meta is consistent (the host wrote it; checked again because the kernels index with it)
 __device__ inline bool ring_ok(const ImuRingMeta& m, int cap) { return m.head >= 0 && m.head < cap && m.count >= 0 && m.count <= cap; }
+
+// The span of a session's ring rg (meta m: ring_ok and count >= 1, checked by the caller) that hnet_ekf::select_imu_readings can touch for the window
+// [t0, t1], copied in time order into lin [cap + 2], by a workgroup of THREADS.  All lanes count the readings more than 10 s behind the newest (never
+// used: hnet_ekf::trim_imu_prop), those before the window's start and those up to its end into the three LDS counters cnt (integers: the order of the
+// atomics changes nothing); hnet_ekf::select_span turns the counts into the span, which is checked against the ring before anything is indexed with
+// it and copied out (it may wrap).  -> its length, 0 when there is nothing usable.  Contains barriers: every call is uniform over the workgroup; lin
+// is published on return.
+template <int THREADS>
+__device__ inline int ring_span(const hnet_ekf::ImuData* rg, const ImuRingMeta m, int cap, double t0, double t1, int* cnt, hnet_ekf::ImuData* lin) {
+    const int t = threadIdx.x;
+    const double newest = ring_at(rg, m.head, cap, m.count - 1).t;
+    if (t < 3) cnt[t] = 0;
+    __syncthreads();
+    int c_old = 0, c_lt = 0, c_le = 0;
+    for (int j = t; j < m.count; j += THREADS) {
+        const double tt = ring_at(rg, m.head, cap, j).t;
+        if (newest - tt > 10) c_old++;
+        else { c_lt += tt < t0 ? 1 : 0; c_le += tt <= t1 ? 1 : 0; }
+    }
+    if (c_old) atomicAdd(&cnt[0], c_old);
+    if (c_lt) atomicAdd(&cnt[1], c_lt);
+    if (c_le) atomicAdd(&cnt[2], c_le);
+    __syncthreads();
+    int first = 0;
+    int len = hnet_ekf::select_span(m.count - cnt[0], cnt[1], cnt[2], &first);
+    if (len < 1 || len > cap || first < 0 || cnt[0] + first + len > m.count) len = 0;
+    for (int k = t; k < len; k += THREADS) lin[k] = ring_at(rg, m.head, cap, cnt[0] + first + k);
+    __syncthreads();
+    return len;
+}
 }  // namespace
 
 // feed: segment blockIdx.y's readings fed[src0 .. src0 + n) -> ring positions (wpos + k) % cap of session id; one lane records the ring's new head / count
@@ -352,13 +402,12 @@ __global__ __launch_bounds__(FILTER_THREADS) void filter_init_kernel(const Advan
         res[b] = AdvanceResult{S.t, 1, 0};
     }
     __syncthreads();
-    store_rec(work[b], S);
+    copy_rec(work[b], S);
 }
 
 // Selection (hnet_ekf::select_imu_readings) for the listed sessions straight from the ring, one workgroup each: window [state t, t_frame] + cam_imu_dt,
-// the state's time read from state[id] (work[b] after the initialiser).  All lanes count the readings more than 10 s behind the newest (never used:
-// hnet_ekf::trim_imu_prop), those before the window's start and those up to its end; hnet_ekf::select_span turns the counts into the span the
-// header's loop can touch; the span is copied out of the ring (it may wrap) and lane 0 runs the header's function on it.
+// the state's time read from state[id] (work[b] after the initialiser).  ring_span copies the span the header's loop can touch out of the ring and lane 0
+// runs the header's function on it.
 // sel + b * 2 * (cap + 2): the span [cap + 2], then the selected readings [cap + 2]; res[b].n_sel their number.
 __global__ __launch_bounds__(FILTER_THREADS) void filter_select_kernel(const AdvanceJob* __restrict__ job, int n_sessions, int cap, const hnet_ekf::ImuData* __restrict__ ring,
                                                                        const ImuRingMeta* __restrict__ meta, const FilterRec* __restrict__ state,
@@ -375,29 +424,11 @@ __global__ __launch_bounds__(FILTER_THREADS) void filter_select_kernel(const Adv
     if (!(jb.t_frame > t_state)) return;                                     // initialised later than this frame (VioManager.cpp:203-206) or at it: nothing to select
     const ImuRingMeta m = meta[id];
     if (!ring_ok(m, cap) || m.count < 1) return;
-    const hnet_ekf::ImuData* rg = ring + (size_t)id * cap;
     const double t0 = t_state + jb.cam_imu_dt, t1 = jb.t_frame + jb.cam_imu_dt;
-    const double newest = ring_at(rg, m.head, cap, m.count - 1).t;
-    if (t < 3) cnt[t] = 0;
-    __syncthreads();
-    int c_old = 0, c_lt = 0, c_le = 0;
-    for (int j = t; j < m.count; j += FILTER_THREADS) {
-        const double tt = ring_at(rg, m.head, cap, j).t;
-        if (newest - tt > 10) c_old++;
-        else { c_lt += tt < t0 ? 1 : 0; c_le += tt <= t1 ? 1 : 0; }
-    }
-    if (c_old) atomicAdd(&cnt[0], c_old);
-    if (c_lt) atomicAdd(&cnt[1], c_lt);
-    if (c_le) atomicAdd(&cnt[2], c_le);
-    __syncthreads();
-    int first = 0;
-    const int n_u = m.count - cnt[0];
-    const int len = hnet_ekf::select_span(n_u, cnt[1], cnt[2], &first);
-    if (len < 1 || len > cap || first < 0 || cnt[0] + first + len > m.count) return;
     hnet_ekf::ImuData* lin = sel + (size_t)b * 2 * (cap + 2);
     hnet_ekf::ImuData* out = lin + (cap + 2);
-    for (int k = t; k < len; k += FILTER_THREADS) lin[k] = ring_at(rg, m.head, cap, cnt[0] + first + k);
-    __syncthreads();
+    const int len = ring_span<FILTER_THREADS>(ring + (size_t)id * cap, m, cap, t0, t1, cnt, lin);    // (every return above is uniform over the workgroup)
+    if (len == 0) return;
     if (t == 0) res[b].n_sel = hnet_ekf::select_imu_readings(lin, len, t0, t1, out);          // writes at most len + 2 readings
 }
 
@@ -406,7 +437,7 @@ __global__ __launch_bounds__(FILTER_THREADS) void filter_scatter_ok_kernel(const
                                                                            const AdvanceResult* __restrict__ res, int n_sessions, FilterRec* __restrict__ state) {
     const int b = blockIdx.x, id = job[b].id;
     if (id < 0 || id >= n_sessions || !res[b].ok) return;
-    store_rec(state[id], work[b]);
+    copy_rec(state[id], work[b]);
 }
 
 // ---- prediction between frames (hnet_filters_predict) ----
@@ -414,14 +445,23 @@ __global__ __launch_bounds__(FILTER_THREADS) void filter_scatter_ok_kernel(const
 namespace {
 constexpr int REC_MEAN_DOUBLES = 29;                                          // t, then p q v ba bg offset: everything of a FilterRec before cov
 static_assert(offsetof(FilterRec, s) + offsetof(hnet_ekf::State, cov) == REC_MEAN_DOUBLES * sizeof(double), "t and the mean are the record's first 29 doubles");
+
+// what the reference's publishers form from the mean s at camera time t (hnet_ekf::odometry_from_state + prior_pixels) and the interval count, into the
+// LDS record R; one lane
+__device__ inline void predict_record(const hnet_ekf::State& s, double t, double cam_imu_dt, int intervals, PredictOut& R) {
+    hnet_ekf::odometry_from_state(s, t, cam_imu_dt, R.o);
+    double prior_cam[8];
+    hnet_ekf::prior_pixels(s, R.prior_px, prior_cam);
+    R.intervals = intervals;
+}
 }  // namespace
 
 // The mean of each listed session at job[b].t_query and what the reference's publishers form from it (hnet_ekf::propagate_mean_with_imu +
 // odometry_from_state + prior_pixels), one wavefront per session: the chain of mean updates is serial, the parallelism is across the sessions.  Of
 // state[id] only t and the mean are read: S has room for the covariance only because propagate_mean takes a State&, S.s.cov is never loaded and
-// nothing here may read it.  The ring is counted and the span copied as filter_select_kernel does, restated here and not shared with it, so that the
-// advance's kernel stays textually as it was and keeps its code; lane 0 then runs the header's selection and mean loop on it.  Reads state / ring / meta / params, writes out[b] and
-// scratch + b * 2 * (cap + 2) (the span [cap + 2], then the selection [cap + 2]) only.  A job the host refused (NO_STATE / WAIT_IMU) gets a zero
+// nothing here may read it.  ring_span copies the span out of the ring, as for filter_select_kernel; lane 0 then runs the header's selection and mean
+// loop on it and forms the record (predict_record).  Reads state / ring / meta / params, writes out[b] and scratch + b * 2 * (cap + 2) (the span
+// [cap + 2], then the selection [cap + 2]) only.  A job the host refused (NO_STATE / WAIT_IMU) gets a zero
 // record with that status, as does a ring the kernel finds empty or inconsistent (WAIT_IMU); t_query <= the state's t gives the state as it is
 // (AT_STATE, 0 intervals).
 __global__ __launch_bounds__(PREDICT_THREADS) void filter_predict_kernel(const PredictJob* __restrict__ job, int n_sessions, int cap,
@@ -436,7 +476,6 @@ __global__ __launch_bounds__(PREDICT_THREADS) void filter_predict_kernel(const P
     const int id = jb.id;
     double* rw = reinterpret_cast<double*>(&R);
     for (int i = t; i < PREDICT_OUT_DOUBLES; i += PREDICT_THREADS) rw[i] = 0.0;          // (all-zero bits: intervals and status too)
-    if (t < 3) cnt[t] = 0;
     __syncthreads();
     int status = (id >= 0 && id < n_sessions) ? jb.status : PRED_NO_STATE;                // (host-validated; uniform over the workgroup, as every test below)
     if (status == PRED_OK) {
@@ -451,36 +490,14 @@ __global__ __launch_bounds__(PREDICT_THREADS) void filter_predict_kernel(const P
         else {
             const ImuRingMeta m = meta[id];
             if (!ring_ok(m, cap) || m.count < 1) status = PRED_WAIT_IMU;          // (the host's mirror says so first: an empty ring has no reading past the query)
-            else {
-                const hnet_ekf::ImuData* rg = ring + (size_t)id * cap;
-                const double t0 = t_state + jb.cam_imu_dt, t1 = jb.t_query + jb.cam_imu_dt;
-                const double newest = ring_at(rg, m.head, cap, m.count - 1).t;
-                int c_old = 0, c_lt = 0, c_le = 0;
-                for (int j = t; j < m.count; j += PREDICT_THREADS) {
-                    const double tt = ring_at(rg, m.head, cap, j).t;
-                    if (newest - tt > 10) c_old++;
-                    else { c_lt += tt < t0 ? 1 : 0; c_le += tt <= t1 ? 1 : 0; }
-                }
-                if (c_old) atomicAdd(&cnt[0], c_old);
-                if (c_lt) atomicAdd(&cnt[1], c_lt);
-                if (c_le) atomicAdd(&cnt[2], c_le);
-                __syncthreads();
-                int first = 0;
-                len = hnet_ekf::select_span(m.count - cnt[0], cnt[1], cnt[2], &first);
-                if (len < 1 || len > cap || first < 0 || cnt[0] + first + len > m.count) len = 0;
-                for (int k = t; k < len; k += PREDICT_THREADS) lin[k] = ring_at(rg, m.head, cap, cnt[0] + first + k);
-                __syncthreads();
-            }
+            else len = ring_span<PREDICT_THREADS>(ring + (size_t)id * cap, m, cap, t_state + jb.cam_imu_dt, jb.t_query + jb.cam_imu_dt, cnt, lin);
         }
         if (t == 0 && status != PRED_WAIT_IMU) {
             const FilterParams& pr = params[id];
             int done = 0;
             if (status == PRED_OK)                                                      // the selection writes at most len + 2 readings
                 done = hnet_ekf::propagate_mean_with_imu(S.s, pr.ext, t_state, jb.t_query, lin, len, pr.gravity_mag, pr.imu_avg != 0, jb.cam_imu_dt, lin + (cap + 2));
-            hnet_ekf::odometry_from_state(S.s, status == PRED_OK ? jb.t_query : t_state, jb.cam_imu_dt, R.o);
-            double prior_cam[8];
-            hnet_ekf::prior_pixels(S.s, R.prior_px, prior_cam);
-            R.intervals = done;
+            predict_record(S.s, status == PRED_OK ? jb.t_query : t_state, jb.cam_imu_dt, done, R);
         }
     }
     if (t == 0) R.status = status;
@@ -492,12 +509,9 @@ __global__ __launch_bounds__(PREDICT_THREADS) void filter_predict_kernel(const P
 // ---- prediction between frames with the covariance (hnet_filters_predict_cov) ----
 
 // filter_predict_kernel's record plus the covariance at the query time, one workgroup of FILTER_THREADS per listed session; read-only.
-// Status, ring count and span copy are filter_predict_kernel's, restated (that kernel and filter_select_kernel keep their text and their code); lane 0
-// runs the header's select_imu_readings on the span.  The intervals then run as in filter_propagate_kernel, every operation in that kernel's order, so
-// mean and covariance are the advance's bit for bit before its reset: per interval lane 0 forms the inputs, the Jacobians and the mean, all lanes
-// T = F P and T F^T + Fw diag(q) Fw^T.  One difference that costs no bit: F and Fw are zeroed ONCE by all lanes and lane 0 calls the header's
-// propagate_jacobians_fill, which writes the same entries in every interval, where propagate_jacobians clears both per interval on one lane.
-// Then lane 0 forms the record as filter_predict_kernel does (the same header calls in the same order) and the 6 x 6 pose Jacobian; the derived
+// The status rules are filter_predict_kernel's and ring_span copies the span; lane 0 runs the header's select_imu_readings on it.  The intervals are
+// filter_propagate_kernel's: cov_interval's body, every operation in its order (restated, see there), so mean and covariance are the advance's bit
+// for bit before its reset.  Then lane 0 forms the record as filter_predict_kernel does (predict_record) and the 6 x 6 pose Jacobian; the derived
 // blocks of hnet_ekf::odometry_cov_from_state go one element per lane through the header's element functions.  AT_STATE: the state's covariance as
 // it is and its blocks; NO_STATE / WAIT_IMU: zero records and a zero row of `full`.  Reads state / ring / meta / params, writes out[b], cov_out[b],
 // full + b * 729 (if given) and scratch + b * 2 * (cap + 2) only.
@@ -510,48 +524,29 @@ __global__ __launch_bounds__(FILTER_THREADS) void filter_predict_cov_kernel(cons
     __shared__ double F[NE], Fw[NS * NW], T[NE];
     __shared__ PredictOut R;
     __shared__ double J[36], TJ[36];
-    __shared__ int cnt[4];                                                              // the three counts, then the number of selected readings
+    __shared__ int cnt[4];                                                              // ring_span's three counts, then the number of selected readings
     const int b = blockIdx.x, t = threadIdx.x;
     const PredictJob jb = job[b];
     const int id = jb.id;
     double* rw = reinterpret_cast<double*>(&R);
     for (int i = t; i < PREDICT_OUT_DOUBLES; i += FILTER_THREADS) rw[i] = 0.0;          // (all-zero bits: intervals and status too)
-    for (int i = t; i < NE; i += FILTER_THREADS) F[i] = 0.0;
-    for (int i = t; i < NS * NW; i += FILTER_THREADS) Fw[i] = 0.0;
-    if (t < 4) cnt[t] = 0;
+    clear_jacobians(F, Fw);
     __syncthreads();
     int status = (id >= 0 && id < n_sessions) ? jb.status : PRED_NO_STATE;              // (host-validated; uniform over the workgroup, as every test below)
     if (status == PRED_OK) {
-        load_rec(S, state[id]);
+        copy_rec(S, state[id]);
         __syncthreads();
         const FilterParams& pr = params[id];
         const double t_state = S.t;
         hnet_ekf::ImuData* lin = scratch + (size_t)b * 2 * (cap + 2);
         hnet_ekf::ImuData* rd = lin + (cap + 2);
-        int len = 0;
         if (!(jb.t_query > t_state)) status = PRED_AT_STATE;
         else {
             const ImuRingMeta m = meta[id];
             if (!ring_ok(m, cap) || m.count < 1) status = PRED_WAIT_IMU;
             else {
-                const hnet_ekf::ImuData* rg = ring + (size_t)id * cap;
                 const double t0 = t_state + jb.cam_imu_dt, t1 = jb.t_query + jb.cam_imu_dt;
-                const double newest = ring_at(rg, m.head, cap, m.count - 1).t;
-                int c_old = 0, c_lt = 0, c_le = 0;
-                for (int j = t; j < m.count; j += FILTER_THREADS) {
-                    const double tt = ring_at(rg, m.head, cap, j).t;
-                    if (newest - tt > 10) c_old++;
-                    else { c_lt += tt < t0 ? 1 : 0; c_le += tt <= t1 ? 1 : 0; }
-                }
-                if (c_old) atomicAdd(&cnt[0], c_old);
-                if (c_lt) atomicAdd(&cnt[1], c_lt);
-                if (c_le) atomicAdd(&cnt[2], c_le);
-                __syncthreads();
-                int first = 0;
-                len = hnet_ekf::select_span(m.count - cnt[0], cnt[1], cnt[2], &first);
-                if (len < 1 || len > cap || first < 0 || cnt[0] + first + len > m.count) len = 0;
-                for (int k = t; k < len; k += FILTER_THREADS) lin[k] = ring_at(rg, m.head, cap, cnt[0] + first + k);
-                __syncthreads();
+                const int len = ring_span<FILTER_THREADS>(ring + (size_t)id * cap, m, cap, t0, t1, cnt, lin);
                 if (t == 0) cnt[3] = hnet_ekf::select_imu_readings(lin, len, t0, t1, rd);    // writes at most len + 2 readings
                 __syncthreads();
             }
@@ -560,7 +555,7 @@ __global__ __launch_bounds__(FILTER_THREADS) void filter_predict_cov_kernel(cons
         if (status == PRED_OK) {
             int n_sel = cnt[3];
             if (n_sel < 0 || n_sel > cap + 2) n_sel = 0;
-            for (int k = 0; k + 1 < n_sel; k++) {                                        // filter_propagate_kernel's interval, F and Fw zeroed above
+            for (int k = 0; k + 1 < n_sel; k++) {                                        // cov_interval's body (F and Fw zeroed above)
                 if (t == 0) {
                     double w_hat[3], a_hat[3];
                     const double dt = hnet_ekf::imu_interval_inputs(S.s, rd[k], rd[k + 1], pr.imu_avg != 0, w_hat, a_hat);
@@ -578,12 +573,13 @@ __global__ __launch_bounds__(FILTER_THREADS) void filter_predict_cov_kernel(cons
                 double o[EPT];
                 for (int r = 0; r < EPT; r++) {                                          // T F^T + Fw diag(q) Fw^T
                     const int e = t + r * FILTER_THREADS;
-                    if (e >= NE) break;
-                    const int i = e / NS, j = e % NS;
-                    double a = 0.0;
-                    for (int q = 0; q < NS; q++) a += T[i * NS + q] * F[j * NS + q];
-                    for (int q = 0; q < NW; q++) a += Fw[i * NW + q] * pr.q[q] * Fw[j * NW + q];
-                    o[r] = a;
+                    if (e < NE) {
+                        const int i = e / NS, j = e % NS;
+                        double a = 0.0;
+                        for (int q = 0; q < NS; q++) a += T[i * NS + q] * F[j * NS + q];
+                        for (int q = 0; q < NW; q++) a += Fw[i * NW + q] * pr.q[q] * Fw[j * NW + q];
+                        o[r] = a;
+                    }
                 }
                 for (int r = 0; r < EPT; r++) {
                     const int e = t + r * FILTER_THREADS;
@@ -594,11 +590,8 @@ __global__ __launch_bounds__(FILTER_THREADS) void filter_predict_cov_kernel(cons
             }
         }
         if (status != PRED_WAIT_IMU) {
-            if (t == 0) {                                                                // filter_predict_kernel's record
-                hnet_ekf::odometry_from_state(S.s, status == PRED_OK ? jb.t_query : t_state, jb.cam_imu_dt, R.o);
-                double prior_cam[8];
-                hnet_ekf::prior_pixels(S.s, R.prior_px, prior_cam);
-                R.intervals = done;
+            if (t == 0) {
+                predict_record(S.s, status == PRED_OK ? jb.t_query : t_state, jb.cam_imu_dt, done, R);
                 hnet_ekf::pose_cov_jacobian(S.s, J);
             }
             __syncthreads();
@@ -633,7 +626,7 @@ static_assert(offsetof(InnovRec, nis) == 16 * sizeof(double) && offsetof(InnovRe
 
 // hnet_ekf::innovation for the measurement filter_update_kernel is about to apply in iteration `it`, one wavefront per listed session, and the gate
 // rule of hnet_ekf::iterated_update_gated.  Of work[b] only the 64 covariance elements cov[sel(i)][sel(j)] are read.  S, r and the Gauss-Jordan inverse
-// are the update kernel's (the header's operations in the header's order, one matrix element per lane); y = S^-1 r by lanes 0 .. 7 and the NIS as a
+// are the update kernel's (S and r formed as it forms them, the inverse by invert8_lanes); y = S^-1 r by lanes 0 .. 7 and the NIS as a
 // serial sum in the header's order.  Flags: a session whose earlier update of this step found S singular (updates[b] < 0), or whose earlier record is
 // REJECTED / SKIPPED, is SKIPPED; a closed reference gate otherwise gives NONE; both leave r, s_diag and nis zero.  A rejection writes 0 to gate[b],
 // which is what makes filter_update_kernel skip this and the later updates and still do the last iteration's reset.  Writes innov[it * n + b] and
@@ -672,33 +665,7 @@ __global__ __launch_bounds__(INNOV_THREADS) void filter_innovation_kernel(const 
     if (t < 8) r[t] = (double)nm[t] / hnet_ekf::F_PIX - prior_cam[(size_t)b * 8 + t];
     __syncthreads();
     if (t < 8) sd[t] = A[t * 9];
-    // hnet_ekf::invert(A, 8) as in filter_update_kernel: lane t holds element (i, j) of both A and V
-    bool singular = false;
-    for (int col = 0; col < 8; col++) {
-        int piv = col;
-        for (int q = col + 1; q < 8; q++)
-            if (fabs(A[q * 8 + col]) > fabs(A[piv * 8 + col])) piv = q;
-        if (A[piv * 8 + col] == 0.0) { singular = true; break; }                 // (every lane sees the same LDS values)
-        __syncthreads();
-        if (piv != col && t < 16) {
-            double* X = t < 8 ? A : V;
-            const double tmp = X[col * 8 + j];
-            X[col * 8 + j] = X[piv * 8 + j];
-            X[piv * 8 + j] = tmp;
-        }
-        __syncthreads();
-        const double d = 1.0 / A[col * 8 + col];
-        __syncthreads();
-        if (t < 16) (t < 8 ? A : V)[col * 8 + j] *= d;
-        __syncthreads();
-        const double f = A[i * 8 + col];
-        __syncthreads();
-        if (i != col && f != 0.0) {
-            A[t] -= f * A[col * 8 + j];
-            V[t] -= f * V[col * 8 + j];
-        }
-        __syncthreads();
-    }
+    const bool singular = invert8_lanes(A, V);
     double nis = (double)NAN;
     if (singular) flag = hnet_ekf::INNOV_SINGULAR;
     else {

@@ -153,13 +153,16 @@ def test_singular_s_advance(blob, ref, iref):
     f.close(); s.close(); e.close()
 
 
-def test_pivoting_swaps_rows_on_the_device(blob, ref, iref):
-    """B. 8 sessions whose S pivots (4 with k_net_cov = 0, 4 with the default), one iteration, no IMU readings: states, updates and records against the
-    host header at the existing gates.  The swap columns are those of the S the device saw; too few of them fail the test."""
+@pytest.mark.parametrize("innov", [False, True], ids=["plain", "innov"])
+def test_pivoting_swaps_rows_on_the_device(blob, ref, iref, innov):
+    """B. 8 sessions whose S pivots (4 with k_net_cov = 0, 4 with the default), one iteration, no IMU readings: states, updates and (innov) records
+    against the host header at the existing gates.  The swap columns are those of the S the device saw; too few of them fail the test.  plain:
+    filter_update_kernel's inverse alone; innov: filter_innovation_kernel inverts the same S in front of it."""
     _capi, _, _, HnetFilters = tg._mods()
     n, iters = 8, 1
     e, s, f = tg._setup(blob, n, iters)
-    f.enable_innovations()
+    if innov:
+        f.enable_innovations()
     t_frame = fe.T_FRAME
     rng = np.random.default_rng(41)
     sts, ps = [], []
@@ -175,7 +178,7 @@ def test_pivoting_swaps_rows_on_the_device(blob, ref, iref):
     imus = [tg._imu(None, 0.0, 0)] * n
     ids = np.arange(n, dtype=np.int32)
     out, net, upd = f.step(ids, [t_frame] * n, imus)
-    recs = f.last_innovations(n)
+    recs = f.last_innovations(n) if innov else None
     cols, worst = set(), {"mean": 0.0, "cov": 0.0, "corr": 0.0, "r": 0.0, "s_diag": 0.0, "nis": 0.0}
     for i in range(n):
         want, u, rec = tgi._host(ref, iref, sts[i][0], ps[i], t_frame, imus[i], net[:, i, :], 1, 0.0)
@@ -187,11 +190,12 @@ def test_pivoting_swaps_rows_on_the_device(blob, ref, iref):
               f"{fe.mean_dev(out[i], want[0]):.3e} cov {fe.cov_dev_max(out[i]['cov'], want[0]['cov']):.3e} corr {fe.cov_dev_corr(out[i]['cov'], want[0]['cov']):.3e}")
         assert col is None and len(swaps) >= fe.MIN_SWAPS, (i, swaps)
         cols |= set(swaps)
-        assert upd[i] == u == 1 and list(recs["flag"][:, i]) == list(rec["flag"]) == [USED]
+        assert upd[i] == u == 1 and list(rec["flag"]) == [USED]
+        assert not innov or list(recs["flag"][:, i]) == [USED]
         worst["mean"] = max(worst["mean"], fe.mean_dev(out[i], want[0]))
         worst["cov"] = max(worst["cov"], fe.cov_dev_max(out[i]["cov"], want[0]["cov"]))
         worst["corr"] = max(worst["corr"], fe.cov_dev_corr(out[i]["cov"], want[0]["cov"]))
-        for fld in ("r", "s_diag", "nis"):
+        for fld in ("r", "s_diag", "nis") if innov else ():
             worst[fld] = max(worst[fld], tgi._rel(recs[fld][:, i], rec[fld]))
     print(f"pivoting: {len(cols)} distinct swap columns {sorted(cols)}; largest differences {worst}")
     assert len(cols) >= fe.MIN_SWAP_COLUMNS, cols
