@@ -46,6 +46,7 @@ SYMBOLS = [
     "hnet_op_photo_residual", "hnet_sessions_photo_residual", "hnet_filters_enable_photometric", "hnet_filters_last_photometric",
     "hnet_filters_set_photo_gate", "hnet_filters_photo_stats", "hnet_filters_reset_photo_stats", "hnet_filters_set_photo_gate_taps",
     "hnet_photo_align_default_opts", "hnet_op_photo_align", "hnet_sessions_photo_align", "hnet_last_photo_align_device_ms",
+    "hnet_op_photo_align_pyramid", "hnet_sessions_photo_align_pyramid", "hnet_op_photo_pyramid",
 ]
 # hnet_filters_advance's status per listed session (include/hnet.h HNET_ADV_*)
 ADV_STEPPED, ADV_WAIT_IMU, ADV_WAIT_INIT, ADV_INITIALIZED, ADV_PROPAGATED, ADV_NO_FRAME = range(6)
@@ -122,6 +123,8 @@ PHOTO_ALIGN_DTYPE = _np.dtype([("offsets_px", "<f4", 8), ("mse0", "<f8"), ("mse"
 assert PHOTO_ALIGN_DTYPE.itemsize == 656      # (pad: the C struct's alignment gap, written as 0 - named, so that numpy copies it and records compare byte for byte)
 ALIGN_CONVERGED, ALIGN_SINGULAR, ALIGN_DEGENERATE, ALIGN_FEW_PIXELS = 1, 2, 4, 8
 ALIGN_MAX_ITERATIONS = 32
+ALIGN_MAX_LEVELS = 4                          # hnet_op_photo_align_pyramid: levels 1 .. 4
+PHOTO_PYRAMID_BYTES = 17920 + 4480 + 1120     # hnet_op_photo_pyramid: levels 1 .. 3 of one frame, packed
 
 
 class PhotoAlignOpts(C.Structure):
@@ -299,6 +302,9 @@ def lib():
     L.hnet_op_photo_align.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp]
     L.hnet_sessions_photo_align.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     L.hnet_last_photo_align_device_ms.argtypes = [vp]
+    L.hnet_op_photo_align_pyramid.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp]
+    L.hnet_sessions_photo_align_pyramid.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp, vp]
+    L.hnet_op_photo_pyramid.argtypes = [vp, vp, C.c_int, vp]
     L.hnet_last_photo_align_device_ms.restype = C.c_double
     for name in SYMBOLS:
         getattr(L, name)   # AttributeError here = the library does not export what include/hnet.h declares

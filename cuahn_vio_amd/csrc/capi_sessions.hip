@@ -362,11 +362,13 @@ int hnet_sessions_photo_residual(hnet_sessions* s, int n, const int32_t* ids, co
 
 // ---- photometric alignment (include/hnet.h hnet_photo_align) on the sessions' current pairs; read-only like the records above ----
 
-int hnet_sessions_photo_align(hnet_sessions* s, int n, const int32_t* ids, const float* offsets0_px, const hnet_photo_align_opts* opts, hnet_photo_align* out) {
+static int sessions_photo_align(hnet_sessions* s, int n, const int32_t* ids, const float* offsets0_px, const hnet_photo_align_opts* opts, int levels,
+                                hnet_photo_align* out, hnet_photo_align* levels_out, const char* who) {
     if (!s) return HNET_ERR_INVALID_ARG;
     hnet_ctx* c = s->ctx;
-    if (!offsets0_px || !out) return fail(c, HNET_ERR_INVALID_ARG, "hnet_sessions_photo_align: offsets / out");
-    int rc = photo_align_check_opts(c, opts, "hnet_sessions_photo_align");
+    if (!offsets0_px || !out) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": offsets / out");
+    if (levels < 1 || levels > HNET_ALIGN_MAX_LEVELS) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": 1 <= levels <= 4");
+    int rc = photo_align_check_opts(c, opts, who);
     if (rc == HNET_OK) rc = sessions_check_ids(s, n, ids);
     if (rc == HNET_OK) rc = sessions_check_pairs(s, n, ids);
     if (rc != HNET_OK) return rc;
@@ -382,7 +384,18 @@ int hnet_sessions_photo_align(hnet_sessions* s, int n, const int32_t* ids, const
     hipStream_t st = c->stream;
     HIPCHK(c, hipMemcpyAsync(d_in, h_in.data(), up, hipMemcpyHostToDevice, st));
     HIPCHK(c, launch_session_gather(s->ring, 2 * s->n, reinterpret_cast<const int32_t*>(d_in + off_bytes), n, (uint8_t*)c->stage_prev, (uint8_t*)c->stage_curr, st));
-    return photo_align_run(c, (const uint8_t*)c->stage_prev, (const uint8_t*)c->stage_curr, n, reinterpret_cast<const float*>(d_in), *opts, out);
+    return photo_align_pyramid_run(c, (const uint8_t*)c->stage_prev, (const uint8_t*)c->stage_curr, n, reinterpret_cast<const float*>(d_in), *opts, levels, out,
+                                   levels_out);
+}
+
+int hnet_sessions_photo_align(hnet_sessions* s, int n, const int32_t* ids, const float* offsets0_px, const hnet_photo_align_opts* opts, hnet_photo_align* out) {
+    return sessions_photo_align(s, n, ids, offsets0_px, opts, 1, out, nullptr, "hnet_sessions_photo_align");
+}
+
+// the coarse-to-fine form on the sessions' current pairs; read-only in the same way
+int hnet_sessions_photo_align_pyramid(hnet_sessions* s, int n, const int32_t* ids, const float* offsets0_px, const hnet_photo_align_opts* opts, int levels,
+                                      hnet_photo_align* out, hnet_photo_align* levels_out) {
+    return sessions_photo_align(s, n, ids, offsets0_px, opts, levels, out, levels_out, "hnet_sessions_photo_align_pyramid");
 }
 
 }  // extern "C"

@@ -549,7 +549,7 @@ void hnet_destroy(hnet_ctx* c) {
     fr(c->und_map[0]); fr(c->und_map[1]); fr(c->raw_dev);
     fr(c->s2_frag[0]); fr(c->s2_frag[3]); fr(c->x16_b4); fr(c->b30_frag); fr(c->b40_frag); fr(c->b41_frag); fr(c->w1_16); fr(c->b3f_w1); fr(c->b42_w2); fr(c->b42_w3); fr(c->feat16); fr(c->head_mask);
     fr(c->ws); fr(c->w1); fr(c->b1); fr(c->w2); fr(c->b2); fr(c->hidden); fr(c->Hm); fr(c->Hm2); fr(c->Htot); fr(c->mean_s); fr(c->logvar_s);
-    fr(c->d_mean); fr(c->d_cov); fr(c->d_err); fr(c->d_err_u8); fr(c->d_prior); fr(c->stage_prev); fr(c->stage_curr);
+    fr(c->d_mean); fr(c->d_cov); fr(c->d_err); fr(c->d_err_u8); fr(c->d_prior); fr(c->stage_prev); fr(c->stage_curr); fr(c->pyr_scratch);
     fr(c->ring[0]); fr(c->ring[1]);
     for (auto e : c->prof_ev) (void)hipEventDestroy(e);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -1027,7 +1027,8 @@ static_assert(sizeof(hnet_photo_align) == sizeof(AlignRec) && offsetof(hnet_phot
               offsetof(hnet_photo_align_opts, lambda0) == offsetof(AlignOpts, lambda0), "hnet_photo_align / _opts are the layouts of include/hnet_photo_align.h");
 static_assert((int)HNET_ALIGN_CONVERGED == hnet_align::CONVERGED && (int)HNET_ALIGN_SINGULAR == hnet_align::SINGULAR &&
               (int)HNET_ALIGN_DEGENERATE == hnet_align::DEGENERATE && (int)HNET_ALIGN_FEW_PIXELS == hnet_align::FEW_PIXELS &&
-              (int)HNET_ALIGN_MAX_ITERATIONS == hnet_align::MAX_ITERATIONS, "the flags of include/hnet_photo_align.h");
+              (int)HNET_ALIGN_MAX_ITERATIONS == hnet_align::MAX_ITERATIONS && (int)HNET_ALIGN_MAX_LEVELS == hnet_align::MAX_LEVELS,
+              "the flags of include/hnet_photo_align.h");
 
 extern "C++" {
 namespace capi {
@@ -1040,26 +1041,37 @@ int photo_align_check_opts(hnet_ctx* c, const hnet_photo_align_opts* opts, const
     return HNET_OK;
 }
 
-int photo_align_run(hnet_ctx* c, const uint8_t* d_img1, const uint8_t* d_img2, int n, const float* d_x0, const hnet_photo_align_opts& opts, hnet_photo_align* out) {
+// levels = 1 is launch_photo_align's sequence and nothing else.  levels_out is transposed on the host: the device keeps the records [levels][n], a level's
+// records being what its solve launches write
+int photo_align_pyramid_run(hnet_ctx* c, const uint8_t* d_img1, const uint8_t* d_img2, int n, const float* d_x0, const hnet_photo_align_opts& opts, int levels,
+                            hnet_photo_align* out, hnet_photo_align* levels_out) {
     AlignOpts o;
     memcpy(&o, &opts, sizeof o);
+    const size_t pyr = (size_t)c->cfg.max_batch * PYR_BYTES;
+    if (levels > 1 && !c->pyr_scratch) HIPCHK(c, dalloc(&c->pyr_scratch, 2 * pyr));
     DevTemps t;
     AlignSums* d_part = nullptr;
     AlignWork* d_work = nullptr;
     AlignRec* d_rec = nullptr;
+    float* d_start = nullptr;
     HIPCHK(c, t.alloc(&d_part, (size_t)n * PHOTO_SLICES));
     HIPCHK(c, t.alloc(&d_work, (size_t)n));
-    HIPCHK(c, t.alloc(&d_rec, (size_t)n));
-    std::vector<AlignRec> h_rec((size_t)n);
+    HIPCHK(c, t.alloc(&d_rec, (size_t)n * levels));
+    if (levels > 1) HIPCHK(c, t.alloc(&d_start, (size_t)n * 8));
+    std::vector<AlignRec> h_rec((size_t)n * levels);
     HIPCHK(c, hipEventRecord(c->ev_align[0], c->stream));
-    HIPCHK(c, launch_photo_align(d_img1, d_img2, n, d_x0, o, d_part, d_work, d_rec, c->stream));
+    HIPCHK(c, launch_photo_align_pyramid(d_img1, d_img2, n, d_x0, o, levels, c->pyr_scratch, c->pyr_scratch ? c->pyr_scratch + pyr : nullptr, d_start, d_part,
+                                         d_work, d_rec, c->stream));
     HIPCHK(c, hipEventRecord(c->ev_align[1], c->stream));
-    HIPCHK(c, hipMemcpyAsync(h_rec.data(), d_rec, (size_t)n * sizeof(AlignRec), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(h_rec.data(), d_rec, h_rec.size() * sizeof(AlignRec), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     float ms = 0;
     HIPCHK(c, hipEventElapsedTime(&ms, c->ev_align[0], c->ev_align[1]));
     c->photo_align_ms = ms;
     memcpy(out, h_rec.data(), (size_t)n * sizeof(AlignRec));
+    if (levels_out)
+        for (int i = 0; i < n; i++)
+            for (int l = 0; l < levels; l++) memcpy(levels_out + (size_t)i * levels + l, &h_rec[(size_t)l * n + i], sizeof(AlignRec));
     return HNET_OK;
 }
 
@@ -1075,13 +1087,15 @@ void hnet_photo_align_default_opts(hnet_photo_align_opts* o) {
 
 double hnet_last_photo_align_device_ms(hnet_ctx* c) { return c ? c->photo_align_ms : 0.0; }
 
-// alignment of n host frame pairs from offsets0_px: ONE upload {img1 | img2 | offsets}, max_iterations + 1 pairs of launches, ONE download, one synchronisation
-int hnet_op_photo_align(hnet_ctx* c, const uint8_t* img1, const uint8_t* img2, int n, const float* offsets0_px, const hnet_photo_align_opts* opts, hnet_photo_align* out) {
+// alignment of n host frame pairs from offsets0_px: ONE upload {img1 | img2 | offsets}, the launch sequence of `levels` levels, ONE download, one synchronisation
+static int op_photo_align(hnet_ctx* c, const uint8_t* img1, const uint8_t* img2, int n, const float* offsets0_px, const hnet_photo_align_opts* opts, int levels,
+                          hnet_photo_align* out, hnet_photo_align* levels_out, const char* who) {
     if (!c) return HNET_ERR_INVALID_ARG;
-    if (!img1 || !img2 || !offsets0_px || !out || n < 1) return fail(c, HNET_ERR_INVALID_ARG, "hnet_op_photo_align: frames / offsets / out, n >= 1");
-    const int rc = photo_align_check_opts(c, opts, "hnet_op_photo_align");
+    if (!img1 || !img2 || !offsets0_px || !out || n < 1) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": frames / offsets / out, n >= 1");
+    if (levels < 1 || levels > HNET_ALIGN_MAX_LEVELS) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": 1 <= levels <= 4");
+    const int rc = photo_align_check_opts(c, opts, who);
     if (rc != HNET_OK) return rc;
-    if (n > c->cfg.max_batch) return fail(c, HNET_ERR_CAPACITY, "hnet_op_photo_align: n exceeds max_batch");
+    if (n > c->cfg.max_batch) return fail(c, HNET_ERR_CAPACITY, std::string(who) + ": n exceeds max_batch");
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
     const size_t img = (size_t)n * NPIX, off_bytes = (size_t)n * 8 * sizeof(float), up = 2 * img + off_bytes;      // (NPIX is a multiple of 16: every section stays aligned)
     DevTemps t;
@@ -1092,7 +1106,36 @@ int hnet_op_photo_align(hnet_ctx* c, const uint8_t* img1, const uint8_t* img2, i
     memcpy(h_in.data() + img, img2, img);
     memcpy(h_in.data() + 2 * img, offsets0_px, off_bytes);
     HIPCHK(c, hipMemcpyAsync(d_in, h_in.data(), up, hipMemcpyHostToDevice, c->stream));
-    return photo_align_run(c, d_in, d_in + img, n, reinterpret_cast<const float*>(d_in + 2 * img), *opts, out);
+    return photo_align_pyramid_run(c, d_in, d_in + img, n, reinterpret_cast<const float*>(d_in + 2 * img), *opts, levels, out, levels_out);
+}
+
+int hnet_op_photo_align(hnet_ctx* c, const uint8_t* img1, const uint8_t* img2, int n, const float* offsets0_px, const hnet_photo_align_opts* opts, hnet_photo_align* out) {
+    return op_photo_align(c, img1, img2, n, offsets0_px, opts, 1, out, nullptr, "hnet_op_photo_align");
+}
+
+// the coarse-to-fine form: the pyramid launch and one launch sequence per level
+int hnet_op_photo_align_pyramid(hnet_ctx* c, const uint8_t* img1, const uint8_t* img2, int n, const float* offsets0_px, const hnet_photo_align_opts* opts, int levels,
+                                hnet_photo_align* out, hnet_photo_align* levels_out) {
+    return op_photo_align(c, img1, img2, n, offsets0_px, opts, levels, out, levels_out, "hnet_op_photo_align_pyramid");
+}
+
+// operator level: levels 1 .. 3 of n host frames -> out [n][PYR_BYTES]
+int hnet_op_photo_pyramid(hnet_ctx* c, const uint8_t* img, int n, uint8_t* out) {
+    if (!c) return HNET_ERR_INVALID_ARG;
+    if (!img || !out || n < 1) return fail(c, HNET_ERR_INVALID_ARG, "hnet_op_photo_pyramid: frames / out, n >= 1");
+    if (n > c->cfg.max_batch) return fail(c, HNET_ERR_CAPACITY, "hnet_op_photo_pyramid: n exceeds max_batch");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    DevTemps t;
+    uint8_t *d_in = nullptr, *d_out = nullptr;
+    HIPCHK(c, t.alloc(&d_in, (size_t)n * NPIX));
+    HIPCHK(c, t.alloc(&d_out, (size_t)n * PYR_BYTES));
+    std::vector<uint8_t> h_out((size_t)n * PYR_BYTES);
+    HIPCHK(c, hipMemcpyAsync(d_in, img, (size_t)n * NPIX, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, launch_photo_pyramid(d_in, nullptr, n, d_out, nullptr, c->stream));
+    HIPCHK(c, hipMemcpyAsync(h_out.data(), d_out, h_out.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    memcpy(out, h_out.data(), h_out.size());
+    return HNET_OK;
 }
 
 // the end of the layer-level operator entry points: n_out floats of the device result d_d to the host

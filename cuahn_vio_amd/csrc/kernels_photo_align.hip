@@ -28,37 +28,12 @@ namespace pa = hnet_align;
 namespace {
 constexpr int PA_THREADS = 256, PA_WAVES = PA_THREADS / 64;
 constexpr int PA_QUADS = PHOTO_SLICE_PIX / (4 * PA_THREADS);                  // 10 quads per thread
-constexpr int PA_ND = pa::NSYM + pa::NH + 1;                                   // 55 double sums: ss | sr | rr, the order of AlignSums
 static_assert(offsetof(AlignSums, sr) == pa::NSYM * 8 && offsetof(AlignSums, rr) == (pa::NSYM + pa::NH) * 8 && offsetof(AlignSums, n_valid) == PA_ND * 8,
               "AlignSums is 55 doubles, then the count");
 // dynamic LDS of the accumulate kernel: img2 | per-wave sums [4][55] f64 | per-wave counts [4] i32 | H [9] f32 | flag
 constexpr int PA_LDS_BYTES = NPIX + PA_WAVES * PA_ND * 8 + PA_WAVES * 4 + 9 * 4 + 4;      // 73 496: two workgroups per CU
 static_assert(NPIX % 16 == 0 && 2 * PA_LDS_BYTES <= 160 * 1024, "aligned sections; two workgroups share a CU's LDS");
 
-__device__ __forceinline__ double pa_wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off);
-    return v;
-}
-__device__ __forceinline__ int pa_wave_sum(int v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off);
-    return v;
-}
-
-// H = (float) dlt_solve(p4 + x) as photo_slice_body forms it; false (and NaN entries) when an entry is not finite
-__device__ __forceinline__ bool pa_homography(const float* x, float* h) {
-    double d[8], hd[9];
-#pragma unroll
-    for (int k = 0; k < 8; k++) d[k] = pa::corner(p4(k), x[k]);
-    dlt_solve(d, hd);
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < 9; k++) ok = ok && isfinite((float)hd[k]);
-#pragma unroll
-    for (int k = 0; k < 9; k++) h[k] = ok ? (float)hd[k] : __builtin_nanf("");
-    return ok;
-}
 }  // namespace
 
 // grid: PHOTO_SLICES * n workgroups (slice = block % PHOTO_SLICES).  x0 != nullptr: the first linearisation, at x0 [n][8]; otherwise at work[pair].x_trial,
@@ -207,6 +182,11 @@ hipError_t photo_align_init_device() {
     return hipFuncSetAttribute((const void*)photo_align_accum_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, PA_LDS_BYTES);
 }
 
+hipError_t launch_photo_align_solve(const AlignSums* partial, const float* x0, int it, const AlignOpts& opts, int n, AlignWork* work, AlignRec* rec, hipStream_t s) {
+    hipLaunchKernelGGL(photo_align_solve_kernel, dim3((unsigned)n), dim3(64), 0, s, partial, x0, it, opts, work, rec);
+    return hipGetLastError();
+}
+
 hipError_t launch_photo_align(const uint8_t* img1, const uint8_t* img2, int n, const float* x0, const AlignOpts& opts, AlignSums* partial, AlignWork* work,
                               AlignRec* rec, hipStream_t s) {
     if (n < 1 || n > (1 << 20) || !img1 || !img2 || !x0 || !partial || !work || !rec || !pa::opts_valid(opts)) return hipErrorInvalidValue;
@@ -216,8 +196,7 @@ hipError_t launch_photo_align(const uint8_t* img1, const uint8_t* img2, int n, c
                            (const AlignWork*)work, (const AlignRec*)rec, partial);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(photo_align_solve_kernel, dim3((unsigned)n), dim3(64), 0, s, (const AlignSums*)partial, x0, it, opts, work, rec);
-        e = hipGetLastError();
+        e = launch_photo_align_solve(partial, x0, it, opts, n, work, rec, s);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;

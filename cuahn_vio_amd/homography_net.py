@@ -277,6 +277,31 @@ class HnetEngine:
         check(self._h, self._L.hnet_op_photo_align(self._h, a.ctypes.data, b.ctypes.data, n, off.ctypes.data, C.addressof(o), out.ctypes.data))
         return out
 
+    def op_photo_align_pyramid(self, img1, img2, offsets0, levels=4, want_levels=False, **opts):
+        """coarse-to-fine photometric alignment (hnet_op_photo_align_pyramid): as op_photo_align, one complete alignment per pyramid level from
+        levels - 1 down to 0 (max_iterations is per level) -> the level-0 records [n]; want_levels: (those, every level's records [n, levels],
+        index = level)"""
+        a = np.ascontiguousarray(img1, dtype=np.uint8).reshape(-1, IMG_H, IMG_W)
+        b = np.ascontiguousarray(img2, dtype=np.uint8).reshape(-1, IMG_H, IMG_W)
+        n = a.shape[0]
+        if b.shape[0] != n:
+            raise ValueError("img1 and img2 must hold the same number of frames")
+        off = np.ascontiguousarray(offsets0, dtype=np.float32).reshape(n, 8)
+        o = _capi.photo_align_opts(**opts)
+        out = np.zeros(n, _capi.PHOTO_ALIGN_DTYPE)
+        lv = np.zeros((n, max(int(levels), 1)), _capi.PHOTO_ALIGN_DTYPE) if want_levels else None
+        check(self._h, self._L.hnet_op_photo_align_pyramid(self._h, a.ctypes.data, b.ctypes.data, n, off.ctypes.data, C.addressof(o), int(levels),
+                                                           out.ctypes.data, lv.ctypes.data if want_levels else None))
+        return (out, lv) if want_levels else out
+
+    def op_photo_pyramid(self, img):
+        """levels 1 .. 3 of uint8 frames [n, 224, 320] (hnet_op_photo_pyramid) -> uint8 [n, _capi.PHOTO_PYRAMID_BYTES]: 160 x 112, 80 x 56 and
+        40 x 28 pixels per frame, level 1 first"""
+        a = np.ascontiguousarray(img, dtype=np.uint8).reshape(-1, IMG_H, IMG_W)
+        out = np.zeros((a.shape[0], _capi.PHOTO_PYRAMID_BYTES), np.uint8)
+        check(self._h, self._L.hnet_op_photo_pyramid(self._h, a.ctypes.data, a.shape[0], out.ctypes.data))
+        return out
+
     def last_photo_align_device_ms(self):
         """device time of the launch sequence of the last alignment call on this context (operator or sessions), milliseconds"""
         return float(self._L.hnet_last_photo_align_device_ms(self._h))
@@ -577,6 +602,18 @@ class HnetSessions:
         out = np.zeros(n, _capi.PHOTO_ALIGN_DTYPE)
         self._check(self._L.hnet_sessions_photo_align(self._s, n, ids.ctypes.data, off.ctypes.data, C.addressof(o), out.ctypes.data))
         return out
+
+    def photo_align_pyramid(self, ids, offsets0, levels=4, want_levels=False, **opts):
+        """coarse-to-fine photometric alignment of the listed sessions' current pairs (hnet_sessions_photo_align_pyramid); read-only; arguments and
+        result as HnetEngine.op_photo_align_pyramid"""
+        ids, n = self._ids(ids)
+        off = np.ascontiguousarray(offsets0, dtype=np.float32).reshape(n, 8)
+        o = _capi.photo_align_opts(**opts)
+        out = np.zeros(n, _capi.PHOTO_ALIGN_DTYPE)
+        lv = np.zeros((n, max(int(levels), 1)), _capi.PHOTO_ALIGN_DTYPE) if want_levels else None
+        self._check(self._L.hnet_sessions_photo_align_pyramid(self._s, n, ids.ctypes.data, off.ctypes.data, C.addressof(o), int(levels), out.ctypes.data,
+                                                              lv.ctypes.data if want_levels else None))
+        return (out, lv) if want_levels else out
 
     def image_count(self, id):
         return int(self._L.hnet_sessions_image_count(self._s, int(id)))

@@ -605,7 +605,8 @@ int  hnet_filters_set_photo_gate_taps(hnet_filters* f, int from_global);
  * No flag: max_iterations trials were made.  max_iterations = 0 is the linearisation alone (info, grad, mse at offsets0_px).
  * `info` is an INFORMATION matrix, not a calibrated covariance: sigma^2 A^-1 with sigma^2 = mse understates the error of offsets_px severalfold (u8
  * rounding and interpolation error are not white noise).  Its scaling is the caller's.
- * The basin of convergence is the texture scale (no image pyramid): start within a few pixels of the truth on fine texture. */
+ * The basin of convergence of this single-level call is the texture scale: start within a pixel or two of the truth on fine texture.  A start that is further
+ * off belongs to hnet_op_photo_align_pyramid below, which runs the same alignment coarse to fine over an image pyramid. */
 typedef struct hnet_photo_align_opts { int32_t max_iterations;  /* 0 .. 32 */  int32_t min_valid;  double lambda0, eps_px; } hnet_photo_align_opts;
 void hnet_photo_align_default_opts(hnet_photo_align_opts* o);      /* 6, 20000, 1e-3, 1e-3 */
 typedef struct hnet_photo_align {
@@ -631,6 +632,29 @@ int  hnet_op_photo_align(hnet_ctx* ctx, const uint8_t* img1, const uint8_t* img2
 int  hnet_sessions_photo_align(hnet_sessions* s, int n, const int32_t* ids, const float* offsets0_px, const hnet_photo_align_opts* opts, hnet_photo_align* out);
 /* device time of the launch sequence of the context's last alignment call (HIP events of its own around it), milliseconds */
 double hnet_last_photo_align_device_ms(hnet_ctx* ctx);
+
+/* ---- coarse-to-fine photometric alignment over a device image pyramid (csrc/kernels_photo_pyramid.hip; the shared code is include/hnet_photo_pyramid.h) ----
+ * Levels 1, 2, 3 of a frame are 160 x 112, 80 x 56 and 40 x 28 u8, each the 2 x 2 box mean of the level below, (a + b + c + d + 2) >> 2, cascaded (exact
+ * integers).  A call with `levels` in 1 .. 4 runs ONE COMPLETE alignment per level, from level levels - 1 down to level 0, each from the offsets at which the
+ * level above ended (the coarsest from offsets0_px), WHATEVER that level's flags: a flag stops its own level only.  The offsets, grad, info and the steps stay
+ * in full-resolution pixels at every level; level-L pixel (u, v) stands at (2^L u + c, 2^L v + c), c = (2^L - 1) / 2, is VALID when all four taps are pixels
+ * of the level-L img2, and its gradient is taken per full-resolution pixel.  The options are the call's, max_iterations PER LEVEL and min_valid >> 2 L at
+ * level L (still floored at 9).  levels = 1 is hnet_op_photo_align, byte for byte.  With 4 levels and 8 trials per level the repository's stock texture is
+ * aligned from zero offsets when the truth is up to 32 px away, where the single-level call needs a start within about 1.5 px.
+ * out [n]: the level-0 records.  levels_out: NULL or [n][levels], index = level: the complete record of every level, its mse in grey^2 of that level's
+ * images and its n_valid* counting that level's pixels.  A start without a homography is DEGENERATE at every level, a constant img2 SINGULAR at every level
+ * with the offsets unchanged, a far-out start FEW_PIXELS at every level.
+ * Errors are those of hnet_op_photo_align, and levels outside 1 .. 4: HNET_ERR_INVALID_ARG.  An error writes nothing.  One upload, one pyramid launch, per
+ * level a gather of the start offsets and max_iterations + 1 pairs of launches, one download and one synchronisation; hnet_last_photo_align_device_ms covers
+ * the whole sequence.  The pyramid's device scratch (2 x max_batch x 23 520 bytes) is allocated by the context's first such call. */
+enum { HNET_ALIGN_MAX_LEVELS = 4 };
+int  hnet_op_photo_align_pyramid(hnet_ctx* ctx, const uint8_t* img1, const uint8_t* img2, int n, const float* offsets0_px, const hnet_photo_align_opts* opts,
+                                 int levels, hnet_photo_align* out /* [n] */, hnet_photo_align* levels_out /* NULL or [n][levels], index = level */);
+/* the same on the current pair of each listed session; read-only like hnet_sessions_photo_align, errors as there plus `levels` */
+int  hnet_sessions_photo_align_pyramid(hnet_sessions* s, int n, const int32_t* ids, const float* offsets0_px, const hnet_photo_align_opts* opts, int levels,
+                                       hnet_photo_align* out, hnet_photo_align* levels_out);
+/* operator level (tests): levels 1 .. 3 of n host frames u8 [n][224][320] -> out [n][17920 + 4480 + 1120] bytes, level 1 first.  1 <= n <= max_batch */
+int  hnet_op_photo_pyramid(hnet_ctx* ctx, const uint8_t* img, int n, uint8_t* out);
 
 int hnet_synchronize(hnet_ctx* ctx, void* stream);
 int hnet_last_timing(const hnet_ctx* ctx, hnet_timing* out);

@@ -4,6 +4,9 @@
 per batch n: hnet_last_photo_align_device_ms (HIP events around the launch sequence) at max_iterations 0 and 6, the host wall time of
 hnet_op_photo_residual with m = 1 (a call that ends in a synchronise; its kernels' own time comes from a kernel trace) and the device time of one
 forward of the same batch (hnet_sessions_last_timing).  Medians over --reps calls after --warmup; stock synthetic pairs started from the sigma = 1 prior.
+  python tools/photo_align_bench.py --levels L [--iterations K] [--batches 1 8 64]
+the coarse-to-fine call instead (hnet_op_photo_align_pyramid): per batch n the device time of L levels with K trials per level (default 8) on
+stock pairs up to 32 px apart, started from zero offsets, with the trials every level made and the worst distance from the truth.
   python tools/photo_align_bench.py --summarize DIR
 prints, from the kernel trace a `rocprofv3 --kernel-trace --output-format csv -d DIR -- python tools/photo_align_bench.py ...` run left in DIR, the mean
 duration of every photometric kernel by grid size."""
@@ -29,11 +32,33 @@ def summarize(d):
     for r in csv.DictReader(open(files[0])):
         k = re.sub(r"\(.*$", "", re.sub(r"hnet::", "", re.sub(r"^void ", "", r["Kernel_Name"])))
         if "photo" in k:
-            acc[(k, int(r.get("Grid_Size") or r["Grid_Size_X"]))].append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1000.0)
-    for (k, g), v in sorted(acc.items()):
+            dims = lambda name: int(r.get(name + "_X") or 1) * int(r.get(name + "_Y") or 1) * int(r.get(name + "_Z") or 1)      # (work-items)
+            grid = int(r["Grid_Size"]) if r.get("Grid_Size") else dims("Grid_Size")
+            wg = dims("Workgroup_Size") if r.get("Workgroup_Size_X") else 256
+            acc[(k, grid, grid // wg)].append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1000.0)
+    for (k, g, w), v in sorted(acc.items()):
         v = np.array(v)
-        print(f"{k:32s} grid {g:7d} ({g // 256 if 'accum' in k or 'residual' in k else g // 64:4d} workgroups)  x{len(v):5d}  mean {v.mean():8.2f} us  "
-              f"median {np.median(v):8.2f} us  min {v.min():8.2f} us")
+        print(f"{k:32s} grid {g:7d} ({w:4d} workgroups)  x{len(v):5d}  mean {v.mean():8.2f} us  median {np.median(v):8.2f} us  min {v.min():8.2f} us")
+
+
+def pyramid(a, blob):
+    from cuahn_vio_amd import synth
+    from cuahn_vio_amd.homography_net import HnetEngine
+    for n in a.batches:
+        pairs = [synth.make_pair(1 + i % 16, 32.0) for i in range(n)]
+        i1, i2, truth = np.stack([p[0] for p in pairs]), np.stack([p[1] for p in pairs]), np.stack([p[2] for p in pairs])
+        start = np.zeros((n, 8), np.float32)
+        e = HnetEngine(blob, variant="prior3", mc_samples=16, dropout_p=0.05, mc_seed=9, max_batch=n)
+        ms = []
+        for r in range(a.warmup + a.reps):
+            rec, lv = e.op_photo_align_pyramid(i1, i2, start, levels=a.levels, want_levels=True, max_iterations=a.iterations)
+            ms.append(e.last_photo_align_device_ms())
+        ms = np.array(ms[a.warmup:])
+        err = np.abs(rec["offsets_px"].astype(np.float64) - truth).max(axis=1)
+        trials = ", ".join(f"L{L} {lv['trials'][:, L].mean():.1f}" for L in range(a.levels - 1, -1, -1))
+        print(f"n = {n:3d}: pyramid levels={a.levels} K={a.iterations} {np.median(ms):.4f} ms (min {ms.min():.4f}); trials per pair {trials}; "
+              f"worst distance from the truth: median {np.median(err):.3f} px, max {err.max():.3f} px", flush=True)
+        e.close()
 
 
 def main():
@@ -41,6 +66,8 @@ def main():
     ap.add_argument("--batches", type=int, nargs="+", default=[1, 8, 64])
     ap.add_argument("--reps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--levels", type=int, default=0)
+    ap.add_argument("--iterations", type=int, default=8)
     ap.add_argument("--summarize")
     a = ap.parse_args()
     if a.summarize:
@@ -48,6 +75,8 @@ def main():
     from cuahn_vio_amd import synth, weights
     from cuahn_vio_amd.homography_net import HnetEngine, HnetSessions
     blob = weights.pack_state_dict(weights.synthetic_state(0))
+    if a.levels:
+        return pyramid(a, blob)
     for n in a.batches:
         pairs = [synth.make_pair(1 + i % 16, 12.0) for i in range(n)]
         i1, i2 = np.stack([p[0] for p in pairs]), np.stack([p[1] for p in pairs])
