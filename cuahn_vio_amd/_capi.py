@@ -47,6 +47,7 @@ SYMBOLS = [
     "hnet_filters_set_photo_gate", "hnet_filters_photo_stats", "hnet_filters_reset_photo_stats", "hnet_filters_set_photo_gate_taps",
     "hnet_photo_align_default_opts", "hnet_op_photo_align", "hnet_sessions_photo_align", "hnet_last_photo_align_device_ms",
     "hnet_op_photo_align_pyramid", "hnet_sessions_photo_align_pyramid", "hnet_op_photo_pyramid",
+    "hnet_photo_robust_default_opts", "hnet_op_photo_align_robust", "hnet_sessions_photo_align_robust", "hnet_photo_robust_marginal",
 ]
 # hnet_filters_advance's status per listed session (include/hnet.h HNET_ADV_*)
 ADV_STEPPED, ADV_WAIT_IMU, ADV_WAIT_INIT, ADV_INITIALIZED, ADV_PROPAGATED, ADV_NO_FRAME = range(6)
@@ -126,6 +127,11 @@ ALIGN_MAX_ITERATIONS = 32
 ALIGN_MAX_LEVELS = 4                          # hnet_op_photo_align_pyramid: levels 1 .. 4
 PHOTO_PYRAMID_BYTES = 17920 + 4480 + 1120     # hnet_op_photo_pyramid: levels 1 .. 3 of one frame, packed
 
+# hnet_photo_robust: hnet_photo_align's fields under "px", then gain, bias, the outlier counts and the ten-parameter gradient and matrix
+PHOTO_ROBUST_DTYPE = _np.dtype([("px", PHOTO_ALIGN_DTYPE), ("gain", "<f8"), ("bias", "<f8"), ("n_outliers0", "<i4"), ("n_outliers", "<i4"),
+                                ("grad10", "<f8", 10), ("info10", "<f8", (10, 10))])
+assert PHOTO_ROBUST_DTYPE.itemsize == 1560
+
 
 class PhotoAlignOpts(C.Structure):
     """hnet_photo_align_opts: trials at the most, valid pixels a point needs, initial damping, convergence threshold in pixels"""
@@ -141,6 +147,35 @@ def photo_align_opts(**kw):
             raise TypeError(f"hnet_photo_align_opts has no field {k!r}")
         setattr(o, k, v)
     return o
+
+
+class PhotoRobustOpts(C.Structure):
+    """hnet_photo_robust_opts: the alignment's options, the brightness model (0 off, 1 gain + bias), the Huber threshold in grey levels (0: quadratic) and
+    the start gain and bias"""
+    _fields_ = [("base", PhotoAlignOpts), ("brightness", C.c_int32), ("pad", C.c_int32), ("huber_k", C.c_double), ("gain0", C.c_double), ("bias0", C.c_double)]
+
+
+def photo_robust_opts(**kw):
+    """the defaults of hnet_photo_robust_default_opts with the given fields replaced (the fields of `base` by their own names)"""
+    o = PhotoRobustOpts()
+    lib().hnet_photo_robust_default_opts(C.byref(o))
+    for k, v in kw.items():
+        if k in ("max_iterations", "min_valid", "lambda0", "eps_px"):
+            setattr(o.base, k, v)
+        elif k in ("brightness", "huber_k", "gain0", "bias0"):
+            setattr(o, k, v)
+        else:
+            raise TypeError(f"hnet_photo_robust_opts has no field {k!r}")
+    return o
+
+
+def photo_robust_marginal(rec):
+    """hnet_photo_robust_marginal of one record -> (info8 [8, 8], grad8 [8]); ValueError when the brightness block has no Cholesky factor"""
+    r = _np.ascontiguousarray(rec, PHOTO_ROBUST_DTYPE).reshape(1)
+    info, grad = _np.zeros((8, 8)), _np.zeros(8)
+    if lib().hnet_photo_robust_marginal(C.c_void_p(r.ctypes.data), C.c_void_p(info.ctypes.data), C.c_void_p(grad.ctypes.data)) != 0:
+        raise ValueError("hnet_photo_robust_marginal: the brightness block has no Cholesky factor")
+    return info, grad
 
 
 # the block-4 input planes (csrc/kernels.h B4_*): [plane][pair][B4_HP][B4_WP] dwords, pixel (u, v) at row v + B4_PADY, column u + B4_PADX
@@ -305,6 +340,11 @@ def lib():
     L.hnet_op_photo_align_pyramid.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp]
     L.hnet_sessions_photo_align_pyramid.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp, vp]
     L.hnet_op_photo_pyramid.argtypes = [vp, vp, C.c_int, vp]
+    L.hnet_photo_robust_default_opts.argtypes = [C.POINTER(PhotoRobustOpts)]
+    L.hnet_photo_robust_default_opts.restype = None
+    L.hnet_op_photo_align_robust.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp]
+    L.hnet_sessions_photo_align_robust.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp, vp]
+    L.hnet_photo_robust_marginal.argtypes = [vp, vp, vp]
     L.hnet_last_photo_align_device_ms.restype = C.c_double
     for name in SYMBOLS:
         getattr(L, name)   # AttributeError here = the library does not export what include/hnet.h declares

@@ -11,6 +11,7 @@
 #include "photo_dev.h"
 #include "photo_align_dev.h"
 #include "photo_pyramid_dev.h"
+#include "photo_robust_dev.h"
 #include "chain_args.h"
 #include "s3_format.h"
 
@@ -226,6 +227,10 @@ inline int run_host_call(hnet_ctx* c, const std::function<int(uint32_t& flag)>& 
 int photo_align_check_opts(hnet_ctx* c, const hnet_photo_align_opts* opts, const char* who);
 int photo_align_pyramid_run(hnet_ctx* c, const uint8_t* d_img1, const uint8_t* d_img2, int n, const float* d_x0, const hnet_photo_align_opts& opts, int levels,
                             hnet_photo_align* out, hnet_photo_align* levels_out);
+// the same for the gain / bias + Huber alignment (capi_photo_robust.hip): out [n] and levels_out (null or [n][levels]) are hnet_photo_robust records
+int photo_robust_check_opts(hnet_ctx* c, const hnet_photo_robust_opts* opts, const char* who);
+int photo_robust_run(hnet_ctx* c, const uint8_t* d_img1, const uint8_t* d_img2, int n, const float* d_x0, const hnet_photo_robust_opts& opts, int levels,
+                     hnet_photo_robust* out, hnet_photo_robust* levels_out);
 void build_undistort_maps(const hnet_camera* cam, std::vector<float>& mx, std::vector<float>& my);
 
 }  // namespace capi

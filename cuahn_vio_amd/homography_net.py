@@ -294,6 +294,23 @@ class HnetEngine:
                                                            out.ctypes.data, lv.ctypes.data if want_levels else None))
         return (out, lv) if want_levels else out
 
+    def op_photo_align_robust(self, img1, img2, offsets0, levels=4, want_levels=False, **opts):
+        """photometric alignment with a gain / bias model and Huber weights (hnet_op_photo_align_robust): as op_photo_align_pyramid; opts: the fields
+        of hnet_photo_align_opts and brightness (0 / 1), huber_k (grey levels, 0: quadratic), gain0, bias0 -> records [n] of
+        _capi.PHOTO_ROBUST_DTYPE; want_levels: (those, every level's records [n, levels], index = level)"""
+        a = np.ascontiguousarray(img1, dtype=np.uint8).reshape(-1, IMG_H, IMG_W)
+        b = np.ascontiguousarray(img2, dtype=np.uint8).reshape(-1, IMG_H, IMG_W)
+        n = a.shape[0]
+        if b.shape[0] != n:
+            raise ValueError("img1 and img2 must hold the same number of frames")
+        off = np.ascontiguousarray(offsets0, dtype=np.float32).reshape(n, 8)
+        o = _capi.photo_robust_opts(**opts)
+        out = np.zeros(n, _capi.PHOTO_ROBUST_DTYPE)
+        lv = np.zeros((n, max(int(levels), 1)), _capi.PHOTO_ROBUST_DTYPE) if want_levels else None
+        check(self._h, self._L.hnet_op_photo_align_robust(self._h, a.ctypes.data, b.ctypes.data, n, off.ctypes.data, C.addressof(o), int(levels),
+                                                          out.ctypes.data, lv.ctypes.data if want_levels else None))
+        return (out, lv) if want_levels else out
+
     def op_photo_pyramid(self, img):
         """levels 1 .. 3 of uint8 frames [n, 224, 320] (hnet_op_photo_pyramid) -> uint8 [n, _capi.PHOTO_PYRAMID_BYTES]: 160 x 112, 80 x 56 and
         40 x 28 pixels per frame, level 1 first"""
@@ -613,6 +630,18 @@ class HnetSessions:
         lv = np.zeros((n, max(int(levels), 1)), _capi.PHOTO_ALIGN_DTYPE) if want_levels else None
         self._check(self._L.hnet_sessions_photo_align_pyramid(self._s, n, ids.ctypes.data, off.ctypes.data, C.addressof(o), int(levels), out.ctypes.data,
                                                               lv.ctypes.data if want_levels else None))
+        return (out, lv) if want_levels else out
+
+    def photo_align_robust(self, ids, offsets0, levels=4, want_levels=False, **opts):
+        """gain / bias + Huber photometric alignment of the listed sessions' current pairs (hnet_sessions_photo_align_robust); read-only; arguments
+        and result as HnetEngine.op_photo_align_robust"""
+        ids, n = self._ids(ids)
+        off = np.ascontiguousarray(offsets0, dtype=np.float32).reshape(n, 8)
+        o = _capi.photo_robust_opts(**opts)
+        out = np.zeros(n, _capi.PHOTO_ROBUST_DTYPE)
+        lv = np.zeros((n, max(int(levels), 1)), _capi.PHOTO_ROBUST_DTYPE) if want_levels else None
+        self._check(self._L.hnet_sessions_photo_align_robust(self._s, n, ids.ctypes.data, off.ctypes.data, C.addressof(o), int(levels), out.ctypes.data,
+                                                             lv.ctypes.data if want_levels else None))
         return (out, lv) if want_levels else out
 
     def image_count(self, id):

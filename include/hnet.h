@@ -656,6 +656,47 @@ int  hnet_sessions_photo_align_pyramid(hnet_sessions* s, int n, const int32_t* i
 /* operator level (tests): levels 1 .. 3 of n host frames u8 [n][224][320] -> out [n][17920 + 4480 + 1120] bytes, level 1 first.  1 <= n <= max_batch */
 int  hnet_op_photo_pyramid(hnet_ctx* ctx, const uint8_t* img, int n, uint8_t* out);
 
+/* ---- photometric alignment with a gain / bias model and Huber weights (csrc/kernels_photo_robust.hip; the shared code is include/hnet_photo_robust.h) ----
+ * The coarse-to-fine call above on TEN parameters: the eight offsets, a gain G and a bias b (grey levels) applied to the sampled img2, for frames of an
+ * auto-exposure camera, and a Huber loss for pixels no homography explains.  Per valid pixel r = ((float) G w + (float)(b / 255) - img1 / 255) * 255; with
+ * k = huber_k (grey levels; 0: quadratic) a pixel with |r| <= k costs rho = r^2 and weighs omega = 1, any other costs rho = k (2 |r| - k) and weighs
+ * omega = k / |r| (an OUTLIER).  The loop is the same Levenberg-Marquardt descent, on the mean of rho (a fixed function of the ten parameters, not a
+ * re-weighted least squares on a moving target): a trial is accepted iff it has a homography, a finite positive gain, a finite bias, at least
+ * max(min_valid, 9) valid pixels and a strictly smaller mean rho.  HNET_ALIGN_CONVERGED is judged on the eight offset components of the step alone;
+ * HNET_ALIGN_SINGULAR on the undamped 10 x 10 (8 x 8 with the model off) matrix.  Levels, min_valid >> 2 L, the start of a level (gain and bias are carried
+ * like the offsets) and the flags are hnet_op_photo_align_pyramid's.
+ * brightness = 0 keeps G = 1, b = 0 and solves the 8 x 8 system; with huber_k = 0 besides, the field `px` of every record of every level equals
+ * hnet_op_photo_align_pyramid's record byte for byte.
+ * px.mse0 / px.mse are the mean rho, px.grad / px.info the offset block of grad10 / info10 at the record's gain.  grad10 / info10: the gradient and the
+ * Gauss-Newton matrix in (offsets [8], gain, bias); rows and columns 8, 9 are zero when the model is off.  n_outliers0 / n_outliers: the valid pixels with
+ * omega < 1 at the start / at the record's point.  Saturated pixels break the affine model and are left to the Huber weights.
+ * Errors are those of hnet_op_photo_align_pyramid, and HNET_ERR_INVALID_ARG for brightness outside 0 / 1, a negative or non-finite huber_k, a non-finite or
+ * non-positive gain0, a non-finite bias0, or gain0 != 1 / bias0 != 0 with the model off.  An error writes nothing.  One upload, the launch sequence, one
+ * download of the records and one synchronisation; hnet_last_photo_align_device_ms covers the whole sequence. */
+typedef struct hnet_photo_robust_opts {
+    hnet_photo_align_opts base;
+    int32_t brightness;        /* 0 off, 1 gain + bias */
+    int32_t pad;
+    double  huber_k;           /* grey levels, 0 = quadratic */
+    double  gain0, bias0;      /* start, 1 and 0 */
+} hnet_photo_robust_opts;
+typedef struct hnet_photo_robust {
+    hnet_photo_align px;       /* common fields: mse0 / mse are the mean robust cost; grad / info are the offset block at the current gain */
+    double  gain, bias;
+    int32_t n_outliers0, n_outliers;
+    double  grad10[10], info10[100];   /* zero rows / columns 8, 9 when the model is off */
+} hnet_photo_robust;
+void hnet_photo_robust_default_opts(hnet_photo_robust_opts* o);      /* base defaults, 1, 10.0, 1, 0 */
+int  hnet_op_photo_align_robust(hnet_ctx* ctx, const uint8_t* img1, const uint8_t* img2, int n, const float* offsets0_px, const hnet_photo_robust_opts* opts,
+                                int levels, hnet_photo_robust* out /* [n] */, hnet_photo_robust* levels_out /* NULL or [n][levels], index = level */);
+/* the same on the current pair of each listed session; read-only like hnet_sessions_photo_align_pyramid */
+int  hnet_sessions_photo_align_robust(hnet_sessions* s, int n, const int32_t* ids, const float* offsets0_px, const hnet_photo_robust_opts* opts, int levels,
+                                      hnet_photo_robust* out, hnet_photo_robust* levels_out);
+/* host only: the information matrix and gradient of the offsets with gain and bias marginalised (the Schur complement of the 2 x 2 brightness block of
+ * info10): what a filter may use when brightness is a nuisance.  With the model off (rows 8, 9 of info10 all zero) it copies px.info / px.grad.
+ * HNET_ERR_INVALID_ARG, nothing written, for a null argument or when the 2 x 2 block has no Cholesky factor. */
+int  hnet_photo_robust_marginal(const hnet_photo_robust* rec, double info8[64], double grad8[8]);
+
 int hnet_synchronize(hnet_ctx* ctx, void* stream);
 int hnet_last_timing(const hnet_ctx* ctx, hnet_timing* out);
 

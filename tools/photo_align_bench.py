@@ -7,6 +7,9 @@ forward of the same batch (hnet_sessions_last_timing).  Medians over --reps call
   python tools/photo_align_bench.py --levels L [--iterations K] [--batches 1 8 64]
 the coarse-to-fine call instead (hnet_op_photo_align_pyramid): per batch n the device time of L levels with K trials per level (default 8) on
 stock pairs up to 32 px apart, started from zero offsets, with the trials every level made and the worst distance from the truth.
+  python tools/photo_align_bench.py --robust [--huber K] [--no-brightness] [--levels L] [--iterations K]
+the gain / bias + Huber call (hnet_op_photo_align_robust) on the same pairs, from the same start and with the same trials (levels defaults
+to 4), with the gain it found.
   python tools/photo_align_bench.py --summarize DIR
 prints, from the kernel trace a `rocprofv3 --kernel-trace --output-format csv -d DIR -- python tools/photo_align_bench.py ...` run left in DIR, the mean
 duration of every photometric kernel by grid size."""
@@ -51,12 +54,18 @@ def pyramid(a, blob):
         e = HnetEngine(blob, variant="prior3", mc_samples=16, dropout_p=0.05, mc_seed=9, max_batch=n)
         ms = []
         for r in range(a.warmup + a.reps):
-            rec, lv = e.op_photo_align_pyramid(i1, i2, start, levels=a.levels, want_levels=True, max_iterations=a.iterations)
+            if a.robust:
+                rob, lvr = e.op_photo_align_robust(i1, i2, start, levels=a.levels, want_levels=True, max_iterations=a.iterations, huber_k=a.huber,
+                                                   brightness=0 if a.no_brightness else 1)
+                rec, lv = rob["px"], lvr["px"]
+            else:
+                rec, lv = e.op_photo_align_pyramid(i1, i2, start, levels=a.levels, want_levels=True, max_iterations=a.iterations)
             ms.append(e.last_photo_align_device_ms())
         ms = np.array(ms[a.warmup:])
+        what = f"robust (k={a.huber:g}, brightness {'off' if a.no_brightness else 'on'}, median gain {np.median(rob['gain']):.4f})" if a.robust else "pyramid"
         err = np.abs(rec["offsets_px"].astype(np.float64) - truth).max(axis=1)
         trials = ", ".join(f"L{L} {lv['trials'][:, L].mean():.1f}" for L in range(a.levels - 1, -1, -1))
-        print(f"n = {n:3d}: pyramid levels={a.levels} K={a.iterations} {np.median(ms):.4f} ms (min {ms.min():.4f}); trials per pair {trials}; "
+        print(f"n = {n:3d}: {what} levels={a.levels} K={a.iterations} {np.median(ms):.4f} ms (min {ms.min():.4f}); trials per pair {trials}; "
               f"worst distance from the truth: median {np.median(err):.3f} px, max {err.max():.3f} px", flush=True)
         e.close()
 
@@ -68,6 +77,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--levels", type=int, default=0)
     ap.add_argument("--iterations", type=int, default=8)
+    ap.add_argument("--robust", action="store_true")
+    ap.add_argument("--huber", type=float, default=10.0)
+    ap.add_argument("--no-brightness", action="store_true")
     ap.add_argument("--summarize")
     a = ap.parse_args()
     if a.summarize:
@@ -75,6 +87,8 @@ def main():
     from cuahn_vio_amd import synth, weights
     from cuahn_vio_amd.homography_net import HnetEngine, HnetSessions
     blob = weights.pack_state_dict(weights.synthetic_state(0))
+    if a.robust and not a.levels:
+        a.levels = 4
     if a.levels:
         return pyramid(a, blob)
     for n in a.batches:
