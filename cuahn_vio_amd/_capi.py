@@ -48,6 +48,7 @@ SYMBOLS = [
     "hnet_photo_align_default_opts", "hnet_op_photo_align", "hnet_sessions_photo_align", "hnet_last_photo_align_device_ms",
     "hnet_op_photo_align_pyramid", "hnet_sessions_photo_align_pyramid", "hnet_op_photo_pyramid",
     "hnet_photo_robust_default_opts", "hnet_op_photo_align_robust", "hnet_sessions_photo_align_robust", "hnet_photo_robust_marginal",
+    "hnet_photo_refine_default_opts", "hnet_filters_set_photo_refine", "hnet_filters_last_refine", "hnet_filters_refine_stats", "hnet_filters_reset_refine_stats",
 ]
 # hnet_filters_advance's status per listed session (include/hnet.h HNET_ADV_*)
 ADV_STEPPED, ADV_WAIT_IMU, ADV_WAIT_INIT, ADV_INITIALIZED, ADV_PROPAGATED, ADV_NO_FRAME = range(6)
@@ -166,6 +167,43 @@ def photo_robust_opts(**kw):
             setattr(o, k, v)
         else:
             raise TypeError(f"hnet_photo_robust_opts has no field {k!r}")
+    return o
+
+
+# hnet_photo_refine: the level-0 record of a fallback alignment, R_px, the fallback's innovation, flags REFINE_* (include/hnet.h HNET_REFINE_*)
+PHOTO_REFINE_DTYPE = _np.dtype([("rec", PHOTO_ROBUST_DTYPE), ("r_px", "<f8", (8, 8)), ("innov", INNOVATION_DTYPE), ("flags", "<i4"), ("pad", "<i4")])
+assert PHOTO_REFINE_DTYPE.itemsize == 1560 + 512 + 144 + 8
+REFINE_ASKED, REFINE_APPLIED, REFINE_NIS_REJECTED, REFINE_S_SINGULAR = 1, 2, 4, 8
+REFINE_BAD_K_NET_COV, REFINE_STOPPED, REFINE_NO_STEP, REFINE_MSE_ABOVE_MAX, REFINE_NO_FACTOR, REFINE_NON_FINITE = 16, 32, 64, 128, 256, 512
+REFINE_UNUSABLE = 16 | 32 | 64 | 128 | 256 | 512
+
+
+class PhotoRefineOpts(C.Structure):
+    """hnet_photo_refine_opts: the alignment's options and levels (shared by the refining sessions of a call), and per session the scale on
+    mse * inverse(info), the floor added to the diagonal (px) and the largest usable mse (0: no limit)"""
+    _fields_ = [("align", PhotoRobustOpts), ("levels", C.c_int32), ("pad", C.c_int32), ("cov_scale", C.c_double), ("sigma_floor_px", C.c_double),
+                ("max_mse", C.c_double)]
+
+
+class RefineStats(C.Structure):
+    """hnet_refine_stats: fallbacks asked for, applied, unusable, refused by the NIS gate; sum and maximum of the fallbacks' NIS"""
+    _fields_ = [("asked", C.c_int64), ("applied", C.c_int64), ("unusable", C.c_int64), ("nis_rejected", C.c_int64), ("sum_nis", C.c_double), ("max_nis", C.c_double)]
+
+
+def photo_refine_opts(**kw):
+    """the defaults of hnet_photo_refine_default_opts (cov_scale = 0: the caller must choose it) with the given fields replaced (the fields of `align`
+    and its `base` by their own names)"""
+    o = PhotoRefineOpts()
+    lib().hnet_photo_refine_default_opts(C.byref(o))
+    for k, v in kw.items():
+        if k in ("max_iterations", "min_valid", "lambda0", "eps_px"):
+            setattr(o.align.base, k, v)
+        elif k in ("brightness", "huber_k", "gain0", "bias0"):
+            setattr(o.align, k, v)
+        elif k in ("levels", "cov_scale", "sigma_floor_px", "max_mse"):
+            setattr(o, k, v)
+        else:
+            raise TypeError(f"hnet_photo_refine_opts has no field {k!r}")
     return o
 
 
@@ -346,6 +384,12 @@ def lib():
     L.hnet_sessions_photo_align_robust.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp, vp]
     L.hnet_photo_robust_marginal.argtypes = [vp, vp, vp]
     L.hnet_last_photo_align_device_ms.restype = C.c_double
+    L.hnet_photo_refine_default_opts.argtypes = [C.POINTER(PhotoRefineOpts)]
+    L.hnet_photo_refine_default_opts.restype = None
+    L.hnet_filters_set_photo_refine.argtypes = [vp, C.c_int, C.POINTER(PhotoRefineOpts)]
+    L.hnet_filters_last_refine.argtypes = [vp, C.c_int, vp]
+    L.hnet_filters_refine_stats.argtypes = [vp, C.c_int, C.POINTER(RefineStats)]
+    L.hnet_filters_reset_refine_stats.argtypes = [vp, C.c_int]
     for name in SYMBOLS:
         getattr(L, name)   # AttributeError here = the library does not export what include/hnet.h declares
     _lib = L

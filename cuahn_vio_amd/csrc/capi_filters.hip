@@ -2,6 +2,7 @@
 // hnet_filters_step and hnet_filters_advance differ in how a call's states get their readings (the host's windows / the device's IMU rings and the
 // initialiser); the IEKF iterations of an attempt, the overflow test and the bookkeeping of an accepted call are one piece of code each, below.
 #include "sessions_internal.h"
+#include "filters_refine_dev.h"
 
 using namespace hnet;
 using namespace capi;
@@ -84,6 +85,35 @@ struct hnet_filters {
     std::vector<PhotoGate> photo_gate;
     std::vector<hnet_photo_stats> photo_stats;
     bool photo_taps_global = false;
+    // the photometric fallback (hnet_filters_set_photo_refine), allocated by the first call that turns it on: the output block then also holds
+    // {refine [n] RefineRec, dense} behind the photometric records; per session the options (host: `align` and `levels` decide a call's launch sequence)
+    // and what the kernels read of them; ONE zeroed scratch block for the alignment and the fallback's measurement; the statistics
+    bool refine = false;
+    size_t off_refine = 0;
+    std::vector<hnet_photo_refine_opts> refine_opts;
+    std::vector<uint8_t> refine_on;
+    RefineCfg* d_refine_cfg = nullptr;         // [n_sessions]
+    uint8_t* d_refine_scratch = nullptr;       // RefineScratch
+    std::vector<hnet_refine_stats> refine_stats;
+    int last_refine_n = 0;                     // sessions the last accepted call has refine records for; 0: it ran without a refining session
+};
+// the sections of d_refine_scratch for max_batch B and N sessions
+struct RefineScratch {
+    RobustRec* rec; RobustStart* start; RobustWork* work; RobustSums* part; float *x0, *prior_px, *m72; InnovRec* innov; double* nis0; size_t bytes;
+    RefineScratch(uint8_t* b, int B, int N) {
+        size_t o = 0;
+        auto take = [&](size_t n) { uint8_t* p = b + o; o += (n + 255) & ~(size_t)255; return p; };
+        rec = reinterpret_cast<RobustRec*>(take((size_t)HNET_ALIGN_MAX_LEVELS * B * sizeof(RobustRec)));
+        start = reinterpret_cast<RobustStart*>(take((size_t)B * sizeof(RobustStart)));
+        work = reinterpret_cast<RobustWork*>(take((size_t)B * sizeof(RobustWork)));
+        part = reinterpret_cast<RobustSums*>(take((size_t)B * PHOTO_SLICES * sizeof(RobustSums)));
+        x0 = reinterpret_cast<float*>(take((size_t)B * 8 * sizeof(float)));
+        prior_px = reinterpret_cast<float*>(take((size_t)B * 8 * sizeof(float)));
+        m72 = reinterpret_cast<float*>(take((size_t)B * 72 * sizeof(float)));
+        innov = reinterpret_cast<InnovRec*>(take((size_t)B * sizeof(InnovRec)));
+        nis0 = reinterpret_cast<double*>(take((size_t)N * sizeof(double)));      // stays zero: "no NIS gate" for a filters object without innovations
+        bytes = o;
+    }
 };
 
 static size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -124,26 +154,28 @@ static void filters_drop_predict_cov(hnet_filters* f) {           // predict_cov
 
 extern "C" {
 
-// the offsets of the step's output block for max_batch B: {net | prior_px | updates | innov (if enabled) | photo (if enabled) | work | results}
-static void filters_out_layout(hnet_filters* f, int B, bool innov, bool photo) {
+// the offsets of the step's output block for max_batch B: {net | prior_px | updates | innov (if enabled) | photo (if enabled) | refine (if on) | work | results}
+static void filters_out_layout(hnet_filters* f, int B, bool innov, bool photo, bool refine) {
     f->off_prior = al256((size_t)f->iters * B * 72 * sizeof(float));
     f->off_upd = f->off_prior + al256((size_t)f->iters * B * 8 * sizeof(float));
     f->off_innov = f->off_upd + al256((size_t)B * sizeof(int32_t));
     f->off_photo = f->off_innov + (innov ? al256((size_t)f->iters * B * sizeof(InnovRec)) : 0);
-    f->off_work = f->off_photo + (photo ? al256((size_t)(2 + f->iters) * B * sizeof(PhotoRec)) : 0);
+    f->off_refine = f->off_photo + (photo ? al256((size_t)(2 + f->iters) * B * sizeof(PhotoRec)) : 0);
+    f->off_work = f->off_refine + (refine ? al256((size_t)B * sizeof(RefineRec)) : 0);
     f->off_res = f->off_work + al256((size_t)B * sizeof(FilterRec));
     f->out_bytes = f->off_res + (size_t)B * sizeof(AdvanceResult);
 }
 // the sections of the output block as typed pointers, on the device (d) and in the pinned copy (h)
-struct OutView { float *net, *prior; int32_t* upd; InnovRec* innov; PhotoRec* photo; FilterRec* work; AdvanceResult* res; };
+struct OutView { float *net, *prior; int32_t* upd; InnovRec* innov; PhotoRec* photo; RefineRec* refine; FilterRec* work; AdvanceResult* res; };
 struct OutViews { OutView d, h; };
 static OutView filters_out_view(const hnet_filters* f, uint8_t* b) {
     return OutView{reinterpret_cast<float*>(b), reinterpret_cast<float*>(b + f->off_prior), reinterpret_cast<int32_t*>(b + f->off_upd), reinterpret_cast<InnovRec*>(b + f->off_innov),
-                   reinterpret_cast<PhotoRec*>(b + f->off_photo), reinterpret_cast<FilterRec*>(b + f->off_work), reinterpret_cast<AdvanceResult*>(b + f->off_res)};
+                   reinterpret_cast<PhotoRec*>(b + f->off_photo), reinterpret_cast<RefineRec*>(b + f->off_refine), reinterpret_cast<FilterRec*>(b + f->off_work), reinterpret_cast<AdvanceResult*>(b + f->off_res)};
 }
 static OutViews filters_out_views(const hnet_filters* f) { return OutViews{filters_out_view(f, f->d_out), filters_out_view(f, f->pin_out)}; }
 // what a step of n stepping sessions downloads in one copy from the start of the output block when the states are not wanted: up to the last record section in use
-static size_t filters_down_head(const hnet_filters* f, int n) {
+static size_t filters_down_head(const hnet_filters* f, int n, bool refining) {
+    if (refining) return f->off_refine + (size_t)n * sizeof(RefineRec);
     if (f->photo) return f->off_photo + (size_t)n * (2 + f->iters) * sizeof(PhotoRec);
     if (f->innov) return f->off_innov + (size_t)f->iters * n * sizeof(InnovRec);
     return f->off_upd + (size_t)n * sizeof(int32_t);
@@ -174,6 +206,39 @@ static bool filters_photo_gated(const hnet_filters* f, int n, const int32_t* ids
     for (int j = 0; j < n; j++)
         if (f->photo_gate[ids[j]].max_ratio > 0.0) return true;
     return false;
+}
+// whether the call in which the sessions ids[0 .. n) step runs the photometric fallback: 1 when one of them has refinement on and a photometric gate
+// (without a gate nothing is ever refused), -1 when two sessions with refinement on differ in `align` or `levels`, else 0.  *ref: a refining session
+static int filters_refining(const hnet_filters* f, int n, const int32_t* ids, int* ref) {
+    if (!f->refine) return 0;
+    int first = -1, refining = 0;
+    for (int j = 0; j < n; j++) {
+        const int id = ids[j];
+        if (!f->refine_on[id]) continue;
+        if (first < 0) first = id;
+        else if (memcmp(&f->refine_opts[id].align, &f->refine_opts[first].align, sizeof(hnet_photo_robust_opts)) != 0 || f->refine_opts[id].levels != f->refine_opts[first].levels)
+            return -1;
+        if (f->photo_gate[id].max_ratio > 0.0) refining = 1;
+    }
+    *ref = first;
+    return refining;
+}
+// after an accepted call with refine records: the records [n] of the sessions ids[0 .. n) go into their statistics (include/hnet.h hnet_refine_stats)
+static void filters_count_refine(hnet_filters* f, int n, const int32_t* ids) {
+    const RefineRec* rec = filters_out_view(f, f->pin_out).refine;
+    for (int j = 0; j < n; j++) {
+        const RefineRec& r = rec[j];
+        if (!(r.flags & HNET_REFINE_ASKED)) continue;
+        hnet_refine_stats& a = f->refine_stats[ids[j]];
+        a.asked++;
+        if (r.flags & HNET_REFINE_APPLIED) a.applied++;
+        if (r.flags & HNET_REFINE_UNUSABLE) a.unusable++;
+        if (r.flags & HNET_REFINE_NIS_REJECTED) a.nis_rejected++;
+        if ((r.flags & (HNET_REFINE_APPLIED | HNET_REFINE_NIS_REJECTED)) && std::isfinite(r.nis)) {
+            a.sum_nis += r.nis;
+            if (r.nis > a.max_nis) a.max_nis = r.nis;
+        }
+    }
 }
 // after an accepted call with photometric records: the records [n][2 + iters] of the sessions ids[0 .. n) go into their statistics (include/hnet.h
 // hnet_photo_stats).  ref_gate: the reference gates as the call uploaded them (the pinned input block: the device's copy is the one the kernels close).
@@ -235,8 +300,11 @@ static int filters_flags(hnet_ctx* const ctx[2], uint32_t* flag, hipStream_t st)
 // photo_gated (one of the n sessions has a photometric gate): the photometric records are formed per iteration instead, between the forward and the
 // innovation kernel - photo_iter_kernel and photo_gate_kernel, which closes d_gate and sets the slot's verdict word on a rejection (iteration 0 writes
 // every verdict word: a repeat re-forms them) - and nothing runs behind ev1.
+// refine_ref >= 0 (filters_refining said 1; photo_gated then holds): the call runs the photometric fallback with the alignment options of session refine_ref.
+// The last iteration's update then leaves the reset to the fallback's update launch, and filters_enqueue_refine follows inside the device window.
+static int filters_enqueue_refine(hnet_filters* f, hnet_ctx* c, const OutView& d, int n, const int32_t* d_ids, int32_t* d_gate, int refine_ref, hipStream_t st);
 static int filters_enqueue_iekf(hnet_filters* f, hnet_ctx* const ctx[2], const OutView& d, int n, const int32_t* d_ids, int32_t* d_gate, const uint64_t* d_seq,
-                                int seq_stride, bool photo_gated, hipStream_t st) {
+                                int seq_stride, bool photo_gated, int refine_ref, hipStream_t st) {
     hnet_ctx* c = ctx[0];
     const int I = f->iters, B = c->cfg.max_batch, N = f->s->n;
     for (int it = 0; it < I && n; it++) {
@@ -254,10 +322,33 @@ static int filters_enqueue_iekf(hnet_filters* f, hnet_ctx* const ctx[2], const O
         if (f->innov)
             HIPCHK(c, launch_filter_innovation(d_ids, n, N, f->d_params, d.work, net_it, f->d_prior_cam, f->d_max_nis, d_gate, d.upd, it, d.innov,
                                                photo_gated ? f->d_photo_verdict : nullptr, st));
-        HIPCHK(c, launch_filter_update(d_ids, n, N, f->d_params, net_it, f->d_prior_cam, d_gate, it != I - 1, it == I - 1, d.work, d.upd, st));
+        HIPCHK(c, launch_filter_update(d_ids, n, N, f->d_params, net_it, f->d_prior_cam, d_gate, it != I - 1, it == I - 1 && refine_ref < 0, d.work, d.upd, st));
     }
+    if (refine_ref >= 0 && n)
+        if (const int r = filters_enqueue_refine(f, c, d, n, d_ids, d_gate, refine_ref, st); r != HNET_OK) return r;
     HIPCHK(c, hipEventRecord(f->ev1, st));
     if (f->photo && n && !photo_gated) HIPCHK(c, filters_launch_photo(f, d, n, st));
+    return HNET_OK;
+}
+// The fallback of a call's n stepping sessions, behind the last iteration's update (which ran with last = 0): which slots align (verdict 1, refinement
+// on, nothing applied) from iteration 0's fp32 prior, the alignment on the staged pairs (NaN starts elsewhere: DEGENERATE at every level, early returns),
+// the measurement (it opens d_gate for the usable slots and closes it for every other), then the filter's own prior, innovation and update launches on
+// it - the update with update_offset = 0 and last = 1: the reset every slot is still owed - and what became of it.
+static int filters_enqueue_refine(hnet_filters* f, hnet_ctx* c, const OutView& d, int n, const int32_t* d_ids, int32_t* d_gate, int refine_ref, hipStream_t st) {
+    const int B = c->cfg.max_batch, N = f->s->n;
+    const RefineScratch w(f->d_refine_scratch, B, N);
+    const hnet_photo_refine_opts& ro = f->refine_opts[refine_ref];
+    RobustOpts o;
+    memcpy(&o, &ro.align, sizeof o);
+    const size_t pyr = (size_t)B * PYR_BYTES;
+    HIPCHK(c, launch_filter_refine_select(d_ids, n, N, f->d_refine_cfg, f->d_photo_verdict, d.upd, d.prior, w.x0, d.refine, st));
+    HIPCHK(c, launch_photo_align_robust((const uint8_t*)c->stage_prev, (const uint8_t*)c->stage_curr, n, w.x0, o, ro.levels, c->pyr_scratch, c->pyr_scratch + pyr, w.start,
+                                        w.part, w.work, w.rec, st));
+    HIPCHK(c, launch_filter_refine_measure(d_ids, n, N, f->d_params, f->d_refine_cfg, w.rec, ro.levels, w.m72, d_gate, d.refine, st));
+    HIPCHK(c, launch_filter_prior(d.work, n, w.prior_px, f->d_prior_cam, st));
+    HIPCHK(c, launch_filter_innovation(d_ids, n, N, f->d_params, d.work, w.m72, f->d_prior_cam, f->innov ? f->d_max_nis : w.nis0, d_gate, d.upd, 0, w.innov, nullptr, st));
+    HIPCHK(c, launch_filter_update(d_ids, n, N, f->d_params, w.m72, f->d_prior_cam, d_gate, 0, 1, d.work, d.upd, st));
+    HIPCHK(c, launch_filter_refine_finish(n, w.innov, d.upd, f->iters, d.refine, st));
     return HNET_OK;
 }
 // an overflow of the fp16 planes among the downloaded outputs of n stepping sessions: the first forward with a non-finite output had finite inputs (its
@@ -271,12 +362,14 @@ static int filters_overflowed(const hnet_filters* f, hnet_ctx* const ctx[2], con
     return -1;
 }
 // the bookkeeping of an accepted call in which the sessions ids[0 .. n) stepped: what the last_* calls describe, the innovation statistics, the timing
-static int filters_accepted(hnet_filters* f, int n, const int32_t* ids, const int32_t* ref_gate, std::chrono::steady_clock::time_point t0, int n_inferences) {
+static int filters_accepted(hnet_filters* f, int n, const int32_t* ids, const int32_t* ref_gate, bool refining, std::chrono::steady_clock::time_point t0, int n_inferences) {
     f->last_n = n;
     f->last_innov_n = f->innov ? n : 0;
     f->last_photo_n = f->photo ? n : 0;
     if (f->innov) filters_count_innovations(f, n, ids);
     if (f->photo) filters_count_photo(f, n, ids, ref_gate);
+    f->last_refine_n = refining ? n : 0;
+    if (refining) filters_count_refine(f, n, ids);
     float ms = 0;
     HIPCHK(f->s->ctx, hipEventElapsedTime(&ms, f->ev0, f->ev1));
     record_timing(f->timing, ms, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), n_inferences, true);
@@ -319,7 +412,7 @@ void hnet_destroy_filters(hnet_filters* f) {
     hnet_ctx* c = f->s->ctx;
     (void)hipSetDevice(c->cfg.device_id);
     (void)hipStreamSynchronize(c->stream);
-    drop_dev(f->d_state); drop_dev(f->d_params); drop_dev(f->d_out); drop_dev(f->d_prior_cam); drop_dev(f->d_in); drop_dev(f->d_feed); drop_dev(f->d_max_nis); drop_dev(f->d_photo_part); drop_dev(f->d_photo_gate); drop_dev(f->d_photo_verdict);
+    drop_dev(f->d_state); drop_dev(f->d_params); drop_dev(f->d_out); drop_dev(f->d_prior_cam); drop_dev(f->d_in); drop_dev(f->d_feed); drop_dev(f->d_max_nis); drop_dev(f->d_photo_part); drop_dev(f->d_photo_gate); drop_dev(f->d_photo_verdict); drop_dev(f->d_refine_cfg); drop_dev(f->d_refine_scratch);
     drop_pin(f->pin_feed); drop_pin(f->pin_out); drop_pin(f->pin_in);
     drop_event(f->ev0); drop_event(f->ev1);
     filters_drop_feed(f);
@@ -342,7 +435,7 @@ int hnet_create_filters(hnet_sessions* s, int max_iekf_iteration, hnet_filters**
     f->t.assign(N, 0.0);
     f->cam_imu_dt.assign(N, dp.cam_imu_dt);
     f->imu_avg.assign(N, dp.imu_avg);
-    filters_out_layout(f, B, false, false);
+    filters_out_layout(f, B, false, false, false);
     f->t_seen.assign(N, -INFINITY);
     f->inited.assign(N, 0);
     f->last_slot.assign(N, -1);
@@ -419,6 +512,10 @@ int hnet_filters_step(hnet_filters* f, int n, const int32_t* ids, const double* 
     int rc = sessions_check_ids(s, n, ids);
     if (rc == HNET_OK) rc = sessions_check_pairs(s, n, ids);
     if (rc != HNET_OK) return rc;
+    int refine_ref = -1;
+    const int refining = filters_refining(f, n, ids, &refine_ref);
+    if (refining < 0) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_step: the sessions with refinement on differ in align / levels (hnet_filters_set_photo_refine)");
+    if (!refining) refine_ref = -1;
     for (int i = 0; i < n; i++) {
         if (!(t_frame[i] > f->t[ids[i]]) || !std::isfinite(t_frame[i]))
             return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_step: t_frame must be later than the state's time (Propagator.cpp:32-43)");
@@ -467,7 +564,7 @@ int hnet_filters_step(hnet_filters* f, int n, const int32_t* ids, const double* 
     const int32_t* d_roff = reinterpret_cast<const int32_t*>(f->d_in + o_off);
     const OutViews o = filters_out_views(f);
     // the output block is laid out for max_batch: download the used parts of each section in one copy up to the last one needed
-    const size_t down = state_out ? f->off_work + (size_t)n * sizeof(FilterRec) : filters_down_head(f, n);
+    const size_t down = state_out ? f->off_work + (size_t)n * sizeof(FilterRec) : filters_down_head(f, n, refining > 0);
     hipStream_t st = c->stream;
     const size_t up = o_off + (size_t)(n + 1) * 4;
     hnet_ctx* const ctx[2] = {c, filters_iter_ctx(f)};
@@ -478,7 +575,7 @@ int hnet_filters_step(hnet_filters* f, int n, const int32_t* ids, const double* 
         HIPCHK(c, hipEventRecord(f->ev0, st));
         HIPCHK(c, launch_session_gather(s->ring, 2 * s->n, d_pairs, n, (uint8_t*)c->stage_prev, (uint8_t*)c->stage_curr, st));
         HIPCHK(c, launch_filter_propagate(d_ids, n, s->n, f->d_state, f->d_params, d_rd, d_roff, d_tf, o.d.work, st));
-        if (const int r = filters_enqueue_iekf(f, ctx, o.d, n, d_ids, d_gate, d_seq, n, photo_gated, st); r != HNET_OK) return r;
+        if (const int r = filters_enqueue_iekf(f, ctx, o.d, n, d_ids, d_gate, d_seq, n, photo_gated, refine_ref, st); r != HNET_OK) return r;
         HIPCHK(c, hipMemcpyAsync(f->pin_out, f->d_out, down, hipMemcpyDeviceToHost, st));
         return filters_flags(ctx, flag_now, st);
     };
@@ -493,7 +590,7 @@ int hnet_filters_step(hnet_filters* f, int n, const int32_t* ids, const double* 
         for (int it = 0; it < I; it++) memcpy(net_out + (size_t)it * n * 72, o.h.net + (size_t)it * c->cfg.max_batch * 72, (size_t)n * 72 * sizeof(float));
     if (updates) memcpy(updates, o.h.upd, (size_t)n * sizeof(int32_t));
     if (state_out) memcpy(state_out, o.h.work, (size_t)n * sizeof(FilterRec));
-    return filters_accepted(f, n, ids, gate, t0, I);
+    return filters_accepted(f, n, ids, gate, refining > 0, t0, I);
 }
 
 int hnet_filters_last_priors(const hnet_filters* f, int n, float* out) {
@@ -675,10 +772,17 @@ int hnet_filters_advance(hnet_filters* f, int n, const int32_t* ids, hnet_filter
     const int n_a = (int)order.size();
     int n_s = 0;
     for (int i = 0; i < n; i++) n_s += status[i] == HNET_ADV_STEPPED;
+    std::vector<int32_t> stepping(n_s);
+    for (int j = 0; j < n_s; j++) stepping[j] = ids[order[j]];
+    int refine_ref = -1;
+    const int refining = filters_refining(f, n_s, stepping.data(), &refine_ref);
+    if (refining < 0) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_advance: the sessions with refinement on differ in align / levels (hnet_filters_set_photo_refine)");
+    if (!refining) refine_ref = -1;
     if (net_out) memset(net_out, 0, (size_t)I * n * 72 * sizeof(float));
     if (updates) memset(updates, 0, (size_t)n * sizeof(int32_t));
     std::fill(f->last_slot.begin(), f->last_slot.end(), -1);
     f->last_photo_n = 0;                                           // (a call in which nothing steps has no photometric records, whatever the call before it left)
+    f->last_refine_n = 0;
     if (n_a == 0) return HNET_OK;
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
     const AdvLayout L(n_a, I);
@@ -719,8 +823,8 @@ int hnet_filters_advance(hnet_filters* f, int n, const int32_t* ids, hnet_filter
         HIPCHK(c, launch_filter_select(d_job, n_a, s->n, f->cap, f->d_ring, f->d_meta, f->d_state, d_work, f->d_sel, d_res, st));
         if (n_s) HIPCHK(c, launch_session_gather(s->ring, 2 * s->n, d_pairs, n_s, (uint8_t*)c->stage_prev, (uint8_t*)c->stage_curr, st));
         HIPCHK(c, launch_filter_propagate_adv(d_job, n_a, s->n, f->cap, f->d_state, f->d_params, f->d_sel, d_res, d_work, st));
-        if (const int r = filters_enqueue_iekf(f, ctx, o.d, n_s, d_ids, d_gate, d_seq, n_a, photo_gated, st); r != HNET_OK) return r;     // (the sequence table has a row of n_a per iteration)
-        if (n_s) HIPCHK(c, hipMemcpyAsync(f->pin_out, f->d_out, filters_down_head(f, n_s), hipMemcpyDeviceToHost, st));
+        if (const int r = filters_enqueue_iekf(f, ctx, o.d, n_s, d_ids, d_gate, d_seq, n_a, photo_gated, refine_ref, st); r != HNET_OK) return r;     // (the sequence table has a row of n_a per iteration)
+        if (n_s) HIPCHK(c, hipMemcpyAsync(f->pin_out, f->d_out, filters_down_head(f, n_s, refining > 0), hipMemcpyDeviceToHost, st));
         if (state_out) HIPCHK(c, hipMemcpyAsync(f->pin_out + f->off_work, d_work, (size_t)n_a * sizeof(FilterRec), hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipMemcpyAsync(f->pin_out + f->off_res, d_res, (size_t)n_a * sizeof(AdvanceResult), hipMemcpyDeviceToHost, st));
         return filters_flags(ctx, flag_now, st);
@@ -757,7 +861,7 @@ int hnet_filters_advance(hnet_filters* f, int n, const int32_t* ids, hnet_filter
         }
         if (state_out) memcpy(state_out + i, o.h.work + j, sizeof(FilterRec));
     }
-    return filters_accepted(f, n_s, hid, gate, t_begin, n_s ? I : 0);     // (the stepping sessions are the first n_s of the call's id table)
+    return filters_accepted(f, n_s, hid, gate, refining > 0, t_begin, n_s ? I : 0);     // (the stepping sessions are the first n_s of the call's id table)
 }
 
 int hnet_filters_last_selection(hnet_filters* f, int id, hnet_imu* out, int cap, int* count) {
@@ -790,12 +894,12 @@ static_assert((int)HNET_INNOV_NONE == (int)hnet_ekf::INNOV_NONE && (int)HNET_INN
 // The output block with room for another kind of record: a new device block and pinned copy laid out for (innov, photo) and `extra_bytes` of zeroed device
 // memory (*extra: the gates start open; the partials are scratch), the old blocks freed only when everything is there.  On failure the layout is the old
 // one again and nothing of the object has changed.
-static int filters_relayout(hnet_filters* f, bool innov, bool photo, const char* who, void** extra, size_t extra_bytes) {
+static int filters_relayout(hnet_filters* f, bool innov, bool photo, bool refine, const char* who, void** extra, size_t extra_bytes) {
     hnet_ctx* c = f->s->ctx;
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
     HIPCHK(c, hipStreamSynchronize(c->stream));                    // (nothing enqueued reads the old output block any more)
     const int B = c->cfg.max_batch;
-    filters_out_layout(f, B, innov, photo);
+    filters_out_layout(f, B, innov, photo, refine);
     uint8_t *d_out = nullptr, *pin_out = nullptr;
     void* d_extra = nullptr;
     hipError_t e = hipMalloc((void**)&d_out, f->out_bytes);
@@ -805,7 +909,7 @@ static int filters_relayout(hnet_filters* f, bool innov, bool photo, const char*
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) {
         drop_dev(d_out); drop_pin(pin_out); drop_dev(d_extra);
-        filters_out_layout(f, B, f->innov, f->photo);
+        filters_out_layout(f, B, f->innov, f->photo, f->refine);
         return fail(c, HNET_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
     }
     (void)hipFree(f->d_out);
@@ -816,6 +920,7 @@ static int filters_relayout(hnet_filters* f, bool innov, bool photo, const char*
     f->last_n = 0;                                                 // what last_priors / last_selection / last_innovations / last_photometric described went with the old block
     f->last_innov_n = 0;
     f->last_photo_n = 0;
+    f->last_refine_n = 0;
     std::fill(f->last_slot.begin(), f->last_slot.end(), -1);
     return HNET_OK;
 }
@@ -824,7 +929,7 @@ int hnet_filters_enable_innovations(hnet_filters* f) {
     if (!f) return HNET_ERR_INVALID_ARG;
     if (f->innov) return fail(f->s->ctx, HNET_ERR_INVALID_ARG, "hnet_filters_enable_innovations: already enabled");
     const int N = f->s->n;
-    const int rc = filters_relayout(f, true, f->photo, "hnet_filters_enable_innovations", (void**)&f->d_max_nis, (size_t)N * sizeof(double));
+    const int rc = filters_relayout(f, true, f->photo, f->refine, "hnet_filters_enable_innovations", (void**)&f->d_max_nis, (size_t)N * sizeof(double));
     if (rc != HNET_OK) return rc;
     f->innov_stats.assign(N, hnet_innovation_stats{0, 0, 0, 0.0, 0.0});
     f->innov = true;
@@ -879,7 +984,7 @@ int hnet_filters_enable_photometric(hnet_filters* f) {
     if (e == hipSuccess) e = hipMemsetAsync(f->d_photo_verdict, 0, (size_t)B * sizeof(int32_t), c->stream);
     int rc = e == hipSuccess ? HNET_OK : fail(c, HNET_ERR_DEVICE, std::string("hnet_filters_enable_photometric: ") + hipGetErrorString(e));
     const size_t part = photo_partial_count(B, 2 + f->iters) * sizeof(PhotoRec);
-    if (rc == HNET_OK) rc = filters_relayout(f, f->innov, true, "hnet_filters_enable_photometric", (void**)&f->d_photo_part, part);      // (synchronises)
+    if (rc == HNET_OK) rc = filters_relayout(f, f->innov, true, false, "hnet_filters_enable_photometric", (void**)&f->d_photo_part, part);      // (synchronises)
     if (rc != HNET_OK) {
         drop_dev(f->d_photo_gate); drop_dev(f->d_photo_verdict);
         return rc;
@@ -932,6 +1037,92 @@ int hnet_filters_last_photometric(const hnet_filters* f, int n, hnet_photo_resid
     if (!f->photo || f->last_photo_n < 1) return fail(f->s->ctx, HNET_ERR_INVALID_ARG, "hnet_filters_last_photometric: the last step ran without photometric records");
     if (n != f->last_photo_n) return fail(f->s->ctx, HNET_ERR_INVALID_ARG, "hnet_filters_last_photometric: n differs from the last step's");
     memcpy(out, filters_out_view(f, f->pin_out).photo, (size_t)n * (2 + f->iters) * sizeof(PhotoRec));
+    return HNET_OK;
+}
+
+// ---- filters, the photometric fallback (include/hnet.h): csrc/kernels_filters_refine.hip around the robust alignment, inside hnet_filters_step / _advance ----
+
+static_assert(sizeof(hnet_photo_refine) == sizeof(RefineRec) && offsetof(hnet_photo_refine, r_px) == offsetof(RefineRec, r_px) && offsetof(hnet_photo_refine, innov) == offsetof(RefineRec, r) &&
+              offsetof(hnet_photo_refine, flags) == offsetof(RefineRec, flags) && sizeof(hnet_photo_refine_opts) == sizeof(RefineOpts) &&
+              offsetof(hnet_photo_refine_opts, levels) == offsetof(RefineOpts, levels) && offsetof(hnet_photo_refine_opts, cov_scale) == offsetof(RefineOpts, cov_scale) &&
+              offsetof(hnet_photo_refine_opts, max_mse) == offsetof(RefineOpts, max_mse), "hnet_photo_refine / _opts are the layouts of include/hnet_photo_refine.h");
+static_assert((int)HNET_REFINE_ASKED == hnet_refine::ASKED && (int)HNET_REFINE_APPLIED == hnet_refine::APPLIED && (int)HNET_REFINE_NIS_REJECTED == hnet_refine::NIS_REJECTED &&
+              (int)HNET_REFINE_S_SINGULAR == hnet_refine::S_SINGULAR && (int)HNET_REFINE_BAD_K_NET_COV == hnet_refine::BAD_K_NET_COV && (int)HNET_REFINE_STOPPED == hnet_refine::STOPPED &&
+              (int)HNET_REFINE_NO_STEP == hnet_refine::NO_STEP && (int)HNET_REFINE_MSE_ABOVE_MAX == hnet_refine::MSE_ABOVE_MAX && (int)HNET_REFINE_NO_FACTOR == hnet_refine::NO_FACTOR &&
+              (int)HNET_REFINE_NON_FINITE == hnet_refine::NON_FINITE && (int)HNET_REFINE_UNUSABLE == hnet_refine::UNUSABLE, "HNET_REFINE_* are the header's flags");
+
+void hnet_photo_refine_default_opts(hnet_photo_refine_opts* o) {
+    if (!o) return;
+    RefineOpts d;
+    hnet_refine::default_opts(d);
+    memcpy(o, &d, sizeof d);
+}
+
+int hnet_filters_set_photo_refine(hnet_filters* f, int id, const hnet_photo_refine_opts* opts) {
+    const char* who = "hnet_filters_set_photo_refine";
+    if (!f) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = f->s->ctx;
+    if (!f->photo) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": photometric records not enabled (hnet_filters_enable_photometric)");
+    if (id < 0 || id >= f->s->n) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": id out of range");
+    hnet_photo_refine_opts o;
+    memset(&o, 0, sizeof o);
+    if (opts) {
+        if (const int rc = photo_robust_check_opts(c, &opts->align, who); rc != HNET_OK) return rc;
+        o = *opts;
+        o.pad = o.align.pad = 0;                                   // (the sessions of a call are compared on the bytes of `align`)
+        RefineOpts r;
+        memcpy(&r, &o, sizeof r);
+        if (!hnet_refine::opts_valid(r))
+            return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": 1 <= levels <= 4, cov_scale > 0, sigma_floor_px >= 0, max_mse >= 0, all finite");
+    }
+    if (!opts && !f->refine) return HNET_OK;                       // (off, and never on)
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    const int N = f->s->n, B = c->cfg.max_batch;
+    if (!f->refine) {
+        const size_t pyr = (size_t)B * PYR_BYTES;
+        if (!c->pyr_scratch) HIPCHK(c, dalloc(&c->pyr_scratch, 2 * pyr));
+        RefineCfg* d_cfg = nullptr;
+        HIPCHK(c, dalloc(&d_cfg, (size_t)N));
+        hipError_t e = hipMemsetAsync(d_cfg, 0, (size_t)N * sizeof(RefineCfg), c->stream);
+        int rc = e == hipSuccess ? HNET_OK : fail(c, HNET_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+        if (rc == HNET_OK) rc = filters_relayout(f, f->innov, f->photo, true, who, (void**)&f->d_refine_scratch, RefineScratch(nullptr, B, N).bytes);      // (synchronises)
+        if (rc != HNET_OK) {
+            drop_dev(d_cfg);
+            return rc;
+        }
+        f->d_refine_cfg = d_cfg;
+        f->refine_opts.assign(N, hnet_photo_refine_opts{});
+        f->refine_on.assign(N, 0);
+        f->refine_stats.assign(N, hnet_refine_stats{0, 0, 0, 0, 0.0, 0.0});
+        f->refine = true;
+    }
+    const RefineCfg g{o.cov_scale, o.sigma_floor_px, o.max_mse, opts ? 1 : 0, 0};
+    HIPCHK(c, hipMemcpyAsync(f->d_refine_cfg + id, &g, sizeof g, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    f->refine_opts[id] = o;
+    f->refine_on[id] = opts ? 1 : 0;
+    return HNET_OK;
+}
+
+int hnet_filters_last_refine(const hnet_filters* f, int n, hnet_photo_refine* out) {
+    if (!f || !out) return HNET_ERR_INVALID_ARG;
+    if (!f->refine || f->last_refine_n < 1) return fail(f->s->ctx, HNET_ERR_INVALID_ARG, "hnet_filters_last_refine: the last step ran without a refining session");
+    if (n != f->last_refine_n) return fail(f->s->ctx, HNET_ERR_INVALID_ARG, "hnet_filters_last_refine: n differs from the last step's");
+    memcpy(out, filters_out_view(f, f->pin_out).refine, (size_t)n * sizeof(RefineRec));
+    return HNET_OK;
+}
+
+int hnet_filters_refine_stats(const hnet_filters* f, int id, hnet_refine_stats* out) {
+    if (!f || !out) return HNET_ERR_INVALID_ARG;
+    if (!f->refine || id < 0 || id >= f->s->n) return fail(f->s->ctx, HNET_ERR_INVALID_ARG, "hnet_filters_refine_stats: refinement never turned on or id out of range");
+    *out = f->refine_stats[id];
+    return HNET_OK;
+}
+
+int hnet_filters_reset_refine_stats(hnet_filters* f, int id) {
+    if (!f) return HNET_ERR_INVALID_ARG;
+    if (!f->refine || id < 0 || id >= f->s->n) return fail(f->s->ctx, HNET_ERR_INVALID_ARG, "hnet_filters_reset_refine_stats: refinement never turned on or id out of range");
+    f->refine_stats[id] = hnet_refine_stats{0, 0, 0, 0, 0.0, 0.0};
     return HNET_OK;
 }
 

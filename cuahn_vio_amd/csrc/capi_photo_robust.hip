@@ -1,6 +1,7 @@
 // capi_photo_robust.hip — hnet_photo_robust_* and hnet_op_photo_align_robust of include/hnet.h (photo_robust_dev.h, csrc/kernels_photo_robust.hip):
 // photometric alignment with a gain / bias model and Huber weights.  The sessions form (capi_sessions.hip) runs on photo_robust_run below.
 #include "capi_internal.h"
+#include "filters_refine_dev.h"
 
 using namespace hnet;
 using namespace capi;
@@ -91,34 +92,12 @@ int hnet_op_photo_align_robust(hnet_ctx* c, const uint8_t* img1, const uint8_t* 
     return photo_robust_run(c, d_in, d_in + img, n, reinterpret_cast<const float*>(d_in + 2 * img), *opts, levels, out, levels_out);
 }
 
-// the Schur complement of the brightness block: info8 = A_xx - A_xc A_cc^-1 A_cx, grad8 = g_x - A_xc A_cc^-1 g_c
+// the Schur complement of the brightness block: info8 = A_xx - A_xc A_cc^-1 A_cx, grad8 = g_x - A_xc A_cc^-1 g_c (include/hnet_photo_refine.h marginal)
 int hnet_photo_robust_marginal(const hnet_photo_robust* rec, double info8[64], double grad8[8]) {
     if (!rec || !info8 || !grad8) return HNET_ERR_INVALID_ARG;
-    const double* A = rec->info10;
-    bool off = true;
-    for (int j = 0; j < 10; j++) off = off && A[80 + j] == 0.0 && A[90 + j] == 0.0 && A[j * 10 + 8] == 0.0 && A[j * 10 + 9] == 0.0;
-    if (off) {
-        memcpy(info8, rec->px.info, 64 * sizeof(double));
-        memcpy(grad8, rec->px.grad, 8 * sizeof(double));
-        return HNET_OK;
-    }
-    // Cholesky of [[a, b], [b, d]]
-    const double a = A[88], b = A[89], d = A[99];
-    if (!(a > 0.0) || !std::isfinite(a)) return HNET_ERR_INVALID_ARG;
-    const double l00 = std::sqrt(a), l10 = b / l00, d2 = d - l10 * l10;
-    if (!(d2 > 0.0) || !std::isfinite(d2)) return HNET_ERR_INVALID_ARG;
-    const double l11 = std::sqrt(d2);
-    // y_i = L^-1 (A_cx column i), yg = L^-1 g_c
-    double y0[8], y1[8];
-    for (int i = 0; i < 8; i++) {
-        y0[i] = A[i * 10 + 8] / l00;
-        y1[i] = (A[i * 10 + 9] - l10 * y0[i]) / l11;
-    }
-    const double yg0 = rec->grad10[8] / l00, yg1 = (rec->grad10[9] - l10 * yg0) / l11;
-    for (int i = 0; i < 8; i++) {
-        for (int j = 0; j < 8; j++) info8[i * 8 + j] = A[i * 10 + j] - (y0[i] * y0[j] + y1[i] * y1[j]);
-        grad8[i] = rec->grad10[i] - (y0[i] * yg0 + y1[i] * yg1);
-    }
+    RobustRec r;
+    memcpy(&r, rec, sizeof r);
+    if (!hnet_refine::marginal(r, info8, grad8)) return HNET_ERR_INVALID_ARG;
     return HNET_OK;
 }
 

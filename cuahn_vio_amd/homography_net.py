@@ -876,6 +876,26 @@ class HnetFilters:
         """tools: the single-candidate launches of a gated step read img2 from global memory (True) or stage it in LDS (False); same records"""
         self._check(self._L.hnet_filters_set_photo_gate_taps(self._f, 1 if from_global else 0))
 
+    # ---- the photometric fallback (include/hnet.h hnet_filters_set_photo_refine) ----
+    def set_photo_refine(self, id, opts):
+        """session id's fallback after a photometric refusal at iteration 0 (needs enable_photometric): opts from _capi.photo_refine_opts(cov_scale = ...,
+        ...), None = off.  The refining sessions of one step must share the alignment options and levels"""
+        self._check(self._L.hnet_filters_set_photo_refine(self._f, int(id), C.byref(opts) if opts is not None else None))
+
+    def last_refine(self, n):
+        """the records [n] of _capi.PHOTO_REFINE_DTYPE of the last step (of n sessions; another n, or a step without a refining session, is refused)"""
+        out = np.zeros(int(n), _capi.PHOTO_REFINE_DTYPE)
+        self._check(self._L.hnet_filters_last_refine(self._f, int(n), out.ctypes.data))
+        return out
+
+    def refine_stats(self, id):
+        st = _capi.RefineStats()
+        self._check(self._L.hnet_filters_refine_stats(self._f, int(id), C.byref(st)))
+        return {"asked": st.asked, "applied": st.applied, "unusable": st.unusable, "nis_rejected": st.nis_rejected, "sum_nis": st.sum_nis, "max_nis": st.max_nis}
+
+    def reset_refine_stats(self, id):
+        self._check(self._L.hnet_filters_reset_refine_stats(self._f, int(id)))
+
     def last_priors(self, n):
         """the fp32 priors [iters, n, 8] the forwards of the last step (of n sessions; another n is refused) read"""
         out = np.zeros((self.iters, int(n), 8), np.float32)

@@ -697,6 +697,69 @@ int  hnet_sessions_photo_align_robust(hnet_sessions* s, int n, const int32_t* id
  * HNET_ERR_INVALID_ARG, nothing written, for a null argument or when the 2 x 2 block has no Cholesky factor. */
 int  hnet_photo_robust_marginal(const hnet_photo_robust* rec, double info8[64], double grad8[8]);
 
+/* ---- hnet_filters: a photometric alignment as the fallback measurement after a refusal (csrc/kernels_filters_refine.hip; the shared code is
+ * include/hnet_photo_refine.h).  Per session and off by default.  When the photometric gate (hnet_filters_set_photo_gate) refuses a session's
+ * estimate at ITERATION 0, the session would get no measurement this frame.  With refinement on, the step instead runs hnet_op_photo_align_robust's
+ * launch sequence on the session's frame pair from iteration 0's fp32 prior (hnet_filters_last_priors row 0) and applies the level-0 record as the
+ * measurement of one more update, hnet_ekf::iterated_update_photo_refined:
+ *   mean  = px.offsets_px,
+ *   R_px  = cov_scale * px.mse * inverse(info8) + sigma_floor_px^2 I, symmetrised, info8 = hnet_photo_robust_marginal's,
+ * handed to the unchanged update as the packed record {mean | (float)(R_px / k_net_cov)}, against the prior of the propagated state, with
+ * update_offset = 0; the offsets are reset afterwards as always.  cov_scale is the CALLER's: nothing calibrates mse * inverse(info8) against the real
+ * error (correlated pixels make it too small; tools/photo_refine_calibrate.py prints what synthetic texture says) - hence no default.
+ * The measurement is UNUSABLE, and the session keeps the state the refusal alone leaves, when (one reason bit each, tested in this order) k_net_cov is not
+ * finite and positive; the record stopped HNET_ALIGN_SINGULAR, _DEGENERATE or _FEW_PIXELS; no trial was accepted at any level (the "measurement" would be
+ * the prior itself); max_mse > 0 and px.mse > max_mse; the marginal has no Cholesky factor (a pivot <= 1e-12 max diag) or the inverse reports singular;
+ * an entry of R_px is not finite.
+ * updates[i] counts the fallback update when it is applied; a fallback S found singular is reported as the existing -1 - applied (= -1).  The records of
+ * hnet_filters_last_innovations and hnet_filters_last_photometric keep their shape and content; the fallback's innovation lives in the refine record
+ * (iteration = max_iekf_iteration) and is filled whether or not hnet_filters_enable_innovations was called.  The session's NIS gate, when set, applies to
+ * the fallback.  A refusal at iteration >= 1, a NIS rejection and a singular S trigger no fallback.
+ * A step or advance in which at least one STEPPING session has refinement on AND a photometric gate enqueues the fallback's launches for all its
+ * stepping sessions (the host knows the configuration, never the verdicts; sessions not refused align from NaN offsets, which costs their workgroups an
+ * early return): 3 small kernels, the alignment's sequence, one prior, one innovation and one update launch, inside the attempt (a repeat redoes
+ * them) and inside hnet_filters_last_timing's device window.  Still one upload, one download, one synchronisation.  Any other call launches exactly what
+ * it launched before, and its results are bit for bit what they are without this API.  All refining sessions of one call must share `align` and `levels`
+ * (one launch sequence serves them): a mismatch is HNET_ERR_INVALID_ARG from the step or advance, nothing changed; cov_scale, sigma_floor_px and max_mse
+ * are per session. */
+typedef struct hnet_photo_refine_opts {
+    hnet_photo_robust_opts align;
+    int32_t levels;            /* 1 .. 4 */
+    int32_t pad;
+    double  cov_scale;         /* > 0; hnet_photo_refine_default_opts leaves 0 on purpose: the caller must choose it */
+    double  sigma_floor_px;    /* >= 0: sigma_floor_px^2 is added to the diagonal of R_px */
+    double  max_mse;           /* 0 = no limit; else a record with px.mse above it is unusable */
+} hnet_photo_refine_opts;
+void hnet_photo_refine_default_opts(hnet_photo_refine_opts* o);      /* robust defaults, 3, 0 (!), 0.05, 0 */
+enum { HNET_REFINE_ASKED = 1,            /* the gate refused iteration 0 of a session with refinement on: `rec` is its alignment's level-0 record */
+       HNET_REFINE_APPLIED = 2,          /* the fallback update was applied */
+       HNET_REFINE_NIS_REJECTED = 4,     /* the session's NIS gate refused the fallback */
+       HNET_REFINE_S_SINGULAR = 8,       /* the fallback's S was singular */
+       HNET_REFINE_BAD_K_NET_COV = 16, HNET_REFINE_STOPPED = 32, HNET_REFINE_NO_STEP = 64, HNET_REFINE_MSE_ABOVE_MAX = 128, HNET_REFINE_NO_FACTOR = 256,
+       HNET_REFINE_NON_FINITE = 512,     /* the UNUSABLE reasons, in the order above */
+       HNET_REFINE_UNUSABLE = 16 | 32 | 64 | 128 | 256 | 512 };
+typedef struct hnet_photo_refine {
+    hnet_photo_robust rec;     /* level 0 of the alignment: byte for byte hnet_sessions_photo_align_robust's from the same start and options */
+    double  r_px[64];          /* zeros when unusable */
+    hnet_innovation innov;     /* hnet_ekf::innovation of the fallback measurement; iteration = max_iekf_iteration; HNET_INNOV_NONE (zeros) when unusable */
+    int32_t flags;             /* HNET_REFINE_*; 0 (and the whole record zero) for a session that asked for no fallback */
+    int32_t pad;               /* written as zero: records compare byte for byte */
+} hnet_photo_refine;
+/* opts == NULL turns refinement off for the session.  The first call with options allocates the alignment's scratch and grows the output block
+ * (hnet_filters_last_* have nothing to describe until the next step).  HNET_ERR_INVALID_ARG, nothing changed: a bad id, a call before
+ * hnet_filters_enable_photometric, options hnet_op_photo_align_robust would refuse, levels outside 1 .. 4, cov_scale <= 0 or not finite, a negative or
+ * non-finite sigma_floor_px or max_mse. */
+int  hnet_filters_set_photo_refine(hnet_filters* f, int id, const hnet_photo_refine_opts* opts);
+/* the records [n] of the last step (n: its n) or advance (n: its STEPPED sessions, in the order listed).  A wrong n, or a last call that ran without a
+ * refining session: HNET_ERR_INVALID_ARG, nothing written */
+int  hnet_filters_last_refine(const hnet_filters* f, int n, hnet_photo_refine* out);
+/* per session, accumulated on the host from the records of accepted calls only (a repeated attempt never counts twice): asked, applied, unusable (any
+ * reason bit), nis_rejected; sum_nis / max_nis over the fallbacks whose NIS was formed and finite (applied or NIS-rejected): what a caller calibrates
+ * cov_scale with (a consistent filter gives a mean of 8). */
+typedef struct hnet_refine_stats { int64_t asked, applied, unusable, nis_rejected; double sum_nis, max_nis; } hnet_refine_stats;
+int  hnet_filters_refine_stats(const hnet_filters* f, int id, hnet_refine_stats* out);
+int  hnet_filters_reset_refine_stats(hnet_filters* f, int id);
+
 int hnet_synchronize(hnet_ctx* ctx, void* stream);
 int hnet_last_timing(const hnet_ctx* ctx, hnet_timing* out);
 
