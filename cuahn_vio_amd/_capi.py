@@ -49,6 +49,8 @@ SYMBOLS = [
     "hnet_op_photo_align_pyramid", "hnet_sessions_photo_align_pyramid", "hnet_op_photo_pyramid",
     "hnet_photo_robust_default_opts", "hnet_op_photo_align_robust", "hnet_sessions_photo_align_robust", "hnet_photo_robust_marginal",
     "hnet_photo_refine_default_opts", "hnet_filters_set_photo_refine", "hnet_filters_last_refine", "hnet_filters_refine_stats", "hnet_filters_reset_refine_stats",
+    "hnet_keyframe_default_opts", "hnet_sessions_enable_keyframes", "hnet_sessions_keyframe_track", "hnet_sessions_keyframe_reset", "hnet_sessions_get_keyframe",
+    "hnet_sessions_last_keyframe_device_ms",
 ]
 # hnet_filters_advance's status per listed session (include/hnet.h HNET_ADV_*)
 ADV_STEPPED, ADV_WAIT_IMU, ADV_WAIT_INIT, ADV_INITIALIZED, ADV_PROPAGATED, ADV_NO_FRAME = range(6)
@@ -204,6 +206,41 @@ def photo_refine_opts(**kw):
             setattr(o, k, v)
         else:
             raise TypeError(f"hnet_photo_refine_opts has no field {k!r}")
+    return o
+
+
+# hnet_keyframe_track: one record per tracked session (hnet_sessions_keyframe_track); flags KF_* (include/hnet.h HNET_KF_*)
+KEYFRAME_TRACK_DTYPE = _np.dtype([("rec", PHOTO_ROBUST_DTYPE), ("start_px", "<f4", 8), ("key_px", "<f4", 8), ("h_origin_curr", "<f8", (3, 3)), ("overlap", "<f8"),
+                                  ("age", "<i4"), ("keyframes", "<i4"), ("flags", "<i4"), ("pad", "<i4")])
+assert KEYFRAME_TRACK_DTYPE.itemsize == 1560 + 160
+KF_FIRST, KF_REKEYED, KF_BRIDGED, KF_GAP, KF_LOW_OVERLAP, KF_MAX_AGE = 1, 2, 4, 8, 16, 32
+KF_NO_START, KF_STOPPED, KF_MSE_ABOVE_MAX, KF_NON_FINITE, KF_ORIGIN_RESTARTED = 64, 128, 256, 512, 1024
+KF_LOST = 64 | 128 | 256 | 512
+
+
+class KeyframeOpts(C.Structure):
+    """hnet_keyframe_opts: the alignment's options and levels, whether the session re-keys by itself, the age (frames) and the overlap (fraction of the
+    frame) at which it does, and the largest mse of a tracked frame (0: no limit)"""
+    _fields_ = [("align", PhotoRobustOpts), ("levels", C.c_int32), ("auto_rekey", C.c_int32), ("max_age", C.c_int32), ("pad", C.c_int32),
+                ("rekey_overlap", C.c_double), ("max_mse", C.c_double)]
+
+
+assert C.sizeof(KeyframeOpts) == 56 + 32
+
+
+def keyframe_opts(**kw):
+    """the defaults of hnet_keyframe_default_opts with the given fields replaced (the fields of `align` and its `base` by their own names)"""
+    o = KeyframeOpts()
+    lib().hnet_keyframe_default_opts(C.byref(o))
+    for k, v in kw.items():
+        if k in ("max_iterations", "min_valid", "lambda0", "eps_px"):
+            setattr(o.align.base, k, v)
+        elif k in ("brightness", "huber_k", "gain0", "bias0"):
+            setattr(o.align, k, v)
+        elif k in ("levels", "auto_rekey", "max_age", "rekey_overlap", "max_mse"):
+            setattr(o, k, v)
+        else:
+            raise TypeError(f"hnet_keyframe_opts has no field {k!r}")
     return o
 
 
@@ -383,6 +420,14 @@ def lib():
     L.hnet_op_photo_align_robust.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp]
     L.hnet_sessions_photo_align_robust.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp, vp]
     L.hnet_photo_robust_marginal.argtypes = [vp, vp, vp]
+    L.hnet_keyframe_default_opts.argtypes = [C.POINTER(KeyframeOpts)]
+    L.hnet_keyframe_default_opts.restype = None
+    L.hnet_sessions_enable_keyframes.argtypes = [vp]
+    L.hnet_sessions_keyframe_track.argtypes = [vp, C.c_int, vp, vp, vp, vp]
+    L.hnet_sessions_keyframe_reset.argtypes = [vp, C.c_int]
+    L.hnet_sessions_get_keyframe.argtypes = [vp, C.c_int, vp]
+    L.hnet_sessions_last_keyframe_device_ms.argtypes = [vp]
+    L.hnet_sessions_last_keyframe_device_ms.restype = C.c_double
     L.hnet_last_photo_align_device_ms.restype = C.c_double
     L.hnet_photo_refine_default_opts.argtypes = [C.POINTER(PhotoRefineOpts)]
     L.hnet_photo_refine_default_opts.restype = None

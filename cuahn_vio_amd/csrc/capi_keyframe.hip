@@ -1,0 +1,214 @@
+// capi_keyframe.hip — hnet_keyframe_* and hnet_sessions_*keyframe* of include/hnet.h (keyframe_dev.h, csrc/kernels_keyframe.hip): per session a
+// frame held longer than one tick, and one call that aligns each listed session's current frame against it from a composed start and applies the rule of
+// include/hnet_keyframe.h on the device.  Additive: a sessions object that never enables keyframes has s->kf == nullptr and allocates and launches nothing here.
+#include "sessions_internal.h"
+#include "keyframe_dev.h"
+
+using namespace hnet;
+using namespace capi;
+
+static_assert(sizeof(hnet_keyframe_track) == sizeof(KeyTrack) && offsetof(hnet_keyframe_track, start_px) == offsetof(KeyTrack, start_px) &&
+              offsetof(hnet_keyframe_track, key_px) == offsetof(KeyTrack, key_px) && offsetof(hnet_keyframe_track, h_origin_curr) == offsetof(KeyTrack, h_origin_curr) &&
+              offsetof(hnet_keyframe_track, overlap) == offsetof(KeyTrack, overlap) && offsetof(hnet_keyframe_track, flags) == offsetof(KeyTrack, flags) &&
+              sizeof(hnet_keyframe_opts) == sizeof(KeyOpts) && offsetof(hnet_keyframe_opts, levels) == offsetof(KeyOpts, levels) &&
+              offsetof(hnet_keyframe_opts, max_age) == offsetof(KeyOpts, max_age) && offsetof(hnet_keyframe_opts, rekey_overlap) == offsetof(KeyOpts, rekey_overlap) &&
+              offsetof(hnet_keyframe_opts, max_mse) == offsetof(KeyOpts, max_mse), "hnet_keyframe_track / _opts are the layouts of include/hnet_keyframe.h");
+static_assert((int)HNET_KF_FIRST == hnet_keyframe::FIRST && (int)HNET_KF_REKEYED == hnet_keyframe::REKEYED && (int)HNET_KF_BRIDGED == hnet_keyframe::BRIDGED &&
+              (int)HNET_KF_GAP == hnet_keyframe::GAP && (int)HNET_KF_LOW_OVERLAP == hnet_keyframe::LOW_OVERLAP && (int)HNET_KF_MAX_AGE == hnet_keyframe::MAX_AGE &&
+              (int)HNET_KF_NO_START == hnet_keyframe::NO_START && (int)HNET_KF_STOPPED == hnet_keyframe::STOPPED && (int)HNET_KF_MSE_ABOVE_MAX == hnet_keyframe::MSE_ABOVE_MAX &&
+              (int)HNET_KF_NON_FINITE == hnet_keyframe::NON_FINITE && (int)HNET_KF_ORIGIN_RESTARTED == hnet_keyframe::ORIGIN_RESTARTED &&
+              (int)HNET_KF_LOST == hnet_keyframe::LOST, "HNET_KF_* are the header's flags");
+
+// the store: everything is sized at enable, for the sessions' count N and the context's max_batch B
+struct hnet_keyframes {
+    uint8_t* key = nullptr;                    // device [N][NPIX], zeroed at enable
+    KeyState* state = nullptr;                 // device [N], zeroed at enable (has_key = 0)
+    uint8_t* scratch = nullptr;                // device: the sections of KeyScratch
+    uint8_t *pin_in = nullptr, *pin_out = nullptr;     // pinned: one call's table and its records [B]
+    hipEvent_t ev[2] = {nullptr, nullptr};     // around the launch sequence of the last track: events of its own, every hnet_timing stays as it was
+    double ms = 0.0;
+    // host mirror of what the device state decides deterministically: whether the session holds a keyframe, and its image count at its previous track
+    std::vector<uint8_t> has_key;
+    std::vector<int> count_at_track;
+};
+
+namespace {
+
+size_t table_bytes(int n) { return (size_t)n * (8 * sizeof(float) + 3 * sizeof(int32_t)); }
+
+// the sections of the scratch for max_batch B: the alignment's, as capi_filters.hip sizes them for 7o, then the call's table, start, records and copy flags
+struct KeyScratch {
+    RobustRec* rec; RobustStart* start; RobustWork* work; RobustSums* part; float* x0; uint8_t* tab; KeyTrack* out; int32_t* copy; size_t bytes;
+    KeyScratch(uint8_t* b, int B) {
+        size_t o = 0;
+        auto take = [&](size_t n) { uint8_t* p = b + o; o += (n + 255) & ~(size_t)255; return p; };
+        rec = reinterpret_cast<RobustRec*>(take((size_t)HNET_ALIGN_MAX_LEVELS * B * sizeof(RobustRec)));
+        start = reinterpret_cast<RobustStart*>(take((size_t)B * sizeof(RobustStart)));
+        work = reinterpret_cast<RobustWork*>(take((size_t)B * sizeof(RobustWork)));
+        part = reinterpret_cast<RobustSums*>(take((size_t)B * PHOTO_SLICES * sizeof(RobustSums)));
+        x0 = reinterpret_cast<float*>(take((size_t)B * 8 * sizeof(float)));
+        tab = take(table_bytes(B));
+        out = reinterpret_cast<KeyTrack*>(take((size_t)B * sizeof(KeyTrack)));
+        copy = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
+        bytes = o;
+    }
+};
+
+// the table of a call of n slots inside a block that holds it
+KeyTable table_view(const uint8_t* b, int n) {
+    const float* step = reinterpret_cast<const float*>(b);
+    const int32_t* ids = reinterpret_cast<const int32_t*>(step + (size_t)8 * n);
+    return KeyTable{step, ids, ids + n, ids + 2 * (size_t)n};
+}
+
+void keyframes_free(hnet_keyframes* k) {
+    if (!k) return;
+    if (k->key) (void)hipFree(k->key);
+    if (k->state) (void)hipFree(k->state);
+    if (k->scratch) (void)hipFree(k->scratch);
+    if (k->pin_in) (void)hipHostFree(k->pin_in);
+    if (k->pin_out) (void)hipHostFree(k->pin_out);
+    for (hipEvent_t e : k->ev)
+        if (e) (void)hipEventDestroy(e);
+    delete k;
+}
+
+}  // namespace
+
+namespace capi {
+
+// (hnet_destroy_sessions has set the device and drained the stream)
+void keyframes_destroy(hnet_sessions* s) {
+    keyframes_free(s->kf);
+    s->kf = nullptr;
+}
+
+// the session's keyframe and origin chain are dropped: its next track is FIRST.  Stream ordered behind every enqueued track; nothing is synchronised.
+int keyframes_drop(hnet_sessions* s, int id) {
+    hnet_keyframes* k = s->kf;
+    if (!k) return HNET_OK;
+    hnet_ctx* c = s->ctx;
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    HIPCHK(c, hipMemsetAsync(k->state + id, 0, sizeof(KeyState), c->stream));
+    k->has_key[id] = 0;
+    k->count_at_track[id] = -1;
+    return HNET_OK;
+}
+
+}  // namespace capi
+
+extern "C" {
+
+void hnet_keyframe_default_opts(hnet_keyframe_opts* o) {
+    if (!o) return;
+    KeyOpts d;
+    hnet_keyframe::default_opts(d);
+    memcpy(o, &d, sizeof d);
+}
+
+int hnet_sessions_enable_keyframes(hnet_sessions* s) {
+    const char* who = "hnet_sessions_enable_keyframes";
+    if (!s) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = s->ctx;
+    if (s->kf) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": keyframes are already enabled");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    const int B = c->cfg.max_batch, N = s->n;
+    const size_t pyr = (size_t)B * PYR_BYTES;
+    if (!c->pyr_scratch) HIPCHK(c, dalloc(&c->pyr_scratch, 2 * pyr));
+    hnet_keyframes* k = new hnet_keyframes();
+    hipError_t e = hipMalloc((void**)&k->key, (size_t)N * NPIX);
+    if (e == hipSuccess) e = hipMalloc((void**)&k->state, (size_t)N * sizeof(KeyState));
+    if (e == hipSuccess) e = hipMalloc((void**)&k->scratch, KeyScratch(nullptr, B).bytes);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&k->pin_in, table_bytes(B), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&k->pin_out, (size_t)B * sizeof(KeyTrack), hipHostMallocDefault);
+    for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipEventCreate(&k->ev[i]);
+    if (e == hipSuccess) e = hipMemsetAsync(k->key, 0, (size_t)N * NPIX, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(k->state, 0, (size_t)N * sizeof(KeyState), c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        keyframes_free(k);
+        return fail(c, HNET_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    }
+    k->has_key.assign(N, 0);
+    k->count_at_track.assign(N, -1);
+    s->kf = k;
+    return HNET_OK;
+}
+
+// ONE upload {step | ids | curr slot | gap}, the launch sequence inside the store's own events, ONE download of the records [n], one synchronisation
+int hnet_sessions_keyframe_track(hnet_sessions* s, int n, const int32_t* ids, const float* step_px, const hnet_keyframe_opts* opts, hnet_keyframe_track* out) {
+    const char* who = "hnet_sessions_keyframe_track";
+    if (!s) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = s->ctx;
+    hnet_keyframes* k = s->kf;
+    if (!k) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": keyframes are not enabled (hnet_sessions_enable_keyframes)");
+    if (!out || !opts) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": opts / out");
+    int rc = photo_robust_check_opts(c, &opts->align, who);
+    if (rc != HNET_OK) return rc;
+    KeyOpts o;
+    memcpy(&o, opts, sizeof o);
+    if (!hnet_keyframe::opts_valid(o))
+        return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": opts: 1 <= levels <= 4, auto_rekey 0 / 1, max_age >= 0, 0 <= rekey_overlap <= 1, max_mse >= 0 and finite");
+    if ((rc = sessions_check_ids(s, n, ids)) != HNET_OK) return rc;
+    for (int i = 0; i < n; i++)
+        if (s->st[ids[i]].count < 1) return fail(c, HNET_ERR_NOT_READY, std::string(who) + ": a listed session has no image");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    const int B = c->cfg.max_batch, N = s->n;
+    const KeyScratch w(k->scratch, B);
+    float* h_step = reinterpret_cast<float*>(k->pin_in);
+    int32_t* h_ids = reinterpret_cast<int32_t*>(h_step + (size_t)8 * n);
+    for (int i = 0; i < n; i++) {
+        const int id = ids[i];
+        for (int j = 0; j < 8; j++) h_step[8 * i + j] = step_px ? step_px[8 * i + j] : 0.0f;
+        h_ids[i] = id;
+        h_ids[n + i] = 2 * id + s->st[id].curr;
+        h_ids[2 * n + i] = k->has_key[id] && s->st[id].count != k->count_at_track[id] + 1 ? 1 : 0;
+    }
+    const KeyTable tab = table_view(w.tab, n);
+    const size_t pyr = (size_t)B * PYR_BYTES;
+    uint8_t *prev = (uint8_t*)c->stage_prev, *curr = (uint8_t*)c->stage_curr;
+    hipStream_t st = c->stream;
+    HIPCHK(c, hipMemcpyAsync(w.tab, k->pin_in, table_bytes(n), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipEventRecord(k->ev[0], st));
+    HIPCHK(c, launch_keyframe_start(tab, n, N, k->state, w.x0, st));
+    HIPCHK(c, launch_keyframe_gather(tab, n, N, k->key, s->ring, 2 * N, prev, curr, st));
+    HIPCHK(c, launch_photo_align_robust(prev, curr, n, w.x0, o.align, o.levels, c->pyr_scratch, c->pyr_scratch + pyr, w.start, w.part, w.work, w.rec, st));
+    HIPCHK(c, launch_keyframe_decide(tab, n, N, w.rec, w.x0, o, k->state, w.out, w.copy, st));
+    HIPCHK(c, launch_keyframe_commit(tab, n, N, w.copy, curr, k->key, st));
+    HIPCHK(c, hipEventRecord(k->ev[1], st));
+    HIPCHK(c, hipMemcpyAsync(k->pin_out, w.out, (size_t)n * sizeof(KeyTrack), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    float ms = 0;
+    HIPCHK(c, hipEventElapsedTime(&ms, k->ev[0], k->ev[1]));
+    k->ms = ms;
+    memcpy(out, k->pin_out, (size_t)n * sizeof(KeyTrack));
+    for (int i = 0; i < n; i++) {
+        k->has_key[ids[i]] = 1;
+        k->count_at_track[ids[i]] = s->st[ids[i]].count;
+    }
+    return HNET_OK;
+}
+
+int hnet_sessions_keyframe_reset(hnet_sessions* s, int id) {
+    if (!s) return HNET_ERR_INVALID_ARG;
+    if (!s->kf) return fail(s->ctx, HNET_ERR_INVALID_ARG, "hnet_sessions_keyframe_reset: keyframes are not enabled (hnet_sessions_enable_keyframes)");
+    if (id < 0 || id >= s->n) return fail(s->ctx, HNET_ERR_INVALID_ARG, "sessions: id out of range");
+    return keyframes_drop(s, id);
+}
+
+int hnet_sessions_get_keyframe(hnet_sessions* s, int id, uint8_t* out) {
+    const char* who = "hnet_sessions_get_keyframe";
+    if (!s) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = s->ctx;
+    if (!s->kf) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": keyframes are not enabled (hnet_sessions_enable_keyframes)");
+    if (!out || id < 0 || id >= s->n) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": id / out");
+    if (!s->kf->has_key[id]) return fail(c, HNET_ERR_NOT_READY, std::string(who) + ": the session holds no keyframe");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    HIPCHK(c, hipMemcpyAsync(out, s->kf->key + (size_t)id * NPIX, NPIX, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return HNET_OK;
+}
+
+double hnet_sessions_last_keyframe_device_ms(hnet_sessions* s) { return s && s->kf ? s->kf->ms : 0.0; }
+
+}  // extern "C"

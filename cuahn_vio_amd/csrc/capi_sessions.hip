@@ -82,6 +82,7 @@ void hnet_destroy_sessions(hnet_sessions* s) {
     hnet_ctx* c = s->ctx;
     (void)hipSetDevice(c->cfg.device_id);
     (void)hipStreamSynchronize(c->stream);
+    keyframes_destroy(s);
     auto fr = [](void* p) { if (p) (void)hipFree(p); };
     fr(s->ring); fr(s->slab); fr(s->d_tab); fr((void*)s->d_maps);
     for (auto& k : s->cams) { fr(k.map[0]); fr(k.map[1]); }
@@ -307,7 +308,7 @@ int hnet_sessions_reset(hnet_sessions* s, int id) {
     s->st[id].curr = 0;
     s->st[id].t = -1.0;
     s->st[id].t_push = NAN;
-    return HNET_OK;
+    return keyframes_drop(s, id);
 }
 
 int hnet_sessions_get_frame(hnet_sessions* s, int id, int which, uint8_t* out) {

@@ -29,12 +29,16 @@ struct hnet_sessions {
     uint8_t* d_tab = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hnet_timing timing = {};
+    struct hnet_keyframes* kf = nullptr;       // the keyframe store (hnet_sessions_enable_keyframes; capi_keyframe.hip) or null: never enabled
 };
 
 namespace capi __attribute__((visibility("hidden"))) {
 
 int sessions_check_ids(hnet_sessions* s, int n, const int32_t* ids);          // n distinct ids in range, n within the context's capacity
 int sessions_check_pairs(hnet_sessions* s, int n, const int32_t* ids);        // every listed session has a pair: HNET_ERR_NOT_READY otherwise (HomographyNet.cpp:155-158, per session)
+// the keyframe layer's part of hnet_destroy_sessions and hnet_sessions_reset (capi_keyframe.hip); both do nothing when keyframes were never enabled
+void keyframes_destroy(hnet_sessions* s);
+int keyframes_drop(hnet_sessions* s, int id);
 // the (prev, curr) ring slots of session `id`'s pair, as launch_session_gather reads them
 inline void sessions_pair(const hnet_sessions* s, int id, int32_t* pair) { pair[0] = 2 * id + (s->st[id].curr ^ 1); pair[1] = 2 * id + s->st[id].curr; }
 

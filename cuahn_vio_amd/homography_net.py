@@ -644,6 +644,33 @@ class HnetSessions:
                                                              lv.ctypes.data if want_levels else None))
         return (out, lv) if want_levels else out
 
+    def enable_keyframes(self):
+        """hnet_sessions_enable_keyframes: allocates the keyframe store; once"""
+        self._check(self._L.hnet_sessions_enable_keyframes(self._s))
+
+    def keyframe_track(self, ids, step_px=None, **opts):
+        """hnet_sessions_keyframe_track: the listed sessions' current frames against their keyframes, started from their state composed with step_px
+        [n, 8] (prev -> curr offsets; None: no motion) -> [n] of _capi.KEYFRAME_TRACK_DTYPE; opts as _capi.keyframe_opts"""
+        ids, n = self._ids(ids)
+        step = None if step_px is None else np.ascontiguousarray(step_px, dtype=np.float32).reshape(n, 8)
+        o = _capi.keyframe_opts(**opts)
+        out = np.zeros(n, _capi.KEYFRAME_TRACK_DTYPE)
+        self._check(self._L.hnet_sessions_keyframe_track(self._s, n, ids.ctypes.data, step.ctypes.data if step is not None else None, C.addressof(o),
+                                                         out.ctypes.data))
+        return out
+
+    def keyframe_reset(self, id):
+        self._check(self._L.hnet_sessions_keyframe_reset(self._s, int(id)))
+
+    def keyframe(self, id):
+        """the session's keyframe as the store holds it (hnet_sessions_get_keyframe)"""
+        out = np.zeros((IMG_H, IMG_W), np.uint8)
+        self._check(self._L.hnet_sessions_get_keyframe(self._s, int(id), out.ctypes.data))
+        return out
+
+    def last_keyframe_device_ms(self):
+        return float(self._L.hnet_sessions_last_keyframe_device_ms(self._s))
+
     def image_count(self, id):
         return int(self._L.hnet_sessions_image_count(self._s, int(id)))
 

@@ -760,6 +760,76 @@ typedef struct hnet_refine_stats { int64_t asked, applied, unusable, nis_rejecte
 int  hnet_filters_refine_stats(const hnet_filters* f, int id, hnet_refine_stats* out);
 int  hnet_filters_reset_refine_stats(hnet_filters* f, int id);
 
+/* ---- sessions, keyframes: each camera tracked against a HELD frame, on the device (csrc/kernels_keyframe.hip; the shared code is include/hnet_keyframe.h;
+ * DESIGN 7p).  Opt-in: a sessions object that never calls hnet_sessions_enable_keyframes allocates, launches and returns exactly what it did before.
+ * Everything else in this header measures between two consecutive frames, so a camera that hovers integrates frame-to-frame homographies and drifts
+ * without bound.  Here every session holds a KEYFRAME longer than one tick, and one call aligns the session's current frame against it with
+ * hnet_op_photo_align_robust's launch sequence: a measurement whose error does not grow with the number of frames.
+ * Conventions: offsets x are ul, bl, br, ur in pixels, H(x) = dlt_solve(p4 + x) in double with h[8] = 1 maps a template pixel to its sampling position in
+ * the other image, hence H_key->curr = H_prev->curr . H_key->prev.  Per session the device keeps {has_key, key_px (key -> previous tracked frame),
+ * h_origin_key (origin -> keyframe; the origin is the first keyframe since the last reset), age, keyframes}.
+ * One track, per listed session:
+ *   no keyframe yet: curr becomes the keyframe, HNET_KF_FIRST | HNET_KF_REKEYED, h_origin_curr = I, keyframes = 1, everything else zero.
+ *   else start_px = the corners of H(step_px) . H(key_px) minus p4 (step_px: the caller's prev -> curr offsets, e.g. the network's mean; NULL = no
+ *     motion); the alignment key -> curr runs from it and `rec` is its level-0 record, byte for byte hnet_op_photo_align_robust(keyframe, curr,
+ *     start_px) with the same options.  A start without a homography is quiet NaNs, on which the alignment reports HNET_ALIGN_DEGENERATE.
+ *   LOST (one reason bit, in this order): HNET_KF_NO_START; HNET_KF_STOPPED (rec stopped SINGULAR, DEGENERATE or FEW_PIXELS); HNET_KF_MSE_ABOVE_MAX
+ *     (max_mse > 0 and not mse <= max_mse); HNET_KF_NON_FINITE (an offset of rec).  A start that accepted no trial is not lost.  With auto_rekey the
+ *     session re-keys on curr (HNET_KF_REKEYED | HNET_KF_BRIDGED) and the origin chain is extended by the composed start (by the previous key_px when
+ *     the start has no homography): dead reckoning.  Without it the keyframe stays and key_px becomes the start (HNET_KF_BRIDGED) when that has a
+ *     homography.
+ *   TRACKED (all else): key_px = rec's offsets.  With auto_rekey the session re-keys AFTER this frame when overlap < rekey_overlap
+ *     (HNET_KF_LOW_OVERLAP) or max_age > 0 and age >= max_age (HNET_KF_MAX_AGE).
+ *   In both: age + 1, overlap = rec.px.n_valid / 71 680, h_origin_curr = H(key_px) . h_origin_key renormalised to h[8] = 1.  A re-key makes curr the
+ *   keyframe: h_origin_key = h_origin_curr, key_px = 0, age = 0, keyframes + 1.  The record's key_px and age are the frame's against the keyframe it was
+ *   measured on; keyframes counts the new one.  When a product of the origin chain has a non-finite entry or |h[8]| below 1e-12 of its largest entry
+ *   the chain restarts at the current keyframe (HNET_KF_ORIGIN_RESTARTED).  HNET_KF_GAP: the session's image count is not its count at the previous track + 1
+ *   (frames no track saw, or the same frame tracked again); it changes nothing else (the alignment's basin, 32 px at 3 levels, decides whether the start served).
+ * hnet_sessions_keyframe_track is read-only for everything the sessions had before: counts, ring, stamps, sequence numbers and
+ * hnet_sessions_last_timing stay as they were (it uses the context's staging arrays like hnet_sessions_photo_align_robust).
+ * Errors, nothing changed and nothing written: HNET_ERR_INVALID_ARG for a call before hnet_sessions_enable_keyframes, a second enable, a null opts or
+ * out, options hnet_op_photo_align_robust would refuse, levels outside 1 .. 4, auto_rekey outside 0 / 1, max_age < 0, rekey_overlap outside 0 .. 1, a
+ * negative or non-finite max_mse, n < 1, an id out of range or repeated; HNET_ERR_CAPACITY for n > max_batch; HNET_ERR_NOT_READY for a listed session
+ * without an image.
+ * Enable allocates the keyframe store [n_sessions][71 680] bytes (zeroed), the state table and the alignment's scratch for max_batch.  A track is ONE
+ * upload {step | ids | curr slot | gap}, 4 small launches around the alignment's sequence (start, gather, decide, commit), ONE download of the records [n]
+ * and one synchronisation; hnet_sessions_last_keyframe_device_ms covers the launches (events of its own). */
+typedef struct hnet_keyframe_opts {
+    hnet_photo_robust_opts align;
+    int32_t levels;            /* 1 .. 4 */
+    int32_t auto_rekey;        /* 0 / 1 */
+    int32_t max_age;           /* >= 0; 0 = no limit */
+    int32_t pad;
+    double  rekey_overlap;     /* 0 .. 1 */
+    double  max_mse;           /* >= 0; 0 = no limit */
+} hnet_keyframe_opts;
+enum { HNET_KF_FIRST = 1, HNET_KF_REKEYED = 2, HNET_KF_BRIDGED = 4, HNET_KF_GAP = 8,
+       HNET_KF_LOW_OVERLAP = 16, HNET_KF_MAX_AGE = 32,                                                   /* the re-key reasons of a TRACKED frame */
+       HNET_KF_NO_START = 64, HNET_KF_STOPPED = 128, HNET_KF_MSE_ABOVE_MAX = 256, HNET_KF_NON_FINITE = 512,    /* the LOST reasons, in the order tested */
+       HNET_KF_ORIGIN_RESTARTED = 1024,
+       HNET_KF_LOST = 64 | 128 | 256 | 512 };
+typedef struct hnet_keyframe_track {
+    hnet_photo_robust rec;      /* level 0, key -> curr; zeros when no alignment result was read (HNET_KF_FIRST) */
+    float   start_px[8];        /* what the alignment started from (quiet NaNs: no homography) */
+    float   key_px[8];          /* key -> curr: rec's offsets when TRACKED, the bridge when LOST */
+    double  h_origin_curr[9];   /* origin -> curr, h[8] = 1 */
+    double  overlap;            /* rec.px.n_valid / 71 680 */
+    int32_t age;                /* frames tracked on the keyframe this one was measured on, this one included */
+    int32_t keyframes;          /* keyframes taken since the last reset, a re-key of this frame included */
+    int32_t flags;              /* HNET_KF_* */
+    int32_t pad;                /* written zero: records compare byte for byte */
+} hnet_keyframe_track;
+void hnet_keyframe_default_opts(hnet_keyframe_opts* o);      /* robust defaults, levels 3, auto_rekey 1, max_age 0, rekey_overlap 0.6, max_mse 0 */
+int  hnet_sessions_enable_keyframes(hnet_sessions* s);       /* once; a second call is HNET_ERR_INVALID_ARG */
+int  hnet_sessions_keyframe_track(hnet_sessions* s, int n, const int32_t* ids, const float* step_px /* [n][8] prev -> curr, or NULL = no motion */,
+                                  const hnet_keyframe_opts* opts, hnet_keyframe_track* out /* [n] */);
+/* drops the session's keyframe and origin chain: its next track is HNET_KF_FIRST.  hnet_sessions_reset does the same when keyframes are enabled.
+ * Stream ordered, no synchronisation.  HNET_ERR_INVALID_ARG before enable or for an id out of range. */
+int  hnet_sessions_keyframe_reset(hnet_sessions* s, int id);
+/* operator level (tests): the session's keyframe, 224 x 320 bytes; HNET_ERR_NOT_READY without one.  One download, one synchronisation. */
+int  hnet_sessions_get_keyframe(hnet_sessions* s, int id, uint8_t* out);
+double hnet_sessions_last_keyframe_device_ms(hnet_sessions* s);     /* 0 before the first track */
+
 int hnet_synchronize(hnet_ctx* ctx, void* stream);
 int hnet_last_timing(const hnet_ctx* ctx, hnet_timing* out);
 
