@@ -51,6 +51,8 @@ SYMBOLS = [
     "hnet_photo_refine_default_opts", "hnet_filters_set_photo_refine", "hnet_filters_last_refine", "hnet_filters_refine_stats", "hnet_filters_reset_refine_stats",
     "hnet_keyframe_default_opts", "hnet_sessions_enable_keyframes", "hnet_sessions_keyframe_track", "hnet_sessions_keyframe_reset", "hnet_sessions_get_keyframe",
     "hnet_sessions_last_keyframe_device_ms",
+    "hnet_keyframe_revisit_default_opts", "hnet_sessions_enable_keyframe_map", "hnet_sessions_keyframe_revisit", "hnet_sessions_keyframe_map_info",
+    "hnet_sessions_get_map_keyframe",
 ]
 # hnet_filters_advance's status per listed session (include/hnet.h HNET_ADV_*)
 ADV_STEPPED, ADV_WAIT_IMU, ADV_WAIT_INIT, ADV_INITIALIZED, ADV_PROPAGATED, ADV_NO_FRAME = range(6)
@@ -244,6 +246,46 @@ def keyframe_opts(**kw):
     return o
 
 
+# the keyframe map (hnet_sessions_enable_keyframe_map): a session's entries and map state (hnet_sessions_keyframe_map_info), and one record per revisited
+# session (hnet_sessions_keyframe_revisit); flags RV_* (include/hnet.h HNET_RV_*)
+KEYFRAME_MAP_ENTRY_DTYPE = _np.dtype([("valid", "<i4"), ("links", "<i4"), ("serial", "<i4"), ("pad", "<i4"), ("h_origin_key", "<f8", (3, 3))])
+KEYFRAME_MAP_STATE_DTYPE = _np.dtype([("cur_slot", "<i4"), ("cur_links", "<i4"), ("cursor", "<i4"), ("serial", "<i4")])
+KEYFRAME_REVISIT_DTYPE = _np.dtype([("rec", PHOTO_ROBUST_DTYPE), ("start_px", "<f4", 8), ("key_px", "<f4", 8), ("h_origin_before", "<f8", (3, 3)),
+                                    ("h_origin_curr", "<f8", (3, 3)), ("closure_px", "<f8", 8), ("overlap", "<f8"), ("slot", "<i4"), ("links", "<i4"),
+                                    ("grid", "<i4"), ("flags", "<i4"), ("pad", "<i4", 2)])
+assert KEYFRAME_MAP_ENTRY_DTYPE.itemsize == 88 and KEYFRAME_MAP_STATE_DTYPE.itemsize == 16 and KEYFRAME_REVISIT_DTYPE.itemsize == 1560 + 304
+RV_NO_CANDIDATE, RV_ATTACHED, RV_STOPPED, RV_MSE_ABOVE_MAX, RV_NON_FINITE, RV_LOW_OVERLAP, RV_CLOSURE_ABOVE_MAX, RV_CHAIN = 1, 2, 4, 8, 16, 32, 64, 128
+RV_REJECTED = 4 | 8 | 16 | 32 | 64 | 128
+KEYFRAME_MAP_MIN_CAPACITY, KEYFRAME_MAP_MAX_CAPACITY = 2, 8
+
+
+class KeyframeRevisitOpts(C.Structure):
+    """hnet_keyframe_revisit_opts: the alignment's options and levels, the fewest grid points (of 64) of a stored keyframe that must lie inside the current
+    frame, the smallest overlap (fraction of the frame) of an accepted alignment, its largest mse and the largest distance (px) of its offsets from the
+    predicted start (0: no limit, both)"""
+    _fields_ = [("align", PhotoRobustOpts), ("levels", C.c_int32), ("min_grid", C.c_int32), ("min_overlap", C.c_double), ("max_mse", C.c_double),
+                ("max_closure_px", C.c_double)]
+
+
+assert C.sizeof(KeyframeRevisitOpts) == 56 + 32
+
+
+def keyframe_revisit_opts(**kw):
+    """the defaults of hnet_keyframe_revisit_default_opts with the given fields replaced (the fields of `align` and its `base` by their own names)"""
+    o = KeyframeRevisitOpts()
+    lib().hnet_keyframe_revisit_default_opts(C.byref(o))
+    for k, v in kw.items():
+        if k in ("max_iterations", "min_valid", "lambda0", "eps_px"):
+            setattr(o.align.base, k, v)
+        elif k in ("brightness", "huber_k", "gain0", "bias0"):
+            setattr(o.align, k, v)
+        elif k in ("levels", "min_grid", "min_overlap", "max_mse", "max_closure_px"):
+            setattr(o, k, v)
+        else:
+            raise TypeError(f"hnet_keyframe_revisit_opts has no field {k!r}")
+    return o
+
+
 def photo_robust_marginal(rec):
     """hnet_photo_robust_marginal of one record -> (info8 [8, 8], grad8 [8]); ValueError when the brightness block has no Cholesky factor"""
     r = _np.ascontiguousarray(rec, PHOTO_ROBUST_DTYPE).reshape(1)
@@ -428,6 +470,12 @@ def lib():
     L.hnet_sessions_get_keyframe.argtypes = [vp, C.c_int, vp]
     L.hnet_sessions_last_keyframe_device_ms.argtypes = [vp]
     L.hnet_sessions_last_keyframe_device_ms.restype = C.c_double
+    L.hnet_keyframe_revisit_default_opts.argtypes = [C.POINTER(KeyframeRevisitOpts)]
+    L.hnet_keyframe_revisit_default_opts.restype = None
+    L.hnet_sessions_enable_keyframe_map.argtypes = [vp, C.c_int]
+    L.hnet_sessions_keyframe_revisit.argtypes = [vp, C.c_int, vp, vp, vp]
+    L.hnet_sessions_keyframe_map_info.argtypes = [vp, C.c_int, vp, vp]
+    L.hnet_sessions_get_map_keyframe.argtypes = [vp, C.c_int, C.c_int, vp]
     L.hnet_last_photo_align_device_ms.restype = C.c_double
     L.hnet_photo_refine_default_opts.argtypes = [C.POINTER(PhotoRefineOpts)]
     L.hnet_photo_refine_default_opts.restype = None

@@ -1,8 +1,12 @@
 // capi_keyframe.hip — hnet_keyframe_* and hnet_sessions_*keyframe* of include/hnet.h (keyframe_dev.h, csrc/kernels_keyframe.hip): per session a
 // frame held longer than one tick, and one call that aligns each listed session's current frame against it from a composed start and applies the rule of
 // include/hnet_keyframe.h on the device.  Additive: a sessions object that never enables keyframes has s->kf == nullptr and allocates and launches nothing here.
+// On top of it the keyframe MAP (keyframe_map_dev.h, csrc/kernels_keyframe_map.hip): every keyframe a track takes is kept in one of M slots
+// per session, and hnet_sessions_keyframe_revisit aligns the current frame against the stored keyframe with the fewest chain links that is still in view
+// and re-attaches the session to it (include/hnet_keyframe_map.h).  Additive again: a store whose map was never enabled has kf->map == nullptr and a track
+// allocates, launches and returns what it did.
 #include "sessions_internal.h"
-#include "keyframe_dev.h"
+#include "keyframe_map_dev.h"
 
 using namespace hnet;
 using namespace capi;
@@ -18,9 +22,32 @@ static_assert((int)HNET_KF_FIRST == hnet_keyframe::FIRST && (int)HNET_KF_REKEYED
               (int)HNET_KF_NO_START == hnet_keyframe::NO_START && (int)HNET_KF_STOPPED == hnet_keyframe::STOPPED && (int)HNET_KF_MSE_ABOVE_MAX == hnet_keyframe::MSE_ABOVE_MAX &&
               (int)HNET_KF_NON_FINITE == hnet_keyframe::NON_FINITE && (int)HNET_KF_ORIGIN_RESTARTED == hnet_keyframe::ORIGIN_RESTARTED &&
               (int)HNET_KF_LOST == hnet_keyframe::LOST, "HNET_KF_* are the header's flags");
+static_assert(sizeof(hnet_keyframe_revisit) == sizeof(MapRevisit) && offsetof(hnet_keyframe_revisit, start_px) == offsetof(MapRevisit, start_px) &&
+              offsetof(hnet_keyframe_revisit, h_origin_before) == offsetof(MapRevisit, h_origin_before) &&
+              offsetof(hnet_keyframe_revisit, closure_px) == offsetof(MapRevisit, closure_px) && offsetof(hnet_keyframe_revisit, overlap) == offsetof(MapRevisit, overlap) &&
+              offsetof(hnet_keyframe_revisit, slot) == offsetof(MapRevisit, slot) && offsetof(hnet_keyframe_revisit, flags) == offsetof(MapRevisit, flags) &&
+              sizeof(hnet_keyframe_revisit_opts) == sizeof(MapOpts) && offsetof(hnet_keyframe_revisit_opts, min_grid) == offsetof(MapOpts, min_grid) &&
+              offsetof(hnet_keyframe_revisit_opts, min_overlap) == offsetof(MapOpts, min_overlap) &&
+              offsetof(hnet_keyframe_revisit_opts, max_closure_px) == offsetof(MapOpts, max_closure_px) && sizeof(hnet_keyframe_map_entry) == sizeof(MapEntry) &&
+              offsetof(hnet_keyframe_map_entry, h_origin_key) == offsetof(MapEntry, h_origin_key) && sizeof(hnet_keyframe_map_state) == sizeof(MapState),
+              "hnet_keyframe_revisit / _opts / _map_entry / _map_state are the layouts of include/hnet_keyframe_map.h");
+static_assert((int)HNET_RV_NO_CANDIDATE == hnet_keyframe_map::RV_NO_CANDIDATE && (int)HNET_RV_ATTACHED == hnet_keyframe_map::RV_ATTACHED &&
+              (int)HNET_RV_STOPPED == hnet_keyframe_map::RV_STOPPED && (int)HNET_RV_MSE_ABOVE_MAX == hnet_keyframe_map::RV_MSE_ABOVE_MAX &&
+              (int)HNET_RV_NON_FINITE == hnet_keyframe_map::RV_NON_FINITE && (int)HNET_RV_LOW_OVERLAP == hnet_keyframe_map::RV_LOW_OVERLAP &&
+              (int)HNET_RV_CLOSURE_ABOVE_MAX == hnet_keyframe_map::RV_CLOSURE_ABOVE_MAX && (int)HNET_RV_CHAIN == hnet_keyframe_map::RV_CHAIN &&
+              (int)HNET_RV_REJECTED == hnet_keyframe_map::RV_REJECTED, "HNET_RV_* are the header's flags");
+
+// the map of a store (hnet_sessions_enable_keyframe_map): sized at its enable, for N sessions, M slots each and max_batch B
+struct KeyMap {
+    MapStore dev = {nullptr, nullptr, nullptr, 0, 0};  // device: images [N][M][NPIX], entries [N][M], states [N]; all zeroed at enable
+    uint8_t* scratch = nullptr;                // device: the sections of MapScratch
+    uint8_t *pin_in = nullptr, *pin_out = nullptr;     // pinned: a revisit's table and its records [B]
+    hipEvent_t ev[2] = {nullptr, nullptr};     // around the launch sequence of the last revisit
+};
 
 // the store: everything is sized at enable, for the sessions' count N and the context's max_batch B
 struct hnet_keyframes {
+    KeyMap* map = nullptr;                     // the keyframe map or null: never enabled
     uint8_t* key = nullptr;                    // device [N][NPIX], zeroed at enable
     KeyState* state = nullptr;                 // device [N], zeroed at enable (has_key = 0)
     uint8_t* scratch = nullptr;                // device: the sections of KeyScratch
@@ -61,8 +88,39 @@ KeyTable table_view(const uint8_t* b, int n) {
     return KeyTable{step, ids, ids + n, ids + 2 * (size_t)n};
 }
 
+// the map's own scratch for max_batch B: a revisit's table {ids | curr ring slot}, and per slot the candidate, the store slot of a track's new keyframe,
+// the attach flag and the revisit's record.  The alignment's scratch and the start offsets are the store's (KeyScratch).
+size_t map_table_bytes(int n) { return (size_t)n * 2 * sizeof(int32_t); }
+struct MapScratch {
+    int32_t *tab, *cand, *store, *attach; MapRevisit* out; size_t bytes;
+    MapScratch(uint8_t* b, int B) {
+        size_t o = 0;
+        auto take = [&](size_t n) { uint8_t* p = b + o; o += (n + 255) & ~(size_t)255; return p; };
+        tab = reinterpret_cast<int32_t*>(take(map_table_bytes(B)));
+        cand = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
+        store = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
+        attach = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
+        out = reinterpret_cast<MapRevisit*>(take((size_t)B * sizeof(MapRevisit)));
+        bytes = o;
+    }
+};
+
+void map_free(KeyMap* m) {
+    if (!m) return;
+    if (m->dev.img) (void)hipFree(m->dev.img);
+    if (m->dev.entry) (void)hipFree(m->dev.entry);
+    if (m->dev.state) (void)hipFree(m->dev.state);
+    if (m->scratch) (void)hipFree(m->scratch);
+    if (m->pin_in) (void)hipHostFree(m->pin_in);
+    if (m->pin_out) (void)hipHostFree(m->pin_out);
+    for (hipEvent_t e : m->ev)
+        if (e) (void)hipEventDestroy(e);
+    delete m;
+}
+
 void keyframes_free(hnet_keyframes* k) {
     if (!k) return;
+    map_free(k->map);
     if (k->key) (void)hipFree(k->key);
     if (k->state) (void)hipFree(k->state);
     if (k->scratch) (void)hipFree(k->scratch);
@@ -90,6 +148,10 @@ int keyframes_drop(hnet_sessions* s, int id) {
     hnet_ctx* c = s->ctx;
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
     HIPCHK(c, hipMemsetAsync(k->state + id, 0, sizeof(KeyState), c->stream));
+    if (const KeyMap* m = k->map) {            // the session's map goes with its origin: no entry stays valid (the images need no clearing)
+        HIPCHK(c, hipMemsetAsync(m->dev.entry + (size_t)id * m->dev.capacity, 0, (size_t)m->dev.capacity * sizeof(MapEntry), c->stream));
+        HIPCHK(c, hipMemsetAsync(m->dev.state + id, 0, sizeof(MapState), c->stream));
+    }
     k->has_key[id] = 0;
     k->count_at_track[id] = -1;
     return HNET_OK;
@@ -175,6 +237,11 @@ int hnet_sessions_keyframe_track(hnet_sessions* s, int n, const int32_t* ids, co
     HIPCHK(c, launch_photo_align_robust(prev, curr, n, w.x0, o.align, o.levels, c->pyr_scratch, c->pyr_scratch + pyr, w.start, w.part, w.work, w.rec, st));
     HIPCHK(c, launch_keyframe_decide(tab, n, N, w.rec, w.x0, o, k->state, w.out, w.copy, st));
     HIPCHK(c, launch_keyframe_commit(tab, n, N, w.copy, curr, k->key, st));
+    if (const KeyMap* m = k->map) {            // with a map: the bookkeeping of the new keyframes, and their images into their slots
+        const MapScratch mw(m->scratch, B);
+        HIPCHK(c, launch_keyframe_map_note(tab.ids, n, w.out, w.copy, k->state, m->dev, mw.store, st));
+        HIPCHK(c, launch_keyframe_map_store(tab.ids, n, mw.store, curr, m->dev, st));
+    }
     HIPCHK(c, hipEventRecord(k->ev[1], st));
     HIPCHK(c, hipMemcpyAsync(k->pin_out, w.out, (size_t)n * sizeof(KeyTrack), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
@@ -205,6 +272,132 @@ int hnet_sessions_get_keyframe(hnet_sessions* s, int id, uint8_t* out) {
     if (!s->kf->has_key[id]) return fail(c, HNET_ERR_NOT_READY, std::string(who) + ": the session holds no keyframe");
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
     HIPCHK(c, hipMemcpyAsync(out, s->kf->key + (size_t)id * NPIX, NPIX, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return HNET_OK;
+}
+
+void hnet_keyframe_revisit_default_opts(hnet_keyframe_revisit_opts* o) {
+    if (!o) return;
+    MapOpts d;
+    hnet_keyframe_map::default_opts(d);
+    memcpy(o, &d, sizeof d);
+}
+
+int hnet_sessions_enable_keyframe_map(hnet_sessions* s, int capacity) {
+    const char* who = "hnet_sessions_enable_keyframe_map";
+    if (!s) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = s->ctx;
+    hnet_keyframes* k = s->kf;
+    if (!k) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": keyframes are not enabled (hnet_sessions_enable_keyframes)");
+    if (k->map) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": the keyframe map is already enabled");
+    if (capacity < hnet_keyframe_map::MIN_CAPACITY || capacity > hnet_keyframe_map::MAX_CAPACITY)
+        return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": 2 <= capacity <= 8");
+    for (int id = 0; id < s->n; id++)
+        if (k->has_key[id]) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": a session already holds a keyframe, which would not be in the map");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    const int B = c->cfg.max_batch, N = s->n, M = capacity;
+    KeyMap* m = new KeyMap();
+    m->dev.n_sessions = N;
+    m->dev.capacity = M;
+    const size_t img = (size_t)N * M * NPIX, ent = (size_t)N * M * sizeof(MapEntry), sta = (size_t)N * sizeof(MapState);
+    hipError_t e = hipMalloc((void**)&m->dev.img, img);
+    if (e == hipSuccess) e = hipMalloc((void**)&m->dev.entry, ent);
+    if (e == hipSuccess) e = hipMalloc((void**)&m->dev.state, sta);
+    if (e == hipSuccess) e = hipMalloc((void**)&m->scratch, MapScratch(nullptr, B).bytes);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&m->pin_in, map_table_bytes(B), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&m->pin_out, (size_t)B * sizeof(MapRevisit), hipHostMallocDefault);
+    for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipEventCreate(&m->ev[i]);
+    if (e == hipSuccess) e = hipMemsetAsync(m->dev.img, 0, img, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(m->dev.entry, 0, ent, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(m->dev.state, 0, sta, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        map_free(m);
+        return fail(c, HNET_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    }
+    k->map = m;
+    return HNET_OK;
+}
+
+// ONE upload {ids | curr slot}, the launch sequence inside the map's own events, ONE download of the records [n], one synchronisation
+int hnet_sessions_keyframe_revisit(hnet_sessions* s, int n, const int32_t* ids, const hnet_keyframe_revisit_opts* opts, hnet_keyframe_revisit* out) {
+    const char* who = "hnet_sessions_keyframe_revisit";
+    if (!s) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = s->ctx;
+    hnet_keyframes* k = s->kf;
+    if (!k) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": keyframes are not enabled (hnet_sessions_enable_keyframes)");
+    KeyMap* m = k->map;
+    if (!m) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": the keyframe map is not enabled (hnet_sessions_enable_keyframe_map)");
+    if (!out || !opts) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": opts / out");
+    int rc = photo_robust_check_opts(c, &opts->align, who);
+    if (rc != HNET_OK) return rc;
+    MapOpts o;
+    memcpy(&o, opts, sizeof o);
+    if (!hnet_keyframe_map::opts_valid(o))
+        return fail(c, HNET_ERR_INVALID_ARG,
+                    std::string(who) + ": opts: 1 <= levels <= 4, 1 <= min_grid <= 64, 0 <= min_overlap <= 1, max_mse and max_closure_px >= 0 and finite");
+    if ((rc = sessions_check_ids(s, n, ids)) != HNET_OK) return rc;
+    for (int i = 0; i < n; i++) {
+        const int id = ids[i];
+        if (s->st[id].count < 1) return fail(c, HNET_ERR_NOT_READY, std::string(who) + ": a listed session has no image");
+        if (!k->has_key[id]) return fail(c, HNET_ERR_NOT_READY, std::string(who) + ": a listed session holds no keyframe");
+        if (s->st[id].count != k->count_at_track[id])
+            return fail(c, HNET_ERR_NOT_READY, std::string(who) + ": a listed session's latest image is not the one its last track saw (track it first)");
+    }
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    const int B = c->cfg.max_batch, N = s->n;
+    const KeyScratch w(k->scratch, B);
+    const MapScratch mw(m->scratch, B);
+    int32_t* h_ids = reinterpret_cast<int32_t*>(m->pin_in);
+    for (int i = 0; i < n; i++) {
+        h_ids[i] = ids[i];
+        h_ids[n + i] = 2 * ids[i] + s->st[ids[i]].curr;
+    }
+    const int32_t *d_ids = mw.tab, *d_slot = mw.tab + n;
+    const size_t pyr = (size_t)B * PYR_BYTES;
+    uint8_t *prev = (uint8_t*)c->stage_prev, *curr = (uint8_t*)c->stage_curr;
+    hipStream_t st = c->stream;
+    HIPCHK(c, hipMemcpyAsync(mw.tab, m->pin_in, map_table_bytes(n), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipEventRecord(m->ev[0], st));
+    HIPCHK(c, launch_keyframe_map_select(d_ids, n, k->state, m->dev, o.min_grid, w.x0, mw.cand, mw.out, st));
+    HIPCHK(c, launch_keyframe_map_gather(d_ids, d_slot, n, mw.cand, m->dev, s->ring, 2 * N, prev, curr, st));
+    HIPCHK(c, launch_photo_align_robust(prev, curr, n, w.x0, o.align, o.levels, c->pyr_scratch, c->pyr_scratch + pyr, w.start, w.part, w.work, w.rec, st));
+    HIPCHK(c, launch_keyframe_map_decide(d_ids, n, w.rec, w.x0, mw.cand, o, k->state, m->dev, mw.out, mw.attach, st));
+    HIPCHK(c, launch_keyframe_map_attach(d_ids, n, mw.cand, mw.attach, m->dev, k->key, st));
+    HIPCHK(c, hipEventRecord(m->ev[1], st));
+    HIPCHK(c, hipMemcpyAsync(m->pin_out, mw.out, (size_t)n * sizeof(MapRevisit), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    float ms = 0;
+    HIPCHK(c, hipEventElapsedTime(&ms, m->ev[0], m->ev[1]));
+    k->ms = ms;
+    memcpy(out, m->pin_out, (size_t)n * sizeof(MapRevisit));
+    return HNET_OK;
+}
+
+int hnet_sessions_keyframe_map_info(hnet_sessions* s, int id, hnet_keyframe_map_entry* entries, hnet_keyframe_map_state* map_state) {
+    const char* who = "hnet_sessions_keyframe_map_info";
+    if (!s) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = s->ctx;
+    if (!s->kf || !s->kf->map) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": the keyframe map is not enabled (hnet_sessions_enable_keyframe_map)");
+    if (!entries || !map_state || id < 0 || id >= s->n) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": id / entries / map_state");
+    const KeyMap* m = s->kf->map;
+    const int M = m->dev.capacity;
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    HIPCHK(c, hipMemcpyAsync(entries, m->dev.entry + (size_t)id * M, (size_t)M * sizeof(MapEntry), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(map_state, m->dev.state + id, sizeof(MapState), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return HNET_OK;
+}
+
+int hnet_sessions_get_map_keyframe(hnet_sessions* s, int id, int slot, uint8_t* out) {
+    const char* who = "hnet_sessions_get_map_keyframe";
+    if (!s) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = s->ctx;
+    if (!s->kf || !s->kf->map) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": the keyframe map is not enabled (hnet_sessions_enable_keyframe_map)");
+    const KeyMap* m = s->kf->map;
+    if (!out || id < 0 || id >= s->n || slot < 0 || slot >= m->dev.capacity) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": id / slot / out");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    HIPCHK(c, hipMemcpyAsync(out, m->dev.img + ((size_t)id * m->dev.capacity + slot) * NPIX, NPIX, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return HNET_OK;
 }

@@ -671,6 +671,35 @@ class HnetSessions:
     def last_keyframe_device_ms(self):
         return float(self._L.hnet_sessions_last_keyframe_device_ms(self._s))
 
+    def enable_keyframe_map(self, capacity):
+        """hnet_sessions_enable_keyframe_map: every keyframe a track takes is kept in one of `capacity` (2 .. 8) slots per session; once, after
+        enable_keyframes and before any session holds a keyframe"""
+        self._check(self._L.hnet_sessions_enable_keyframe_map(self._s, int(capacity)))
+        self._map_capacity = int(capacity)
+
+    def keyframe_revisit(self, ids, **opts):
+        """hnet_sessions_keyframe_revisit: the listed sessions' current frames against the stored keyframe with the fewest chain links that is still in
+        view; a session whose alignment passes is re-attached to it -> [n] of _capi.KEYFRAME_REVISIT_DTYPE; opts as _capi.keyframe_revisit_opts"""
+        ids, n = self._ids(ids)
+        o = _capi.keyframe_revisit_opts(**opts)
+        out = np.zeros(n, _capi.KEYFRAME_REVISIT_DTYPE)
+        self._check(self._L.hnet_sessions_keyframe_revisit(self._s, n, ids.ctypes.data, C.addressof(o), out.ctypes.data))
+        return out
+
+    def keyframe_map_info(self, id):
+        """-> (entries [capacity] of _capi.KEYFRAME_MAP_ENTRY_DTYPE, map state [1] of _capi.KEYFRAME_MAP_STATE_DTYPE) of the session
+        (hnet_sessions_keyframe_map_info)"""
+        cap = getattr(self, "_map_capacity", _capi.KEYFRAME_MAP_MAX_CAPACITY)
+        entries, state = np.zeros(cap, _capi.KEYFRAME_MAP_ENTRY_DTYPE), np.zeros(1, _capi.KEYFRAME_MAP_STATE_DTYPE)
+        self._check(self._L.hnet_sessions_keyframe_map_info(self._s, int(id), entries.ctypes.data, state.ctypes.data))
+        return entries, state
+
+    def map_keyframe(self, id, slot):
+        """the image in slot `slot` of the session's map as the store holds it (hnet_sessions_get_map_keyframe)"""
+        out = np.zeros((IMG_H, IMG_W), np.uint8)
+        self._check(self._L.hnet_sessions_get_map_keyframe(self._s, int(id), int(slot), out.ctypes.data))
+        return out
+
     def image_count(self, id):
         return int(self._L.hnet_sessions_image_count(self._s, int(id)))
 

@@ -828,7 +828,68 @@ int  hnet_sessions_keyframe_track(hnet_sessions* s, int n, const int32_t* ids, c
 int  hnet_sessions_keyframe_reset(hnet_sessions* s, int id);
 /* operator level (tests): the session's keyframe, 224 x 320 bytes; HNET_ERR_NOT_READY without one.  One download, one synchronisation. */
 int  hnet_sessions_get_keyframe(hnet_sessions* s, int id, uint8_t* out);
-double hnet_sessions_last_keyframe_device_ms(hnet_sessions* s);     /* 0 before the first track */
+double hnet_sessions_last_keyframe_device_ms(hnet_sessions* s);     /* 0 before the first track; with a map: of the last track or revisit */
+
+/* ---- sessions, a MAP of keyframes and closing loops against it, on the device (csrc/kernels_keyframe_map.hip; the shared code is
+ * include/hnet_keyframe_map.h).  Opt-in on top of the keyframes: a sessions object that never calls hnet_sessions_enable_keyframe_map allocates,
+ * launches and returns exactly what it did before, and with a map the track's records stay byte for byte what they are without one.
+ * A track removes the drift of a camera that stays on one keyframe, not the drift of the keyframe chain: every re-key extends h_origin_key by one
+ * measured link, a lost frame by dead reckoning, and the old keyframe is overwritten.  With a map every keyframe a track takes is also kept in one of
+ * `capacity` (2 .. 8) slots per session, as {valid, links, serial, h_origin_key}: links counts the chain links between the origin and that keyframe,
+ * serial numbers the session's stored keyframes from 1.  Slot 0 is never evicted (the oldest keyframe the chain knows), slots 1 .. capacity-1 are a
+ * ring.  HNET_KF_ORIGIN_RESTARTED and HNET_KF_FIRST invalidate the session's entries; hnet_sessions_keyframe_reset and hnet_sessions_reset clear them.
+ * One revisit, per listed session (its latest image must be the one its last track saw: the state's key_px then describes the current frame):
+ *   h_origin_before = H(key_px) . h_origin_key, the chain's value for the current frame.  For every valid entry other than the current keyframe's with
+ *   FEWER links than it, G = h_origin_before . inverse(entry.h_origin_key) predicts where the stored keyframe lies in the current frame; of an inset
+ *   8 x 8 grid of its pixels (20 + 40 i, 14 + 28 j) `grid` lie inside the frame.  The candidate is the entry with grid >= min_grid and the fewest links
+ *   (then the larger grid, then the lower slot); start_px = the corners of G minus p4.  None: HNET_RV_NO_CANDIDATE, rec zero, start_px quiet NaNs.
+ *   The alignment candidate -> curr runs from start_px; `rec` is its level-0 record, byte for byte hnet_op_photo_align_robust(stored keyframe, curr,
+ *   start_px) with the same options.  REJECTED, one reason bit, in this order: HNET_RV_STOPPED (rec stopped SINGULAR, DEGENERATE or FEW_PIXELS);
+ *   HNET_RV_MSE_ABOVE_MAX (max_mse > 0 and not mse <= max_mse); HNET_RV_NON_FINITE (an offset of rec); HNET_RV_LOW_OVERLAP (n_valid / 71 680 <
+ *   min_overlap); HNET_RV_CLOSURE_ABOVE_MAX (max_closure_px > 0 and the worst |offset - start| exceeds it: a false match inside the basin);
+ *   HNET_RV_CHAIN (H(offsets) . entry.h_origin_key is degenerate).  Else HNET_RV_ATTACHED: the stored keyframe becomes the session's keyframe again,
+ *   key_px = rec's offsets, h_origin_key = the entry's, age = 0, keyframes unchanged; the next track measures against it, and the next re-key has the
+ *   entry's links + 1.  A rejected or candidate-less revisit changes nothing.
+ * Read-only for everything else, like a track.  Errors, nothing changed and nothing written: everything hnet_sessions_keyframe_track refuses (with
+ * min_grid outside 1 .. 64, min_overlap outside 0 .. 1, a negative or non-finite max_mse or max_closure_px for its own options); HNET_ERR_INVALID_ARG
+ * before hnet_sessions_enable_keyframe_map; HNET_ERR_NOT_READY for a listed session without a keyframe or with an image its last track did not see.
+ * hnet_sessions_enable_keyframe_map: once, after hnet_sessions_enable_keyframes and before any session holds a keyframe (HNET_ERR_INVALID_ARG
+ * otherwise, and for a capacity outside 2 .. 8); allocates [n_sessions][capacity][71 680] bytes (zeroed), the entries, the map states and per-slot
+ * scratch for max_batch.  A revisit is ONE upload {ids | curr slot}, 4 small launches around the alignment's sequence (select, gather, decide, attach),
+ * ONE download of the records [n] and one synchronisation; a track with a map has 2 small launches more (note, store). */
+typedef struct hnet_keyframe_revisit_opts {
+    hnet_photo_robust_opts align;
+    int32_t levels;            /* 1 .. 4 */
+    int32_t min_grid;          /* 1 .. 64 */
+    double  min_overlap;       /* 0 .. 1 */
+    double  max_mse;           /* >= 0; 0 = no limit */
+    double  max_closure_px;    /* >= 0; 0 = no limit */
+} hnet_keyframe_revisit_opts;
+enum { HNET_RV_NO_CANDIDATE = 1, HNET_RV_ATTACHED = 2,
+       HNET_RV_STOPPED = 4, HNET_RV_MSE_ABOVE_MAX = 8, HNET_RV_NON_FINITE = 16, HNET_RV_LOW_OVERLAP = 32, HNET_RV_CLOSURE_ABOVE_MAX = 64,
+       HNET_RV_CHAIN = 128,                                                                              /* the REJECTED reasons, in the order tested */
+       HNET_RV_REJECTED = 4 | 8 | 16 | 32 | 64 | 128 };
+typedef struct hnet_keyframe_map_entry { int32_t valid, links, serial, pad; double h_origin_key[9]; } hnet_keyframe_map_entry;
+typedef struct hnet_keyframe_map_state { int32_t cur_slot /* the held keyframe's slot, -1: not in the map */, cur_links, cursor, serial; } hnet_keyframe_map_state;
+typedef struct hnet_keyframe_revisit {
+    hnet_photo_robust rec;       /* level 0, stored keyframe -> curr; zeros without a candidate */
+    float   start_px[8];         /* what the alignment started from (quiet NaNs: no candidate) */
+    float   key_px[8];           /* the session's key_px after the call: rec's offsets when attached, else unchanged */
+    double  h_origin_before[9];  /* origin -> curr by the chain as it was */
+    double  h_origin_curr[9];    /* origin -> curr after the call: through the candidate when attached, else h_origin_before */
+    double  closure_px[8];       /* corners of h_origin_curr minus corners of h_origin_before: the drift the attach removed; zeros unless attached */
+    double  overlap;             /* rec.px.n_valid / 71 680; 0 without a candidate */
+    int32_t slot, links, grid;   /* the candidate's; -1, 0, 0 without one */
+    int32_t flags;               /* HNET_RV_* */
+    int32_t pad[2];              /* written zero: records compare byte for byte */
+} hnet_keyframe_revisit;
+void hnet_keyframe_revisit_default_opts(hnet_keyframe_revisit_opts* o);  /* robust defaults, levels 3, min_grid 32, min_overlap 0.5, max_mse 0, max_closure_px 0 */
+int  hnet_sessions_enable_keyframe_map(hnet_sessions* s, int capacity);
+int  hnet_sessions_keyframe_revisit(hnet_sessions* s, int n, const int32_t* ids, const hnet_keyframe_revisit_opts* opts, hnet_keyframe_revisit* out /* [n] */);
+/* operator level (tests): the session's entries [capacity] and map state; a stored image, 224 x 320 bytes, whatever the entry's validity (zeros when the
+ * slot was never written).  One download, one synchronisation each.  HNET_ERR_INVALID_ARG before hnet_sessions_enable_keyframe_map. */
+int  hnet_sessions_keyframe_map_info(hnet_sessions* s, int id, hnet_keyframe_map_entry* entries /* [capacity] */, hnet_keyframe_map_state* map_state);
+int  hnet_sessions_get_map_keyframe(hnet_sessions* s, int id, int slot, uint8_t* out);
 
 int hnet_synchronize(hnet_ctx* ctx, void* stream);
 int hnet_last_timing(const hnet_ctx* ctx, hnet_timing* out);
