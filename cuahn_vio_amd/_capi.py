@@ -49,6 +49,8 @@ SYMBOLS = [
     "hnet_op_photo_align_pyramid", "hnet_sessions_photo_align_pyramid", "hnet_op_photo_pyramid",
     "hnet_photo_robust_default_opts", "hnet_op_photo_align_robust", "hnet_sessions_photo_align_robust", "hnet_photo_robust_marginal",
     "hnet_photo_refine_default_opts", "hnet_filters_set_photo_refine", "hnet_filters_last_refine", "hnet_filters_refine_stats", "hnet_filters_reset_refine_stats",
+    "hnet_photo_search_default_opts", "hnet_op_photo_search", "hnet_sessions_photo_search",
+    "hnet_keyframe_relocalise_default_opts", "hnet_sessions_keyframe_relocalise",
     "hnet_keyframe_default_opts", "hnet_sessions_enable_keyframes", "hnet_sessions_keyframe_track", "hnet_sessions_keyframe_reset", "hnet_sessions_get_keyframe",
     "hnet_sessions_last_keyframe_device_ms",
     "hnet_keyframe_revisit_default_opts", "hnet_sessions_enable_keyframe_map", "hnet_sessions_keyframe_revisit", "hnet_sessions_keyframe_map_info",
@@ -286,6 +288,78 @@ def keyframe_revisit_opts(**kw):
     return o
 
 
+# the coarse search over integer translations (hnet_op_photo_search): one record per pair; flags PS_* (include/hnet.h HNET_PS_*).  A score table is
+# [PS_SHIFTS_Y, PS_SHIFTS_X] doubles, index [dy + PS_MAX_RY, dx + PS_MAX_RX]
+PHOTO_SEARCH_DTYPE = _np.dtype([("start_px", "<f4", 8), ("dx", "<i4"), ("dy", "<i4"), ("dx2", "<i4"), ("dy2", "<i4"), ("n_overlap", "<i4"), ("flags", "<i4"),
+                                ("score", "<f8"), ("second", "<f8"), ("sa", "<i4"), ("sb", "<i4"), ("sab", "<i4"), ("saa", "<i4"), ("sbb", "<i4"), ("pad", "<i4")])
+assert PHOTO_SEARCH_DTYPE.itemsize == 96
+PS_FOUND, PS_NO_TEXTURE, PS_LOW_SCORE, PS_AMBIGUOUS = 1, 2, 4, 8
+PS_MAX_RX, PS_MAX_RY, PS_SHIFTS_X, PS_SHIFTS_Y = 30, 20, 61, 41
+PS_THUMB_W, PS_THUMB_H = 40, 28
+
+
+class PhotoSearchOpts(C.Structure):
+    """hnet_photo_search_opts: the radii of the search and the fewest pixels of an overlap (level-3 pixels), the lowest score of a FOUND peak and the
+    least margin over the best score elsewhere"""
+    _fields_ = [("radius_x", C.c_int32), ("radius_y", C.c_int32), ("min_overlap", C.c_int32), ("pad", C.c_int32), ("min_score", C.c_double),
+                ("min_margin", C.c_double)]
+
+
+assert C.sizeof(PhotoSearchOpts) == 32
+_SEARCH_FIELDS = ("radius_x", "radius_y", "min_overlap", "min_score", "min_margin")
+
+
+def photo_search_opts(**kw):
+    """the defaults of hnet_photo_search_default_opts with the given fields replaced"""
+    o = PhotoSearchOpts()
+    lib().hnet_photo_search_default_opts(C.byref(o))
+    for k, v in kw.items():
+        if k not in _SEARCH_FIELDS:
+            raise TypeError(f"hnet_photo_search_opts has no field {k!r}")
+        setattr(o, k, v)
+    return o
+
+
+# hnet_keyframe_relocalise: one record per listed session (hnet_sessions_keyframe_relocalise); rv.flags RL_* (include/hnet.h HNET_RL_*)
+KEYFRAME_RELOC_DTYPE = _np.dtype([("rv", KEYFRAME_REVISIT_DTYPE), ("search", PHOTO_SEARCH_DTYPE), ("target", "<i4"), ("n_searched", "<i4"), ("n_found", "<i4"),
+                                  ("pad", "<i4")])
+assert KEYFRAME_RELOC_DTYPE.itemsize == 1864 + 96 + 16
+RL_NO_CANDIDATE, RL_ATTACHED, RL_STOPPED, RL_MSE_ABOVE_MAX, RL_NON_FINITE, RL_LOW_OVERLAP, RL_CLOSURE_ABOVE_MAX, RL_CHAIN, RL_RETRACKED = 1, 2, 4, 8, 16, 32, 64, 128, 256
+RL_REJECTED = 4 | 8 | 16 | 32 | 64 | 128
+RL_TARGET_HELD, RL_TARGET_NONE = -1, -2
+
+
+class KeyframeRelocOpts(C.Structure):
+    """hnet_keyframe_relocalise_opts: the alignment's options and levels, the search's options, the smallest overlap (fraction of the frame) of an accepted
+    alignment, its largest mse and the largest distance (px) of its offsets from the searched start (0: no limit, both)"""
+    _fields_ = [("align", PhotoRobustOpts), ("levels", C.c_int32), ("pad", C.c_int32), ("search", PhotoSearchOpts), ("min_overlap", C.c_double),
+                ("max_mse", C.c_double), ("max_closure_px", C.c_double)]
+
+
+assert C.sizeof(KeyframeRelocOpts) == 56 + 64
+
+
+def keyframe_relocalise_opts(**kw):
+    """the defaults of hnet_keyframe_relocalise_default_opts with the given fields replaced (the fields of `align`, its `base` and `search` by their own
+    names; the search's min_overlap as search_min_overlap)"""
+    o = KeyframeRelocOpts()
+    lib().hnet_keyframe_relocalise_default_opts(C.byref(o))
+    for k, v in kw.items():
+        if k in ("max_iterations", "min_valid", "lambda0", "eps_px"):
+            setattr(o.align.base, k, v)
+        elif k in ("brightness", "huber_k", "gain0", "bias0"):
+            setattr(o.align, k, v)
+        elif k in ("levels", "min_overlap", "max_mse", "max_closure_px"):
+            setattr(o, k, v)
+        elif k == "search_min_overlap":
+            o.search.min_overlap = v
+        elif k in _SEARCH_FIELDS:
+            setattr(o.search, k, v)
+        else:
+            raise TypeError(f"hnet_keyframe_relocalise_opts has no field {k!r}")
+    return o
+
+
 def photo_robust_marginal(rec):
     """hnet_photo_robust_marginal of one record -> (info8 [8, 8], grad8 [8]); ValueError when the brightness block has no Cholesky factor"""
     r = _np.ascontiguousarray(rec, PHOTO_ROBUST_DTYPE).reshape(1)
@@ -476,6 +550,13 @@ def lib():
     L.hnet_sessions_keyframe_revisit.argtypes = [vp, C.c_int, vp, vp, vp]
     L.hnet_sessions_keyframe_map_info.argtypes = [vp, C.c_int, vp, vp]
     L.hnet_sessions_get_map_keyframe.argtypes = [vp, C.c_int, C.c_int, vp]
+    L.hnet_photo_search_default_opts.argtypes = [C.POINTER(PhotoSearchOpts)]
+    L.hnet_photo_search_default_opts.restype = None
+    L.hnet_op_photo_search.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp]
+    L.hnet_sessions_photo_search.argtypes = [vp, C.c_int, vp, vp, vp]
+    L.hnet_keyframe_relocalise_default_opts.argtypes = [C.POINTER(KeyframeRelocOpts)]
+    L.hnet_keyframe_relocalise_default_opts.restype = None
+    L.hnet_sessions_keyframe_relocalise.argtypes = [vp, C.c_int, vp, vp, vp]
     L.hnet_last_photo_align_device_ms.restype = C.c_double
     L.hnet_photo_refine_default_opts.argtypes = [C.POINTER(PhotoRefineOpts)]
     L.hnet_photo_refine_default_opts.restype = None

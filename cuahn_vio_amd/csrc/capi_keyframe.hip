@@ -5,8 +5,12 @@
 // per session, and hnet_sessions_keyframe_revisit aligns the current frame against the stored keyframe with the fewest chain links that is still in view
 // and re-attaches the session to it (include/hnet_keyframe_map.h).  Additive again: a store whose map was never enabled has kf->map == nullptr and a track
 // allocates, launches and returns what it did.
+// And the RELOCALISATION (photo_search_dev.h, csrc/kernels_photo_search.hip): hnet_sessions_keyframe_relocalise searches the current frame's
+// thumbnail against the held keyframe's and every stored one's, aligns against the best FOUND candidate from the searched start and re-tracks or
+// re-attaches the session (include/hnet_keyframe_reloc.h).  Its scratch is allocated by its first call: a store that never relocalises has
+// kf->reloc == nullptr.
 #include "sessions_internal.h"
-#include "keyframe_map_dev.h"
+#include "photo_search_dev.h"
 
 using namespace hnet;
 using namespace capi;
@@ -37,6 +41,26 @@ static_assert((int)HNET_RV_NO_CANDIDATE == hnet_keyframe_map::RV_NO_CANDIDATE &&
               (int)HNET_RV_CLOSURE_ABOVE_MAX == hnet_keyframe_map::RV_CLOSURE_ABOVE_MAX && (int)HNET_RV_CHAIN == hnet_keyframe_map::RV_CHAIN &&
               (int)HNET_RV_REJECTED == hnet_keyframe_map::RV_REJECTED, "HNET_RV_* are the header's flags");
 
+static_assert(sizeof(hnet_keyframe_relocalise) == sizeof(RelocRec) && offsetof(hnet_keyframe_relocalise, search) == offsetof(RelocRec, search) &&
+              offsetof(hnet_keyframe_relocalise, target) == offsetof(RelocRec, target) && offsetof(hnet_keyframe_relocalise, n_found) == offsetof(RelocRec, n_found) &&
+              sizeof(hnet_keyframe_relocalise_opts) == sizeof(RelocOpts) && offsetof(hnet_keyframe_relocalise_opts, levels) == offsetof(RelocOpts, levels) &&
+              offsetof(hnet_keyframe_relocalise_opts, search) == offsetof(RelocOpts, search) &&
+              offsetof(hnet_keyframe_relocalise_opts, min_overlap) == offsetof(RelocOpts, min_overlap) &&
+              offsetof(hnet_keyframe_relocalise_opts, max_closure_px) == offsetof(RelocOpts, max_closure_px),
+              "hnet_keyframe_relocalise / _opts are the layouts of include/hnet_keyframe_reloc.h");
+static_assert((int)HNET_RL_NO_CANDIDATE == hnet_keyframe_reloc::RL_NO_CANDIDATE && (int)HNET_RL_ATTACHED == hnet_keyframe_reloc::RL_ATTACHED &&
+              (int)HNET_RL_STOPPED == hnet_keyframe_reloc::RL_STOPPED && (int)HNET_RL_MSE_ABOVE_MAX == hnet_keyframe_reloc::RL_MSE_ABOVE_MAX &&
+              (int)HNET_RL_NON_FINITE == hnet_keyframe_reloc::RL_NON_FINITE && (int)HNET_RL_LOW_OVERLAP == hnet_keyframe_reloc::RL_LOW_OVERLAP &&
+              (int)HNET_RL_CLOSURE_ABOVE_MAX == hnet_keyframe_reloc::RL_CLOSURE_ABOVE_MAX && (int)HNET_RL_CHAIN == hnet_keyframe_reloc::RL_CHAIN &&
+              (int)HNET_RL_RETRACKED == hnet_keyframe_reloc::RL_RETRACKED && (int)HNET_RL_REJECTED == hnet_keyframe_reloc::RL_REJECTED,
+              "HNET_RL_* are the header's flags");
+
+// the scratch of the relocalisation (allocated by the first hnet_sessions_keyframe_relocalise), for max_batch B and the largest map
+struct KeyReloc {
+    uint8_t* scratch = nullptr;                // device: the sections of RelocScratch
+    uint8_t *pin_in = nullptr, *pin_out = nullptr;     // pinned: a call's table and its records [B]
+};
+
 // the map of a store (hnet_sessions_enable_keyframe_map): sized at its enable, for N sessions, M slots each and max_batch B
 struct KeyMap {
     MapStore dev = {nullptr, nullptr, nullptr, 0, 0};  // device: images [N][M][NPIX], entries [N][M], states [N]; all zeroed at enable
@@ -48,6 +72,7 @@ struct KeyMap {
 // the store: everything is sized at enable, for the sessions' count N and the context's max_batch B
 struct hnet_keyframes {
     KeyMap* map = nullptr;                     // the keyframe map or null: never enabled
+    KeyReloc* reloc = nullptr;                 // the relocalisation's scratch or null: never called
     uint8_t* key = nullptr;                    // device [N][NPIX], zeroed at enable
     KeyState* state = nullptr;                 // device [N], zeroed at enable (has_key = 0)
     uint8_t* scratch = nullptr;                // device: the sections of KeyScratch
@@ -105,6 +130,34 @@ struct MapScratch {
     }
 };
 
+// the relocalisation's own scratch for max_batch B: the call's table {ids | curr ring slot}, per slot the thumbnails of up to 9 candidates and of the
+// current frame, whether each candidate exists and its search record, the pick (candidate index and map slot), the attach flag and the call's record.
+// The alignment's scratch and the start offsets are the store's (KeyScratch).
+struct RelocScratch {
+    int32_t *tab, *valid, *cand, *mslot, *attach; uint8_t* thumbs; SearchRec* srec; RelocRec* out; size_t bytes;
+    RelocScratch(uint8_t* b, int B) {
+        size_t o = 0;
+        auto take = [&](size_t n) { uint8_t* p = b + o; o += (n + 255) & ~(size_t)255; return p; };
+        tab = reinterpret_cast<int32_t*>(take(map_table_bytes(B)));
+        thumbs = take((size_t)B * (RELOC_MAX_CANDIDATES + 1) * THUMB_BYTES);
+        valid = reinterpret_cast<int32_t*>(take((size_t)B * RELOC_MAX_CANDIDATES * sizeof(int32_t)));
+        srec = reinterpret_cast<SearchRec*>(take((size_t)B * RELOC_MAX_CANDIDATES * sizeof(SearchRec)));
+        cand = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
+        mslot = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
+        attach = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
+        out = reinterpret_cast<RelocRec*>(take((size_t)B * sizeof(RelocRec)));
+        bytes = o;
+    }
+};
+
+void reloc_free(KeyReloc* r) {
+    if (!r) return;
+    if (r->scratch) (void)hipFree(r->scratch);
+    if (r->pin_in) (void)hipHostFree(r->pin_in);
+    if (r->pin_out) (void)hipHostFree(r->pin_out);
+    delete r;
+}
+
 void map_free(KeyMap* m) {
     if (!m) return;
     if (m->dev.img) (void)hipFree(m->dev.img);
@@ -121,6 +174,7 @@ void map_free(KeyMap* m) {
 void keyframes_free(hnet_keyframes* k) {
     if (!k) return;
     map_free(k->map);
+    reloc_free(k->reloc);
     if (k->key) (void)hipFree(k->key);
     if (k->state) (void)hipFree(k->state);
     if (k->scratch) (void)hipFree(k->scratch);
@@ -399,6 +453,87 @@ int hnet_sessions_get_map_keyframe(hnet_sessions* s, int id, int slot, uint8_t* 
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
     HIPCHK(c, hipMemcpyAsync(out, m->dev.img + ((size_t)id * m->dev.capacity + slot) * NPIX, NPIX, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return HNET_OK;
+}
+
+void hnet_keyframe_relocalise_default_opts(hnet_keyframe_relocalise_opts* o) {
+    if (!o) return;
+    RelocOpts d;
+    hnet_keyframe_reloc::default_opts(d);
+    memcpy(o, &d, sizeof d);
+}
+
+// ONE upload {ids | curr slot}, the launch sequence inside the store's own events, ONE download of the records [n], one synchronisation
+int hnet_sessions_keyframe_relocalise(hnet_sessions* s, int n, const int32_t* ids, const hnet_keyframe_relocalise_opts* opts, hnet_keyframe_relocalise* out) {
+    const char* who = "hnet_sessions_keyframe_relocalise";
+    if (!s) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = s->ctx;
+    hnet_keyframes* k = s->kf;
+    if (!k) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": keyframes are not enabled (hnet_sessions_enable_keyframes)");
+    if (!out || !opts) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": opts / out");
+    int rc = photo_robust_check_opts(c, &opts->align, who);
+    if (rc != HNET_OK) return rc;
+    RelocOpts o;
+    memcpy(&o, opts, sizeof o);
+    if (!hnet_search::opts_valid(o.search))
+        return fail(c, HNET_ERR_INVALID_ARG,
+                    std::string(who) + ": opts.search: 0 <= radius_x <= 30, 0 <= radius_y <= 20, 16 <= min_overlap <= 1120, -1 <= min_score <= 1, 0 <= min_margin <= 2");
+    if (!hnet_keyframe_reloc::opts_valid(o))
+        return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": opts: 1 <= levels <= 4, 0 <= min_overlap <= 1, max_mse and max_closure_px >= 0 and finite");
+    o.pad = 0;
+    o.search.pad = 0;
+    if ((rc = sessions_check_ids(s, n, ids)) != HNET_OK) return rc;
+    for (int i = 0; i < n; i++) {
+        const int id = ids[i];
+        if (s->st[id].count < 1) return fail(c, HNET_ERR_NOT_READY, std::string(who) + ": a listed session has no image");
+        if (!k->has_key[id]) return fail(c, HNET_ERR_NOT_READY, std::string(who) + ": a listed session holds no keyframe");
+        if (s->st[id].count != k->count_at_track[id])
+            return fail(c, HNET_ERR_NOT_READY, std::string(who) + ": a listed session's latest image is not the one its last track saw (track it first)");
+    }
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    const int B = c->cfg.max_batch, N = s->n;
+    if (!k->reloc) {                           // the first call: nothing is enqueued yet
+        KeyReloc* r = new KeyReloc();
+        hipError_t e = hipMalloc((void**)&r->scratch, RelocScratch(nullptr, B).bytes);
+        if (e == hipSuccess) e = hipHostMalloc((void**)&r->pin_in, map_table_bytes(B), hipHostMallocDefault);
+        if (e == hipSuccess) e = hipHostMalloc((void**)&r->pin_out, (size_t)B * sizeof(RelocRec), hipHostMallocDefault);
+        if (e != hipSuccess) {
+            reloc_free(r);
+            return fail(c, HNET_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+        }
+        k->reloc = r;
+    }
+    KeyReloc* r = k->reloc;
+    const KeyScratch w(k->scratch, B);
+    const RelocScratch rw(r->scratch, B);
+    const MapStore none = {nullptr, nullptr, nullptr, N, 0};
+    const MapStore& map = k->map ? k->map->dev : none;
+    const int M = map.capacity;                // 0 without a map
+    int32_t* h_ids = reinterpret_cast<int32_t*>(r->pin_in);
+    for (int i = 0; i < n; i++) {
+        h_ids[i] = ids[i];
+        h_ids[n + i] = 2 * ids[i] + s->st[ids[i]].curr;
+    }
+    const int32_t *d_ids = rw.tab, *d_slot = rw.tab + n;
+    const size_t pyr = (size_t)B * PYR_BYTES;
+    uint8_t *prev = (uint8_t*)c->stage_prev, *curr = (uint8_t*)c->stage_curr;
+    hipStream_t st = c->stream;
+    HIPCHK(c, hipMemcpyAsync(rw.tab, r->pin_in, map_table_bytes(n), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipEventRecord(k->ev[0], st));
+    HIPCHK(c, launch_reloc_thumbs(d_ids, d_slot, n, N, k->state, k->key, map, s->ring, 2 * N, rw.thumbs, rw.valid, st));
+    HIPCHK(c, launch_photo_search(rw.thumbs, M + 2, M + 2, M + 1, M + 1, n, rw.valid, o.search, rw.srec, nullptr, st));
+    HIPCHK(c, launch_reloc_pick(d_ids, n, N, k->state, M, rw.valid, rw.srec, w.x0, rw.cand, rw.mslot, rw.out, st));
+    HIPCHK(c, launch_reloc_gather(d_ids, d_slot, n, N, rw.cand, k->key, map, s->ring, 2 * N, prev, curr, st));
+    HIPCHK(c, launch_photo_align_robust(prev, curr, n, w.x0, o.align, o.levels, c->pyr_scratch, c->pyr_scratch + pyr, w.start, w.part, w.work, w.rec, st));
+    HIPCHK(c, launch_reloc_decide(d_ids, n, N, w.rec, w.x0, rw.cand, o, k->state, map, rw.out, rw.attach, st));
+    if (k->map) HIPCHK(c, launch_keyframe_map_attach(d_ids, n, rw.mslot, rw.attach, map, k->key, st));
+    HIPCHK(c, hipEventRecord(k->ev[1], st));
+    HIPCHK(c, hipMemcpyAsync(r->pin_out, rw.out, (size_t)n * sizeof(RelocRec), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    float ms = 0;
+    HIPCHK(c, hipEventElapsedTime(&ms, k->ev[0], k->ev[1]));
+    k->ms = ms;
+    memcpy(out, r->pin_out, (size_t)n * sizeof(RelocRec));
     return HNET_OK;
 }
 

@@ -311,6 +311,22 @@ class HnetEngine:
                                                           out.ctypes.data, lv.ctypes.data if want_levels else None))
         return (out, lv) if want_levels else out
 
+    def op_photo_search(self, img1, img2, want_scores=False, **opts):
+        """coarse search over integer translations between the 40 x 28 thumbnails of uint8 frames [n, 224, 320] (hnet_op_photo_search): a start for the
+        alignments from up to 240 x 160 px away; opts as _capi.photo_search_opts -> records [n] of _capi.PHOTO_SEARCH_DTYPE; want_scores: (those, the
+        score of every shift [n, 41, 61], index [dy + 20, dx + 30], NaN where a shift is not scored or lies outside the radii)"""
+        a = np.ascontiguousarray(img1, dtype=np.uint8).reshape(-1, IMG_H, IMG_W)
+        b = np.ascontiguousarray(img2, dtype=np.uint8).reshape(-1, IMG_H, IMG_W)
+        n = a.shape[0]
+        if b.shape[0] != n:
+            raise ValueError("img1 and img2 must hold the same number of frames")
+        o = _capi.photo_search_opts(**opts)
+        out = np.zeros(n, _capi.PHOTO_SEARCH_DTYPE)
+        sc = np.zeros((n, _capi.PS_SHIFTS_Y, _capi.PS_SHIFTS_X)) if want_scores else None
+        check(self._h, self._L.hnet_op_photo_search(self._h, a.ctypes.data, b.ctypes.data, n, C.addressof(o), out.ctypes.data,
+                                                    sc.ctypes.data if want_scores else None))
+        return (out, sc) if want_scores else out
+
     def op_photo_pyramid(self, img):
         """levels 1 .. 3 of uint8 frames [n, 224, 320] (hnet_op_photo_pyramid) -> uint8 [n, _capi.PHOTO_PYRAMID_BYTES]: 160 x 112, 80 x 56 and
         40 x 28 pixels per frame, level 1 first"""
@@ -698,6 +714,25 @@ class HnetSessions:
         """the image in slot `slot` of the session's map as the store holds it (hnet_sessions_get_map_keyframe)"""
         out = np.zeros((IMG_H, IMG_W), np.uint8)
         self._check(self._L.hnet_sessions_get_map_keyframe(self._s, int(id), int(slot), out.ctypes.data))
+        return out
+
+    def photo_search(self, ids, **opts):
+        """coarse search over integer translations on the listed sessions' current pairs (hnet_sessions_photo_search); read-only; result as
+        HnetEngine.op_photo_search"""
+        ids, n = self._ids(ids)
+        o = _capi.photo_search_opts(**opts)
+        out = np.zeros(n, _capi.PHOTO_SEARCH_DTYPE)
+        self._check(self._L.hnet_sessions_photo_search(self._s, n, ids.ctypes.data, C.addressof(o), out.ctypes.data))
+        return out
+
+    def keyframe_relocalise(self, ids, **opts):
+        """hnet_sessions_keyframe_relocalise: the listed sessions' current frames searched against their held keyframe and every stored one, aligned
+        against the best FOUND candidate from the searched start; a session whose alignment passes is re-tracked on its keyframe or re-attached to the
+        stored one -> [n] of _capi.KEYFRAME_RELOC_DTYPE; opts as _capi.keyframe_relocalise_opts"""
+        ids, n = self._ids(ids)
+        o = _capi.keyframe_relocalise_opts(**opts)
+        out = np.zeros(n, _capi.KEYFRAME_RELOC_DTYPE)
+        self._check(self._L.hnet_sessions_keyframe_relocalise(self._s, n, ids.ctypes.data, C.addressof(o), out.ctypes.data))
         return out
 
     def image_count(self, id):

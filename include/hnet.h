@@ -828,7 +828,7 @@ int  hnet_sessions_keyframe_track(hnet_sessions* s, int n, const int32_t* ids, c
 int  hnet_sessions_keyframe_reset(hnet_sessions* s, int id);
 /* operator level (tests): the session's keyframe, 224 x 320 bytes; HNET_ERR_NOT_READY without one.  One download, one synchronisation. */
 int  hnet_sessions_get_keyframe(hnet_sessions* s, int id, uint8_t* out);
-double hnet_sessions_last_keyframe_device_ms(hnet_sessions* s);     /* 0 before the first track; with a map: of the last track or revisit */
+double hnet_sessions_last_keyframe_device_ms(hnet_sessions* s);     /* 0 before the first track; of the last track, revisit or relocalise */
 
 /* ---- sessions, a MAP of keyframes and closing loops against it, on the device (csrc/kernels_keyframe_map.hip; the shared code is
  * include/hnet_keyframe_map.h).  Opt-in on top of the keyframes: a sessions object that never calls hnet_sessions_enable_keyframe_map allocates,
@@ -890,6 +890,96 @@ int  hnet_sessions_keyframe_revisit(hnet_sessions* s, int n, const int32_t* ids,
  * slot was never written).  One download, one synchronisation each.  HNET_ERR_INVALID_ARG before hnet_sessions_enable_keyframe_map. */
 int  hnet_sessions_keyframe_map_info(hnet_sessions* s, int id, hnet_keyframe_map_entry* entries /* [capacity] */, hnet_keyframe_map_state* map_state);
 int  hnet_sessions_get_map_keyframe(hnet_sessions* s, int id, int slot, uint8_t* out);
+
+/* ---- a start that needs no prediction: a coarse search over integer translations, and finding a lost camera among its keyframes, on the device
+ * (csrc/kernels_photo_search.hip; the shared code is include/hnet_photo_search.h and include/hnet_keyframe_reloc.h).  Opt-in: a program that
+ * never calls these entry points allocates, launches and returns exactly what it did before.
+ * Every alignment above needs a start inside its basin (about 24 px at four levels), and both the track and the revisit get theirs from a prediction.
+ * The search compares the level-3 thumbnails (40 x 28 u8, level 3 of the pyramid of hnet_op_photo_pyramid bit for bit) of img1 and img2 at every integer
+ * shift (dx, dy), |dx| <= radius_x <= 30, |dy| <= radius_y <= 20, 8 full-resolution pixels per step: template pixel (u, v) of img1 against img2 at
+ * (u + dx, v + dy), the sense of H(x).  Over the overlap (n pixels) the integer sums Sa, Sb, Sab, Saa, Sbb give, exact in int64, num = n Sab - Sa Sb,
+ * va = n Saa - Sa^2, vb = n Sbb - Sb^2; a shift is SCORED when n >= min_overlap, va > 0 and vb > 0, score = (double) num / sqrt((double) va * (double) vb).
+ * The best: highest score, then smaller dx^2 + dy^2, then smaller dy, then smaller dx.  `second` is the best by the same order among the scored shifts
+ * more than one step from it in x or y; -1 when there is none.  Flags, exactly one, in this order: HNET_PS_NO_TEXTURE (nothing was scored: a constant
+ * thumbnail, or a min_overlap nothing meets; dx = dy = 0, score -1, sums 0), HNET_PS_LOW_SCORE (score < min_score), HNET_PS_AMBIGUOUS
+ * (score - second < min_margin), else HNET_PS_FOUND.  start_px is (8 dx, 8 dy) on all four corners when FOUND, quiet NaNs otherwise (on which the
+ * alignments report HNET_ALIGN_DEGENERATE at once).  The defaults were set between the figures of a prototype on synthetic views, not calibrated on
+ * footage.  A record depends on its pair and the options alone.
+ * Errors, nothing written: HNET_ERR_INVALID_ARG for a null argument, n < 1 or options out of range (radius_x outside 0 .. 30, radius_y outside 0 .. 20,
+ * min_overlap outside 16 .. 1120, min_score outside -1 .. 1, min_margin outside 0 .. 2, a NaN); HNET_ERR_CAPACITY for n > max_batch.  One upload, two
+ * launches (thumbnails, search), one download, one synchronisation. */
+typedef struct hnet_photo_search_opts {
+    int32_t radius_x;          /* 0 .. 30 level-3 pixels */
+    int32_t radius_y;          /* 0 .. 20 */
+    int32_t min_overlap;       /* 16 .. 1120 level-3 pixels */
+    int32_t pad;
+    double  min_score;         /* -1 .. 1 */
+    double  min_margin;        /* 0 .. 2 */
+} hnet_photo_search_opts;
+enum { HNET_PS_FOUND = 1, HNET_PS_NO_TEXTURE = 2, HNET_PS_LOW_SCORE = 4, HNET_PS_AMBIGUOUS = 8 };
+#define HNET_PS_SHIFTS_X 61
+#define HNET_PS_SHIFTS_Y 41
+typedef struct hnet_photo_search {
+    float   start_px[8];       /* (8 dx, 8 dy) on the four corners when FOUND, else quiet NaNs */
+    int32_t dx, dy;            /* the best shift, level-3 pixels */
+    int32_t dx2, dy2;          /* the second's shift; 0, 0 without one */
+    int32_t n_overlap;         /* pixels of the best shift's overlap */
+    int32_t flags;             /* HNET_PS_* */
+    double  score, second;     /* -1 without one */
+    int32_t sa, sb, sab, saa, sbb;     /* the sums of the best shift */
+    int32_t pad;               /* written zero: records compare byte for byte */
+} hnet_photo_search;
+void hnet_photo_search_default_opts(hnet_photo_search_opts* o);      /* 30, 20, 140, 0.75, 0.1 */
+/* operator call, host pointers: img1 / img2 u8 [n][224][320], out [n]; scores_out NULL or double [n][41][61], index [dy + 20][dx + 30]: the score of every
+ * shift of the full range, quiet NaN where a shift is not scored or lies outside the radii (operator level, for the tests) */
+int  hnet_op_photo_search(hnet_ctx* ctx, const uint8_t* img1, const uint8_t* img2, int n, const hnet_photo_search_opts* opts, hnet_photo_search* out,
+                          double* scores_out);
+/* the same on the (prev, curr) pair of each listed session, byte for byte the operator call; read-only like hnet_sessions_photo_align_robust, errors as
+ * there */
+int  hnet_sessions_photo_search(hnet_sessions* s, int n, const int32_t* ids, const hnet_photo_search_opts* opts, hnet_photo_search* out);
+
+/* hnet_sessions_keyframe_relocalise: after hnet_sessions_enable_keyframes, with or without a map.  The intended use: track, see HNET_KF_LOST, relocalise
+ * on the same frame.  The candidates of a listed session are its held keyframe (target -1) and, with a map, every valid entry with slot != cur_slot
+ * (target = the slot); there is no condition on links and no chain prediction.  Every candidate is searched against the session's current frame
+ * (candidate = img1).  The pick is the FOUND candidate of the highest score; ties go to the held keyframe, then the lower slot.  None:
+ * HNET_RL_NO_CANDIDATE, target -2, nothing changes.  Otherwise the alignment candidate -> curr runs from the search's start_px with
+ * hnet_op_photo_align_robust's launch sequence, rv.rec being its level-0 record byte for byte, and one decision follows on the device.
+ *   A map entry: the decision of hnet_sessions_keyframe_revisit exactly as it is, with the searched start in place of the selected one; the reasons and
+ *   effects are unchanged, HNET_RL_ATTACHED re-anchors h_origin_key to the entry's.  rv.grid is 0.
+ *   The held keyframe: the same REJECTED reasons in the same order without HNET_RL_CHAIN; else HNET_RL_RETRACKED: key_px = rec's offsets, everything
+ *   else of the state and the map state unchanged.  rv.slot = -1, rv.links = 0; rv.h_origin_curr = H(key_px) . h_origin_key (h_origin_before when that
+ *   product is degenerate or the call is rejected), rv.closure_px as hnet_keyframe_revisit defines it.
+ * A rejected or candidate-less call changes neither state.  Read-only for everything else, like a track.
+ * Errors, nothing changed and nothing written: everything hnet_sessions_keyframe_revisit refuses except that the map need not be enabled (min_grid does
+ * not exist here); the search options out of range; HNET_ERR_NOT_READY for a listed session without a keyframe or whose latest image is not the one its
+ * last track saw.  The first call allocates the thumbnails and records of max_batch x 9 candidates.  A call is ONE upload {ids | curr slot}, the
+ * launches (thumbnails, search, pick, gather, the alignment's sequence, decide, and the map's attach), ONE download of the records [n] and one
+ * synchronisation; hnet_sessions_last_keyframe_device_ms covers it. */
+typedef struct hnet_keyframe_relocalise_opts {
+    hnet_photo_robust_opts align;
+    int32_t levels;            /* 1 .. 4 */
+    int32_t pad;
+    hnet_photo_search_opts search;
+    double  min_overlap;       /* 0 .. 1 */
+    double  max_mse;           /* >= 0; 0 = no limit */
+    double  max_closure_px;    /* >= 0; 0 = no limit: the worst |offset - searched start| */
+} hnet_keyframe_relocalise_opts;
+enum { HNET_RL_NO_CANDIDATE = 1, HNET_RL_ATTACHED = 2,
+       HNET_RL_STOPPED = 4, HNET_RL_MSE_ABOVE_MAX = 8, HNET_RL_NON_FINITE = 16, HNET_RL_LOW_OVERLAP = 32, HNET_RL_CLOSURE_ABOVE_MAX = 64,
+       HNET_RL_CHAIN = 128,                                                                              /* the REJECTED reasons: HNET_RV_*'s values */
+       HNET_RL_RETRACKED = 256,
+       HNET_RL_REJECTED = 4 | 8 | 16 | 32 | 64 | 128 };
+typedef struct hnet_keyframe_relocalise {
+    hnet_keyframe_revisit rv;    /* the alignment's level-0 record, start_px, key_px, h_origin_before / _curr, closure_px, overlap, slot, links; flags HNET_RL_* */
+    hnet_photo_search search;    /* of the picked candidate; all zero without a pick */
+    int32_t target;              /* -1: the held keyframe, >= 0: the map slot, -2: no pick */
+    int32_t n_searched;          /* candidates searched */
+    int32_t n_found;             /* of them HNET_PS_FOUND */
+    int32_t pad;                 /* written zero */
+} hnet_keyframe_relocalise;
+void hnet_keyframe_relocalise_default_opts(hnet_keyframe_relocalise_opts* o);  /* robust defaults, levels 4, search defaults, min_overlap 0.5, max_mse 0, max_closure_px 0 */
+int  hnet_sessions_keyframe_relocalise(hnet_sessions* s, int n, const int32_t* ids, const hnet_keyframe_relocalise_opts* opts,
+                                       hnet_keyframe_relocalise* out /* [n] */);
 
 int hnet_synchronize(hnet_ctx* ctx, void* stream);
 int hnet_last_timing(const hnet_ctx* ctx, hnet_timing* out);
