@@ -51,6 +51,8 @@ SYMBOLS = [
     "hnet_photo_refine_default_opts", "hnet_filters_set_photo_refine", "hnet_filters_last_refine", "hnet_filters_refine_stats", "hnet_filters_reset_refine_stats",
     "hnet_photo_search_default_opts", "hnet_op_photo_search", "hnet_sessions_photo_search",
     "hnet_keyframe_relocalise_default_opts", "hnet_sessions_keyframe_relocalise",
+    "hnet_photo_search_make_hyp", "hnet_photo_search_yaw_table", "hnet_photo_search_default_yaw_table", "hnet_op_photo_search_oriented",
+    "hnet_sessions_photo_search_oriented", "hnet_sessions_keyframe_relocalise_oriented",
     "hnet_keyframe_default_opts", "hnet_sessions_enable_keyframes", "hnet_sessions_keyframe_track", "hnet_sessions_keyframe_reset", "hnet_sessions_get_keyframe",
     "hnet_sessions_last_keyframe_device_ms",
     "hnet_keyframe_revisit_default_opts", "hnet_sessions_enable_keyframe_map", "hnet_sessions_keyframe_revisit", "hnet_sessions_keyframe_map_info",
@@ -360,6 +362,42 @@ def keyframe_relocalise_opts(**kw):
     return o
 
 
+# the search under a table of orientation hypotheses (hnet_op_photo_search_oriented): a table entry, and one record per pair: 7r's record of the winning
+# entry, then the winner's index, the entries with a scored shift, the runner-up's index and score, and the winner's matrix
+PHOTO_SEARCH_HYP_DTYPE = _np.dtype([("a", "<f8", 4), ("b", "<i4", 4)])
+PHOTO_SEARCH_ORIENTED_DTYPE = _np.dtype([("base", PHOTO_SEARCH_DTYPE), ("hyp", "<i4"), ("n_scored", "<i4"), ("hyp2", "<i4"), ("pad0", "<i4"), ("score2", "<f8"),
+                                         ("a", "<f8", 4), ("pad", "<i4", 2)])
+KEYFRAME_RELOC_ORIENTED_DTYPE = _np.dtype([("rv", KEYFRAME_REVISIT_DTYPE), ("search", PHOTO_SEARCH_ORIENTED_DTYPE), ("target", "<i4"), ("n_searched", "<i4"),
+                                           ("n_found", "<i4"), ("pad", "<i4")])
+assert PHOTO_SEARCH_HYP_DTYPE.itemsize == 48 and PHOTO_SEARCH_ORIENTED_DTYPE.itemsize == 160 and KEYFRAME_RELOC_ORIENTED_DTYPE.itemsize == 1864 + 160 + 16
+PS_MAX_HYP, PS_DEFAULT_HYP = 64, 60
+
+
+def photo_search_hyp(angle_rad, scale=1.0):
+    """one table entry (hnet_photo_search_make_hyp) -> [1] of PHOTO_SEARCH_HYP_DTYPE; ValueError for a non-finite angle or a scale outside [0.5, 2]"""
+    out = _np.zeros(1, PHOTO_SEARCH_HYP_DTYPE)
+    if not lib().hnet_photo_search_make_hyp(float(angle_rad), float(scale), out.ctypes.data):
+        raise ValueError("hnet_photo_search_make_hyp: a finite angle and 0.5 <= scale <= 2")
+    return out
+
+
+def photo_search_yaw_table(first_deg=-180.0, step_deg=6.0, count=PS_DEFAULT_HYP):
+    """`count` entries of scale 1 at first_deg + k step_deg degrees (hnet_photo_search_yaw_table); the defaults are the documented default table"""
+    if not 1 <= int(count) <= PS_MAX_HYP:
+        raise ValueError("hnet_photo_search_yaw_table: 1 <= count <= 64")
+    out = _np.zeros(int(count), PHOTO_SEARCH_HYP_DTYPE)
+    if not lib().hnet_photo_search_yaw_table(float(first_deg), float(step_deg), int(count), out.ctypes.data):
+        raise ValueError("hnet_photo_search_yaw_table: finite angles")
+    return out
+
+
+def photo_search_table(hyps):
+    """the table a call passes on: None = the default yaw table; else [n_hyp] of PHOTO_SEARCH_HYP_DTYPE as it is (the library refuses what it must)"""
+    if hyps is None:
+        return photo_search_yaw_table()
+    return _np.ascontiguousarray(hyps, PHOTO_SEARCH_HYP_DTYPE).reshape(-1)
+
+
 def photo_robust_marginal(rec):
     """hnet_photo_robust_marginal of one record -> (info8 [8, 8], grad8 [8]); ValueError when the brightness block has no Cholesky factor"""
     r = _np.ascontiguousarray(rec, PHOTO_ROBUST_DTYPE).reshape(1)
@@ -557,6 +595,12 @@ def lib():
     L.hnet_keyframe_relocalise_default_opts.argtypes = [C.POINTER(KeyframeRelocOpts)]
     L.hnet_keyframe_relocalise_default_opts.restype = None
     L.hnet_sessions_keyframe_relocalise.argtypes = [vp, C.c_int, vp, vp, vp]
+    L.hnet_photo_search_make_hyp.argtypes = [C.c_double, C.c_double, vp]
+    L.hnet_photo_search_yaw_table.argtypes = [C.c_double, C.c_double, C.c_int, vp]
+    L.hnet_photo_search_default_yaw_table.argtypes = [vp]
+    L.hnet_op_photo_search_oriented.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp]
+    L.hnet_sessions_photo_search_oriented.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp]
+    L.hnet_sessions_keyframe_relocalise_oriented.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp]
     L.hnet_last_photo_align_device_ms.restype = C.c_double
     L.hnet_photo_refine_default_opts.argtypes = [C.POINTER(PhotoRefineOpts)]
     L.hnet_photo_refine_default_opts.restype = None

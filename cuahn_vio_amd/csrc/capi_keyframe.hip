@@ -9,8 +9,11 @@
 // thumbnail against the held keyframe's and every stored one's, aligns against the best FOUND candidate from the searched start and re-tracks or
 // re-attaches the session (include/hnet_keyframe_reloc.h).  Its scratch is allocated by its first call: a store that never relocalises has
 // kf->reloc == nullptr.
+// And the ORIENTED relocalisation (photo_search_oriented_dev.h, csrc/kernels_photo_search_oriented.hip): hnet_sessions_keyframe_relocalise_oriented
+// is the same call with the search under a table of orientation hypotheses; the thumbnails, the gather, the alignment and the attach are the same launches.
+// Its scratch is its own and allocated by its first call: kf->oreloc == nullptr until then.
 #include "sessions_internal.h"
-#include "photo_search_dev.h"
+#include "photo_search_oriented_dev.h"
 
 using namespace hnet;
 using namespace capi;
@@ -54,6 +57,10 @@ static_assert((int)HNET_RL_NO_CANDIDATE == hnet_keyframe_reloc::RL_NO_CANDIDATE 
               (int)HNET_RL_CLOSURE_ABOVE_MAX == hnet_keyframe_reloc::RL_CLOSURE_ABOVE_MAX && (int)HNET_RL_CHAIN == hnet_keyframe_reloc::RL_CHAIN &&
               (int)HNET_RL_RETRACKED == hnet_keyframe_reloc::RL_RETRACKED && (int)HNET_RL_REJECTED == hnet_keyframe_reloc::RL_REJECTED,
               "HNET_RL_* are the header's flags");
+static_assert(sizeof(hnet_keyframe_relocalise_oriented) == sizeof(OrientedRelocRec) && offsetof(hnet_keyframe_relocalise_oriented, search) == offsetof(OrientedRelocRec, search) &&
+              offsetof(hnet_keyframe_relocalise_oriented, target) == offsetof(OrientedRelocRec, target) &&
+              offsetof(hnet_keyframe_relocalise_oriented, n_found) == offsetof(OrientedRelocRec, n_found),
+              "hnet_keyframe_relocalise_oriented is 7r's record around the oriented search record");
 
 // the scratch of the relocalisation (allocated by the first hnet_sessions_keyframe_relocalise), for max_batch B and the largest map
 struct KeyReloc {
@@ -73,6 +80,7 @@ struct KeyMap {
 struct hnet_keyframes {
     KeyMap* map = nullptr;                     // the keyframe map or null: never enabled
     KeyReloc* reloc = nullptr;                 // the relocalisation's scratch or null: never called
+    KeyReloc* oreloc = nullptr;                // the oriented relocalisation's scratch (the sections of OrientedScratch) or null: never called
     uint8_t* key = nullptr;                    // device [N][NPIX], zeroed at enable
     KeyState* state = nullptr;                 // device [N], zeroed at enable (has_key = 0)
     uint8_t* scratch = nullptr;                // device: the sections of KeyScratch
@@ -150,6 +158,27 @@ struct RelocScratch {
     }
 };
 
+// the oriented relocalisation's own scratch for max_batch B: the call's table {ids | curr ring slot | hypotheses [64]}, RelocScratch's sections with the
+// oriented records, and per candidate the records of up to 64 entries
+size_t oriented_table_bytes(int n) { return map_table_bytes(n) + (size_t)SEARCH_MAX_HYP * sizeof(SearchHyp); }
+struct OrientedScratch {
+    int32_t *tab, *valid, *cand, *mslot, *attach; uint8_t* thumbs; SearchRec* hrec; OrientedRec* srec; OrientedRelocRec* out; size_t bytes;
+    OrientedScratch(uint8_t* b, int B) {
+        size_t o = 0;
+        auto take = [&](size_t n) { uint8_t* p = b + o; o += (n + 255) & ~(size_t)255; return p; };
+        tab = reinterpret_cast<int32_t*>(take(oriented_table_bytes(B)));
+        thumbs = take((size_t)B * (RELOC_MAX_CANDIDATES + 1) * THUMB_BYTES);
+        valid = reinterpret_cast<int32_t*>(take((size_t)B * RELOC_MAX_CANDIDATES * sizeof(int32_t)));
+        hrec = reinterpret_cast<SearchRec*>(take((size_t)B * RELOC_MAX_CANDIDATES * SEARCH_MAX_HYP * sizeof(SearchRec)));
+        srec = reinterpret_cast<OrientedRec*>(take((size_t)B * RELOC_MAX_CANDIDATES * sizeof(OrientedRec)));
+        cand = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
+        mslot = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
+        attach = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
+        out = reinterpret_cast<OrientedRelocRec*>(take((size_t)B * sizeof(OrientedRelocRec)));
+        bytes = o;
+    }
+};
+
 void reloc_free(KeyReloc* r) {
     if (!r) return;
     if (r->scratch) (void)hipFree(r->scratch);
@@ -175,6 +204,7 @@ void keyframes_free(hnet_keyframes* k) {
     if (!k) return;
     map_free(k->map);
     reloc_free(k->reloc);
+    reloc_free(k->oreloc);
     if (k->key) (void)hipFree(k->key);
     if (k->state) (void)hipFree(k->state);
     if (k->scratch) (void)hipFree(k->scratch);
@@ -534,6 +564,87 @@ int hnet_sessions_keyframe_relocalise(hnet_sessions* s, int n, const int32_t* id
     HIPCHK(c, hipEventElapsedTime(&ms, k->ev[0], k->ev[1]));
     k->ms = ms;
     memcpy(out, r->pin_out, (size_t)n * sizeof(RelocRec));
+    return HNET_OK;
+}
+
+// hnet_sessions_keyframe_relocalise with the oriented search: ONE upload {ids | curr slot | table}, the launch sequence inside the store's own events, ONE
+// download of the records [n], one synchronisation
+int hnet_sessions_keyframe_relocalise_oriented(hnet_sessions* s, int n, const int32_t* ids, const hnet_keyframe_relocalise_opts* opts,
+                                               const hnet_photo_search_hyp* hyps, int n_hyp, hnet_keyframe_relocalise_oriented* out) {
+    const char* who = "hnet_sessions_keyframe_relocalise_oriented";
+    if (!s) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = s->ctx;
+    hnet_keyframes* k = s->kf;
+    if (!k) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": keyframes are not enabled (hnet_sessions_enable_keyframes)");
+    if (!out || !opts) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": opts / out");
+    int rc = photo_robust_check_opts(c, &opts->align, who);
+    if (rc != HNET_OK) return rc;
+    RelocOpts o;
+    memcpy(&o, opts, sizeof o);
+    if (!hnet_search::opts_valid(o.search))
+        return fail(c, HNET_ERR_INVALID_ARG,
+                    std::string(who) + ": opts.search: 0 <= radius_x <= 30, 0 <= radius_y <= 20, 16 <= min_overlap <= 1120, -1 <= min_score <= 1, 0 <= min_margin <= 2");
+    if (!hnet_keyframe_reloc::opts_valid(o))
+        return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": opts: 1 <= levels <= 4, 0 <= min_overlap <= 1, max_mse and max_closure_px >= 0 and finite");
+    o.pad = 0;
+    o.search.pad = 0;
+    if ((rc = photo_search_check_table(c, hyps, n_hyp, who)) != HNET_OK) return rc;
+    if ((rc = sessions_check_ids(s, n, ids)) != HNET_OK) return rc;
+    for (int i = 0; i < n; i++) {
+        const int id = ids[i];
+        if (s->st[id].count < 1) return fail(c, HNET_ERR_NOT_READY, std::string(who) + ": a listed session has no image");
+        if (!k->has_key[id]) return fail(c, HNET_ERR_NOT_READY, std::string(who) + ": a listed session holds no keyframe");
+        if (s->st[id].count != k->count_at_track[id])
+            return fail(c, HNET_ERR_NOT_READY, std::string(who) + ": a listed session's latest image is not the one its last track saw (track it first)");
+    }
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    const int B = c->cfg.max_batch, N = s->n;
+    if (!k->oreloc) {                          // the first call: nothing is enqueued yet
+        KeyReloc* r = new KeyReloc();
+        hipError_t e = hipMalloc((void**)&r->scratch, OrientedScratch(nullptr, B).bytes);
+        if (e == hipSuccess) e = hipHostMalloc((void**)&r->pin_in, oriented_table_bytes(B), hipHostMallocDefault);
+        if (e == hipSuccess) e = hipHostMalloc((void**)&r->pin_out, (size_t)B * sizeof(OrientedRelocRec), hipHostMallocDefault);
+        if (e != hipSuccess) {
+            reloc_free(r);
+            return fail(c, HNET_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+        }
+        k->oreloc = r;
+    }
+    KeyReloc* r = k->oreloc;
+    const KeyScratch w(k->scratch, B);
+    const OrientedScratch rw(r->scratch, B);
+    const MapStore none = {nullptr, nullptr, nullptr, N, 0};
+    const MapStore& map = k->map ? k->map->dev : none;
+    const int M = map.capacity;                // 0 without a map
+    int32_t* h_ids = reinterpret_cast<int32_t*>(r->pin_in);
+    for (int i = 0; i < n; i++) {
+        h_ids[i] = ids[i];
+        h_ids[n + i] = 2 * ids[i] + s->st[ids[i]].curr;
+    }
+    const size_t tab = (size_t)n_hyp * sizeof(SearchHyp);
+    memcpy(r->pin_in + map_table_bytes(n), hyps, tab);          // (8 n bytes in front: the table is aligned)
+    const int32_t *d_ids = rw.tab, *d_slot = rw.tab + n;
+    const SearchHyp* d_hyps = reinterpret_cast<const SearchHyp*>(rw.tab + 2 * (size_t)n);
+    const size_t pyr = (size_t)B * PYR_BYTES;
+    uint8_t *prev = (uint8_t*)c->stage_prev, *curr = (uint8_t*)c->stage_curr;
+    hipStream_t st = c->stream;
+    HIPCHK(c, hipMemcpyAsync(rw.tab, r->pin_in, map_table_bytes(n) + tab, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipEventRecord(k->ev[0], st));
+    HIPCHK(c, launch_reloc_thumbs(d_ids, d_slot, n, N, k->state, k->key, map, s->ring, 2 * N, rw.thumbs, rw.valid, st));
+    HIPCHK(c, launch_photo_search_oriented(rw.thumbs, M + 2, M + 2, M + 1, M + 1, n, rw.valid, o.search, d_hyps, n_hyp, rw.hrec, nullptr, st));
+    HIPCHK(c, launch_photo_search_winner(rw.hrec, d_hyps, n_hyp, n * (M + 1), rw.valid, rw.srec, st));
+    HIPCHK(c, launch_reloc_pick_oriented(d_ids, n, N, k->state, M, rw.valid, rw.srec, w.x0, rw.cand, rw.mslot, rw.out, st));
+    HIPCHK(c, launch_reloc_gather(d_ids, d_slot, n, N, rw.cand, k->key, map, s->ring, 2 * N, prev, curr, st));
+    HIPCHK(c, launch_photo_align_robust(prev, curr, n, w.x0, o.align, o.levels, c->pyr_scratch, c->pyr_scratch + pyr, w.start, w.part, w.work, w.rec, st));
+    HIPCHK(c, launch_reloc_decide_oriented(d_ids, n, N, w.rec, w.x0, rw.cand, o, k->state, map, rw.out, rw.attach, st));
+    if (k->map) HIPCHK(c, launch_keyframe_map_attach(d_ids, n, rw.mslot, rw.attach, map, k->key, st));
+    HIPCHK(c, hipEventRecord(k->ev[1], st));
+    HIPCHK(c, hipMemcpyAsync(r->pin_out, rw.out, (size_t)n * sizeof(OrientedRelocRec), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    float ms = 0;
+    HIPCHK(c, hipEventElapsedTime(&ms, k->ev[0], k->ev[1]));
+    k->ms = ms;
+    memcpy(out, r->pin_out, (size_t)n * sizeof(OrientedRelocRec));
     return HNET_OK;
 }
 

@@ -327,6 +327,23 @@ class HnetEngine:
                                                     sc.ctypes.data if want_scores else None))
         return (out, sc) if want_scores else out
 
+    def op_photo_search_oriented(self, img1, img2, hyps=None, want_scores=False, **opts):
+        """the coarse search under a table of orientation hypotheses (hnet_op_photo_search_oriented): a start for the alignments for a camera that has also
+        turned; hyps [n_hyp] of _capi.PHOTO_SEARCH_HYP_DTYPE (None: the default table, 60 yaws of 6 degrees), opts as _capi.photo_search_opts ->
+        records [n] of _capi.PHOTO_SEARCH_ORIENTED_DTYPE; want_scores: (those, the score of every entry and shift [n, n_hyp, 41, 61])"""
+        a = np.ascontiguousarray(img1, dtype=np.uint8).reshape(-1, IMG_H, IMG_W)
+        b = np.ascontiguousarray(img2, dtype=np.uint8).reshape(-1, IMG_H, IMG_W)
+        n = a.shape[0]
+        if b.shape[0] != n:
+            raise ValueError("img1 and img2 must hold the same number of frames")
+        o = _capi.photo_search_opts(**opts)
+        h = _capi.photo_search_table(hyps)
+        out = np.zeros(n, _capi.PHOTO_SEARCH_ORIENTED_DTYPE)
+        sc = np.zeros((n, max(len(h), 1), _capi.PS_SHIFTS_Y, _capi.PS_SHIFTS_X)) if want_scores else None
+        check(self._h, self._L.hnet_op_photo_search_oriented(self._h, a.ctypes.data, b.ctypes.data, n, C.addressof(o), h.ctypes.data, len(h), out.ctypes.data,
+                                                             sc.ctypes.data if want_scores else None))
+        return (out, sc) if want_scores else out
+
     def op_photo_pyramid(self, img):
         """levels 1 .. 3 of uint8 frames [n, 224, 320] (hnet_op_photo_pyramid) -> uint8 [n, _capi.PHOTO_PYRAMID_BYTES]: 160 x 112, 80 x 56 and
         40 x 28 pixels per frame, level 1 first"""
@@ -733,6 +750,26 @@ class HnetSessions:
         o = _capi.keyframe_relocalise_opts(**opts)
         out = np.zeros(n, _capi.KEYFRAME_RELOC_DTYPE)
         self._check(self._L.hnet_sessions_keyframe_relocalise(self._s, n, ids.ctypes.data, C.addressof(o), out.ctypes.data))
+        return out
+
+    def photo_search_oriented(self, ids, hyps=None, **opts):
+        """the search under a table of orientation hypotheses on the listed sessions' current pairs (hnet_sessions_photo_search_oriented); read-only;
+        result as HnetEngine.op_photo_search_oriented"""
+        ids, n = self._ids(ids)
+        o = _capi.photo_search_opts(**opts)
+        h = _capi.photo_search_table(hyps)
+        out = np.zeros(n, _capi.PHOTO_SEARCH_ORIENTED_DTYPE)
+        self._check(self._L.hnet_sessions_photo_search_oriented(self._s, n, ids.ctypes.data, C.addressof(o), h.ctypes.data, len(h), out.ctypes.data))
+        return out
+
+    def keyframe_relocalise_oriented(self, ids, hyps=None, **opts):
+        """hnet_sessions_keyframe_relocalise_oriented: keyframe_relocalise with the search under a table of orientation hypotheses (hyps as
+        op_photo_search_oriented) -> [n] of _capi.KEYFRAME_RELOC_ORIENTED_DTYPE; opts as _capi.keyframe_relocalise_opts"""
+        ids, n = self._ids(ids)
+        o = _capi.keyframe_relocalise_opts(**opts)
+        h = _capi.photo_search_table(hyps)
+        out = np.zeros(n, _capi.KEYFRAME_RELOC_ORIENTED_DTYPE)
+        self._check(self._L.hnet_sessions_keyframe_relocalise_oriented(self._s, n, ids.ctypes.data, C.addressof(o), h.ctypes.data, len(h), out.ctypes.data))
         return out
 
     def image_count(self, id):

@@ -981,6 +981,64 @@ void hnet_keyframe_relocalise_default_opts(hnet_keyframe_relocalise_opts* o);  /
 int  hnet_sessions_keyframe_relocalise(hnet_sessions* s, int n, const int32_t* ids, const hnet_keyframe_relocalise_opts* opts,
                                        hnet_keyframe_relocalise* out /* [n] */);
 
+/* ---- the same search under a table of ORIENTATION hypotheses: a camera that is lost and has turned (csrc/kernels_photo_search_oriented.hip; the shared
+ * code is include/hnet_photo_search_oriented.h).  Opt-in like the search above.
+ * A hypothesis is a linear map A about the frame centre c = (159.5, 111.5), x' = c + A (x - c) + t in the sense of H(x): a table entry holds A (a, row
+ * major) and b = round(65536 A^-1).  hnet_photo_search_make_hyp fills one from an angle and a scale in [0.5, 2] on the host; the device never evaluates a
+ * trigonometric function.  A table has 1 .. 64 entries; hnet_photo_search_yaw_table fills `count` entries of scale 1 at first_deg + k step_deg degrees; the
+ * documented default is 60 entries of 6 degrees from -180.
+ * Per entry the template thumbnail is warped by b in integers (bilinear in 1/256 steps; a pixel whose taps leave the thumbnail is masked out), and the
+ * search above runs with the sums restricted to the valid template pixels: n = sum m, Sa = sum a, Saa = sum a^2, Sab = sum a b, Sb = sum m b,
+ * Sbb = sum m b^2, the same score, best and second.  The winner over the table is the entry with the highest best score, ties to the lower index; the
+ * flags are the four above, judged on the winner's best and its OWN second; nothing scored under any entry: HNET_PS_NO_TEXTURE.  The runner-up (hyp2,
+ * score2: the best of the other entries) is reported and never gated: neighbouring entries are near-peaks by construction.  start_px at corner x_i is
+ * c + A (x_i - c) + 8 (dx, dy) - x_i when FOUND, quiet NaNs otherwise.  With a table of only the identity, `base` is hnet_op_photo_search's record byte
+ * for byte.
+ * Errors, nothing written and nothing enqueued: those of hnet_op_photo_search; HNET_ERR_INVALID_ARG for a null table, n_hyp outside 1 .. 64, an entry with
+ * a non-finite a or |b[i]| > 2 * 65536.  One upload, three launches (thumbnails, search, winner), one download, one synchronisation. */
+#define HNET_PS_MAX_HYP 64
+typedef struct hnet_photo_search_hyp {
+    double  a[4];              /* A, row major */
+    int32_t b[4];              /* round(65536 A^-1), row major */
+} hnet_photo_search_hyp;
+typedef struct hnet_photo_search_oriented {
+    hnet_photo_search base;    /* of the winning entry; start_px under the entry */
+    int32_t hyp;               /* the winner's table index; -1 without one */
+    int32_t n_scored;          /* entries with a scored shift */
+    int32_t hyp2;              /* the runner-up's table index; -1 without one */
+    int32_t pad0;              /* written zero */
+    double  score2;            /* the runner-up's best score; -1 without one */
+    double  a[4];              /* the winner's A; zeros without one */
+    int32_t pad[2];            /* written zero */
+} hnet_photo_search_oriented;
+/* 1 on success; 0, nothing written, for a non-finite angle or a scale outside [0.5, 2] */
+int  hnet_photo_search_make_hyp(double angle_rad, double scale, hnet_photo_search_hyp* out);
+/* 1 on success; 0 for a count outside 1 .. 64, a null table or a non-finite angle */
+int  hnet_photo_search_yaw_table(double first_deg, double step_deg, int count, hnet_photo_search_hyp* out /* [count] */);
+/* the documented default: 60 entries of 6 degrees from -180; returns the count (60), 0 for a null table */
+#define HNET_PS_DEFAULT_HYP 60
+int  hnet_photo_search_default_yaw_table(hnet_photo_search_hyp* out /* [60] */);
+/* operator call, host pointers: as hnet_op_photo_search; hyps [n_hyp]; scores_out NULL or double [n][n_hyp][41][61] */
+int  hnet_op_photo_search_oriented(hnet_ctx* ctx, const uint8_t* img1, const uint8_t* img2, int n, const hnet_photo_search_opts* opts,
+                                   const hnet_photo_search_hyp* hyps, int n_hyp, hnet_photo_search_oriented* out, double* scores_out);
+/* the same on the (prev, curr) pair of each listed session, byte for byte the operator call; read-only, errors as hnet_sessions_photo_search */
+int  hnet_sessions_photo_search_oriented(hnet_sessions* s, int n, const int32_t* ids, const hnet_photo_search_opts* opts, const hnet_photo_search_hyp* hyps,
+                                         int n_hyp, hnet_photo_search_oriented* out);
+
+/* hnet_sessions_keyframe_relocalise_oriented: hnet_sessions_keyframe_relocalise with the oriented search over the same candidates; the pick, the
+ * alignment from the searched start, the decision and the attach are that call's, unchanged, and so are its options and its refusals, plus the table's.
+ * The first call allocates its scratch (the entries' records of max_batch x 9 candidates x 64 entries) before anything is enqueued.  A call is ONE upload
+ * {ids | curr slot | table}, the launches (thumbnails, search, winner, pick, gather, the alignment's sequence, decide, and the map's attach), ONE
+ * download and one synchronisation; hnet_sessions_last_keyframe_device_ms covers it. */
+typedef struct hnet_keyframe_relocalise_oriented {
+    hnet_keyframe_revisit rv;             /* as hnet_keyframe_relocalise */
+    hnet_photo_search_oriented search;    /* of the picked candidate; all zero without a pick */
+    int32_t target, n_searched, n_found;  /* as hnet_keyframe_relocalise */
+    int32_t pad;                          /* written zero */
+} hnet_keyframe_relocalise_oriented;
+int  hnet_sessions_keyframe_relocalise_oriented(hnet_sessions* s, int n, const int32_t* ids, const hnet_keyframe_relocalise_opts* opts,
+                                                const hnet_photo_search_hyp* hyps, int n_hyp, hnet_keyframe_relocalise_oriented* out /* [n] */);
+
 int hnet_synchronize(hnet_ctx* ctx, void* stream);
 int hnet_last_timing(const hnet_ctx* ctx, hnet_timing* out);
 
