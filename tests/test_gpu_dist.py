@@ -46,6 +46,7 @@ def test_finish_on_the_gathered_layout_is_bitwise_the_finish_on_reordered_sample
     lv = gathered[:, 1].permute(1, 0, 2, 3).reshape(B, world * nl, 8).contiguous().to(dev)
     gd = gathered.contiguous().to(dev)
     o1, o2 = torch.zeros(B, 72, device=dev), torch.zeros(B, 72, device=dev)
+    torch.cuda.synchronize()                                          # torch's fills before the context's own stream writes the buffers
     eng = HnetEngine(blob, variant="full", mc_samples=world * nl, dropout_p=0.05, mc_seed=1, max_batch=B)
     eng.mc_finish_packed_device(ms.data_ptr(), lv.data_ptr(), world * nl, h1.data_ptr(), B, o1.data_ptr())
     eng.mc_finish_gathered_device(gd.data_ptr(), world, nl, h1.data_ptr(), B, o2.data_ptr())

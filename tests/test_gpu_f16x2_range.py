@@ -124,6 +124,7 @@ def test_device_entry_points_raise_the_overflow_flag(blob):
     i1, i2 = _pair(6)
     dev = torch.device("cuda", 0)
     mean, cov = torch.zeros(2, 8, device=dev), torch.zeros(2, 64, device=dev)
+    torch.cuda.synchronize()                                   # torch's fills before the context's own stream writes the buffers
     e = HnetEngine(blob, variant="full", mc_samples=4, dropout_p=0.05, mc_seed=1, max_batch=2, precision=PREC_F16X2)
     assert e.overflow_flag() == 0                              # the warm-up forward of hnet_create left it clear
     p_ok, c_ok = torch.from_numpy(np.stack([i1, i2])).to(dev), torch.from_numpy(np.stack([i2, i1])).to(dev)
@@ -137,6 +138,7 @@ def test_device_entry_points_raise_the_overflow_flag(blob):
     assert e.precision() == PREC_F16X2                         # the device path never switches the mode by itself
     # the sharded path ends in heads_fc2: same word
     ms, lv, h1 = torch.zeros(1, 4, 8, device=dev), torch.zeros(1, 4, 8, device=dev), torch.zeros(1, 9, device=dev)
+    torch.cuda.synchronize()
     e.infer_mc_partial_device(pb.data_ptr(), cb.data_ptr(), PIX_F32, None, 1, 0, ms.data_ptr(), lv.data_ptr(), h1.data_ptr())
     assert e.overflow_flag() == 1
     e.close()

@@ -19,6 +19,7 @@ def test_group_steps_equal_single_context_steps(blob, n_ctx, variant, n_mc, batc
     dp = prior.data_ptr() if variant != "full" else None
     kw = dict(variant=variant, mc_samples=n_mc, dropout_p=0.05, mc_seed=9, max_batch=batch)
     ref = torch.zeros(steps, batch, 72, device=dev)
+    torch.cuda.synchronize()                                   # torch's fill before the context's own stream writes the buffer
     e = HnetEngine(blob, **kw)
     for i in range(steps):
         e.infer_batch_packed_device(prev.data_ptr(), curr.data_ptr(), PIX_U8, dp, batch, 1000 * i, ref[i].data_ptr())
@@ -27,6 +28,7 @@ def test_group_steps_equal_single_context_steps(blob, n_ctx, variant, n_mc, batc
     g = HnetGroup(blob, n_ctx, **kw)
     assert g.n == n_ctx and len({g.stream(i) for i in range(n_ctx)}) == n_ctx and all(g.stream(i) for i in range(n_ctx))
     out = torch.zeros(steps, batch, 72, device=dev)
+    torch.cuda.synchronize()                                   # torch's fill before the members' streams write the buffer
     used = [g.infer_batch_packed_device(prev.data_ptr(), curr.data_ptr(), PIX_U8, dp, batch, 1000 * i, out[i].data_ptr()) for i in range(steps)]
     assert used == [i % n_ctx for i in range(steps)]
     # a consumer stream joined behind the members reads complete results without a host synchronisation in between

@@ -166,6 +166,7 @@ def test_last_arriver_split_k_many_repetitions_against_the_reduce_launches(blob,
         e = _engine_env(blob, env, **kw)
         n = reps if name == "last_arriver" else 3
         out = torch.zeros(n, batch, 72, device=dev)
+        torch.cuda.synchronize()                                   # torch's fill before the context's own stream writes the buffer
         for i in range(n):
             e.infer_batch_packed_device(prev.data_ptr(), curr.data_ptr(), PIX_U8, d_prior, batch, 5, out[i].data_ptr())
         e.synchronize()
@@ -174,7 +175,10 @@ def test_last_arriver_split_k_many_repetitions_against_the_reduce_launches(blob,
         e.close()
     o, h = got["last_arriver"]
     differ = [i for i in range(1, reps) if not np.array_equal(o[i], o[0])]
-    assert differ == [], f"{len(differ)} of {reps} forwards differ from the first (first at {differ[0]})"
+    rows = [o[i][b] for i in differ for b in range(batch) if not np.array_equal(o[i][b], o[0][b])]
+    zeroed = sum(1 for r in rows if not r.any())               # an all-zero row is a buffer overwritten after the forward; any other value is a wrong sum
+    assert differ == [], (f"{len(differ)} of {reps} forwards differ from the first (first at {differ[0]}): of the {len(rows)} differing rows {zeroed} are all zero "
+                          f"(a buffer overwritten) and {len(rows) - zeroed} hold other values (wrong sums)")
     o30, h30 = got["reduce_launches"]
     assert np.array_equal(h, h30)                                  # blocks 1 - 3: the same sums in the same order (HNET_CHAIN=0 on both sides: _engine_env below)
     assert np.abs(o[0][:, :8] - o30[0][:, :8]).max() < TOL_PX_PATHS      # (the heads' first FC of the latency path sums K in another order)
@@ -248,6 +252,7 @@ def test_tail_chains_many_forwards_back_to_back(blob):
     e = HnetEngine(blob, variant="full", mc_samples=16, dropout_p=0.05, mc_seed=3, max_batch=8, precision=3)
     reps, sizes = 500, (1, 8, 3, 1, 5)
     out = torch.zeros(reps, 8, 72, device=dev)
+    torch.cuda.synchronize()                                       # torch's fill before the context's own stream writes the buffer
     for i in range(reps):
         e.infer_batch_packed_device(prev.data_ptr(), curr.data_ptr(), PIX_U8, None, sizes[i % len(sizes)], 5, out[i].data_ptr())
     e.synchronize()

@@ -329,6 +329,7 @@ def test_mc_sharding_is_rank_invariant(blob, oracle):
         e = HnetEngine(blob, variant="full", mc_samples=n, dropout_p=0.05, mc_seed=MC_SEED, max_batch=2, mc_shard=(8 * r, 8 * r + 8))
         ms = torch.zeros(2, 8, 8, device=dev)
         lv = torch.zeros(2, 8, 8, device=dev)
+        torch.cuda.synchronize()                               # torch's fills before the context's own stream writes the buffers
         e.infer_mc_partial_device(tp.data_ptr(), tc.data_ptr(), PIX_U8, None, 2, 7, ms.data_ptr(), lv.data_ptr(), h1.data_ptr())
         e.synchronize()
         ms_all[:, 8 * r:8 * r + 8] = ms
@@ -336,6 +337,7 @@ def test_mc_sharding_is_rank_invariant(blob, oracle):
         shards.append(e)
     mean = torch.zeros(2, 8, device=dev)
     cov = torch.zeros(2, 64, device=dev)
+    torch.cuda.synchronize()                                   # the slice copies and the fills run on torch's stream, mc_finish_device on the context's
     full.mc_finish_device(ms_all.data_ptr(), lv_all.data_ptr(), n, h1.data_ptr(), 2, mean.data_ptr(), cov.data_ptr())
     full.synchronize()
     assert np.array_equal(mean.cpu().numpy(), mean_ref)
@@ -359,6 +361,7 @@ def test_device_resident_entry_point_and_timing(blob):
     tp, tc = torch.from_numpy(prev).to(dev), torch.from_numpy(curr).to(dev)
     mean = torch.zeros(4, 8, device=dev)
     cov = torch.zeros(4, 64, device=dev)
+    torch.cuda.synchronize()                                   # torch's fills before the context's own stream writes the buffers
     eng.infer_batch_device(tp.data_ptr(), tc.data_ptr(), PIX_U8, None, 4, 0, mean.data_ptr(), cov.data_ptr())
     eng.synchronize()
     assert np.array_equal(mean.cpu().numpy(), mean_h) and np.array_equal(cov.cpu().numpy().reshape(4, 8, 8), cov_h)

@@ -35,6 +35,7 @@ def _seqs_call(e, prev, curr, prior, seqs, want_err=False):
     sq = torch.from_numpy(np.asarray(seqs, dtype=np.uint64).view(np.int64).copy()).to(dev)
     out = torch.zeros(b, 72, device=dev)
     err = torch.zeros(b, 224, 320, device=dev) if want_err else None
+    torch.cuda.synchronize()                                   # torch's fills before the context's own stream writes the buffers
     e.infer_batch_seqs_packed_device(p.data_ptr(), c.data_ptr(), PIX_U8, pr.data_ptr() if pr is not None else None, b, sq.data_ptr(), out.data_ptr(),
                                      err.data_ptr() if want_err else None)
     e.synchronize()
@@ -51,6 +52,7 @@ def _packed_call(e, prev, curr, prior, seq0, want_err=False):
     pr = None if prior is None else torch.from_numpy(np.ascontiguousarray(prior, dtype=np.float32)).to(dev)
     out = torch.zeros(b, 72, device=dev)
     err = torch.zeros(b, 224, 320, device=dev) if want_err else None
+    torch.cuda.synchronize()                                   # torch's fills before the context's own stream writes the buffers
     e.infer_batch_packed_device(p.data_ptr(), c.data_ptr(), PIX_U8, pr.data_ptr() if pr is not None else None, b, seq0, out.data_ptr(),
                                 err.data_ptr() if want_err else None)
     e.synchronize()
