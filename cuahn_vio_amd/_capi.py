@@ -57,6 +57,7 @@ SYMBOLS = [
     "hnet_sessions_last_keyframe_device_ms",
     "hnet_keyframe_revisit_default_opts", "hnet_sessions_enable_keyframe_map", "hnet_sessions_keyframe_revisit", "hnet_sessions_keyframe_map_info",
     "hnet_sessions_get_map_keyframe",
+    "hnet_keyframe_recover_default_opts", "hnet_sessions_keyframe_track_recover",
 ]
 # hnet_filters_advance's status per listed session (include/hnet.h HNET_ADV_*)
 ADV_STEPPED, ADV_WAIT_IMU, ADV_WAIT_INIT, ADV_INITIALIZED, ADV_PROPAGATED, ADV_NO_FRAME = range(6)
@@ -398,6 +399,33 @@ def photo_search_table(hyps):
     return _np.ascontiguousarray(hyps, PHOTO_SEARCH_HYP_DTYPE).reshape(-1)
 
 
+# hnet_keyframe_recover: one record per listed session of a track with recovery (hnet_sessions_keyframe_track_recover): the track's record, whose flags may
+# hold KF_RECOVERED, and the oriented relocalise's (all zero but target = -2 for a session that was not lost)
+KF_RECOVERED = 2048
+KEYFRAME_RECOVER_DTYPE = _np.dtype([("track", KEYFRAME_TRACK_DTYPE), ("reloc", KEYFRAME_RELOC_ORIENTED_DTYPE)])
+assert KEYFRAME_RECOVER_DTYPE.itemsize == 1720 + 2040
+
+
+class KeyframeRecoverOpts(C.Structure):
+    """hnet_keyframe_recover_opts: the track's options and the relocalise's"""
+    _fields_ = [("track", KeyframeOpts), ("reloc", KeyframeRelocOpts)]
+
+
+assert C.sizeof(KeyframeRecoverOpts) == 88 + 120
+
+
+def keyframe_recover_opts(track=None, reloc=None):
+    """the defaults of hnet_keyframe_recover_default_opts with either block replaced: a KeyframeOpts / KeyframeRelocOpts as it is, or a dict in the keyword
+    form of keyframe_opts / keyframe_relocalise_opts"""
+    o = KeyframeRecoverOpts()
+    lib().hnet_keyframe_recover_default_opts(C.byref(o))
+    if track is not None:
+        o.track = track if isinstance(track, KeyframeOpts) else keyframe_opts(**track)
+    if reloc is not None:
+        o.reloc = reloc if isinstance(reloc, KeyframeRelocOpts) else keyframe_relocalise_opts(**reloc)
+    return o
+
+
 def photo_robust_marginal(rec):
     """hnet_photo_robust_marginal of one record -> (info8 [8, 8], grad8 [8]); ValueError when the brightness block has no Cholesky factor"""
     r = _np.ascontiguousarray(rec, PHOTO_ROBUST_DTYPE).reshape(1)
@@ -601,6 +629,9 @@ def lib():
     L.hnet_op_photo_search_oriented.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp]
     L.hnet_sessions_photo_search_oriented.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp]
     L.hnet_sessions_keyframe_relocalise_oriented.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp]
+    L.hnet_keyframe_recover_default_opts.argtypes = [C.POINTER(KeyframeRecoverOpts)]
+    L.hnet_keyframe_recover_default_opts.restype = None
+    L.hnet_sessions_keyframe_track_recover.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int, vp]
     L.hnet_last_photo_align_device_ms.restype = C.c_double
     L.hnet_photo_refine_default_opts.argtypes = [C.POINTER(PhotoRefineOpts)]
     L.hnet_photo_refine_default_opts.restype = None

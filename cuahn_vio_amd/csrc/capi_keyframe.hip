@@ -12,8 +12,12 @@
 // And the ORIENTED relocalisation (photo_search_oriented_dev.h, csrc/kernels_photo_search_oriented.hip): hnet_sessions_keyframe_relocalise_oriented
 // is the same call with the search under a table of orientation hypotheses; the thumbnails, the gather, the alignment and the attach are the same launches.
 // Its scratch is its own and allocated by its first call: kf->oreloc == nullptr until then.
+// And the RECOVERY inside the track (keyframe_recover_dev.h, csrc/kernels_keyframe_recover.hip): hnet_sessions_keyframe_track_recover is a track
+// whose LOST sessions are relocalised (oriented) before their re-key is committed, in one upload, one download and one synchronisation; every launch
+// of the track and of the relocalisation is the unchanged one but the decision, the thumbnails and a finish.  Its scratch is its own and allocated by
+// its first call: kf->recover == nullptr until then.
 #include "sessions_internal.h"
-#include "photo_search_oriented_dev.h"
+#include "keyframe_recover_dev.h"
 
 using namespace hnet;
 using namespace capi;
@@ -61,6 +65,9 @@ static_assert(sizeof(hnet_keyframe_relocalise_oriented) == sizeof(OrientedRelocR
               offsetof(hnet_keyframe_relocalise_oriented, target) == offsetof(OrientedRelocRec, target) &&
               offsetof(hnet_keyframe_relocalise_oriented, n_found) == offsetof(OrientedRelocRec, n_found),
               "hnet_keyframe_relocalise_oriented is 7r's record around the oriented search record");
+static_assert(sizeof(hnet_keyframe_recover) == sizeof(RecoverRec) && offsetof(hnet_keyframe_recover, reloc) == offsetof(RecoverRec, reloc) &&
+              sizeof(hnet_keyframe_recover_opts) == sizeof(RecoverOpts) && offsetof(hnet_keyframe_recover_opts, reloc) == offsetof(RecoverOpts, reloc) &&
+              (int)HNET_KF_RECOVERED == hnet_keyframe_recovery::RECOVERED, "hnet_keyframe_recover / _opts are the layouts of include/hnet_keyframe_recover.h");
 
 // the scratch of the relocalisation (allocated by the first hnet_sessions_keyframe_relocalise), for max_batch B and the largest map
 struct KeyReloc {
@@ -81,6 +88,7 @@ struct hnet_keyframes {
     KeyMap* map = nullptr;                     // the keyframe map or null: never enabled
     KeyReloc* reloc = nullptr;                 // the relocalisation's scratch or null: never called
     KeyReloc* oreloc = nullptr;                // the oriented relocalisation's scratch (the sections of OrientedScratch) or null: never called
+    KeyReloc* recover = nullptr;               // the track-with-recovery's scratch (the sections of RecoverScratch) or null: never called
     uint8_t* key = nullptr;                    // device [N][NPIX], zeroed at enable
     KeyState* state = nullptr;                 // device [N], zeroed at enable (has_key = 0)
     uint8_t* scratch = nullptr;                // device: the sections of KeyScratch
@@ -179,6 +187,37 @@ struct OrientedScratch {
     }
 };
 
+// the track-with-recovery's own scratch for max_batch B: the call's table {step | ids | curr slot | gap | (padding to 8 bytes) | hypotheses [64]},
+// OrientedScratch's sections, and per slot T1's stash, whether the relocalisation runs, the second commit's copy flag, whether T1 was restored, the second
+// store's map slot and the call's record.  The alignment's scratch, the start offsets, the track records and the first copy flags are the store's
+// (KeyScratch); the first store's map slots are the map's (MapScratch).
+size_t recover_ids_bytes(int n) { return (table_bytes(n) + 7) & ~(size_t)7; }
+size_t recover_table_bytes(int n, int n_hyp) { return recover_ids_bytes(n) + (size_t)n_hyp * sizeof(SearchHyp); }
+struct RecoverScratch {
+    int32_t *valid, *cand, *mslot, *attach, *active, *copy2, *redo, *store2; uint8_t *tab, *thumbs; SearchRec* hrec; OrientedRec* srec; OrientedRelocRec* rout;
+    RecoverStash* stash; RecoverRec* out; size_t bytes;
+    RecoverScratch(uint8_t* b, int B) {
+        size_t o = 0;
+        auto take = [&](size_t n) { uint8_t* p = b + o; o += (n + 255) & ~(size_t)255; return p; };
+        tab = take(recover_table_bytes(B, SEARCH_MAX_HYP));
+        thumbs = take((size_t)B * (RELOC_MAX_CANDIDATES + 1) * THUMB_BYTES);
+        valid = reinterpret_cast<int32_t*>(take((size_t)B * RELOC_MAX_CANDIDATES * sizeof(int32_t)));
+        hrec = reinterpret_cast<SearchRec*>(take((size_t)B * RELOC_MAX_CANDIDATES * SEARCH_MAX_HYP * sizeof(SearchRec)));
+        srec = reinterpret_cast<OrientedRec*>(take((size_t)B * RELOC_MAX_CANDIDATES * sizeof(OrientedRec)));
+        cand = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
+        mslot = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
+        attach = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
+        rout = reinterpret_cast<OrientedRelocRec*>(take((size_t)B * sizeof(OrientedRelocRec)));
+        stash = reinterpret_cast<RecoverStash*>(take((size_t)B * sizeof(RecoverStash)));
+        active = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
+        copy2 = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
+        redo = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
+        store2 = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
+        out = reinterpret_cast<RecoverRec*>(take((size_t)B * sizeof(RecoverRec)));
+        bytes = o;
+    }
+};
+
 void reloc_free(KeyReloc* r) {
     if (!r) return;
     if (r->scratch) (void)hipFree(r->scratch);
@@ -205,6 +244,7 @@ void keyframes_free(hnet_keyframes* k) {
     map_free(k->map);
     reloc_free(k->reloc);
     reloc_free(k->oreloc);
+    reloc_free(k->recover);
     if (k->key) (void)hipFree(k->key);
     if (k->state) (void)hipFree(k->state);
     if (k->scratch) (void)hipFree(k->scratch);
@@ -645,6 +685,130 @@ int hnet_sessions_keyframe_relocalise_oriented(hnet_sessions* s, int n, const in
     HIPCHK(c, hipEventElapsedTime(&ms, k->ev[0], k->ev[1]));
     k->ms = ms;
     memcpy(out, r->pin_out, (size_t)n * sizeof(OrientedRelocRec));
+    return HNET_OK;
+}
+
+void hnet_keyframe_recover_default_opts(hnet_keyframe_recover_opts* o) {
+    if (!o) return;
+    RecoverOpts d;
+    hnet_keyframe_recovery::default_opts(d);
+    memcpy(o, &d, sizeof d);
+}
+
+// hnet_sessions_keyframe_track with the oriented relocalisation of the LOST sessions inside it: ONE upload {step | ids | curr slot | gap | table}, the
+// launch sequence inside the store's own events, ONE download of the records [n], one synchronisation.  The track's and the relocalisation's launches act
+// on disjoint sessions after the first commit: the sessions that are not lost are committed by it and every candidate of theirs is absent from the
+// search; the lost ones hold T0 (no copy) until the finish.
+int hnet_sessions_keyframe_track_recover(hnet_sessions* s, int n, const int32_t* ids, const float* step_px, const hnet_keyframe_recover_opts* opts,
+                                         const hnet_photo_search_hyp* hyps, int n_hyp, hnet_keyframe_recover* out) {
+    const char* who = "hnet_sessions_keyframe_track_recover";
+    if (!s) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = s->ctx;
+    hnet_keyframes* k = s->kf;
+    if (!k) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": keyframes are not enabled (hnet_sessions_enable_keyframes)");
+    if (!out || !opts) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": opts / out");
+    int rc = photo_robust_check_opts(c, &opts->track.align, who);
+    if (rc != HNET_OK) return rc;
+    RecoverOpts o;
+    memcpy(&o, opts, sizeof o);
+    if (!hnet_keyframe::opts_valid(o.track))
+        return fail(c, HNET_ERR_INVALID_ARG,
+                    std::string(who) + ": opts.track: 1 <= levels <= 4, auto_rekey 0 / 1, max_age >= 0, 0 <= rekey_overlap <= 1, max_mse >= 0 and finite");
+    if ((rc = photo_robust_check_opts(c, &opts->reloc.align, who)) != HNET_OK) return rc;
+    if (!hnet_search::opts_valid(o.reloc.search))
+        return fail(c, HNET_ERR_INVALID_ARG, std::string(who) +
+                                                 ": opts.reloc.search: 0 <= radius_x <= 30, 0 <= radius_y <= 20, 16 <= min_overlap <= 1120, -1 <= min_score <= 1, 0 <= min_margin <= 2");
+    if (!hnet_keyframe_reloc::opts_valid(o.reloc))
+        return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": opts.reloc: 1 <= levels <= 4, 0 <= min_overlap <= 1, max_mse and max_closure_px >= 0 and finite");
+    o.reloc.pad = 0;
+    o.reloc.search.pad = 0;
+    SearchHyp identity;
+    if (!hyps && n_hyp == 0) {                 // the identity entry alone
+        hnet_search_oriented::make_hyp(0.0, 1.0, identity);
+        hyps = reinterpret_cast<const hnet_photo_search_hyp*>(&identity);
+        n_hyp = 1;
+    }
+    if ((rc = photo_search_check_table(c, hyps, n_hyp, who)) != HNET_OK) return rc;
+    if ((rc = sessions_check_ids(s, n, ids)) != HNET_OK) return rc;
+    for (int i = 0; i < n; i++)
+        if (s->st[ids[i]].count < 1) return fail(c, HNET_ERR_NOT_READY, std::string(who) + ": a listed session has no image");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    const int B = c->cfg.max_batch, N = s->n;
+    if (!k->recover) {                         // the first call: nothing is enqueued yet
+        KeyReloc* r = new KeyReloc();
+        hipError_t e = hipMalloc((void**)&r->scratch, RecoverScratch(nullptr, B).bytes);
+        if (e == hipSuccess) e = hipHostMalloc((void**)&r->pin_in, recover_table_bytes(B, SEARCH_MAX_HYP), hipHostMallocDefault);
+        if (e == hipSuccess) e = hipHostMalloc((void**)&r->pin_out, (size_t)B * sizeof(RecoverRec), hipHostMallocDefault);
+        if (e != hipSuccess) {
+            reloc_free(r);
+            return fail(c, HNET_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+        }
+        k->recover = r;
+    }
+    KeyReloc* r = k->recover;
+    const KeyScratch w(k->scratch, B);
+    const RecoverScratch rw(r->scratch, B);
+    const MapStore none = {nullptr, nullptr, nullptr, N, 0};
+    const MapStore& map = k->map ? k->map->dev : none;
+    const int M = map.capacity;                // 0 without a map
+    float* h_step = reinterpret_cast<float*>(r->pin_in);
+    int32_t* h_ids = reinterpret_cast<int32_t*>(h_step + (size_t)8 * n);
+    for (int i = 0; i < n; i++) {
+        const int id = ids[i];
+        for (int j = 0; j < 8; j++) h_step[8 * i + j] = step_px ? step_px[8 * i + j] : 0.0f;
+        h_ids[i] = id;
+        h_ids[n + i] = 2 * id + s->st[id].curr;
+        h_ids[2 * n + i] = k->has_key[id] && s->st[id].count != k->count_at_track[id] + 1 ? 1 : 0;
+    }
+    const size_t head = recover_ids_bytes(n), tabb = (size_t)n_hyp * sizeof(SearchHyp);
+    memset(r->pin_in + table_bytes(n), 0, head - table_bytes(n));
+    memcpy(r->pin_in + head, hyps, tabb);
+    const KeyTable tab = table_view(rw.tab, n);
+    const int32_t *d_ids = tab.ids, *d_slot = tab.slot;
+    const SearchHyp* d_hyps = reinterpret_cast<const SearchHyp*>(rw.tab + head);
+    const size_t pyr = (size_t)B * PYR_BYTES;
+    uint8_t *prev = (uint8_t*)c->stage_prev, *curr = (uint8_t*)c->stage_curr;
+    hipStream_t st = c->stream;
+    HIPCHK(c, hipMemcpyAsync(rw.tab, r->pin_in, head + tabb, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipEventRecord(k->ev[0], st));
+    // the track up to its decision, which is deferred for the lost sessions
+    HIPCHK(c, launch_keyframe_start(tab, n, N, k->state, w.x0, st));
+    HIPCHK(c, launch_keyframe_gather(tab, n, N, k->key, s->ring, 2 * N, prev, curr, st));
+    HIPCHK(c, launch_photo_align_robust(prev, curr, n, w.x0, o.track.align, o.track.levels, c->pyr_scratch, c->pyr_scratch + pyr, w.start, w.part, w.work, w.rec, st));
+    HIPCHK(c, launch_recover_decide(tab, n, N, w.rec, w.x0, o.track, k->state, w.out, w.copy, rw.stash, rw.active, st));
+    HIPCHK(c, launch_keyframe_commit(tab, n, N, w.copy, curr, k->key, st));
+    if (const KeyMap* m = k->map) {
+        const MapScratch mw(m->scratch, B);
+        HIPCHK(c, launch_keyframe_map_note(d_ids, n, w.out, w.copy, k->state, m->dev, mw.store, st));
+        HIPCHK(c, launch_keyframe_map_store(d_ids, n, mw.store, curr, m->dev, st));
+    }
+    // the oriented relocalisation of the lost sessions on T0's state; the others ride through on absent candidates and quiet-NaN starts
+    HIPCHK(c, launch_recover_thumbs(d_ids, d_slot, n, N, rw.active, k->state, k->key, map, s->ring, 2 * N, rw.thumbs, rw.valid, st));
+    HIPCHK(c, launch_photo_search_oriented(rw.thumbs, M + 2, M + 2, M + 1, M + 1, n, rw.valid, o.reloc.search, d_hyps, n_hyp, rw.hrec, nullptr, st));
+    HIPCHK(c, launch_photo_search_winner(rw.hrec, d_hyps, n_hyp, n * (M + 1), rw.valid, rw.srec, st));
+    HIPCHK(c, launch_reloc_pick_oriented(d_ids, n, N, k->state, M, rw.valid, rw.srec, w.x0, rw.cand, rw.mslot, rw.rout, st));
+    HIPCHK(c, launch_reloc_gather(d_ids, d_slot, n, N, rw.cand, k->key, map, s->ring, 2 * N, prev, curr, st));
+    HIPCHK(c, launch_photo_align_robust(prev, curr, n, w.x0, o.reloc.align, o.reloc.levels, c->pyr_scratch, c->pyr_scratch + pyr, w.start, w.part, w.work, w.rec, st));
+    HIPCHK(c, launch_reloc_decide_oriented(d_ids, n, N, w.rec, w.x0, rw.cand, o.reloc, k->state, map, rw.rout, rw.attach, st));
+    if (k->map) HIPCHK(c, launch_keyframe_map_attach(d_ids, n, rw.mslot, rw.attach, map, k->key, st));
+    // T0 | RECOVERED or T1, and T1's commit for the unrecovered sessions (curr still holds every slot's current frame)
+    HIPCHK(c, launch_recover_finish(d_ids, n, N, rw.active, rw.stash, rw.rout, k->state, w.out, rw.copy2, rw.redo, rw.out, st));
+    HIPCHK(c, launch_keyframe_commit(tab, n, N, rw.copy2, curr, k->key, st));
+    if (const KeyMap* m = k->map) {
+        HIPCHK(c, launch_recover_note(d_ids, n, w.out, rw.copy2, rw.redo, k->state, m->dev, rw.store2, st));
+        HIPCHK(c, launch_keyframe_map_store(d_ids, n, rw.store2, curr, m->dev, st));
+    }
+    HIPCHK(c, hipEventRecord(k->ev[1], st));
+    HIPCHK(c, hipMemcpyAsync(r->pin_out, rw.out, (size_t)n * sizeof(RecoverRec), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    float ms = 0;
+    HIPCHK(c, hipEventElapsedTime(&ms, k->ev[0], k->ev[1]));
+    k->ms = ms;
+    memcpy(out, r->pin_out, (size_t)n * sizeof(RecoverRec));
+    for (int i = 0; i < n; i++) {
+        k->has_key[ids[i]] = 1;
+        k->count_at_track[ids[i]] = s->st[ids[i]].count;
+    }
     return HNET_OK;
 }
 

@@ -772,6 +772,19 @@ class HnetSessions:
         self._check(self._L.hnet_sessions_keyframe_relocalise_oriented(self._s, n, ids.ctypes.data, C.addressof(o), h.ctypes.data, len(h), out.ctypes.data))
         return out
 
+    def keyframe_track_recover(self, ids, step_px=None, hyps=None, track=None, reloc=None):
+        """hnet_sessions_keyframe_track_recover: keyframe_track whose LOST sessions are relocalised (oriented; hyps as op_photo_search_oriented) before
+        their re-key is committed; a recovered session keeps its keyframe or is attached to a stored one and its track record holds KF_RECOVERED, an
+        unrecovered one gets keyframe_track's result -> [n] of _capi.KEYFRAME_RECOVER_DTYPE; track / reloc as _capi.keyframe_recover_opts"""
+        ids, n = self._ids(ids)
+        step = None if step_px is None else np.ascontiguousarray(step_px, dtype=np.float32).reshape(n, 8)
+        o = _capi.keyframe_recover_opts(track, reloc)
+        h = _capi.photo_search_table(hyps)
+        out = np.zeros(n, _capi.KEYFRAME_RECOVER_DTYPE)
+        self._check(self._L.hnet_sessions_keyframe_track_recover(self._s, n, ids.ctypes.data, step.ctypes.data if step is not None else None, C.addressof(o),
+                                                                 h.ctypes.data, len(h), out.ctypes.data))
+        return out
+
     def image_count(self, id):
         return int(self._L.hnet_sessions_image_count(self._s, int(id)))
 

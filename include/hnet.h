@@ -1039,6 +1039,37 @@ typedef struct hnet_keyframe_relocalise_oriented {
 int  hnet_sessions_keyframe_relocalise_oriented(hnet_sessions* s, int n, const int32_t* ids, const hnet_keyframe_relocalise_opts* opts,
                                                 const hnet_photo_search_hyp* hyps, int n_hyp, hnet_keyframe_relocalise_oriented* out /* [n] */);
 
+/* ---- sessions, recovering a lost camera INSIDE the track, before the bridge (csrc/kernels_keyframe_recover.hip; the shared code is
+ * include/hnet_keyframe_recover.h).  Opt-in: a program that never calls hnet_sessions_keyframe_track_recover allocates, launches and returns
+ * what it did before.  hnet_sessions_keyframe_track with auto_rekey commits its verdict in the same call: a LOST frame becomes the keyframe and the origin
+ * chain takes a link of dead reckoning, after which a relocalise finds the current frame on itself.  This call is that track with the oriented
+ * relocalisation run between the LOST verdict and its commit.  Callable after hnet_sessions_enable_keyframes, with or without a map; hyps == NULL with
+ * n_hyp == 0 is the identity entry alone.  Per listed session, independent of the other slots, with T1 = the track's decision under opts.track and T0 =
+ * the same under opts.track with auto_rekey = 0, both on the state before the call:
+ *   not LOST (HNET_KF_FIRST included): the state, `track`, the keyframe store and the map are exactly hnet_sessions_keyframe_track(opts.track)'s; `reloc`
+ *     is all zero except target = -2.
+ *   LOST: the session takes T0's state (the keyframe stays, key_px is the bridge, the age grows by one) and the map's note runs on T0's flags (a restart
+ *     invalidates the entries before they are searched); then hnet_sessions_keyframe_relocalise_oriented(opts.reloc, hyps) runs on that state against the
+ *     current frame exactly as it is, and `reloc` is its record byte for byte.
+ *     HNET_RL_RETRACKED or HNET_RL_ATTACHED: the state is what that call leaves (key_px = reloc.rv.key_px); `track` is T0's record with HNET_KF_RECOVERED
+ *       or-ed into flags: rec, start_px and the bridge in key_px are kept and show why the frame was lost.  No re-key is judged on a recovered frame: the
+ *       next track judges overlap and age.
+ *     HNET_RL_NO_CANDIDATE or a REJECTED reason: the state, `track`, the keyframe store and the map are exactly hnet_sessions_keyframe_track(opts.track)'s,
+ *       i.e. T1 formed from the state before the call, for either value of auto_rekey.
+ * The host bookkeeping moves as a track moves it: a relocalise or a revisit may follow at once.  Read-only for everything else, like a track.  Errors,
+ * nothing changed, written or enqueued: everything hnet_sessions_keyframe_track refuses, and the option and table refusals of
+ * hnet_sessions_keyframe_relocalise_oriented.  The first call allocates its scratch before anything is enqueued.  A call is ONE upload
+ * {step | ids | curr slot | gap | table}, the track's launches with the decision deferred, the relocalisation's launches with the candidates of the
+ * sessions that are not lost marked absent (those ride through on quiet-NaN starts), a finish, a second commit for the unrecovered sessions, ONE download
+ * and one synchronisation; hnet_sessions_last_keyframe_device_ms covers it. */
+enum { HNET_KF_RECOVERED = 2048 };
+typedef struct hnet_keyframe_recover_opts { hnet_keyframe_opts track; hnet_keyframe_relocalise_opts reloc; } hnet_keyframe_recover_opts;
+typedef struct hnet_keyframe_recover { hnet_keyframe_track track; hnet_keyframe_relocalise_oriented reloc; } hnet_keyframe_recover;
+void hnet_keyframe_recover_default_opts(hnet_keyframe_recover_opts* o);   /* the two defaults, and track.max_mse stays 0: the caller chooses it */
+int  hnet_sessions_keyframe_track_recover(hnet_sessions* s, int n, const int32_t* ids, const float* step_px /* [n][8] or NULL, as the track's */,
+                                          const hnet_keyframe_recover_opts* opts, const hnet_photo_search_hyp* hyps, int n_hyp,
+                                          hnet_keyframe_recover* out /* [n] */);
+
 int hnet_synchronize(hnet_ctx* ctx, void* stream);
 int hnet_last_timing(const hnet_ctx* ctx, hnet_timing* out);
 
