@@ -58,6 +58,8 @@ SYMBOLS = [
     "hnet_keyframe_revisit_default_opts", "hnet_sessions_enable_keyframe_map", "hnet_sessions_keyframe_revisit", "hnet_sessions_keyframe_map_info",
     "hnet_sessions_get_map_keyframe",
     "hnet_keyframe_recover_default_opts", "hnet_sessions_keyframe_track_recover",
+    "hnet_keyframe_measure_default_opts", "hnet_filters_set_keyframe_measure", "hnet_filters_last_keyframe_measure", "hnet_filters_keyframe_measure_stats",
+    "hnet_filters_reset_keyframe_measure_stats",
 ]
 # hnet_filters_advance's status per listed session (include/hnet.h HNET_ADV_*)
 ADV_STEPPED, ADV_WAIT_IMU, ADV_WAIT_INIT, ADV_INITIALIZED, ADV_PROPAGATED, ADV_NO_FRAME = range(6)
@@ -248,6 +250,54 @@ def keyframe_opts(**kw):
             setattr(o, k, v)
         else:
             raise TypeError(f"hnet_keyframe_opts has no field {k!r}")
+    return o
+
+
+# hnet_keyframe_measure: a session's in-step keyframe track as a filter measurement (hnet_filters_set_keyframe_measure): the track's record, the filter's
+# step, z_px, R_px, the measurement's innovation, flags KFM_* (include/hnet.h HNET_KFM_*)
+KEYFRAME_MEASURE_DTYPE = _np.dtype([("track", KEYFRAME_TRACK_DTYPE), ("step_px", "<f4", 8), ("z_px", "<f4", 8), ("r_px", "<f8", (8, 8)),
+                                    ("innov", INNOVATION_DTYPE), ("flags", "<i4"), ("pad", "<i4")])
+assert KEYFRAME_MEASURE_DTYPE.itemsize == 1720 + 64 + 512 + 144 + 8
+KFM_ALWAYS, KFM_IF_NONE = 0, 1
+KFM_ASKED, KFM_APPLIED, KFM_NIS_REJECTED, KFM_S_SINGULAR = 1, 2, 4, 8
+KFM_BAD_K_NET_COV, KFM_STOPPED, KFM_NO_STEP, KFM_MSE_ABOVE_MAX, KFM_NO_FACTOR, KFM_NON_FINITE = 16, 32, 64, 128, 256, 512
+KFM_FIRST, KFM_TRACK_LOST, KFM_TRACK_GAP, KFM_PREV_NOT_MEASURED, KFM_NO_INVERSE, KFM_NOT_SELECTED = 1024, 2048, 4096, 8192, 16384, 32768
+KFM_UNUSABLE = 16 | 32 | 64 | 128 | 256 | 512 | 1024 | 2048 | 4096 | 8192 | 16384
+
+
+class KeyframeMeasureOpts(C.Structure):
+    """hnet_keyframe_measure_opts: the in-step track's options (shared by the measuring sessions of a call), and per session the scale on
+    mse * inverse(info), the floor added to the diagonal (px), the largest usable mse (0: no limit) and when the measurement is applied"""
+    _fields_ = [("track", KeyframeOpts), ("cov_scale", C.c_double), ("sigma_floor_px", C.c_double), ("max_mse", C.c_double), ("when", C.c_int32),
+                ("pad", C.c_int32)]
+
+
+assert C.sizeof(KeyframeMeasureOpts) == 88 + 32
+
+
+class KeyframeMeasureStats(C.Structure):
+    """hnet_keyframe_measure_stats: measurements asked for, applied, unusable, refused by the NIS gate; sum and maximum of their NIS"""
+    _fields_ = [("asked", C.c_int64), ("applied", C.c_int64), ("unusable", C.c_int64), ("nis_rejected", C.c_int64), ("sum_nis", C.c_double), ("max_nis", C.c_double)]
+
+
+def keyframe_measure_opts(**kw):
+    """the defaults of hnet_keyframe_measure_default_opts (cov_scale = 0: the caller must choose it) with the given fields replaced: the track's by their
+    own names (its max_mse as track_max_mse), the measurement's cov_scale, sigma_floor_px, max_mse and when"""
+    o = KeyframeMeasureOpts()
+    lib().hnet_keyframe_measure_default_opts(C.byref(o))
+    for k, v in kw.items():
+        if k in ("max_iterations", "min_valid", "lambda0", "eps_px"):
+            setattr(o.track.align.base, k, v)
+        elif k in ("brightness", "huber_k", "gain0", "bias0"):
+            setattr(o.track.align, k, v)
+        elif k in ("levels", "auto_rekey", "max_age", "rekey_overlap"):
+            setattr(o.track, k, v)
+        elif k == "track_max_mse":
+            o.track.max_mse = v
+        elif k in ("cov_scale", "sigma_floor_px", "max_mse", "when"):
+            setattr(o, k, v)
+        else:
+            raise TypeError(f"hnet_keyframe_measure_opts has no field {k!r}")
     return o
 
 
@@ -639,6 +689,12 @@ def lib():
     L.hnet_filters_last_refine.argtypes = [vp, C.c_int, vp]
     L.hnet_filters_refine_stats.argtypes = [vp, C.c_int, C.POINTER(RefineStats)]
     L.hnet_filters_reset_refine_stats.argtypes = [vp, C.c_int]
+    L.hnet_keyframe_measure_default_opts.argtypes = [C.POINTER(KeyframeMeasureOpts)]
+    L.hnet_keyframe_measure_default_opts.restype = None
+    L.hnet_filters_set_keyframe_measure.argtypes = [vp, C.c_int, C.POINTER(KeyframeMeasureOpts)]
+    L.hnet_filters_last_keyframe_measure.argtypes = [vp, C.c_int, vp]
+    L.hnet_filters_keyframe_measure_stats.argtypes = [vp, C.c_int, C.POINTER(KeyframeMeasureStats)]
+    L.hnet_filters_reset_keyframe_measure_stats.argtypes = [vp, C.c_int]
     for name in SYMBOLS:
         getattr(L, name)   # AttributeError here = the library does not export what include/hnet.h declares
     _lib = L

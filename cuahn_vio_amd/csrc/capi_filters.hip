@@ -3,6 +3,7 @@
 // initialiser); the IEKF iterations of an attempt, the overflow test and the bookkeeping of an accepted call are one piece of code each, below.
 #include "sessions_internal.h"
 #include "filters_refine_dev.h"
+#include "filters_keyframe_dev.h"
 
 using namespace hnet;
 using namespace capi;
@@ -96,6 +97,18 @@ struct hnet_filters {
     uint8_t* d_refine_scratch = nullptr;       // RefineScratch
     std::vector<hnet_refine_stats> refine_stats;
     int last_refine_n = 0;                     // sessions the last accepted call has refine records for; 0: it ran without a refining session
+    // the keyframe track as an in-step measurement (hnet_filters_set_keyframe_measure), allocated by the first call that turns it on: the output
+    // block then also holds {kfm [n] KfmRec, dense} behind the refine records; per session the options (host: `track` decides a call's launch sequence)
+    // and what the kernels read of them; ONE zeroed scratch block (KfmScratch: the gathered frames, the measurement, the working copies of the keyframe
+    // state table and of the prev_ok words, and the prev_ok words themselves); the statistics
+    bool kfm = false;
+    size_t off_kfm = 0;
+    std::vector<hnet_keyframe_measure_opts> kfm_opts;
+    std::vector<uint8_t> kfm_on;
+    KfmCfg* d_kfm_cfg = nullptr;               // [n_sessions]
+    uint8_t* d_kfm_scratch = nullptr;          // KfmScratch
+    std::vector<hnet_keyframe_measure_stats> kfm_stats;
+    int last_kfm_n = 0;                        // sessions the last accepted call has measure records for; 0: it ran without a measuring session
 };
 // the sections of d_refine_scratch for max_batch B and N sessions
 struct RefineScratch {
@@ -115,6 +128,30 @@ struct RefineScratch {
         bytes = o;
     }
 };
+
+// the sections of d_kfm_scratch for max_batch B and N sessions
+struct KfmScratch {
+    uint8_t *prev, *curr; float *step, *prior_px, *m72; InnovRec* innov; int32_t *opened, *prev_ok, *prev_ok_work; KeyState* state_work; double* nis0; size_t bytes;
+    KfmScratch(uint8_t* b, int B, int N) {
+        size_t o = 0;
+        auto take = [&](size_t n) { uint8_t* p = b + o; o += (n + 255) & ~(size_t)255; return p; };
+        prev = take((size_t)B * NPIX);
+        curr = take((size_t)B * NPIX);
+        step = reinterpret_cast<float*>(take((size_t)B * 8 * sizeof(float)));
+        prior_px = reinterpret_cast<float*>(take((size_t)B * 8 * sizeof(float)));
+        m72 = reinterpret_cast<float*>(take((size_t)B * 72 * sizeof(float)));
+        innov = reinterpret_cast<InnovRec*>(take((size_t)B * sizeof(InnovRec)));
+        opened = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
+        prev_ok = reinterpret_cast<int32_t*>(take((size_t)N * sizeof(int32_t)));      // starts zero: never measured
+        prev_ok_work = reinterpret_cast<int32_t*>(take((size_t)N * sizeof(int32_t)));
+        state_work = reinterpret_cast<KeyState*>(take((size_t)N * sizeof(KeyState)));
+        nis0 = reinterpret_cast<double*>(take((size_t)N * sizeof(double)));           // stays zero: "no NIS gate" for a filters object without innovations
+        bytes = o;
+    }
+};
+// a call's keyframe measurement: the session whose track options serve it (-1: the call has no measuring session) and the {ids | curr slot | gap}
+// sections of the track's table on the device
+struct KfmCall { int ref; const int32_t* d_tab; };
 
 static size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
@@ -154,27 +191,29 @@ static void filters_drop_predict_cov(hnet_filters* f) {           // predict_cov
 
 extern "C" {
 
-// the offsets of the step's output block for max_batch B: {net | prior_px | updates | innov (if enabled) | photo (if enabled) | refine (if on) | work | results}
-static void filters_out_layout(hnet_filters* f, int B, bool innov, bool photo, bool refine) {
+// the offsets of the step's output block for max_batch B: {net | prior_px | updates | innov (if enabled) | photo (if enabled) | refine (if on) | kfm (if on) | work | results}
+static void filters_out_layout(hnet_filters* f, int B, bool innov, bool photo, bool refine, bool kfm) {
     f->off_prior = al256((size_t)f->iters * B * 72 * sizeof(float));
     f->off_upd = f->off_prior + al256((size_t)f->iters * B * 8 * sizeof(float));
     f->off_innov = f->off_upd + al256((size_t)B * sizeof(int32_t));
     f->off_photo = f->off_innov + (innov ? al256((size_t)f->iters * B * sizeof(InnovRec)) : 0);
     f->off_refine = f->off_photo + (photo ? al256((size_t)(2 + f->iters) * B * sizeof(PhotoRec)) : 0);
-    f->off_work = f->off_refine + (refine ? al256((size_t)B * sizeof(RefineRec)) : 0);
+    f->off_kfm = f->off_refine + (refine ? al256((size_t)B * sizeof(RefineRec)) : 0);
+    f->off_work = f->off_kfm + (kfm ? al256((size_t)B * sizeof(KfmRec)) : 0);
     f->off_res = f->off_work + al256((size_t)B * sizeof(FilterRec));
     f->out_bytes = f->off_res + (size_t)B * sizeof(AdvanceResult);
 }
 // the sections of the output block as typed pointers, on the device (d) and in the pinned copy (h)
-struct OutView { float *net, *prior; int32_t* upd; InnovRec* innov; PhotoRec* photo; RefineRec* refine; FilterRec* work; AdvanceResult* res; };
+struct OutView { float *net, *prior; int32_t* upd; InnovRec* innov; PhotoRec* photo; RefineRec* refine; KfmRec* kfm; FilterRec* work; AdvanceResult* res; };
 struct OutViews { OutView d, h; };
 static OutView filters_out_view(const hnet_filters* f, uint8_t* b) {
     return OutView{reinterpret_cast<float*>(b), reinterpret_cast<float*>(b + f->off_prior), reinterpret_cast<int32_t*>(b + f->off_upd), reinterpret_cast<InnovRec*>(b + f->off_innov),
-                   reinterpret_cast<PhotoRec*>(b + f->off_photo), reinterpret_cast<RefineRec*>(b + f->off_refine), reinterpret_cast<FilterRec*>(b + f->off_work), reinterpret_cast<AdvanceResult*>(b + f->off_res)};
+                   reinterpret_cast<PhotoRec*>(b + f->off_photo), reinterpret_cast<RefineRec*>(b + f->off_refine), reinterpret_cast<KfmRec*>(b + f->off_kfm), reinterpret_cast<FilterRec*>(b + f->off_work), reinterpret_cast<AdvanceResult*>(b + f->off_res)};
 }
 static OutViews filters_out_views(const hnet_filters* f) { return OutViews{filters_out_view(f, f->d_out), filters_out_view(f, f->pin_out)}; }
 // what a step of n stepping sessions downloads in one copy from the start of the output block when the states are not wanted: up to the last record section in use
-static size_t filters_down_head(const hnet_filters* f, int n, bool refining) {
+static size_t filters_down_head(const hnet_filters* f, int n, bool refining, bool measuring) {
+    if (measuring) return f->off_kfm + (size_t)n * sizeof(KfmRec);
     if (refining) return f->off_refine + (size_t)n * sizeof(RefineRec);
     if (f->photo) return f->off_photo + (size_t)n * (2 + f->iters) * sizeof(PhotoRec);
     if (f->innov) return f->off_innov + (size_t)f->iters * n * sizeof(InnovRec);
@@ -235,6 +274,46 @@ static void filters_count_refine(hnet_filters* f, int n, const int32_t* ids) {
         if (r.flags & HNET_REFINE_UNUSABLE) a.unusable++;
         if (r.flags & HNET_REFINE_NIS_REJECTED) a.nis_rejected++;
         if ((r.flags & (HNET_REFINE_APPLIED | HNET_REFINE_NIS_REJECTED)) && std::isfinite(r.nis)) {
+            a.sum_nis += r.nis;
+            if (r.nis > a.max_nis) a.max_nis = r.nis;
+        }
+    }
+}
+// whether the call in which the sessions ids[0 .. n) step runs the keyframe measurement: 1 when one of them has it on (*ref: such a session), -1 when two
+// of them differ in the track's options, -2 when one of the n sessions has refinement on as well (left open: DESIGN 7v), else 0
+static int filters_measuring(const hnet_filters* f, int n, const int32_t* ids, int* ref) {
+    *ref = -1;
+    if (!f->kfm) return 0;
+    int first = -1;
+    for (int j = 0; j < n; j++) {
+        const int id = ids[j];
+        if (!f->kfm_on[id]) continue;
+        if (first < 0) first = id;
+        else if (memcmp(&f->kfm_opts[id].track, &f->kfm_opts[first].track, sizeof(hnet_keyframe_opts)) != 0) return -1;
+    }
+    if (first < 0) return 0;
+    if (f->refine)
+        for (int j = 0; j < n; j++)
+            if (f->refine_on[ids[j]]) return -2;
+    *ref = first;
+    return 1;
+}
+static int filters_measuring_refused(hnet_ctx* c, int measuring, const char* who) {
+    return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + (measuring == -1 ? ": the sessions with the keyframe measurement on differ in the track's options (hnet_filters_set_keyframe_measure)"
+                                                                              : ": sessions with refinement on and sessions with the keyframe measurement on step in one call"));
+}
+// after an accepted call with measure records: the records [n] of the sessions ids[0 .. n) go into their statistics (include/hnet.h hnet_keyframe_measure_stats)
+static void filters_count_kfm(hnet_filters* f, int n, const int32_t* ids) {
+    const KfmRec* rec = filters_out_view(f, f->pin_out).kfm;
+    for (int j = 0; j < n; j++) {
+        const KfmRec& r = rec[j];
+        if (!(r.flags & HNET_KFM_ASKED)) continue;
+        hnet_keyframe_measure_stats& a = f->kfm_stats[ids[j]];
+        a.asked++;
+        if (r.flags & HNET_KFM_APPLIED) a.applied++;
+        if (r.flags & HNET_KFM_UNUSABLE) a.unusable++;
+        if (r.flags & HNET_KFM_NIS_REJECTED) a.nis_rejected++;
+        if ((r.flags & (HNET_KFM_APPLIED | HNET_KFM_NIS_REJECTED)) && std::isfinite(r.nis)) {
             a.sum_nis += r.nis;
             if (r.nis > a.max_nis) a.max_nis = r.nis;
         }
@@ -302,9 +381,13 @@ static int filters_flags(hnet_ctx* const ctx[2], uint32_t* flag, hipStream_t st)
 // every verdict word: a repeat re-forms them) - and nothing runs behind ev1.
 // refine_ref >= 0 (filters_refining said 1; photo_gated then holds): the call runs the photometric fallback with the alignment options of session refine_ref.
 // The last iteration's update then leaves the reset to the fallback's update launch, and filters_enqueue_refine follows inside the device window.
+// kfm.ref >= 0 (filters_measuring said 1; refine_ref is then -1): the call runs the keyframe measurement with the track options of session kfm.ref.  The
+// last iteration's update then runs with update_offset = 1 and leaves the reset to the measurement's update launch, and filters_enqueue_keyframe follows
+// inside the device window.
 static int filters_enqueue_refine(hnet_filters* f, hnet_ctx* c, const OutView& d, int n, const int32_t* d_ids, int32_t* d_gate, int refine_ref, hipStream_t st);
+static int filters_enqueue_keyframe(hnet_filters* f, hnet_ctx* c, const OutView& d, int n, const int32_t* d_ids, int32_t* d_gate, const KfmCall& kfm, hipStream_t st);
 static int filters_enqueue_iekf(hnet_filters* f, hnet_ctx* const ctx[2], const OutView& d, int n, const int32_t* d_ids, int32_t* d_gate, const uint64_t* d_seq,
-                                int seq_stride, bool photo_gated, int refine_ref, hipStream_t st) {
+                                int seq_stride, bool photo_gated, int refine_ref, const KfmCall& kfm, hipStream_t st) {
     hnet_ctx* c = ctx[0];
     const int I = f->iters, B = c->cfg.max_batch, N = f->s->n;
     for (int it = 0; it < I && n; it++) {
@@ -322,10 +405,13 @@ static int filters_enqueue_iekf(hnet_filters* f, hnet_ctx* const ctx[2], const O
         if (f->innov)
             HIPCHK(c, launch_filter_innovation(d_ids, n, N, f->d_params, d.work, net_it, f->d_prior_cam, f->d_max_nis, d_gate, d.upd, it, d.innov,
                                                photo_gated ? f->d_photo_verdict : nullptr, st));
-        HIPCHK(c, launch_filter_update(d_ids, n, N, f->d_params, net_it, f->d_prior_cam, d_gate, it != I - 1, it == I - 1 && refine_ref < 0, d.work, d.upd, st));
+        HIPCHK(c, launch_filter_update(d_ids, n, N, f->d_params, net_it, f->d_prior_cam, d_gate, it != I - 1 || kfm.ref >= 0, it == I - 1 && refine_ref < 0 && kfm.ref < 0,
+                                       d.work, d.upd, st));
     }
     if (refine_ref >= 0 && n)
         if (const int r = filters_enqueue_refine(f, c, d, n, d_ids, d_gate, refine_ref, st); r != HNET_OK) return r;
+    if (kfm.ref >= 0 && n)
+        if (const int r = filters_enqueue_keyframe(f, c, d, n, d_ids, d_gate, kfm, st); r != HNET_OK) return r;
     HIPCHK(c, hipEventRecord(f->ev1, st));
     if (f->photo && n && !photo_gated) HIPCHK(c, filters_launch_photo(f, d, n, st));
     return HNET_OK;
@@ -351,6 +437,40 @@ static int filters_enqueue_refine(hnet_filters* f, hnet_ctx* c, const OutView& d
     HIPCHK(c, launch_filter_refine_finish(n, w.innov, d.upd, f->iters, d.refine, st));
     return HNET_OK;
 }
+// The keyframe measurement of a call's n stepping sessions, behind the last iteration's update (which ran with update_offset = 1 and last = 0): the
+// filter's step into the track's table, the track's launches up to decide (capi_keyframe.hip: the keyframe gathered into the feature's own buffers,
+// decide on a working copy of the state table; slots that do not measure carry id -1 and NaN steps: early returns), the measurement (it opens d_gate
+// for the usable selected slots and closes it for every other), then the filter's own prior, innovation and update launches on it - the update with
+// update_offset = 0 and last = 1: the reset every slot is still owed - and what became of it.  Nothing here writes the keyframe store, the map or the
+// prev_ok words: filters_commit_keyframe does, once the attempt is accepted.
+static int filters_enqueue_keyframe(hnet_filters* f, hnet_ctx* c, const OutView& d, int n, const int32_t* d_ids, int32_t* d_gate, const KfmCall& kfm, hipStream_t st) {
+    const int B = c->cfg.max_batch, N = f->s->n;
+    const KfmScratch w(f->d_kfm_scratch, B, N);
+    KeyOpts ko;
+    memcpy(&ko, &f->kfm_opts[kfm.ref].track, sizeof ko);
+    const KeyTable tab{w.step, kfm.d_tab, kfm.d_tab + n, kfm.d_tab + 2 * (size_t)n};
+    capi::KeyInstep v;
+    HIPCHK(c, launch_filter_kfm_step(d_ids, n, N, f->d_kfm_cfg, d.work, w.step, d.kfm, st));
+    if (const int r = capi::keyframes_instep_track(f->s, tab, n, ko, w.prev, w.curr, w.state_work, &v, st); r != HNET_OK) return r;
+    HIPCHK(c, hipMemcpyAsync(w.prev_ok_work, w.prev_ok, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+    HIPCHK(c, launch_filter_kfm_measure(d_ids, n, N, f->d_params, f->d_kfm_cfg, v.state, w.prev_ok, v.out, v.rec, ko.levels, d.upd, w.m72, d_gate, w.opened, d.kfm, st));
+    HIPCHK(c, launch_filter_prior(d.work, n, w.prior_px, f->d_prior_cam, st));
+    HIPCHK(c, launch_filter_innovation(d_ids, n, N, f->d_params, d.work, w.m72, f->d_prior_cam, f->innov ? f->d_max_nis : w.nis0, d_gate, d.upd, 0, w.innov, nullptr, st));
+    HIPCHK(c, launch_filter_update(d_ids, n, N, f->d_params, w.m72, f->d_prior_cam, d_gate, 0, 1, d.work, d.upd, st));
+    HIPCHK(c, launch_filter_kfm_finish(d_ids, n, N, w.innov, d.upd, w.opened, f->iters, w.prev_ok_work, d.kfm, st));
+    return HNET_OK;
+}
+// the tail of an ACCEPTED call with a keyframe measurement, stream ordered behind the attempt and not synchronised: the track's commits (the state
+// table, the new keyframes' images, the map's note and store) and the prev_ok words; then the keyframe layer's host mirrors
+static int filters_commit_keyframe(hnet_filters* f, hnet_ctx* c, int n, const int32_t* ids, const KfmCall& kfm, hipStream_t st) {
+    const int B = c->cfg.max_batch, N = f->s->n;
+    const KfmScratch w(f->d_kfm_scratch, B, N);
+    const KeyTable tab{w.step, kfm.d_tab, kfm.d_tab + n, kfm.d_tab + 2 * (size_t)n};
+    if (const int r = capi::keyframes_instep_commit(f->s, tab, n, w.curr, w.state_work, st); r != HNET_OK) return r;
+    HIPCHK(c, hipMemcpyAsync(w.prev_ok, w.prev_ok_work, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+    capi::keyframes_instep_accepted(f->s, n, ids, f->kfm_on.data());
+    return HNET_OK;
+}
 // an overflow of the fp16 planes among the downloaded outputs of n stepping sessions: the first forward with a non-finite output had finite inputs (its
 // fp32 priors; later priors follow from it).  -> the index in ctx of the context to repair, -1: none
 static int filters_overflowed(const hnet_filters* f, hnet_ctx* const ctx[2], const OutView& h, int n) {
@@ -362,7 +482,8 @@ static int filters_overflowed(const hnet_filters* f, hnet_ctx* const ctx[2], con
     return -1;
 }
 // the bookkeeping of an accepted call in which the sessions ids[0 .. n) stepped: what the last_* calls describe, the innovation statistics, the timing
-static int filters_accepted(hnet_filters* f, int n, const int32_t* ids, const int32_t* ref_gate, bool refining, std::chrono::steady_clock::time_point t0, int n_inferences) {
+static int filters_accepted(hnet_filters* f, int n, const int32_t* ids, const int32_t* ref_gate, bool refining, bool measuring, std::chrono::steady_clock::time_point t0,
+                            int n_inferences) {
     f->last_n = n;
     f->last_innov_n = f->innov ? n : 0;
     f->last_photo_n = f->photo ? n : 0;
@@ -370,6 +491,8 @@ static int filters_accepted(hnet_filters* f, int n, const int32_t* ids, const in
     if (f->photo) filters_count_photo(f, n, ids, ref_gate);
     f->last_refine_n = refining ? n : 0;
     if (refining) filters_count_refine(f, n, ids);
+    f->last_kfm_n = measuring ? n : 0;
+    if (measuring) filters_count_kfm(f, n, ids);
     float ms = 0;
     HIPCHK(f->s->ctx, hipEventElapsedTime(&ms, f->ev0, f->ev1));
     record_timing(f->timing, ms, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), n_inferences, true);
@@ -412,7 +535,7 @@ void hnet_destroy_filters(hnet_filters* f) {
     hnet_ctx* c = f->s->ctx;
     (void)hipSetDevice(c->cfg.device_id);
     (void)hipStreamSynchronize(c->stream);
-    drop_dev(f->d_state); drop_dev(f->d_params); drop_dev(f->d_out); drop_dev(f->d_prior_cam); drop_dev(f->d_in); drop_dev(f->d_feed); drop_dev(f->d_max_nis); drop_dev(f->d_photo_part); drop_dev(f->d_photo_gate); drop_dev(f->d_photo_verdict); drop_dev(f->d_refine_cfg); drop_dev(f->d_refine_scratch);
+    drop_dev(f->d_state); drop_dev(f->d_params); drop_dev(f->d_out); drop_dev(f->d_prior_cam); drop_dev(f->d_in); drop_dev(f->d_feed); drop_dev(f->d_max_nis); drop_dev(f->d_photo_part); drop_dev(f->d_photo_gate); drop_dev(f->d_photo_verdict); drop_dev(f->d_refine_cfg); drop_dev(f->d_refine_scratch); drop_dev(f->d_kfm_cfg); drop_dev(f->d_kfm_scratch);
     drop_pin(f->pin_feed); drop_pin(f->pin_out); drop_pin(f->pin_in);
     drop_event(f->ev0); drop_event(f->ev1);
     filters_drop_feed(f);
@@ -435,7 +558,7 @@ int hnet_create_filters(hnet_sessions* s, int max_iekf_iteration, hnet_filters**
     f->t.assign(N, 0.0);
     f->cam_imu_dt.assign(N, dp.cam_imu_dt);
     f->imu_avg.assign(N, dp.imu_avg);
-    filters_out_layout(f, B, false, false, false);
+    filters_out_layout(f, B, false, false, false, false);
     f->t_seen.assign(N, -INFINITY);
     f->inited.assign(N, 0);
     f->last_slot.assign(N, -1);
@@ -516,6 +639,9 @@ int hnet_filters_step(hnet_filters* f, int n, const int32_t* ids, const double* 
     const int refining = filters_refining(f, n, ids, &refine_ref);
     if (refining < 0) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_step: the sessions with refinement on differ in align / levels (hnet_filters_set_photo_refine)");
     if (!refining) refine_ref = -1;
+    int kfm_ref = -1;
+    const int measuring = filters_measuring(f, n, ids, &kfm_ref);
+    if (measuring < 0) return filters_measuring_refused(c, measuring, "hnet_filters_step");
     for (int i = 0; i < n; i++) {
         if (!(t_frame[i] > f->t[ids[i]]) || !std::isfinite(t_frame[i]))
             return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_step: t_frame must be later than the state's time (Propagator.cpp:32-43)");
@@ -531,7 +657,8 @@ int hnet_filters_step(hnet_filters* f, int n, const int32_t* ids, const double* 
     for (int i = 0; i < n; i++) total += imu_off[i + 1] - imu_off[i] + 2;
     const size_t o_t = al256((size_t)total * sizeof(hnet_ekf::ImuData)), o_seq = o_t + al256((size_t)n * 8), o_ids = o_seq + al256((size_t)I * n * 8);
     const size_t o_gate = o_ids + al256((size_t)n * 4), o_pairs = o_gate + al256((size_t)n * 4), o_off = o_pairs + al256((size_t)n * 8);
-    const size_t in_bytes = o_off + al256((size_t)(n + 1) * 4);
+    const size_t o_kf = o_off + al256((size_t)(n + 1) * 4);                          // (with a measuring session: the track's {ids | curr slot | gap} behind the rest)
+    const size_t in_bytes = o_kf + (measuring ? al256((size_t)n * 12) : 0);
     if ((rc = grow_block(c, &f->pin_in, &f->d_in, &f->in_cap, in_bytes)) != HNET_OK) return rc;
     hnet_ekf::ImuData* rd = reinterpret_cast<hnet_ekf::ImuData*>(f->pin_in);
     double* tf = reinterpret_cast<double*>(f->pin_in + o_t);
@@ -555,6 +682,8 @@ int hnet_filters_step(hnet_filters* f, int n, const int32_t* ids, const double* 
         sessions_pair(s, id, pairs + 2 * i);
     }
     roff[n] = R;
+    if (measuring) capi::keyframes_instep_table(s, n, ids, f->kfm_on.data(), reinterpret_cast<int32_t*>(f->pin_in + o_kf));
+    const KfmCall kfm{kfm_ref, reinterpret_cast<const int32_t*>(f->d_in + o_kf)};
     const hnet_ekf::ImuData* d_rd = reinterpret_cast<const hnet_ekf::ImuData*>(f->d_in);
     const double* d_tf = reinterpret_cast<const double*>(f->d_in + o_t);
     const uint64_t* d_seq = reinterpret_cast<const uint64_t*>(f->d_in + o_seq);
@@ -564,9 +693,9 @@ int hnet_filters_step(hnet_filters* f, int n, const int32_t* ids, const double* 
     const int32_t* d_roff = reinterpret_cast<const int32_t*>(f->d_in + o_off);
     const OutViews o = filters_out_views(f);
     // the output block is laid out for max_batch: download the used parts of each section in one copy up to the last one needed
-    const size_t down = state_out ? f->off_work + (size_t)n * sizeof(FilterRec) : filters_down_head(f, n, refining > 0);
+    const size_t down = state_out ? f->off_work + (size_t)n * sizeof(FilterRec) : filters_down_head(f, n, refining > 0, measuring > 0);
     hipStream_t st = c->stream;
-    const size_t up = o_off + (size_t)(n + 1) * 4;
+    const size_t up = measuring ? o_kf + (size_t)n * 12 : o_off + (size_t)(n + 1) * 4;
     hnet_ctx* const ctx[2] = {c, filters_iter_ctx(f)};
     const bool photo_gated = filters_photo_gated(f, n, ids);
     auto enqueue = [&](uint32_t* flag_now) -> int {
@@ -575,13 +704,15 @@ int hnet_filters_step(hnet_filters* f, int n, const int32_t* ids, const double* 
         HIPCHK(c, hipEventRecord(f->ev0, st));
         HIPCHK(c, launch_session_gather(s->ring, 2 * s->n, d_pairs, n, (uint8_t*)c->stage_prev, (uint8_t*)c->stage_curr, st));
         HIPCHK(c, launch_filter_propagate(d_ids, n, s->n, f->d_state, f->d_params, d_rd, d_roff, d_tf, o.d.work, st));
-        if (const int r = filters_enqueue_iekf(f, ctx, o.d, n, d_ids, d_gate, d_seq, n, photo_gated, refine_ref, st); r != HNET_OK) return r;
+        if (const int r = filters_enqueue_iekf(f, ctx, o.d, n, d_ids, d_gate, d_seq, n, photo_gated, refine_ref, kfm, st); r != HNET_OK) return r;
         HIPCHK(c, hipMemcpyAsync(f->pin_out, f->d_out, down, hipMemcpyDeviceToHost, st));
         return filters_flags(ctx, flag_now, st);
     };
     if ((rc = run_host_call(ctx, enqueue, [&] { return filters_overflowed(f, ctx, o.h, n); })) != HNET_OK) return rc;
     // accepted: the listed states take the step's result (stream order: later calls see it), the bookkeeping advances
     HIPCHK(c, launch_filter_scatter(o.d.work, d_ids, n, s->n, f->d_state, st));
+    if (measuring)
+        if ((rc = filters_commit_keyframe(f, c, n, ids, kfm, st)) != HNET_OK) return rc;
     for (int i = 0; i < n; i++) {
         f->t[ids[i]] = t_frame[i];
         s->st[ids[i]].seq += (uint64_t)I;
@@ -590,7 +721,7 @@ int hnet_filters_step(hnet_filters* f, int n, const int32_t* ids, const double* 
         for (int it = 0; it < I; it++) memcpy(net_out + (size_t)it * n * 72, o.h.net + (size_t)it * c->cfg.max_batch * 72, (size_t)n * 72 * sizeof(float));
     if (updates) memcpy(updates, o.h.upd, (size_t)n * sizeof(int32_t));
     if (state_out) memcpy(state_out, o.h.work, (size_t)n * sizeof(FilterRec));
-    return filters_accepted(f, n, ids, gate, refining > 0, t0, I);
+    return filters_accepted(f, n, ids, gate, refining > 0, measuring > 0, t0, I);
 }
 
 int hnet_filters_last_priors(const hnet_filters* f, int n, float* out) {
@@ -623,13 +754,14 @@ void hnet_filter_default_init_params(hnet_init_params* p) {
 static InitParams init_params_dev(const hnet_init_params& p) { return InitParams{p.window_time, p.imu_thresh, p.init_height, p.wait_for_jerk ? 1 : 0, 0}; }
 // the advance input block for n sessions: jobs | seq [iters][n] | gate | ids | pairs
 struct AdvLayout {
-    size_t o_seq, o_gate, o_ids, o_pairs, bytes;
+    size_t o_seq, o_gate, o_ids, o_pairs, o_kf, bytes;        // (o_kf: the track's {ids | curr slot | gap} of a call with a measuring session, uploaded only then)
     AdvLayout(int n, int iters) {
         o_seq = al256((size_t)n * sizeof(AdvanceJob));
         o_gate = o_seq + al256((size_t)iters * n * 8);
         o_ids = o_gate + al256((size_t)n * 4);
         o_pairs = o_ids + al256((size_t)n * 4);
-        bytes = o_pairs + al256((size_t)n * 8);
+        o_kf = o_pairs + al256((size_t)n * 8);
+        bytes = o_kf + al256((size_t)n * 12);
     }
 };
 
@@ -778,11 +910,15 @@ int hnet_filters_advance(hnet_filters* f, int n, const int32_t* ids, hnet_filter
     const int refining = filters_refining(f, n_s, stepping.data(), &refine_ref);
     if (refining < 0) return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_advance: the sessions with refinement on differ in align / levels (hnet_filters_set_photo_refine)");
     if (!refining) refine_ref = -1;
+    int kfm_ref = -1;
+    const int measuring = filters_measuring(f, n_s, stepping.data(), &kfm_ref);
+    if (measuring < 0) return filters_measuring_refused(c, measuring, "hnet_filters_advance");
     if (net_out) memset(net_out, 0, (size_t)I * n * 72 * sizeof(float));
     if (updates) memset(updates, 0, (size_t)n * sizeof(int32_t));
     std::fill(f->last_slot.begin(), f->last_slot.end(), -1);
     f->last_photo_n = 0;                                           // (a call in which nothing steps has no photometric records, whatever the call before it left)
     f->last_refine_n = 0;
+    f->last_kfm_n = 0;
     if (n_a == 0) return HNET_OK;
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
     const AdvLayout L(n_a, I);
@@ -803,6 +939,8 @@ int hnet_filters_advance(hnet_filters* f, int n, const int32_t* ids, hnet_filter
         hid[j] = id;
         sessions_pair(s, id, pairs + 2 * j);
     }
+    if (measuring) capi::keyframes_instep_table(s, n_s, stepping.data(), f->kfm_on.data(), reinterpret_cast<int32_t*>(f->pin_adv + L.o_kf));
+    const KfmCall kfm{kfm_ref, reinterpret_cast<const int32_t*>(f->d_adv + L.o_kf)};
     const AdvanceJob* d_job = reinterpret_cast<const AdvanceJob*>(f->d_adv);
     const uint64_t* d_seq = reinterpret_cast<const uint64_t*>(f->d_adv + L.o_seq);
     int32_t* d_gate = reinterpret_cast<int32_t*>(f->d_adv + L.o_gate);
@@ -815,7 +953,7 @@ int hnet_filters_advance(hnet_filters* f, int n, const int32_t* ids, hnet_filter
     hnet_ctx* const ctx[2] = {c, n_s ? filters_iter_ctx(f) : nullptr};
     const bool photo_gated = filters_photo_gated(f, n_s, hid);
     auto enqueue = [&](uint32_t* flag_now) -> int {
-        HIPCHK(c, hipMemcpyAsync(f->d_adv, f->pin_adv, L.bytes, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(f->d_adv, f->pin_adv, measuring ? L.o_kf + (size_t)n_s * 12 : L.o_kf, hipMemcpyHostToDevice, st));
         HIPCHK(c, hipMemsetAsync(o.d.upd, 0, (size_t)n_a * sizeof(int32_t), st));
         HIPCHK(c, hipEventRecord(f->ev0, st));
         if (any_init)                                              // (the sessions without a state are among the propagate-only ones)
@@ -823,8 +961,8 @@ int hnet_filters_advance(hnet_filters* f, int n, const int32_t* ids, hnet_filter
         HIPCHK(c, launch_filter_select(d_job, n_a, s->n, f->cap, f->d_ring, f->d_meta, f->d_state, d_work, f->d_sel, d_res, st));
         if (n_s) HIPCHK(c, launch_session_gather(s->ring, 2 * s->n, d_pairs, n_s, (uint8_t*)c->stage_prev, (uint8_t*)c->stage_curr, st));
         HIPCHK(c, launch_filter_propagate_adv(d_job, n_a, s->n, f->cap, f->d_state, f->d_params, f->d_sel, d_res, d_work, st));
-        if (const int r = filters_enqueue_iekf(f, ctx, o.d, n_s, d_ids, d_gate, d_seq, n_a, photo_gated, refine_ref, st); r != HNET_OK) return r;     // (the sequence table has a row of n_a per iteration)
-        if (n_s) HIPCHK(c, hipMemcpyAsync(f->pin_out, f->d_out, filters_down_head(f, n_s, refining > 0), hipMemcpyDeviceToHost, st));
+        if (const int r = filters_enqueue_iekf(f, ctx, o.d, n_s, d_ids, d_gate, d_seq, n_a, photo_gated, refine_ref, kfm, st); r != HNET_OK) return r;     // (the sequence table has a row of n_a per iteration)
+        if (n_s) HIPCHK(c, hipMemcpyAsync(f->pin_out, f->d_out, filters_down_head(f, n_s, refining > 0, measuring > 0), hipMemcpyDeviceToHost, st));
         if (state_out) HIPCHK(c, hipMemcpyAsync(f->pin_out + f->off_work, d_work, (size_t)n_a * sizeof(FilterRec), hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipMemcpyAsync(f->pin_out + f->off_res, d_res, (size_t)n_a * sizeof(AdvanceResult), hipMemcpyDeviceToHost, st));
         return filters_flags(ctx, flag_now, st);
@@ -832,6 +970,8 @@ int hnet_filters_advance(hnet_filters* f, int n, const int32_t* ids, hnet_filter
     if ((rc = run_host_call(ctx, enqueue, [&] { return filters_overflowed(f, ctx, o.h, n_s); })) != HNET_OK) return rc;
     // accepted: the states take the results (not those the initialiser refused), the bookkeeping advances
     HIPCHK(c, launch_filter_scatter_ok(d_work, d_job, d_res, n_a, s->n, f->d_state, st));
+    if (measuring)
+        if ((rc = filters_commit_keyframe(f, c, n_s, stepping.data(), kfm, st)) != HNET_OK) return rc;
     const AdvanceResult* h_res = o.h.res;
     for (int j = 0; j < n_a; j++) {
         const int i = order[j], id = ids[i];
@@ -861,7 +1001,7 @@ int hnet_filters_advance(hnet_filters* f, int n, const int32_t* ids, hnet_filter
         }
         if (state_out) memcpy(state_out + i, o.h.work + j, sizeof(FilterRec));
     }
-    return filters_accepted(f, n_s, hid, gate, refining > 0, t_begin, n_s ? I : 0);     // (the stepping sessions are the first n_s of the call's id table)
+    return filters_accepted(f, n_s, hid, gate, refining > 0, measuring > 0, t_begin, n_s ? I : 0);     // (the stepping sessions are the first n_s of the call's id table)
 }
 
 int hnet_filters_last_selection(hnet_filters* f, int id, hnet_imu* out, int cap, int* count) {
@@ -894,12 +1034,12 @@ static_assert((int)HNET_INNOV_NONE == (int)hnet_ekf::INNOV_NONE && (int)HNET_INN
 // The output block with room for another kind of record: a new device block and pinned copy laid out for (innov, photo) and `extra_bytes` of zeroed device
 // memory (*extra: the gates start open; the partials are scratch), the old blocks freed only when everything is there.  On failure the layout is the old
 // one again and nothing of the object has changed.
-static int filters_relayout(hnet_filters* f, bool innov, bool photo, bool refine, const char* who, void** extra, size_t extra_bytes) {
+static int filters_relayout(hnet_filters* f, bool innov, bool photo, bool refine, bool kfm, const char* who, void** extra, size_t extra_bytes) {
     hnet_ctx* c = f->s->ctx;
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
     HIPCHK(c, hipStreamSynchronize(c->stream));                    // (nothing enqueued reads the old output block any more)
     const int B = c->cfg.max_batch;
-    filters_out_layout(f, B, innov, photo, refine);
+    filters_out_layout(f, B, innov, photo, refine, kfm);
     uint8_t *d_out = nullptr, *pin_out = nullptr;
     void* d_extra = nullptr;
     hipError_t e = hipMalloc((void**)&d_out, f->out_bytes);
@@ -909,7 +1049,7 @@ static int filters_relayout(hnet_filters* f, bool innov, bool photo, bool refine
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) {
         drop_dev(d_out); drop_pin(pin_out); drop_dev(d_extra);
-        filters_out_layout(f, B, f->innov, f->photo, f->refine);
+        filters_out_layout(f, B, f->innov, f->photo, f->refine, f->kfm);
         return fail(c, HNET_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
     }
     (void)hipFree(f->d_out);
@@ -921,6 +1061,7 @@ static int filters_relayout(hnet_filters* f, bool innov, bool photo, bool refine
     f->last_innov_n = 0;
     f->last_photo_n = 0;
     f->last_refine_n = 0;
+    f->last_kfm_n = 0;
     std::fill(f->last_slot.begin(), f->last_slot.end(), -1);
     return HNET_OK;
 }
@@ -929,7 +1070,7 @@ int hnet_filters_enable_innovations(hnet_filters* f) {
     if (!f) return HNET_ERR_INVALID_ARG;
     if (f->innov) return fail(f->s->ctx, HNET_ERR_INVALID_ARG, "hnet_filters_enable_innovations: already enabled");
     const int N = f->s->n;
-    const int rc = filters_relayout(f, true, f->photo, f->refine, "hnet_filters_enable_innovations", (void**)&f->d_max_nis, (size_t)N * sizeof(double));
+    const int rc = filters_relayout(f, true, f->photo, f->refine, f->kfm, "hnet_filters_enable_innovations", (void**)&f->d_max_nis, (size_t)N * sizeof(double));
     if (rc != HNET_OK) return rc;
     f->innov_stats.assign(N, hnet_innovation_stats{0, 0, 0, 0.0, 0.0});
     f->innov = true;
@@ -984,7 +1125,7 @@ int hnet_filters_enable_photometric(hnet_filters* f) {
     if (e == hipSuccess) e = hipMemsetAsync(f->d_photo_verdict, 0, (size_t)B * sizeof(int32_t), c->stream);
     int rc = e == hipSuccess ? HNET_OK : fail(c, HNET_ERR_DEVICE, std::string("hnet_filters_enable_photometric: ") + hipGetErrorString(e));
     const size_t part = photo_partial_count(B, 2 + f->iters) * sizeof(PhotoRec);
-    if (rc == HNET_OK) rc = filters_relayout(f, f->innov, true, false, "hnet_filters_enable_photometric", (void**)&f->d_photo_part, part);      // (synchronises)
+    if (rc == HNET_OK) rc = filters_relayout(f, f->innov, true, false, f->kfm, "hnet_filters_enable_photometric", (void**)&f->d_photo_part, part);      // (synchronises)
     if (rc != HNET_OK) {
         drop_dev(f->d_photo_gate); drop_dev(f->d_photo_verdict);
         return rc;
@@ -1064,6 +1205,7 @@ int hnet_filters_set_photo_refine(hnet_filters* f, int id, const hnet_photo_refi
     hnet_ctx* c = f->s->ctx;
     if (!f->photo) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": photometric records not enabled (hnet_filters_enable_photometric)");
     if (id < 0 || id >= f->s->n) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": id out of range");
+    if (opts && f->kfm && f->kfm_on[id]) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": the session has the keyframe measurement on (hnet_filters_set_keyframe_measure)");
     hnet_photo_refine_opts o;
     memset(&o, 0, sizeof o);
     if (opts) {
@@ -1085,7 +1227,7 @@ int hnet_filters_set_photo_refine(hnet_filters* f, int id, const hnet_photo_refi
         HIPCHK(c, dalloc(&d_cfg, (size_t)N));
         hipError_t e = hipMemsetAsync(d_cfg, 0, (size_t)N * sizeof(RefineCfg), c->stream);
         int rc = e == hipSuccess ? HNET_OK : fail(c, HNET_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-        if (rc == HNET_OK) rc = filters_relayout(f, f->innov, f->photo, true, who, (void**)&f->d_refine_scratch, RefineScratch(nullptr, B, N).bytes);      // (synchronises)
+        if (rc == HNET_OK) rc = filters_relayout(f, f->innov, f->photo, true, f->kfm, who, (void**)&f->d_refine_scratch, RefineScratch(nullptr, B, N).bytes);      // (synchronises)
         if (rc != HNET_OK) {
             drop_dev(d_cfg);
             return rc;
@@ -1123,6 +1265,103 @@ int hnet_filters_reset_refine_stats(hnet_filters* f, int id) {
     if (!f) return HNET_ERR_INVALID_ARG;
     if (!f->refine || id < 0 || id >= f->s->n) return fail(f->s->ctx, HNET_ERR_INVALID_ARG, "hnet_filters_reset_refine_stats: refinement never turned on or id out of range");
     f->refine_stats[id] = hnet_refine_stats{0, 0, 0, 0, 0.0, 0.0};
+    return HNET_OK;
+}
+
+// ---- filters, the keyframe track as an in-step measurement (include/hnet.h): csrc/kernels_filters_keyframe.hip around the keyframe track's
+// launches (capi_keyframe.hip), inside hnet_filters_step / _advance ----
+
+static_assert(sizeof(hnet_keyframe_measure) == sizeof(KfmRec) && offsetof(hnet_keyframe_measure, step_px) == offsetof(KfmRec, step_px) &&
+              offsetof(hnet_keyframe_measure, z_px) == offsetof(KfmRec, z_px) && offsetof(hnet_keyframe_measure, r_px) == offsetof(KfmRec, r_px) &&
+              offsetof(hnet_keyframe_measure, innov) == offsetof(KfmRec, r) && offsetof(hnet_keyframe_measure, flags) == offsetof(KfmRec, flags) &&
+              sizeof(hnet_keyframe_measure_opts) == sizeof(KfmOpts) && offsetof(hnet_keyframe_measure_opts, cov_scale) == offsetof(KfmOpts, cov_scale) &&
+              offsetof(hnet_keyframe_measure_opts, max_mse) == offsetof(KfmOpts, max_mse) && offsetof(hnet_keyframe_measure_opts, when) == offsetof(KfmOpts, when),
+              "hnet_keyframe_measure / _opts are the layouts of include/hnet_keyframe_measure.h");
+static_assert((int)HNET_KFM_ASKED == hnet_kfm::ASKED && (int)HNET_KFM_APPLIED == hnet_kfm::APPLIED && (int)HNET_KFM_NIS_REJECTED == hnet_kfm::NIS_REJECTED &&
+              (int)HNET_KFM_S_SINGULAR == hnet_kfm::S_SINGULAR && (int)HNET_KFM_BAD_K_NET_COV == hnet_kfm::BAD_K_NET_COV && (int)HNET_KFM_STOPPED == hnet_kfm::STOPPED &&
+              (int)HNET_KFM_NO_STEP == hnet_kfm::NO_STEP && (int)HNET_KFM_MSE_ABOVE_MAX == hnet_kfm::MSE_ABOVE_MAX && (int)HNET_KFM_NO_FACTOR == hnet_kfm::NO_FACTOR &&
+              (int)HNET_KFM_NON_FINITE == hnet_kfm::NON_FINITE && (int)HNET_KFM_FIRST == hnet_kfm::FIRST && (int)HNET_KFM_TRACK_LOST == hnet_kfm::TRACK_LOST &&
+              (int)HNET_KFM_TRACK_GAP == hnet_kfm::TRACK_GAP && (int)HNET_KFM_PREV_NOT_MEASURED == hnet_kfm::PREV_NOT_MEASURED &&
+              (int)HNET_KFM_NO_INVERSE == hnet_kfm::NO_INVERSE && (int)HNET_KFM_NOT_SELECTED == hnet_kfm::NOT_SELECTED && (int)HNET_KFM_UNUSABLE == hnet_kfm::UNUSABLE &&
+              (int)HNET_KFM_ALWAYS == hnet_kfm::ALWAYS && (int)HNET_KFM_IF_NONE == hnet_kfm::IF_NONE, "HNET_KFM_* are the header's values");
+
+void hnet_keyframe_measure_default_opts(hnet_keyframe_measure_opts* o) {
+    if (!o) return;
+    KfmOpts d;
+    hnet_kfm::default_opts(d);
+    memcpy(o, &d, sizeof d);
+}
+
+int hnet_filters_set_keyframe_measure(hnet_filters* f, int id, const hnet_keyframe_measure_opts* opts) {
+    const char* who = "hnet_filters_set_keyframe_measure";
+    if (!f) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = f->s->ctx;
+    if (!capi::keyframes_enabled(f->s)) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": keyframes are not enabled (hnet_sessions_enable_keyframes)");
+    if (id < 0 || id >= f->s->n) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": id out of range");
+    hnet_keyframe_measure_opts o;
+    memset(&o, 0, sizeof o);
+    if (opts) {
+        if (f->refine && f->refine_on[id]) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": the session has refinement on (hnet_filters_set_photo_refine)");
+        if (const int rc = photo_robust_check_opts(c, &opts->track.align, who); rc != HNET_OK) return rc;
+        o = *opts;
+        o.pad = o.track.pad = o.track.align.pad = 0;               // (the sessions of a call are compared on the bytes of `track`)
+        KfmOpts r;
+        memcpy(&r, &o, sizeof r);
+        if (!hnet_kfm::opts_valid(r))
+            return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": track: 1 <= levels <= 4, auto_rekey 0 / 1, max_age >= 0, 0 <= rekey_overlap <= 1, max_mse >= 0; "
+                                                                    "cov_scale > 0, sigma_floor_px >= 0, max_mse >= 0, all finite; when ALWAYS or IF_NONE");
+    }
+    if (!opts && !f->kfm) return HNET_OK;                          // (off, and never on)
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    const int N = f->s->n, B = c->cfg.max_batch;
+    if (!f->kfm) {
+        KfmCfg* d_cfg = nullptr;
+        HIPCHK(c, dalloc(&d_cfg, (size_t)N));
+        hipError_t e = hipMemsetAsync(d_cfg, 0, (size_t)N * sizeof(KfmCfg), c->stream);
+        int rc = e == hipSuccess ? HNET_OK : fail(c, HNET_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+        if (rc == HNET_OK) rc = filters_relayout(f, f->innov, f->photo, f->refine, true, who, (void**)&f->d_kfm_scratch, KfmScratch(nullptr, B, N).bytes);      // (synchronises)
+        if (rc != HNET_OK) {
+            drop_dev(d_cfg);
+            return rc;
+        }
+        f->d_kfm_cfg = d_cfg;
+        f->kfm_opts.assign(N, hnet_keyframe_measure_opts{});
+        f->kfm_on.assign(N, 0);
+        f->kfm_stats.assign(N, hnet_keyframe_measure_stats{0, 0, 0, 0, 0.0, 0.0});
+        f->kfm = true;
+    }
+    const KfmCfg g{o.cov_scale, o.sigma_floor_px, o.max_mse, o.when, opts ? 1 : 0};
+    HIPCHK(c, hipMemcpyAsync(f->d_kfm_cfg + id, &g, sizeof g, hipMemcpyHostToDevice, c->stream));
+    if (!opts) {                                                   // (a session that stops measuring has no previous in-step track when it starts again)
+        const KfmScratch w(f->d_kfm_scratch, B, N);
+        HIPCHK(c, hipMemsetAsync(w.prev_ok + id, 0, sizeof(int32_t), c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    f->kfm_opts[id] = o;
+    f->kfm_on[id] = opts ? 1 : 0;
+    return HNET_OK;
+}
+
+int hnet_filters_last_keyframe_measure(const hnet_filters* f, int n, hnet_keyframe_measure* out) {
+    if (!f || !out) return HNET_ERR_INVALID_ARG;
+    if (!f->kfm || f->last_kfm_n < 1) return fail(f->s->ctx, HNET_ERR_INVALID_ARG, "hnet_filters_last_keyframe_measure: the last step ran without a measuring session");
+    if (n != f->last_kfm_n) return fail(f->s->ctx, HNET_ERR_INVALID_ARG, "hnet_filters_last_keyframe_measure: n differs from the last step's");
+    memcpy(out, filters_out_view(f, f->pin_out).kfm, (size_t)n * sizeof(KfmRec));
+    return HNET_OK;
+}
+
+int hnet_filters_keyframe_measure_stats(const hnet_filters* f, int id, hnet_keyframe_measure_stats* out) {
+    if (!f || !out) return HNET_ERR_INVALID_ARG;
+    if (!f->kfm || id < 0 || id >= f->s->n) return fail(f->s->ctx, HNET_ERR_INVALID_ARG, "hnet_filters_keyframe_measure_stats: the keyframe measurement never turned on or id out of range");
+    *out = f->kfm_stats[id];
+    return HNET_OK;
+}
+
+int hnet_filters_reset_keyframe_measure_stats(hnet_filters* f, int id) {
+    if (!f) return HNET_ERR_INVALID_ARG;
+    if (!f->kfm || id < 0 || id >= f->s->n)
+        return fail(f->s->ctx, HNET_ERR_INVALID_ARG, "hnet_filters_reset_keyframe_measure_stats: the keyframe measurement never turned on or id out of range");
+    f->kfm_stats[id] = hnet_keyframe_measure_stats{0, 0, 0, 0, 0.0, 0.0};
     return HNET_OK;
 }
 

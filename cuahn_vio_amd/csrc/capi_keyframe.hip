@@ -16,8 +16,11 @@
 // whose LOST sessions are relocalised (oriented) before their re-key is committed, in one upload, one download and one synchronisation; every launch
 // of the track and of the relocalisation is the unchanged one but the decision, the thumbnails and a finish.  Its scratch is its own and allocated by
 // its first call: kf->recover == nullptr until then.
+// And the track INSIDE a filter step (filters_keyframe_dev.h): capi_filters.hip enqueues the track's unchanged launches through the
+// keyframes_instep_* functions below, with the store's own scratch, decide on a copy of the state table and the commits deferred to the accepted attempt.
 #include "sessions_internal.h"
 #include "keyframe_recover_dev.h"
+#include "filters_keyframe_dev.h"
 
 using namespace hnet;
 using namespace capi;
@@ -279,6 +282,59 @@ int keyframes_drop(hnet_sessions* s, int id) {
     k->has_key[id] = 0;
     k->count_at_track[id] = -1;
     return HNET_OK;
+}
+
+bool keyframes_enabled(const hnet_sessions* s) { return s->kf != nullptr; }
+
+void keyframes_instep_table(const hnet_sessions* s, int n, const int32_t* ids, const uint8_t* on, int32_t* tab) {
+    const hnet_keyframes* k = s->kf;
+    for (int i = 0; i < n; i++) {
+        const int id = ids[i];
+        tab[i] = on[id] ? id : -1;
+        tab[n + i] = 2 * id + s->st[id].curr;
+        tab[2 * n + i] = k->has_key[id] && s->st[id].count != k->count_at_track[id] + 1 ? 1 : 0;
+    }
+}
+
+// (the launches of hnet_sessions_keyframe_track between its upload and its commit, in its order; the store's events and ms stay the last track's)
+int keyframes_instep_track(hnet_sessions* s, const KeyTable& tab, int n, const KeyOpts& o, uint8_t* prev, uint8_t* curr, KeyState* state_work, KeyInstep* v,
+                           hipStream_t st) {
+    hnet_ctx* c = s->ctx;
+    hnet_keyframes* k = s->kf;
+    const int B = c->cfg.max_batch, N = s->n;
+    const KeyScratch w(k->scratch, B);
+    const size_t pyr = (size_t)B * PYR_BYTES;
+    HIPCHK(c, hipMemcpyAsync(state_work, k->state, (size_t)N * sizeof(KeyState), hipMemcpyDeviceToDevice, st));
+    HIPCHK(c, launch_keyframe_start(tab, n, N, k->state, w.x0, st));
+    HIPCHK(c, launch_keyframe_gather(tab, n, N, k->key, s->ring, 2 * N, prev, curr, st));
+    HIPCHK(c, launch_photo_align_robust(prev, curr, n, w.x0, o.align, o.levels, c->pyr_scratch, c->pyr_scratch + pyr, w.start, w.part, w.work, w.rec, st));
+    HIPCHK(c, launch_keyframe_decide(tab, n, N, w.rec, w.x0, o, state_work, w.out, w.copy, st));
+    *v = KeyInstep{w.rec, w.out, k->state};
+    return HNET_OK;
+}
+
+int keyframes_instep_commit(hnet_sessions* s, const KeyTable& tab, int n, const uint8_t* curr, const KeyState* state_work, hipStream_t st) {
+    hnet_ctx* c = s->ctx;
+    hnet_keyframes* k = s->kf;
+    const int B = c->cfg.max_batch, N = s->n;
+    const KeyScratch w(k->scratch, B);
+    HIPCHK(c, hipMemcpyAsync(k->state, state_work, (size_t)N * sizeof(KeyState), hipMemcpyDeviceToDevice, st));
+    HIPCHK(c, launch_keyframe_commit(tab, n, N, w.copy, curr, k->key, st));
+    if (const KeyMap* m = k->map) {
+        const MapScratch mw(m->scratch, B);
+        HIPCHK(c, launch_keyframe_map_note(tab.ids, n, w.out, w.copy, k->state, m->dev, mw.store, st));
+        HIPCHK(c, launch_keyframe_map_store(tab.ids, n, mw.store, curr, m->dev, st));
+    }
+    return HNET_OK;
+}
+
+void keyframes_instep_accepted(hnet_sessions* s, int n, const int32_t* ids, const uint8_t* on) {
+    hnet_keyframes* k = s->kf;
+    for (int i = 0; i < n; i++)
+        if (on[ids[i]]) {
+            k->has_key[ids[i]] = 1;
+            k->count_at_track[ids[i]] = s->st[ids[i]].count;
+        }
 }
 
 }  // namespace capi

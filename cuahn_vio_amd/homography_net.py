@@ -1037,6 +1037,26 @@ class HnetFilters:
     def reset_refine_stats(self, id):
         self._check(self._L.hnet_filters_reset_refine_stats(self._f, int(id)))
 
+    # ---- the keyframe track as an in-step measurement (include/hnet.h hnet_filters_set_keyframe_measure) ----
+    def set_keyframe_measure(self, id, opts):
+        """session id's keyframe track inside the step, fed to the filter before the reset (needs the sessions' enable_keyframes): opts from
+        _capi.keyframe_measure_opts(cov_scale = ...), or None = off"""
+        self._check(self._L.hnet_filters_set_keyframe_measure(self._f, int(id), C.byref(opts) if opts is not None else None))
+
+    def last_keyframe_measure(self, n):
+        """the records [n] of _capi.KEYFRAME_MEASURE_DTYPE of the last step (of n sessions; another n, or a step without a measuring session, is refused)"""
+        out = np.zeros(int(n), _capi.KEYFRAME_MEASURE_DTYPE)
+        self._check(self._L.hnet_filters_last_keyframe_measure(self._f, int(n), out.ctypes.data))
+        return out
+
+    def keyframe_measure_stats(self, id):
+        st = _capi.KeyframeMeasureStats()
+        self._check(self._L.hnet_filters_keyframe_measure_stats(self._f, int(id), C.byref(st)))
+        return {k: getattr(st, k) for k, _ in st._fields_}
+
+    def reset_keyframe_measure_stats(self, id):
+        self._check(self._L.hnet_filters_reset_keyframe_measure_stats(self._f, int(id)))
+
     def last_priors(self, n):
         """the fp32 priors [iters, n, 8] the forwards of the last step (of n sessions; another n is refused) read"""
         out = np.zeros((self.iters, int(n), 8), np.float32)

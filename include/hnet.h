@@ -1070,6 +1070,79 @@ int  hnet_sessions_keyframe_track_recover(hnet_sessions* s, int n, const int32_t
                                           const hnet_keyframe_recover_opts* opts, const hnet_photo_search_hyp* hyps, int n_hyp,
                                           hnet_keyframe_recover* out /* [n] */);
 
+/* ---- hnet_filters: a session's keyframe track as a filter measurement, INSIDE the step (csrc/kernels_filters_keyframe.hip; the shared code is
+ * include/hnet_keyframe_measure.h).  Per session and off by default.  The keyframe layers above measure every camera without drift, but the
+ * filter resets its offset states (and their covariance) after every update: a keyframe result handed over after hnet_filters_step meets H P H^T = 0
+ * and carries nothing.  With the feature on, a stepping session's step instead ends like this, hnet_ekf::iterated_update_keyframe_measured:
+ *   step_px = (float)(159.5 * offset) of the state after the network's iterations (the last one's update then runs with update_offset = 1: rows 0 .. 14
+ *     of dx do not depend on it and the offsets are reset afterwards, so every other session keeps its bytes);
+ *   hnet_sessions_keyframe_track with that step: start_px = compose(step_px, key_px), the robust alignment key -> curr, the unchanged rule with
+ *     opts.track and the session's gap.  The keyframe state, the store and, with a map enabled, its entries end exactly as that call leaves them;
+ *   z_px = the corners of H(track.rec offsets) . inverse(H(key_px before the track)) minus p4, rounded to fp32: the CONSECUTIVE-frame offsets the
+ *     network measures and the offset states predict, but with errors that telescope - the composition of the H(z_px) over a stay on one keyframe is
+ *     the last key_px, whatever the individual errors were;
+ *   R_px = cov_scale * mse * inverse(info8) + sigma_floor_px^2 I, symmetrised, as hnet_filters_set_photo_refine forms it; cov_scale is the CALLER's and
+ *     has no default.  Two approximations are deliberate: the Jacobian of z_px with respect to the new key_px is taken as I, and the noise of the
+ *     previous key_px is ignored (which is what lets the errors telescope);
+ *   the packed record {z_px | (float)(R_px / k_net_cov)} goes to the unchanged innovation (with the session's NIS gate, when set) and update kernels,
+ *     against the prior of the current state, with update_offset = 0; the reset follows.
+ * The measurement is UNUSABLE and nothing is applied when (one reason bit each, tested in this order) the session held no keyframe before the call
+ * (HNET_KFM_FIRST); the track's record has a LOST bit; it has HNET_KF_GAP; the session's previous in-step track left no measured key_px
+ * (HNET_KFM_PREV_NOT_MEASURED: a word per session, 1 after TRACKED or FIRST, 0 after LOST and for a session never measured; a reset of the keyframe
+ * makes the next track FIRST); H(key_px before) has no inverse (|det| below 1e-12 of the cube of its largest entry) or a corner of the product has
+ * z <= 0 or is not finite; then hnet_filters_set_photo_refine's reasons on the level-0 record, in their order.
+ * `when`: HNET_KFM_ALWAYS applies a usable measurement after whatever the network's iterations did; HNET_KFM_IF_NONE only when they applied nothing
+ * (the slot's update counter is 0).  After a singular S of the network's own neither applies.  A usable measurement kept out is HNET_KFM_NOT_SELECTED.
+ * updates[i] counts the keyframe update; its S found singular is the existing -1 - applied.  Every other record keeps its shape and content.
+ * A step or advance in which at least one STEPPING session measures enqueues, for all its stepping sessions, 3 small kernels, the track's launches (the
+ * keyframe gathered into a buffer of the feature's own: the context's staging keeps the consecutive pair), one prior, one innovation and one update
+ * launch, inside the attempt and inside hnet_filters_last_timing's device window; the track's commits (state table, new keyframe images, map note and
+ * store) and the prev_ok words follow the ACCEPTED attempt, stream ordered, without a second synchronisation: a repeated attempt leaves what a single
+ * one leaves.  Still one upload, one download, one synchronisation.  Any other call launches exactly what it launched before.
+ * HNET_ERR_INVALID_ARG from the step or advance, nothing changed: stepping sessions that measure with different opts.track (one launch sequence serves
+ * them all; the measurement's own fields are per session), or measuring and refining (hnet_filters_set_photo_refine) sessions in one call. */
+enum { HNET_KFM_ALWAYS = 0, HNET_KFM_IF_NONE = 1 };
+typedef struct hnet_keyframe_measure_opts {
+    hnet_keyframe_opts track;  /* the in-step track's options */
+    double  cov_scale;         /* > 0; hnet_keyframe_measure_default_opts leaves 0 on purpose: the caller must choose it */
+    double  sigma_floor_px;    /* >= 0: sigma_floor_px^2 is added to the diagonal of R_px */
+    double  max_mse;           /* 0 = no limit; else a record with px.mse above it is unusable (the track's own limit is track.max_mse) */
+    int32_t when;              /* HNET_KFM_ALWAYS / HNET_KFM_IF_NONE */
+    int32_t pad;
+} hnet_keyframe_measure_opts;
+void hnet_keyframe_measure_default_opts(hnet_keyframe_measure_opts* o);      /* keyframe defaults, 0 (!), 0.05, 0, ALWAYS */
+enum { HNET_KFM_ASKED = 1,               /* the session measures: `track` is its in-step track's record */
+       HNET_KFM_APPLIED = 2,             /* the keyframe update was applied */
+       HNET_KFM_NIS_REJECTED = 4,        /* the session's NIS gate refused the measurement */
+       HNET_KFM_S_SINGULAR = 8,          /* the measurement's S was singular */
+       HNET_KFM_BAD_K_NET_COV = 16, HNET_KFM_STOPPED = 32, HNET_KFM_NO_STEP = 64, HNET_KFM_MSE_ABOVE_MAX = 128, HNET_KFM_NO_FACTOR = 256,
+       HNET_KFM_NON_FINITE = 512,        /* HNET_REFINE_*'s reasons, tested last */
+       HNET_KFM_FIRST = 1024, HNET_KFM_TRACK_LOST = 2048, HNET_KFM_TRACK_GAP = 4096, HNET_KFM_PREV_NOT_MEASURED = 8192, HNET_KFM_NO_INVERSE = 16384,
+       HNET_KFM_NOT_SELECTED = 32768,    /* `when`, or a singular S of the network's own, kept the measurement out: not an UNUSABLE reason */
+       HNET_KFM_UNUSABLE = 16 | 32 | 64 | 128 | 256 | 512 | 1024 | 2048 | 4096 | 8192 | 16384 };
+typedef struct hnet_keyframe_measure {
+    hnet_keyframe_track track; /* byte for byte hnet_sessions_keyframe_track's record for step_px */
+    float   step_px[8];        /* the filter's own step */
+    float   z_px[8];           /* zeros when unusable */
+    double  r_px[64];          /* zeros when unusable */
+    hnet_innovation innov;     /* of the keyframe measurement; iteration = max_iekf_iteration; HNET_INNOV_NONE (zeros) when unusable or not selected */
+    int32_t flags;             /* HNET_KFM_*; 0 (and the whole record zero) for a session that does not measure */
+    int32_t pad;               /* written as zero: records compare byte for byte */
+} hnet_keyframe_measure;
+/* opts == NULL turns the feature off for the session.  The first call with options allocates the feature's buffers and grows the output block
+ * (hnet_filters_last_* have nothing to describe until the next step).  HNET_ERR_INVALID_ARG, nothing changed: a bad id, a call before
+ * hnet_sessions_enable_keyframes, track options hnet_sessions_keyframe_track would refuse, cov_scale <= 0 or not finite, a negative or non-finite
+ * sigma_floor_px or max_mse, a `when` that is neither value, a session with hnet_filters_set_photo_refine on (and that call refuses a measuring session). */
+int  hnet_filters_set_keyframe_measure(hnet_filters* f, int id, const hnet_keyframe_measure_opts* opts);
+/* the records [n] of the last step (n: its n) or advance (n: its STEPPED sessions, in the order listed).  A wrong n, or a last call that ran without a
+ * measuring session: HNET_ERR_INVALID_ARG, nothing written */
+int  hnet_filters_last_keyframe_measure(const hnet_filters* f, int n, hnet_keyframe_measure* out);
+/* per session, accumulated on the host from the records of accepted calls only: asked, applied, unusable (any reason bit), nis_rejected; sum_nis /
+ * max_nis over the measurements whose NIS was formed and finite: what a caller calibrates cov_scale with (a consistent filter gives a mean of 8). */
+typedef struct hnet_keyframe_measure_stats { int64_t asked, applied, unusable, nis_rejected; double sum_nis, max_nis; } hnet_keyframe_measure_stats;
+int  hnet_filters_keyframe_measure_stats(const hnet_filters* f, int id, hnet_keyframe_measure_stats* out);
+int  hnet_filters_reset_keyframe_measure_stats(hnet_filters* f, int id);
+
 int hnet_synchronize(hnet_ctx* ctx, void* stream);
 int hnet_last_timing(const hnet_ctx* ctx, hnet_timing* out);
 
