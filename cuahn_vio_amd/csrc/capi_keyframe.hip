@@ -7,15 +7,14 @@
 // allocates, launches and returns what it did.
 // And the RELOCALISATION (photo_search_dev.h, csrc/kernels_photo_search.hip): hnet_sessions_keyframe_relocalise searches the current frame's
 // thumbnail against the held keyframe's and every stored one's, aligns against the best FOUND candidate from the searched start and re-tracks or
-// re-attaches the session (include/hnet_keyframe_reloc.h).  Its scratch is allocated by its first call: a store that never relocalises has
-// kf->reloc == nullptr.
+// re-attaches the session (include/hnet_keyframe_reloc.h).
 // And the ORIENTED relocalisation (photo_search_oriented_dev.h, csrc/kernels_photo_search_oriented.hip): hnet_sessions_keyframe_relocalise_oriented
-// is the same call with the search under a table of orientation hypotheses; the thumbnails, the gather, the alignment and the attach are the same launches.
-// Its scratch is its own and allocated by its first call: kf->oreloc == nullptr until then.
+// is the same call with the search under a table of orientation hypotheses.
 // And the RECOVERY inside the track (keyframe_recover_dev.h, csrc/kernels_keyframe_recover.hip): hnet_sessions_keyframe_track_recover is a track
 // whose LOST sessions are relocalised (oriented) before their re-key is committed, in one upload, one download and one synchronisation; every launch
-// of the track and of the relocalisation is the unchanged one but the decision, the thumbnails and a finish.  Its scratch is its own and allocated by
-// its first call: kf->recover == nullptr until then.
+// of the track and of the relocalisation is the unchanged one but the decision and a finish.
+// The three share ONE launch sequence (enqueue_relocalise) and ONE scratch (RelocScratch), allocated by whichever of them is called first: a
+// store that never relocalises has kf->reloc == nullptr.
 // And the track INSIDE a filter step (filters_keyframe_dev.h): capi_filters.hip enqueues the track's unchanged launches through the
 // keyframes_instep_* functions below, with the store's own scratch, decide on a copy of the state table and the commits deferred to the accepted attempt.
 #include "sessions_internal.h"
@@ -72,10 +71,10 @@ static_assert(sizeof(hnet_keyframe_recover) == sizeof(RecoverRec) && offsetof(hn
               sizeof(hnet_keyframe_recover_opts) == sizeof(RecoverOpts) && offsetof(hnet_keyframe_recover_opts, reloc) == offsetof(RecoverOpts, reloc) &&
               (int)HNET_KF_RECOVERED == hnet_keyframe_recovery::RECOVERED, "hnet_keyframe_recover / _opts are the layouts of include/hnet_keyframe_recover.h");
 
-// the scratch of the relocalisation (allocated by the first hnet_sessions_keyframe_relocalise), for max_batch B and the largest map
+// the scratch of the relocalisation (allocated by the first relocalise, oriented relocalise or track with recovery), for max_batch B and the largest map
 struct KeyReloc {
     uint8_t* scratch = nullptr;                // device: the sections of RelocScratch
-    uint8_t *pin_in = nullptr, *pin_out = nullptr;     // pinned: a call's table and its records [B]
+    uint8_t *pin_in = nullptr, *pin_out = nullptr;     // pinned: the largest call's table and its records [B]
 };
 
 // the map of a store (hnet_sessions_enable_keyframe_map): sized at its enable, for N sessions, M slots each and max_batch B
@@ -89,9 +88,7 @@ struct KeyMap {
 // the store: everything is sized at enable, for the sessions' count N and the context's max_batch B
 struct hnet_keyframes {
     KeyMap* map = nullptr;                     // the keyframe map or null: never enabled
-    KeyReloc* reloc = nullptr;                 // the relocalisation's scratch or null: never called
-    KeyReloc* oreloc = nullptr;                // the oriented relocalisation's scratch (the sections of OrientedScratch) or null: never called
-    KeyReloc* recover = nullptr;               // the track-with-recovery's scratch (the sections of RecoverScratch) or null: never called
+    KeyReloc* reloc = nullptr;                 // the relocalisation's scratch or null: none of its three calls was ever made
     uint8_t* key = nullptr;                    // device [N][NPIX], zeroed at enable
     KeyState* state = nullptr;                 // device [N], zeroed at enable (has_key = 0)
     uint8_t* scratch = nullptr;                // device: the sections of KeyScratch
@@ -149,77 +146,41 @@ struct MapScratch {
     }
 };
 
-// the relocalisation's own scratch for max_batch B: the call's table {ids | curr ring slot}, per slot the thumbnails of up to 9 candidates and of the
-// current frame, whether each candidate exists and its search record, the pick (candidate index and map slot), the attach flag and the call's record.
-// The alignment's scratch and the start offsets are the store's (KeyScratch).
-struct RelocScratch {
-    int32_t *tab, *valid, *cand, *mslot, *attach; uint8_t* thumbs; SearchRec* srec; RelocRec* out; size_t bytes;
-    RelocScratch(uint8_t* b, int B) {
-        size_t o = 0;
-        auto take = [&](size_t n) { uint8_t* p = b + o; o += (n + 255) & ~(size_t)255; return p; };
-        tab = reinterpret_cast<int32_t*>(take(map_table_bytes(B)));
-        thumbs = take((size_t)B * (RELOC_MAX_CANDIDATES + 1) * THUMB_BYTES);
-        valid = reinterpret_cast<int32_t*>(take((size_t)B * RELOC_MAX_CANDIDATES * sizeof(int32_t)));
-        srec = reinterpret_cast<SearchRec*>(take((size_t)B * RELOC_MAX_CANDIDATES * sizeof(SearchRec)));
-        cand = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
-        mslot = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
-        attach = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
-        out = reinterpret_cast<RelocRec*>(take((size_t)B * sizeof(RelocRec)));
-        bytes = o;
-    }
-};
-
-// the oriented relocalisation's own scratch for max_batch B: the call's table {ids | curr ring slot | hypotheses [64]}, RelocScratch's sections with the
-// oriented records, and per candidate the records of up to 64 entries
-size_t oriented_table_bytes(int n) { return map_table_bytes(n) + (size_t)SEARCH_MAX_HYP * sizeof(SearchHyp); }
-struct OrientedScratch {
-    int32_t *tab, *valid, *cand, *mslot, *attach; uint8_t* thumbs; SearchRec* hrec; OrientedRec* srec; OrientedRelocRec* out; size_t bytes;
-    OrientedScratch(uint8_t* b, int B) {
-        size_t o = 0;
-        auto take = [&](size_t n) { uint8_t* p = b + o; o += (n + 255) & ~(size_t)255; return p; };
-        tab = reinterpret_cast<int32_t*>(take(oriented_table_bytes(B)));
-        thumbs = take((size_t)B * (RELOC_MAX_CANDIDATES + 1) * THUMB_BYTES);
-        valid = reinterpret_cast<int32_t*>(take((size_t)B * RELOC_MAX_CANDIDATES * sizeof(int32_t)));
-        hrec = reinterpret_cast<SearchRec*>(take((size_t)B * RELOC_MAX_CANDIDATES * SEARCH_MAX_HYP * sizeof(SearchRec)));
-        srec = reinterpret_cast<OrientedRec*>(take((size_t)B * RELOC_MAX_CANDIDATES * sizeof(OrientedRec)));
-        cand = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
-        mslot = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
-        attach = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
-        out = reinterpret_cast<OrientedRelocRec*>(take((size_t)B * sizeof(OrientedRelocRec)));
-        bytes = o;
-    }
-};
-
-// the track-with-recovery's own scratch for max_batch B: the call's table {step | ids | curr slot | gap | (padding to 8 bytes) | hypotheses [64]},
-// OrientedScratch's sections, and per slot T1's stash, whether the relocalisation runs, the second commit's copy flag, whether T1 was restored, the second
-// store's map slot and the call's record.  The alignment's scratch, the start offsets, the track records and the first copy flags are the store's
-// (KeyScratch); the first store's map slots are the map's (MapScratch).
+// the relocalisation's own scratch for max_batch B, one layout for its three calls.  The call's table: {ids | curr ring slot} of a relocalise, with
+// {hypotheses [<= 64]} behind it of an oriented one, {step | ids | curr slot | gap | (padding to 8 bytes) | hypotheses} of a track with recovery.  Per slot
+// the thumbnails of up to 9 candidates and of the current frame, whether each candidate exists, per candidate the records of up to 64 entries (oriented)
+// and its search record, the pick (candidate index and map slot), the attach flag and the relocalisation's record; srec and out hold plain or oriented
+// records and are sized for the oriented ones.  Then what only the track with recovery uses: per slot T1's stash, whether the relocalisation runs, the
+// second commit's copy flag, whether T1 was restored, the second store's map slot and the call's record.  The alignment's scratch, the start offsets,
+// the track records and the first copy flags are the store's (KeyScratch); the first store's map slots are the map's (MapScratch).
 size_t recover_ids_bytes(int n) { return (table_bytes(n) + 7) & ~(size_t)7; }
 size_t recover_table_bytes(int n, int n_hyp) { return recover_ids_bytes(n) + (size_t)n_hyp * sizeof(SearchHyp); }
-struct RecoverScratch {
-    int32_t *valid, *cand, *mslot, *attach, *active, *copy2, *redo, *store2; uint8_t *tab, *thumbs; SearchRec* hrec; OrientedRec* srec; OrientedRelocRec* rout;
-    RecoverStash* stash; RecoverRec* out; size_t bytes;
-    RecoverScratch(uint8_t* b, int B) {
+struct RelocScratch {
+    uint8_t *tab, *thumbs, *srec, *out; int32_t *valid, *cand, *mslot, *attach; SearchRec* hrec;
+    RecoverStash* stash; int32_t *active, *copy2, *redo, *store2; RecoverRec* rout; size_t bytes;
+    RelocScratch(uint8_t* b, int B) {
         size_t o = 0;
         auto take = [&](size_t n) { uint8_t* p = b + o; o += (n + 255) & ~(size_t)255; return p; };
         tab = take(recover_table_bytes(B, SEARCH_MAX_HYP));
         thumbs = take((size_t)B * (RELOC_MAX_CANDIDATES + 1) * THUMB_BYTES);
         valid = reinterpret_cast<int32_t*>(take((size_t)B * RELOC_MAX_CANDIDATES * sizeof(int32_t)));
         hrec = reinterpret_cast<SearchRec*>(take((size_t)B * RELOC_MAX_CANDIDATES * SEARCH_MAX_HYP * sizeof(SearchRec)));
-        srec = reinterpret_cast<OrientedRec*>(take((size_t)B * RELOC_MAX_CANDIDATES * sizeof(OrientedRec)));
+        srec = take((size_t)B * RELOC_MAX_CANDIDATES * sizeof(OrientedRec));
         cand = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
         mslot = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
         attach = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
-        rout = reinterpret_cast<OrientedRelocRec*>(take((size_t)B * sizeof(OrientedRelocRec)));
+        out = take((size_t)B * sizeof(OrientedRelocRec));
         stash = reinterpret_cast<RecoverStash*>(take((size_t)B * sizeof(RecoverStash)));
         active = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
         copy2 = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
         redo = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
         store2 = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
-        out = reinterpret_cast<RecoverRec*>(take((size_t)B * sizeof(RecoverRec)));
+        rout = reinterpret_cast<RecoverRec*>(take((size_t)B * sizeof(RecoverRec)));
         bytes = o;
     }
 };
+static_assert(sizeof(OrientedRec) >= sizeof(SearchRec) && sizeof(OrientedRelocRec) >= sizeof(RelocRec) && sizeof(RecoverRec) >= sizeof(OrientedRelocRec),
+              "RelocScratch and the pinned blocks are sized by the widest records");
 
 void reloc_free(KeyReloc* r) {
     if (!r) return;
@@ -246,8 +207,6 @@ void keyframes_free(hnet_keyframes* k) {
     if (!k) return;
     map_free(k->map);
     reloc_free(k->reloc);
-    reloc_free(k->oreloc);
-    reloc_free(k->recover);
     if (k->key) (void)hipFree(k->key);
     if (k->state) (void)hipFree(k->state);
     if (k->scratch) (void)hipFree(k->scratch);
@@ -256,6 +215,135 @@ void keyframes_free(hnet_keyframes* k) {
     for (hipEvent_t e : k->ev)
         if (e) (void)hipEventDestroy(e);
     delete k;
+}
+
+// every listed session has an image; tracked: and holds a keyframe that its last track took from its latest image
+int check_listed(hnet_sessions* s, int n, const int32_t* ids, const char* who, bool tracked) {
+    hnet_ctx* c = s->ctx;
+    const hnet_keyframes* k = s->kf;
+    for (int i = 0; i < n; i++) {
+        const int id = ids[i];
+        if (s->st[id].count < 1) return fail(c, HNET_ERR_NOT_READY, std::string(who) + ": a listed session has no image");
+        if (!tracked) continue;
+        if (!k->has_key[id]) return fail(c, HNET_ERR_NOT_READY, std::string(who) + ": a listed session holds no keyframe");
+        if (s->st[id].count != k->count_at_track[id])
+            return fail(c, HNET_ERR_NOT_READY, std::string(who) + ": a listed session's latest image is not the one its last track saw (track it first)");
+    }
+    return HNET_OK;
+}
+
+// o <- *opts with its pads zeroed, or the context's error; name: what the caller calls the struct ("opts", "opts.reloc")
+int reloc_check_opts(hnet_ctx* c, const hnet_keyframe_relocalise_opts* opts, const char* who, const char* name, RelocOpts& o) {
+    const int rc = photo_robust_check_opts(c, &opts->align, who);
+    if (rc != HNET_OK) return rc;
+    memcpy(&o, opts, sizeof o);
+    if (!hnet_search::opts_valid(o.search))
+        return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": " + name +
+                                                 ".search: 0 <= radius_x <= 30, 0 <= radius_y <= 20, 16 <= min_overlap <= 1120, -1 <= min_score <= 1, 0 <= min_margin <= 2");
+    if (!hnet_keyframe_reloc::opts_valid(o))
+        return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": " + name + ": 1 <= levels <= 4, 0 <= min_overlap <= 1, max_mse and max_closure_px >= 0 and finite");
+    o.pad = 0;
+    o.search.pad = 0;
+    return HNET_OK;
+}
+
+// the relocalisation's scratch, allocated by the first call that needs it, before that call enqueues anything
+int reloc_ensure(hnet_ctx* c, hnet_keyframes* k, const char* who) {
+    if (k->reloc) return HNET_OK;
+    const int B = c->cfg.max_batch;
+    KeyReloc* r = new KeyReloc();
+    hipError_t e = hipMalloc((void**)&r->scratch, RelocScratch(nullptr, B).bytes);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&r->pin_in, recover_table_bytes(B, SEARCH_MAX_HYP), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&r->pin_out, (size_t)B * sizeof(RecoverRec), hipHostMallocDefault);
+    if (e != hipSuccess) {
+        reloc_free(r);
+        return fail(c, HNET_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    }
+    k->reloc = r;
+    return HNET_OK;
+}
+
+// ONE relocalisation of the n listed slots on the stream, between a call's upload and its download: thumbnails, search, pick, gather, robust alignment,
+// decision, attach.  d_ids, d_slot: the call's device table; active: null, or per slot whether it takes part (a track with recovery); d_hyps: null for the
+// plain search, with SearchRec in rw.srec and RelocRec in rw.out, or the device table of the oriented one, with OrientedRec and OrientedRelocRec there.
+int enqueue_relocalise(hnet_sessions* s, const RelocScratch& rw, const int32_t* d_ids, const int32_t* d_slot, int n, const int32_t* active, const SearchHyp* d_hyps,
+                       int n_hyp, const RelocOpts& o) {
+    hnet_ctx* c = s->ctx;
+    hnet_keyframes* k = s->kf;
+    const int B = c->cfg.max_batch, N = s->n;
+    const KeyScratch w(k->scratch, B);
+    const MapStore none = {nullptr, nullptr, nullptr, N, 0};
+    const MapStore& map = k->map ? k->map->dev : none;
+    const int M = map.capacity;                // 0 without a map
+    const size_t pyr = (size_t)B * PYR_BYTES;
+    uint8_t *prev = (uint8_t*)c->stage_prev, *curr = (uint8_t*)c->stage_curr;
+    hipStream_t st = c->stream;
+    HIPCHK(c, launch_reloc_thumbs(d_ids, d_slot, n, N, active, k->state, k->key, map, s->ring, 2 * N, rw.thumbs, rw.valid, st));
+    if (d_hyps) {
+        OrientedRec* srec = reinterpret_cast<OrientedRec*>(rw.srec);
+        HIPCHK(c, launch_photo_search_oriented(rw.thumbs, M + 2, M + 2, M + 1, M + 1, n, rw.valid, o.search, d_hyps, n_hyp, rw.hrec, nullptr, st));
+        HIPCHK(c, launch_photo_search_winner(rw.hrec, d_hyps, n_hyp, n * (M + 1), rw.valid, srec, st));
+        HIPCHK(c, launch_reloc_pick(d_ids, n, N, k->state, M, rw.valid, srec, w.x0, rw.cand, rw.mslot, reinterpret_cast<OrientedRelocRec*>(rw.out), st));
+    } else {
+        SearchRec* srec = reinterpret_cast<SearchRec*>(rw.srec);
+        HIPCHK(c, launch_photo_search(rw.thumbs, M + 2, M + 2, M + 1, M + 1, n, rw.valid, o.search, srec, nullptr, st));
+        HIPCHK(c, launch_reloc_pick(d_ids, n, N, k->state, M, rw.valid, srec, w.x0, rw.cand, rw.mslot, reinterpret_cast<RelocRec*>(rw.out), st));
+    }
+    HIPCHK(c, launch_reloc_gather(d_ids, d_slot, n, N, rw.cand, k->key, map, s->ring, 2 * N, prev, curr, st));
+    HIPCHK(c, launch_photo_align_robust(prev, curr, n, w.x0, o.align, o.levels, c->pyr_scratch, c->pyr_scratch + pyr, w.start, w.part, w.work, w.rec, st));
+    if (d_hyps)
+        HIPCHK(c, launch_reloc_decide(d_ids, n, N, w.rec, w.x0, rw.cand, o, k->state, map, reinterpret_cast<OrientedRelocRec*>(rw.out), rw.attach, st));
+    else
+        HIPCHK(c, launch_reloc_decide(d_ids, n, N, w.rec, w.x0, rw.cand, o, k->state, map, reinterpret_cast<RelocRec*>(rw.out), rw.attach, st));
+    if (k->map) HIPCHK(c, launch_keyframe_map_attach(d_ids, n, rw.mslot, rw.attach, map, k->key, st));
+    return HNET_OK;
+}
+
+// the end of a call whose launches began at ev[0]: the closing event, ONE download of its records, one synchronisation, the device time between the events
+int finish_call(hnet_ctx* c, hnet_keyframes* k, hipEvent_t* ev, const void* d_out, uint8_t* pin_out, void* out, size_t bytes) {
+    hipStream_t st = c->stream;
+    HIPCHK(c, hipEventRecord(ev[1], st));
+    HIPCHK(c, hipMemcpyAsync(pin_out, d_out, bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    float ms = 0;
+    HIPCHK(c, hipEventElapsedTime(&ms, ev[0], ev[1]));
+    k->ms = ms;
+    memcpy(out, pin_out, bytes);
+    return HNET_OK;
+}
+
+// ONE upload {ids | curr slot | the oriented call's table}, the launch sequence inside the store's own events, ONE download of the records [n], one
+// synchronisation.  oriented: under the table hyps [n_hyp], out [n] hnet_keyframe_relocalise_oriented; else the plain call, out [n] hnet_keyframe_relocalise.
+int relocalise(hnet_sessions* s, int n, const int32_t* ids, const hnet_keyframe_relocalise_opts* opts, bool oriented, const hnet_photo_search_hyp* hyps,
+               int n_hyp, void* out, const char* who) {
+    if (!s) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = s->ctx;
+    hnet_keyframes* k = s->kf;
+    if (!k) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": keyframes are not enabled (hnet_sessions_enable_keyframes)");
+    if (!out || !opts) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": opts / out");
+    RelocOpts o;
+    int rc = reloc_check_opts(c, opts, who, "opts", o);
+    if (rc != HNET_OK) return rc;
+    if (oriented && (rc = photo_search_check_table(c, hyps, n_hyp, who)) != HNET_OK) return rc;
+    if ((rc = sessions_check_ids(s, n, ids)) != HNET_OK) return rc;
+    if ((rc = check_listed(s, n, ids, who, true)) != HNET_OK) return rc;
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    if ((rc = reloc_ensure(c, k, who)) != HNET_OK) return rc;
+    KeyReloc* r = k->reloc;
+    const RelocScratch rw(r->scratch, c->cfg.max_batch);
+    int32_t* h_ids = reinterpret_cast<int32_t*>(r->pin_in);
+    for (int i = 0; i < n; i++) {
+        h_ids[i] = ids[i];
+        h_ids[n + i] = 2 * ids[i] + s->st[ids[i]].curr;
+    }
+    const size_t head = map_table_bytes(n), tab = oriented ? (size_t)n_hyp * sizeof(SearchHyp) : 0;
+    if (oriented) memcpy(r->pin_in + head, hyps, tab);                 // (8 n bytes in front: the table is aligned)
+    const int32_t* d_ids = reinterpret_cast<const int32_t*>(rw.tab);
+    const SearchHyp* d_hyps = oriented ? reinterpret_cast<const SearchHyp*>(rw.tab + head) : nullptr;
+    HIPCHK(c, hipMemcpyAsync(rw.tab, r->pin_in, head + tab, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipEventRecord(k->ev[0], c->stream));
+    if ((rc = enqueue_relocalise(s, rw, d_ids, d_ids + n, n, nullptr, d_hyps, n_hyp, o)) != HNET_OK) return rc;
+    return finish_call(c, k, k->ev, rw.out, r->pin_out, out, (size_t)n * (oriented ? sizeof(OrientedRelocRec) : sizeof(RelocRec)));
 }
 
 }  // namespace
@@ -392,8 +480,7 @@ int hnet_sessions_keyframe_track(hnet_sessions* s, int n, const int32_t* ids, co
     if (!hnet_keyframe::opts_valid(o))
         return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": opts: 1 <= levels <= 4, auto_rekey 0 / 1, max_age >= 0, 0 <= rekey_overlap <= 1, max_mse >= 0 and finite");
     if ((rc = sessions_check_ids(s, n, ids)) != HNET_OK) return rc;
-    for (int i = 0; i < n; i++)
-        if (s->st[ids[i]].count < 1) return fail(c, HNET_ERR_NOT_READY, std::string(who) + ": a listed session has no image");
+    if ((rc = check_listed(s, n, ids, who, false)) != HNET_OK) return rc;
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
     const int B = c->cfg.max_batch, N = s->n;
     const KeyScratch w(k->scratch, B);
@@ -422,13 +509,7 @@ int hnet_sessions_keyframe_track(hnet_sessions* s, int n, const int32_t* ids, co
         HIPCHK(c, launch_keyframe_map_note(tab.ids, n, w.out, w.copy, k->state, m->dev, mw.store, st));
         HIPCHK(c, launch_keyframe_map_store(tab.ids, n, mw.store, curr, m->dev, st));
     }
-    HIPCHK(c, hipEventRecord(k->ev[1], st));
-    HIPCHK(c, hipMemcpyAsync(k->pin_out, w.out, (size_t)n * sizeof(KeyTrack), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    float ms = 0;
-    HIPCHK(c, hipEventElapsedTime(&ms, k->ev[0], k->ev[1]));
-    k->ms = ms;
-    memcpy(out, k->pin_out, (size_t)n * sizeof(KeyTrack));
+    if ((rc = finish_call(c, k, k->ev, w.out, k->pin_out, out, (size_t)n * sizeof(KeyTrack))) != HNET_OK) return rc;
     for (int i = 0; i < n; i++) {
         k->has_key[ids[i]] = 1;
         k->count_at_track[ids[i]] = s->st[ids[i]].count;
@@ -517,13 +598,7 @@ int hnet_sessions_keyframe_revisit(hnet_sessions* s, int n, const int32_t* ids, 
         return fail(c, HNET_ERR_INVALID_ARG,
                     std::string(who) + ": opts: 1 <= levels <= 4, 1 <= min_grid <= 64, 0 <= min_overlap <= 1, max_mse and max_closure_px >= 0 and finite");
     if ((rc = sessions_check_ids(s, n, ids)) != HNET_OK) return rc;
-    for (int i = 0; i < n; i++) {
-        const int id = ids[i];
-        if (s->st[id].count < 1) return fail(c, HNET_ERR_NOT_READY, std::string(who) + ": a listed session has no image");
-        if (!k->has_key[id]) return fail(c, HNET_ERR_NOT_READY, std::string(who) + ": a listed session holds no keyframe");
-        if (s->st[id].count != k->count_at_track[id])
-            return fail(c, HNET_ERR_NOT_READY, std::string(who) + ": a listed session's latest image is not the one its last track saw (track it first)");
-    }
+    if ((rc = check_listed(s, n, ids, who, true)) != HNET_OK) return rc;
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
     const int B = c->cfg.max_batch, N = s->n;
     const KeyScratch w(k->scratch, B);
@@ -544,14 +619,7 @@ int hnet_sessions_keyframe_revisit(hnet_sessions* s, int n, const int32_t* ids, 
     HIPCHK(c, launch_photo_align_robust(prev, curr, n, w.x0, o.align, o.levels, c->pyr_scratch, c->pyr_scratch + pyr, w.start, w.part, w.work, w.rec, st));
     HIPCHK(c, launch_keyframe_map_decide(d_ids, n, w.rec, w.x0, mw.cand, o, k->state, m->dev, mw.out, mw.attach, st));
     HIPCHK(c, launch_keyframe_map_attach(d_ids, n, mw.cand, mw.attach, m->dev, k->key, st));
-    HIPCHK(c, hipEventRecord(m->ev[1], st));
-    HIPCHK(c, hipMemcpyAsync(m->pin_out, mw.out, (size_t)n * sizeof(MapRevisit), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    float ms = 0;
-    HIPCHK(c, hipEventElapsedTime(&ms, m->ev[0], m->ev[1]));
-    k->ms = ms;
-    memcpy(out, m->pin_out, (size_t)n * sizeof(MapRevisit));
-    return HNET_OK;
+    return finish_call(c, k, m->ev, mw.out, m->pin_out, out, (size_t)n * sizeof(MapRevisit));
 }
 
 int hnet_sessions_keyframe_map_info(hnet_sessions* s, int id, hnet_keyframe_map_entry* entries, hnet_keyframe_map_state* map_state) {
@@ -589,159 +657,14 @@ void hnet_keyframe_relocalise_default_opts(hnet_keyframe_relocalise_opts* o) {
     memcpy(o, &d, sizeof d);
 }
 
-// ONE upload {ids | curr slot}, the launch sequence inside the store's own events, ONE download of the records [n], one synchronisation
 int hnet_sessions_keyframe_relocalise(hnet_sessions* s, int n, const int32_t* ids, const hnet_keyframe_relocalise_opts* opts, hnet_keyframe_relocalise* out) {
-    const char* who = "hnet_sessions_keyframe_relocalise";
-    if (!s) return HNET_ERR_INVALID_ARG;
-    hnet_ctx* c = s->ctx;
-    hnet_keyframes* k = s->kf;
-    if (!k) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": keyframes are not enabled (hnet_sessions_enable_keyframes)");
-    if (!out || !opts) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": opts / out");
-    int rc = photo_robust_check_opts(c, &opts->align, who);
-    if (rc != HNET_OK) return rc;
-    RelocOpts o;
-    memcpy(&o, opts, sizeof o);
-    if (!hnet_search::opts_valid(o.search))
-        return fail(c, HNET_ERR_INVALID_ARG,
-                    std::string(who) + ": opts.search: 0 <= radius_x <= 30, 0 <= radius_y <= 20, 16 <= min_overlap <= 1120, -1 <= min_score <= 1, 0 <= min_margin <= 2");
-    if (!hnet_keyframe_reloc::opts_valid(o))
-        return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": opts: 1 <= levels <= 4, 0 <= min_overlap <= 1, max_mse and max_closure_px >= 0 and finite");
-    o.pad = 0;
-    o.search.pad = 0;
-    if ((rc = sessions_check_ids(s, n, ids)) != HNET_OK) return rc;
-    for (int i = 0; i < n; i++) {
-        const int id = ids[i];
-        if (s->st[id].count < 1) return fail(c, HNET_ERR_NOT_READY, std::string(who) + ": a listed session has no image");
-        if (!k->has_key[id]) return fail(c, HNET_ERR_NOT_READY, std::string(who) + ": a listed session holds no keyframe");
-        if (s->st[id].count != k->count_at_track[id])
-            return fail(c, HNET_ERR_NOT_READY, std::string(who) + ": a listed session's latest image is not the one its last track saw (track it first)");
-    }
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    const int B = c->cfg.max_batch, N = s->n;
-    if (!k->reloc) {                           // the first call: nothing is enqueued yet
-        KeyReloc* r = new KeyReloc();
-        hipError_t e = hipMalloc((void**)&r->scratch, RelocScratch(nullptr, B).bytes);
-        if (e == hipSuccess) e = hipHostMalloc((void**)&r->pin_in, map_table_bytes(B), hipHostMallocDefault);
-        if (e == hipSuccess) e = hipHostMalloc((void**)&r->pin_out, (size_t)B * sizeof(RelocRec), hipHostMallocDefault);
-        if (e != hipSuccess) {
-            reloc_free(r);
-            return fail(c, HNET_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-        }
-        k->reloc = r;
-    }
-    KeyReloc* r = k->reloc;
-    const KeyScratch w(k->scratch, B);
-    const RelocScratch rw(r->scratch, B);
-    const MapStore none = {nullptr, nullptr, nullptr, N, 0};
-    const MapStore& map = k->map ? k->map->dev : none;
-    const int M = map.capacity;                // 0 without a map
-    int32_t* h_ids = reinterpret_cast<int32_t*>(r->pin_in);
-    for (int i = 0; i < n; i++) {
-        h_ids[i] = ids[i];
-        h_ids[n + i] = 2 * ids[i] + s->st[ids[i]].curr;
-    }
-    const int32_t *d_ids = rw.tab, *d_slot = rw.tab + n;
-    const size_t pyr = (size_t)B * PYR_BYTES;
-    uint8_t *prev = (uint8_t*)c->stage_prev, *curr = (uint8_t*)c->stage_curr;
-    hipStream_t st = c->stream;
-    HIPCHK(c, hipMemcpyAsync(rw.tab, r->pin_in, map_table_bytes(n), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipEventRecord(k->ev[0], st));
-    HIPCHK(c, launch_reloc_thumbs(d_ids, d_slot, n, N, k->state, k->key, map, s->ring, 2 * N, rw.thumbs, rw.valid, st));
-    HIPCHK(c, launch_photo_search(rw.thumbs, M + 2, M + 2, M + 1, M + 1, n, rw.valid, o.search, rw.srec, nullptr, st));
-    HIPCHK(c, launch_reloc_pick(d_ids, n, N, k->state, M, rw.valid, rw.srec, w.x0, rw.cand, rw.mslot, rw.out, st));
-    HIPCHK(c, launch_reloc_gather(d_ids, d_slot, n, N, rw.cand, k->key, map, s->ring, 2 * N, prev, curr, st));
-    HIPCHK(c, launch_photo_align_robust(prev, curr, n, w.x0, o.align, o.levels, c->pyr_scratch, c->pyr_scratch + pyr, w.start, w.part, w.work, w.rec, st));
-    HIPCHK(c, launch_reloc_decide(d_ids, n, N, w.rec, w.x0, rw.cand, o, k->state, map, rw.out, rw.attach, st));
-    if (k->map) HIPCHK(c, launch_keyframe_map_attach(d_ids, n, rw.mslot, rw.attach, map, k->key, st));
-    HIPCHK(c, hipEventRecord(k->ev[1], st));
-    HIPCHK(c, hipMemcpyAsync(r->pin_out, rw.out, (size_t)n * sizeof(RelocRec), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    float ms = 0;
-    HIPCHK(c, hipEventElapsedTime(&ms, k->ev[0], k->ev[1]));
-    k->ms = ms;
-    memcpy(out, r->pin_out, (size_t)n * sizeof(RelocRec));
-    return HNET_OK;
+    return relocalise(s, n, ids, opts, false, nullptr, 0, out, "hnet_sessions_keyframe_relocalise");
 }
 
-// hnet_sessions_keyframe_relocalise with the oriented search: ONE upload {ids | curr slot | table}, the launch sequence inside the store's own events, ONE
-// download of the records [n], one synchronisation
+// hnet_sessions_keyframe_relocalise with the oriented search
 int hnet_sessions_keyframe_relocalise_oriented(hnet_sessions* s, int n, const int32_t* ids, const hnet_keyframe_relocalise_opts* opts,
                                                const hnet_photo_search_hyp* hyps, int n_hyp, hnet_keyframe_relocalise_oriented* out) {
-    const char* who = "hnet_sessions_keyframe_relocalise_oriented";
-    if (!s) return HNET_ERR_INVALID_ARG;
-    hnet_ctx* c = s->ctx;
-    hnet_keyframes* k = s->kf;
-    if (!k) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": keyframes are not enabled (hnet_sessions_enable_keyframes)");
-    if (!out || !opts) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": opts / out");
-    int rc = photo_robust_check_opts(c, &opts->align, who);
-    if (rc != HNET_OK) return rc;
-    RelocOpts o;
-    memcpy(&o, opts, sizeof o);
-    if (!hnet_search::opts_valid(o.search))
-        return fail(c, HNET_ERR_INVALID_ARG,
-                    std::string(who) + ": opts.search: 0 <= radius_x <= 30, 0 <= radius_y <= 20, 16 <= min_overlap <= 1120, -1 <= min_score <= 1, 0 <= min_margin <= 2");
-    if (!hnet_keyframe_reloc::opts_valid(o))
-        return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": opts: 1 <= levels <= 4, 0 <= min_overlap <= 1, max_mse and max_closure_px >= 0 and finite");
-    o.pad = 0;
-    o.search.pad = 0;
-    if ((rc = photo_search_check_table(c, hyps, n_hyp, who)) != HNET_OK) return rc;
-    if ((rc = sessions_check_ids(s, n, ids)) != HNET_OK) return rc;
-    for (int i = 0; i < n; i++) {
-        const int id = ids[i];
-        if (s->st[id].count < 1) return fail(c, HNET_ERR_NOT_READY, std::string(who) + ": a listed session has no image");
-        if (!k->has_key[id]) return fail(c, HNET_ERR_NOT_READY, std::string(who) + ": a listed session holds no keyframe");
-        if (s->st[id].count != k->count_at_track[id])
-            return fail(c, HNET_ERR_NOT_READY, std::string(who) + ": a listed session's latest image is not the one its last track saw (track it first)");
-    }
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    const int B = c->cfg.max_batch, N = s->n;
-    if (!k->oreloc) {                          // the first call: nothing is enqueued yet
-        KeyReloc* r = new KeyReloc();
-        hipError_t e = hipMalloc((void**)&r->scratch, OrientedScratch(nullptr, B).bytes);
-        if (e == hipSuccess) e = hipHostMalloc((void**)&r->pin_in, oriented_table_bytes(B), hipHostMallocDefault);
-        if (e == hipSuccess) e = hipHostMalloc((void**)&r->pin_out, (size_t)B * sizeof(OrientedRelocRec), hipHostMallocDefault);
-        if (e != hipSuccess) {
-            reloc_free(r);
-            return fail(c, HNET_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-        }
-        k->oreloc = r;
-    }
-    KeyReloc* r = k->oreloc;
-    const KeyScratch w(k->scratch, B);
-    const OrientedScratch rw(r->scratch, B);
-    const MapStore none = {nullptr, nullptr, nullptr, N, 0};
-    const MapStore& map = k->map ? k->map->dev : none;
-    const int M = map.capacity;                // 0 without a map
-    int32_t* h_ids = reinterpret_cast<int32_t*>(r->pin_in);
-    for (int i = 0; i < n; i++) {
-        h_ids[i] = ids[i];
-        h_ids[n + i] = 2 * ids[i] + s->st[ids[i]].curr;
-    }
-    const size_t tab = (size_t)n_hyp * sizeof(SearchHyp);
-    memcpy(r->pin_in + map_table_bytes(n), hyps, tab);          // (8 n bytes in front: the table is aligned)
-    const int32_t *d_ids = rw.tab, *d_slot = rw.tab + n;
-    const SearchHyp* d_hyps = reinterpret_cast<const SearchHyp*>(rw.tab + 2 * (size_t)n);
-    const size_t pyr = (size_t)B * PYR_BYTES;
-    uint8_t *prev = (uint8_t*)c->stage_prev, *curr = (uint8_t*)c->stage_curr;
-    hipStream_t st = c->stream;
-    HIPCHK(c, hipMemcpyAsync(rw.tab, r->pin_in, map_table_bytes(n) + tab, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipEventRecord(k->ev[0], st));
-    HIPCHK(c, launch_reloc_thumbs(d_ids, d_slot, n, N, k->state, k->key, map, s->ring, 2 * N, rw.thumbs, rw.valid, st));
-    HIPCHK(c, launch_photo_search_oriented(rw.thumbs, M + 2, M + 2, M + 1, M + 1, n, rw.valid, o.search, d_hyps, n_hyp, rw.hrec, nullptr, st));
-    HIPCHK(c, launch_photo_search_winner(rw.hrec, d_hyps, n_hyp, n * (M + 1), rw.valid, rw.srec, st));
-    HIPCHK(c, launch_reloc_pick_oriented(d_ids, n, N, k->state, M, rw.valid, rw.srec, w.x0, rw.cand, rw.mslot, rw.out, st));
-    HIPCHK(c, launch_reloc_gather(d_ids, d_slot, n, N, rw.cand, k->key, map, s->ring, 2 * N, prev, curr, st));
-    HIPCHK(c, launch_photo_align_robust(prev, curr, n, w.x0, o.align, o.levels, c->pyr_scratch, c->pyr_scratch + pyr, w.start, w.part, w.work, w.rec, st));
-    HIPCHK(c, launch_reloc_decide_oriented(d_ids, n, N, w.rec, w.x0, rw.cand, o, k->state, map, rw.out, rw.attach, st));
-    if (k->map) HIPCHK(c, launch_keyframe_map_attach(d_ids, n, rw.mslot, rw.attach, map, k->key, st));
-    HIPCHK(c, hipEventRecord(k->ev[1], st));
-    HIPCHK(c, hipMemcpyAsync(r->pin_out, rw.out, (size_t)n * sizeof(OrientedRelocRec), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    float ms = 0;
-    HIPCHK(c, hipEventElapsedTime(&ms, k->ev[0], k->ev[1]));
-    k->ms = ms;
-    memcpy(out, r->pin_out, (size_t)n * sizeof(OrientedRelocRec));
-    return HNET_OK;
+    return relocalise(s, n, ids, opts, true, hyps, n_hyp, out, "hnet_sessions_keyframe_relocalise_oriented");
 }
 
 void hnet_keyframe_recover_default_opts(hnet_keyframe_recover_opts* o) {
@@ -766,18 +689,11 @@ int hnet_sessions_keyframe_track_recover(hnet_sessions* s, int n, const int32_t*
     int rc = photo_robust_check_opts(c, &opts->track.align, who);
     if (rc != HNET_OK) return rc;
     RecoverOpts o;
-    memcpy(&o, opts, sizeof o);
+    memcpy(&o.track, &opts->track, sizeof o.track);
     if (!hnet_keyframe::opts_valid(o.track))
         return fail(c, HNET_ERR_INVALID_ARG,
                     std::string(who) + ": opts.track: 1 <= levels <= 4, auto_rekey 0 / 1, max_age >= 0, 0 <= rekey_overlap <= 1, max_mse >= 0 and finite");
-    if ((rc = photo_robust_check_opts(c, &opts->reloc.align, who)) != HNET_OK) return rc;
-    if (!hnet_search::opts_valid(o.reloc.search))
-        return fail(c, HNET_ERR_INVALID_ARG, std::string(who) +
-                                                 ": opts.reloc.search: 0 <= radius_x <= 30, 0 <= radius_y <= 20, 16 <= min_overlap <= 1120, -1 <= min_score <= 1, 0 <= min_margin <= 2");
-    if (!hnet_keyframe_reloc::opts_valid(o.reloc))
-        return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": opts.reloc: 1 <= levels <= 4, 0 <= min_overlap <= 1, max_mse and max_closure_px >= 0 and finite");
-    o.reloc.pad = 0;
-    o.reloc.search.pad = 0;
+    if ((rc = reloc_check_opts(c, &opts->reloc, who, "opts.reloc", o.reloc)) != HNET_OK) return rc;
     SearchHyp identity;
     if (!hyps && n_hyp == 0) {                 // the identity entry alone
         hnet_search_oriented::make_hyp(0.0, 1.0, identity);
@@ -786,27 +702,13 @@ int hnet_sessions_keyframe_track_recover(hnet_sessions* s, int n, const int32_t*
     }
     if ((rc = photo_search_check_table(c, hyps, n_hyp, who)) != HNET_OK) return rc;
     if ((rc = sessions_check_ids(s, n, ids)) != HNET_OK) return rc;
-    for (int i = 0; i < n; i++)
-        if (s->st[ids[i]].count < 1) return fail(c, HNET_ERR_NOT_READY, std::string(who) + ": a listed session has no image");
+    if ((rc = check_listed(s, n, ids, who, false)) != HNET_OK) return rc;
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
     const int B = c->cfg.max_batch, N = s->n;
-    if (!k->recover) {                         // the first call: nothing is enqueued yet
-        KeyReloc* r = new KeyReloc();
-        hipError_t e = hipMalloc((void**)&r->scratch, RecoverScratch(nullptr, B).bytes);
-        if (e == hipSuccess) e = hipHostMalloc((void**)&r->pin_in, recover_table_bytes(B, SEARCH_MAX_HYP), hipHostMallocDefault);
-        if (e == hipSuccess) e = hipHostMalloc((void**)&r->pin_out, (size_t)B * sizeof(RecoverRec), hipHostMallocDefault);
-        if (e != hipSuccess) {
-            reloc_free(r);
-            return fail(c, HNET_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-        }
-        k->recover = r;
-    }
-    KeyReloc* r = k->recover;
+    if ((rc = reloc_ensure(c, k, who)) != HNET_OK) return rc;
+    KeyReloc* r = k->reloc;
     const KeyScratch w(k->scratch, B);
-    const RecoverScratch rw(r->scratch, B);
-    const MapStore none = {nullptr, nullptr, nullptr, N, 0};
-    const MapStore& map = k->map ? k->map->dev : none;
-    const int M = map.capacity;                // 0 without a map
+    const RelocScratch rw(r->scratch, B);
     float* h_step = reinterpret_cast<float*>(r->pin_in);
     int32_t* h_ids = reinterpret_cast<int32_t*>(h_step + (size_t)8 * n);
     for (int i = 0; i < n; i++) {
@@ -820,7 +722,7 @@ int hnet_sessions_keyframe_track_recover(hnet_sessions* s, int n, const int32_t*
     memset(r->pin_in + table_bytes(n), 0, head - table_bytes(n));
     memcpy(r->pin_in + head, hyps, tabb);
     const KeyTable tab = table_view(rw.tab, n);
-    const int32_t *d_ids = tab.ids, *d_slot = tab.slot;
+    const int32_t* d_ids = tab.ids;
     const SearchHyp* d_hyps = reinterpret_cast<const SearchHyp*>(rw.tab + head);
     const size_t pyr = (size_t)B * PYR_BYTES;
     uint8_t *prev = (uint8_t*)c->stage_prev, *curr = (uint8_t*)c->stage_curr;
@@ -839,28 +741,15 @@ int hnet_sessions_keyframe_track_recover(hnet_sessions* s, int n, const int32_t*
         HIPCHK(c, launch_keyframe_map_store(d_ids, n, mw.store, curr, m->dev, st));
     }
     // the oriented relocalisation of the lost sessions on T0's state; the others ride through on absent candidates and quiet-NaN starts
-    HIPCHK(c, launch_recover_thumbs(d_ids, d_slot, n, N, rw.active, k->state, k->key, map, s->ring, 2 * N, rw.thumbs, rw.valid, st));
-    HIPCHK(c, launch_photo_search_oriented(rw.thumbs, M + 2, M + 2, M + 1, M + 1, n, rw.valid, o.reloc.search, d_hyps, n_hyp, rw.hrec, nullptr, st));
-    HIPCHK(c, launch_photo_search_winner(rw.hrec, d_hyps, n_hyp, n * (M + 1), rw.valid, rw.srec, st));
-    HIPCHK(c, launch_reloc_pick_oriented(d_ids, n, N, k->state, M, rw.valid, rw.srec, w.x0, rw.cand, rw.mslot, rw.rout, st));
-    HIPCHK(c, launch_reloc_gather(d_ids, d_slot, n, N, rw.cand, k->key, map, s->ring, 2 * N, prev, curr, st));
-    HIPCHK(c, launch_photo_align_robust(prev, curr, n, w.x0, o.reloc.align, o.reloc.levels, c->pyr_scratch, c->pyr_scratch + pyr, w.start, w.part, w.work, w.rec, st));
-    HIPCHK(c, launch_reloc_decide_oriented(d_ids, n, N, w.rec, w.x0, rw.cand, o.reloc, k->state, map, rw.rout, rw.attach, st));
-    if (k->map) HIPCHK(c, launch_keyframe_map_attach(d_ids, n, rw.mslot, rw.attach, map, k->key, st));
+    if ((rc = enqueue_relocalise(s, rw, d_ids, tab.slot, n, rw.active, d_hyps, n_hyp, o.reloc)) != HNET_OK) return rc;
     // T0 | RECOVERED or T1, and T1's commit for the unrecovered sessions (curr still holds every slot's current frame)
-    HIPCHK(c, launch_recover_finish(d_ids, n, N, rw.active, rw.stash, rw.rout, k->state, w.out, rw.copy2, rw.redo, rw.out, st));
+    HIPCHK(c, launch_recover_finish(d_ids, n, N, rw.active, rw.stash, reinterpret_cast<const OrientedRelocRec*>(rw.out), k->state, w.out, rw.copy2, rw.redo, rw.rout, st));
     HIPCHK(c, launch_keyframe_commit(tab, n, N, rw.copy2, curr, k->key, st));
     if (const KeyMap* m = k->map) {
         HIPCHK(c, launch_recover_note(d_ids, n, w.out, rw.copy2, rw.redo, k->state, m->dev, rw.store2, st));
         HIPCHK(c, launch_keyframe_map_store(d_ids, n, rw.store2, curr, m->dev, st));
     }
-    HIPCHK(c, hipEventRecord(k->ev[1], st));
-    HIPCHK(c, hipMemcpyAsync(r->pin_out, rw.out, (size_t)n * sizeof(RecoverRec), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    float ms = 0;
-    HIPCHK(c, hipEventElapsedTime(&ms, k->ev[0], k->ev[1]));
-    k->ms = ms;
-    memcpy(out, r->pin_out, (size_t)n * sizeof(RecoverRec));
+    if ((rc = finish_call(c, k, k->ev, rw.rout, r->pin_out, out, (size_t)n * sizeof(RecoverRec))) != HNET_OK) return rc;
     for (int i = 0; i < n; i++) {
         k->has_key[ids[i]] = 1;
         k->count_at_track[ids[i]] = s->st[ids[i]].count;

@@ -18,9 +18,9 @@ static_assert(sizeof(hnet_photo_search) == sizeof(SearchRec) && offsetof(hnet_ph
 static_assert((int)HNET_PS_FOUND == ps::FOUND && (int)HNET_PS_NO_TEXTURE == ps::NO_TEXTURE && (int)HNET_PS_LOW_SCORE == ps::LOW_SCORE &&
               (int)HNET_PS_AMBIGUOUS == ps::AMBIGUOUS && HNET_PS_SHIFTS_X == ps::NSX && HNET_PS_SHIFTS_Y == ps::NSY, "HNET_PS_* are the header's");
 
-namespace {
+namespace capi {
 
-int check_opts(hnet_ctx* c, const hnet_photo_search_opts* opts, const char* who, SearchOpts& o) {
+int photo_search_check_opts(hnet_ctx* c, const hnet_photo_search_opts* opts, const char* who, SearchOpts& o) {
     if (!opts) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": opts");
     memcpy(&o, opts, sizeof o);
     if (!ps::opts_valid(o))
@@ -29,6 +29,10 @@ int check_opts(hnet_ctx* c, const hnet_photo_search_opts* opts, const char* who,
     o.pad = 0;
     return HNET_OK;
 }
+
+}  // namespace capi
+
+namespace {
 
 // the thumbnails are in place on the stream: the search, ONE download {records [n] | score tables [n]}, one synchronisation
 int search_run(hnet_ctx* c, DevTemps& t, const uint8_t* d_thumbs, int ta_stride, int tb_stride, int tb_off, int n, const SearchOpts& o, hnet_photo_search* out,
@@ -64,7 +68,7 @@ int hnet_op_photo_search(hnet_ctx* c, const uint8_t* img1, const uint8_t* img2, 
     if (!c) return HNET_ERR_INVALID_ARG;
     if (!img1 || !img2 || !out || n < 1) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": frames / out, n >= 1");
     SearchOpts o;
-    const int rc = check_opts(c, opts, who, o);
+    const int rc = photo_search_check_opts(c, opts, who, o);
     if (rc != HNET_OK) return rc;
     if (n > c->cfg.max_batch) return fail(c, HNET_ERR_CAPACITY, std::string(who) + ": n exceeds max_batch");
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
@@ -89,7 +93,7 @@ int hnet_sessions_photo_search(hnet_sessions* s, int n, const int32_t* ids, cons
     hnet_ctx* c = s->ctx;
     if (!out) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": out");
     SearchOpts o;
-    int rc = check_opts(c, opts, who, o);
+    int rc = photo_search_check_opts(c, opts, who, o);
     if (rc == HNET_OK) rc = sessions_check_ids(s, n, ids);
     if (rc == HNET_OK) rc = sessions_check_pairs(s, n, ids);
     if (rc != HNET_OK) return rc;

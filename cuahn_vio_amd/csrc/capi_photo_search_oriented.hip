@@ -8,7 +8,6 @@
 using namespace hnet;
 using namespace capi;
 
-namespace ps = hnet_search;
 namespace po = hnet_search_oriented;
 
 static_assert(sizeof(hnet_photo_search_hyp) == sizeof(SearchHyp) && offsetof(hnet_photo_search_hyp, b) == offsetof(SearchHyp, b) &&
@@ -19,16 +18,6 @@ static_assert(sizeof(hnet_photo_search_hyp) == sizeof(SearchHyp) && offsetof(hne
               "hnet_photo_search_hyp / _oriented are the layouts of include/hnet_photo_search_oriented.h");
 
 namespace {
-
-int check_opts(hnet_ctx* c, const hnet_photo_search_opts* opts, const char* who, SearchOpts& o) {
-    if (!opts) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": opts");
-    memcpy(&o, opts, sizeof o);
-    if (!ps::opts_valid(o))
-        return fail(c, HNET_ERR_INVALID_ARG,
-                    std::string(who) + ": opts: 0 <= radius_x <= 30, 0 <= radius_y <= 20, 16 <= min_overlap <= 1120, -1 <= min_score <= 1, 0 <= min_margin <= 2");
-    o.pad = 0;
-    return HNET_OK;
-}
 
 // the thumbnails and the table are in place on the stream: the search, the winner, ONE download {records [n] | score tables [n][n_hyp]}, one synchronisation
 int search_run(hnet_ctx* c, DevTemps& t, const uint8_t* d_thumbs, int ta_stride, int tb_stride, int tb_off, int n, const SearchOpts& o, const SearchHyp* d_hyps,
@@ -89,7 +78,7 @@ int hnet_op_photo_search_oriented(hnet_ctx* c, const uint8_t* img1, const uint8_
     if (!c) return HNET_ERR_INVALID_ARG;
     if (!img1 || !img2 || !out || n < 1) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": frames / out, n >= 1");
     SearchOpts o;
-    int rc = check_opts(c, opts, who, o);
+    int rc = photo_search_check_opts(c, opts, who, o);
     if (rc == HNET_OK) rc = photo_search_check_table(c, hyps, n_hyp, who);
     if (rc != HNET_OK) return rc;
     if (n > c->cfg.max_batch) return fail(c, HNET_ERR_CAPACITY, std::string(who) + ": n exceeds max_batch");
@@ -117,7 +106,7 @@ int hnet_sessions_photo_search_oriented(hnet_sessions* s, int n, const int32_t* 
     hnet_ctx* c = s->ctx;
     if (!out) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": out");
     SearchOpts o;
-    int rc = check_opts(c, opts, who, o);
+    int rc = photo_search_check_opts(c, opts, who, o);
     if (rc == HNET_OK) rc = photo_search_check_table(c, hyps, n_hyp, who);
     if (rc == HNET_OK) rc = sessions_check_ids(s, n, ids);
     if (rc == HNET_OK) rc = sessions_check_pairs(s, n, ids);

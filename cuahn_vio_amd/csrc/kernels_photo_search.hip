@@ -1,6 +1,6 @@
 // kernels_photo_search.hip — the device side of the coarse search over integer translations (include/hnet.h hnet_op_photo_search,
-// hnet_sessions_photo_search) and of the relocalisation of a session among its keyframes (hnet_sessions_keyframe_relocalise) around the
-// unchanged launch_photo_align_robust.
+// hnet_sessions_photo_search) and of the relocalisation of a session among its keyframes (hnet_sessions_keyframe_relocalise, its oriented
+// form and the one inside hnet_sessions_keyframe_track_recover) around the unchanged launch_photo_align_robust.
 //
 // photo_thumbs_kernel / reloc_thumbs_kernel: one thread per thumbnail pixel reads its 8 x 8 block of the frame as eight 8-byte loads and runs
 // hnet_search::thumb_pixel's cascade on it: level 3 of 7m's pyramid bit for bit, 1 120 bytes per frame, without the levels in between.
@@ -9,11 +9,14 @@
 // doubles (20 008 bytes).  Thread t takes shifts t, t + 1024, t + 2048: per row of the overlap and group of four template pixels one dword of the template, two
 // of the image joined at the shift's byte offset (v_alignbyte_b32), a byte mask at the two ends of the row, and five packed-u8 dot products
 // (v_dot4_u32_u8) for Sa, Sb, Sab, Saa, Sbb.  Integer sums: whatever the grouping, they are the host reference's.  The score is
-// hnet_search::shift_score.  The best and the second are two reductions of the table under the header's total order, a fixed tree through LDS.
+// hnet_search::shift_score.  The best and the second are two reductions of the table under the header's total order, a fixed tree through LDS
+// (photo_search_kernel_dev.h, with the oriented kernel).
 // The per-slot kernels of the relocalisation are one wavefront each, fp64 on lane 0, and this file is built with -ffp-contract=off like
-// kernels_keyframe_map.hip: decide_relocalise and decide_revisit are the host reference's operations in its order.  The copy kernel moves 16-byte
+// kernels_keyframe_map.hip: decide_relocalise and decide_revisit are the host reference's operations in its order.  The pick and the decision are
+// templates over the call's record, instantiated here for the plain and for the oriented records.  The copy kernel moves 16-byte
 // vectors.  No atomics, nothing waits on another workgroup, nothing spins; every id, slot and candidate index is tested against its table.
-#include "photo_search_dev.h"
+#include "photo_search_oriented_dev.h"
+#include "photo_search_kernel_dev.h"
 
 namespace hnet {
 
@@ -27,16 +30,10 @@ constexpr int SV = NPIX / 16;                       // 16-byte vectors per frame
 constexpr int SV_BLOCKS = (SV + 255) / 256;
 constexpr int REC_DOUBLES = (int)(sizeof(RobustRec) / sizeof(double));
 constexpr int THUMB_BLOCKS = (ps::TPIX + 255) / 256;                 // 5 workgroups of 256 threads per thumbnail
-constexpr int PS_THREADS = 1024, PS_GUARD = 32;                      // guard bytes on either side of the image thumbnail in LDS
-constexpr int TWORDS = ps::TPIX / 4, ROW_WORDS = ps::TW / 4, BWORDS = (ps::TPIX + 2 * PS_GUARD) / 4;
-static_assert(ps::TW % 4 == 0 && PS_GUARD % 4 == 0 && PS_GUARD >= ps::MAX_RX + 2, "rows are whole dwords; the guard holds the farthest column of a shifted group");
-// the farthest dword a shift reads: row TH - 1, the last group of the row, shifted right by MAX_RX, and the dword after it
-static_assert(((PS_GUARD + (ps::TH - 1) * ps::TW + ps::MAX_RX + (ps::TW - 4)) >> 2) + 1 < BWORDS && PS_GUARD - ps::MAX_RX >= 0, "a shifted group stays inside the guards");
-static_assert(sizeof(RobustRec) % sizeof(double) == 0 && offsetof(RelocRec, rv) == 0 && offsetof(MapRevisit, rec) == 0 && sizeof(RelocRec) % sizeof(double) == 0 &&
-              sizeof(SearchRec) % 4 == 0, "RelocRec: the record first, as doubles");
+constexpr int PS_THREADS = 1024;
+static_assert(sizeof(RobustRec) % sizeof(double) == 0 && offsetof(RelocRec, rv) == 0 && offsetof(OrientedRelocRec, rv) == 0 && offsetof(MapRevisit, rec) == 0 &&
+              sizeof(RelocRec) % sizeof(double) == 0 && sizeof(SearchRec) % 4 == 0 && sizeof(OrientedRec) % 4 == 0, "the call's record: the alignment's first, as doubles");
 static_assert(ps::STEP == 8 && ps::TW * ps::STEP == IMG_W && ps::TH * ps::STEP == IMG_H, "a thumbnail pixel is an 8 x 8 block of the frame");
-
-__device__ inline bool map_ok(const MapStore& map) { return map.img != nullptr && map.capacity >= km::MIN_CAPACITY && map.capacity <= km::MAX_CAPACITY; }
 
 // thumbnail pixel `pix` of the frame at src (8-byte aligned): the block's rows as 8-byte loads into a local 8 x 8 block, then the header's cascade on it
 __device__ __forceinline__ uint8_t thumb_from_frame(const uint8_t* src, int pix) {
@@ -95,30 +92,9 @@ __device__ __forceinline__ void shift_sums_dot(const uint32_t* a_w, const uint32
     s.sa = (int32_t)sa; s.sb = (int32_t)sb; s.sab = (int32_t)sab; s.saa = (int32_t)saa; s.sbb = (int32_t)sbb;
 }
 
-// the workgroup's best of the table under the header's order; `around` >= 0: among the shifts outside the 3 x 3 around it.  Every thread returns it.
-__device__ __forceinline__ ps::Best table_best(const double* sc, int around, double* red_s, int32_t* red_i) {
-    const int tid = threadIdx.x;
-    ps::Best b;
-    ps::best_none(b);
-    for (int i = tid; i < ps::NSHIFT; i += PS_THREADS)
-        if (around < 0 || ps::outside3(i, around)) ps::offer(b, sc[i], i);
-    red_s[tid] = b.score;
-    red_i[tid] = b.index;
-    __syncthreads();
-    for (int st = PS_THREADS / 2; st > 0; st >>= 1) {
-        if (tid < st) {
-            ps::Best x = {red_s[tid], red_i[tid]};
-            ps::offer(x, red_s[tid + st], red_i[tid + st]);
-            red_s[tid] = x.score;
-            red_i[tid] = x.index;
-        }
-        __syncthreads();
-    }
-    b.score = red_s[0];
-    b.index = red_i[0];
-    __syncthreads();                                                      // (red_* are free again)
-    return b;
-}
+// the search part of a candidate's record: the pick compares plain and oriented records by it
+__device__ __forceinline__ const SearchRec& search_part(const SearchRec& r) { return r; }
+__device__ __forceinline__ const SearchRec& search_part(const OrientedRec& r) { return r.base; }
 }  // namespace
 
 // grid (THUMB_BLOCKS, count)
@@ -164,32 +140,19 @@ __global__ __launch_bounds__(PS_THREADS) void photo_search_kernel(const uint8_t*
         sc[i] = v;
     }
     __syncthreads();
-    const ps::Best best = table_best(sc, -1, red_s, red_i);
-    ps::Best second;
-    ps::best_none(second);
-    if (best.index >= 0) second = table_best(sc, best.index, red_s, red_i);      // (workgroup-uniform: every thread holds the same best)
-    if (tid == 0) {
-        ps::Sums s = {0, 0, 0, 0, 0, 0};
-        if (best.index >= 0) {
-            int dx, dy;
-            ps::index_shift(best.index, dx, dy);
-            shift_sums_dot(a_w, b_w, dx, dy, s);
-        }
-        ps::finish(best, second, s, o, rec[job]);
-    }
-    if (scores)
-        for (int i = tid; i < ps::NSHIFT; i += PS_THREADS) scores[(size_t)job * ps::NSHIFT + i] = sc[i];
+    search_finish<PS_THREADS>(sc, red_s, red_i, o, [&](int dx, int dy, ps::Sums& s) { shift_sums_dot(a_w, b_w, dx, dy, s); }, (size_t)job, rec, scores);
 }
 
-// grid (THUMB_BLOCKS * (M + 2), n)
+// grid (THUMB_BLOCKS * (M + 2), n); active != nullptr: a slot with active[b] == 0 has no candidate
 __global__ __launch_bounds__(256) void reloc_thumbs_kernel(const int32_t* __restrict__ ids, const int32_t* __restrict__ slot, int n_sessions,
-                                                           const KeyState* __restrict__ state, const uint8_t* __restrict__ key, MapStore map,
-                                                           const uint8_t* __restrict__ ring, int n_slots, uint8_t* __restrict__ thumbs, int32_t* __restrict__ valid) {
-    const int M = map_ok(map) ? map.capacity : 0;
+                                                           const int32_t* __restrict__ active, const KeyState* __restrict__ state, const uint8_t* __restrict__ key,
+                                                           MapStore map, const uint8_t* __restrict__ ring, int n_slots, uint8_t* __restrict__ thumbs,
+                                                           int32_t* __restrict__ valid) {
+    const int M = reloc_map_ok(map) ? map.capacity : 0;
     const int j = blockIdx.x / THUMB_BLOCKS, pix = (blockIdx.x - j * THUMB_BLOCKS) * 256 + threadIdx.x, b = blockIdx.y;
     if (j > M + 1) return;                                                // (the grid is the host's M + 2)
     const int id = ids[b], sc = slot[b];
-    const bool call_ok = id >= 0 && id < n_sessions && id < map.n_sessions && sc >= 0 && sc < n_slots;
+    const bool call_ok = (!active || active[b] != 0) && id >= 0 && id < n_sessions && id < map.n_sessions && sc >= 0 && sc < n_slots;
     const uint8_t* src = nullptr;
     if (call_ok) {
         if (j == 0) {
@@ -206,9 +169,12 @@ __global__ __launch_bounds__(256) void reloc_thumbs_kernel(const int32_t* __rest
     thumbs[((size_t)b * (M + 2) + j) * ps::TPIX + pix] = thumb_from_frame(src, pix);
 }
 
+// SRec / Out: SearchRec / RelocRec, or OrientedRec / OrientedRelocRec
+template <class SRec, class Out>
 __global__ __launch_bounds__(KEY_THREADS) void reloc_pick_kernel(const int32_t* __restrict__ ids, int n, int n_sessions, const KeyState* __restrict__ state, int M,
-                                                                 const int32_t* __restrict__ valid, const SearchRec* __restrict__ srec, float* __restrict__ x0,
-                                                                 int32_t* __restrict__ cand, int32_t* __restrict__ mslot, RelocRec* __restrict__ out) {
+                                                                 const int32_t* __restrict__ valid, const SRec* __restrict__ srec, float* __restrict__ x0,
+                                                                 int32_t* __restrict__ cand, int32_t* __restrict__ mslot, Out* __restrict__ out) {
+    static_assert(sizeof(out->search) == sizeof(SRec), "the record holds the pick's search record");
     const int b = blockIdx.x;
     if (b >= n || threadIdx.x != 0) return;
     const int id = ids[b];
@@ -221,17 +187,17 @@ __global__ __launch_bounds__(KEY_THREADS) void reloc_pick_kernel(const int32_t* 
         if (state[id].has_key != 0) km::origin_curr(state[id], hb);
         for (int c = 0; c <= M; c++) {
             if (valid[(size_t)b * (M + 1) + c] == 0) continue;
-            const SearchRec& r = srec[(size_t)b * (M + 1) + c];
+            const SearchRec& r = search_part(srec[(size_t)b * (M + 1) + c]);
             searched++;
             found += r.flags == ps::FOUND ? 1 : 0;
             rl::offer(p, c, r);
         }
     }
-    const SearchRec* pick = p.index >= 0 ? srec + (size_t)b * (M + 1) + p.index : nullptr;
+    const SRec* pick = p.index >= 0 ? srec + (size_t)b * (M + 1) + p.index : nullptr;
     uint32_t* so = reinterpret_cast<uint32_t*>(&out[b].search);
     const uint32_t* si = reinterpret_cast<const uint32_t*>(pick);
-    for (int k = 0; k < (int)(sizeof(SearchRec) / 4); k++) so[k] = pick ? si[k] : 0u;
-    for (int k = 0; k < 8; k++) x0[(size_t)b * 8 + k] = pick ? pick->start_px[k] : kf::quiet_nan();
+    for (int k = 0; k < (int)(sizeof(SRec) / 4); k++) so[k] = pick ? si[k] : 0u;
+    for (int k = 0; k < 8; k++) x0[(size_t)b * 8 + k] = pick ? search_part(*pick).start_px[k] : kf::quiet_nan();
     cand[b] = p.index;
     mslot[b] = p.index >= 1 ? p.index - 1 : -1;
     out[b].target = rl::target_of(p.index);
@@ -254,13 +220,15 @@ __global__ __launch_bounds__(256) void reloc_gather_kernel(const int32_t* __rest
     curr[(size_t)b * SV + v] = q;
 }
 
+// Out: RelocRec or OrientedRelocRec
+template <class Out>
 __global__ __launch_bounds__(KEY_THREADS) void reloc_decide_kernel(const int32_t* __restrict__ ids, int n, int n_sessions, const RobustRec* __restrict__ rec,
                                                                    const float* x0, const int32_t* __restrict__ cand, RelocOpts opts, KeyState* state, MapStore map,
-                                                                   RelocRec* out, int32_t* __restrict__ attach) {
+                                                                   Out* out, int32_t* __restrict__ attach) {
     const int b = blockIdx.x, t = threadIdx.x;
     if (b >= n) return;
     const int id = ids[b];
-    const int M = map_ok(map) ? map.capacity : 0;
+    const int M = reloc_map_ok(map) ? map.capacity : 0;
     const bool valid = id >= 0 && id < n_sessions && id < map.n_sessions;
     int c = cand[b];
     if (!valid || c < 0 || c > M) c = -1;
@@ -295,6 +263,22 @@ __global__ __launch_bounds__(KEY_THREADS) void reloc_decide_kernel(const int32_t
 
 namespace {
 bool bad_grid(int n) { return n < 1 || n > 65535; }
+
+template <class SRec, class Out>
+hipError_t reloc_pick(const int32_t* ids, int n, int n_sessions, const KeyState* state, int M, const int32_t* valid, const SRec* srec, float* x0, int32_t* cand,
+                      int32_t* mslot, Out* out, hipStream_t s) {
+    if (n < 1 || M < 0 || M > km::MAX_CAPACITY) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((reloc_pick_kernel<SRec, Out>), dim3((unsigned)n), dim3(KEY_THREADS), 0, s, ids, n, n_sessions, state, M, valid, srec, x0, cand, mslot, out);
+    return hipGetLastError();
+}
+
+template <class Out>
+hipError_t reloc_decide(const int32_t* ids, int n, int n_sessions, const RobustRec* rec, const float* x0, const int32_t* cand, const RelocOpts& opts, KeyState* state,
+                        const MapStore& map, Out* out, int32_t* attach, hipStream_t s) {
+    if (n < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((reloc_decide_kernel<Out>), dim3((unsigned)n), dim3(KEY_THREADS), 0, s, ids, n, n_sessions, rec, x0, cand, opts, state, map, out, attach);
+    return hipGetLastError();
+}
 }  // namespace
 
 hipError_t launch_photo_thumbs(const uint8_t* frames, const int32_t* idx, int n_frames, int count, uint8_t* thumbs, hipStream_t s) {
@@ -312,20 +296,23 @@ hipError_t launch_photo_search(const uint8_t* thumbs, int ta_stride, int tb_stri
     return hipGetLastError();
 }
 
-hipError_t launch_reloc_thumbs(const int32_t* ids, const int32_t* slot, int n, int n_sessions, const KeyState* state, const uint8_t* key, const MapStore& map,
-                               const uint8_t* ring, int n_slots, uint8_t* thumbs, int32_t* valid, hipStream_t s) {
+hipError_t launch_reloc_thumbs(const int32_t* ids, const int32_t* slot, int n, int n_sessions, const int32_t* active, const KeyState* state, const uint8_t* key,
+                               const MapStore& map, const uint8_t* ring, int n_slots, uint8_t* thumbs, int32_t* valid, hipStream_t s) {
     const int M = map.img ? map.capacity : 0;
     if (bad_grid(n) || M < 0 || M > km::MAX_CAPACITY || ((((uintptr_t)key) | (uintptr_t)map.img | (uintptr_t)ring) & 7)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(reloc_thumbs_kernel, dim3((unsigned)(THUMB_BLOCKS * (M + 2)), (unsigned)n), dim3(256), 0, s, ids, slot, n_sessions, state, key, map, ring, n_slots,
-                       thumbs, valid);
+    hipLaunchKernelGGL(reloc_thumbs_kernel, dim3((unsigned)(THUMB_BLOCKS * (M + 2)), (unsigned)n), dim3(256), 0, s, ids, slot, n_sessions, active, state, key, map,
+                       ring, n_slots, thumbs, valid);
     return hipGetLastError();
 }
 
 hipError_t launch_reloc_pick(const int32_t* ids, int n, int n_sessions, const KeyState* state, int M, const int32_t* valid, const SearchRec* srec, float* x0,
                              int32_t* cand, int32_t* mslot, RelocRec* out, hipStream_t s) {
-    if (n < 1 || M < 0 || M > km::MAX_CAPACITY) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(reloc_pick_kernel, dim3((unsigned)n), dim3(KEY_THREADS), 0, s, ids, n, n_sessions, state, M, valid, srec, x0, cand, mslot, out);
-    return hipGetLastError();
+    return reloc_pick(ids, n, n_sessions, state, M, valid, srec, x0, cand, mslot, out, s);
+}
+
+hipError_t launch_reloc_pick(const int32_t* ids, int n, int n_sessions, const KeyState* state, int M, const int32_t* valid, const OrientedRec* srec, float* x0,
+                             int32_t* cand, int32_t* mslot, OrientedRelocRec* out, hipStream_t s) {
+    return reloc_pick(ids, n, n_sessions, state, M, valid, srec, x0, cand, mslot, out, s);
 }
 
 hipError_t launch_reloc_gather(const int32_t* ids, const int32_t* slot, int n, int n_sessions, const int32_t* cand, const uint8_t* key, const MapStore& map,
@@ -339,9 +326,12 @@ hipError_t launch_reloc_gather(const int32_t* ids, const int32_t* slot, int n, i
 
 hipError_t launch_reloc_decide(const int32_t* ids, int n, int n_sessions, const RobustRec* rec, const float* x0, const int32_t* cand, const RelocOpts& opts,
                                KeyState* state, const MapStore& map, RelocRec* out, int32_t* attach, hipStream_t s) {
-    if (n < 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(reloc_decide_kernel, dim3((unsigned)n), dim3(KEY_THREADS), 0, s, ids, n, n_sessions, rec, x0, cand, opts, state, map, out, attach);
-    return hipGetLastError();
+    return reloc_decide(ids, n, n_sessions, rec, x0, cand, opts, state, map, out, attach, s);
+}
+
+hipError_t launch_reloc_decide(const int32_t* ids, int n, int n_sessions, const RobustRec* rec, const float* x0, const int32_t* cand, const RelocOpts& opts,
+                               KeyState* state, const MapStore& map, OrientedRelocRec* out, int32_t* attach, hipStream_t s) {
+    return reloc_decide(ids, n, n_sessions, rec, x0, cand, opts, state, map, out, attach, s);
 }
 
 }  // namespace hnet

@@ -1,41 +1,31 @@
 // kernels_photo_search_oriented.hip — the device side of the coarse search under a table of orientation hypotheses (include/hnet.h
-// hnet_op_photo_search_oriented, hnet_sessions_photo_search_oriented) and of the oriented relocalisation
-// (hnet_sessions_keyframe_relocalise_oriented) around the unchanged launch_photo_align_robust.
+// hnet_op_photo_search_oriented, hnet_sessions_photo_search_oriented).  The oriented relocalisation
+// (hnet_sessions_keyframe_relocalise_oriented) runs these two kernels between the per-slot kernels of kernels_photo_search.hip.
 //
 // photo_search_oriented_kernel: one workgroup of 256 threads per (entry, template, image) job.  The template thumbnail goes to LDS, the workgroup warps it
 // there by the entry's integer matrix (hnet_search_oriented::warp_pixel) into template bytes and mask bytes: no launch of its own and no trip through
 // global memory.  The image sits between 7r's two zeroed guards.  Thread t takes shifts t, t + 256, ...: 7r's scheme with the mask, per row of the overlap
 // and group of four pixels one dword of the template, one of the mask, two of the image joined at the shift's byte offset, and six packed-u8 dot
 // products (7r's five and n): n from the mask, Sb = dot(q, m), Sbb = dot(q & 255 m, q); Sa, Saa and Sab as in 7r, the warped template being zero where
-// masked.  Integer sums: whatever the grouping, they are the host reference's.  The score is hnet_search::shift_score, the entry's best and second 7r's
-// two reductions.
+// masked.  Integer sums: whatever the grouping, they are the host reference's.  The score is hnet_search::shift_score; the entry's best and second and
+// its record are photo_search_kernel_dev.h's search_finish, the tail 7r's kernel runs.
 // 256 threads and not 7r's 1024: with n_hyp times the workgroups the launch is bound by throughput, and 28 KB of LDS per workgroup lets five of them
 // share a compute unit (20 wavefronts) where 1024 threads and 37 KB allow two.
 // photo_search_winner_kernel: one wavefront per (template, image) pair, lane h holds entry h's best; the winner and the runner-up under
 // hnet_search_oriented::hyp_better by a butterfly of lane exchanges (a total order: every lane ends with the same answer), lane 0 writes the record.
-// The per-slot kernels of the relocalisation are 7r's on the wider records, fp64 on lane 0; this file is built with -ffp-contract=off.
+// This file is built with -ffp-contract=off.
 // No atomics, no scratch, nothing waits on another workgroup; every table index, id, slot and candidate index is tested against its bound.
 #include "photo_search_oriented_dev.h"
+#include "photo_search_kernel_dev.h"
 
 namespace hnet {
 
-namespace kf = hnet_keyframe;
-namespace km = hnet_keyframe_map;
 namespace ps = hnet_search;
 namespace po = hnet_search_oriented;
-namespace rl = hnet_keyframe_reloc;
 
 namespace {
-constexpr int REC_DOUBLES = (int)(sizeof(RobustRec) / sizeof(double));
-constexpr int PO_THREADS = 256, PS_GUARD = 32;                       // guard bytes on either side of the image thumbnail in LDS
-constexpr int TWORDS = ps::TPIX / 4, ROW_WORDS = ps::TW / 4, BWORDS = (ps::TPIX + 2 * PS_GUARD) / 4;
-static_assert(ps::TW % 4 == 0 && PS_GUARD % 4 == 0 && PS_GUARD >= ps::MAX_RX + 2, "rows are whole dwords; the guard holds the farthest column of a shifted group");
-// the farthest dword a shift reads: row TH - 1, the last group of the row, shifted right by MAX_RX, and the dword after it
-static_assert(((PS_GUARD + (ps::TH - 1) * ps::TW + ps::MAX_RX + (ps::TW - 4)) >> 2) + 1 < BWORDS && PS_GUARD - ps::MAX_RX >= 0, "a shifted group stays inside the guards");
-static_assert(sizeof(RobustRec) % sizeof(double) == 0 && offsetof(MapRevisit, rec) == 0 && sizeof(SearchRec) % 4 == 0 && sizeof(OrientedRec) % 4 == 0 &&
-              sizeof(OrientedRec) / 4 <= 64, "the record first, as doubles; a wavefront zeroes a search record in one step");
-
-__device__ inline bool map_ok(const MapStore& map) { return map.img != nullptr && map.capacity >= km::MIN_CAPACITY && map.capacity <= km::MAX_CAPACITY; }
+constexpr int PO_THREADS = 256;
+static_assert(sizeof(SearchRec) % 4 == 0 && sizeof(OrientedRec) % 4 == 0 && sizeof(OrientedRec) / 4 <= 64, "a wavefront zeroes a search record in one step");
 
 // hnet_search_oriented::shift_sums on the dwords in LDS: a_w the warped template [TWORDS], m_w its mask (bytes 1 / 0), b_w the image behind its guard
 __device__ __forceinline__ void shift_sums_masked(const uint32_t* a_w, const uint32_t* m_w, const uint32_t* b_w, int dx, int dy, ps::Sums& s) {
@@ -63,31 +53,6 @@ __device__ __forceinline__ void shift_sums_masked(const uint32_t* a_w, const uin
         }
     }
     s.n = (int32_t)n; s.sa = (int32_t)sa; s.sb = (int32_t)sb; s.sab = (int32_t)sab; s.saa = (int32_t)saa; s.sbb = (int32_t)sbb;
-}
-
-// the workgroup's best of the table under 7r's order; `around` >= 0: among the shifts outside the 3 x 3 around it.  Every thread returns it.
-__device__ __forceinline__ ps::Best table_best(const double* sc, int around, double* red_s, int32_t* red_i) {
-    const int tid = threadIdx.x;
-    ps::Best b;
-    ps::best_none(b);
-    for (int i = tid; i < ps::NSHIFT; i += PO_THREADS)
-        if (around < 0 || ps::outside3(i, around)) ps::offer(b, sc[i], i);
-    red_s[tid] = b.score;
-    red_i[tid] = b.index;
-    __syncthreads();
-    for (int st = PO_THREADS / 2; st > 0; st >>= 1) {
-        if (tid < st) {
-            ps::Best x = {red_s[tid], red_i[tid]};
-            ps::offer(x, red_s[tid + st], red_i[tid + st]);
-            red_s[tid] = x.score;
-            red_i[tid] = x.index;
-        }
-        __syncthreads();
-    }
-    b.score = red_s[0];
-    b.index = red_i[0];
-    __syncthreads();                                                      // (red_* are free again)
-    return b;
 }
 
 // the better of a lane's entry and every other lane's: hnet_search_oriented::offer_hyp is associative and commutative, so every lane returns the same
@@ -148,21 +113,7 @@ __global__ __launch_bounds__(PO_THREADS) void photo_search_oriented_kernel(const
         sc[i] = v;
     }
     __syncthreads();
-    const ps::Best best = table_best(sc, -1, red_s, red_i);
-    ps::Best second;
-    ps::best_none(second);
-    if (best.index >= 0) second = table_best(sc, best.index, red_s, red_i);      // (workgroup-uniform: every thread holds the same best)
-    if (tid == 0) {
-        ps::Sums s = {0, 0, 0, 0, 0, 0};
-        if (best.index >= 0) {
-            int dx, dy;
-            ps::index_shift(best.index, dx, dy);
-            shift_sums_masked(a_w, m_w, b_w, dx, dy, s);
-        }
-        ps::finish(best, second, s, o, hrec[slot]);
-    }
-    if (scores)
-        for (int i = tid; i < ps::NSHIFT; i += PO_THREADS) scores[slot * ps::NSHIFT + i] = sc[i];
+    search_finish<PO_THREADS>(sc, red_s, red_i, o, [&](int dx, int dy, ps::Sums& s) { shift_sums_masked(a_w, m_w, b_w, dx, dy, s); }, slot, hrec, scores);
 }
 
 // grid (jobs)
@@ -186,83 +137,6 @@ __global__ __launch_bounds__(KEY_THREADS) void photo_search_winner_kernel(const 
     if (lane == 0) po::finish(ph, hyps, n_hyp, win, second, n_scored, out[job]);
 }
 
-// 7r's reloc_pick_kernel on the oriented records
-__global__ __launch_bounds__(KEY_THREADS) void reloc_pick_oriented_kernel(const int32_t* __restrict__ ids, int n, int n_sessions, const KeyState* __restrict__ state,
-                                                                          int M, const int32_t* __restrict__ valid, const OrientedRec* __restrict__ osrec,
-                                                                          float* __restrict__ x0, int32_t* __restrict__ cand, int32_t* __restrict__ mslot,
-                                                                          OrientedRelocRec* __restrict__ out) {
-    const int b = blockIdx.x;
-    if (b >= n || threadIdx.x != 0) return;
-    const int id = ids[b];
-    double hb[9];
-    for (int k = 0; k < 9; k++) hb[k] = (k & 3) == 0 ? 1.0 : 0.0;
-    rl::Pick p;
-    rl::pick_none(p);
-    int searched = 0, found = 0;
-    if (id >= 0 && id < n_sessions && M >= 0 && M <= km::MAX_CAPACITY) {
-        if (state[id].has_key != 0) km::origin_curr(state[id], hb);
-        for (int c = 0; c <= M; c++) {
-            if (valid[(size_t)b * (M + 1) + c] == 0) continue;
-            const SearchRec& r = osrec[(size_t)b * (M + 1) + c].base;
-            searched++;
-            found += r.flags == ps::FOUND ? 1 : 0;
-            rl::offer(p, c, r);
-        }
-    }
-    const OrientedRec* pick = p.index >= 0 ? osrec + (size_t)b * (M + 1) + p.index : nullptr;
-    uint32_t* so = reinterpret_cast<uint32_t*>(&out[b].search);
-    const uint32_t* si = reinterpret_cast<const uint32_t*>(pick);
-    for (int k = 0; k < (int)(sizeof(OrientedRec) / 4); k++) so[k] = pick ? si[k] : 0u;
-    for (int k = 0; k < 8; k++) x0[(size_t)b * 8 + k] = pick ? pick->base.start_px[k] : kf::quiet_nan();
-    cand[b] = p.index;
-    mslot[b] = p.index >= 1 ? p.index - 1 : -1;
-    out[b].target = rl::target_of(p.index);
-    out[b].n_searched = searched;
-    out[b].n_found = found;
-    out[b].pad = 0;
-    for (int k = 0; k < 9; k++) out[b].rv.h_origin_before[k] = hb[k];
-}
-
-// 7r's reloc_decide_kernel on the oriented records
-__global__ __launch_bounds__(KEY_THREADS) void reloc_decide_oriented_kernel(const int32_t* __restrict__ ids, int n, int n_sessions, const RobustRec* __restrict__ rec,
-                                                                            const float* x0, const int32_t* __restrict__ cand, RelocOpts opts, KeyState* state,
-                                                                            MapStore map, OrientedRelocRec* out, int32_t* __restrict__ attach) {
-    const int b = blockIdx.x, t = threadIdx.x;
-    if (b >= n) return;
-    const int id = ids[b];
-    const int M = map_ok(map) ? map.capacity : 0;
-    const bool valid = id >= 0 && id < n_sessions && id < map.n_sessions;
-    int c = cand[b];
-    if (!valid || c < 0 || c > M) c = -1;
-    const double* src = reinterpret_cast<const double*>(rec + b);
-    double* dst = reinterpret_cast<double*>(out + b);
-    for (int i = t; i < REC_DOUBLES; i += KEY_THREADS) dst[i] = c >= 0 ? src[i] : 0.0;
-    if (t != 0) return;
-    MapRevisit& rv = out[b].rv;
-    if (!valid) {
-        for (int i = REC_DOUBLES; i < (int)(sizeof(MapRevisit) / sizeof(double)); i++) dst[i] = 0.0;
-        rv.slot = -1;
-        rv.flags = rl::RL_NO_CANDIDATE;
-        attach[b] = 0;
-        return;
-    }
-    if (c == 0) {
-        rl::decide_relocalise(state[id], x0 + (size_t)b * 8, rv.h_origin_before, rec[b], opts, state[id], rv);
-        attach[b] = 0;
-        return;
-    }
-    MapOpts mo;
-    rl::revisit_opts(opts, mo);
-    if (M > 0) {
-        const MapEntry* e = map.entry + (size_t)id * M;
-        attach[b] = km::decide_revisit(state[id], map.state[id], c >= 1 ? e + (c - 1) : nullptr, c - 1, 0, x0 + (size_t)b * 8, rv.h_origin_before, rec[b], mo, state[id],
-                                       map.state[id], rv);
-    } else {                                                              // without a map only "no pick" arrives here
-        MapState none = {-1, 0, 0, 0};
-        attach[b] = km::decide_revisit(state[id], none, nullptr, -1, 0, x0 + (size_t)b * 8, rv.h_origin_before, rec[b], mo, state[id], none, rv);
-    }
-}
-
 hipError_t launch_photo_search_oriented(const uint8_t* thumbs, int ta_stride, int tb_stride, int tb_off, int jobs_x, int n, const int32_t* valid,
                                         const SearchOpts& opts, const SearchHyp* hyps, int n_hyp, SearchRec* hrec, double* scores, hipStream_t s) {
     if (n < 1 || n > 65535 || jobs_x < 1 || jobs_x > RELOC_MAX_CANDIDATES || ta_stride < 1 || tb_stride < 1 || tb_off < 0 || !thumbs || !hrec || !hyps ||
@@ -276,20 +150,6 @@ hipError_t launch_photo_search_oriented(const uint8_t* thumbs, int ta_stride, in
 hipError_t launch_photo_search_winner(const SearchRec* hrec, const SearchHyp* hyps, int n_hyp, int jobs, const int32_t* valid, OrientedRec* out, hipStream_t s) {
     if (jobs < 1 || !hrec || !hyps || !out || n_hyp < 1 || n_hyp > SEARCH_MAX_HYP) return hipErrorInvalidValue;
     hipLaunchKernelGGL(photo_search_winner_kernel, dim3((unsigned)jobs), dim3(KEY_THREADS), 0, s, hrec, hyps, n_hyp, jobs, valid, out);
-    return hipGetLastError();
-}
-
-hipError_t launch_reloc_pick_oriented(const int32_t* ids, int n, int n_sessions, const KeyState* state, int M, const int32_t* valid, const OrientedRec* osrec,
-                                      float* x0, int32_t* cand, int32_t* mslot, OrientedRelocRec* out, hipStream_t s) {
-    if (n < 1 || M < 0 || M > km::MAX_CAPACITY) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(reloc_pick_oriented_kernel, dim3((unsigned)n), dim3(KEY_THREADS), 0, s, ids, n, n_sessions, state, M, valid, osrec, x0, cand, mslot, out);
-    return hipGetLastError();
-}
-
-hipError_t launch_reloc_decide_oriented(const int32_t* ids, int n, int n_sessions, const RobustRec* rec, const float* x0, const int32_t* cand,
-                                        const RelocOpts& opts, KeyState* state, const MapStore& map, OrientedRelocRec* out, int32_t* attach, hipStream_t s) {
-    if (n < 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(reloc_decide_oriented_kernel, dim3((unsigned)n), dim3(KEY_THREADS), 0, s, ids, n, n_sessions, rec, x0, cand, opts, state, map, out, attach);
     return hipGetLastError();
 }
 

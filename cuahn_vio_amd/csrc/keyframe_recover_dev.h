@@ -27,10 +27,6 @@ static_assert(sizeof(RecoverOpts) == sizeof(KeyOpts) + sizeof(RelocOpts) && size
 // active[b] (1: the frame is LOST and the relocalisation is to run on it; 0 for an id outside the table)
 hipError_t launch_recover_decide(const KeyTable& tab, int n, int n_sessions, const RobustRec* rec, const float* x0, const KeyOpts& opts, KeyState* state,
                                  KeyTrack* out, int32_t* copy, RecoverStash* stash, int32_t* active, hipStream_t s);
-// launch_reloc_thumbs with every candidate of a slot with active[b] == 0 marked absent (and no thumbnail made for it): on that input the search, the
-// winner, the pick, the gather, the alignment, the decision and the attach do nothing for the slot
-hipError_t launch_recover_thumbs(const int32_t* ids, const int32_t* slot, int n, int n_sessions, const int32_t* active, const KeyState* state, const uint8_t* key,
-                                 const MapStore& map, const uint8_t* ring, int n_slots, uint8_t* thumbs, int32_t* valid, hipStream_t s);
 // One wavefront per slot, after the relocalisation's decision (reloc [n]: its records): hnet_keyframe_recovery::finish on the active slots (the state and
 // track[b] in place) -> copy2[b] and redo[b] (1: unrecovered, T1 was restored), and out[b] = {track[b] | reloc[b], or the zero record when inactive}
 hipError_t launch_recover_finish(const int32_t* ids, int n, int n_sessions, const int32_t* active, const RecoverStash* stash, const OrientedRelocRec* reloc,

@@ -34,9 +34,11 @@ hipError_t launch_photo_search(const uint8_t* thumbs, int ta_stride, int tb_stri
 
 // ---- a relocalise (ids, slot: the call's table {ids [n] | curr ring slot [n]}); M = map.capacity, or 0 without a map (map.img == nullptr).  Per listed
 // session b the candidates are index 0 (the held keyframe) and 1 + slot (a valid entry other than the current keyframe's); thumbs [n][M + 2] holds theirs
-// and, last, the current frame's; valid [n][M + 1] whether a candidate exists (0 for all when the id or the ring slot is outside its table)
-hipError_t launch_reloc_thumbs(const int32_t* ids, const int32_t* slot, int n, int n_sessions, const KeyState* state, const uint8_t* key, const MapStore& map,
-                               const uint8_t* ring, int n_slots, uint8_t* thumbs, int32_t* valid, hipStream_t s);
+// and, last, the current frame's; valid [n][M + 1] whether a candidate exists (0 for all when the id or the ring slot is outside its table).
+// active != nullptr (a track with recovery): every candidate of a slot with active[b] == 0 is absent and no thumbnail is made for it; on that input the
+// search, the winner, the pick, the gather, the alignment, the decision and the attach do nothing for the slot
+hipError_t launch_reloc_thumbs(const int32_t* ids, const int32_t* slot, int n, int n_sessions, const int32_t* active, const KeyState* state, const uint8_t* key,
+                               const MapStore& map, const uint8_t* ring, int n_slots, uint8_t* thumbs, int32_t* valid, hipStream_t s);
 // One wavefront per slot, lane 0, over the search records srec [n][M + 1]: hnet_keyframe_reloc::offer in the order of the indices -> cand[b] (the index or
 // -1), mslot[b] (the map slot or -1), x0[b] (the pick's start, quiet NaNs without one), and out[b]'s search record, target, counts and h_origin_before
 hipError_t launch_reloc_pick(const int32_t* ids, int n, int n_sessions, const KeyState* state, int M, const int32_t* valid, const SearchRec* srec, float* x0,
@@ -50,3 +52,10 @@ hipError_t launch_reloc_decide(const int32_t* ids, int n, int n_sessions, const 
                                KeyState* state, const MapStore& map, RelocRec* out, int32_t* attach, hipStream_t s);
 
 }  // namespace hnet
+
+struct hnet_ctx;
+struct hnet_photo_search_opts;
+namespace capi {
+// HNET_OK and o <- *opts with its pad zeroed, or the context's error set for options no search may run under (capi_photo_search.hip)
+int photo_search_check_opts(hnet_ctx* c, const hnet_photo_search_opts* opts, const char* who, hnet::SearchOpts& o);
+}  // namespace capi

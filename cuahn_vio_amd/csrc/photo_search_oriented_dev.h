@@ -35,11 +35,11 @@ hipError_t launch_photo_search_oriented(const uint8_t* thumbs, int ta_stride, in
 hipError_t launch_photo_search_winner(const SearchRec* hrec, const SearchHyp* hyps, int n_hyp, int jobs, const int32_t* valid, OrientedRec* out, hipStream_t s);
 
 // ---- the oriented relocalise: launch_reloc_thumbs, launch_reloc_gather and launch_keyframe_map_attach are 7r's and 7q's; the pick and the decision are
-// 7r's kernels on the wider records (osrec [n][M + 1], out [n])
-hipError_t launch_reloc_pick_oriented(const int32_t* ids, int n, int n_sessions, const KeyState* state, int M, const int32_t* valid, const OrientedRec* osrec,
-                                      float* x0, int32_t* cand, int32_t* mslot, OrientedRelocRec* out, hipStream_t s);
-hipError_t launch_reloc_decide_oriented(const int32_t* ids, int n, int n_sessions, const RobustRec* rec, const float* x0, const int32_t* cand,
-                                        const RelocOpts& opts, KeyState* state, const MapStore& map, OrientedRelocRec* out, int32_t* attach, hipStream_t s);
+// photo_search_dev.h's on the wider records (srec [n][M + 1], out [n]): the same kernel templates, instantiated in kernels_photo_search.hip
+hipError_t launch_reloc_pick(const int32_t* ids, int n, int n_sessions, const KeyState* state, int M, const int32_t* valid, const OrientedRec* srec, float* x0,
+                             int32_t* cand, int32_t* mslot, OrientedRelocRec* out, hipStream_t s);
+hipError_t launch_reloc_decide(const int32_t* ids, int n, int n_sessions, const RobustRec* rec, const float* x0, const int32_t* cand, const RelocOpts& opts,
+                               KeyState* state, const MapStore& map, OrientedRelocRec* out, int32_t* attach, hipStream_t s);
 
 }  // namespace hnet
 
