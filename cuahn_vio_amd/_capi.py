@@ -53,6 +53,8 @@ SYMBOLS = [
     "hnet_keyframe_relocalise_default_opts", "hnet_sessions_keyframe_relocalise",
     "hnet_photo_search_make_hyp", "hnet_photo_search_yaw_table", "hnet_photo_search_default_yaw_table", "hnet_op_photo_search_oriented",
     "hnet_sessions_photo_search_oriented", "hnet_sessions_keyframe_relocalise_oriented",
+    "hnet_photo_search_fine_default_opts", "hnet_photo_search_fine_yaw_table", "hnet_op_photo_search_fine", "hnet_sessions_photo_search_fine",
+    "hnet_sessions_keyframe_relocalise_fine",
     "hnet_keyframe_default_opts", "hnet_sessions_enable_keyframes", "hnet_sessions_keyframe_track", "hnet_sessions_keyframe_reset", "hnet_sessions_get_keyframe",
     "hnet_sessions_last_keyframe_device_ms",
     "hnet_keyframe_revisit_default_opts", "hnet_sessions_enable_keyframe_map", "hnet_sessions_keyframe_revisit", "hnet_sessions_keyframe_map_info",
@@ -449,6 +451,73 @@ def photo_search_table(hyps):
     return _np.ascontiguousarray(hyps, PHOTO_SEARCH_HYP_DTYPE).reshape(-1)
 
 
+# the fine stage around the oriented winner (hnet_op_photo_search_fine): the oriented record, then the fine part: the final start, flags PSF_* (include/hnet.h
+# HNET_PSF_*), the best fine entry j and its offsets (ex, ey), the level-2 shift, the overlap, the score, the fine entry's matrix and the sums.  A fine
+# score table is [n_fine, 9, 9] doubles, index [j, ey + 4, ex + 4]
+PHOTO_SEARCH_FINE_PART_DTYPE = _np.dtype([("start_px", "<f4", 8), ("flags", "<i4"), ("j", "<i4"), ("ex", "<i4"), ("ey", "<i4"), ("sx", "<i4"), ("sy", "<i4"),
+                                          ("n_overlap", "<i4"), ("pad0", "<i4"), ("score", "<f8"), ("a", "<f8", 4), ("sa", "<i4"), ("sb", "<i4"), ("sab", "<i4"),
+                                          ("saa", "<i4"), ("sbb", "<i4"), ("pad1", "<i4")])
+PHOTO_SEARCH_FINE_DTYPE = _np.dtype([("coarse", PHOTO_SEARCH_ORIENTED_DTYPE), ("fine", PHOTO_SEARCH_FINE_PART_DTYPE)])
+KEYFRAME_RELOC_FINE_DTYPE = _np.dtype([("base", KEYFRAME_RELOC_ORIENTED_DTYPE), ("fine", PHOTO_SEARCH_FINE_PART_DTYPE)])
+assert PHOTO_SEARCH_FINE_PART_DTYPE.itemsize == 128 and PHOTO_SEARCH_FINE_DTYPE.itemsize == 288 and KEYFRAME_RELOC_FINE_DTYPE.itemsize == 2040 + 128
+PSF_REFINED, PSF_SKIPPED, PSF_NOTHING_SCORED, PSF_LOW_SCORE = 1, 2, 4, 8
+PSF_MAX_FINE, PSF_MAX_RADIUS, PSF_SHIFTS = 9, 4, 9
+
+
+class PhotoSearchFineOpts(C.Structure):
+    """hnet_photo_search_fine_opts: the radius of the fine shifts (level-2 pixels), the entries per row of the fine table and the lowest score of a
+    REFINED result (the coarse default, not calibrated for level 2)"""
+    _fields_ = [("radius", C.c_int32), ("n_fine", C.c_int32), ("min_score", C.c_double), ("pad", C.c_int32 * 2)]
+
+
+assert C.sizeof(PhotoSearchFineOpts) == 24
+
+
+def photo_search_fine_opts(**kw):
+    """the defaults of hnet_photo_search_fine_default_opts with the given fields (radius, n_fine, min_score) replaced"""
+    o = PhotoSearchFineOpts()
+    lib().hnet_photo_search_fine_default_opts(C.byref(o))
+    for k, v in kw.items():
+        if k not in ("radius", "n_fine", "min_score"):
+            raise TypeError(f"hnet_photo_search_fine_opts has no field {k!r}")
+        setattr(o, k, v)
+    return o
+
+
+def photo_search_fine_yaw_table(first_deg=-180.0, step_deg=6.0, count=PS_DEFAULT_HYP, n_fine=5):
+    """[count, n_fine] entries around those of photo_search_yaw_table(first_deg, step_deg, count) (hnet_photo_search_fine_yaw_table)"""
+    if not 1 <= int(count) <= PS_MAX_HYP or not 1 <= int(n_fine) <= PSF_MAX_FINE:
+        raise ValueError("hnet_photo_search_fine_yaw_table: 1 <= count <= 64, 1 <= n_fine <= 9")
+    out = _np.zeros((int(count), int(n_fine)), PHOTO_SEARCH_HYP_DTYPE)
+    if not lib().hnet_photo_search_fine_yaw_table(float(first_deg), float(step_deg), int(count), int(n_fine), out.ctypes.data):
+        raise ValueError("hnet_photo_search_fine_yaw_table: finite angles")
+    return out
+
+
+def photo_search_fine_table(fine, hyps, n_fine, step_deg=None):
+    """the fine table a call passes on -> [n_hyp, n_fine] of PHOTO_SEARCH_HYP_DTYPE.  fine given: as it is (the library refuses what it must).  fine None:
+    the table that matches `hyps`: for hyps None the default tables' (photo_search_fine_yaw_table()); else entry [h, j] is hyps[h] turned by
+    (j - (n_fine - 1) / 2) (step_deg / n_fine) degrees at its own scale, step_deg defaulting to the smallest angle between two neighbouring entries of
+    hyps (6 degrees for a single entry), and for odd n_fine the middle entry is hyps[h] itself"""
+    n_fine = int(n_fine)
+    if fine is not None:
+        return _np.ascontiguousarray(fine, PHOTO_SEARCH_HYP_DTYPE).reshape(-1, n_fine)
+    if hyps is None:
+        return photo_search_fine_yaw_table(n_fine=n_fine)
+    h = photo_search_table(hyps)
+    deg = _np.rad2deg(_np.arctan2(h["a"][:, 2], h["a"][:, 0]))
+    scale = _np.hypot(h["a"][:, 0], h["a"][:, 2])
+    if step_deg is None:
+        d = _np.abs((_np.diff(deg) + 180.0) % 360.0 - 180.0)
+        step_deg = float(d[d > 0].min()) if (d > 0).any() else 6.0
+    out = _np.zeros((len(h), n_fine), PHOTO_SEARCH_HYP_DTYPE)
+    for k in range(len(h)):
+        for j in range(n_fine):
+            off = (j - (n_fine - 1) / 2.0) * (step_deg / n_fine)
+            out[k, j] = h[k] if off == 0.0 else photo_search_hyp(_np.deg2rad(deg[k] + off), min(max(float(scale[k]), 0.5), 2.0))[0]
+    return out
+
+
 # hnet_keyframe_recover: one record per listed session of a track with recovery (hnet_sessions_keyframe_track_recover): the track's record, whose flags may
 # hold KF_RECOVERED, and the oriented relocalise's (all zero but target = -2 for a session that was not lost)
 KF_RECOVERED = 2048
@@ -679,6 +748,12 @@ def lib():
     L.hnet_op_photo_search_oriented.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp]
     L.hnet_sessions_photo_search_oriented.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp]
     L.hnet_sessions_keyframe_relocalise_oriented.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp]
+    L.hnet_photo_search_fine_default_opts.argtypes = [C.POINTER(PhotoSearchFineOpts)]
+    L.hnet_photo_search_fine_default_opts.restype = None
+    L.hnet_photo_search_fine_yaw_table.argtypes = [C.c_double, C.c_double, C.c_int, C.c_int, vp]
+    L.hnet_op_photo_search_fine.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]
+    L.hnet_sessions_photo_search_fine.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp]
+    L.hnet_sessions_keyframe_relocalise_fine.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp]
     L.hnet_keyframe_recover_default_opts.argtypes = [C.POINTER(KeyframeRecoverOpts)]
     L.hnet_keyframe_recover_default_opts.restype = None
     L.hnet_sessions_keyframe_track_recover.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int, vp]

@@ -15,10 +15,14 @@
 // of the track and of the relocalisation is the unchanged one but the decision and a finish.
 // The three share ONE launch sequence (enqueue_relocalise) and ONE scratch (RelocScratch), allocated by whichever of them is called first: a
 // store that never relocalises has kf->reloc == nullptr.
+// And the FINE stage of the oriented relocalisation (photo_search_fine_dev.h, csrc/kernels_photo_search_fine.hip):
+// hnet_sessions_keyframe_relocalise_fine runs enqueue_relocalise with the fine search of the picked candidate between the gather and the alignment, on a
+// scratch of its own (FineScratch): a store that never makes the call has kf->fine == nullptr, and RelocScratch is what it was.
 // And the track INSIDE a filter step (filters_keyframe_dev.h): capi_filters.hip enqueues the track's unchanged launches through the
 // keyframes_instep_* functions below, with the store's own scratch, decide on a copy of the state table and the commits deferred to the accepted attempt.
 #include "sessions_internal.h"
 #include "keyframe_recover_dev.h"
+#include "photo_search_fine_dev.h"
 #include "filters_keyframe_dev.h"
 
 using namespace hnet;
@@ -67,6 +71,8 @@ static_assert(sizeof(hnet_keyframe_relocalise_oriented) == sizeof(OrientedRelocR
               offsetof(hnet_keyframe_relocalise_oriented, target) == offsetof(OrientedRelocRec, target) &&
               offsetof(hnet_keyframe_relocalise_oriented, n_found) == offsetof(OrientedRelocRec, n_found),
               "hnet_keyframe_relocalise_oriented is 7r's record around the oriented search record");
+static_assert(sizeof(hnet_keyframe_relocalise_fine) == sizeof(FineRelocRec) && offsetof(hnet_keyframe_relocalise_fine, fine) == offsetof(FineRelocRec, fine),
+              "hnet_keyframe_relocalise_fine is the oriented relocalise's record followed by the fine part");
 static_assert(sizeof(hnet_keyframe_recover) == sizeof(RecoverRec) && offsetof(hnet_keyframe_recover, reloc) == offsetof(RecoverRec, reloc) &&
               sizeof(hnet_keyframe_recover_opts) == sizeof(RecoverOpts) && offsetof(hnet_keyframe_recover_opts, reloc) == offsetof(RecoverOpts, reloc) &&
               (int)HNET_KF_RECOVERED == hnet_keyframe_recovery::RECOVERED, "hnet_keyframe_recover / _opts are the layouts of include/hnet_keyframe_recover.h");
@@ -75,6 +81,12 @@ static_assert(sizeof(hnet_keyframe_recover) == sizeof(RecoverRec) && offsetof(hn
 struct KeyReloc {
     uint8_t* scratch = nullptr;                // device: the sections of RelocScratch
     uint8_t *pin_in = nullptr, *pin_out = nullptr;     // pinned: the largest call's table and its records [B]
+};
+
+// the scratch of the fine relocalise (allocated by the first hnet_sessions_keyframe_relocalise_fine), for max_batch B
+struct KeyFine {
+    uint8_t* scratch = nullptr;                // device: the sections of FineScratch
+    uint8_t *pin_in = nullptr, *pin_out = nullptr;     // pinned: the call's table and its records [B]
 };
 
 // the map of a store (hnet_sessions_enable_keyframe_map): sized at its enable, for N sessions, M slots each and max_batch B
@@ -88,7 +100,8 @@ struct KeyMap {
 // the store: everything is sized at enable, for the sessions' count N and the context's max_batch B
 struct hnet_keyframes {
     KeyMap* map = nullptr;                     // the keyframe map or null: never enabled
-    KeyReloc* reloc = nullptr;                 // the relocalisation's scratch or null: none of its three calls was ever made
+    KeyReloc* reloc = nullptr;                 // the relocalisation's scratch or null: none of its calls was ever made
+    KeyFine* fine = nullptr;                   // the fine relocalise's scratch or null: the call was never made
     uint8_t* key = nullptr;                    // device [N][NPIX], zeroed at enable
     KeyState* state = nullptr;                 // device [N], zeroed at enable (has_key = 0)
     uint8_t* scratch = nullptr;                // device: the sections of KeyScratch
@@ -182,6 +195,33 @@ struct RelocScratch {
 static_assert(sizeof(OrientedRec) >= sizeof(SearchRec) && sizeof(OrientedRelocRec) >= sizeof(RelocRec) && sizeof(RecoverRec) >= sizeof(OrientedRelocRec),
               "RelocScratch and the pinned blocks are sized by the widest records");
 
+// the fine relocalise's own scratch for max_batch B.  The call's table {ids | curr ring slot | hypotheses [<= 64] | fine table [<= 64][<= 9]}: ONE upload,
+// so the oriented table lies here and not in RelocScratch.  Per slot the level-2 thumbnails of the picked candidate [B] and of the current frame [B], the
+// records of up to 9 fine entries, and the call's record.  Everything else is RelocScratch's and the store's.
+size_t fine_table_bytes(int n, int n_hyp, int n_fine) { return map_table_bytes(n) + (size_t)n_hyp * (1 + n_fine) * sizeof(SearchHyp); }
+struct FineScratch {
+    uint8_t *tab, *thumbs; FineEntry* ent; FineRelocRec* out; size_t bytes;
+    FineScratch(uint8_t* b, int B) {
+        size_t o = 0;
+        auto take = [&](size_t n) { uint8_t* p = b + o; o += (n + 255) & ~(size_t)255; return p; };
+        tab = take(fine_table_bytes(B, SEARCH_MAX_HYP, FINE_MAX));
+        thumbs = take((size_t)2 * B * FINE_THUMB_BYTES);
+        ent = reinterpret_cast<FineEntry*>(take((size_t)B * FINE_MAX * sizeof(FineEntry)));
+        out = reinterpret_cast<FineRelocRec*>(take((size_t)B * sizeof(FineRelocRec)));
+        bytes = o;
+    }
+};
+// what enqueue_relocalise runs between the gather and the alignment of a fine relocalise
+struct FineStage { const FineScratch* fw; FineOpts fo; const SearchHyp* d_fine; };
+
+void fine_free(KeyFine* f) {
+    if (!f) return;
+    if (f->scratch) (void)hipFree(f->scratch);
+    if (f->pin_in) (void)hipHostFree(f->pin_in);
+    if (f->pin_out) (void)hipHostFree(f->pin_out);
+    delete f;
+}
+
 void reloc_free(KeyReloc* r) {
     if (!r) return;
     if (r->scratch) (void)hipFree(r->scratch);
@@ -207,6 +247,7 @@ void keyframes_free(hnet_keyframes* k) {
     if (!k) return;
     map_free(k->map);
     reloc_free(k->reloc);
+    fine_free(k->fine);
     if (k->key) (void)hipFree(k->key);
     if (k->state) (void)hipFree(k->state);
     if (k->scratch) (void)hipFree(k->scratch);
@@ -263,11 +304,29 @@ int reloc_ensure(hnet_ctx* c, hnet_keyframes* k, const char* who) {
     return HNET_OK;
 }
 
+// the fine relocalise's scratch, allocated by its first call, before that call enqueues anything
+int fine_ensure(hnet_ctx* c, hnet_keyframes* k, const char* who) {
+    if (k->fine) return HNET_OK;
+    const int B = c->cfg.max_batch;
+    KeyFine* f = new KeyFine();
+    hipError_t e = hipMalloc((void**)&f->scratch, FineScratch(nullptr, B).bytes);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&f->pin_in, fine_table_bytes(B, SEARCH_MAX_HYP, FINE_MAX), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&f->pin_out, (size_t)B * sizeof(FineRelocRec), hipHostMallocDefault);
+    if (e != hipSuccess) {
+        fine_free(f);
+        return fail(c, HNET_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    }
+    k->fine = f;
+    return HNET_OK;
+}
+
 // ONE relocalisation of the n listed slots on the stream, between a call's upload and its download: thumbnails, search, pick, gather, robust alignment,
 // decision, attach.  d_ids, d_slot: the call's device table; active: null, or per slot whether it takes part (a track with recovery); d_hyps: null for the
 // plain search, with SearchRec in rw.srec and RelocRec in rw.out, or the device table of the oriented one, with OrientedRec and OrientedRelocRec there.
+// fs: null, or the fine stage of an oriented call: after the gather the picked candidate and the current frame lie in the staging pair; their level-2
+// thumbnails, the fine search on the pick's search record and the fine winner, which writes the fine part into fs->fw->out and the final start over w.x0.
 int enqueue_relocalise(hnet_sessions* s, const RelocScratch& rw, const int32_t* d_ids, const int32_t* d_slot, int n, const int32_t* active, const SearchHyp* d_hyps,
-                       int n_hyp, const RelocOpts& o) {
+                       int n_hyp, const RelocOpts& o, const FineStage* fs = nullptr) {
     hnet_ctx* c = s->ctx;
     hnet_keyframes* k = s->kf;
     const int B = c->cfg.max_batch, N = s->n;
@@ -290,6 +349,15 @@ int enqueue_relocalise(hnet_sessions* s, const RelocScratch& rw, const int32_t* 
         HIPCHK(c, launch_reloc_pick(d_ids, n, N, k->state, M, rw.valid, srec, w.x0, rw.cand, rw.mslot, reinterpret_cast<RelocRec*>(rw.out), st));
     }
     HIPCHK(c, launch_reloc_gather(d_ids, d_slot, n, N, rw.cand, k->key, map, s->ring, 2 * N, prev, curr, st));
+    if (fs && d_hyps) {
+        const FineScratch& fw = *fs->fw;
+        const uint8_t* coarse = rw.out + offsetof(OrientedRelocRec, search);
+        HIPCHK(c, launch_photo_fine_thumbs(prev, nullptr, n, n, fw.thumbs, st));
+        HIPCHK(c, launch_photo_fine_thumbs(curr, nullptr, n, n, fw.thumbs + (size_t)n * FINE_THUMB_BYTES, st));
+        HIPCHK(c, launch_photo_search_fine(fw.thumbs, 1, 1, n, n, coarse, (int)sizeof(OrientedRelocRec), rw.cand, o.search, fs->fo, fs->d_fine, n_hyp, fw.ent, nullptr, st));
+        HIPCHK(c, launch_photo_search_fine_winner(fw.ent, n, coarse, (int)sizeof(OrientedRelocRec), rw.cand, fs->fo, fs->d_fine, n_hyp, reinterpret_cast<uint8_t*>(fw.out),
+                                                  (int)sizeof(FineRelocRec), (int)offsetof(FineRelocRec, fine), false, w.x0, st));
+    }
     HIPCHK(c, launch_photo_align_robust(prev, curr, n, w.x0, o.align, o.levels, c->pyr_scratch, c->pyr_scratch + pyr, w.start, w.part, w.work, w.rec, st));
     if (d_hyps)
         HIPCHK(c, launch_reloc_decide(d_ids, n, N, w.rec, w.x0, rw.cand, o, k->state, map, reinterpret_cast<OrientedRelocRec*>(rw.out), rw.attach, st));
@@ -344,6 +412,48 @@ int relocalise(hnet_sessions* s, int n, const int32_t* ids, const hnet_keyframe_
     HIPCHK(c, hipEventRecord(k->ev[0], c->stream));
     if ((rc = enqueue_relocalise(s, rw, d_ids, d_ids + n, n, nullptr, d_hyps, n_hyp, o)) != HNET_OK) return rc;
     return finish_call(c, k, k->ev, rw.out, r->pin_out, out, (size_t)n * (oriented ? sizeof(OrientedRelocRec) : sizeof(RelocRec)));
+}
+
+// hnet_sessions_keyframe_relocalise_oriented with the fine stage on the picked candidate: ONE upload {ids | curr slot | table | fine table} into the fine
+// scratch, the launch sequence inside the store's own events, the oriented records packed in front of the fine parts, ONE download, one synchronisation
+int relocalise_fine(hnet_sessions* s, int n, const int32_t* ids, const hnet_keyframe_relocalise_opts* opts, const hnet_photo_search_hyp* hyps, int n_hyp,
+                    const hnet_photo_search_fine_opts* fine_opts, const hnet_photo_search_hyp* fine, hnet_keyframe_relocalise_fine* out, const char* who) {
+    if (!s) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = s->ctx;
+    hnet_keyframes* k = s->kf;
+    if (!k) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": keyframes are not enabled (hnet_sessions_enable_keyframes)");
+    if (!out || !opts) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": opts / out");
+    RelocOpts o;
+    FineStage fs;
+    int rc = reloc_check_opts(c, opts, who, "opts", o);
+    if (rc != HNET_OK) return rc;
+    if ((rc = photo_search_check_table(c, hyps, n_hyp, who)) != HNET_OK) return rc;
+    if ((rc = photo_search_fine_check(c, fine_opts, fine, n_hyp, who, fs.fo)) != HNET_OK) return rc;
+    if ((rc = sessions_check_ids(s, n, ids)) != HNET_OK) return rc;
+    if ((rc = check_listed(s, n, ids, who, true)) != HNET_OK) return rc;
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    if ((rc = reloc_ensure(c, k, who)) != HNET_OK) return rc;
+    if ((rc = fine_ensure(c, k, who)) != HNET_OK) return rc;
+    KeyFine* f = k->fine;
+    const RelocScratch rw(k->reloc->scratch, c->cfg.max_batch);
+    const FineScratch fw(f->scratch, c->cfg.max_batch);
+    int32_t* h_ids = reinterpret_cast<int32_t*>(f->pin_in);
+    for (int i = 0; i < n; i++) {
+        h_ids[i] = ids[i];
+        h_ids[n + i] = 2 * ids[i] + s->st[ids[i]].curr;
+    }
+    const size_t head = map_table_bytes(n), tab = (size_t)n_hyp * sizeof(SearchHyp), ftab = tab * fs.fo.n_fine;      // (8 n bytes in front: the tables are aligned)
+    memcpy(f->pin_in + head, hyps, tab);
+    memcpy(f->pin_in + head + tab, fine, ftab);
+    const int32_t* d_ids = reinterpret_cast<const int32_t*>(fw.tab);
+    const SearchHyp* d_hyps = reinterpret_cast<const SearchHyp*>(fw.tab + head);
+    fs.fw = &fw;
+    fs.d_fine = reinterpret_cast<const SearchHyp*>(fw.tab + head + tab);
+    HIPCHK(c, hipMemcpyAsync(fw.tab, f->pin_in, head + tab + ftab, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipEventRecord(k->ev[0], c->stream));
+    if ((rc = enqueue_relocalise(s, rw, d_ids, d_ids + n, n, nullptr, d_hyps, n_hyp, o, &fs)) != HNET_OK) return rc;
+    HIPCHK(c, launch_reloc_fine_pack(reinterpret_cast<const OrientedRelocRec*>(rw.out), n, fw.out, c->stream));
+    return finish_call(c, k, k->ev, fw.out, f->pin_out, out, (size_t)n * sizeof(FineRelocRec));
 }
 
 }  // namespace
@@ -665,6 +775,13 @@ int hnet_sessions_keyframe_relocalise(hnet_sessions* s, int n, const int32_t* id
 int hnet_sessions_keyframe_relocalise_oriented(hnet_sessions* s, int n, const int32_t* ids, const hnet_keyframe_relocalise_opts* opts,
                                                const hnet_photo_search_hyp* hyps, int n_hyp, hnet_keyframe_relocalise_oriented* out) {
     return relocalise(s, n, ids, opts, true, hyps, n_hyp, out, "hnet_sessions_keyframe_relocalise_oriented");
+}
+
+// hnet_sessions_keyframe_relocalise_oriented with the fine stage on the picked candidate
+int hnet_sessions_keyframe_relocalise_fine(hnet_sessions* s, int n, const int32_t* ids, const hnet_keyframe_relocalise_opts* opts, const hnet_photo_search_hyp* hyps,
+                                           int n_hyp, const hnet_photo_search_fine_opts* fine_opts, const hnet_photo_search_hyp* fine,
+                                           hnet_keyframe_relocalise_fine* out) {
+    return relocalise_fine(s, n, ids, opts, hyps, n_hyp, fine_opts, fine, out, "hnet_sessions_keyframe_relocalise_fine");
 }
 
 void hnet_keyframe_recover_default_opts(hnet_keyframe_recover_opts* o) {

@@ -344,6 +344,26 @@ class HnetEngine:
                                                              sc.ctypes.data if want_scores else None))
         return (out, sc) if want_scores else out
 
+    def op_photo_search_fine(self, img1, img2, hyps=None, fine=None, fine_opts=None, want_scores=False, **opts):
+        """the oriented search followed by the fine stage around its winner on level-2 thumbnails (hnet_op_photo_search_fine): a closer start for the
+        alignments, also under a coarser table; hyps as op_photo_search_oriented, fine [n_hyp, n_fine] of _capi.PHOTO_SEARCH_HYP_DTYPE (None: the table
+        that matches hyps, _capi.photo_search_fine_table), fine_opts a dict of radius / n_fine / min_score, opts as _capi.photo_search_opts ->
+        records [n] of _capi.PHOTO_SEARCH_FINE_DTYPE; want_scores: (those, the fine score of every entry and shift [n, n_fine, 9, 9])"""
+        a = np.ascontiguousarray(img1, dtype=np.uint8).reshape(-1, IMG_H, IMG_W)
+        b = np.ascontiguousarray(img2, dtype=np.uint8).reshape(-1, IMG_H, IMG_W)
+        n = a.shape[0]
+        if b.shape[0] != n:
+            raise ValueError("img1 and img2 must hold the same number of frames")
+        o = _capi.photo_search_opts(**opts)
+        fo = _capi.photo_search_fine_opts(**(fine_opts or {}))
+        h = _capi.photo_search_table(hyps)
+        f = _capi.photo_search_fine_table(fine, hyps, fo.n_fine)
+        out = np.zeros(n, _capi.PHOTO_SEARCH_FINE_DTYPE)
+        sc = np.zeros((n, max(fo.n_fine, 1), _capi.PSF_SHIFTS, _capi.PSF_SHIFTS)) if want_scores else None
+        check(self._h, self._L.hnet_op_photo_search_fine(self._h, a.ctypes.data, b.ctypes.data, n, C.addressof(o), h.ctypes.data, len(h), C.addressof(fo),
+                                                         f.ctypes.data, out.ctypes.data, sc.ctypes.data if want_scores else None))
+        return (out, sc) if want_scores else out
+
     def op_photo_pyramid(self, img):
         """levels 1 .. 3 of uint8 frames [n, 224, 320] (hnet_op_photo_pyramid) -> uint8 [n, _capi.PHOTO_PYRAMID_BYTES]: 160 x 112, 80 x 56 and
         40 x 28 pixels per frame, level 1 first"""
@@ -770,6 +790,33 @@ class HnetSessions:
         h = _capi.photo_search_table(hyps)
         out = np.zeros(n, _capi.KEYFRAME_RELOC_ORIENTED_DTYPE)
         self._check(self._L.hnet_sessions_keyframe_relocalise_oriented(self._s, n, ids.ctypes.data, C.addressof(o), h.ctypes.data, len(h), out.ctypes.data))
+        return out
+
+    def photo_search_fine(self, ids, hyps=None, fine=None, fine_opts=None, **opts):
+        """the oriented search and the fine stage on the listed sessions' current pairs (hnet_sessions_photo_search_fine); read-only; result as
+        HnetEngine.op_photo_search_fine"""
+        ids, n = self._ids(ids)
+        o = _capi.photo_search_opts(**opts)
+        fo = _capi.photo_search_fine_opts(**(fine_opts or {}))
+        h = _capi.photo_search_table(hyps)
+        f = _capi.photo_search_fine_table(fine, hyps, fo.n_fine)
+        out = np.zeros(n, _capi.PHOTO_SEARCH_FINE_DTYPE)
+        self._check(self._L.hnet_sessions_photo_search_fine(self._s, n, ids.ctypes.data, C.addressof(o), h.ctypes.data, len(h), C.addressof(fo), f.ctypes.data,
+                                                            out.ctypes.data))
+        return out
+
+    def keyframe_relocalise_fine(self, ids, hyps=None, fine=None, fine_opts=None, **opts):
+        """hnet_sessions_keyframe_relocalise_fine: keyframe_relocalise_oriented with the fine stage on the picked candidate, whose final start the
+        alignment takes (hyps, fine and fine_opts as op_photo_search_fine) -> [n] of _capi.KEYFRAME_RELOC_FINE_DTYPE; opts as
+        _capi.keyframe_relocalise_opts"""
+        ids, n = self._ids(ids)
+        o = _capi.keyframe_relocalise_opts(**opts)
+        fo = _capi.photo_search_fine_opts(**(fine_opts or {}))
+        h = _capi.photo_search_table(hyps)
+        f = _capi.photo_search_fine_table(fine, hyps, fo.n_fine)
+        out = np.zeros(n, _capi.KEYFRAME_RELOC_FINE_DTYPE)
+        self._check(self._L.hnet_sessions_keyframe_relocalise_fine(self._s, n, ids.ctypes.data, C.addressof(o), h.ctypes.data, len(h), C.addressof(fo),
+                                                                   f.ctypes.data, out.ctypes.data))
         return out
 
     def keyframe_track_recover(self, ids, step_px=None, hyps=None, track=None, reloc=None):

@@ -1039,6 +1039,75 @@ typedef struct hnet_keyframe_relocalise_oriented {
 int  hnet_sessions_keyframe_relocalise_oriented(hnet_sessions* s, int n, const int32_t* ids, const hnet_keyframe_relocalise_opts* opts,
                                                 const hnet_photo_search_hyp* hyps, int n_hyp, hnet_keyframe_relocalise_oriented* out /* [n] */);
 
+/* ---- a FINE stage around the oriented winner, on level-2 thumbnails (csrc/kernels_photo_search_fine.hip; the shared code is
+ * include/hnet_photo_search_fine.h).  Opt-in like the searches above: a program that never calls these allocates, launches and returns what it did.
+ * The oriented search hands the alignment a start that is wrong by up to half a table step plus 4 px of the level-3 shift.  The fine stage runs on the
+ * 80 x 56 level-2 thumbnails (level 2 of the alignment's pyramid bit for bit): n_fine sub-step entries fine[hyp][0 .. n_fine) around the winning entry
+ * `hyp`, each over the shifts (2 dx + ex, 2 dy + ey) with |ex|, |ey| <= radius around twice the winning shift, warped and summed as the oriented search
+ * does (the constants 79 / 55 in place of 39 / 27) and scored by the same score under 4 * opts.min_overlap.  The best over (entry j, ex, ey): the highest
+ * score, then the smaller ex^2 + ey^2, then the smaller ey, then the smaller ex, then the lower j.
+ * The fine table is [n_hyp][n_fine] entries, 1 <= n_fine <= 9, row h for coarse entry h; only the winner's row is read.
+ * hnet_photo_search_fine_yaw_table fills entry [h][j] at (first_deg + h step_deg) + (j - (n_fine - 1) / 2) (step_deg / n_fine) degrees, scale 1: the table
+ * that matches hnet_photo_search_yaw_table(first_deg, step_deg, count); for odd n_fine its middle column is that table byte for byte.
+ * Flags of the fine part, exactly one, in this order: HNET_PSF_SKIPPED (the coarse record is not HNET_PS_FOUND: j = -1, ex = ey = sx = sy = 0, score -1,
+ * a and sums 0, start_px quiet NaNs), HNET_PSF_NOTHING_SCORED (the same values; start_px is the coarse start_px unchanged), HNET_PSF_LOW_SCORE (the best
+ * fine score is below min_score: the rejected best is reported; start_px is the coarse start_px unchanged), else HNET_PSF_REFINED: start_px at corner x_i
+ * is c + A_f (x_i - c) + 4 (sx, sy) - x_i.  Scores of the two levels are never compared.  min_score defaults to the coarse 0.75 and is not calibrated.
+ * Errors, nothing written and nothing enqueued: those of hnet_op_photo_search_oriented; HNET_ERR_INVALID_ARG for null fine options or a null fine table,
+ * n_fine outside 1 .. 9, radius outside 0 .. 4, min_score outside [-1, 1] or NaN, a fine entry with a non-finite a or |b[i]| > 2 * 65536.
+ * One upload, six launches (both thumbnails, search, winner, fine search, fine winner), one download, one synchronisation. */
+enum { HNET_PSF_REFINED = 1, HNET_PSF_SKIPPED = 2, HNET_PSF_NOTHING_SCORED = 4, HNET_PSF_LOW_SCORE = 8 };
+#define HNET_PSF_MAX_FINE 9
+#define HNET_PSF_MAX_RADIUS 4
+typedef struct hnet_photo_search_fine_opts {
+    int32_t radius;            /* 0 .. 4 level-2 pixels around twice the coarse shift */
+    int32_t n_fine;            /* 1 .. 9 entries per row of the fine table */
+    double  min_score;         /* the lowest fine score of HNET_PSF_REFINED */
+    int32_t pad[2];            /* ignored */
+} hnet_photo_search_fine_opts;
+typedef struct hnet_photo_search_fine_part {
+    float   start_px[8];       /* the FINAL start for the alignment */
+    int32_t flags;             /* HNET_PSF_* */
+    int32_t j, ex, ey;         /* the best fine entry and its offsets */
+    int32_t sx, sy;            /* the level-2 shift (2 dx + ex, 2 dy + ey) */
+    int32_t n_overlap;         /* valid template pixels of the overlap of the best */
+    int32_t pad0;              /* written zero */
+    double  score;             /* of the best; -1 without one */
+    double  a[4];              /* the fine entry's A; zeros without one */
+    int32_t sa, sb, sab, saa, sbb;     /* the sums of the best */
+    int32_t pad1;              /* written zero */
+} hnet_photo_search_fine_part;
+typedef struct hnet_photo_search_fine {
+    hnet_photo_search_oriented coarse;   /* byte for byte hnet_op_photo_search_oriented's record */
+    hnet_photo_search_fine_part fine;
+} hnet_photo_search_fine;
+void hnet_photo_search_fine_default_opts(hnet_photo_search_fine_opts* o);      /* radius 3, n_fine 5, min_score 0.75 */
+/* 1 on success; 0 for a count outside 1 .. 64, n_fine outside 1 .. 9, a null table or a non-finite angle */
+int  hnet_photo_search_fine_yaw_table(double first_deg, double step_deg, int count, int n_fine, hnet_photo_search_hyp* out /* [count][n_fine] */);
+/* operator call, host pointers: as hnet_op_photo_search_oriented; fine [n_hyp][fine_opts->n_fine]; scores_out NULL or double [n][n_fine][9][9], index
+ * (ey + 4) * 9 + (ex + 4), quiet NaN where a shift is not scored or lies outside the radius */
+int  hnet_op_photo_search_fine(hnet_ctx* ctx, const uint8_t* img1, const uint8_t* img2, int n, const hnet_photo_search_opts* opts,
+                               const hnet_photo_search_hyp* hyps, int n_hyp, const hnet_photo_search_fine_opts* fine_opts, const hnet_photo_search_hyp* fine,
+                               hnet_photo_search_fine* out, double* scores_out);
+/* the same on the (prev, curr) pair of each listed session, byte for byte the operator call; read-only, errors as hnet_sessions_photo_search_oriented */
+int  hnet_sessions_photo_search_fine(hnet_sessions* s, int n, const int32_t* ids, const hnet_photo_search_opts* opts, const hnet_photo_search_hyp* hyps,
+                                     int n_hyp, const hnet_photo_search_fine_opts* fine_opts, const hnet_photo_search_hyp* fine, hnet_photo_search_fine* out);
+
+/* hnet_sessions_keyframe_relocalise_fine: hnet_sessions_keyframe_relocalise_oriented with the fine stage on the PICKED candidate only: after the pick and
+ * the gather, the level-2 thumbnails of the candidate and the current frame, the fine search and its winner, which writes the final start over the
+ * alignment's start.  The alignment, the decision and the attach are that call's, unchanged; `base` is its record (rv.start_px is the final start) and
+ * `fine` the fine part, HNET_PSF_SKIPPED with a quiet-NaN start for a slot without a pick.  With a coarser table (30 entries of 12 degrees) the call costs
+ * less than the oriented one under its default table and starts the alignment closer.  Refusals: that call's and the fine ones above.  The
+ * first call allocates the fine scratch of its own before anything is enqueued.  ONE upload {ids | curr slot | table | fine table}, ONE download and one
+ * synchronisation; hnet_sessions_last_keyframe_device_ms covers it. */
+typedef struct hnet_keyframe_relocalise_fine {
+    hnet_keyframe_relocalise_oriented base;
+    hnet_photo_search_fine_part fine;
+} hnet_keyframe_relocalise_fine;
+int  hnet_sessions_keyframe_relocalise_fine(hnet_sessions* s, int n, const int32_t* ids, const hnet_keyframe_relocalise_opts* opts,
+                                            const hnet_photo_search_hyp* hyps, int n_hyp, const hnet_photo_search_fine_opts* fine_opts,
+                                            const hnet_photo_search_hyp* fine, hnet_keyframe_relocalise_fine* out /* [n] */);
+
 /* ---- sessions, recovering a lost camera INSIDE the track, before the bridge (csrc/kernels_keyframe_recover.hip; the shared code is
  * include/hnet_keyframe_recover.h).  Opt-in: a program that never calls hnet_sessions_keyframe_track_recover allocates, launches and returns
  * what it did before.  hnet_sessions_keyframe_track with auto_rekey commits its verdict in the same call: a LOST frame becomes the keyframe and the origin
