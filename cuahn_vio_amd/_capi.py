@@ -61,7 +61,7 @@ SYMBOLS = [
     "hnet_sessions_get_map_keyframe",
     "hnet_keyframe_recover_default_opts", "hnet_sessions_keyframe_track_recover",
     "hnet_keyframe_measure_default_opts", "hnet_filters_set_keyframe_measure", "hnet_filters_last_keyframe_measure", "hnet_filters_keyframe_measure_stats",
-    "hnet_filters_reset_keyframe_measure_stats",
+    "hnet_filters_reset_keyframe_measure_stats", "hnet_filters_set_keyframe_recover", "hnet_filters_last_keyframe_recover",
 ]
 # hnet_filters_advance's status per listed session (include/hnet.h HNET_ADV_*)
 ADV_STEPPED, ADV_WAIT_IMU, ADV_WAIT_INIT, ADV_INITIALIZED, ADV_PROPAGATED, ADV_NO_FRAME = range(6)
@@ -545,6 +545,14 @@ def keyframe_recover_opts(track=None, reloc=None):
     return o
 
 
+# hnet_keyframe_measure_recover: a measuring session's record with recovery inside its in-step track (hnet_filters_set_keyframe_recover): the measure
+# record, whose track may hold KF_RECOVERED and whose flags may hold the two bits below, and the oriented relocalise's record
+KFM_FROM_RELOC, KFM_REATTACHED = 65536, 131072
+KFMR_UNUSABLE = KFM_UNUSABLE | KFM_REATTACHED
+KEYFRAME_MEASURE_RECOVER_DTYPE = _np.dtype([("m", KEYFRAME_MEASURE_DTYPE), ("reloc", KEYFRAME_RELOC_ORIENTED_DTYPE)])
+assert KEYFRAME_MEASURE_RECOVER_DTYPE.itemsize == 2448 + 2040
+
+
 def photo_robust_marginal(rec):
     """hnet_photo_robust_marginal of one record -> (info8 [8, 8], grad8 [8]); ValueError when the brightness block has no Cholesky factor"""
     r = _np.ascontiguousarray(rec, PHOTO_ROBUST_DTYPE).reshape(1)
@@ -770,6 +778,8 @@ def lib():
     L.hnet_filters_last_keyframe_measure.argtypes = [vp, C.c_int, vp]
     L.hnet_filters_keyframe_measure_stats.argtypes = [vp, C.c_int, C.POINTER(KeyframeMeasureStats)]
     L.hnet_filters_reset_keyframe_measure_stats.argtypes = [vp, C.c_int]
+    L.hnet_filters_set_keyframe_recover.argtypes = [vp, C.c_int, vp, vp, C.c_int]
+    L.hnet_filters_last_keyframe_recover.argtypes = [vp, C.c_int, vp]
     for name in SYMBOLS:
         getattr(L, name)   # AttributeError here = the library does not export what include/hnet.h declares
     _lib = L

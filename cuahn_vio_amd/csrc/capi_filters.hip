@@ -4,6 +4,7 @@
 #include "sessions_internal.h"
 #include "filters_refine_dev.h"
 #include "filters_keyframe_dev.h"
+#include "filters_keyframe_recover_dev.h"
 
 using namespace hnet;
 using namespace capi;
@@ -109,6 +110,17 @@ struct hnet_filters {
     uint8_t* d_kfm_scratch = nullptr;          // KfmScratch
     std::vector<hnet_keyframe_measure_stats> kfm_stats;
     int last_kfm_n = 0;                        // sessions the last accepted call has measure records for; 0: it ran without a measuring session
+    // recovery inside the in-step track (hnet_filters_set_keyframe_recover), allocated by the first call that turns it on: the output block
+    // then also holds {kfmr [n] OrientedRelocRec, dense} behind the measure records; per measuring session the reloc options and the table (host: they
+    // decide a call's launch sequence; device: every session's table, uploaded when it is set) and ONE zeroed scratch block (KfmrScratch)
+    bool kfmr = false;
+    size_t off_kfmr = 0;
+    std::vector<RelocOpts> kfmr_opts;
+    std::vector<SearchHyp> kfmr_tab;           // [n_sessions][SEARCH_MAX_HYP], zero behind a session's entries
+    std::vector<int> kfmr_n_hyp;
+    std::vector<uint8_t> kfmr_on;
+    uint8_t* d_kfmr_scratch = nullptr;         // KfmrScratch
+    int last_kfmr_n = 0;                       // sessions the last accepted call has relocalise records for; 0: it ran without a recovering session
 };
 // the sections of d_refine_scratch for max_batch B and N sessions
 struct RefineScratch {
@@ -149,9 +161,22 @@ struct KfmScratch {
         bytes = o;
     }
 };
-// a call's keyframe measurement: the session whose track options serve it (-1: the call has no measuring session) and the {ids | curr slot | gap}
-// sections of the track's table on the device
-struct KfmCall { int ref; const int32_t* d_tab; };
+// the sections of d_kfmr_scratch for max_batch B and N sessions: the per-session recover_on words (start zero: off) and tables, the per-slot trials the
+// track's alignment accepted
+struct KfmrScratch {
+    int32_t *on, *accepted; SearchHyp* hyps; size_t bytes;
+    KfmrScratch(uint8_t* b, int B, int N) {
+        size_t o = 0;
+        auto take = [&](size_t n) { uint8_t* p = b + o; o += (n + 255) & ~(size_t)255; return p; };
+        on = reinterpret_cast<int32_t*>(take((size_t)N * sizeof(int32_t)));
+        accepted = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
+        hyps = reinterpret_cast<SearchHyp*>(take((size_t)N * SEARCH_MAX_HYP * sizeof(SearchHyp)));
+        bytes = o;
+    }
+};
+// a call's keyframe measurement: the session whose track options serve it (-1: the call has no measuring session), the {ids | curr slot | gap}
+// sections of the track's table on the device, and the session whose reloc options and table serve the call's recovery (-1: no stepping session recovers)
+struct KfmCall { int ref; const int32_t* d_tab; int rref; };
 
 static size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
@@ -199,20 +224,23 @@ static void filters_out_layout(hnet_filters* f, int B, bool innov, bool photo, b
     f->off_photo = f->off_innov + (innov ? al256((size_t)f->iters * B * sizeof(InnovRec)) : 0);
     f->off_refine = f->off_photo + (photo ? al256((size_t)(2 + f->iters) * B * sizeof(PhotoRec)) : 0);
     f->off_kfm = f->off_refine + (refine ? al256((size_t)B * sizeof(RefineRec)) : 0);
-    f->off_work = f->off_kfm + (kfm ? al256((size_t)B * sizeof(KfmRec)) : 0);
+    f->off_kfmr = f->off_kfm + (kfm ? al256((size_t)B * sizeof(KfmRec)) : 0);
+    f->off_work = f->off_kfmr + (f->kfmr ? al256((size_t)B * sizeof(OrientedRelocRec)) : 0);      // (the relocalise records: once recovery was turned on)
     f->off_res = f->off_work + al256((size_t)B * sizeof(FilterRec));
     f->out_bytes = f->off_res + (size_t)B * sizeof(AdvanceResult);
 }
 // the sections of the output block as typed pointers, on the device (d) and in the pinned copy (h)
-struct OutView { float *net, *prior; int32_t* upd; InnovRec* innov; PhotoRec* photo; RefineRec* refine; KfmRec* kfm; FilterRec* work; AdvanceResult* res; };
+struct OutView { float *net, *prior; int32_t* upd; InnovRec* innov; PhotoRec* photo; RefineRec* refine; KfmRec* kfm; FilterRec* work; AdvanceResult* res; OrientedRelocRec* kfmr; };
 struct OutViews { OutView d, h; };
 static OutView filters_out_view(const hnet_filters* f, uint8_t* b) {
     return OutView{reinterpret_cast<float*>(b), reinterpret_cast<float*>(b + f->off_prior), reinterpret_cast<int32_t*>(b + f->off_upd), reinterpret_cast<InnovRec*>(b + f->off_innov),
-                   reinterpret_cast<PhotoRec*>(b + f->off_photo), reinterpret_cast<RefineRec*>(b + f->off_refine), reinterpret_cast<KfmRec*>(b + f->off_kfm), reinterpret_cast<FilterRec*>(b + f->off_work), reinterpret_cast<AdvanceResult*>(b + f->off_res)};
+                   reinterpret_cast<PhotoRec*>(b + f->off_photo), reinterpret_cast<RefineRec*>(b + f->off_refine), reinterpret_cast<KfmRec*>(b + f->off_kfm), reinterpret_cast<FilterRec*>(b + f->off_work), reinterpret_cast<AdvanceResult*>(b + f->off_res),
+                   reinterpret_cast<OrientedRelocRec*>(b + f->off_kfmr)};
 }
 static OutViews filters_out_views(const hnet_filters* f) { return OutViews{filters_out_view(f, f->d_out), filters_out_view(f, f->pin_out)}; }
 // what a step of n stepping sessions downloads in one copy from the start of the output block when the states are not wanted: up to the last record section in use
-static size_t filters_down_head(const hnet_filters* f, int n, bool refining, bool measuring) {
+static size_t filters_down_head(const hnet_filters* f, int n, bool refining, bool measuring, bool recovering) {
+    if (recovering) return f->off_kfmr + (size_t)n * sizeof(OrientedRelocRec);
     if (measuring) return f->off_kfm + (size_t)n * sizeof(KfmRec);
     if (refining) return f->off_refine + (size_t)n * sizeof(RefineRec);
     if (f->photo) return f->off_photo + (size_t)n * (2 + f->iters) * sizeof(PhotoRec);
@@ -298,6 +326,29 @@ static int filters_measuring(const hnet_filters* f, int n, const int32_t* ids, i
     *ref = first;
     return 1;
 }
+// whether the call in which the sessions ids[0 .. n) step recovers inside its in-step track: 1 when one of them has recovery on (*ref: such a
+// session), -1 when two of them differ in the reloc options, -2 when they differ in their tables, else 0
+static int filters_recovering(const hnet_filters* f, int n, const int32_t* ids, int* ref) {
+    *ref = -1;
+    if (!f->kfmr) return 0;
+    int first = -1;
+    for (int j = 0; j < n; j++) {
+        const int id = ids[j];
+        if (!f->kfmr_on[id] || !f->kfm_on[id]) continue;
+        if (first < 0) first = id;
+        else if (memcmp(&f->kfmr_opts[id], &f->kfmr_opts[first], sizeof(RelocOpts)) != 0) return -1;
+        else if (f->kfmr_n_hyp[id] != f->kfmr_n_hyp[first] ||
+                 memcmp(&f->kfmr_tab[(size_t)id * SEARCH_MAX_HYP], &f->kfmr_tab[(size_t)first * SEARCH_MAX_HYP], (size_t)SEARCH_MAX_HYP * sizeof(SearchHyp)) != 0)
+            return -2;
+    }
+    if (first < 0) return 0;
+    *ref = first;
+    return 1;
+}
+static int filters_recovering_refused(hnet_ctx* c, int recovering, const char* who) {
+    return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + (recovering == -1 ? ": the recovering sessions differ in the reloc options (hnet_filters_set_keyframe_recover)"
+                                                                              : ": the recovering sessions differ in their tables (hnet_filters_set_keyframe_recover)"));
+}
 static int filters_measuring_refused(hnet_ctx* c, int measuring, const char* who) {
     return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + (measuring == -1 ? ": the sessions with the keyframe measurement on differ in the track's options (hnet_filters_set_keyframe_measure)"
                                                                               : ": sessions with refinement on and sessions with the keyframe measurement on step in one call"));
@@ -311,7 +362,7 @@ static void filters_count_kfm(hnet_filters* f, int n, const int32_t* ids) {
         hnet_keyframe_measure_stats& a = f->kfm_stats[ids[j]];
         a.asked++;
         if (r.flags & HNET_KFM_APPLIED) a.applied++;
-        if (r.flags & HNET_KFM_UNUSABLE) a.unusable++;
+        if (r.flags & HNET_KFMR_UNUSABLE) a.unusable++;            // (HNET_KFM_REATTACHED occurs with recovery on only)
         if (r.flags & HNET_KFM_NIS_REJECTED) a.nis_rejected++;
         if ((r.flags & (HNET_KFM_APPLIED | HNET_KFM_NIS_REJECTED)) && std::isfinite(r.nis)) {
             a.sum_nis += r.nis;
@@ -449,6 +500,23 @@ static int filters_enqueue_keyframe(hnet_filters* f, hnet_ctx* c, const OutView&
     KeyOpts ko;
     memcpy(&ko, &f->kfm_opts[kfm.ref].track, sizeof ko);
     const KeyTable tab{w.step, kfm.d_tab, kfm.d_tab + n, kfm.d_tab + 2 * (size_t)n};
+    if (kfm.rref >= 0) {                                           //  the track with recovery, the measure and finish kernels that read its records
+        const KfmrScratch rw(f->d_kfmr_scratch, B, N);
+        capi::KeyInstepRecover rv;
+        HIPCHK(c, launch_filter_kfm_step(d_ids, n, N, f->d_kfm_cfg, d.work, w.step, d.kfm, st));
+        if (const int r = capi::keyframes_instep_track_recover(f->s, tab, n, ko, f->kfmr_opts[kfm.rref], rw.hyps + (size_t)kfm.rref * SEARCH_MAX_HYP, f->kfmr_n_hyp[kfm.rref],
+                                                               rw.on, w.prev, w.curr, w.state_work, rw.accepted, &rv, st);
+            r != HNET_OK)
+            return r;
+        HIPCHK(c, hipMemcpyAsync(w.prev_ok_work, w.prev_ok, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        HIPCHK(c, launch_filter_kfmr_measure(d_ids, n, N, f->d_params, f->d_kfm_cfg, rv.state, w.prev_ok, rv.rout, rw.accepted, rv.rec2, f->kfmr_opts[kfm.rref].levels, d.upd,
+                                             w.m72, d_gate, w.opened, d.kfm, st));
+        HIPCHK(c, launch_filter_prior(d.work, n, w.prior_px, f->d_prior_cam, st));
+        HIPCHK(c, launch_filter_innovation(d_ids, n, N, f->d_params, d.work, w.m72, f->d_prior_cam, f->innov ? f->d_max_nis : w.nis0, d_gate, d.upd, 0, w.innov, nullptr, st));
+        HIPCHK(c, launch_filter_update(d_ids, n, N, f->d_params, w.m72, f->d_prior_cam, d_gate, 0, 1, d.work, d.upd, st));
+        HIPCHK(c, launch_filter_kfmr_finish(d_ids, n, N, w.innov, d.upd, w.opened, f->iters, rv.rout, w.prev_ok_work, d.kfm, d.kfmr, st));
+        return HNET_OK;
+    }
     capi::KeyInstep v;
     HIPCHK(c, launch_filter_kfm_step(d_ids, n, N, f->d_kfm_cfg, d.work, w.step, d.kfm, st));
     if (const int r = capi::keyframes_instep_track(f->s, tab, n, ko, w.prev, w.curr, w.state_work, &v, st); r != HNET_OK) return r;
@@ -466,7 +534,10 @@ static int filters_commit_keyframe(hnet_filters* f, hnet_ctx* c, int n, const in
     const int B = c->cfg.max_batch, N = f->s->n;
     const KfmScratch w(f->d_kfm_scratch, B, N);
     const KeyTable tab{w.step, kfm.d_tab, kfm.d_tab + n, kfm.d_tab + 2 * (size_t)n};
-    if (const int r = capi::keyframes_instep_commit(f->s, tab, n, w.curr, w.state_work, st); r != HNET_OK) return r;
+    if (const int r = kfm.rref >= 0 ? capi::keyframes_instep_commit_recover(f->s, tab, n, w.curr, w.state_work, st)
+                                    : capi::keyframes_instep_commit(f->s, tab, n, w.curr, w.state_work, st);
+        r != HNET_OK)
+        return r;
     HIPCHK(c, hipMemcpyAsync(w.prev_ok, w.prev_ok_work, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
     capi::keyframes_instep_accepted(f->s, n, ids, f->kfm_on.data());
     return HNET_OK;
@@ -482,8 +553,8 @@ static int filters_overflowed(const hnet_filters* f, hnet_ctx* const ctx[2], con
     return -1;
 }
 // the bookkeeping of an accepted call in which the sessions ids[0 .. n) stepped: what the last_* calls describe, the innovation statistics, the timing
-static int filters_accepted(hnet_filters* f, int n, const int32_t* ids, const int32_t* ref_gate, bool refining, bool measuring, std::chrono::steady_clock::time_point t0,
-                            int n_inferences) {
+static int filters_accepted(hnet_filters* f, int n, const int32_t* ids, const int32_t* ref_gate, bool refining, bool measuring, bool recovering,
+                            std::chrono::steady_clock::time_point t0, int n_inferences) {
     f->last_n = n;
     f->last_innov_n = f->innov ? n : 0;
     f->last_photo_n = f->photo ? n : 0;
@@ -493,6 +564,7 @@ static int filters_accepted(hnet_filters* f, int n, const int32_t* ids, const in
     if (refining) filters_count_refine(f, n, ids);
     f->last_kfm_n = measuring ? n : 0;
     if (measuring) filters_count_kfm(f, n, ids);
+    f->last_kfmr_n = recovering ? n : 0;
     float ms = 0;
     HIPCHK(f->s->ctx, hipEventElapsedTime(&ms, f->ev0, f->ev1));
     record_timing(f->timing, ms, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), n_inferences, true);
@@ -535,7 +607,7 @@ void hnet_destroy_filters(hnet_filters* f) {
     hnet_ctx* c = f->s->ctx;
     (void)hipSetDevice(c->cfg.device_id);
     (void)hipStreamSynchronize(c->stream);
-    drop_dev(f->d_state); drop_dev(f->d_params); drop_dev(f->d_out); drop_dev(f->d_prior_cam); drop_dev(f->d_in); drop_dev(f->d_feed); drop_dev(f->d_max_nis); drop_dev(f->d_photo_part); drop_dev(f->d_photo_gate); drop_dev(f->d_photo_verdict); drop_dev(f->d_refine_cfg); drop_dev(f->d_refine_scratch); drop_dev(f->d_kfm_cfg); drop_dev(f->d_kfm_scratch);
+    drop_dev(f->d_state); drop_dev(f->d_params); drop_dev(f->d_out); drop_dev(f->d_prior_cam); drop_dev(f->d_in); drop_dev(f->d_feed); drop_dev(f->d_max_nis); drop_dev(f->d_photo_part); drop_dev(f->d_photo_gate); drop_dev(f->d_photo_verdict); drop_dev(f->d_refine_cfg); drop_dev(f->d_refine_scratch); drop_dev(f->d_kfm_cfg); drop_dev(f->d_kfm_scratch); drop_dev(f->d_kfmr_scratch);
     drop_pin(f->pin_feed); drop_pin(f->pin_out); drop_pin(f->pin_in);
     drop_event(f->ev0); drop_event(f->ev1);
     filters_drop_feed(f);
@@ -642,6 +714,9 @@ int hnet_filters_step(hnet_filters* f, int n, const int32_t* ids, const double* 
     int kfm_ref = -1;
     const int measuring = filters_measuring(f, n, ids, &kfm_ref);
     if (measuring < 0) return filters_measuring_refused(c, measuring, "hnet_filters_step");
+    int kfmr_ref = -1;
+    const int recovering = measuring ? filters_recovering(f, n, ids, &kfmr_ref) : 0;
+    if (recovering < 0) return filters_recovering_refused(c, recovering, "hnet_filters_step");
     for (int i = 0; i < n; i++) {
         if (!(t_frame[i] > f->t[ids[i]]) || !std::isfinite(t_frame[i]))
             return fail(c, HNET_ERR_INVALID_ARG, "hnet_filters_step: t_frame must be later than the state's time (Propagator.cpp:32-43)");
@@ -683,7 +758,7 @@ int hnet_filters_step(hnet_filters* f, int n, const int32_t* ids, const double* 
     }
     roff[n] = R;
     if (measuring) capi::keyframes_instep_table(s, n, ids, f->kfm_on.data(), reinterpret_cast<int32_t*>(f->pin_in + o_kf));
-    const KfmCall kfm{kfm_ref, reinterpret_cast<const int32_t*>(f->d_in + o_kf)};
+    const KfmCall kfm{kfm_ref, reinterpret_cast<const int32_t*>(f->d_in + o_kf), kfmr_ref};
     const hnet_ekf::ImuData* d_rd = reinterpret_cast<const hnet_ekf::ImuData*>(f->d_in);
     const double* d_tf = reinterpret_cast<const double*>(f->d_in + o_t);
     const uint64_t* d_seq = reinterpret_cast<const uint64_t*>(f->d_in + o_seq);
@@ -693,7 +768,7 @@ int hnet_filters_step(hnet_filters* f, int n, const int32_t* ids, const double* 
     const int32_t* d_roff = reinterpret_cast<const int32_t*>(f->d_in + o_off);
     const OutViews o = filters_out_views(f);
     // the output block is laid out for max_batch: download the used parts of each section in one copy up to the last one needed
-    const size_t down = state_out ? f->off_work + (size_t)n * sizeof(FilterRec) : filters_down_head(f, n, refining > 0, measuring > 0);
+    const size_t down = state_out ? f->off_work + (size_t)n * sizeof(FilterRec) : filters_down_head(f, n, refining > 0, measuring > 0, recovering > 0);
     hipStream_t st = c->stream;
     const size_t up = measuring ? o_kf + (size_t)n * 12 : o_off + (size_t)(n + 1) * 4;
     hnet_ctx* const ctx[2] = {c, filters_iter_ctx(f)};
@@ -721,7 +796,7 @@ int hnet_filters_step(hnet_filters* f, int n, const int32_t* ids, const double* 
         for (int it = 0; it < I; it++) memcpy(net_out + (size_t)it * n * 72, o.h.net + (size_t)it * c->cfg.max_batch * 72, (size_t)n * 72 * sizeof(float));
     if (updates) memcpy(updates, o.h.upd, (size_t)n * sizeof(int32_t));
     if (state_out) memcpy(state_out, o.h.work, (size_t)n * sizeof(FilterRec));
-    return filters_accepted(f, n, ids, gate, refining > 0, measuring > 0, t0, I);
+    return filters_accepted(f, n, ids, gate, refining > 0, measuring > 0, recovering > 0, t0, I);
 }
 
 int hnet_filters_last_priors(const hnet_filters* f, int n, float* out) {
@@ -913,12 +988,16 @@ int hnet_filters_advance(hnet_filters* f, int n, const int32_t* ids, hnet_filter
     int kfm_ref = -1;
     const int measuring = filters_measuring(f, n_s, stepping.data(), &kfm_ref);
     if (measuring < 0) return filters_measuring_refused(c, measuring, "hnet_filters_advance");
+    int kfmr_ref = -1;
+    const int recovering = measuring ? filters_recovering(f, n_s, stepping.data(), &kfmr_ref) : 0;
+    if (recovering < 0) return filters_recovering_refused(c, recovering, "hnet_filters_advance");
     if (net_out) memset(net_out, 0, (size_t)I * n * 72 * sizeof(float));
     if (updates) memset(updates, 0, (size_t)n * sizeof(int32_t));
     std::fill(f->last_slot.begin(), f->last_slot.end(), -1);
     f->last_photo_n = 0;                                           // (a call in which nothing steps has no photometric records, whatever the call before it left)
     f->last_refine_n = 0;
     f->last_kfm_n = 0;
+    f->last_kfmr_n = 0;
     if (n_a == 0) return HNET_OK;
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
     const AdvLayout L(n_a, I);
@@ -940,7 +1019,7 @@ int hnet_filters_advance(hnet_filters* f, int n, const int32_t* ids, hnet_filter
         sessions_pair(s, id, pairs + 2 * j);
     }
     if (measuring) capi::keyframes_instep_table(s, n_s, stepping.data(), f->kfm_on.data(), reinterpret_cast<int32_t*>(f->pin_adv + L.o_kf));
-    const KfmCall kfm{kfm_ref, reinterpret_cast<const int32_t*>(f->d_adv + L.o_kf)};
+    const KfmCall kfm{kfm_ref, reinterpret_cast<const int32_t*>(f->d_adv + L.o_kf), kfmr_ref};
     const AdvanceJob* d_job = reinterpret_cast<const AdvanceJob*>(f->d_adv);
     const uint64_t* d_seq = reinterpret_cast<const uint64_t*>(f->d_adv + L.o_seq);
     int32_t* d_gate = reinterpret_cast<int32_t*>(f->d_adv + L.o_gate);
@@ -962,7 +1041,7 @@ int hnet_filters_advance(hnet_filters* f, int n, const int32_t* ids, hnet_filter
         if (n_s) HIPCHK(c, launch_session_gather(s->ring, 2 * s->n, d_pairs, n_s, (uint8_t*)c->stage_prev, (uint8_t*)c->stage_curr, st));
         HIPCHK(c, launch_filter_propagate_adv(d_job, n_a, s->n, f->cap, f->d_state, f->d_params, f->d_sel, d_res, d_work, st));
         if (const int r = filters_enqueue_iekf(f, ctx, o.d, n_s, d_ids, d_gate, d_seq, n_a, photo_gated, refine_ref, kfm, st); r != HNET_OK) return r;     // (the sequence table has a row of n_a per iteration)
-        if (n_s) HIPCHK(c, hipMemcpyAsync(f->pin_out, f->d_out, filters_down_head(f, n_s, refining > 0, measuring > 0), hipMemcpyDeviceToHost, st));
+        if (n_s) HIPCHK(c, hipMemcpyAsync(f->pin_out, f->d_out, filters_down_head(f, n_s, refining > 0, measuring > 0, recovering > 0), hipMemcpyDeviceToHost, st));
         if (state_out) HIPCHK(c, hipMemcpyAsync(f->pin_out + f->off_work, d_work, (size_t)n_a * sizeof(FilterRec), hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipMemcpyAsync(f->pin_out + f->off_res, d_res, (size_t)n_a * sizeof(AdvanceResult), hipMemcpyDeviceToHost, st));
         return filters_flags(ctx, flag_now, st);
@@ -1001,7 +1080,7 @@ int hnet_filters_advance(hnet_filters* f, int n, const int32_t* ids, hnet_filter
         }
         if (state_out) memcpy(state_out + i, o.h.work + j, sizeof(FilterRec));
     }
-    return filters_accepted(f, n_s, hid, gate, refining > 0, measuring > 0, t_begin, n_s ? I : 0);     // (the stepping sessions are the first n_s of the call's id table)
+    return filters_accepted(f, n_s, hid, gate, refining > 0, measuring > 0, recovering > 0, t_begin, n_s ? I : 0);     // (the stepping sessions are the first n_s of the call's id table)
 }
 
 int hnet_filters_last_selection(hnet_filters* f, int id, hnet_imu* out, int cap, int* count) {
@@ -1062,6 +1141,7 @@ static int filters_relayout(hnet_filters* f, bool innov, bool photo, bool refine
     f->last_photo_n = 0;
     f->last_refine_n = 0;
     f->last_kfm_n = 0;
+    f->last_kfmr_n = 0;
     std::fill(f->last_slot.begin(), f->last_slot.end(), -1);
     return HNET_OK;
 }
@@ -1335,10 +1415,12 @@ int hnet_filters_set_keyframe_measure(hnet_filters* f, int id, const hnet_keyfra
     if (!opts) {                                                   // (a session that stops measuring has no previous in-step track when it starts again)
         const KfmScratch w(f->d_kfm_scratch, B, N);
         HIPCHK(c, hipMemsetAsync(w.prev_ok + id, 0, sizeof(int32_t), c->stream));
+        if (f->kfmr) HIPCHK(c, hipMemsetAsync(KfmrScratch(f->d_kfmr_scratch, B, N).on + id, 0, sizeof(int32_t), c->stream));      // (and recovers no more)
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     f->kfm_opts[id] = o;
     f->kfm_on[id] = opts ? 1 : 0;
+    if (!opts && f->kfmr) f->kfmr_on[id] = 0;
     return HNET_OK;
 }
 
@@ -1347,6 +1429,73 @@ int hnet_filters_last_keyframe_measure(const hnet_filters* f, int n, hnet_keyfra
     if (!f->kfm || f->last_kfm_n < 1) return fail(f->s->ctx, HNET_ERR_INVALID_ARG, "hnet_filters_last_keyframe_measure: the last step ran without a measuring session");
     if (n != f->last_kfm_n) return fail(f->s->ctx, HNET_ERR_INVALID_ARG, "hnet_filters_last_keyframe_measure: n differs from the last step's");
     memcpy(out, filters_out_view(f, f->pin_out).kfm, (size_t)n * sizeof(KfmRec));
+    return HNET_OK;
+}
+
+// ---- filters, recovery inside the in-step track (include/hnet.h): csrc/kernels_filters_keyframe_recover.hip around
+// hnet_sessions_keyframe_track_recover's launches (capi_keyframe.hip) ----
+
+static_assert(sizeof(hnet_keyframe_measure_recover) == sizeof(KfmrRec) && offsetof(hnet_keyframe_measure_recover, reloc) == offsetof(KfmrRec, reloc) &&
+              sizeof(hnet_keyframe_relocalise_oriented) == sizeof(OrientedRelocRec) && sizeof(hnet_photo_search_hyp) == sizeof(SearchHyp) &&
+              sizeof(hnet_keyframe_relocalise_opts) == sizeof(RelocOpts),
+              "hnet_keyframe_measure_recover is the layout of include/hnet_keyframe_measure_recover.h; the table and the options are copied as they are");
+static_assert((int)HNET_KFM_FROM_RELOC == hnet_kfmr::FROM_RELOC && (int)HNET_KFM_REATTACHED == hnet_kfmr::REATTACHED && (int)HNET_KFMR_UNUSABLE == hnet_kfmr::UNUSABLE,
+              "HNET_KFM_FROM_RELOC / _REATTACHED and HNET_KFMR_UNUSABLE are the header's values");
+
+int hnet_filters_set_keyframe_recover(hnet_filters* f, int id, const hnet_keyframe_relocalise_opts* reloc, const hnet_photo_search_hyp* hyps, int n_hyp) {
+    const char* who = "hnet_filters_set_keyframe_recover";
+    if (!f) return HNET_ERR_INVALID_ARG;
+    hnet_ctx* c = f->s->ctx;
+    if (id < 0 || id >= f->s->n) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": id out of range");
+    if (!f->kfm || !f->kfm_on[id]) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": the session has no keyframe measurement on (hnet_filters_set_keyframe_measure)");
+    const int N = f->s->n, B = c->cfg.max_batch;
+    RelocOpts o;
+    std::vector<SearchHyp> table(SEARCH_MAX_HYP);
+    int n_table = 0;
+    memset(&o, 0, sizeof o);
+    memset(table.data(), 0, table.size() * sizeof(SearchHyp));
+    if (reloc) {
+        if (const int rc = capi::keyframes_recover_check(f->s, reloc, hyps, n_hyp, who, o, table.data(), &n_table); rc != HNET_OK) return rc;
+    } else if (!f->kfmr) {
+        return HNET_OK;                                            // (off, and never on)
+    }
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    if (reloc)
+        if (const int rc = capi::keyframes_instep_recover_ensure(f->s, who); rc != HNET_OK) return rc;
+    if (!f->kfmr) {
+        f->kfmr = true;                                            // (filters_out_layout reads it)
+        const int rc = filters_relayout(f, f->innov, f->photo, f->refine, f->kfm, who, (void**)&f->d_kfmr_scratch, KfmrScratch(nullptr, B, N).bytes);      // (synchronises)
+        if (rc != HNET_OK) {
+            f->kfmr = false;
+            filters_out_layout(f, B, f->innov, f->photo, f->refine, f->kfm);
+            return rc;
+        }
+        f->kfmr_opts.assign(N, RelocOpts{});
+        f->kfmr_tab.assign((size_t)N * SEARCH_MAX_HYP, SearchHyp{});
+        f->kfmr_n_hyp.assign(N, 0);
+        f->kfmr_on.assign(N, 0);
+    }
+    const KfmrScratch w(f->d_kfmr_scratch, B, N);
+    const int32_t on = reloc ? 1 : 0;
+    HIPCHK(c, hipMemcpyAsync(w.hyps + (size_t)id * SEARCH_MAX_HYP, table.data(), (size_t)SEARCH_MAX_HYP * sizeof(SearchHyp), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(w.on + id, &on, sizeof on, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    f->kfmr_opts[id] = o;
+    memcpy(&f->kfmr_tab[(size_t)id * SEARCH_MAX_HYP], table.data(), (size_t)SEARCH_MAX_HYP * sizeof(SearchHyp));
+    f->kfmr_n_hyp[id] = n_table;
+    f->kfmr_on[id] = (uint8_t)on;
+    return HNET_OK;
+}
+
+int hnet_filters_last_keyframe_recover(const hnet_filters* f, int n, hnet_keyframe_measure_recover* out) {
+    if (!f || !out) return HNET_ERR_INVALID_ARG;
+    if (!f->kfmr || f->last_kfmr_n < 1) return fail(f->s->ctx, HNET_ERR_INVALID_ARG, "hnet_filters_last_keyframe_recover: the last step ran without a recovering session");
+    if (n != f->last_kfmr_n) return fail(f->s->ctx, HNET_ERR_INVALID_ARG, "hnet_filters_last_keyframe_recover: n differs from the last step's");
+    const OutView h = filters_out_view(f, f->pin_out);
+    for (int j = 0; j < n; j++) {
+        memcpy(&out[j].m, h.kfm + j, sizeof(KfmRec));
+        memcpy(&out[j].reloc, h.kfmr + j, sizeof(OrientedRelocRec));
+    }
     return HNET_OK;
 }
 

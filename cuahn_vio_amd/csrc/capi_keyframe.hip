@@ -20,10 +20,14 @@
 // scratch of its own (FineScratch): a store that never makes the call has kf->fine == nullptr, and RelocScratch is what it was.
 // And the track INSIDE a filter step (filters_keyframe_dev.h): capi_filters.hip enqueues the track's unchanged launches through the
 // keyframes_instep_* functions below, with the store's own scratch, decide on a copy of the state table and the commits deferred to the accepted attempt.
+// And the RECOVERY inside that in-step track (filters_keyframe_recover_dev.h): the launches of hnet_sessions_keyframe_track_recover on working
+// copies of the state table and of the map's entries and states (KeyInstepWork, allocated by hnet_filters_set_keyframe_recover), every image write
+// deferred to the accepted attempt.  enqueue_relocalise takes what it reads and writes as a RelocTargets for that.
 #include "sessions_internal.h"
 #include "keyframe_recover_dev.h"
 #include "photo_search_fine_dev.h"
 #include "filters_keyframe_dev.h"
+#include "filters_keyframe_recover_dev.h"
 
 using namespace hnet;
 using namespace capi;
@@ -97,11 +101,19 @@ struct KeyMap {
     hipEvent_t ev[2] = {nullptr, nullptr};     // around the launch sequence of the last revisit
 };
 
+// the working copies of an in-step track with recovery: the map's entries [N][M] and states [N]; null without a map.  Allocated by whichever comes
+// second of keyframes_instep_recover_ensure and hnet_sessions_enable_keyframe_map (instep_map_alloc)
+struct KeyInstepWork {
+    MapEntry* entry = nullptr;
+    MapState* state = nullptr;
+};
+
 // the store: everything is sized at enable, for the sessions' count N and the context's max_batch B
 struct hnet_keyframes {
     KeyMap* map = nullptr;                     // the keyframe map or null: never enabled
     KeyReloc* reloc = nullptr;                 // the relocalisation's scratch or null: none of its calls was ever made
     KeyFine* fine = nullptr;                   // the fine relocalise's scratch or null: the call was never made
+    KeyInstepWork* instep = nullptr;           // the in-step recovery's working copies or null: no filter ever turned it on
     uint8_t* key = nullptr;                    // device [N][NPIX], zeroed at enable
     KeyState* state = nullptr;                 // device [N], zeroed at enable (has_key = 0)
     uint8_t* scratch = nullptr;                // device: the sections of KeyScratch
@@ -243,8 +255,32 @@ void map_free(KeyMap* m) {
     delete m;
 }
 
+void instep_free(KeyInstepWork* w) {
+    if (!w) return;
+    if (w->entry) (void)hipFree(w->entry);
+    if (w->state) (void)hipFree(w->state);
+    delete w;
+}
+
+// the working copies of the map m for N sessions; on failure w is as it was
+hipError_t instep_map_alloc(KeyInstepWork* w, const KeyMap* m, int N) {
+    if (w->entry) return hipSuccess;
+    MapEntry* en = nullptr;
+    MapState* st = nullptr;
+    hipError_t e = hipMalloc((void**)&en, (size_t)N * m->dev.capacity * sizeof(MapEntry));
+    if (e == hipSuccess) e = hipMalloc((void**)&st, (size_t)N * sizeof(MapState));
+    if (e != hipSuccess) {
+        if (en) (void)hipFree(en);
+        return e;
+    }
+    w->entry = en;
+    w->state = st;
+    return hipSuccess;
+}
+
 void keyframes_free(hnet_keyframes* k) {
     if (!k) return;
+    instep_free(k->instep);
     map_free(k->map);
     reloc_free(k->reloc);
     fine_free(k->fine);
@@ -320,33 +356,45 @@ int fine_ensure(hnet_ctx* c, hnet_keyframes* k, const char* who) {
     return HNET_OK;
 }
 
+// what a relocalisation reads and writes besides its scratch
+struct RelocTargets { KeyState* state; MapStore map; uint8_t *prev, *curr, *attach_key; };
+// the store's own tables, the context's staging pair, the attach into the store: what the three sessions calls pass
+RelocTargets reloc_targets_store(hnet_sessions* s) {
+    hnet_ctx* c = s->ctx;
+    hnet_keyframes* k = s->kf;
+    const MapStore none = {nullptr, nullptr, nullptr, s->n, 0};
+    return RelocTargets{k->state, k->map ? k->map->dev : none, (uint8_t*)c->stage_prev, (uint8_t*)c->stage_curr, k->key};
+}
+
 // ONE relocalisation of the n listed slots on the stream, between a call's upload and its download: thumbnails, search, pick, gather, robust alignment,
 // decision, attach.  d_ids, d_slot: the call's device table; active: null, or per slot whether it takes part (a track with recovery); d_hyps: null for the
 // plain search, with SearchRec in rw.srec and RelocRec in rw.out, or the device table of the oriented one, with OrientedRec and OrientedRelocRec there.
 // fs: null, or the fine stage of an oriented call: after the gather the picked candidate and the current frame lie in the staging pair; their level-2
 // thumbnails, the fine search on the pick's search record and the fine winner, which writes the fine part into fs->fw->out and the final start over w.x0.
-int enqueue_relocalise(hnet_sessions* s, const RelocScratch& rw, const int32_t* d_ids, const int32_t* d_slot, int n, const int32_t* active, const SearchHyp* d_hyps,
-                       int n_hyp, const RelocOpts& o, const FineStage* fs = nullptr) {
+// tg: the state table and the map it reads and writes, the staging pair of its gather and alignment, and the key images the attach writes (null: the
+// attach is the caller's, behind rw.mslot and rw.attach).
+int enqueue_relocalise(hnet_sessions* s, const RelocTargets& tg, const RelocScratch& rw, const int32_t* d_ids, const int32_t* d_slot, int n, const int32_t* active,
+                       const SearchHyp* d_hyps, int n_hyp, const RelocOpts& o, const FineStage* fs = nullptr) {
     hnet_ctx* c = s->ctx;
     hnet_keyframes* k = s->kf;
     const int B = c->cfg.max_batch, N = s->n;
     const KeyScratch w(k->scratch, B);
-    const MapStore none = {nullptr, nullptr, nullptr, N, 0};
-    const MapStore& map = k->map ? k->map->dev : none;
+    const MapStore& map = tg.map;
     const int M = map.capacity;                // 0 without a map
     const size_t pyr = (size_t)B * PYR_BYTES;
-    uint8_t *prev = (uint8_t*)c->stage_prev, *curr = (uint8_t*)c->stage_curr;
+    uint8_t *prev = tg.prev, *curr = tg.curr;
+    KeyState* state = tg.state;
     hipStream_t st = c->stream;
-    HIPCHK(c, launch_reloc_thumbs(d_ids, d_slot, n, N, active, k->state, k->key, map, s->ring, 2 * N, rw.thumbs, rw.valid, st));
+    HIPCHK(c, launch_reloc_thumbs(d_ids, d_slot, n, N, active, state, k->key, map, s->ring, 2 * N, rw.thumbs, rw.valid, st));
     if (d_hyps) {
         OrientedRec* srec = reinterpret_cast<OrientedRec*>(rw.srec);
         HIPCHK(c, launch_photo_search_oriented(rw.thumbs, M + 2, M + 2, M + 1, M + 1, n, rw.valid, o.search, d_hyps, n_hyp, rw.hrec, nullptr, st));
         HIPCHK(c, launch_photo_search_winner(rw.hrec, d_hyps, n_hyp, n * (M + 1), rw.valid, srec, st));
-        HIPCHK(c, launch_reloc_pick(d_ids, n, N, k->state, M, rw.valid, srec, w.x0, rw.cand, rw.mslot, reinterpret_cast<OrientedRelocRec*>(rw.out), st));
+        HIPCHK(c, launch_reloc_pick(d_ids, n, N, state, M, rw.valid, srec, w.x0, rw.cand, rw.mslot, reinterpret_cast<OrientedRelocRec*>(rw.out), st));
     } else {
         SearchRec* srec = reinterpret_cast<SearchRec*>(rw.srec);
         HIPCHK(c, launch_photo_search(rw.thumbs, M + 2, M + 2, M + 1, M + 1, n, rw.valid, o.search, srec, nullptr, st));
-        HIPCHK(c, launch_reloc_pick(d_ids, n, N, k->state, M, rw.valid, srec, w.x0, rw.cand, rw.mslot, reinterpret_cast<RelocRec*>(rw.out), st));
+        HIPCHK(c, launch_reloc_pick(d_ids, n, N, state, M, rw.valid, srec, w.x0, rw.cand, rw.mslot, reinterpret_cast<RelocRec*>(rw.out), st));
     }
     HIPCHK(c, launch_reloc_gather(d_ids, d_slot, n, N, rw.cand, k->key, map, s->ring, 2 * N, prev, curr, st));
     if (fs && d_hyps) {
@@ -360,10 +408,10 @@ int enqueue_relocalise(hnet_sessions* s, const RelocScratch& rw, const int32_t* 
     }
     HIPCHK(c, launch_photo_align_robust(prev, curr, n, w.x0, o.align, o.levels, c->pyr_scratch, c->pyr_scratch + pyr, w.start, w.part, w.work, w.rec, st));
     if (d_hyps)
-        HIPCHK(c, launch_reloc_decide(d_ids, n, N, w.rec, w.x0, rw.cand, o, k->state, map, reinterpret_cast<OrientedRelocRec*>(rw.out), rw.attach, st));
+        HIPCHK(c, launch_reloc_decide(d_ids, n, N, w.rec, w.x0, rw.cand, o, state, map, reinterpret_cast<OrientedRelocRec*>(rw.out), rw.attach, st));
     else
-        HIPCHK(c, launch_reloc_decide(d_ids, n, N, w.rec, w.x0, rw.cand, o, k->state, map, reinterpret_cast<RelocRec*>(rw.out), rw.attach, st));
-    if (k->map) HIPCHK(c, launch_keyframe_map_attach(d_ids, n, rw.mslot, rw.attach, map, k->key, st));
+        HIPCHK(c, launch_reloc_decide(d_ids, n, N, w.rec, w.x0, rw.cand, o, state, map, reinterpret_cast<RelocRec*>(rw.out), rw.attach, st));
+    if (k->map && tg.attach_key) HIPCHK(c, launch_keyframe_map_attach(d_ids, n, rw.mslot, rw.attach, map, tg.attach_key, st));
     return HNET_OK;
 }
 
@@ -410,7 +458,7 @@ int relocalise(hnet_sessions* s, int n, const int32_t* ids, const hnet_keyframe_
     const SearchHyp* d_hyps = oriented ? reinterpret_cast<const SearchHyp*>(rw.tab + head) : nullptr;
     HIPCHK(c, hipMemcpyAsync(rw.tab, r->pin_in, head + tab, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipEventRecord(k->ev[0], c->stream));
-    if ((rc = enqueue_relocalise(s, rw, d_ids, d_ids + n, n, nullptr, d_hyps, n_hyp, o)) != HNET_OK) return rc;
+    if ((rc = enqueue_relocalise(s, reloc_targets_store(s), rw, d_ids, d_ids + n, n, nullptr, d_hyps, n_hyp, o)) != HNET_OK) return rc;
     return finish_call(c, k, k->ev, rw.out, r->pin_out, out, (size_t)n * (oriented ? sizeof(OrientedRelocRec) : sizeof(RelocRec)));
 }
 
@@ -451,7 +499,7 @@ int relocalise_fine(hnet_sessions* s, int n, const int32_t* ids, const hnet_keyf
     fs.d_fine = reinterpret_cast<const SearchHyp*>(fw.tab + head + tab);
     HIPCHK(c, hipMemcpyAsync(fw.tab, f->pin_in, head + tab + ftab, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipEventRecord(k->ev[0], c->stream));
-    if ((rc = enqueue_relocalise(s, rw, d_ids, d_ids + n, n, nullptr, d_hyps, n_hyp, o, &fs)) != HNET_OK) return rc;
+    if ((rc = enqueue_relocalise(s, reloc_targets_store(s), rw, d_ids, d_ids + n, n, nullptr, d_hyps, n_hyp, o, &fs)) != HNET_OK) return rc;
     HIPCHK(c, launch_reloc_fine_pack(reinterpret_cast<const OrientedRelocRec*>(rw.out), n, fw.out, c->stream));
     return finish_call(c, k, k->ev, fw.out, f->pin_out, out, (size_t)n * sizeof(FineRelocRec));
 }
@@ -533,6 +581,108 @@ void keyframes_instep_accepted(hnet_sessions* s, int n, const int32_t* ids, cons
             k->has_key[ids[i]] = 1;
             k->count_at_track[ids[i]] = s->st[ids[i]].count;
         }
+}
+
+int keyframes_recover_check(hnet_sessions* s, const hnet_keyframe_relocalise_opts* opts, const hnet_photo_search_hyp* hyps, int n_hyp, const char* who, RelocOpts& o,
+                            SearchHyp* table, int* n_table) {
+    hnet_ctx* c = s->ctx;
+    int rc = reloc_check_opts(c, opts, who, "reloc", o);
+    if (rc != HNET_OK) return rc;
+    SearchHyp identity;
+    if (!hyps && n_hyp == 0) {                 // the identity entry alone
+        hnet_search_oriented::make_hyp(0.0, 1.0, identity);
+        hyps = reinterpret_cast<const hnet_photo_search_hyp*>(&identity);
+        n_hyp = 1;
+    }
+    if ((rc = photo_search_check_table(c, hyps, n_hyp, who)) != HNET_OK) return rc;
+    static_assert(sizeof(hnet_photo_search_hyp) == sizeof(SearchHyp), "the table is copied as it is");
+    memset(table, 0, (size_t)SEARCH_MAX_HYP * sizeof(SearchHyp));
+    memcpy(table, hyps, (size_t)n_hyp * sizeof(SearchHyp));
+    *n_table = n_hyp;
+    return HNET_OK;
+}
+
+int keyframes_instep_recover_ensure(hnet_sessions* s, const char* who) {
+    hnet_ctx* c = s->ctx;
+    hnet_keyframes* k = s->kf;
+    if (!k) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": keyframes are not enabled (hnet_sessions_enable_keyframes)");
+    if (k->instep) return HNET_OK;                 // (a map enabled since then brought its working copies with it: hnet_sessions_enable_keyframe_map)
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    if (const int rc = reloc_ensure(c, k, who); rc != HNET_OK) return rc;
+    KeyInstepWork* w = new KeyInstepWork();
+    if (const KeyMap* m = k->map) {
+        const hipError_t e = instep_map_alloc(w, m, s->n);
+        if (e != hipSuccess) {
+            instep_free(w);
+            return fail(c, HNET_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+        }
+    }
+    k->instep = w;
+    return HNET_OK;
+}
+
+// the map as an in-step track with recovery sees it: the store's images (read only before the accepted attempt) around the working entries and states
+static MapStore instep_map(const hnet_sessions* s) {
+    const hnet_keyframes* k = s->kf;
+    if (!k->map) return MapStore{nullptr, nullptr, nullptr, s->n, 0};
+    return MapStore{k->map->dev.img, k->instep->entry, k->instep->state, k->map->dev.n_sessions, k->map->dev.capacity};
+}
+
+// (hnet_sessions_keyframe_track_recover's launches between its upload and its download, in its order, without the commits and stores of images and
+// without the attach; every attempt starts from the committed tables, so that a repeated one leaves one map serial and not two)
+int keyframes_instep_track_recover(hnet_sessions* s, const KeyTable& tab, int n, const KeyOpts& o, const RelocOpts& ro, const SearchHyp* d_hyps, int n_hyp,
+                                   const int32_t* recover_on, uint8_t* prev, uint8_t* curr, KeyState* state_work, int32_t* accepted, KeyInstepRecover* v,
+                                   hipStream_t st) {
+    hnet_ctx* c = s->ctx;
+    hnet_keyframes* k = s->kf;
+    const int B = c->cfg.max_batch, N = s->n;
+    const KeyScratch w(k->scratch, B);
+    const RelocScratch rw(k->reloc->scratch, B);
+    const size_t pyr = (size_t)B * PYR_BYTES;
+    const MapStore map = instep_map(s);
+    HIPCHK(c, hipMemcpyAsync(state_work, k->state, (size_t)N * sizeof(KeyState), hipMemcpyDeviceToDevice, st));
+    if (const KeyMap* m = k->map) {
+        HIPCHK(c, hipMemcpyAsync(map.entry, m->dev.entry, (size_t)N * map.capacity * sizeof(MapEntry), hipMemcpyDeviceToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(map.state, m->dev.state, (size_t)N * sizeof(MapState), hipMemcpyDeviceToDevice, st));
+    }
+    // the track up to its decision, which is deferred for the lost sessions that recover
+    HIPCHK(c, launch_keyframe_start(tab, n, N, k->state, w.x0, st));
+    HIPCHK(c, launch_keyframe_gather(tab, n, N, k->key, s->ring, 2 * N, prev, curr, st));
+    HIPCHK(c, launch_photo_align_robust(prev, curr, n, w.x0, o.align, o.levels, c->pyr_scratch, c->pyr_scratch + pyr, w.start, w.part, w.work, w.rec, st));
+    HIPCHK(c, launch_filter_kfmr_decide(tab, n, N, w.rec, o.levels, w.x0, o, recover_on, state_work, w.out, w.copy, rw.stash, rw.active, accepted, st));
+    if (const KeyMap* m = k->map) {
+        const MapScratch mw(m->scratch, B);
+        HIPCHK(c, launch_keyframe_map_note(tab.ids, n, w.out, w.copy, state_work, map, mw.store, st));
+    }
+    // the oriented relocalisation of the lost sessions on T0's state: the first commit wrote no image a lost session's search reads, so with the image
+    // commits deferred the search reads the images it would have read
+    const RelocTargets tg{state_work, map, prev, curr, nullptr};
+    if (const int rc = enqueue_relocalise(s, tg, rw, tab.ids, tab.slot, n, rw.active, d_hyps, n_hyp, ro); rc != HNET_OK) return rc;
+    HIPCHK(c, launch_recover_finish(tab.ids, n, N, rw.active, rw.stash, reinterpret_cast<const OrientedRelocRec*>(rw.out), state_work, w.out, rw.copy2, rw.redo, rw.rout, st));
+    if (k->map) HIPCHK(c, launch_recover_note(tab.ids, n, w.out, rw.copy2, rw.redo, state_work, map, rw.store2, st));
+    *v = KeyInstepRecover{w.rec, rw.rout, k->state};
+    return HNET_OK;
+}
+
+int keyframes_instep_commit_recover(hnet_sessions* s, const KeyTable& tab, int n, const uint8_t* curr, const KeyState* state_work, hipStream_t st) {
+    hnet_ctx* c = s->ctx;
+    hnet_keyframes* k = s->kf;
+    const int B = c->cfg.max_batch, N = s->n;
+    const KeyScratch w(k->scratch, B);
+    const RelocScratch rw(k->reloc->scratch, B);
+    HIPCHK(c, hipMemcpyAsync(k->state, state_work, (size_t)N * sizeof(KeyState), hipMemcpyDeviceToDevice, st));
+    HIPCHK(c, launch_keyframe_commit(tab, n, N, w.copy, curr, k->key, st));
+    if (const KeyMap* m = k->map) {
+        const MapScratch mw(m->scratch, B);
+        const KeyInstepWork* iw = k->instep;
+        HIPCHK(c, hipMemcpyAsync(m->dev.entry, iw->entry, (size_t)N * m->dev.capacity * sizeof(MapEntry), hipMemcpyDeviceToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(m->dev.state, iw->state, (size_t)N * sizeof(MapState), hipMemcpyDeviceToDevice, st));
+        HIPCHK(c, launch_keyframe_map_store(tab.ids, n, mw.store, curr, m->dev, st));
+        HIPCHK(c, launch_keyframe_map_attach(tab.ids, n, rw.mslot, rw.attach, m->dev, k->key, st));
+    }
+    HIPCHK(c, launch_keyframe_commit(tab, n, N, rw.copy2, curr, k->key, st));
+    if (const KeyMap* m = k->map) HIPCHK(c, launch_keyframe_map_store(tab.ids, n, rw.store2, curr, m->dev, st));
+    return HNET_OK;
 }
 
 }  // namespace capi
@@ -678,6 +828,7 @@ int hnet_sessions_enable_keyframe_map(hnet_sessions* s, int capacity) {
     if (e == hipSuccess) e = hipHostMalloc((void**)&m->pin_in, map_table_bytes(B), hipHostMallocDefault);
     if (e == hipSuccess) e = hipHostMalloc((void**)&m->pin_out, (size_t)B * sizeof(MapRevisit), hipHostMallocDefault);
     for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipEventCreate(&m->ev[i]);
+    if (e == hipSuccess && k->instep) e = instep_map_alloc(k->instep, m, N);      // (a filter turned the in-step recovery on before the map existed)
     if (e == hipSuccess) e = hipMemsetAsync(m->dev.img, 0, img, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(m->dev.entry, 0, ent, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(m->dev.state, 0, sta, c->stream);
@@ -858,7 +1009,7 @@ int hnet_sessions_keyframe_track_recover(hnet_sessions* s, int n, const int32_t*
         HIPCHK(c, launch_keyframe_map_store(d_ids, n, mw.store, curr, m->dev, st));
     }
     // the oriented relocalisation of the lost sessions on T0's state; the others ride through on absent candidates and quiet-NaN starts
-    if ((rc = enqueue_relocalise(s, rw, d_ids, tab.slot, n, rw.active, d_hyps, n_hyp, o.reloc)) != HNET_OK) return rc;
+    if ((rc = enqueue_relocalise(s, reloc_targets_store(s), rw, d_ids, tab.slot, n, rw.active, d_hyps, n_hyp, o.reloc)) != HNET_OK) return rc;
     // T0 | RECOVERED or T1, and T1's commit for the unrecovered sessions (curr still holds every slot's current frame)
     HIPCHK(c, launch_recover_finish(d_ids, n, N, rw.active, rw.stash, reinterpret_cast<const OrientedRelocRec*>(rw.out), k->state, w.out, rw.copy2, rw.redo, rw.rout, st));
     HIPCHK(c, launch_keyframe_commit(tab, n, N, rw.copy2, curr, k->key, st));

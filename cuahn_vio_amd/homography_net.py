@@ -1096,6 +1096,23 @@ class HnetFilters:
         self._check(self._L.hnet_filters_last_keyframe_measure(self._f, int(n), out.ctypes.data))
         return out
 
+    def set_keyframe_recover(self, id, reloc=None, hyps=None):
+        """recovery inside session id's in-step keyframe track (hnet_filters_set_keyframe_recover; the session must measure): reloc a KeyframeRelocOpts
+        or a dict in the keyword form of _capi.keyframe_relocalise_opts, hyps as op_photo_search_oriented (None: the default yaw table); reloc None = off"""
+        if reloc is None:
+            self._check(self._L.hnet_filters_set_keyframe_recover(self._f, int(id), None, None, 0))
+            return
+        o = reloc if isinstance(reloc, _capi.KeyframeRelocOpts) else _capi.keyframe_relocalise_opts(**reloc)
+        h = _capi.photo_search_table(hyps)
+        self._check(self._L.hnet_filters_set_keyframe_recover(self._f, int(id), C.addressof(o), h.ctypes.data, len(h)))
+
+    def last_keyframe_recover(self, n):
+        """the records [n] of _capi.KEYFRAME_MEASURE_RECOVER_DTYPE of the last step (of n sessions; another n, or a step without a recovering session,
+        is refused)"""
+        out = np.zeros(int(n), _capi.KEYFRAME_MEASURE_RECOVER_DTYPE)
+        self._check(self._L.hnet_filters_last_keyframe_recover(self._f, int(n), out.ctypes.data))
+        return out
+
     def keyframe_measure_stats(self, id):
         st = _capi.KeyframeMeasureStats()
         self._check(self._L.hnet_filters_keyframe_measure_stats(self._f, int(id), C.byref(st)))

@@ -1212,6 +1212,42 @@ typedef struct hnet_keyframe_measure_stats { int64_t asked, applied, unusable, n
 int  hnet_filters_keyframe_measure_stats(const hnet_filters* f, int id, hnet_keyframe_measure_stats* out);
 int  hnet_filters_reset_keyframe_measure_stats(hnet_filters* f, int id);
 
+/* ---- hnet_filters: recovering a lost camera INSIDE the in-step keyframe track (csrc/kernels_filters_keyframe_recover.hip; the shared code is
+ * include/hnet_keyframe_measure_recover.h).  Per measuring session and off by default.  With auto_rekey = 1 a frame the in-step track judges
+ * LOST is committed inside the step: the lost frame becomes the keyframe, the origin chain takes a link of dead reckoning and prev_ok goes to 0 - and
+ * nothing can be put between the verdict and its commit from outside.  With the feature on, the session's in-step track becomes
+ * hnet_sessions_keyframe_track_recover with the filter's own step_px, the session's gap, the measure options' `track` block and the reloc options and
+ * table given here: a LOST session is relocalised (oriented) on T0's state before its re-key is committed.  The keyframe state, the store and the map
+ * end byte for byte as that sessions call leaves them.  Then, in this order: HNET_KFM_FIRST; HNET_KFM_TRACK_LOST only for a LOST record without
+ * HNET_KF_RECOVERED; HNET_KFM_REATTACHED when the relocalise re-attached the session to a map keyframe (HNET_RL_ATTACHED): the keyframe changed under
+ * the session, the frame has no consecutive-frame meaning and is FIRST-like, nothing is applied; the remaining reasons as before.  A frame recovered on
+ * its own keyframe (HNET_RL_RETRACKED) still measures: z_px and R_px are formed from the relocalise's level-0 record reloc.rv.rec (the trials accepted
+ * over the levels of ITS alignment) against key_px before the call, and the informational HNET_KFM_FROM_RELOC is set.  Such a z_px may lie far from the
+ * prior - a kidnapped camera really did move - and whether it is applied is the session's NIS gate's business.  prev_ok stays 1 after either recovery.
+ * No fine stage runs inside the step and no re-key is judged on a recovered frame.  `when` applies unchanged.  The per-session statistics count
+ * "unusable" with HNET_KFMR_UNUSABLE; without the feature the new bit never occurs.
+ * A step or advance with at least one recovering STEPPING session enqueues hnet_sessions_keyframe_track_recover's launches in place of the track's, on
+ * working copies of the state table and of the map's entries and states; every image write (the first commit, the attach, the second commit, both map
+ * stores) follows the ACCEPTED attempt, stream ordered: a repeated attempt leaves what a single one leaves.  Still one upload, one download, one
+ * synchronisation.  A call without a recovering stepping session launches exactly what it launched before.
+ * HNET_ERR_INVALID_ARG from the step or advance, nothing changed: stepping recovering sessions whose reloc options or tables differ byte-wise. */
+enum { HNET_KFM_FROM_RELOC = 65536,      /* the measurement was taken from the relocalise's record; informational */
+       HNET_KFM_REATTACHED = 131072,     /* UNUSABLE: the frame was re-attached to a map keyframe */
+       HNET_KFMR_UNUSABLE = HNET_KFM_UNUSABLE | 131072 };
+typedef struct hnet_keyframe_measure_recover {
+    hnet_keyframe_measure m;   /* m.track: byte for byte hnet_sessions_keyframe_track_recover's `track` for m.step_px */
+    hnet_keyframe_relocalise_oriented reloc;   /* its `reloc`: all zero with target -2 for a session that needed no recovery or has the feature off */
+} hnet_keyframe_measure_recover;
+/* reloc == NULL turns recovery off for the session; hyps == NULL with n_hyp == 0 is the identity entry alone.  The table is copied.  The first call with
+ * options allocates the feature's buffers and grows the output block (hnet_filters_last_* have nothing to describe until the next step).  Turning the
+ * measurement off (hnet_filters_set_keyframe_measure with NULL) turns recovery off.  HNET_ERR_INVALID_ARG, nothing changed: a bad id, a session without
+ * hnet_filters_set_keyframe_measure on, options or a table hnet_sessions_keyframe_relocalise_oriented would refuse.  A keyframe map may be enabled
+ * before or after (while no session holds a keyframe, as always): the working copies of its tables come with whichever call is second. */
+int  hnet_filters_set_keyframe_recover(hnet_filters* f, int id, const hnet_keyframe_relocalise_opts* reloc, const hnet_photo_search_hyp* hyps, int n_hyp);
+/* hnet_filters_last_keyframe_measure's records with the relocalise records.  A wrong n, or a last call that ran without a recovering session:
+ * HNET_ERR_INVALID_ARG, nothing written */
+int  hnet_filters_last_keyframe_recover(const hnet_filters* f, int n, hnet_keyframe_measure_recover* out);
+
 int hnet_synchronize(hnet_ctx* ctx, void* stream);
 int hnet_last_timing(const hnet_ctx* ctx, hnet_timing* out);
 
