@@ -1,10 +1,13 @@
 // capi_filters.hip — hnet_filters_* and hnet_filter_default_* of include/hnet.h: one device filter per session of a sessions object (sessions_internal.h).
 // hnet_filters_step and hnet_filters_advance differ in how a call's states get their readings (the host's windows / the device's IMU rings and the
 // initialiser); the IEKF iterations of an attempt, the overflow test and the bookkeeping of an accepted call are one piece of code each, below.
+// The two features that add a measurement behind the network's iterations - the photometric fallback (filters_enqueue_refine) and the keyframe
+// measurement with or without recovery (filters_enqueue_keyframe, ONE path: the track is capi_keyframe.hip's keyframes_instep_track, the measure and
+// finish kernels kernels_filters_keyframe.hip's) - share the filter's own launches on it (filters_enqueue_measured).  The sections of every
+// scratch block are carved by capi_internal.h's Carver.
 #include "sessions_internal.h"
 #include "filters_refine_dev.h"
 #include "filters_keyframe_dev.h"
-#include "filters_keyframe_recover_dev.h"
 
 using namespace hnet;
 using namespace capi;
@@ -126,18 +129,17 @@ struct hnet_filters {
 struct RefineScratch {
     RobustRec* rec; RobustStart* start; RobustWork* work; RobustSums* part; float *x0, *prior_px, *m72; InnovRec* innov; double* nis0; size_t bytes;
     RefineScratch(uint8_t* b, int B, int N) {
-        size_t o = 0;
-        auto take = [&](size_t n) { uint8_t* p = b + o; o += (n + 255) & ~(size_t)255; return p; };
-        rec = reinterpret_cast<RobustRec*>(take((size_t)HNET_ALIGN_MAX_LEVELS * B * sizeof(RobustRec)));
-        start = reinterpret_cast<RobustStart*>(take((size_t)B * sizeof(RobustStart)));
-        work = reinterpret_cast<RobustWork*>(take((size_t)B * sizeof(RobustWork)));
-        part = reinterpret_cast<RobustSums*>(take((size_t)B * PHOTO_SLICES * sizeof(RobustSums)));
-        x0 = reinterpret_cast<float*>(take((size_t)B * 8 * sizeof(float)));
-        prior_px = reinterpret_cast<float*>(take((size_t)B * 8 * sizeof(float)));
-        m72 = reinterpret_cast<float*>(take((size_t)B * 72 * sizeof(float)));
-        innov = reinterpret_cast<InnovRec*>(take((size_t)B * sizeof(InnovRec)));
-        nis0 = reinterpret_cast<double*>(take((size_t)N * sizeof(double)));      // stays zero: "no NIS gate" for a filters object without innovations
-        bytes = o;
+        Carver cv{b};
+        rec = cv.take<RobustRec>((size_t)HNET_ALIGN_MAX_LEVELS * B);
+        start = cv.take<RobustStart>((size_t)B);
+        work = cv.take<RobustWork>((size_t)B);
+        part = cv.take<RobustSums>((size_t)B * PHOTO_SLICES);
+        x0 = cv.take<float>((size_t)B * 8);
+        prior_px = cv.take<float>((size_t)B * 8);
+        m72 = cv.take<float>((size_t)B * 72);
+        innov = cv.take<InnovRec>((size_t)B);
+        nis0 = cv.take<double>((size_t)N);      // stays zero: "no NIS gate" for a filters object without innovations
+        bytes = cv.used;
     }
 };
 
@@ -145,20 +147,19 @@ struct RefineScratch {
 struct KfmScratch {
     uint8_t *prev, *curr; float *step, *prior_px, *m72; InnovRec* innov; int32_t *opened, *prev_ok, *prev_ok_work; KeyState* state_work; double* nis0; size_t bytes;
     KfmScratch(uint8_t* b, int B, int N) {
-        size_t o = 0;
-        auto take = [&](size_t n) { uint8_t* p = b + o; o += (n + 255) & ~(size_t)255; return p; };
-        prev = take((size_t)B * NPIX);
-        curr = take((size_t)B * NPIX);
-        step = reinterpret_cast<float*>(take((size_t)B * 8 * sizeof(float)));
-        prior_px = reinterpret_cast<float*>(take((size_t)B * 8 * sizeof(float)));
-        m72 = reinterpret_cast<float*>(take((size_t)B * 72 * sizeof(float)));
-        innov = reinterpret_cast<InnovRec*>(take((size_t)B * sizeof(InnovRec)));
-        opened = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
-        prev_ok = reinterpret_cast<int32_t*>(take((size_t)N * sizeof(int32_t)));      // starts zero: never measured
-        prev_ok_work = reinterpret_cast<int32_t*>(take((size_t)N * sizeof(int32_t)));
-        state_work = reinterpret_cast<KeyState*>(take((size_t)N * sizeof(KeyState)));
-        nis0 = reinterpret_cast<double*>(take((size_t)N * sizeof(double)));           // stays zero: "no NIS gate" for a filters object without innovations
-        bytes = o;
+        Carver cv{b};
+        prev = cv.take((size_t)B * NPIX);
+        curr = cv.take((size_t)B * NPIX);
+        step = cv.take<float>((size_t)B * 8);
+        prior_px = cv.take<float>((size_t)B * 8);
+        m72 = cv.take<float>((size_t)B * 72);
+        innov = cv.take<InnovRec>((size_t)B);
+        opened = cv.take<int32_t>((size_t)B);
+        prev_ok = cv.take<int32_t>((size_t)N);      // starts zero: never measured
+        prev_ok_work = cv.take<int32_t>((size_t)N);
+        state_work = cv.take<KeyState>((size_t)N);
+        nis0 = cv.take<double>((size_t)N);           // stays zero: "no NIS gate" for a filters object without innovations
+        bytes = cv.used;
     }
 };
 // the sections of d_kfmr_scratch for max_batch B and N sessions: the per-session recover_on words (start zero: off) and tables, the per-slot trials the
@@ -166,12 +167,11 @@ struct KfmScratch {
 struct KfmrScratch {
     int32_t *on, *accepted; SearchHyp* hyps; size_t bytes;
     KfmrScratch(uint8_t* b, int B, int N) {
-        size_t o = 0;
-        auto take = [&](size_t n) { uint8_t* p = b + o; o += (n + 255) & ~(size_t)255; return p; };
-        on = reinterpret_cast<int32_t*>(take((size_t)N * sizeof(int32_t)));
-        accepted = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
-        hyps = reinterpret_cast<SearchHyp*>(take((size_t)N * SEARCH_MAX_HYP * sizeof(SearchHyp)));
-        bytes = o;
+        Carver cv{b};
+        on = cv.take<int32_t>((size_t)N);
+        accepted = cv.take<int32_t>((size_t)B);
+        hyps = cv.take<SearchHyp>((size_t)N * SEARCH_MAX_HYP);
+        bytes = cv.used;
     }
 };
 // a call's keyframe measurement: the session whose track options serve it (-1: the call has no measuring session), the {ids | curr slot | gap}
@@ -467,6 +467,17 @@ static int filters_enqueue_iekf(hnet_filters* f, hnet_ctx* const ctx[2], const O
     if (f->photo && n && !photo_gated) HIPCHK(c, filters_launch_photo(f, d, n, st));
     return HNET_OK;
 }
+// The filter's own launches on a feature's packed measurement m72 [n][72], behind the feature's measure kernel (which opened d_gate for the usable slots
+// and closed it for every other): the prior into the feature's prior_px, the innovation record into the feature's innov under the sessions' NIS gates
+// (nis0: zeros, for a filters object without innovations), and the update with update_offset = 0 and last = 1: the reset every slot is still owed.
+static int filters_enqueue_measured(hnet_filters* f, hnet_ctx* c, const OutView& d, int n, const int32_t* d_ids, int32_t* d_gate, float* prior_px, const float* m72,
+                                    const double* nis0, InnovRec* innov, hipStream_t st) {
+    const int N = f->s->n;
+    HIPCHK(c, launch_filter_prior(d.work, n, prior_px, f->d_prior_cam, st));
+    HIPCHK(c, launch_filter_innovation(d_ids, n, N, f->d_params, d.work, m72, f->d_prior_cam, f->innov ? f->d_max_nis : nis0, d_gate, d.upd, 0, innov, nullptr, st));
+    HIPCHK(c, launch_filter_update(d_ids, n, N, f->d_params, m72, f->d_prior_cam, d_gate, 0, 1, d.work, d.upd, st));
+    return HNET_OK;
+}
 // The fallback of a call's n stepping sessions, behind the last iteration's update (which ran with last = 0): which slots align (verdict 1, refinement
 // on, nothing applied) from iteration 0's fp32 prior, the alignment on the staged pairs (NaN starts elsewhere: DEGENERATE at every level, early returns),
 // the measurement (it opens d_gate for the usable slots and closes it for every other), then the filter's own prior, innovation and update launches on
@@ -482,9 +493,7 @@ static int filters_enqueue_refine(hnet_filters* f, hnet_ctx* c, const OutView& d
     HIPCHK(c, launch_photo_align_robust((const uint8_t*)c->stage_prev, (const uint8_t*)c->stage_curr, n, w.x0, o, ro.levels, c->pyr_scratch, c->pyr_scratch + pyr, w.start,
                                         w.part, w.work, w.rec, st));
     HIPCHK(c, launch_filter_refine_measure(d_ids, n, N, f->d_params, f->d_refine_cfg, w.rec, ro.levels, w.m72, d_gate, d.refine, st));
-    HIPCHK(c, launch_filter_prior(d.work, n, w.prior_px, f->d_prior_cam, st));
-    HIPCHK(c, launch_filter_innovation(d_ids, n, N, f->d_params, d.work, w.m72, f->d_prior_cam, f->innov ? f->d_max_nis : w.nis0, d_gate, d.upd, 0, w.innov, nullptr, st));
-    HIPCHK(c, launch_filter_update(d_ids, n, N, f->d_params, w.m72, f->d_prior_cam, d_gate, 0, 1, d.work, d.upd, st));
+    if (const int r = filters_enqueue_measured(f, c, d, n, d_ids, d_gate, w.prior_px, w.m72, w.nis0, w.innov, st); r != HNET_OK) return r;
     HIPCHK(c, launch_filter_refine_finish(n, w.innov, d.upd, f->iters, d.refine, st));
     return HNET_OK;
 }
@@ -500,32 +509,18 @@ static int filters_enqueue_keyframe(hnet_filters* f, hnet_ctx* c, const OutView&
     KeyOpts ko;
     memcpy(&ko, &f->kfm_opts[kfm.ref].track, sizeof ko);
     const KeyTable tab{w.step, kfm.d_tab, kfm.d_tab + n, kfm.d_tab + 2 * (size_t)n};
-    if (kfm.rref >= 0) {                                           //  the track with recovery, the measure and finish kernels that read its records
-        const KfmrScratch rw(f->d_kfmr_scratch, B, N);
-        capi::KeyInstepRecover rv;
-        HIPCHK(c, launch_filter_kfm_step(d_ids, n, N, f->d_kfm_cfg, d.work, w.step, d.kfm, st));
-        if (const int r = capi::keyframes_instep_track_recover(f->s, tab, n, ko, f->kfmr_opts[kfm.rref], rw.hyps + (size_t)kfm.rref * SEARCH_MAX_HYP, f->kfmr_n_hyp[kfm.rref],
-                                                               rw.on, w.prev, w.curr, w.state_work, rw.accepted, &rv, st);
-            r != HNET_OK)
-            return r;
-        HIPCHK(c, hipMemcpyAsync(w.prev_ok_work, w.prev_ok, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-        HIPCHK(c, launch_filter_kfmr_measure(d_ids, n, N, f->d_params, f->d_kfm_cfg, rv.state, w.prev_ok, rv.rout, rw.accepted, rv.rec2, f->kfmr_opts[kfm.rref].levels, d.upd,
-                                             w.m72, d_gate, w.opened, d.kfm, st));
-        HIPCHK(c, launch_filter_prior(d.work, n, w.prior_px, f->d_prior_cam, st));
-        HIPCHK(c, launch_filter_innovation(d_ids, n, N, f->d_params, d.work, w.m72, f->d_prior_cam, f->innov ? f->d_max_nis : w.nis0, d_gate, d.upd, 0, w.innov, nullptr, st));
-        HIPCHK(c, launch_filter_update(d_ids, n, N, f->d_params, w.m72, f->d_prior_cam, d_gate, 0, 1, d.work, d.upd, st));
-        HIPCHK(c, launch_filter_kfmr_finish(d_ids, n, N, w.innov, d.upd, w.opened, f->iters, rv.rout, w.prev_ok_work, d.kfm, d.kfmr, st));
-        return HNET_OK;
-    }
+    const bool recovering = kfm.rref >= 0;                         //  the track with recovery; the measure and finish kernels then read its records
+    const KfmrScratch rw(recovering ? f->d_kfmr_scratch : nullptr, B, N);
+    capi::KeyRecovery rc{};
+    if (recovering) rc = capi::KeyRecovery{f->kfmr_opts[kfm.rref], rw.hyps + (size_t)kfm.rref * SEARCH_MAX_HYP, f->kfmr_n_hyp[kfm.rref], rw.on, rw.accepted};
     capi::KeyInstep v;
     HIPCHK(c, launch_filter_kfm_step(d_ids, n, N, f->d_kfm_cfg, d.work, w.step, d.kfm, st));
-    if (const int r = capi::keyframes_instep_track(f->s, tab, n, ko, w.prev, w.curr, w.state_work, &v, st); r != HNET_OK) return r;
+    if (const int r = capi::keyframes_instep_track(f->s, tab, n, ko, recovering ? &rc : nullptr, w.prev, w.curr, w.state_work, &v); r != HNET_OK) return r;
     HIPCHK(c, hipMemcpyAsync(w.prev_ok_work, w.prev_ok, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-    HIPCHK(c, launch_filter_kfm_measure(d_ids, n, N, f->d_params, f->d_kfm_cfg, v.state, w.prev_ok, v.out, v.rec, ko.levels, d.upd, w.m72, d_gate, w.opened, d.kfm, st));
-    HIPCHK(c, launch_filter_prior(d.work, n, w.prior_px, f->d_prior_cam, st));
-    HIPCHK(c, launch_filter_innovation(d_ids, n, N, f->d_params, d.work, w.m72, f->d_prior_cam, f->innov ? f->d_max_nis : w.nis0, d_gate, d.upd, 0, w.innov, nullptr, st));
-    HIPCHK(c, launch_filter_update(d_ids, n, N, f->d_params, w.m72, f->d_prior_cam, d_gate, 0, 1, d.work, d.upd, st));
-    HIPCHK(c, launch_filter_kfm_finish(d_ids, n, N, w.innov, d.upd, w.opened, f->iters, w.prev_ok_work, d.kfm, st));
+    HIPCHK(c, launch_filter_kfm_measure(d_ids, n, N, f->d_params, f->d_kfm_cfg, v.state, w.prev_ok, v.track, v.rout, rc.accepted, v.rec, v.levels, d.upd,
+                                        w.m72, d_gate, w.opened, d.kfm, st));
+    if (const int r = filters_enqueue_measured(f, c, d, n, d_ids, d_gate, w.prior_px, w.m72, w.nis0, w.innov, st); r != HNET_OK) return r;
+    HIPCHK(c, launch_filter_kfm_finish(d_ids, n, N, w.innov, d.upd, w.opened, f->iters, v.rout, w.prev_ok_work, d.kfm, recovering ? d.kfmr : nullptr, st));
     return HNET_OK;
 }
 // the tail of an ACCEPTED call with a keyframe measurement, stream ordered behind the attempt and not synchronised: the track's commits (the state
@@ -534,10 +529,7 @@ static int filters_commit_keyframe(hnet_filters* f, hnet_ctx* c, int n, const in
     const int B = c->cfg.max_batch, N = f->s->n;
     const KfmScratch w(f->d_kfm_scratch, B, N);
     const KeyTable tab{w.step, kfm.d_tab, kfm.d_tab + n, kfm.d_tab + 2 * (size_t)n};
-    if (const int r = kfm.rref >= 0 ? capi::keyframes_instep_commit_recover(f->s, tab, n, w.curr, w.state_work, st)
-                                    : capi::keyframes_instep_commit(f->s, tab, n, w.curr, w.state_work, st);
-        r != HNET_OK)
-        return r;
+    if (const int r = capi::keyframes_instep_commit(f->s, tab, n, kfm.rref >= 0, w.curr, w.state_work); r != HNET_OK) return r;
     HIPCHK(c, hipMemcpyAsync(w.prev_ok, w.prev_ok_work, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
     capi::keyframes_instep_accepted(f->s, n, ids, f->kfm_on.data());
     return HNET_OK;
@@ -757,7 +749,7 @@ int hnet_filters_step(hnet_filters* f, int n, const int32_t* ids, const double* 
         sessions_pair(s, id, pairs + 2 * i);
     }
     roff[n] = R;
-    if (measuring) capi::keyframes_instep_table(s, n, ids, f->kfm_on.data(), reinterpret_cast<int32_t*>(f->pin_in + o_kf));
+    if (measuring) capi::keyframes_table(s, n, ids, f->kfm_on.data(), reinterpret_cast<int32_t*>(f->pin_in + o_kf));
     const KfmCall kfm{kfm_ref, reinterpret_cast<const int32_t*>(f->d_in + o_kf), kfmr_ref};
     const hnet_ekf::ImuData* d_rd = reinterpret_cast<const hnet_ekf::ImuData*>(f->d_in);
     const double* d_tf = reinterpret_cast<const double*>(f->d_in + o_t);
@@ -1018,7 +1010,7 @@ int hnet_filters_advance(hnet_filters* f, int n, const int32_t* ids, hnet_filter
         hid[j] = id;
         sessions_pair(s, id, pairs + 2 * j);
     }
-    if (measuring) capi::keyframes_instep_table(s, n_s, stepping.data(), f->kfm_on.data(), reinterpret_cast<int32_t*>(f->pin_adv + L.o_kf));
+    if (measuring) capi::keyframes_table(s, n_s, stepping.data(), f->kfm_on.data(), reinterpret_cast<int32_t*>(f->pin_adv + L.o_kf));
     const KfmCall kfm{kfm_ref, reinterpret_cast<const int32_t*>(f->d_adv + L.o_kf), kfmr_ref};
     const AdvanceJob* d_job = reinterpret_cast<const AdvanceJob*>(f->d_adv);
     const uint64_t* d_seq = reinterpret_cast<const uint64_t*>(f->d_adv + L.o_seq);
@@ -1432,7 +1424,7 @@ int hnet_filters_last_keyframe_measure(const hnet_filters* f, int n, hnet_keyfra
     return HNET_OK;
 }
 
-// ---- filters, recovery inside the in-step track (include/hnet.h): csrc/kernels_filters_keyframe_recover.hip around
+// ---- filters, recovery inside the in-step track (include/hnet.h): csrc/kernels_filters_keyframe.hip around
 // hnet_sessions_keyframe_track_recover's launches (capi_keyframe.hip) ----
 
 static_assert(sizeof(hnet_keyframe_measure_recover) == sizeof(KfmrRec) && offsetof(hnet_keyframe_measure_recover, reloc) == offsetof(KfmrRec, reloc) &&

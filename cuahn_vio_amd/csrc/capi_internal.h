@@ -198,6 +198,19 @@ bool all_finite(const T* v, size_t n) {
     return true;
 }
 
+// The sections of a scratch block, carved in order: take<T>(count) is the next section, count elements of T at a 256-byte boundary; `used`: the bytes
+// taken so far (base null: only the size is wanted)
+struct Carver {
+    uint8_t* base;
+    size_t used = 0;
+    template <typename T = uint8_t>
+    T* take(size_t count) {
+        T* p = reinterpret_cast<T*>(base + used);
+        used += (count * sizeof(T) + 255) & ~(size_t)255;
+        return p;
+    }
+};
+
 // Device temporaries of the operator-level entry points: freed on every return path (HIPCHK returns early).
 struct DevTemps {
     std::vector<void*> ptrs;

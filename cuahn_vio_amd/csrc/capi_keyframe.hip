@@ -20,14 +20,15 @@
 // scratch of its own (FineScratch): a store that never makes the call has kf->fine == nullptr, and RelocScratch is what it was.
 // And the track INSIDE a filter step (filters_keyframe_dev.h): capi_filters.hip enqueues the track's unchanged launches through the
 // keyframes_instep_* functions below, with the store's own scratch, decide on a copy of the state table and the commits deferred to the accepted attempt.
-// And the RECOVERY inside that in-step track (filters_keyframe_recover_dev.h): the launches of hnet_sessions_keyframe_track_recover on working
-// copies of the state table and of the map's entries and states (KeyInstepWork, allocated by hnet_filters_set_keyframe_recover), every image write
-// deferred to the accepted attempt.  enqueue_relocalise takes what it reads and writes as a RelocTargets for that.
+// And the RECOVERY inside that in-step track: the launches of hnet_sessions_keyframe_track_recover on working copies of the state table and
+// of the map's entries and states (KeyInstepWork, allocated by hnet_filters_set_keyframe_recover), every image write deferred to the accepted attempt.
+// The four tracks - the two sessions calls and the in-step track with and without recovery - share ONE launch sequence (enqueue_track), as
+// the relocalisations do: what each reads and writes is its RelocTargets, the recovering part its KeyRecovery.  The host table of a track has one
+// filler (keyframes_table) and the accepted in-step attempt one commit (keyframes_instep_commit).
 #include "sessions_internal.h"
 #include "keyframe_recover_dev.h"
 #include "photo_search_fine_dev.h"
 #include "filters_keyframe_dev.h"
-#include "filters_keyframe_recover_dev.h"
 
 using namespace hnet;
 using namespace capi;
@@ -133,17 +134,16 @@ size_t table_bytes(int n) { return (size_t)n * (8 * sizeof(float) + 3 * sizeof(i
 struct KeyScratch {
     RobustRec* rec; RobustStart* start; RobustWork* work; RobustSums* part; float* x0; uint8_t* tab; KeyTrack* out; int32_t* copy; size_t bytes;
     KeyScratch(uint8_t* b, int B) {
-        size_t o = 0;
-        auto take = [&](size_t n) { uint8_t* p = b + o; o += (n + 255) & ~(size_t)255; return p; };
-        rec = reinterpret_cast<RobustRec*>(take((size_t)HNET_ALIGN_MAX_LEVELS * B * sizeof(RobustRec)));
-        start = reinterpret_cast<RobustStart*>(take((size_t)B * sizeof(RobustStart)));
-        work = reinterpret_cast<RobustWork*>(take((size_t)B * sizeof(RobustWork)));
-        part = reinterpret_cast<RobustSums*>(take((size_t)B * PHOTO_SLICES * sizeof(RobustSums)));
-        x0 = reinterpret_cast<float*>(take((size_t)B * 8 * sizeof(float)));
-        tab = take(table_bytes(B));
-        out = reinterpret_cast<KeyTrack*>(take((size_t)B * sizeof(KeyTrack)));
-        copy = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
-        bytes = o;
+        Carver cv{b};
+        rec = cv.take<RobustRec>((size_t)HNET_ALIGN_MAX_LEVELS * B);
+        start = cv.take<RobustStart>(B);
+        work = cv.take<RobustWork>(B);
+        part = cv.take<RobustSums>((size_t)B * PHOTO_SLICES);
+        x0 = cv.take<float>((size_t)B * 8);
+        tab = cv.take(table_bytes(B));
+        out = cv.take<KeyTrack>(B);
+        copy = cv.take<int32_t>(B);
+        bytes = cv.used;
     }
 };
 
@@ -160,14 +160,13 @@ size_t map_table_bytes(int n) { return (size_t)n * 2 * sizeof(int32_t); }
 struct MapScratch {
     int32_t *tab, *cand, *store, *attach; MapRevisit* out; size_t bytes;
     MapScratch(uint8_t* b, int B) {
-        size_t o = 0;
-        auto take = [&](size_t n) { uint8_t* p = b + o; o += (n + 255) & ~(size_t)255; return p; };
-        tab = reinterpret_cast<int32_t*>(take(map_table_bytes(B)));
-        cand = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
-        store = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
-        attach = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
-        out = reinterpret_cast<MapRevisit*>(take((size_t)B * sizeof(MapRevisit)));
-        bytes = o;
+        Carver cv{b};
+        tab = cv.take<int32_t>((size_t)B * 2);
+        cand = cv.take<int32_t>(B);
+        store = cv.take<int32_t>(B);
+        attach = cv.take<int32_t>(B);
+        out = cv.take<MapRevisit>(B);
+        bytes = cv.used;
     }
 };
 
@@ -184,24 +183,23 @@ struct RelocScratch {
     uint8_t *tab, *thumbs, *srec, *out; int32_t *valid, *cand, *mslot, *attach; SearchRec* hrec;
     RecoverStash* stash; int32_t *active, *copy2, *redo, *store2; RecoverRec* rout; size_t bytes;
     RelocScratch(uint8_t* b, int B) {
-        size_t o = 0;
-        auto take = [&](size_t n) { uint8_t* p = b + o; o += (n + 255) & ~(size_t)255; return p; };
-        tab = take(recover_table_bytes(B, SEARCH_MAX_HYP));
-        thumbs = take((size_t)B * (RELOC_MAX_CANDIDATES + 1) * THUMB_BYTES);
-        valid = reinterpret_cast<int32_t*>(take((size_t)B * RELOC_MAX_CANDIDATES * sizeof(int32_t)));
-        hrec = reinterpret_cast<SearchRec*>(take((size_t)B * RELOC_MAX_CANDIDATES * SEARCH_MAX_HYP * sizeof(SearchRec)));
-        srec = take((size_t)B * RELOC_MAX_CANDIDATES * sizeof(OrientedRec));
-        cand = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
-        mslot = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
-        attach = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
-        out = take((size_t)B * sizeof(OrientedRelocRec));
-        stash = reinterpret_cast<RecoverStash*>(take((size_t)B * sizeof(RecoverStash)));
-        active = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
-        copy2 = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
-        redo = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
-        store2 = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
-        rout = reinterpret_cast<RecoverRec*>(take((size_t)B * sizeof(RecoverRec)));
-        bytes = o;
+        Carver cv{b};
+        tab = cv.take(recover_table_bytes(B, SEARCH_MAX_HYP));
+        thumbs = cv.take((size_t)B * (RELOC_MAX_CANDIDATES + 1) * THUMB_BYTES);
+        valid = cv.take<int32_t>((size_t)B * RELOC_MAX_CANDIDATES);
+        hrec = cv.take<SearchRec>((size_t)B * RELOC_MAX_CANDIDATES * SEARCH_MAX_HYP);
+        srec = cv.take((size_t)B * RELOC_MAX_CANDIDATES * sizeof(OrientedRec));
+        cand = cv.take<int32_t>(B);
+        mslot = cv.take<int32_t>(B);
+        attach = cv.take<int32_t>(B);
+        out = cv.take((size_t)B * sizeof(OrientedRelocRec));
+        stash = cv.take<RecoverStash>(B);
+        active = cv.take<int32_t>(B);
+        copy2 = cv.take<int32_t>(B);
+        redo = cv.take<int32_t>(B);
+        store2 = cv.take<int32_t>(B);
+        rout = cv.take<RecoverRec>(B);
+        bytes = cv.used;
     }
 };
 static_assert(sizeof(OrientedRec) >= sizeof(SearchRec) && sizeof(OrientedRelocRec) >= sizeof(RelocRec) && sizeof(RecoverRec) >= sizeof(OrientedRelocRec),
@@ -214,13 +212,12 @@ size_t fine_table_bytes(int n, int n_hyp, int n_fine) { return map_table_bytes(n
 struct FineScratch {
     uint8_t *tab, *thumbs; FineEntry* ent; FineRelocRec* out; size_t bytes;
     FineScratch(uint8_t* b, int B) {
-        size_t o = 0;
-        auto take = [&](size_t n) { uint8_t* p = b + o; o += (n + 255) & ~(size_t)255; return p; };
-        tab = take(fine_table_bytes(B, SEARCH_MAX_HYP, FINE_MAX));
-        thumbs = take((size_t)2 * B * FINE_THUMB_BYTES);
-        ent = reinterpret_cast<FineEntry*>(take((size_t)B * FINE_MAX * sizeof(FineEntry)));
-        out = reinterpret_cast<FineRelocRec*>(take((size_t)B * sizeof(FineRelocRec)));
-        bytes = o;
+        Carver cv{b};
+        tab = cv.take(fine_table_bytes(B, SEARCH_MAX_HYP, FINE_MAX));
+        thumbs = cv.take((size_t)2 * B * FINE_THUMB_BYTES);
+        ent = cv.take<FineEntry>((size_t)B * FINE_MAX);
+        out = cv.take<FineRelocRec>(B);
+        bytes = cv.used;
     }
 };
 // what enqueue_relocalise runs between the gather and the alignment of a fine relocalise
@@ -356,9 +353,11 @@ int fine_ensure(hnet_ctx* c, hnet_keyframes* k, const char* who) {
     return HNET_OK;
 }
 
-// what a relocalisation reads and writes besides its scratch
-struct RelocTargets { KeyState* state; MapStore map; uint8_t *prev, *curr, *attach_key; };
-// the store's own tables, the context's staging pair, the attach into the store: what the three sessions calls pass
+// what a track or a relocalisation reads and writes besides its scratch: the state table its decisions write, the map whose entries and states its notes
+// and decisions write (entry null: none, the sequence has no note), the staging pair of its gather and alignment, and the key images that its commits
+// and its attach write in sequence, each with its map store (null: every image write is left to a later commit, keyframes_instep_commit)
+struct RelocTargets { KeyState* state; MapStore map; uint8_t *prev, *curr, *commit_key; };
+// the store's own tables, the context's staging pair, the commits and the attach into the store: what the sessions calls pass
 RelocTargets reloc_targets_store(hnet_sessions* s) {
     hnet_ctx* c = s->ctx;
     hnet_keyframes* k = s->kf;
@@ -372,7 +371,7 @@ RelocTargets reloc_targets_store(hnet_sessions* s) {
 // fs: null, or the fine stage of an oriented call: after the gather the picked candidate and the current frame lie in the staging pair; their level-2
 // thumbnails, the fine search on the pick's search record and the fine winner, which writes the fine part into fs->fw->out and the final start over w.x0.
 // tg: the state table and the map it reads and writes, the staging pair of its gather and alignment, and the key images the attach writes (null: the
-// attach is the caller's, behind rw.mslot and rw.attach).
+// attach is the later commit's, behind rw.mslot and rw.attach).
 int enqueue_relocalise(hnet_sessions* s, const RelocTargets& tg, const RelocScratch& rw, const int32_t* d_ids, const int32_t* d_slot, int n, const int32_t* active,
                        const SearchHyp* d_hyps, int n_hyp, const RelocOpts& o, const FineStage* fs = nullptr) {
     hnet_ctx* c = s->ctx;
@@ -411,8 +410,63 @@ int enqueue_relocalise(hnet_sessions* s, const RelocTargets& tg, const RelocScra
         HIPCHK(c, launch_reloc_decide(d_ids, n, N, w.rec, w.x0, rw.cand, o, state, map, reinterpret_cast<OrientedRelocRec*>(rw.out), rw.attach, st));
     else
         HIPCHK(c, launch_reloc_decide(d_ids, n, N, w.rec, w.x0, rw.cand, o, state, map, reinterpret_cast<RelocRec*>(rw.out), rw.attach, st));
-    if (k->map && tg.attach_key) HIPCHK(c, launch_keyframe_map_attach(d_ids, n, rw.mslot, rw.attach, map, tg.attach_key, st));
+    if (k->map && tg.commit_key) HIPCHK(c, launch_keyframe_map_attach(d_ids, n, rw.mslot, rw.attach, map, tg.commit_key, st));
     return HNET_OK;
+}
+
+// ONE track of the n slots of the device table `tab` on the stream, between a call's upload and its download: start, gather, robust alignment, decide,
+// (commit, map note, map store).  rc: null, or the recovering part - the decision deferred for the lost sessions, then the oriented relocalisation of
+// those on T0's state (the others ride through on absent candidates and quiet-NaN starts), T0 | RECOVERED or T1 (launch_recover_finish, the call's
+// records in RelocScratch::rout) and T1's commit, note and store for the unrecovered sessions (curr still holds every slot's current frame).  The
+// track's and the relocalisation's launches act on disjoint sessions after the first commit.  A track without rc touches no RelocScratch.
+// tg: as enqueue_relocalise's.  With tg.commit_key null no image is written: the first commit wrote no image a lost session's search reads, so the
+// search reads the images it would have read.
+int enqueue_track(hnet_sessions* s, const RelocTargets& tg, const KeyTable& tab, int n, const KeyOpts& o, const KeyRecovery* rc) {
+    hnet_ctx* c = s->ctx;
+    hnet_keyframes* k = s->kf;
+    const int B = c->cfg.max_batch, N = s->n;
+    const KeyScratch w(k->scratch, B);
+    const RelocScratch rw(rc ? k->reloc->scratch : nullptr, B);
+    const MapScratch mw(k->map ? k->map->scratch : nullptr, B);
+    const bool notes = k->map && tg.map.entry;
+    const size_t pyr = (size_t)B * PYR_BYTES;
+    hipStream_t st = c->stream;
+    HIPCHK(c, launch_keyframe_start(tab, n, N, k->state, w.x0, st));
+    HIPCHK(c, launch_keyframe_gather(tab, n, N, k->key, s->ring, 2 * N, tg.prev, tg.curr, st));
+    HIPCHK(c, launch_photo_align_robust(tg.prev, tg.curr, n, w.x0, o.align, o.levels, c->pyr_scratch, c->pyr_scratch + pyr, w.start, w.part, w.work, w.rec, st));
+    if (rc)
+        HIPCHK(c, launch_recover_decide(tab, n, N, w.rec, o.levels, w.x0, o, rc->recover_on, tg.state, w.out, w.copy, rw.stash, rw.active, rc->accepted, st));
+    else
+        HIPCHK(c, launch_keyframe_decide(tab, n, N, w.rec, w.x0, o, tg.state, w.out, w.copy, st));
+    if (tg.commit_key) HIPCHK(c, launch_keyframe_commit(tab, n, N, w.copy, tg.curr, tg.commit_key, st));
+    if (notes) {                               // with a map: the bookkeeping of the new keyframes, and their images into their slots
+        HIPCHK(c, launch_keyframe_map_note(tab.ids, n, w.out, w.copy, tg.state, tg.map, mw.store, st));
+        if (tg.commit_key) HIPCHK(c, launch_keyframe_map_store(tab.ids, n, mw.store, tg.curr, tg.map, st));
+    }
+    if (!rc) return HNET_OK;
+    if (const int r = enqueue_relocalise(s, tg, rw, tab.ids, tab.slot, n, rw.active, rc->d_hyps, rc->n_hyp, rc->o); r != HNET_OK) return r;
+    HIPCHK(c, launch_recover_finish(tab.ids, n, N, rw.active, rw.stash, reinterpret_cast<const OrientedRelocRec*>(rw.out), tg.state, w.out, rw.copy2, rw.redo, rw.rout, st));
+    if (tg.commit_key) HIPCHK(c, launch_keyframe_commit(tab, n, N, rw.copy2, tg.curr, tg.commit_key, st));
+    if (notes) {
+        HIPCHK(c, launch_recover_note(tab.ids, n, w.out, rw.copy2, rw.redo, tg.state, tg.map, rw.store2, st));
+        if (tg.commit_key) HIPCHK(c, launch_keyframe_map_store(tab.ids, n, rw.store2, tg.curr, tg.map, st));
+    }
+    return HNET_OK;
+}
+
+// hyps null with n_hyp 0: the identity entry alone, made in `identity`
+void default_table(const hnet_photo_search_hyp*& hyps, int& n_hyp, SearchHyp& identity) {
+    if (hyps || n_hyp != 0) return;
+    hnet_search_oriented::make_hyp(0.0, 1.0, identity);
+    hyps = reinterpret_cast<const hnet_photo_search_hyp*>(&identity);
+    n_hyp = 1;
+}
+
+// the host table {step | ids | curr slot | gap} of a sessions call's track in a pinned block (step_px null: zero steps)
+void table_fill(const hnet_sessions* s, int n, const int32_t* ids, const float* step_px, uint8_t* pin) {
+    float* h_step = reinterpret_cast<float*>(pin);
+    for (int i = 0; i < 8 * n; i++) h_step[i] = step_px ? step_px[i] : 0.0f;
+    keyframes_table(s, n, ids, nullptr, reinterpret_cast<int32_t*>(h_step + (size_t)8 * n));
 }
 
 // the end of a call whose launches began at ev[0]: the closing event, ONE download of its records, one synchronisation, the device time between the events
@@ -532,45 +586,62 @@ int keyframes_drop(hnet_sessions* s, int id) {
 
 bool keyframes_enabled(const hnet_sessions* s) { return s->kf != nullptr; }
 
-void keyframes_instep_table(const hnet_sessions* s, int n, const int32_t* ids, const uint8_t* on, int32_t* tab) {
+void keyframes_table(const hnet_sessions* s, int n, const int32_t* ids, const uint8_t* on, int32_t* tab) {
     const hnet_keyframes* k = s->kf;
     for (int i = 0; i < n; i++) {
         const int id = ids[i];
-        tab[i] = on[id] ? id : -1;
+        tab[i] = !on || on[id] ? id : -1;
         tab[n + i] = 2 * id + s->st[id].curr;
         tab[2 * n + i] = k->has_key[id] && s->st[id].count != k->count_at_track[id] + 1 ? 1 : 0;
     }
 }
 
-// (the launches of hnet_sessions_keyframe_track between its upload and its commit, in its order; the store's events and ms stay the last track's)
-int keyframes_instep_track(hnet_sessions* s, const KeyTable& tab, int n, const KeyOpts& o, uint8_t* prev, uint8_t* curr, KeyState* state_work, KeyInstep* v,
-                           hipStream_t st) {
+// (the store's events and ms stay the last sessions call's.  A plain track has no working copy of the map: its note waits for the commit; one with
+// recovery notes on the working copies, which the relocalisation reads, and every attempt starts from the committed tables)
+int keyframes_instep_track(hnet_sessions* s, const KeyTable& tab, int n, const KeyOpts& o, const KeyRecovery* rc, uint8_t* prev, uint8_t* curr, KeyState* state_work,
+                           KeyInstep* v) {
     hnet_ctx* c = s->ctx;
     hnet_keyframes* k = s->kf;
     const int B = c->cfg.max_batch, N = s->n;
-    const KeyScratch w(k->scratch, B);
-    const size_t pyr = (size_t)B * PYR_BYTES;
+    hipStream_t st = c->stream;
+    MapStore map = {nullptr, nullptr, nullptr, N, 0};
     HIPCHK(c, hipMemcpyAsync(state_work, k->state, (size_t)N * sizeof(KeyState), hipMemcpyDeviceToDevice, st));
-    HIPCHK(c, launch_keyframe_start(tab, n, N, k->state, w.x0, st));
-    HIPCHK(c, launch_keyframe_gather(tab, n, N, k->key, s->ring, 2 * N, prev, curr, st));
-    HIPCHK(c, launch_photo_align_robust(prev, curr, n, w.x0, o.align, o.levels, c->pyr_scratch, c->pyr_scratch + pyr, w.start, w.part, w.work, w.rec, st));
-    HIPCHK(c, launch_keyframe_decide(tab, n, N, w.rec, w.x0, o, state_work, w.out, w.copy, st));
-    *v = KeyInstep{w.rec, w.out, k->state};
+    if (const KeyMap* m = rc ? k->map : nullptr) {     // the store's images (read only before the accepted attempt) around the working entries and states
+        map = MapStore{m->dev.img, k->instep->entry, k->instep->state, m->dev.n_sessions, m->dev.capacity};
+        HIPCHK(c, hipMemcpyAsync(map.entry, m->dev.entry, (size_t)N * map.capacity * sizeof(MapEntry), hipMemcpyDeviceToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(map.state, m->dev.state, (size_t)N * sizeof(MapState), hipMemcpyDeviceToDevice, st));
+    }
+    if (const int r = enqueue_track(s, RelocTargets{state_work, map, prev, curr, nullptr}, tab, n, o, rc); r != HNET_OK) return r;
+    const KeyScratch w(k->scratch, B);
+    if (rc) *v = KeyInstep{w.rec, rc->o.levels, nullptr, RelocScratch(k->reloc->scratch, B).rout, k->state};
+    else *v = KeyInstep{w.rec, o.levels, w.out, nullptr, k->state};
     return HNET_OK;
 }
 
-int keyframes_instep_commit(hnet_sessions* s, const KeyTable& tab, int n, const uint8_t* curr, const KeyState* state_work, hipStream_t st) {
+int keyframes_instep_commit(hnet_sessions* s, const KeyTable& tab, int n, bool recovering, const uint8_t* curr, const KeyState* state_work) {
     hnet_ctx* c = s->ctx;
     hnet_keyframes* k = s->kf;
     const int B = c->cfg.max_batch, N = s->n;
     const KeyScratch w(k->scratch, B);
+    const RelocScratch rw(recovering ? k->reloc->scratch : nullptr, B);
+    const KeyMap* m = k->map;
+    hipStream_t st = c->stream;
     HIPCHK(c, hipMemcpyAsync(k->state, state_work, (size_t)N * sizeof(KeyState), hipMemcpyDeviceToDevice, st));
     HIPCHK(c, launch_keyframe_commit(tab, n, N, w.copy, curr, k->key, st));
-    if (const KeyMap* m = k->map) {
+    if (m) {
         const MapScratch mw(m->scratch, B);
-        HIPCHK(c, launch_keyframe_map_note(tab.ids, n, w.out, w.copy, k->state, m->dev, mw.store, st));
+        if (recovering) {
+            HIPCHK(c, hipMemcpyAsync(m->dev.entry, k->instep->entry, (size_t)N * m->dev.capacity * sizeof(MapEntry), hipMemcpyDeviceToDevice, st));
+            HIPCHK(c, hipMemcpyAsync(m->dev.state, k->instep->state, (size_t)N * sizeof(MapState), hipMemcpyDeviceToDevice, st));
+        } else {
+            HIPCHK(c, launch_keyframe_map_note(tab.ids, n, w.out, w.copy, k->state, m->dev, mw.store, st));
+        }
         HIPCHK(c, launch_keyframe_map_store(tab.ids, n, mw.store, curr, m->dev, st));
     }
+    if (!recovering) return HNET_OK;
+    if (m) HIPCHK(c, launch_keyframe_map_attach(tab.ids, n, rw.mslot, rw.attach, m->dev, k->key, st));
+    HIPCHK(c, launch_keyframe_commit(tab, n, N, rw.copy2, curr, k->key, st));
+    if (m) HIPCHK(c, launch_keyframe_map_store(tab.ids, n, rw.store2, curr, m->dev, st));
     return HNET_OK;
 }
 
@@ -589,11 +660,7 @@ int keyframes_recover_check(hnet_sessions* s, const hnet_keyframe_relocalise_opt
     int rc = reloc_check_opts(c, opts, who, "reloc", o);
     if (rc != HNET_OK) return rc;
     SearchHyp identity;
-    if (!hyps && n_hyp == 0) {                 // the identity entry alone
-        hnet_search_oriented::make_hyp(0.0, 1.0, identity);
-        hyps = reinterpret_cast<const hnet_photo_search_hyp*>(&identity);
-        n_hyp = 1;
-    }
+    default_table(hyps, n_hyp, identity);
     if ((rc = photo_search_check_table(c, hyps, n_hyp, who)) != HNET_OK) return rc;
     static_assert(sizeof(hnet_photo_search_hyp) == sizeof(SearchHyp), "the table is copied as it is");
     memset(table, 0, (size_t)SEARCH_MAX_HYP * sizeof(SearchHyp));
@@ -618,70 +685,6 @@ int keyframes_instep_recover_ensure(hnet_sessions* s, const char* who) {
         }
     }
     k->instep = w;
-    return HNET_OK;
-}
-
-// the map as an in-step track with recovery sees it: the store's images (read only before the accepted attempt) around the working entries and states
-static MapStore instep_map(const hnet_sessions* s) {
-    const hnet_keyframes* k = s->kf;
-    if (!k->map) return MapStore{nullptr, nullptr, nullptr, s->n, 0};
-    return MapStore{k->map->dev.img, k->instep->entry, k->instep->state, k->map->dev.n_sessions, k->map->dev.capacity};
-}
-
-// (hnet_sessions_keyframe_track_recover's launches between its upload and its download, in its order, without the commits and stores of images and
-// without the attach; every attempt starts from the committed tables, so that a repeated one leaves one map serial and not two)
-int keyframes_instep_track_recover(hnet_sessions* s, const KeyTable& tab, int n, const KeyOpts& o, const RelocOpts& ro, const SearchHyp* d_hyps, int n_hyp,
-                                   const int32_t* recover_on, uint8_t* prev, uint8_t* curr, KeyState* state_work, int32_t* accepted, KeyInstepRecover* v,
-                                   hipStream_t st) {
-    hnet_ctx* c = s->ctx;
-    hnet_keyframes* k = s->kf;
-    const int B = c->cfg.max_batch, N = s->n;
-    const KeyScratch w(k->scratch, B);
-    const RelocScratch rw(k->reloc->scratch, B);
-    const size_t pyr = (size_t)B * PYR_BYTES;
-    const MapStore map = instep_map(s);
-    HIPCHK(c, hipMemcpyAsync(state_work, k->state, (size_t)N * sizeof(KeyState), hipMemcpyDeviceToDevice, st));
-    if (const KeyMap* m = k->map) {
-        HIPCHK(c, hipMemcpyAsync(map.entry, m->dev.entry, (size_t)N * map.capacity * sizeof(MapEntry), hipMemcpyDeviceToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(map.state, m->dev.state, (size_t)N * sizeof(MapState), hipMemcpyDeviceToDevice, st));
-    }
-    // the track up to its decision, which is deferred for the lost sessions that recover
-    HIPCHK(c, launch_keyframe_start(tab, n, N, k->state, w.x0, st));
-    HIPCHK(c, launch_keyframe_gather(tab, n, N, k->key, s->ring, 2 * N, prev, curr, st));
-    HIPCHK(c, launch_photo_align_robust(prev, curr, n, w.x0, o.align, o.levels, c->pyr_scratch, c->pyr_scratch + pyr, w.start, w.part, w.work, w.rec, st));
-    HIPCHK(c, launch_filter_kfmr_decide(tab, n, N, w.rec, o.levels, w.x0, o, recover_on, state_work, w.out, w.copy, rw.stash, rw.active, accepted, st));
-    if (const KeyMap* m = k->map) {
-        const MapScratch mw(m->scratch, B);
-        HIPCHK(c, launch_keyframe_map_note(tab.ids, n, w.out, w.copy, state_work, map, mw.store, st));
-    }
-    // the oriented relocalisation of the lost sessions on T0's state: the first commit wrote no image a lost session's search reads, so with the image
-    // commits deferred the search reads the images it would have read
-    const RelocTargets tg{state_work, map, prev, curr, nullptr};
-    if (const int rc = enqueue_relocalise(s, tg, rw, tab.ids, tab.slot, n, rw.active, d_hyps, n_hyp, ro); rc != HNET_OK) return rc;
-    HIPCHK(c, launch_recover_finish(tab.ids, n, N, rw.active, rw.stash, reinterpret_cast<const OrientedRelocRec*>(rw.out), state_work, w.out, rw.copy2, rw.redo, rw.rout, st));
-    if (k->map) HIPCHK(c, launch_recover_note(tab.ids, n, w.out, rw.copy2, rw.redo, state_work, map, rw.store2, st));
-    *v = KeyInstepRecover{w.rec, rw.rout, k->state};
-    return HNET_OK;
-}
-
-int keyframes_instep_commit_recover(hnet_sessions* s, const KeyTable& tab, int n, const uint8_t* curr, const KeyState* state_work, hipStream_t st) {
-    hnet_ctx* c = s->ctx;
-    hnet_keyframes* k = s->kf;
-    const int B = c->cfg.max_batch, N = s->n;
-    const KeyScratch w(k->scratch, B);
-    const RelocScratch rw(k->reloc->scratch, B);
-    HIPCHK(c, hipMemcpyAsync(k->state, state_work, (size_t)N * sizeof(KeyState), hipMemcpyDeviceToDevice, st));
-    HIPCHK(c, launch_keyframe_commit(tab, n, N, w.copy, curr, k->key, st));
-    if (const KeyMap* m = k->map) {
-        const MapScratch mw(m->scratch, B);
-        const KeyInstepWork* iw = k->instep;
-        HIPCHK(c, hipMemcpyAsync(m->dev.entry, iw->entry, (size_t)N * m->dev.capacity * sizeof(MapEntry), hipMemcpyDeviceToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(m->dev.state, iw->state, (size_t)N * sizeof(MapState), hipMemcpyDeviceToDevice, st));
-        HIPCHK(c, launch_keyframe_map_store(tab.ids, n, mw.store, curr, m->dev, st));
-        HIPCHK(c, launch_keyframe_map_attach(tab.ids, n, rw.mslot, rw.attach, m->dev, k->key, st));
-    }
-    HIPCHK(c, launch_keyframe_commit(tab, n, N, rw.copy2, curr, k->key, st));
-    if (const KeyMap* m = k->map) HIPCHK(c, launch_keyframe_map_store(tab.ids, n, rw.store2, curr, m->dev, st));
     return HNET_OK;
 }
 
@@ -742,33 +745,11 @@ int hnet_sessions_keyframe_track(hnet_sessions* s, int n, const int32_t* ids, co
     if ((rc = sessions_check_ids(s, n, ids)) != HNET_OK) return rc;
     if ((rc = check_listed(s, n, ids, who, false)) != HNET_OK) return rc;
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    const int B = c->cfg.max_batch, N = s->n;
-    const KeyScratch w(k->scratch, B);
-    float* h_step = reinterpret_cast<float*>(k->pin_in);
-    int32_t* h_ids = reinterpret_cast<int32_t*>(h_step + (size_t)8 * n);
-    for (int i = 0; i < n; i++) {
-        const int id = ids[i];
-        for (int j = 0; j < 8; j++) h_step[8 * i + j] = step_px ? step_px[8 * i + j] : 0.0f;
-        h_ids[i] = id;
-        h_ids[n + i] = 2 * id + s->st[id].curr;
-        h_ids[2 * n + i] = k->has_key[id] && s->st[id].count != k->count_at_track[id] + 1 ? 1 : 0;
-    }
-    const KeyTable tab = table_view(w.tab, n);
-    const size_t pyr = (size_t)B * PYR_BYTES;
-    uint8_t *prev = (uint8_t*)c->stage_prev, *curr = (uint8_t*)c->stage_curr;
-    hipStream_t st = c->stream;
-    HIPCHK(c, hipMemcpyAsync(w.tab, k->pin_in, table_bytes(n), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipEventRecord(k->ev[0], st));
-    HIPCHK(c, launch_keyframe_start(tab, n, N, k->state, w.x0, st));
-    HIPCHK(c, launch_keyframe_gather(tab, n, N, k->key, s->ring, 2 * N, prev, curr, st));
-    HIPCHK(c, launch_photo_align_robust(prev, curr, n, w.x0, o.align, o.levels, c->pyr_scratch, c->pyr_scratch + pyr, w.start, w.part, w.work, w.rec, st));
-    HIPCHK(c, launch_keyframe_decide(tab, n, N, w.rec, w.x0, o, k->state, w.out, w.copy, st));
-    HIPCHK(c, launch_keyframe_commit(tab, n, N, w.copy, curr, k->key, st));
-    if (const KeyMap* m = k->map) {            // with a map: the bookkeeping of the new keyframes, and their images into their slots
-        const MapScratch mw(m->scratch, B);
-        HIPCHK(c, launch_keyframe_map_note(tab.ids, n, w.out, w.copy, k->state, m->dev, mw.store, st));
-        HIPCHK(c, launch_keyframe_map_store(tab.ids, n, mw.store, curr, m->dev, st));
-    }
+    const KeyScratch w(k->scratch, c->cfg.max_batch);
+    table_fill(s, n, ids, step_px, k->pin_in);
+    HIPCHK(c, hipMemcpyAsync(w.tab, k->pin_in, table_bytes(n), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipEventRecord(k->ev[0], c->stream));
+    if ((rc = enqueue_track(s, reloc_targets_store(s), table_view(w.tab, n), n, o, nullptr)) != HNET_OK) return rc;
     if ((rc = finish_call(c, k, k->ev, w.out, k->pin_out, out, (size_t)n * sizeof(KeyTrack))) != HNET_OK) return rc;
     for (int i = 0; i < n; i++) {
         k->has_key[ids[i]] = 1;
@@ -963,60 +944,22 @@ int hnet_sessions_keyframe_track_recover(hnet_sessions* s, int n, const int32_t*
                     std::string(who) + ": opts.track: 1 <= levels <= 4, auto_rekey 0 / 1, max_age >= 0, 0 <= rekey_overlap <= 1, max_mse >= 0 and finite");
     if ((rc = reloc_check_opts(c, &opts->reloc, who, "opts.reloc", o.reloc)) != HNET_OK) return rc;
     SearchHyp identity;
-    if (!hyps && n_hyp == 0) {                 // the identity entry alone
-        hnet_search_oriented::make_hyp(0.0, 1.0, identity);
-        hyps = reinterpret_cast<const hnet_photo_search_hyp*>(&identity);
-        n_hyp = 1;
-    }
+    default_table(hyps, n_hyp, identity);
     if ((rc = photo_search_check_table(c, hyps, n_hyp, who)) != HNET_OK) return rc;
     if ((rc = sessions_check_ids(s, n, ids)) != HNET_OK) return rc;
     if ((rc = check_listed(s, n, ids, who, false)) != HNET_OK) return rc;
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    const int B = c->cfg.max_batch, N = s->n;
     if ((rc = reloc_ensure(c, k, who)) != HNET_OK) return rc;
     KeyReloc* r = k->reloc;
-    const KeyScratch w(k->scratch, B);
-    const RelocScratch rw(r->scratch, B);
-    float* h_step = reinterpret_cast<float*>(r->pin_in);
-    int32_t* h_ids = reinterpret_cast<int32_t*>(h_step + (size_t)8 * n);
-    for (int i = 0; i < n; i++) {
-        const int id = ids[i];
-        for (int j = 0; j < 8; j++) h_step[8 * i + j] = step_px ? step_px[8 * i + j] : 0.0f;
-        h_ids[i] = id;
-        h_ids[n + i] = 2 * id + s->st[id].curr;
-        h_ids[2 * n + i] = k->has_key[id] && s->st[id].count != k->count_at_track[id] + 1 ? 1 : 0;
-    }
+    const RelocScratch rw(r->scratch, c->cfg.max_batch);
+    table_fill(s, n, ids, step_px, r->pin_in);
     const size_t head = recover_ids_bytes(n), tabb = (size_t)n_hyp * sizeof(SearchHyp);
     memset(r->pin_in + table_bytes(n), 0, head - table_bytes(n));
     memcpy(r->pin_in + head, hyps, tabb);
-    const KeyTable tab = table_view(rw.tab, n);
-    const int32_t* d_ids = tab.ids;
-    const SearchHyp* d_hyps = reinterpret_cast<const SearchHyp*>(rw.tab + head);
-    const size_t pyr = (size_t)B * PYR_BYTES;
-    uint8_t *prev = (uint8_t*)c->stage_prev, *curr = (uint8_t*)c->stage_curr;
-    hipStream_t st = c->stream;
-    HIPCHK(c, hipMemcpyAsync(rw.tab, r->pin_in, head + tabb, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipEventRecord(k->ev[0], st));
-    // the track up to its decision, which is deferred for the lost sessions
-    HIPCHK(c, launch_keyframe_start(tab, n, N, k->state, w.x0, st));
-    HIPCHK(c, launch_keyframe_gather(tab, n, N, k->key, s->ring, 2 * N, prev, curr, st));
-    HIPCHK(c, launch_photo_align_robust(prev, curr, n, w.x0, o.track.align, o.track.levels, c->pyr_scratch, c->pyr_scratch + pyr, w.start, w.part, w.work, w.rec, st));
-    HIPCHK(c, launch_recover_decide(tab, n, N, w.rec, w.x0, o.track, k->state, w.out, w.copy, rw.stash, rw.active, st));
-    HIPCHK(c, launch_keyframe_commit(tab, n, N, w.copy, curr, k->key, st));
-    if (const KeyMap* m = k->map) {
-        const MapScratch mw(m->scratch, B);
-        HIPCHK(c, launch_keyframe_map_note(d_ids, n, w.out, w.copy, k->state, m->dev, mw.store, st));
-        HIPCHK(c, launch_keyframe_map_store(d_ids, n, mw.store, curr, m->dev, st));
-    }
-    // the oriented relocalisation of the lost sessions on T0's state; the others ride through on absent candidates and quiet-NaN starts
-    if ((rc = enqueue_relocalise(s, reloc_targets_store(s), rw, d_ids, tab.slot, n, rw.active, d_hyps, n_hyp, o.reloc)) != HNET_OK) return rc;
-    // T0 | RECOVERED or T1, and T1's commit for the unrecovered sessions (curr still holds every slot's current frame)
-    HIPCHK(c, launch_recover_finish(d_ids, n, N, rw.active, rw.stash, reinterpret_cast<const OrientedRelocRec*>(rw.out), k->state, w.out, rw.copy2, rw.redo, rw.rout, st));
-    HIPCHK(c, launch_keyframe_commit(tab, n, N, rw.copy2, curr, k->key, st));
-    if (const KeyMap* m = k->map) {
-        HIPCHK(c, launch_recover_note(d_ids, n, w.out, rw.copy2, rw.redo, k->state, m->dev, rw.store2, st));
-        HIPCHK(c, launch_keyframe_map_store(d_ids, n, rw.store2, curr, m->dev, st));
-    }
+    const KeyRecovery rec{o.reloc, reinterpret_cast<const SearchHyp*>(rw.tab + head), n_hyp, nullptr, nullptr};
+    HIPCHK(c, hipMemcpyAsync(rw.tab, r->pin_in, head + tabb, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipEventRecord(k->ev[0], c->stream));
+    if ((rc = enqueue_track(s, reloc_targets_store(s), table_view(rw.tab, n), n, o.track, &rec)) != HNET_OK) return rc;
     if ((rc = finish_call(c, k, k->ev, rw.rout, r->pin_out, out, (size_t)n * sizeof(RecoverRec))) != HNET_OK) return rc;
     for (int i = 0; i < n; i++) {
         k->has_key[ids[i]] = 1;

@@ -1,22 +1,29 @@
 // kernels_filters_keyframe.hip — the device glue of the keyframe track as an in-step measurement of hnet_filters (include/hnet.h
-// hnet_filters_set_keyframe_measure) between the network's last update, the unchanged launches of the keyframe track and the filter's own
-// innovation and update kernels: the filter's step as the track's step, the track's record as the packed 72-float measurement those kernels take, and
-// what became of it.  One wavefront per slot; fp64, serial on lane 0 where the rule is serial, and like kernels_filters_refine.hip built with
-// -ffp-contract=off: the measurement is include/hnet_keyframe_measure.h's, element (t >> 3, t & 7) of the matrices on lane t, and the inverse is
+// hnet_filters_set_keyframe_measure and hnet_filters_set_keyframe_recover) between the network's last update, the unchanged launches of
+// the keyframe track, with or without the recovery of a lost camera inside it, and the filter's own innovation and update kernels: the filter's step as
+// the track's step, the track's record as the packed 72-float measurement those kernels take, with the source of the measurement picked per slot, and
+// what became of it, with the relocalise records assembled behind the measure records.  ONE measure and ONE finish kernel serve the plain and the
+// recovering track: the rule is include/hnet_keyframe_measure_recover.h's, which on a record without RECOVERED is include/hnet_keyframe_measure.h's bit
+// for bit.  One wavefront per slot; fp64, serial on lane 0 where the rule is serial, and like kernels_filters_refine.hip built with -ffp-contract=off:
+// element (t >> 3, t & 7) of the matrices on lane t, in the collective body shared with the fallback (filters_measure_dev.h), and the inverse is
 // invert8_lanes.  No atomics, no scratch memory, nothing waits on another workgroup; ids and slots are bounds-checked here.  The host side that enqueues
 // these kernels is capi_filters.hip.
 #include "filters_keyframe_dev.h"
-#include "filters_invert_dev.h"
+#include "filters_measure_dev.h"
 
 namespace hnet {
 
 namespace rf = hnet_refine;
 namespace kfm = hnet_kfm;
+namespace kfmr = hnet_kfmr;
+namespace kr = hnet_keyframe_recovery;
 
 static_assert(offsetof(KfmRec, flags) == (KFM_REC_DOUBLES - 1) * sizeof(double) && sizeof(KeyTrack) % sizeof(double) == 0 && offsetof(KfmRec, track) == 0,
               "KfmRec: the track first, doubles throughout, then flags | pad");
 static_assert(offsetof(KfmRec, s_diag) == offsetof(KfmRec, r) + 8 * sizeof(double) && offsetof(KfmRec, nis) == offsetof(KfmRec, r) + 16 * sizeof(double),
               "KfmRec: r, s_diag, nis as in InnovRec");
+static_assert(offsetof(RecoverRec, track) == 0 && offsetof(RecoverRec, reloc) == sizeof(KeyTrack) && sizeof(OrientedRelocRec) == (size_t)kr::RELOC_WORDS * 4,
+              "RecoverRec: the track, then the relocalise record as 32-bit words");
 
 __global__ __launch_bounds__(KFM_THREADS) void filter_kfm_step_kernel(const int32_t* __restrict__ ids, int n, int n_sessions, const KfmCfg* __restrict__ cfg,
                                                                       const FilterRec* __restrict__ work, float* __restrict__ step, KfmRec* __restrict__ out) {
@@ -35,15 +42,17 @@ __global__ __launch_bounds__(KFM_THREADS) void filter_kfm_step_kernel(const int3
     }
 }
 
+// (track, reloc: slot b's records lie b * stride bytes behind them)
 __global__ __launch_bounds__(KFM_THREADS) void filter_kfm_measure_kernel(const int32_t* __restrict__ ids, int n, int n_sessions, const FilterParams* __restrict__ params,
                                                                          const KfmCfg* __restrict__ cfg, const KeyState* __restrict__ key_state,
-                                                                         const int32_t* __restrict__ prev_ok, const KeyTrack* __restrict__ track,
+                                                                         const int32_t* __restrict__ prev_ok, const uint8_t* __restrict__ track,
+                                                                         const uint8_t* __restrict__ reloc, int stride, const int32_t* __restrict__ accepted,
                                                                          const RobustRec* __restrict__ rec, int levels, const int32_t* __restrict__ updates,
                                                                          float* __restrict__ m72, int32_t* __restrict__ gate, int32_t* __restrict__ opened, KfmRec* out) {
     __shared__ double M[64], V[64], L[64];
     __shared__ rf::Bright f;
-    __shared__ float z[8];
     __shared__ int why, bad;
+    __shared__ float z[8];
     const int b = blockIdx.x, t = threadIdx.x;
     if (b >= n) return;
     const int id = ids[b];
@@ -51,8 +60,10 @@ __global__ __launch_bounds__(KFM_THREADS) void filter_kfm_measure_kernel(const i
         if (t == 0) { gate[b] = 0; opened[b] = -1; }
         return;
     }
-    const KeyTrack& tr = track[b];
-    const RobustRec& r0 = tr.rec;
+    const KeyTrack& tr = *reinterpret_cast<const KeyTrack*>(track + (size_t)b * stride);
+    const OrientedRelocRec* rl = reloc ? reinterpret_cast<const OrientedRelocRec*>(reloc + (size_t)b * stride) : nullptr;
+    const bool from = rl && kfmr::from_reloc(tr.flags);                          // (read only where no reason was found: then RL_RETRACKED)
+    const RobustRec& r0 = from ? rl->rv.rec : tr.rec;
     const double kc = params[id].k_net_cov;
     const KfmCfg cf = cfg[id];
     const int upd = updates[b];
@@ -60,39 +71,19 @@ __global__ __launch_bounds__(KFM_THREADS) void filter_kfm_measure_kernel(const i
     const double* src = reinterpret_cast<const double*>(&tr);
     double* dst = reinterpret_cast<double*>(&out[b].track);
     for (int i = t; i < (int)(sizeof(KeyTrack) / sizeof(double)); i += KFM_THREADS) dst[i] = src[i];
+    int pre = 0, acc = 0;
     if (t == 0) {
         const KeyState& ks = key_state[id];
-        int w = kfm::usable(ks.has_key != 0, tr.flags, prev_ok[id]);
-        if (!w && !kfm::relative_z(ks.key_px, r0.px.offsets_px, z)) w = kfm::NO_INVERSE;
-        if (!w) {
-            int accepted = 0;
-            for (int l = 0; l < levels; l++) accepted += rec[(size_t)l * n + b].px.accepted;
-            w = rf::precheck(r0, accepted, cf.max_mse, kc);
+        pre = kfmr::usable_recover(ks.has_key != 0, tr.flags, rl ? rl->rv.flags : 0, prev_ok[id]);
+        if (!pre && !kfm::relative_z(ks.key_px, r0.px.offsets_px, z)) pre = kfm::NO_INVERSE;
+        if (!pre) {
+            if (accepted && !from) acc = accepted[b];                            // (the relocalisation's alignment has reused rec: the track's count was kept)
+            else
+                for (int l = 0; l < levels; l++) acc += rec[(size_t)l * n + b].px.accepted;
         }
-        if (!w && !rf::marginal_factor(r0, f)) w = rf::NO_FACTOR;
-        why = w;
-        bad = 0;
     }
-    __syncthreads();
-    const int i = t >> 3, j = t & 7;
-    if (!why) {
-        M[t] = rf::marginal_info(r0, f, i, j);
-        V[t] = i == j ? 1.0 : 0.0;
-    }
-    __syncthreads();
-    if (!why && t == 0 && !rf::has_factor(M, L)) why = rf::NO_FACTOR;
-    __syncthreads();
-    const bool singular = !why && invert8_lanes(M, V);                           // (V = inverse(info8); every lane read `why` behind the barrier above)
-    __syncthreads();
-    if (singular && t == 0) why = rf::NO_FACTOR;
-    __syncthreads();
-    double R = 0.0;
-    if (!why) {
-        R = rf::r_px_entry(V, r0.px.mse, cf.cov_scale, cf.sigma_floor_px, i, j);
-        if (!std::isfinite(R)) bad = 1;
-    }
-    __syncthreads();
-    const int reason = why ? why : bad ? (int)rf::NON_FINITE : 0;
+    double R;
+    const int reason = refine_measure_lanes(r0, acc, pre, cf.max_mse, cf.cov_scale, cf.sigma_floor_px, kc, M, V, L, f, why, bad, R);
     const int skipped = sel ? 0 : (int)kfm::NOT_SELECTED;
     if (reason) {
         if (t == 0) { out[b].flags = kfm::ASKED | reason | skipped; gate[b] = 0; opened[b] = -1; }
@@ -105,7 +96,7 @@ __global__ __launch_bounds__(KFM_THREADS) void filter_kfm_measure_kernel(const i
         out[b].z_px[t] = z[t];
     }
     if (t == 0) {
-        out[b].flags = kfm::ASKED | skipped;
+        out[b].flags = kfm::ASKED | skipped | (from ? (int)kfmr::FROM_RELOC : 0);
         gate[b] = sel ? 1 : 0;
         opened[b] = sel ? upd : -1;
     }
@@ -113,9 +104,15 @@ __global__ __launch_bounds__(KFM_THREADS) void filter_kfm_measure_kernel(const i
 
 __global__ __launch_bounds__(KFM_THREADS) void filter_kfm_finish_kernel(const int32_t* __restrict__ ids, int n, int n_sessions, const InnovRec* __restrict__ innov,
                                                                         const int32_t* __restrict__ updates, const int32_t* __restrict__ opened, int iters,
-                                                                        int32_t* __restrict__ prev_ok_next, KfmRec* out) {
+                                                                        const RecoverRec* __restrict__ rout, int32_t* __restrict__ prev_ok_next, KfmRec* out,
+                                                                        OrientedRelocRec* __restrict__ reloc_out) {
     const int b = blockIdx.x, t = threadIdx.x;
     if (b >= n) return;
+    if (reloc_out) {
+        const uint32_t* rs = reinterpret_cast<const uint32_t*>(&rout[b].reloc);
+        uint32_t* ro = reinterpret_cast<uint32_t*>(reloc_out + b);
+        for (int i = t; i < kr::RELOC_WORDS; i += KFM_THREADS) ro[i] = rs[i];
+    }
     const int id = ids[b];
     if (id < 0 || id >= n_sessions || !(out[b].flags & kfm::ASKED)) return;
     const int before = opened[b];
@@ -131,7 +128,7 @@ __global__ __launch_bounds__(KFM_THREADS) void filter_kfm_finish_kernel(const in
             else if (updates[b] > before) fl |= kfm::APPLIED;
         }
         out[b].flags = fl;
-        prev_ok_next[id] = kfm::next_prev_ok(out[b].track.flags);
+        prev_ok_next[id] = kfmr::next_prev_ok_recover(out[b].track.flags);
     }
 }
 
@@ -142,18 +139,21 @@ hipError_t launch_filter_kfm_step(const int32_t* ids, int n, int n_sessions, con
 }
 
 hipError_t launch_filter_kfm_measure(const int32_t* ids, int n, int n_sessions, const FilterParams* params, const KfmCfg* cfg, const KeyState* key_state,
-                                     const int32_t* prev_ok, const KeyTrack* track, const RobustRec* rec, int levels, const int32_t* updates, float* m72,
-                                     int32_t* gate, int32_t* opened, KfmRec* out, hipStream_t s) {
-    if (n < 1 || levels < 1 || levels > hnet_align::MAX_LEVELS) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(filter_kfm_measure_kernel, dim3((unsigned)n), dim3(KFM_THREADS), 0, s, ids, n, n_sessions, params, cfg, key_state, prev_ok, track, rec, levels,
-                       updates, m72, gate, opened, out);
+                                     const int32_t* prev_ok, const KeyTrack* track, const RecoverRec* rout, const int32_t* accepted, const RobustRec* rec, int levels,
+                                     const int32_t* updates, float* m72, int32_t* gate, int32_t* opened, KfmRec* out, hipStream_t s) {
+    if (n < 1 || levels < 1 || levels > hnet_align::MAX_LEVELS || !track == !rout || (rout && !accepted)) return hipErrorInvalidValue;
+    const uint8_t* tr = reinterpret_cast<const uint8_t*>(rout ? &rout->track : track);
+    const uint8_t* rl = rout ? reinterpret_cast<const uint8_t*>(&rout->reloc) : nullptr;
+    hipLaunchKernelGGL(filter_kfm_measure_kernel, dim3((unsigned)n), dim3(KFM_THREADS), 0, s, ids, n, n_sessions, params, cfg, key_state, prev_ok, tr, rl,
+                       (int)(rout ? sizeof(RecoverRec) : sizeof(KeyTrack)), accepted, rec, levels, updates, m72, gate, opened, out);
     return hipGetLastError();
 }
 
 hipError_t launch_filter_kfm_finish(const int32_t* ids, int n, int n_sessions, const InnovRec* innov, const int32_t* updates, const int32_t* opened, int iters,
-                                    int32_t* prev_ok_next, KfmRec* out, hipStream_t s) {
-    if (n < 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(filter_kfm_finish_kernel, dim3((unsigned)n), dim3(KFM_THREADS), 0, s, ids, n, n_sessions, innov, updates, opened, iters, prev_ok_next, out);
+                                    const RecoverRec* rout, int32_t* prev_ok_next, KfmRec* out, OrientedRelocRec* reloc_out, hipStream_t s) {
+    if (n < 1 || !rout != !reloc_out) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(filter_kfm_finish_kernel, dim3((unsigned)n), dim3(KFM_THREADS), 0, s, ids, n, n_sessions, innov, updates, opened, iters, rout, prev_ok_next, out,
+                       reloc_out);
     return hipGetLastError();
 }
 

@@ -1,10 +1,10 @@
 // kernels_filters_refine.hip — the device glue of the photometric fallback of hnet_filters (include/hnet.h hnet_filters_set_photo_refine)
 // between photo_gate_kernel's verdicts, launch_photo_align_robust and the filter's own innovation and update kernels: which slots of a step align, the
 // alignment's record as the packed 72-float measurement those kernels take, and what became of it.  One wavefront per slot; fp64 and, like
-// kernels_filters.hip, built with -ffp-contract=off: the measurement is include/hnet_photo_refine.h's, element (t >> 3, t & 7) on lane t, and the
-// inverse is invert8_lanes.  No atomics, nothing waits on another workgroup.  The host side that enqueues these kernels is capi_filters.hip.
-#include "filters_refine_dev.h"
-#include "filters_invert_dev.h"
+// kernels_filters.hip, built with -ffp-contract=off: the measurement is include/hnet_photo_refine.h's, element (t >> 3, t & 7) on lane t, in the
+// collective body it shares with the keyframe measurement (filters_measure_dev.h), and the inverse is invert8_lanes.  No atomics, nothing waits on
+// another workgroup.  The host side that enqueues these kernels is capi_filters.hip.
+#include "filters_measure_dev.h"
 
 namespace hnet {
 
@@ -44,34 +44,11 @@ __global__ __launch_bounds__(REFINE_THREADS) void filter_refine_measure_kernel(c
     const double* src = reinterpret_cast<const double*>(&r0);
     double* dst = reinterpret_cast<double*>(&out[b].rec);
     for (int i = t; i < (int)(sizeof(RobustRec) / sizeof(double)); i += REFINE_THREADS) dst[i] = src[i];
-    if (t == 0) {
-        int accepted = 0;
+    int accepted = 0;
+    if (t == 0)
         for (int l = 0; l < levels; l++) accepted += rec[(size_t)l * n + b].px.accepted;
-        int w = rf::precheck(r0, accepted, cf.max_mse, kc);
-        if (!w && !rf::marginal_factor(r0, f)) w = rf::NO_FACTOR;
-        why = w;
-        bad = 0;
-    }
-    __syncthreads();
-    const int i = t >> 3, j = t & 7;
-    if (!why) {
-        M[t] = rf::marginal_info(r0, f, i, j);
-        V[t] = i == j ? 1.0 : 0.0;
-    }
-    __syncthreads();
-    if (!why && t == 0 && !rf::has_factor(M, L)) why = rf::NO_FACTOR;
-    __syncthreads();
-    const bool singular = !why && invert8_lanes(M, V);                           // (V = inverse(info8); every lane read `why` behind the barrier above)
-    __syncthreads();
-    if (singular && t == 0) why = rf::NO_FACTOR;
-    __syncthreads();
-    double R = 0.0;
-    if (!why) {
-        R = rf::r_px_entry(V, r0.px.mse, cf.cov_scale, cf.sigma_floor_px, i, j);
-        if (!std::isfinite(R)) bad = 1;
-    }
-    __syncthreads();
-    const int reason = why ? why : bad ? (int)rf::NON_FINITE : 0;
+    double R;
+    const int reason = refine_measure_lanes(r0, accepted, 0, cf.max_mse, cf.cov_scale, cf.sigma_floor_px, kc, M, V, L, f, why, bad, R);
     if (reason) {
         if (t == 0) { out[b].flags = rf::ASKED | reason; gate[b] = 0; }
         return;

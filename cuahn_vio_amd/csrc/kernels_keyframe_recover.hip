@@ -1,7 +1,7 @@
 // kernels_keyframe_recover.hip — the device side of recovering a lost camera inside the track (include/hnet.h hnet_sessions_keyframe_track_recover;
 // DESIGN 7u).  Three kernels between the unchanged launches of a track (7p, 7q) and of an oriented relocalisation (7r, 7s), whose thumbnails kernel
 // takes active[] and marks every candidate of a session that is not lost absent: the track's decision in its deferred form (the lost sessions commit T0
-// and keep T1 aside), the finish that selects between "T0 | RECOVERED" and T1 and assembles the call's one output array, and the map's note for the
+// and keep T1 aside; for the track inside a filter step, DESIGN 7y, per session the deferred or the plain form), the finish that selects between "T0 | RECOVERED" and T1 and assembles the call's one output array, and the map's note for the
 // sessions whose T1 was restored.  The per-slot kernels are one wavefront each, fp64 on lane 0, and like kernels_keyframe.hip this file is built with
 // -ffp-contract=off: decide_deferred and finish are the host reference's operations in its order.  No atomics, no LDS, nothing waits on another
 // workgroup, nothing spins; every id, ring slot and map slot is tested against its table.  The host side that enqueues these kernels is capi_keyframe.hip.
@@ -21,10 +21,12 @@ static_assert(sizeof(RobustRec) % sizeof(double) == 0 && offsetof(KeyTrack, rec)
 static_assert(sizeof(KeyTrack) % 4 == 0 && sizeof(OrientedRelocRec) == (size_t)kr::RELOC_WORDS * 4 && offsetof(RecoverRec, track) == 0, "records as 32-bit words");
 }  // namespace
 
-// keyframe_decide_kernel with the deferred decision
-__global__ __launch_bounds__(KEY_THREADS) void recover_decide_kernel(KeyTable tab, int n, int n_sessions, const RobustRec* __restrict__ rec, const float* x0, KeyOpts opts,
-                                                                     KeyState* state, KeyTrack* out, int32_t* __restrict__ copy, RecoverStash* __restrict__ stash,
-                                                                     int32_t* __restrict__ active) {
+// keyframe_decide_kernel with the deferred decision, or per session (recover_on) the plain one; accepted: null, or where the trials the alignment
+// accepted over its levels are kept
+__global__ __launch_bounds__(KEY_THREADS) void recover_decide_kernel(KeyTable tab, int n, int n_sessions, const RobustRec* __restrict__ rec, int levels, const float* x0,
+                                                                     KeyOpts opts, const int32_t* __restrict__ recover_on, KeyState* state, KeyTrack* out,
+                                                                     int32_t* __restrict__ copy, RecoverStash* __restrict__ stash, int32_t* __restrict__ active,
+                                                                     int32_t* __restrict__ accepted) {
     const int b = blockIdx.x, t = threadIdx.x;
     if (b >= n) return;
     const int id = tab.ids[b];
@@ -34,6 +36,11 @@ __global__ __launch_bounds__(KEY_THREADS) void recover_decide_kernel(KeyTable ta
     double* dst = reinterpret_cast<double*>(out + b);
     for (int i = t; i < REC_DOUBLES; i += KEY_THREADS) dst[i] = read ? src[i] : 0.0;
     if (t != 0) return;
+    if (accepted) {
+        int acc = 0;
+        for (int l = 0; l < levels; l++) acc += rec[(size_t)l * n + b].px.accepted;
+        accepted[b] = acc;
+    }
     if (!valid) {
         for (int i = REC_DOUBLES; i < (int)(sizeof(KeyTrack) / sizeof(double)); i++) dst[i] = 0.0;
         kr::stash_zero(stash[b]);
@@ -42,7 +49,12 @@ __global__ __launch_bounds__(KEY_THREADS) void recover_decide_kernel(KeyTable ta
         return;
     }
     int act = 0;
-    copy[b] = kr::decide_deferred(state[id], x0 + (size_t)b * 8, rec[b], opts, tab.gap[b] != 0, state[id], out[b], stash[b], act);
+    if (!recover_on || recover_on[id] != 0) {
+        copy[b] = kr::decide_deferred(state[id], x0 + (size_t)b * 8, rec[b], opts, tab.gap[b] != 0, state[id], out[b], stash[b], act);
+    } else {
+        copy[b] = kf::decide(state[id], x0 + (size_t)b * 8, rec[b], opts, tab.gap[b] != 0, state[id], out[b]);
+        kr::stash_zero(stash[b]);
+    }
     active[b] = act;
 }
 
@@ -84,10 +96,12 @@ __global__ __launch_bounds__(KEY_THREADS) void recover_note_kernel(const int32_t
     store[b] = slot;
 }
 
-hipError_t launch_recover_decide(const KeyTable& tab, int n, int n_sessions, const RobustRec* rec, const float* x0, const KeyOpts& opts, KeyState* state,
-                                 KeyTrack* out, int32_t* copy, RecoverStash* stash, int32_t* active, hipStream_t s) {
-    if (n < 1 || !stash || !active) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(recover_decide_kernel, dim3((unsigned)n), dim3(KEY_THREADS), 0, s, tab, n, n_sessions, rec, x0, opts, state, out, copy, stash, active);
+hipError_t launch_recover_decide(const KeyTable& tab, int n, int n_sessions, const RobustRec* rec, int levels, const float* x0, const KeyOpts& opts,
+                                 const int32_t* recover_on, KeyState* state, KeyTrack* out, int32_t* copy, RecoverStash* stash, int32_t* active, int32_t* accepted,
+                                 hipStream_t s) {
+    if (n < 1 || levels < 1 || levels > hnet_align::MAX_LEVELS || !stash || !active) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(recover_decide_kernel, dim3((unsigned)n), dim3(KEY_THREADS), 0, s, tab, n, n_sessions, rec, levels, x0, opts, recover_on, state, out, copy, stash,
+                       active, accepted);
     return hipGetLastError();
 }
 

@@ -22,11 +22,14 @@ static_assert(sizeof(RecoverOpts) == sizeof(KeyOpts) + sizeof(RelocOpts) && size
               sizeof(RecoverRec) == sizeof(KeyTrack) + sizeof(OrientedRelocRec) && offsetof(RecoverRec, reloc) == sizeof(KeyTrack) &&
               sizeof(RecoverStash) == sizeof(KeyState) + 160 && sizeof(RecoverRec) % 8 == 0, "packed layouts");
 
-// ---- a track with recovery (tab: the track's table; rec: the level-0 records [n] of the track's alignment).  One wavefront per slot b < n, after the
+// ---- a track with recovery (tab: the track's table; rec: the records [levels][n] of the track's alignment).  One wavefront per slot b < n, after the
 // alignment: hnet_keyframe_recovery::decide_deferred on the session's state -> out[b] (every byte written), the new state, copy[b], stash[b] and
-// active[b] (1: the frame is LOST and the relocalisation is to run on it; 0 for an id outside the table)
-hipError_t launch_recover_decide(const KeyTable& tab, int n, int n_sessions, const RobustRec* rec, const float* x0, const KeyOpts& opts, KeyState* state,
-                                 KeyTrack* out, int32_t* copy, RecoverStash* stash, int32_t* active, hipStream_t s);
+// active[b] (1: the frame is LOST and the relocalisation is to run on it; 0 for an id outside the table).  recover_on: null, or [n_sessions] - a session
+// whose word is 0 gets what launch_keyframe_decide leaves in out[b] and copy[b] instead (active 0, the stash zero).  accepted: null, or [n] -
+// accepted[b] = the trials the alignment accepted over its levels (the relocalisation's alignment reuses rec)
+hipError_t launch_recover_decide(const KeyTable& tab, int n, int n_sessions, const RobustRec* rec, int levels, const float* x0, const KeyOpts& opts,
+                                 const int32_t* recover_on, KeyState* state, KeyTrack* out, int32_t* copy, RecoverStash* stash, int32_t* active, int32_t* accepted,
+                                 hipStream_t s);
 // One wavefront per slot, after the relocalisation's decision (reloc [n]: its records): hnet_keyframe_recovery::finish on the active slots (the state and
 // track[b] in place) -> copy2[b] and redo[b] (1: unrecovered, T1 was restored), and out[b] = {track[b] | reloc[b], or the zero record when inactive}
 hipError_t launch_recover_finish(const int32_t* ids, int n, int n_sessions, const int32_t* active, const RecoverStash* stash, const OrientedRelocRec* reloc,

@@ -1,5 +1,5 @@
 """hnet_filters with recovery inside the in-step keyframe track (include/hnet.h hnet_filters_set_keyframe_recover;
-csrc/kernels_filters_keyframe_recover.hip).  A fleet that measures and never heard of it, one that set and cleared it and one where it is on
+csrc/kernels_filters_keyframe.hip).  A fleet that measures and never heard of it, one that set and cleared it and one where it is on
 and nobody is lost must agree byte for byte; per frame of 7u's four rows the in-step track must be hnet_sessions_keyframe_track_recover's with the
 filter's own step on a sessions object that is not run under the filter - records, keyframe, map - the measurement the host header's on the device's
 records, and the flags those of the host rows; a mixed call out of order; a repeated attempt; advance against step; the NIS gate on the jumped frame;
