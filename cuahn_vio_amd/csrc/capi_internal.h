@@ -144,7 +144,7 @@ struct hnet_ctx {
     int n_local = 0, s_begin = 0;
     // timing
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipEvent_t ev_align[2] = {nullptr, nullptr};          // around the launch sequence of the last photometric alignment (photo_align_pyramid_run): events of its own,
+    hipEvent_t ev_align[2] = {nullptr, nullptr};          // around the launch sequence of the last photometric alignment (photo_align_run): events of its own,
     double photo_align_ms = 0.0;                          // so that the read-only calls leave ev0 / ev1 and every hnet_timing as they were
     uint8_t* pyr_scratch = nullptr;                       // levels 1 .. 3 of img1 [max_batch] | img2 [max_batch] of a coarse-to-fine alignment; allocated on first use
     hnet_timing timing = {};
@@ -234,16 +234,16 @@ inline int run_host_call(hnet_ctx* c, const std::function<int(uint32_t& flag)>& 
     hnet_ctx* const ctx[2] = {c, nullptr};
     return run_host_call(ctx, [&](uint32_t* flag) { return enqueue(flag[0]); }, [&] { return overflowed() ? 0 : -1; });
 }
-// photometric alignment of n pairs resident on the device (hnet_capi.hip), single-level (levels = 1) or coarse to fine: d_x0 [n][8] start offsets;
-// the launch sequence on c->stream, ONE download of the records - out [n] the level-0 records, levels_out null or [n][levels] - and one synchronisation.
-// The caller has validated n, levels (1 .. 4) and opts (photo_align_check_opts) and enqueued its upload on c->stream.
+// photometric alignment of n pairs resident on the device (capi_photo_align.hip), single-level (levels = 1) or coarse to fine: d_x0 [n][8] start
+// offsets; the launch sequence on c->stream, ONE download of the records - out [n] the level-0 records, levels_out null or [n][levels] - and one
+// synchronisation.  The caller has validated n, levels (1 .. 4) and opts (photo_align_check_opts) and enqueued its upload on c->stream.
 int photo_align_check_opts(hnet_ctx* c, const hnet_photo_align_opts* opts, const char* who);
-int photo_align_pyramid_run(hnet_ctx* c, const uint8_t* d_img1, const uint8_t* d_img2, int n, const float* d_x0, const hnet_photo_align_opts& opts, int levels,
-                            hnet_photo_align* out, hnet_photo_align* levels_out);
-// the same for the gain / bias + Huber alignment (capi_photo_robust.hip): out [n] and levels_out (null or [n][levels]) are hnet_photo_robust records
+int photo_align_run(hnet_ctx* c, const uint8_t* d_img1, const uint8_t* d_img2, int n, const float* d_x0, const hnet_photo_align_opts& opts, int levels,
+                    hnet_photo_align* out, hnet_photo_align* levels_out);
+// the same for the gain / bias + Huber alignment: out [n] and levels_out (null or [n][levels]) are hnet_photo_robust records
 int photo_robust_check_opts(hnet_ctx* c, const hnet_photo_robust_opts* opts, const char* who);
-int photo_robust_run(hnet_ctx* c, const uint8_t* d_img1, const uint8_t* d_img2, int n, const float* d_x0, const hnet_photo_robust_opts& opts, int levels,
-                     hnet_photo_robust* out, hnet_photo_robust* levels_out);
+int photo_align_run(hnet_ctx* c, const uint8_t* d_img1, const uint8_t* d_img2, int n, const float* d_x0, const hnet_photo_robust_opts& opts, int levels,
+                    hnet_photo_robust* out, hnet_photo_robust* levels_out);
 void build_undistort_maps(const hnet_camera* cam, std::vector<float>& mx, std::vector<float>& my);
 
 }  // namespace capi

@@ -363,13 +363,16 @@ int hnet_sessions_photo_residual(hnet_sessions* s, int n, const int32_t* ids, co
 
 // ---- photometric alignment (include/hnet.h hnet_photo_align) on the sessions' current pairs; read-only like the records above ----
 
-static int sessions_photo_align(hnet_sessions* s, int n, const int32_t* ids, const float* offsets0_px, const hnet_photo_align_opts* opts, int levels,
-                                hnet_photo_align* out, hnet_photo_align* levels_out, const char* who) {
+// the front of the plain and the gain / bias + Huber form: the checks, the upload, the gather of the pairs, then the form's run
+extern "C++" {
+template <class PubOpts, class PubRec>
+static int sessions_photo_align(hnet_sessions* s, int n, const int32_t* ids, const float* offsets0_px, const PubOpts* opts,
+                                int (*check_opts)(hnet_ctx*, const PubOpts*, const char*), int levels, PubRec* out, PubRec* levels_out, const char* who) {
     if (!s) return HNET_ERR_INVALID_ARG;
     hnet_ctx* c = s->ctx;
     if (!offsets0_px || !out) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": offsets / out");
     if (levels < 1 || levels > HNET_ALIGN_MAX_LEVELS) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": 1 <= levels <= 4");
-    int rc = photo_align_check_opts(c, opts, who);
+    int rc = check_opts(c, opts, who);
     if (rc == HNET_OK) rc = sessions_check_ids(s, n, ids);
     if (rc == HNET_OK) rc = sessions_check_pairs(s, n, ids);
     if (rc != HNET_OK) return rc;
@@ -385,45 +388,24 @@ static int sessions_photo_align(hnet_sessions* s, int n, const int32_t* ids, con
     hipStream_t st = c->stream;
     HIPCHK(c, hipMemcpyAsync(d_in, h_in.data(), up, hipMemcpyHostToDevice, st));
     HIPCHK(c, launch_session_gather(s->ring, 2 * s->n, reinterpret_cast<const int32_t*>(d_in + off_bytes), n, (uint8_t*)c->stage_prev, (uint8_t*)c->stage_curr, st));
-    return photo_align_pyramid_run(c, (const uint8_t*)c->stage_prev, (const uint8_t*)c->stage_curr, n, reinterpret_cast<const float*>(d_in), *opts, levels, out,
-                                   levels_out);
+    return photo_align_run(c, (const uint8_t*)c->stage_prev, (const uint8_t*)c->stage_curr, n, reinterpret_cast<const float*>(d_in), *opts, levels, out, levels_out);
 }
+}  // extern "C++"
 
 int hnet_sessions_photo_align(hnet_sessions* s, int n, const int32_t* ids, const float* offsets0_px, const hnet_photo_align_opts* opts, hnet_photo_align* out) {
-    return sessions_photo_align(s, n, ids, offsets0_px, opts, 1, out, nullptr, "hnet_sessions_photo_align");
+    return sessions_photo_align(s, n, ids, offsets0_px, opts, photo_align_check_opts, 1, out, (hnet_photo_align*)nullptr, "hnet_sessions_photo_align");
 }
 
 // the coarse-to-fine form on the sessions' current pairs; read-only in the same way
 int hnet_sessions_photo_align_pyramid(hnet_sessions* s, int n, const int32_t* ids, const float* offsets0_px, const hnet_photo_align_opts* opts, int levels,
                                       hnet_photo_align* out, hnet_photo_align* levels_out) {
-    return sessions_photo_align(s, n, ids, offsets0_px, opts, levels, out, levels_out, "hnet_sessions_photo_align_pyramid");
+    return sessions_photo_align(s, n, ids, offsets0_px, opts, photo_align_check_opts, levels, out, levels_out, "hnet_sessions_photo_align_pyramid");
 }
 
 // the gain / bias + Huber form on the sessions' current pairs; read-only in the same way, the same upload and gather
 int hnet_sessions_photo_align_robust(hnet_sessions* s, int n, const int32_t* ids, const float* offsets0_px, const hnet_photo_robust_opts* opts, int levels,
                                      hnet_photo_robust* out, hnet_photo_robust* levels_out) {
-    const char* who = "hnet_sessions_photo_align_robust";
-    if (!s) return HNET_ERR_INVALID_ARG;
-    hnet_ctx* c = s->ctx;
-    if (!offsets0_px || !out) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": offsets / out");
-    if (levels < 1 || levels > HNET_ALIGN_MAX_LEVELS) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": 1 <= levels <= 4");
-    int rc = photo_robust_check_opts(c, opts, who);
-    if (rc == HNET_OK) rc = sessions_check_ids(s, n, ids);
-    if (rc == HNET_OK) rc = sessions_check_pairs(s, n, ids);
-    if (rc != HNET_OK) return rc;
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    const size_t off_bytes = (size_t)n * 8 * sizeof(float), up = off_bytes + (size_t)n * 8;
-    std::vector<uint8_t> h_in(up);
-    memcpy(h_in.data(), offsets0_px, off_bytes);
-    for (int i = 0; i < n; i++) sessions_pair(s, ids[i], reinterpret_cast<int32_t*>(h_in.data() + off_bytes) + 2 * i);
-    DevTemps t;
-    uint8_t* d_in = nullptr;
-    HIPCHK(c, t.alloc(&d_in, up));
-    hipStream_t st = c->stream;
-    HIPCHK(c, hipMemcpyAsync(d_in, h_in.data(), up, hipMemcpyHostToDevice, st));
-    HIPCHK(c, launch_session_gather(s->ring, 2 * s->n, reinterpret_cast<const int32_t*>(d_in + off_bytes), n, (uint8_t*)c->stage_prev, (uint8_t*)c->stage_curr, st));
-    return photo_robust_run(c, (const uint8_t*)c->stage_prev, (const uint8_t*)c->stage_curr, n, reinterpret_cast<const float*>(d_in), *opts, levels, out,
-                            levels_out);
+    return sessions_photo_align(s, n, ids, offsets0_px, opts, photo_robust_check_opts, levels, out, levels_out, "hnet_sessions_photo_align_robust");
 }
 
 }  // extern "C"

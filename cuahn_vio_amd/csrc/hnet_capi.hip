@@ -169,7 +169,6 @@ int create_impl(const hnet_config* cfg_in, const uint8_t* blob, size_t len, hnet
     CK(chain_init_device());
     CK(photo_init_device());
     CK(photo_align_init_device());
-    CK(photo_robust_init_device());
     if (preset_stream) { c->stream = preset_stream; c->owns_stream = false; }      // a group member: the group created its streams first, each on a priority level / hardware queue of its own
     else CK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     CK(hipEventCreate(&c->ev0));
@@ -1019,105 +1018,6 @@ int hnet_op_photo_residual(hnet_ctx* c, const uint8_t* img1, const uint8_t* img2
     memcpy(out, h_res.data(), (size_t)n * m * sizeof(PhotoRec));
     if (map_out) memcpy(map_out, h_res.data() + rec_bytes, map_bytes);
     return HNET_OK;
-}
-
-// ---- photometric alignment (include/hnet.h hnet_photo_align; csrc/kernels_photo_align.hip) ----
-static_assert(sizeof(hnet_photo_align) == sizeof(AlignRec) && offsetof(hnet_photo_align, mse0) == offsetof(AlignRec, mse0) &&
-              offsetof(hnet_photo_align, n_valid0) == offsetof(AlignRec, n_valid0) && offsetof(hnet_photo_align, lambda) == offsetof(AlignRec, lambda) &&
-              offsetof(hnet_photo_align, info) == offsetof(AlignRec, info) && sizeof(hnet_photo_align_opts) == sizeof(AlignOpts) &&
-              offsetof(hnet_photo_align_opts, lambda0) == offsetof(AlignOpts, lambda0), "hnet_photo_align / _opts are the layouts of include/hnet_photo_align.h");
-static_assert((int)HNET_ALIGN_CONVERGED == hnet_align::CONVERGED && (int)HNET_ALIGN_SINGULAR == hnet_align::SINGULAR &&
-              (int)HNET_ALIGN_DEGENERATE == hnet_align::DEGENERATE && (int)HNET_ALIGN_FEW_PIXELS == hnet_align::FEW_PIXELS &&
-              (int)HNET_ALIGN_MAX_ITERATIONS == hnet_align::MAX_ITERATIONS && (int)HNET_ALIGN_MAX_LEVELS == hnet_align::MAX_LEVELS,
-              "the flags of include/hnet_photo_align.h");
-
-extern "C++" {
-namespace capi {
-
-int photo_align_check_opts(hnet_ctx* c, const hnet_photo_align_opts* opts, const char* who) {
-    AlignOpts o;
-    if (opts) memcpy(&o, opts, sizeof o);
-    if (!opts || !hnet_align::opts_valid(o))
-        return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": opts: 0 <= max_iterations <= 32, min_valid >= 0, 0 < lambda0 <= 1e100, eps_px >= 0, all finite");
-    return HNET_OK;
-}
-
-// levels = 1 is launch_photo_align's sequence and nothing else.  levels_out is transposed on the host: the device keeps the records [levels][n], a level's
-// records being what its solve launches write
-int photo_align_pyramid_run(hnet_ctx* c, const uint8_t* d_img1, const uint8_t* d_img2, int n, const float* d_x0, const hnet_photo_align_opts& opts, int levels,
-                            hnet_photo_align* out, hnet_photo_align* levels_out) {
-    AlignOpts o;
-    memcpy(&o, &opts, sizeof o);
-    const size_t pyr = (size_t)c->cfg.max_batch * PYR_BYTES;
-    if (levels > 1 && !c->pyr_scratch) HIPCHK(c, dalloc(&c->pyr_scratch, 2 * pyr));
-    DevTemps t;
-    AlignSums* d_part = nullptr;
-    AlignWork* d_work = nullptr;
-    AlignRec* d_rec = nullptr;
-    float* d_start = nullptr;
-    HIPCHK(c, t.alloc(&d_part, (size_t)n * PHOTO_SLICES));
-    HIPCHK(c, t.alloc(&d_work, (size_t)n));
-    HIPCHK(c, t.alloc(&d_rec, (size_t)n * levels));
-    if (levels > 1) HIPCHK(c, t.alloc(&d_start, (size_t)n * 8));
-    std::vector<AlignRec> h_rec((size_t)n * levels);
-    HIPCHK(c, hipEventRecord(c->ev_align[0], c->stream));
-    HIPCHK(c, launch_photo_align_pyramid(d_img1, d_img2, n, d_x0, o, levels, c->pyr_scratch, c->pyr_scratch ? c->pyr_scratch + pyr : nullptr, d_start, d_part,
-                                         d_work, d_rec, c->stream));
-    HIPCHK(c, hipEventRecord(c->ev_align[1], c->stream));
-    HIPCHK(c, hipMemcpyAsync(h_rec.data(), d_rec, h_rec.size() * sizeof(AlignRec), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    float ms = 0;
-    HIPCHK(c, hipEventElapsedTime(&ms, c->ev_align[0], c->ev_align[1]));
-    c->photo_align_ms = ms;
-    memcpy(out, h_rec.data(), (size_t)n * sizeof(AlignRec));
-    if (levels_out)
-        for (int i = 0; i < n; i++)
-            for (int l = 0; l < levels; l++) memcpy(levels_out + (size_t)i * levels + l, &h_rec[(size_t)l * n + i], sizeof(AlignRec));
-    return HNET_OK;
-}
-
-}  // namespace capi
-}  // extern "C++"
-
-void hnet_photo_align_default_opts(hnet_photo_align_opts* o) {
-    if (!o) return;
-    AlignOpts d;
-    hnet_align::default_opts(d);
-    memcpy(o, &d, sizeof d);
-}
-
-double hnet_last_photo_align_device_ms(hnet_ctx* c) { return c ? c->photo_align_ms : 0.0; }
-
-// alignment of n host frame pairs from offsets0_px: ONE upload {img1 | img2 | offsets}, the launch sequence of `levels` levels, ONE download, one synchronisation
-static int op_photo_align(hnet_ctx* c, const uint8_t* img1, const uint8_t* img2, int n, const float* offsets0_px, const hnet_photo_align_opts* opts, int levels,
-                          hnet_photo_align* out, hnet_photo_align* levels_out, const char* who) {
-    if (!c) return HNET_ERR_INVALID_ARG;
-    if (!img1 || !img2 || !offsets0_px || !out || n < 1) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": frames / offsets / out, n >= 1");
-    if (levels < 1 || levels > HNET_ALIGN_MAX_LEVELS) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": 1 <= levels <= 4");
-    const int rc = photo_align_check_opts(c, opts, who);
-    if (rc != HNET_OK) return rc;
-    if (n > c->cfg.max_batch) return fail(c, HNET_ERR_CAPACITY, std::string(who) + ": n exceeds max_batch");
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    const size_t img = (size_t)n * NPIX, off_bytes = (size_t)n * 8 * sizeof(float), up = 2 * img + off_bytes;      // (NPIX is a multiple of 16: every section stays aligned)
-    DevTemps t;
-    uint8_t* d_in = nullptr;
-    HIPCHK(c, t.alloc(&d_in, up));
-    std::vector<uint8_t> h_in(up);
-    memcpy(h_in.data(), img1, img);
-    memcpy(h_in.data() + img, img2, img);
-    memcpy(h_in.data() + 2 * img, offsets0_px, off_bytes);
-    HIPCHK(c, hipMemcpyAsync(d_in, h_in.data(), up, hipMemcpyHostToDevice, c->stream));
-    return photo_align_pyramid_run(c, d_in, d_in + img, n, reinterpret_cast<const float*>(d_in + 2 * img), *opts, levels, out, levels_out);
-}
-
-int hnet_op_photo_align(hnet_ctx* c, const uint8_t* img1, const uint8_t* img2, int n, const float* offsets0_px, const hnet_photo_align_opts* opts, hnet_photo_align* out) {
-    return op_photo_align(c, img1, img2, n, offsets0_px, opts, 1, out, nullptr, "hnet_op_photo_align");
-}
-
-// the coarse-to-fine form: the pyramid launch and one launch sequence per level
-int hnet_op_photo_align_pyramid(hnet_ctx* c, const uint8_t* img1, const uint8_t* img2, int n, const float* offsets0_px, const hnet_photo_align_opts* opts, int levels,
-                                hnet_photo_align* out, hnet_photo_align* levels_out) {
-    return op_photo_align(c, img1, img2, n, offsets0_px, opts, levels, out, levels_out, "hnet_op_photo_align_pyramid");
 }
 
 // operator level: levels 1 .. 3 of n host frames -> out [n][PYR_BYTES]

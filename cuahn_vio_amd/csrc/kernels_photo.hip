@@ -48,18 +48,6 @@ constexpr int PH_ITER_CAND = 3;                                                /
 constexpr int PH_ITER_LDS_STAGED = NPIX + ph_aux_bytes(PH_ITER_CAND), PH_ITER_LDS_GLOBAL = ph_aux_bytes(PH_ITER_CAND);
 static_assert(NPIX % 16 == 0, "the aux sections start 16-byte aligned behind img2");
 static_assert(2 * PH_LDS_BYTES <= 160 * 1024, "two workgroups share a CU's LDS");
-
-// one fixed tree over the 64 lanes; the total ends in lane 0
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off);
-    return v;
-}
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off);
-    return v;
-}
 }  // namespace
 
 // The work of one workgroup (row slice `slice` of pair `pair`) for the m candidates first .. first + m - 1 of a pair's `stride` candidates: candidate c's

@@ -1,23 +1,10 @@
-// kernels_photo_pyramid.hip — the image pyramid and the coarse levels of photometric alignment (photo_pyramid_dev.h, include/hnet.h
-// hnet_op_photo_align_pyramid).  Level 0 stays on kernels_photo_align.hip, whose kernels this file does not touch.
+// kernels_photo_pyramid.hip — the image pyramid of photometric alignment (photo_pyramid_dev.h, include/hnet.h hnet_op_photo_pyramid).  The
+// alignment on its levels is kernels_photo_align.hip's.
 //
 // photo_pyramid_kernel: ONE launch per call makes levels 1, 2, 3 of every frame.  A workgroup of 320 threads owns a band of 32 rows of one frame: each thread
 // reads 16 pixels of two adjacent rows with two 16-byte loads (level 0 is read once), writes its 8 level-1 pixels to global memory and to LDS; level 2 is
 // made from the ROUNDED level 1 in LDS, level 3 from level 2 in LDS (hnet_align::down4: exact integers, bit-identical to the host reference).
-//
-// photo_pyr_accum_kernel<L>: photo_align_accum_kernel's contract on the level-L images.  One workgroup per (row slice, pair), the pair's level-L img2 staged
-// in LDS with 16-byte loads (17 920, 4 480 or 1 120 bytes), pixels of the slice taken in ascending order with a stride of the workgroup, 55 double
-// accumulators and the count per thread, lanes reduced by a fixed __shfl_down tree, the waves in wave order through LDS, one partial per slice and no
-// floating-point atomics: a record depends on its pair, start and options alone.  112, 56 and 28 rows divide by PHOTO_SLICES = 7, so
-// photo_align_solve_kernel adds the 7 partials of every level unchanged.  The per-pixel quantity is include/hnet_photo_pyramid.h's (level_coords,
-// level_position, level_row), the functions the host reference runs in a loop; the division is warp_coords' reciprocal form, bit-identical to IEEE x / z.
-// As at level 0 a product of two floats is exact in a double: the device and the host reference differ in the ORDER of the additions only.
-//
-// The start offsets of a level are the offsets the level above ended at, whatever its flags: photo_pyr_gather_kernel copies them (as bits) from the records
-// [n] of 656 bytes into the contiguous [n][8] the accumulate and solve kernels read.  Levels and iterations are separate launches; nothing waits on another
-// workgroup, and a stopped pair's workgroups return at once (a workgroup-uniform branch).
 #include "photo_pyramid_dev.h"
-#include "warp_dev.h"
 
 namespace hnet {
 
@@ -70,164 +57,11 @@ __global__ __launch_bounds__(PYR_THREADS) void photo_pyramid_kernel(const uint8_
     }
 }
 
-namespace {
-constexpr int pl_threads(int L) { return L == 1 ? 256 : (L == 2 ? 128 : 64); }  // 10, 5 and 2.5 pixels per thread and slice
-
-// warp_coords' quotients (csrc/warp_dev.h): the reciprocal form where Z is far from the ends of the exponent range, the compiler's division elsewhere
-struct WarpDiv {
-    __device__ __forceinline__ void operator()(float X, float Y, float Z, float& qx, float& qy) const {
-        if (warp_z_safe(Z)) {
-            const float r1 = warp_rcp_refined(Z);
-            qx = warp_div_with(X, Z, r1);
-            qy = warp_div_with(Y, Z, r1);
-        } else {
-            qx = X / Z;
-            qy = Y / Z;
-        }
-    }
-};
-}  // namespace
-
-// grid: PHOTO_SLICES * n workgroups of pl_threads(L) (slice = block % PHOTO_SLICES).  pyr1 / pyr2: [n][PYR_BYTES].  x0 != nullptr: the level's first
-// linearisation, at x0 [n][8]; otherwise at work[pair].x_trial, and a pair whose record OF THIS LEVEL carries a flag has stopped.
-template <int L>
-__global__ __launch_bounds__(pl_threads(L)) void photo_pyr_accum_kernel(const uint8_t* __restrict__ pyr1, const uint8_t* __restrict__ pyr2,
-                                                                        const float* __restrict__ x0, const AlignWork* __restrict__ work,
-                                                                        const AlignRec* __restrict__ rec, AlignSums* __restrict__ partial) {
-    constexpr int W = pa::level_w(L), LPIX = pa::level_pix(L), SLICE_PIX = LPIX / PHOTO_SLICES, THREADS = pl_threads(L), WAVES = THREADS / 64;
-    static_assert(L >= 1 && L < pa::MAX_LEVELS && pa::level_h(L) % PHOTO_SLICES == 0 && LPIX % 16 == 0 && pa::level_offset(L) % 16 == 0, "whole rows per slice");
-    __shared__ __attribute__((aligned(16))) uint8_t tile[LPIX];
-    __shared__ double w_sum[WAVES * PA_ND];
-    __shared__ int w_cnt[WAVES];
-    __shared__ float hs[9];
-    const int pair = blockIdx.x / PHOTO_SLICES, slice = blockIdx.x - pair * PHOTO_SLICES;
-    if (!x0 && rec[pair].flags != 0) return;                                  // (workgroup-uniform)
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    {
-        const uint4* src = reinterpret_cast<const uint4*>(pyr2 + (size_t)pair * PYR_BYTES + pa::level_offset(L));
-        for (int i = tid; i < LPIX / 16; i += THREADS) reinterpret_cast<uint4*>(tile)[i] = src[i];
-    }
-    if (tid == 0) {
-        float h[9];
-        pa_homography(x0 ? x0 + (size_t)pair * 8 : work[pair].x_trial, h);
-#pragma unroll
-        for (int k = 0; k < 9; k++) hs[k] = h[k];
-    }
-    __syncthreads();
-    float h[9];
-#pragma unroll
-    for (int k = 0; k < 9; k++) h[k] = hs[k];
-
-    const uint8_t* a_img = pyr1 + (size_t)pair * PYR_BYTES + pa::level_offset(L);
-    double acc[PA_ND];
-#pragma unroll
-    for (int k = 0; k < PA_ND; k++) acc[k] = 0.0;
-    int n_valid = 0;
-    for (int i = tid; i < SLICE_PIX; i += THREADS) {
-        const int pix = slice * SLICE_PIX + i;
-        const int v = pix / W, u = pix - v * W;
-        const float fu = pa::level_centre(L, u), fv = pa::level_centre(L, v);
-        float ix0, iy0, Z, ix, iy;
-        pa::level_coords(h, fu, fv, WarpDiv{}, ix0, iy0, Z);
-        if (!pa::level_position(L, ix0, iy0, ix, iy)) continue;              // (false for NaN)
-        const uint8_t* p = tile + (int)floorf(iy) * W + (int)floorf(ix);
-        float r, s[pa::NH];
-        pa::level_row(L, PixRead<uint8_t>::cvt(p[0]), PixRead<uint8_t>::cvt(p[1]), PixRead<uint8_t>::cvt(p[W]), PixRead<uint8_t>::cvt(p[W + 1]),
-                      PixRead<uint8_t>::cvt(a_img[pix]), ix, iy, ix0, iy0, Z, fu, fv, r, s);
-        double sd[pa::NH];
-#pragma unroll
-        for (int k = 0; k < pa::NH; k++) sd[k] = (double)s[k];
-        const double rd = (double)r;
-#pragma unroll
-        for (int k = 0; k < pa::NH; k++) {
-#pragma unroll
-            for (int j = k; j < pa::NH; j++) acc[pa::sym_index(k, j)] += sd[k] * sd[j];
-            acc[pa::NSYM + k] += sd[k] * rd;
-        }
-        acc[pa::NSYM + pa::NH] += rd * rd;
-        n_valid++;
-    }
-#pragma unroll
-    for (int k = 0; k < PA_ND; k++) {
-        const double t = pa_wave_sum(acc[k]);
-        if (lane == 0) w_sum[wave * PA_ND + k] = t;
-    }
-    n_valid = pa_wave_sum(n_valid);
-    if (lane == 0) w_cnt[wave] = n_valid;
-    __syncthreads();
-    AlignSums* out = partial + (size_t)pair * PHOTO_SLICES + slice;
-    if (tid < PA_ND) {
-        double t = 0.0;
-#pragma unroll
-        for (int w = 0; w < WAVES; w++) t += w_sum[w * PA_ND + tid];
-        reinterpret_cast<double*>(out)[tid] = t;
-    } else if (tid == PA_ND) {
-        int t = 0;
-#pragma unroll
-        for (int w = 0; w < WAVES; w++) t += w_cnt[w];
-        out->n_valid = t;
-        out->pad = 0;
-    }
-}
-static_assert(PA_ND + 1 <= 64, "one wave writes a partial");
-
-// start [n][8] = rec[pair].offsets_px, as bits (a NaN keeps its payload)
-__global__ __launch_bounds__(256) void photo_pyr_gather_kernel(const AlignRec* __restrict__ rec, uint32_t* __restrict__ start, int n) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n * 8) start[i] = reinterpret_cast<const uint32_t*>(rec[i >> 3].offsets_px)[i & 7];
-}
-
 hipError_t launch_photo_pyramid(const uint8_t* img_a, const uint8_t* img_b, int n, uint8_t* pyr_a, uint8_t* pyr_b, hipStream_t s) {
     if (n < 1 || n >= (1 << 15) || !img_a || !pyr_a || (img_b != nullptr) != (pyr_b != nullptr)) return hipErrorInvalidValue;      // (2 n frames in grid.y)
     if ((((uintptr_t)img_a) & 15) || (((uintptr_t)img_b) & 15) || (((uintptr_t)pyr_a) & 15) || (((uintptr_t)pyr_b) & 15)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(photo_pyramid_kernel, dim3(PYR_BANDS, (unsigned)(img_b ? 2 * n : n)), dim3(PYR_THREADS), 0, s, img_a, img_b, n, pyr_a, pyr_b);
     return hipGetLastError();
-}
-
-namespace {
-template <int L>
-hipError_t launch_level(const uint8_t* pyr1, const uint8_t* pyr2, int n, const float* x0, const AlignOpts& o, AlignSums* partial, AlignWork* work, AlignRec* rec,
-                        hipStream_t s) {
-    for (int it = 0; it <= o.max_iterations; it++) {
-        hipLaunchKernelGGL(photo_pyr_accum_kernel<L>, dim3((unsigned)(n * PHOTO_SLICES)), dim3(pl_threads(L)), 0, s, pyr1, pyr2, it == 0 ? x0 : nullptr,
-                           (const AlignWork*)work, (const AlignRec*)rec, partial);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        e = launch_photo_align_solve(partial, x0, it, o, n, work, rec, s);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-}  // namespace
-
-hipError_t launch_photo_align_pyramid(const uint8_t* img1, const uint8_t* img2, int n, const float* x0, const AlignOpts& opts, int levels, uint8_t* pyr1,
-                                      uint8_t* pyr2, float* start, AlignSums* partial, AlignWork* work, AlignRec* rec, hipStream_t s) {
-    if (levels < 1 || levels > pa::MAX_LEVELS || n < 1 || n > (1 << 20) || !x0 || (levels > 1 && !start) || !partial || !work || !rec || !pa::opts_valid(opts))
-        return hipErrorInvalidValue;
-    if (levels > 1) {
-        const hipError_t e = launch_photo_pyramid(img1, img2, n, pyr1, pyr2, s);
-        if (e != hipSuccess) return e;
-    }
-    for (int L = levels - 1; L >= 0; L--) {
-        AlignOpts o = opts;
-        o.min_valid = pa::level_min_valid(opts.min_valid, L);
-        AlignRec* r = rec + (size_t)L * n;
-        const float* x = x0;
-        if (L < levels - 1) {
-            hipLaunchKernelGGL(photo_pyr_gather_kernel, dim3((unsigned)((n * 8 + 255) / 256)), dim3(256), 0, s, (const AlignRec*)(r + n),
-                               reinterpret_cast<uint32_t*>(start), n);
-            const hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return e;
-            x = start;
-        }
-        hipError_t e;
-        if (L == 0) e = launch_photo_align(img1, img2, n, x, o, partial, work, r, s);
-        else if (L == 1) e = launch_level<1>(pyr1, pyr2, n, x, o, partial, work, r, s);
-        else if (L == 2) e = launch_level<2>(pyr1, pyr2, n, x, o, partial, work, r, s);
-        else e = launch_level<3>(pyr1, pyr2, n, x, o, partial, work, r, s);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
 }
 
 }  // namespace hnet

@@ -24,6 +24,18 @@ static_assert(sizeof(PhotoRec) == 24, "records are 24 bytes");
 //   offsets == nullptr (a filters step): c = 0 zero offsets, c = 1 prior[b 8 ..], c >= 2 net[(c - 2) net_iter_stride + b 72 ..] (the packed mean of forward c - 2)
 struct PhotoCands { const float* offsets; const float* prior; const float* net; size_t net_iter_stride; };
 
+// one fixed tree over the 64 lanes; the total ends in lane 0 (the residual records and every accumulate kernel of the alignment reduce with it)
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off);
+    return v;
+}
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off);
+    return v;
+}
+
 inline size_t photo_partial_count(int n, int m) { return (size_t)n * m * PHOTO_SLICES; }      // PhotoRec partials launch_photo_residual needs
 
 hipError_t photo_init_device();       // dynamic-LDS limit of photo_residual_kernel; once per device

@@ -82,6 +82,21 @@ __device__ inline void warp_coords(const float* h, int u, int v, float& ix, floa
     iy = ((gy + 1.0f) * 0.5f) * (float)(IMG_H - 1);
 }
 
+// warp_coords' quotients as the division include/hnet_photo_pyramid.h level_coords takes: the reciprocal form where Z is far from the ends of the exponent
+// range, the compiler's division elsewhere
+struct WarpDiv {
+    __device__ __forceinline__ void operator()(float X, float Y, float Z, float& qx, float& qy) const {
+        if (warp_z_safe(Z)) {
+            const float r1 = warp_rcp_refined(Z);
+            qx = warp_div_with(X, Z, r1);
+            qy = warp_div_with(Y, Z, r1);
+        } else {
+            qx = X / Z;
+            qy = Y / Z;
+        }
+    }
+};
+
 // bilinear blend of the four taps around (ix, iy) read from global memory; out-of-image taps contribute 0
 template <typename PIX, bool LUT = true>
 __device__ inline float warp_taps_global(const PIX* img, float ix, float iy, const float* lut) {

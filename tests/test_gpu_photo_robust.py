@@ -1,5 +1,5 @@
 """Photometric alignment with a gain / bias model and Huber weights on the device (include/hnet.h hnet_op_photo_align_robust;
-csrc/kernels_photo_robust.hip): one linearisation per level and the whole trace against the host reference tests/cpp/photo_robust_ref.cpp, the
+csrc/kernels_photo_align.hip): one linearisation per level and the whole trace against the host reference tests/cpp/photo_robust_ref.cpp, the
 accuracy rows against the truth and against hnet_op_photo_align_pyramid, the model-off identity with that call, the hostile starts, bitwise independence of
 the batch, the read-only sessions call and the refusals.  Calls of n = 1 and n = 3.  Main model prior-3, N = 16, max_batch 3."""
 import ctypes as C

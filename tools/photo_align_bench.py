@@ -10,6 +10,10 @@ stock pairs up to 32 px apart, started from zero offsets, with the trials every 
   python tools/photo_align_bench.py --robust [--huber K] [--no-brightness] [--levels L] [--iterations K]
 the gain / bias + Huber call (hnet_op_photo_align_robust) on the same pairs, from the same start and with the same trials (levels defaults
 to 4), with the gain it found.
+  python tools/photo_align_bench.py --parent DIR [--rounds 3] [--batches 1 8 64]
+this tree against a built checkout of the parent commit in DIR: the device time of the plain call (K = 0 and 6), the pyramid call (4 levels, K = 8) and the
+robust call (1 and 4 levels, K = 8), each tree in fresh child processes in turn, --rounds medians per cell.  A median of this tree above the parent's
+largest by more than the parent's own spread reads REGRESSION.
   python tools/photo_align_bench.py --summarize DIR
 prints, from the kernel trace a `rocprofv3 --kernel-trace --output-format csv -d DIR -- python tools/photo_align_bench.py ...` run left in DIR, the mean
 duration of every photometric kernel by grid size."""
@@ -19,6 +23,7 @@ import csv
 import glob
 import os
 import re
+import subprocess
 import sys
 import time
 
@@ -70,8 +75,65 @@ def pyramid(a, blob):
         e.close()
 
 
+CELLS = ("plain K=0", "plain K=6", "pyramid levels=4 K=8", "robust levels=1 K=8", "robust levels=4 K=8")
+
+
+def cells_only(a):
+    """the cells of --parent on the tree named by --root: one line "CELL n index median_ms" per cell and batch"""
+    from cuahn_vio_amd import synth, weights
+    from cuahn_vio_amd.homography_net import HnetEngine
+    blob = weights.pack_state_dict(weights.synthetic_state(0))
+    for n in a.batches:
+        near = [synth.make_pair(1 + i % 16, 12.0) for i in range(n)]
+        far = [synth.make_pair(1 + i % 16, 32.0) for i in range(n)]
+        prior = np.stack([synth.make_prior(1 + i % 16, near[i][2], 1.0) for i in range(n)])
+        n1, n2, f1, f2 = (np.stack([p[k] for p in ps]) for ps in (near, far) for k in (0, 1))
+        zero = np.zeros((n, 8), np.float32)
+        e = HnetEngine(blob, variant="prior3", mc_samples=16, dropout_p=0.05, mc_seed=9, max_batch=n)
+        calls = (lambda: e.op_photo_align(n1, n2, prior, max_iterations=0),
+                 lambda: e.op_photo_align(n1, n2, prior, max_iterations=6),
+                 lambda: e.op_photo_align_pyramid(f1, f2, zero, levels=4, max_iterations=8),
+                 lambda: e.op_photo_align_robust(f1, f2, zero, levels=1, max_iterations=8, huber_k=10.0, brightness=1),
+                 lambda: e.op_photo_align_robust(f1, f2, zero, levels=4, max_iterations=8, huber_k=10.0, brightness=1))
+        for j, call in enumerate(calls):
+            ms = []
+            for r in range(a.warmup + a.reps):
+                call()
+                ms.append(e.last_photo_align_device_ms())
+            print(f"CELL {n} {j} {np.median(ms[a.warmup:]):.4f}", flush=True)
+        e.close()
+
+
+def against_parent(a):
+    """this tree and the parent in turn, each in fresh child processes, --rounds medians per cell"""
+    here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    trees = [("this tree", here), ("parent", os.path.abspath(a.parent))]
+    got = {name: collections.defaultdict(list) for name, _ in trees}
+    for _ in range(a.rounds):
+        for name, root in trees:
+            env = dict(os.environ)
+            env.pop("HNET_LIB_PATH", None)
+            out = subprocess.run([sys.executable, os.path.abspath(__file__), "--cells-only", "--root", root, "--batches", *map(str, a.batches), "--reps", str(a.reps),
+                                  "--warmup", str(a.warmup)], check=True, capture_output=True, text=True, env=env, cwd=root, timeout=600).stdout
+            for line in out.splitlines():
+                if line.startswith("CELL "):
+                    _, n, j, ms = line.split()
+                    got[name][(int(n), int(j))].append(float(ms))
+    for n in a.batches:
+        for j, what in enumerate(CELLS):
+            mine, par = got["this tree"][(n, j)], got["parent"][(n, j)]
+            spread = max(par) - min(par)
+            verdict = "REGRESSION" if max(mine) > max(par) + spread else "no regression"
+            print(f"n = {n:3d}, {what:22s}: this tree " + " ".join(f"{x:.4f}" for x in mine) + " ms | parent " + " ".join(f"{x:.4f}" for x in par) +
+                  f" ms | largest {max(mine):.4f} against {max(par):.4f}, the parent's spread {spread:.4f}: {verdict}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--parent", default=None, help="a built checkout of the parent commit: the device time of the cells of CELLS on both trees")
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--cells-only", action="store_true", help="the cells of --parent alone, on the tree named by --root")
+    ap.add_argument("--root", default=None)
     ap.add_argument("--batches", type=int, nargs="+", default=[1, 8, 64])
     ap.add_argument("--reps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=5)
@@ -84,6 +146,12 @@ def main():
     a = ap.parse_args()
     if a.summarize:
         return summarize(a.summarize)
+    if a.parent:
+        return against_parent(a)
+    if a.root:
+        sys.path.insert(0, a.root)
+    if a.cells_only:
+        return cells_only(a)
     from cuahn_vio_amd import synth, weights
     from cuahn_vio_amd.homography_net import HnetEngine, HnetSessions
     blob = weights.pack_state_dict(weights.synthetic_state(0))
