@@ -62,6 +62,7 @@ SYMBOLS = [
     "hnet_keyframe_recover_default_opts", "hnet_sessions_keyframe_track_recover",
     "hnet_keyframe_measure_default_opts", "hnet_filters_set_keyframe_measure", "hnet_filters_last_keyframe_measure", "hnet_filters_keyframe_measure_stats",
     "hnet_filters_reset_keyframe_measure_stats", "hnet_filters_set_keyframe_recover", "hnet_filters_last_keyframe_recover",
+    "hnet_keyframe_render_fit_view", "hnet_op_keyframe_render", "hnet_sessions_enable_keyframe_render", "hnet_sessions_keyframe_render",
 ]
 # hnet_filters_advance's status per listed session (include/hnet.h HNET_ADV_*)
 ADV_STEPPED, ADV_WAIT_IMU, ADV_WAIT_INIT, ADV_INITIALIZED, ADV_PROPAGATED, ADV_NO_FRAME = range(6)
@@ -341,6 +342,32 @@ def keyframe_revisit_opts(**kw):
         else:
             raise TypeError(f"hnet_keyframe_revisit_opts has no field {k!r}")
     return o
+
+
+# a keyframe map rendered into a view (hnet_op_keyframe_render, hnet_sessions_keyframe_render): one record per rendered map; modes RENDER_*
+# (include/hnet.h HNET_RENDER_*)
+KEYFRAME_RENDER_DTYPE = _np.dtype([("h_origin_view", "<f8", (3, 3)), ("n_covered", "<u8"), ("n_overlap", "<u8"), ("n", "<u8", 8), ("sse", "<u8", 8),
+                                   ("used_mask", "<i4"), ("skipped_mask", "<i4")])
+assert KEYFRAME_RENDER_DTYPE.itemsize == 224
+RENDER_FEWEST_LINKS, RENDER_NEWEST, RENDER_MEAN = 0, 1, 2
+RENDER_MAX_DIM = 8192
+
+
+class KeyframeRenderOpts(C.Structure):
+    """hnet_keyframe_render_opts: the view's size and how the samples that cover a pixel are blended (RENDER_*)"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("mode", C.c_int32), ("pad", C.c_int32)]
+
+
+assert C.sizeof(KeyframeRenderOpts) == 16
+
+
+def keyframe_render_fit_view(entries, width, height, margin_px=0.0):
+    """hnet_keyframe_render_fit_view: the view [3, 3] of width x height pixels that shows every valid entry of `entries` (KEYFRAME_MAP_ENTRY_DTYPE) with
+    margin_px free on every side, or None when there is none (no usable entry, a map or a view without extent)"""
+    e = _np.ascontiguousarray(entries, dtype=KEYFRAME_MAP_ENTRY_DTYPE).reshape(-1)
+    h = _np.zeros((3, 3))
+    ok = lib().hnet_keyframe_render_fit_view(e.ctypes.data, len(e), int(width), int(height), float(margin_px), h.ctypes.data)
+    return h if ok else None
 
 
 # the coarse search over integer translations (hnet_op_photo_search): one record per pair; flags PS_* (include/hnet.h HNET_PS_*).  A score table is
@@ -780,6 +807,10 @@ def lib():
     L.hnet_filters_reset_keyframe_measure_stats.argtypes = [vp, C.c_int]
     L.hnet_filters_set_keyframe_recover.argtypes = [vp, C.c_int, vp, vp, C.c_int]
     L.hnet_filters_last_keyframe_recover.argtypes = [vp, C.c_int, vp]
+    L.hnet_keyframe_render_fit_view.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_double, vp]
+    L.hnet_op_keyframe_render.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]
+    L.hnet_sessions_enable_keyframe_render.argtypes = [vp, C.c_int, C.c_int]
+    L.hnet_sessions_keyframe_render.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp]
     for name in SYMBOLS:
         getattr(L, name)   # AttributeError here = the library does not export what include/hnet.h declares
     _lib = L

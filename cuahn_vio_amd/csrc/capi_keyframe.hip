@@ -22,6 +22,8 @@
 // keyframes_instep_* functions below, with the store's own scratch, decide on a copy of the state table and the commits deferred to the accepted attempt.
 // And the RECOVERY inside that in-step track: the launches of hnet_sessions_keyframe_track_recover on working copies of the state table and
 // of the map's entries and states (KeyInstepWork, allocated by hnet_filters_set_keyframe_recover), every image write deferred to the accepted attempt.
+// And the RENDER of a map into a view (keyframe_render_dev.h) lives in capi_keyframe_render.hip: the store only holds its pointer, frees it,
+// and hands out what the render reads (keyframes_render_hooks, keyframes_check_tracked).
 // The four tracks - the two sessions calls and the in-step track with and without recovery - share ONE launch sequence (enqueue_track), as
 // the relocalisations do: what each reads and writes is its RelocTargets, the recovering part its KeyRecovery.  The host table of a track has one
 // filler (keyframes_table) and the accepted in-step attempt one commit (keyframes_instep_commit).
@@ -29,6 +31,7 @@
 #include "keyframe_recover_dev.h"
 #include "photo_search_fine_dev.h"
 #include "filters_keyframe_dev.h"
+#include "keyframe_render_dev.h"
 
 using namespace hnet;
 using namespace capi;
@@ -115,6 +118,7 @@ struct hnet_keyframes {
     KeyReloc* reloc = nullptr;                 // the relocalisation's scratch or null: none of its calls was ever made
     KeyFine* fine = nullptr;                   // the fine relocalise's scratch or null: the call was never made
     KeyInstepWork* instep = nullptr;           // the in-step recovery's working copies or null: no filter ever turned it on
+    KeyRender* render = nullptr;               // the render's buffers (capi_keyframe_render.hip) or null: hnet_sessions_enable_keyframe_render was never called
     uint8_t* key = nullptr;                    // device [N][NPIX], zeroed at enable
     KeyState* state = nullptr;                 // device [N], zeroed at enable (has_key = 0)
     uint8_t* scratch = nullptr;                // device: the sections of KeyScratch
@@ -278,6 +282,7 @@ hipError_t instep_map_alloc(KeyInstepWork* w, const KeyMap* m, int N) {
 void keyframes_free(hnet_keyframes* k) {
     if (!k) return;
     instep_free(k->instep);
+    keyframes_render_free(k->render);
     map_free(k->map);
     reloc_free(k->reloc);
     fine_free(k->fine);
@@ -585,6 +590,18 @@ int keyframes_drop(hnet_sessions* s, int id) {
 }
 
 bool keyframes_enabled(const hnet_sessions* s) { return s->kf != nullptr; }
+
+bool keyframes_render_hooks(hnet_sessions* s, KeyRenderHooks* h) {
+    hnet_keyframes* k = s->kf;
+    if (!k || !k->map) return false;
+    const MapStore& m = k->map->dev;
+    h->src = RenderSource{m.img, m.entry, k->state, m.n_sessions, m.capacity};
+    h->render = &k->render;
+    h->ms = &k->ms;
+    return true;
+}
+
+int keyframes_check_tracked(hnet_sessions* s, int n, const int32_t* ids, const char* who) { return check_listed(s, n, ids, who, true); }
 
 void keyframes_table(const hnet_sessions* s, int n, const int32_t* ids, const uint8_t* on, int32_t* tab) {
     const hnet_keyframes* k = s->kf;

@@ -327,6 +327,22 @@ class HnetEngine:
                                                     sc.ctypes.data if want_scores else None))
         return (out, sc) if want_scores else out
 
+    def op_keyframe_render(self, images, entries, h_origin_view, width, height, mode=_capi.RENDER_FEWEST_LINKS):
+        """m (1 .. 8) stored keyframes [m, 224, 320] uint8 with their entries [m] of _capi.KEYFRAME_MAP_ENTRY_DTYPE rendered into the view h_origin_view
+        [3, 3] of width x height pixels (hnet_op_keyframe_render) -> (image [height, width] uint8, cover [height, width] uint8, record [1] of
+        _capi.KEYFRAME_RENDER_DTYPE); mode: _capi.RENDER_*"""
+        img = np.ascontiguousarray(images, dtype=np.uint8).reshape(-1, IMG_H, IMG_W)
+        ent = np.ascontiguousarray(entries, dtype=_capi.KEYFRAME_MAP_ENTRY_DTYPE).reshape(-1)
+        if len(ent) != img.shape[0]:
+            raise ValueError("images and entries must hold the same number of keyframes")
+        hv = np.ascontiguousarray(h_origin_view, dtype=np.float64).reshape(9)
+        o = _capi.KeyframeRenderOpts(int(width), int(height), int(mode), 0)
+        shape = (max(int(height), 1), max(int(width), 1))
+        out, cover, rec = np.zeros(shape, np.uint8), np.zeros(shape, np.uint8), np.zeros(1, _capi.KEYFRAME_RENDER_DTYPE)
+        check(self._h, self._L.hnet_op_keyframe_render(self._h, len(ent), img.ctypes.data, ent.ctypes.data, hv.ctypes.data, C.addressof(o), out.ctypes.data,
+                                                       cover.ctypes.data, rec.ctypes.data))
+        return out, cover, rec
+
     def op_photo_search_oriented(self, img1, img2, hyps=None, want_scores=False, **opts):
         """the coarse search under a table of orientation hypotheses (hnet_op_photo_search_oriented): a start for the alignments for a camera that has also
         turned; hyps [n_hyp] of _capi.PHOTO_SEARCH_HYP_DTYPE (None: the default table, 60 yaws of 6 degrees), opts as _capi.photo_search_opts ->
@@ -752,6 +768,23 @@ class HnetSessions:
         out = np.zeros((IMG_H, IMG_W), np.uint8)
         self._check(self._L.hnet_sessions_get_map_keyframe(self._s, int(id), int(slot), out.ctypes.data))
         return out
+
+    def enable_keyframe_render(self, max_width, max_height):
+        """hnet_sessions_enable_keyframe_render: allocates the render's buffers for views up to max_width x max_height; once, after enable_keyframe_map"""
+        self._check(self._L.hnet_sessions_enable_keyframe_render(self._s, int(max_width), int(max_height)))
+
+    def keyframe_render(self, ids, width, height, h_origin_view=None, mode=_capi.RENDER_FEWEST_LINKS):
+        """hnet_sessions_keyframe_render: the listed sessions' keyframe maps, each into its view h_origin_view [n, 3, 3] (None: each session's current
+        frame as its origin chain predicts it) of width x height pixels -> (images [n, height, width] uint8, covers [n, height, width] uint8, records
+        [n] of _capi.KEYFRAME_RENDER_DTYPE); read-only; mode: _capi.RENDER_*"""
+        ids, n = self._ids(ids)
+        hv = None if h_origin_view is None else np.ascontiguousarray(h_origin_view, dtype=np.float64).reshape(n, 9)
+        o = _capi.KeyframeRenderOpts(int(width), int(height), int(mode), 0)
+        shape = (n, max(int(height), 1), max(int(width), 1))
+        out, cover, rec = np.zeros(shape, np.uint8), np.zeros(shape, np.uint8), np.zeros(n, _capi.KEYFRAME_RENDER_DTYPE)
+        self._check(self._L.hnet_sessions_keyframe_render(self._s, n, ids.ctypes.data, hv.ctypes.data if hv is not None else None, C.addressof(o),
+                                                          out.ctypes.data, cover.ctypes.data, rec.ctypes.data))
+        return out, cover, rec
 
     def photo_search(self, ids, **opts):
         """coarse search over integer translations on the listed sessions' current pairs (hnet_sessions_photo_search); read-only; result as

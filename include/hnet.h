@@ -1248,6 +1248,45 @@ int  hnet_filters_set_keyframe_recover(hnet_filters* f, int id, const hnet_keyfr
  * HNET_ERR_INVALID_ARG, nothing written */
 int  hnet_filters_last_keyframe_recover(const hnet_filters* f, int n, hnet_keyframe_measure_recover* out);
 
+/* ---- a keyframe map RENDERED into a view, on the device (csrc/kernels_keyframe_render.hip; the shared code is include/hnet_keyframe_render.h;
+ * DESIGN 7ab).  Every stored keyframe of a map carries h_origin_key; a view is a width x height u8 image with h_origin_view (origin -> view, h[8] = 1).
+ * Each pixel of the view samples every stored keyframe it falls into (bilinear, the position in double), the samples are blended by `mode`, out_cover
+ * holds how many keyframes covered the pixel, and the record counts, in integers, how far each keyframe's samples lie from what is displayed where two
+ * or more overlap: sse[j] / n[j] is entry j's disagreement with the composite, and an entry whose h_origin_key is off stands out.  Read-only for every
+ * state the sessions hold, and opt-in: a sessions object that never calls hnet_sessions_enable_keyframe_render allocates, launches and returns what it did. */
+enum { HNET_RENDER_FEWEST_LINKS = 0,   /* the covering keyframe with the fewest chain links, then the lower slot: the least-drifted ground */
+       HNET_RENDER_NEWEST = 1,         /* the covering keyframe with the largest serial */
+       HNET_RENDER_MEAN = 2 };         /* (sum + cover / 2) / cover of the covering samples, in integers */
+#define HNET_RENDER_MAX_DIM 8192       /* the largest width or height of a view */
+typedef struct hnet_keyframe_render_opts { int32_t width, height, mode, pad; } hnet_keyframe_render_opts;
+typedef struct hnet_keyframe_render_rec {
+    double   h_origin_view[9];     /* the view that was rendered */
+    uint64_t n_covered, n_overlap; /* pixels with cover >= 1, >= 2 */
+    uint64_t n[8], sse[8];         /* per map slot, over the pixels with cover >= 2 it covers: their count and the sum of (sample - output)^2; zeros beyond capacity */
+    int32_t  used_mask, skipped_mask;   /* the slots that took part; the slots below the capacity that did not (invalid, or no S: a singular matrix) */
+} hnet_keyframe_render_rec;        /* every byte written: records compare byte for byte */
+/* The view that shows all of a map: the corners of every valid entry taken to the origin frame, bounded, scaled uniformly and centred in the view with
+ * margin_px free on every side.  Host side, in double.  0 (h_origin_view untouched): no usable entry, a box or a view without extent, a corner behind
+ * the camera or a non-finite value; else 1. */
+int  hnet_keyframe_render_fit_view(const hnet_keyframe_map_entry* entries, int capacity, int width, int height, double margin_px, double* h_origin_view /* [9] */);
+/* Operator level: m (1 .. 8) caller-supplied images [m][224][320] and entries [m] rendered into ONE view; no session is involved.  out_img and
+ * out_cover [height][width].  One upload, the two launches, one download, one synchronisation.  HNET_ERR_INVALID_ARG, nothing written: a null argument,
+ * m outside 1 .. 8, a mode outside the three, width or height outside 1 .. HNET_RENDER_MAX_DIM, a non-finite entry of h_origin_view. */
+int  hnet_op_keyframe_render(hnet_ctx* ctx, int m, const uint8_t* images, const hnet_keyframe_map_entry* entries, const double* h_origin_view /* [9] */,
+                             const hnet_keyframe_render_opts* opts, uint8_t* out_img, uint8_t* out_cover, hnet_keyframe_render_rec* rec);
+/* once, after hnet_sessions_enable_keyframe_map: the view and cover images of max_batch slots up to max_width x max_height, tables, pinned blocks and
+ * events of its own.  HNET_ERR_INVALID_ARG: before the map, a second call, a maximum outside 1 .. HNET_RENDER_MAX_DIM. */
+int  hnet_sessions_enable_keyframe_render(hnet_sessions* s, int max_width, int max_height);
+/* The listed sessions' maps, each into its own view: h_origin_view [n][9], or NULL = each session's current frame as its origin chain predicts it
+ * (h_origin_curr of its last track).  out_img and out_cover [n][height][width], out [n].  ONE upload, the two launches, ONE download and one
+ * synchronisation; hnet_sessions_last_keyframe_device_ms covers it.  A session whose map has no valid entry is not an error: zeros, and a record that is
+ * zero but for the view and skipped_mask.  Refused before anything is enqueued, nothing written: HNET_ERR_INVALID_ARG for a call before the enable, a null
+ * argument, a mode outside the three, width or height below 1 or above the enabled maximum, a non-finite view entry, an id out of range or repeated;
+ * HNET_ERR_CAPACITY for n > max_batch; HNET_ERR_NOT_READY for a NULL view on a session without a keyframe or whose latest image is not the one its last
+ * track saw. */
+int  hnet_sessions_keyframe_render(hnet_sessions* s, int n, const int32_t* ids, const double* h_origin_view, const hnet_keyframe_render_opts* opts,
+                                   uint8_t* out_img, uint8_t* out_cover, hnet_keyframe_render_rec* out);
+
 int hnet_synchronize(hnet_ctx* ctx, void* stream);
 int hnet_last_timing(const hnet_ctx* ctx, hnet_timing* out);
 
