@@ -1158,8 +1158,8 @@ int  hnet_sessions_keyframe_track_recover(hnet_sessions* s, int n, const int32_t
  * The measurement is UNUSABLE and nothing is applied when (one reason bit each, tested in this order) the session held no keyframe before the call
  * (HNET_KFM_FIRST); the track's record has a LOST bit; it has HNET_KF_GAP; the session's previous in-step track left no measured key_px
  * (HNET_KFM_PREV_NOT_MEASURED: a word per session, 1 after TRACKED or FIRST, 0 after LOST and for a session never measured; a reset of the keyframe
- * makes the next track FIRST); H(key_px before) has no inverse (|det| below 1e-12 of the cube of its largest entry) or a corner of the product has
- * z <= 0 or is not finite; then hnet_filters_set_photo_refine's reasons on the level-0 record, in their order.
+ * makes the next track FIRST); H(key_px before) has no inverse (|det| below 1e-12 of the cube of its largest entry in frame units:
+ * include/hnet_keyframe_map.h inverse) or a corner of the product has z <= 0 or is not finite; then hnet_filters_set_photo_refine's reasons on the level-0 record, in their order.
  * `when`: HNET_KFM_ALWAYS applies a usable measurement after whatever the network's iterations did; HNET_KFM_IF_NONE only when they applied nothing
  * (the slot's update counter is 0).  After a singular S of the network's own neither applies.  A usable measurement kept out is HNET_KFM_NOT_SELECTED.
  * updates[i] counts the keyframe update; its S found singular is the existing -1 - applied.  Every other record keeps its shape and content.

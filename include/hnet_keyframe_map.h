@@ -13,9 +13,10 @@
  *   stored with the new state's h_origin_key: links = 0 for FIRST, else cur_links + 1; into slot 0 when that is invalid, else into slot 1 + cursor, and
  *   the cursor advances modulo M - 1; cur_slot and cur_links become the new entry's.  Otherwise nothing changes.
  * origin_curr(state, h): h_origin_curr = chain(H(key_px), h_origin_key), the chain's value for the frame the state's key_px describes.
- * relative(h_origin_curr, entry, G, start_px) -> bool: G = h_origin_curr . inverse(entry.h_origin_key), the inverse as adjugate / determinant; false when
- *   |det| is below ORIGIN_TINY times the cube of the largest entry or anything is not finite.  G is renormalised to G[8] = 1 and maps a pixel of the
- *   stored keyframe to its position in the current frame.  start_px = the corners of G applied to p4, minus p4, rounded to fp32; false when a corner's z
+ * inverse(a, inv) -> bool: adjugate / determinant, the one inverse of this header and of hnet_keyframe_render.h; false when |det| is below ORIGIN_TINY
+ *   times the cube of the largest entry IN FRAME UNITS (a conjugated by diag(1 / 320, 1 / 320, 1), see the function) or anything is not finite.
+ * relative(h_origin_curr, entry, G, start_px) -> bool: G = h_origin_curr . inverse(entry.h_origin_key); false when the inverse fails or anything is not
+ *   finite.  G is renormalised to G[8] = 1 and maps a pixel of the stored keyframe to its position in the current frame.  start_px = the corners of G applied to p4, minus p4, rounded to fp32; false when a corner's z
  *   is not positive or a corner is not finite.
  * grid_inside(G, i), i in 0 .. 63: the template point (20 + 40 (i & 7), 14 + 28 (i >> 3)) is inside when z > 0, 0 <= x <= 319, 0 <= y <= 223.  The grid
  *   count is the number of points inside, of 64.  The grid is inset on purpose: a coarse test of visibility that a pixel of drift cannot flip at the
@@ -137,11 +138,14 @@ inline bool corners(const double m[9], double o[8]) {
     return ok;
 }
 
-/* false: G and start_px hold nothing to be used */
-inline bool relative(const double h_origin_curr[9], const Entry& e, double G[9], float start_px[8]) {
+/* inv = adjugate(a) / det(a); false (inv untouched) when a is not finite or degenerate: |det| below ORIGIN_TINY times the cube of the largest entry of
+ * a IN FRAME UNITS.  The entries of a homography mix units (pixels in [2] and [5], 1 / pixels in [6] and [7]), so the largest is taken over a conjugated by
+ * diag(1 / 320, 1 / 320, 1): [2] and [5] divided by FRAME_UNIT, [6] and [7] multiplied by it, the rest as they are.  The determinant is the same either
+ * way.  A translation by t px then counts as t / 320 frame widths and is refused beyond 320 x 10^4 = 3.2 x 10^6 px, not beyond 10^4 px. */
+constexpr double FRAME_UNIT = 320.0;
+inline bool inverse(const double a[9], double inv[9]) {
     HNET_ALIGN_NO_CONTRACT
-    const double* a = e.h_origin_key;
-    double adj[9], inv[9], o[8];
+    double adj[9];
     adj[0] = a[4] * a[8] - a[5] * a[7]; adj[1] = a[2] * a[7] - a[1] * a[8]; adj[2] = a[1] * a[5] - a[2] * a[4];
     adj[3] = a[5] * a[6] - a[3] * a[8]; adj[4] = a[0] * a[8] - a[2] * a[6]; adj[5] = a[2] * a[3] - a[0] * a[5];
     adj[6] = a[3] * a[7] - a[4] * a[6]; adj[7] = a[1] * a[6] - a[0] * a[7]; adj[8] = a[0] * a[4] - a[1] * a[3];
@@ -149,12 +153,22 @@ inline bool relative(const double h_origin_curr[9], const Entry& e, double G[9],
     double top = 0.0;
     bool ok = std::isfinite(det);
     for (int k = 0; k < 9; k++) {
-        const double v = std::fabs(a[k]);
-        top = v > top ? v : top;
-        ok = ok && std::isfinite(a[k]) && std::isfinite(h_origin_curr[k]);
+        const double v = std::fabs(a[k]), f = (k == 2 || k == 5) ? v / FRAME_UNIT : (k == 6 || k == 7) ? v * FRAME_UNIT : v;
+        top = f > top ? f : top;
+        ok = ok && std::isfinite(a[k]);
     }
     if (!ok || !(std::fabs(det) >= kf::ORIGIN_TINY * ((top * top) * top)) || det == 0.0) return false;
     for (int k = 0; k < 9; k++) inv[k] = adj[k] / det;
+    return true;
+}
+
+/* false: G and start_px hold nothing to be used */
+inline bool relative(const double h_origin_curr[9], const Entry& e, double G[9], float start_px[8]) {
+    HNET_ALIGN_NO_CONTRACT
+    double inv[9], o[8];
+    for (int k = 0; k < 9; k++)
+        if (!std::isfinite(h_origin_curr[k])) return false;
+    if (!inverse(e.h_origin_key, inv)) return false;
     if (!kf::chain(h_origin_curr, inv, G)) return false;
     if (!corners(G, o)) return false;
     for (int k = 0; k < 8; k++) start_px[k] = (float)o[k];

@@ -6,9 +6,9 @@
  * A view is a width x height u8 image with h_origin_view (origin -> view, h[8] = 1).
  *
  * render_setup(h_origin_view, entry, S) -> bool: S = entry.h_origin_key . inverse(h_origin_view), renormalised to S[8] = 1 (hnet_keyframe::chain): S maps
- *   a pixel of the view to its sampling position in the stored keyframe.  The inverse is adjugate / determinant with relative's test: false when |det|
- *   is below ORIGIN_TINY times the cube of the largest entry.  False too when the entry is not valid, when h_origin_key fails the same test (its S would
- *   map the view onto a line), when the product is degenerate or anything is not finite.
+ *   a pixel of the view to its sampling position in the stored keyframe.  The inverse is hnet_keyframe_map::inverse, the one relative calls: false when
+ *   |det| is below ORIGIN_TINY times the cube of the largest entry in frame units.  False too when the entry is not valid, when h_origin_key fails the
+ *   same test (its S would map the view onto a line), when the product is degenerate or anything is not finite.
  * render_sample(S, img, u, v, val) -> bool: (X, Y, Z) = S (u, v, 1) in double, each as (S0 u + S1 v) + S2; x = X / Z, y = Y / Z.  Invalid unless Z > 0,
  *   x and y are finite, 0 <= x <= 319 and 0 <= y <= 223.  x0 = floor(x), x1 = min(x0 + 1, 319), fx = (float)(x - x0), the same in y.  The blend, in float
  *   and in THIS order (nothing contracted):
@@ -60,32 +60,12 @@ inline bool opts_valid(const Opts& o) {
 struct Counters { uint64_t n_covered, n_overlap, n[MAX_ENTRIES], sse[MAX_ENTRIES]; };
 struct Record { double h_origin_view[9]; Counters c; int32_t used_mask, skipped_mask; };
 
-/* inv = adjugate(a) / det(a); false (inv untouched) when a is not finite or degenerate by relative's test */
-inline bool inverse(const double a[9], double inv[9]) {
-    HNET_ALIGN_NO_CONTRACT
-    double adj[9];
-    adj[0] = a[4] * a[8] - a[5] * a[7]; adj[1] = a[2] * a[7] - a[1] * a[8]; adj[2] = a[1] * a[5] - a[2] * a[4];
-    adj[3] = a[5] * a[6] - a[3] * a[8]; adj[4] = a[0] * a[8] - a[2] * a[6]; adj[5] = a[2] * a[3] - a[0] * a[5];
-    adj[6] = a[3] * a[7] - a[4] * a[6]; adj[7] = a[1] * a[6] - a[0] * a[7]; adj[8] = a[0] * a[4] - a[1] * a[3];
-    const double det = (a[0] * adj[0] + a[1] * adj[3]) + a[2] * adj[6];
-    double top = 0.0;
-    bool ok = std::isfinite(det);
-    for (int k = 0; k < 9; k++) {
-        const double v = std::fabs(a[k]);
-        top = v > top ? v : top;
-        ok = ok && std::isfinite(a[k]);
-    }
-    if (!ok || !(std::fabs(det) >= kf::ORIGIN_TINY * ((top * top) * top)) || det == 0.0) return false;
-    for (int k = 0; k < 9; k++) inv[k] = adj[k] / det;
-    return true;
-}
-
 /* false: S holds nothing to be used */
 inline bool render_setup(const double h_origin_view[9], const km::Entry& e, double S[9]) {
     HNET_ALIGN_NO_CONTRACT
     double inv[9];
-    if (e.valid == 0 || !inverse(e.h_origin_key, inv)) return false;        /* (a singular h_origin_key: S would map the view onto a line) */
-    if (!inverse(h_origin_view, inv)) return false;
+    if (e.valid == 0 || !km::inverse(e.h_origin_key, inv)) return false;    /* (a singular h_origin_key: S would map the view onto a line) */
+    if (!km::inverse(h_origin_view, inv)) return false;
     for (int k = 0; k < 9; k++)
         if (!std::isfinite(inv[k])) return false;
     return kf::chain(e.h_origin_key, inv, S);
@@ -170,7 +150,7 @@ inline bool render_fit_view(const km::Entry* e, int capacity, int width, int hei
     int used = 0;
     for (int j = 0; j < capacity; j++) {
         double inv[9];
-        if (!e[j].valid || !inverse(e[j].h_origin_key, inv)) continue;
+        if (!e[j].valid || !km::inverse(e[j].h_origin_key, inv)) continue;
         for (int c = 0; c < 4; c++) {
             const double u = hnet::p4(2 * c), v = hnet::p4(2 * c + 1);
             const double X = (inv[0] * u + inv[1] * v) + inv[2], Y = (inv[3] * u + inv[4] * v) + inv[5], Z = (inv[6] * u + inv[7] * v) + inv[8];

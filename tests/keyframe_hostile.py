@@ -122,7 +122,10 @@ MAP_EXPECT = {
     # a bridge far outside the image is chained in without a restart: the map stays valid and no entry is in view of the chain's h_origin_curr again
     ("1e12", 1): dict(track=(FIRST, EVERY, EVERY, EVERY, STOPPED | BRIDGED | REKEYED), track5=EVERY, **_FULL),
     ("1e12", 0): dict(track=(FIRST, 0, 0, 0, STOPPED | BRIDGED), track5={2: NO_START, 5: STOPPED}, **_ALONE),
-    ("1e6", 1): dict(track=(FIRST, EVERY, EVERY, EVERY, STOPPED | BRIDGED | REKEYED), track5=EVERY, **_FULL),
+    # 1e6 px is inside the domain of the map's inverse (3.2e6 px): the bridge's keyframe, stored 1e6 px out with links 4, is found again one frame later
+    # (all 64 grid points) and the revisit attaches it.  Until the inverse judged its determinant in frame units this entry was refused like 1e12's.
+    ("1e6", 1): dict(track=(FIRST, EVERY, EVERY, EVERY, STOPPED | BRIDGED | REKEYED), track5=EVERY, rv=((NO_CANDIDATE, -1, 0, 0), (ATTACHED, 2, 4, 64)),
+                     valid=((1, 1, 1),) * 4, mstate=((2, 4, 0, 5), (2, 4, 0, 5), (1, 5, 1, 6), (2, 4, 1, 6))),
     ("1e6", 0): dict(track=(FIRST, 0, 0, 0, STOPPED | BRIDGED), track5={2: NO_START, 5: STOPPED | BRIDGED}, **_ALONE),
     # a step that cannot be composed is bridged by the previous key_px: the chain goes on and both revisits attach slot 0
     ("nan", 1): dict(track=(FIRST, EVERY, EVERY, EVERY, NO_START | BRIDGED | REKEYED), track5=EVERY, rv=((ATTACHED, 0, 0, 64),) * 2, valid=((1, 1, 1),) * 4,

@@ -49,10 +49,21 @@ def opts_kw(o):
 GRID = np.array([[20.0 + 40.0 * (i & 7), 14.0 + 28.0 * (i >> 3), 1.0] for i in range(64)])
 
 
+FRAME_UNITS = np.array([[1.0, 1.0, 1 / 320.0], [1.0, 1.0, 1 / 320.0], [320.0, 320.0, 1.0]])    # a matrix conjugated by diag(1 / 320, 1 / 320, 1), entry by entry
+
+
+def np_invertible(h):
+    """the header's test of inverse: finite, and |det| at least 1e-12 times the cube of the largest entry in frame units"""
+    h = np.asarray(h, np.float64).reshape(3, 3)
+    with np.errstate(all="ignore"):
+        det = np.linalg.det(h) if np.isfinite(h).all() else np.nan
+        return bool(np.isfinite(det) and det != 0.0 and abs(det) >= 1e-12 * np.abs(h * FRAME_UNITS).max() ** 3)
+
+
 def np_relative(h_curr, h_key):
     """-> (G [3, 3] with G[2, 2] = 1, start [8] f64 unrounded) or None: G = h_curr . inverse(h_key) by LAPACK"""
     h_curr, h_key = np.asarray(h_curr, np.float64).reshape(3, 3), np.asarray(h_key, np.float64).reshape(3, 3)
-    if not (np.isfinite(h_curr).all() and np.isfinite(h_key).all()) or abs(np.linalg.det(h_key)) < 1e-12 * np.abs(h_key).max() ** 3:
+    if not np.isfinite(h_curr).all() or not np_invertible(h_key):
         return None
     g = h_curr @ np.linalg.inv(h_key)
     if not np.isfinite(g).all() or abs(g[2, 2]) < 1e-12 * np.abs(g).max():
