@@ -63,6 +63,8 @@ SYMBOLS = [
     "hnet_keyframe_measure_default_opts", "hnet_filters_set_keyframe_measure", "hnet_filters_last_keyframe_measure", "hnet_filters_keyframe_measure_stats",
     "hnet_filters_reset_keyframe_measure_stats", "hnet_filters_set_keyframe_recover", "hnet_filters_last_keyframe_recover",
     "hnet_keyframe_render_fit_view", "hnet_op_keyframe_render", "hnet_sessions_enable_keyframe_render", "hnet_sessions_keyframe_render",
+    "hnet_keyframe_adjust_default_opts", "hnet_op_keyframe_adjust_solve", "hnet_op_keyframe_adjust", "hnet_sessions_enable_keyframe_adjust",
+    "hnet_sessions_keyframe_adjust",
 ]
 # hnet_filters_advance's status per listed session (include/hnet.h HNET_ADV_*)
 ADV_STEPPED, ADV_WAIT_IMU, ADV_WAIT_INIT, ADV_INITIALIZED, ADV_PROPAGATED, ADV_NO_FRAME = range(6)
@@ -368,6 +370,53 @@ def keyframe_render_fit_view(entries, width, height, margin_px=0.0):
     h = _np.zeros((3, 3))
     ok = lib().hnet_keyframe_render_fit_view(e.ctypes.data, len(e), int(width), int(height), float(margin_px), h.ctypes.data)
     return h if ok else None
+
+
+# the joint adjustment of a keyframe map (hnet_op_keyframe_adjust_solve, hnet_op_keyframe_adjust, hnet_sessions_keyframe_adjust): one record per
+# session with its table of 28 edges; verdicts ADJ_*, edge flags ADJ_EDGE_*, weightings ADJ_WEIGHT_* (include/hnet.h HNET_ADJ_*)
+KEYFRAME_ADJUST_EDGE_DTYPE = _np.dtype([("i", "<i4"), ("j", "<i4"), ("grid", "<i4"), ("flags", "<i4"), ("start_px", "<f4", 8), ("offsets_px", "<f4", 8),
+                                        ("mse", "<f8"), ("overlap", "<f8"), ("r0_px", "<f8"), ("r_px", "<f8")])
+KEYFRAME_ADJUST_DTYPE = _np.dtype([("flags", "<i4"), ("anchor", "<i4"), ("n_pairs", "<i4"), ("n_jobs", "<i4"), ("n_edges", "<i4"), ("adjusted_mask", "<i4"),
+                                   ("unconnected_mask", "<i4"), ("trials", "<i4"), ("accepted", "<i4"), ("pad", "<i4"), ("cost0", "<f8"), ("cost", "<f8"),
+                                   ("lambda", "<f8"), ("delta_px", "<f8", (8, 8)), ("h_origin_key", "<f8", (8, 3, 3)), ("edge", KEYFRAME_ADJUST_EDGE_DTYPE, 28)])
+assert KEYFRAME_ADJUST_EDGE_DTYPE.itemsize == 112 and KEYFRAME_ADJUST_DTYPE.itemsize == 40 + 24 + 512 + 576 + 28 * 112
+ADJ_FEW_ENTRIES, ADJ_NO_EDGES, ADJ_SINGULAR, ADJ_NO_GAIN, ADJ_SHIFT_ABOVE_MAX, ADJ_CHAIN, ADJ_ADJUSTED, ADJ_CONVERGED = 1, 2, 4, 8, 16, 32, 64, 128
+ADJ_EDGE_ACCEPTED, ADJ_EDGE_STOPPED, ADJ_EDGE_MSE_ABOVE_MAX, ADJ_EDGE_NON_FINITE, ADJ_EDGE_LOW_OVERLAP, ADJ_EDGE_CLOSURE_ABOVE_MAX = 1, 2, 4, 8, 16, 32
+ADJ_EDGE_NO_RELATIVE = 64
+ADJ_WEIGHT_UNIT, ADJ_WEIGHT_INFO = 0, 1
+ADJ_MAX_EDGES, ADJ_MAX_TRIALS = 28, 64
+
+
+class KeyframeAdjustOpts(C.Structure):
+    """hnet_keyframe_adjust_opts: the alignment's options and levels and the revisit's gates for a pair and its edge (min_grid, min_overlap, max_mse,
+    max_closure_px), the weighting of the edges (ADJ_WEIGHT_*) with the floor under an edge's mse, the solve's trials at the most, initial damping and
+    convergence threshold (px), the largest accepted |delta| (px; 0: no limit) and whether the new matrices are written into the map"""
+    _fields_ = [("align", PhotoRobustOpts), ("levels", C.c_int32), ("min_grid", C.c_int32), ("min_overlap", C.c_double), ("max_mse", C.c_double),
+                ("max_closure_px", C.c_double), ("weighting", C.c_int32), ("max_trials", C.c_int32), ("mse_floor", C.c_double), ("lambda0", C.c_double),
+                ("eps_px", C.c_double), ("max_shift_px", C.c_double), ("apply", C.c_int32), ("pad", C.c_int32)]
+
+
+assert C.sizeof(KeyframeAdjustOpts) == 56 + 80
+
+
+def keyframe_adjust_opts(**kw):
+    """the defaults of hnet_keyframe_adjust_default_opts with the given fields replaced: the alignment's by their own names with its lambda0 and eps_px as
+    align_lambda0 and align_eps_px, the adjustment's by theirs"""
+    o = KeyframeAdjustOpts()
+    lib().hnet_keyframe_adjust_default_opts(C.byref(o))
+    for k, v in kw.items():
+        if k in ("max_iterations", "min_valid"):
+            setattr(o.align.base, k, v)
+        elif k in ("align_lambda0", "align_eps_px"):
+            setattr(o.align.base, k[6:], v)
+        elif k in ("brightness", "huber_k", "gain0", "bias0"):
+            setattr(o.align, k, v)
+        elif k in ("levels", "min_grid", "min_overlap", "max_mse", "max_closure_px", "weighting", "max_trials", "mse_floor", "lambda0", "eps_px", "max_shift_px",
+                   "apply"):
+            setattr(o, k, v)
+        else:
+            raise TypeError(f"hnet_keyframe_adjust_opts has no field {k!r}")
+    return o
 
 
 # the coarse search over integer translations (hnet_op_photo_search): one record per pair; flags PS_* (include/hnet.h HNET_PS_*).  A score table is
@@ -811,6 +860,12 @@ def lib():
     L.hnet_op_keyframe_render.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]
     L.hnet_sessions_enable_keyframe_render.argtypes = [vp, C.c_int, C.c_int]
     L.hnet_sessions_keyframe_render.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp]
+    L.hnet_keyframe_adjust_default_opts.argtypes = [vp]
+    L.hnet_keyframe_adjust_default_opts.restype = None
+    L.hnet_op_keyframe_adjust_solve.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp, vp]
+    L.hnet_op_keyframe_adjust.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
+    L.hnet_sessions_enable_keyframe_adjust.argtypes = [vp]
+    L.hnet_sessions_keyframe_adjust.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     for name in SYMBOLS:
         getattr(L, name)   # AttributeError here = the library does not export what include/hnet.h declares
     _lib = L

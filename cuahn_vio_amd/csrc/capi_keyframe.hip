@@ -24,6 +24,8 @@
 // of the map's entries and states (KeyInstepWork, allocated by hnet_filters_set_keyframe_recover), every image write deferred to the accepted attempt.
 // And the RENDER of a map into a view (keyframe_render_dev.h) lives in capi_keyframe_render.hip: the store only holds its pointer, frees it,
 // and hands out what the render reads (keyframes_render_hooks, keyframes_check_tracked).
+// And the joint ADJUSTMENT of a map (keyframe_adjust_dev.h) lives in capi_keyframe_adjust.hip in the same way: the store holds its pointer,
+// frees it, and hands out the map, the states and the alignment's scratch (keyframes_adjust_hooks).
 // The four tracks - the two sessions calls and the in-step track with and without recovery - share ONE launch sequence (enqueue_track), as
 // the relocalisations do: what each reads and writes is its RelocTargets, the recovering part its KeyRecovery.  The host table of a track has one
 // filler (keyframes_table) and the accepted in-step attempt one commit (keyframes_instep_commit).
@@ -32,6 +34,7 @@
 #include "photo_search_fine_dev.h"
 #include "filters_keyframe_dev.h"
 #include "keyframe_render_dev.h"
+#include "keyframe_adjust_dev.h"
 
 using namespace hnet;
 using namespace capi;
@@ -119,6 +122,7 @@ struct hnet_keyframes {
     KeyFine* fine = nullptr;                   // the fine relocalise's scratch or null: the call was never made
     KeyInstepWork* instep = nullptr;           // the in-step recovery's working copies or null: no filter ever turned it on
     KeyRender* render = nullptr;               // the render's buffers (capi_keyframe_render.hip) or null: hnet_sessions_enable_keyframe_render was never called
+    KeyAdjust* adjust = nullptr;               // the adjustment's buffers (capi_keyframe_adjust.hip) or null: hnet_sessions_enable_keyframe_adjust was never called
     uint8_t* key = nullptr;                    // device [N][NPIX], zeroed at enable
     KeyState* state = nullptr;                 // device [N], zeroed at enable (has_key = 0)
     uint8_t* scratch = nullptr;                // device: the sections of KeyScratch
@@ -283,6 +287,7 @@ void keyframes_free(hnet_keyframes* k) {
     if (!k) return;
     instep_free(k->instep);
     keyframes_render_free(k->render);
+    keyframes_adjust_free(k->adjust);
     map_free(k->map);
     reloc_free(k->reloc);
     fine_free(k->fine);
@@ -602,6 +607,18 @@ bool keyframes_render_hooks(hnet_sessions* s, KeyRenderHooks* h) {
 }
 
 int keyframes_check_tracked(hnet_sessions* s, int n, const int32_t* ids, const char* who) { return check_listed(s, n, ids, who, true); }
+
+bool keyframes_adjust_hooks(hnet_sessions* s, KeyAdjustHooks* h) {
+    hnet_keyframes* k = s->kf;
+    if (!k || !k->map) return false;
+    const MapStore& m = k->map->dev;
+    const KeyScratch w(k->scratch, s->ctx->cfg.max_batch);
+    h->src = AdjustSource{m.img, m.entry, k->state, m.state, m.n_sessions, m.capacity};
+    h->align = AdjustAlign{w.rec, w.start, w.work, w.part, w.x0};
+    h->adjust = &k->adjust;
+    h->ms = &k->ms;
+    return true;
+}
 
 void keyframes_table(const hnet_sessions* s, int n, const int32_t* ids, const uint8_t* on, int32_t* tab) {
     const hnet_keyframes* k = s->kf;

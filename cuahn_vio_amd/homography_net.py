@@ -343,6 +343,34 @@ class HnetEngine:
                                                        cover.ctypes.data, rec.ctypes.data))
         return out, cover, rec
 
+    def op_keyframe_adjust_solve(self, entries, edges, edge_infos=None, **opts):
+        """the solve of a keyframe map's joint adjustment alone (hnet_op_keyframe_adjust_solve): entries [m] (1 .. 8) of _capi.KEYFRAME_MAP_ENTRY_DTYPE,
+        edges [n_edges] (0 .. 28) of _capi.KEYFRAME_ADJUST_EDGE_DTYPE, edge_infos None or [n_edges, 8, 8] -> record [1] of _capi.KEYFRAME_ADJUST_DTYPE;
+        opts as _capi.keyframe_adjust_opts"""
+        ent = np.ascontiguousarray(entries, dtype=_capi.KEYFRAME_MAP_ENTRY_DTYPE).reshape(-1)
+        ed = np.ascontiguousarray(edges, dtype=_capi.KEYFRAME_ADJUST_EDGE_DTYPE).reshape(-1)
+        inf = None if edge_infos is None else np.ascontiguousarray(edge_infos, dtype=np.float64).reshape(len(ed), 64)
+        o = _capi.keyframe_adjust_opts(**opts)
+        rec = np.zeros(1, _capi.KEYFRAME_ADJUST_DTYPE)
+        check(self._h, self._L.hnet_op_keyframe_adjust_solve(self._h, len(ent), ent.ctypes.data, len(ed), ed.ctypes.data if len(ed) else None,
+                                                             inf.ctypes.data if inf is not None and len(ed) else None, C.addressof(o), rec.ctypes.data))
+        return rec
+
+    def op_keyframe_adjust(self, images, entries, want_edge_records=False, **opts):
+        """the joint adjustment of m (1 .. 8) stored keyframes [m, 224, 320] uint8 with their entries [m] (hnet_op_keyframe_adjust): every overlapping
+        pair aligned, all places solved for at once -> record [1] of _capi.KEYFRAME_ADJUST_DTYPE; want_edge_records: (that, the jobs' level-0
+        alignment records [28] of _capi.PHOTO_ROBUST_DTYPE in job order); opts as _capi.keyframe_adjust_opts"""
+        img = np.ascontiguousarray(images, dtype=np.uint8).reshape(-1, IMG_H, IMG_W)
+        ent = np.ascontiguousarray(entries, dtype=_capi.KEYFRAME_MAP_ENTRY_DTYPE).reshape(-1)
+        if len(ent) != img.shape[0]:
+            raise ValueError("images and entries must hold the same number of keyframes")
+        o = _capi.keyframe_adjust_opts(**opts)
+        rec = np.zeros(1, _capi.KEYFRAME_ADJUST_DTYPE)
+        er = np.zeros(_capi.ADJ_MAX_EDGES, _capi.PHOTO_ROBUST_DTYPE) if want_edge_records else None
+        check(self._h, self._L.hnet_op_keyframe_adjust(self._h, len(ent), img.ctypes.data, ent.ctypes.data, C.addressof(o), rec.ctypes.data,
+                                                       er.ctypes.data if want_edge_records else None))
+        return (rec, er) if want_edge_records else rec
+
     def op_photo_search_oriented(self, img1, img2, hyps=None, want_scores=False, **opts):
         """the coarse search under a table of orientation hypotheses (hnet_op_photo_search_oriented): a start for the alignments for a camera that has also
         turned; hyps [n_hyp] of _capi.PHOTO_SEARCH_HYP_DTYPE (None: the default table, 60 yaws of 6 degrees), opts as _capi.photo_search_opts ->
@@ -785,6 +813,22 @@ class HnetSessions:
         self._check(self._L.hnet_sessions_keyframe_render(self._s, n, ids.ctypes.data, hv.ctypes.data if hv is not None else None, C.addressof(o),
                                                           out.ctypes.data, cover.ctypes.data, rec.ctypes.data))
         return out, cover, rec
+
+    def enable_keyframe_adjust(self):
+        """hnet_sessions_enable_keyframe_adjust: allocates the adjustment's tables, records and pinned blocks; once, after enable_keyframe_map"""
+        self._check(self._L.hnet_sessions_enable_keyframe_adjust(self._s))
+
+    def keyframe_adjust(self, ids, want_edge_records=False, **opts):
+        """hnet_sessions_keyframe_adjust: the listed sessions' keyframe maps, each adjusted jointly -> records [n] of _capi.KEYFRAME_ADJUST_DTYPE;
+        want_edge_records: (those, the jobs' level-0 alignment records [n, 28] of _capi.PHOTO_ROBUST_DTYPE).  apply=1 writes the new matrices into the
+        maps; otherwise read-only.  opts as _capi.keyframe_adjust_opts"""
+        ids, n = self._ids(ids)
+        o = _capi.keyframe_adjust_opts(**opts)
+        rec = np.zeros(n, _capi.KEYFRAME_ADJUST_DTYPE)
+        er = np.zeros((n, _capi.ADJ_MAX_EDGES), _capi.PHOTO_ROBUST_DTYPE) if want_edge_records else None
+        self._check(self._L.hnet_sessions_keyframe_adjust(self._s, n, ids.ctypes.data, C.addressof(o), rec.ctypes.data,
+                                                          er.ctypes.data if want_edge_records else None))
+        return (rec, er) if want_edge_records else rec
 
     def photo_search(self, ids, **opts):
         """coarse search over integer translations on the listed sessions' current pairs (hnet_sessions_photo_search); read-only; result as

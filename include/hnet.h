@@ -1287,6 +1287,78 @@ int  hnet_sessions_enable_keyframe_render(hnet_sessions* s, int max_width, int m
 int  hnet_sessions_keyframe_render(hnet_sessions* s, int n, const int32_t* ids, const double* h_origin_view, const hnet_keyframe_render_opts* opts,
                                    uint8_t* out_img, uint8_t* out_cover, hnet_keyframe_render_rec* out);
 
+/* ---- a keyframe map ADJUSTED jointly, on the device (csrc/kernels_keyframe_adjust.hip; the shared code is include/hnet_keyframe_adjust.h).
+ * A revisit re-attaches the session to one stored keyframe; every entry stored in between keeps its drifted h_origin_key.  The adjustment re-measures
+ * every overlapping pair (i < j) of a session's stored keyframes with the robust alignment - template image i, other image j, start composed from the two
+ * matrices - and solves for all their places at once: per entry k of the anchor's component a correction delta_k (four-corner offsets in keyframe k's
+ * own pixels, X_k' = H(delta_k) . X_k), by Levenberg-Marquardt on sum r^T W r over the accepted edges, r = offsets - corners(H(delta_j) X_j X_i^-1
+ * H(delta_i)^-1).  The anchor - the usable entry with the fewest links, then the lowest slot - does not move.  All or nothing per session: the new
+ * matrices exist only under HNET_ADJ_ADJUSTED.  Opt-in: a sessions object that never calls hnet_sessions_enable_keyframe_adjust allocates, launches and
+ * returns what it did. */
+enum { HNET_ADJ_FEW_ENTRIES = 1,       /* fewer than two usable (valid, invertible) entries */
+       HNET_ADJ_NO_EDGES = 2,          /* no accepted edge reaches the anchor */
+       HNET_ADJ_SINGULAR = 4,          /* the normal matrix has a Cholesky pivot <= 1e-12 max diag, or a step is not finite: the edges leave an entry free */
+       HNET_ADJ_NO_GAIN = 8,           /* not cost < cost0 */
+       HNET_ADJ_SHIFT_ABOVE_MAX = 16,  /* max_shift_px > 0 and the worst |delta| exceeds it: the guard against a false match */
+       HNET_ADJ_CHAIN = 32,            /* a H(delta_k) . X_k is degenerate */
+       HNET_ADJ_ADJUSTED = 64,         /* the record's h_origin_key are the new matrices (and, with apply, the map's) */
+       HNET_ADJ_CONVERGED = 128 };     /* beside the verdict: an accepted step moved no component by eps_px or more */
+enum { HNET_ADJ_EDGE_ACCEPTED = 1, HNET_ADJ_EDGE_STOPPED = 2, HNET_ADJ_EDGE_MSE_ABOVE_MAX = 4, HNET_ADJ_EDGE_NON_FINITE = 8, HNET_ADJ_EDGE_LOW_OVERLAP = 16,
+       HNET_ADJ_EDGE_CLOSURE_ABOVE_MAX = 32,   /* hnet_keyframe_revisit's reasons, in its order */
+       HNET_ADJ_EDGE_NO_RELATIVE = 64 };       /* a caller-supplied row that cannot be an edge: slots not i < j < m, an unusable endpoint, a non-finite offset */
+enum { HNET_ADJ_WEIGHT_UNIT = 0,       /* W = I */
+       HNET_ADJ_WEIGHT_INFO = 1 };     /* W = the record's 8 x 8 information matrix / max(mse, mse_floor) */
+#define HNET_ADJ_MAX_EDGES 28
+#define HNET_ADJ_MAX_TRIALS 64
+typedef struct hnet_keyframe_adjust_opts {
+    hnet_photo_robust_opts align;      /* the alignment of every pair */
+    int32_t levels, min_grid;          /* its levels (1 .. 4); the fewest grid points (of 64) of keyframe i inside keyframe j for a pair to be a job */
+    double  min_overlap, max_mse, max_closure_px;      /* an edge's gates, as hnet_keyframe_revisit_opts' (0: no limit, the last two) */
+    int32_t weighting, max_trials;     /* HNET_ADJ_WEIGHT_*; trials of the solve at the most, 1 .. HNET_ADJ_MAX_TRIALS */
+    double  mse_floor, lambda0, eps_px, max_shift_px;  /* the floor under an edge's mse (> 0); initial damping (0 < . <= 1e100); convergence (px); 0: no limit */
+    int32_t apply, pad;                /* 1: the new matrices are written into the map (the operator-level calls have no map: ignored there) */
+} hnet_keyframe_adjust_opts;
+typedef struct hnet_keyframe_adjust_edge {
+    int32_t i, j, grid, flags;         /* the pair, keyframe i's grid count inside j, HNET_ADJ_EDGE_* */
+    float   start_px[8], offsets_px[8];/* the alignment's start and result: where keyframe i's corners lie in j */
+    double  mse, overlap;              /* the record's mean robust cost and n_valid / 71 680 */
+    double  r0_px, r_px;               /* the worst residual component before and after the solve (0 for an edge outside it) */
+} hnet_keyframe_adjust_edge;
+typedef struct hnet_keyframe_adjust {
+    int32_t flags, anchor;             /* HNET_ADJ_*; the anchor's slot or -1 */
+    int32_t n_pairs, n_jobs, n_edges;  /* pairs of usable entries, those aligned, those accepted */
+    int32_t adjusted_mask, unconnected_mask;   /* the anchor's component (the anchor included); the usable entries outside it, which keep their bytes */
+    int32_t trials, accepted, pad;
+    double  cost0, cost, lambda;
+    double  delta_px[8][8];            /* what the solve reached, whenever it ran (zeros for the anchor and outside the component) */
+    double  h_origin_key[8][9];        /* under HNET_ADJ_ADJUSTED the new matrices; the old one for every other slot below the capacity, zeros above */
+    hnet_keyframe_adjust_edge edge[HNET_ADJ_MAX_EDGES];        /* the jobs in pair order; unused rows are zero */
+} hnet_keyframe_adjust;                /* every byte written: records compare byte for byte */
+void hnet_keyframe_adjust_default_opts(hnet_keyframe_adjust_opts* o);
+/* Operator level, the solve alone: caller-supplied entries [m] (1 .. 8) and edge rows [n_edges] (0 .. 28; i, j, flags, offsets_px and mse are read),
+ * edge_infos NULL (identity) or [n_edges][64], as one session of capacity m.  One upload, one launch, one download, one synchronisation.
+ * HNET_ERR_INVALID_ARG, nothing written: a null argument, m or n_edges out of range, invalid options. */
+int  hnet_op_keyframe_adjust_solve(hnet_ctx* ctx, int m, const hnet_keyframe_map_entry* entries, int n_edges, const hnet_keyframe_adjust_edge* edges,
+                                   const double* edge_infos, const hnet_keyframe_adjust_opts* opts, hnet_keyframe_adjust* out);
+/* Operator level, the whole adjustment: pairs, alignments and solve on caller-supplied images [m][224][320] and entries [m].  out_edge_records NULL or
+ * [28] level-0 records of the jobs, in job order (unused rows zero).  The jobs run in rounds of max_batch alignments; TWO synchronisations, one after the
+ * pairs (a small download of the job table sizes the rounds) and one at the end.  Errors as above. */
+int  hnet_op_keyframe_adjust(hnet_ctx* ctx, int m, const uint8_t* images, const hnet_keyframe_map_entry* entries, const hnet_keyframe_adjust_opts* opts,
+                             hnet_keyframe_adjust* out, hnet_photo_robust* out_edge_records);
+/* once, after hnet_sessions_enable_keyframe_map: job tables, edge tables, records, pinned blocks and events of max_batch slots.
+ * HNET_ERR_INVALID_ARG: before the map, a second call. */
+int  hnet_sessions_enable_keyframe_adjust(hnet_sessions* s);
+/* The listed sessions' maps, each adjusted on its own: out [n], out_edge_records NULL or [n][28].  An occasional call after a closure, not a per-tick
+ * one: the jobs of all listed sessions run in rounds of max_batch alignments (a session's jobs may straddle a round) on the staging arrays and the
+ * alignment scratch of the keyframe store, and the call has TWO synchronisations, one after the pairs kernel and one at the end.
+ * hnet_sessions_last_keyframe_device_ms covers it (from the pairs kernel to the solve, the host's sizing of the rounds included).  With opts.apply the
+ * new matrices are written into the map's entries and the state's h_origin_key follows entry cur_slot's; valid, links, serial, cursor, key_px, age and
+ * the images are never touched; without it the call is read-only.  A session with fewer than two valid entries is not an error: HNET_ADJ_FEW_ENTRIES.
+ * Refused before anything is enqueued, nothing written: HNET_ERR_INVALID_ARG for a call before the enable, a null argument, invalid options, an id out
+ * of range or repeated; HNET_ERR_CAPACITY for n > max_batch. */
+int  hnet_sessions_keyframe_adjust(hnet_sessions* s, int n, const int32_t* ids, const hnet_keyframe_adjust_opts* opts, hnet_keyframe_adjust* out,
+                                   hnet_photo_robust* out_edge_records);
+
 int hnet_synchronize(hnet_ctx* ctx, void* stream);
 int hnet_last_timing(const hnet_ctx* ctx, hnet_timing* out);
 
