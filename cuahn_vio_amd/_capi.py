@@ -48,6 +48,8 @@ SYMBOLS = [
     "hnet_photo_align_default_opts", "hnet_op_photo_align", "hnet_sessions_photo_align", "hnet_last_photo_align_device_ms",
     "hnet_op_photo_align_pyramid", "hnet_sessions_photo_align_pyramid", "hnet_op_photo_pyramid",
     "hnet_photo_robust_default_opts", "hnet_op_photo_align_robust", "hnet_sessions_photo_align_robust", "hnet_photo_robust_marginal",
+    "hnet_op_photo_align_masked", "hnet_keyframe_localise_default_opts", "hnet_op_keyframe_localise", "hnet_sessions_enable_keyframe_localise",
+    "hnet_sessions_keyframe_localise",
     "hnet_photo_refine_default_opts", "hnet_filters_set_photo_refine", "hnet_filters_last_refine", "hnet_filters_refine_stats", "hnet_filters_reset_refine_stats",
     "hnet_photo_search_default_opts", "hnet_op_photo_search", "hnet_sessions_photo_search",
     "hnet_keyframe_relocalise_default_opts", "hnet_sessions_keyframe_relocalise",
@@ -353,6 +355,37 @@ KEYFRAME_RENDER_DTYPE = _np.dtype([("h_origin_view", "<f8", (3, 3)), ("n_covered
 assert KEYFRAME_RENDER_DTYPE.itemsize == 224
 RENDER_FEWEST_LINKS, RENDER_NEWEST, RENDER_MEAN = 0, 1, 2
 RENDER_MAX_DIM = 8192
+
+
+class KeyframeLocaliseOpts(C.Structure):
+    """hnet_keyframe_localise_opts: the masked alignment's options and levels, the render mode of the template, the smallest cover of the template and
+    overlap of an accepted alignment (fractions of the frame), its largest mse and the largest |offset| (px; 0: no limit, both), and apply (0 / 1)"""
+    _fields_ = [("align", PhotoRobustOpts), ("levels", C.c_int32), ("mode", C.c_int32), ("min_cover", C.c_double), ("min_overlap", C.c_double),
+                ("max_mse", C.c_double), ("max_shift_px", C.c_double), ("apply", C.c_int32), ("pad", C.c_int32)]
+
+
+assert C.sizeof(KeyframeLocaliseOpts) == 104
+KEYFRAME_LOCALISE_DTYPE = _np.dtype([("rec", PHOTO_ROBUST_DTYPE), ("h_origin_before", "<f8", (3, 3)), ("h_origin_curr", "<f8", (3, 3)), ("correction_px", "<f8", 8),
+                                     ("cover", "<f8"), ("overlap", "<f8"), ("used_mask", "<i4"), ("links_before", "<i4"), ("links", "<i4"), ("flags", "<i4"),
+                                     ("pad", "<i4", 2)])
+assert KEYFRAME_LOCALISE_DTYPE.itemsize == 1808
+LOC_NO_MAP, LOC_LOW_COVER, LOC_STOPPED, LOC_MSE_ABOVE_MAX, LOC_NON_FINITE, LOC_LOW_OVERLAP, LOC_SHIFT_ABOVE_MAX, LOC_CHAIN, LOC_LOCALISED = 1, 2, 4, 8, 16, 32, 64, 128, 256
+
+
+def keyframe_localise_opts(**kw):
+    """the defaults of hnet_keyframe_localise_default_opts with the given fields replaced (the fields of `align` and its `base` by their own names)"""
+    o = KeyframeLocaliseOpts()
+    lib().hnet_keyframe_localise_default_opts(C.byref(o))
+    for k, v in kw.items():
+        if k in ("max_iterations", "min_valid", "lambda0", "eps_px"):
+            setattr(o.align.base, k, v)
+        elif k in ("brightness", "huber_k", "gain0", "bias0"):
+            setattr(o.align, k, v)
+        elif k in ("levels", "mode", "min_cover", "min_overlap", "max_mse", "max_shift_px", "apply"):
+            setattr(o, k, v)
+        else:
+            raise TypeError(f"unknown option {k}")
+    return o
 
 
 class KeyframeRenderOpts(C.Structure):
@@ -803,6 +836,12 @@ def lib():
     L.hnet_photo_robust_default_opts.argtypes = [C.POINTER(PhotoRobustOpts)]
     L.hnet_photo_robust_default_opts.restype = None
     L.hnet_op_photo_align_robust.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp]
+    L.hnet_op_photo_align_masked.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp]
+    L.hnet_keyframe_localise_default_opts.argtypes = [C.POINTER(KeyframeLocaliseOpts)]
+    L.hnet_keyframe_localise_default_opts.restype = None
+    L.hnet_op_keyframe_localise.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.hnet_sessions_enable_keyframe_localise.argtypes = [vp]
+    L.hnet_sessions_keyframe_localise.argtypes = [vp, C.c_int, vp, vp, vp]
     L.hnet_sessions_photo_align_robust.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp, vp]
     L.hnet_photo_robust_marginal.argtypes = [vp, vp, vp]
     L.hnet_keyframe_default_opts.argtypes = [C.POINTER(KeyframeOpts)]

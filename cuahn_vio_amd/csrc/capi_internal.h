@@ -244,6 +244,9 @@ int photo_align_run(hnet_ctx* c, const uint8_t* d_img1, const uint8_t* d_img2, i
 int photo_robust_check_opts(hnet_ctx* c, const hnet_photo_robust_opts* opts, const char* who);
 int photo_align_run(hnet_ctx* c, const uint8_t* d_img1, const uint8_t* d_img2, int n, const float* d_x0, const hnet_photo_robust_opts& opts, int levels,
                     hnet_photo_robust* out, hnet_photo_robust* levels_out);
+// the robust form on the template pixels the masks d_mask1 [n][NPIX] admit; opts checked by photo_robust_check_opts
+int photo_align_masked_run(hnet_ctx* c, const uint8_t* d_img1, const uint8_t* d_mask1, const uint8_t* d_img2, int n, const float* d_x0,
+                           const hnet_photo_robust_opts& opts, int levels, hnet_photo_robust* out, hnet_photo_robust* levels_out);
 void build_undistort_maps(const hnet_camera* cam, std::vector<float>& mx, std::vector<float>& my);
 
 }  // namespace capi

@@ -26,6 +26,7 @@
 // and hands out what the render reads (keyframes_render_hooks, keyframes_check_tracked).
 // And the joint ADJUSTMENT of a map (keyframe_adjust_dev.h) lives in capi_keyframe_adjust.hip in the same way: the store holds its pointer,
 // frees it, and hands out the map, the states and the alignment's scratch (keyframes_adjust_hooks).
+// And the LOCALISE against the rendered map (keyframe_localise_dev.h) lives in capi_keyframe_localise.hip in the same way (keyframes_localise_hooks).
 // The four tracks - the two sessions calls and the in-step track with and without recovery - share ONE launch sequence (enqueue_track), as
 // the relocalisations do: what each reads and writes is its RelocTargets, the recovering part its KeyRecovery.  The host table of a track has one
 // filler (keyframes_table) and the accepted in-step attempt one commit (keyframes_instep_commit).
@@ -35,6 +36,7 @@
 #include "filters_keyframe_dev.h"
 #include "keyframe_render_dev.h"
 #include "keyframe_adjust_dev.h"
+#include "keyframe_localise_dev.h"
 
 using namespace hnet;
 using namespace capi;
@@ -123,6 +125,7 @@ struct hnet_keyframes {
     KeyInstepWork* instep = nullptr;           // the in-step recovery's working copies or null: no filter ever turned it on
     KeyRender* render = nullptr;               // the render's buffers (capi_keyframe_render.hip) or null: hnet_sessions_enable_keyframe_render was never called
     KeyAdjust* adjust = nullptr;               // the adjustment's buffers (capi_keyframe_adjust.hip) or null: hnet_sessions_enable_keyframe_adjust was never called
+    KeyLocalise* localise = nullptr;           // the localise's buffers (capi_keyframe_localise.hip) or null: hnet_sessions_enable_keyframe_localise was never called
     uint8_t* key = nullptr;                    // device [N][NPIX], zeroed at enable
     KeyState* state = nullptr;                 // device [N], zeroed at enable (has_key = 0)
     uint8_t* scratch = nullptr;                // device: the sections of KeyScratch
@@ -288,6 +291,7 @@ void keyframes_free(hnet_keyframes* k) {
     instep_free(k->instep);
     keyframes_render_free(k->render);
     keyframes_adjust_free(k->adjust);
+    keyframes_localise_free(k->localise);
     map_free(k->map);
     reloc_free(k->reloc);
     fine_free(k->fine);
@@ -616,6 +620,21 @@ bool keyframes_adjust_hooks(hnet_sessions* s, KeyAdjustHooks* h) {
     h->src = AdjustSource{m.img, m.entry, k->state, m.state, m.n_sessions, m.capacity};
     h->align = AdjustAlign{w.rec, w.start, w.work, w.part, w.x0};
     h->adjust = &k->adjust;
+    h->ms = &k->ms;
+    return true;
+}
+
+bool keyframes_localise_hooks(hnet_sessions* s, KeyLocaliseHooks* h) {
+    hnet_keyframes* k = s->kf;
+    if (!k || !k->map) return false;
+    const MapStore& m = k->map->dev;
+    const KeyScratch w(k->scratch, s->ctx->cfg.max_batch);
+    h->src = RenderSource{m.img, m.entry, k->state, m.n_sessions, m.capacity};
+    h->state = k->state;
+    h->mstate = m.state;
+    h->entry = m.entry;
+    h->align = AdjustAlign{w.rec, w.start, w.work, w.part, w.x0};
+    h->localise = &k->localise;
     h->ms = &k->ms;
     return true;
 }

@@ -1,8 +1,9 @@
 // capi_photo_align.hip — the photometric alignment of include/hnet.h on host frames, in its two forms: hnet_photo_align_* / hnet_op_photo_align[_pyramid]
-//  and hnet_photo_robust_* / hnet_op_photo_align_robust (gain / bias model and Huber weights).  The kernels and the launch
-// sequence are kernels_photo_align.hip's.  The sessions forms (capi_sessions.hip) run on photo_align_run below.
+//  and hnet_photo_robust_* / hnet_op_photo_align_robust (gain / bias model and Huber weights), the latter also on the template pixels a mask
+// admits (hnet_op_photo_align_masked).  The kernels and the launch sequence are kernels_photo_align.hip's and kernels_photo_masked.hip's.  The sessions forms (capi_sessions.hip) run on photo_align_run below.
 #include "capi_internal.h"
 #include "filters_refine_dev.h"
+#include "photo_masked_dev.h"
 
 using namespace hnet;
 using namespace capi;
@@ -26,9 +27,9 @@ namespace {
 // The run of both forms on n pairs resident on the device: the scratch (n_start elements of start), the launch sequence between the ev_align events, ONE
 // download and one synchronisation.  levels_out is transposed on the host: the device keeps the records [levels][n], a level's records being what its solve
 // launches write.
-template <class Opts, class Start, class Sums, class Work, class Rec, class PubOpts, class PubRec>
-int run(hnet_ctx* c, const uint8_t* d_img1, const uint8_t* d_img2, int n, const float* d_x0, const PubOpts& opts, int levels, size_t n_start,
-        hipError_t (*launch)(const uint8_t*, const uint8_t*, int, const float*, const Opts&, int, uint8_t*, uint8_t*, Start*, Sums*, Work*, Rec*, hipStream_t),
+// launch: (img1, img2, n, x0, const Opts&, levels, pyr1, pyr2, Start*, Sums*, Work*, Rec*, stream) -> hipError_t.
+template <class Opts, class Start, class Sums, class Work, class Rec, class PubOpts, class PubRec, class Launch>
+int run(hnet_ctx* c, const uint8_t* d_img1, const uint8_t* d_img2, int n, const float* d_x0, const PubOpts& opts, int levels, size_t n_start, const Launch& launch,
         PubRec* out, PubRec* levels_out) {
     static_assert(sizeof(Opts) == sizeof(PubOpts) && sizeof(Rec) == sizeof(PubRec), "the public layouts");
     Opts o;
@@ -109,11 +110,26 @@ int photo_robust_check_opts(hnet_ctx* c, const hnet_photo_robust_opts* opts, con
 // the plain form needs a start array only below the coarsest level: levels = 1 is {accumulate, solve} pairs at d_x0 and nothing else
 int photo_align_run(hnet_ctx* c, const uint8_t* d_img1, const uint8_t* d_img2, int n, const float* d_x0, const hnet_photo_align_opts& opts, int levels,
                     hnet_photo_align* out, hnet_photo_align* levels_out) {
-    return run(c, d_img1, d_img2, n, d_x0, opts, levels, levels > 1 ? (size_t)n * 8 : 0, launch_photo_align_pyramid, out, levels_out);
+    return run<AlignOpts, float, AlignSums, AlignWork, AlignRec>(c, d_img1, d_img2, n, d_x0, opts, levels, levels > 1 ? (size_t)n * 8 : 0, launch_photo_align_pyramid, out,
+                                                                 levels_out);
 }
 int photo_align_run(hnet_ctx* c, const uint8_t* d_img1, const uint8_t* d_img2, int n, const float* d_x0, const hnet_photo_robust_opts& opts, int levels,
                     hnet_photo_robust* out, hnet_photo_robust* levels_out) {
-    return run(c, d_img1, d_img2, n, d_x0, opts, levels, (size_t)n, launch_photo_align_robust, out, levels_out);
+    return run<RobustOpts, RobustStart, RobustSums, RobustWork, RobustRec>(c, d_img1, d_img2, n, d_x0, opts, levels, (size_t)n, launch_photo_align_robust, out, levels_out);
+}
+// the robust form on the template pixels d_mask1 admits: the mask pyramid and its counts are temporaries of the call
+int photo_align_masked_run(hnet_ctx* c, const uint8_t* d_img1, const uint8_t* d_mask1, const uint8_t* d_img2, int n, const float* d_x0,
+                           const hnet_photo_robust_opts& opts, int levels, hnet_photo_robust* out, hnet_photo_robust* levels_out) {
+    DevTemps t;
+    uint8_t* d_mpyr = nullptr;
+    int32_t* d_n_mask = nullptr;
+    HIPCHK(c, t.alloc(&d_mpyr, (size_t)n * PYR_BYTES));
+    HIPCHK(c, t.alloc(&d_n_mask, (size_t)n * N_MASK));
+    const auto launch = [=](const uint8_t* img1, const uint8_t* img2, int n_, const float* x0, const RobustOpts& o, int levels_, uint8_t* pyr1, uint8_t* pyr2,
+                            RobustStart* start, RobustSums* part, RobustWork* work, RobustRec* rec, hipStream_t s) {
+        return launch_photo_align_masked(img1, d_mask1, img2, n_, x0, o, levels_, pyr1, pyr2, d_mpyr, d_n_mask, start, part, work, rec, s);
+    };
+    return run<RobustOpts, RobustStart, RobustSums, RobustWork, RobustRec>(c, d_img1, d_img2, n, d_x0, opts, levels, (size_t)n, launch, out, levels_out);
 }
 
 }  // namespace capi
@@ -149,6 +165,30 @@ int hnet_op_photo_align_pyramid(hnet_ctx* c, const uint8_t* img1, const uint8_t*
 int hnet_op_photo_align_robust(hnet_ctx* c, const uint8_t* img1, const uint8_t* img2, int n, const float* offsets0_px, const hnet_photo_robust_opts* opts, int levels,
                                hnet_photo_robust* out, hnet_photo_robust* levels_out) {
     return op_photo_align(c, img1, img2, n, offsets0_px, opts, photo_robust_check_opts, levels, out, levels_out, "hnet_op_photo_align_robust");
+}
+
+// the same with a mask beside img1: ONE upload {img1 | mask1 | img2 | offsets}
+int hnet_op_photo_align_masked(hnet_ctx* c, const uint8_t* img1, const uint8_t* mask1, const uint8_t* img2, int n, const float* offsets0_px,
+                               const hnet_photo_robust_opts* opts, int levels, hnet_photo_robust* out, hnet_photo_robust* levels_out) {
+    const char* who = "hnet_op_photo_align_masked";
+    if (!c) return HNET_ERR_INVALID_ARG;
+    if (!img1 || !mask1 || !img2 || !offsets0_px || !out || n < 1) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": frames / mask / offsets / out, n >= 1");
+    if (levels < 1 || levels > HNET_ALIGN_MAX_LEVELS) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": 1 <= levels <= 4");
+    const int rc = photo_robust_check_opts(c, opts, who);
+    if (rc != HNET_OK) return rc;
+    if (n > c->cfg.max_batch) return fail(c, HNET_ERR_CAPACITY, std::string(who) + ": n exceeds max_batch");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    const size_t img = (size_t)n * NPIX, off_bytes = (size_t)n * 8 * sizeof(float), up = 3 * img + off_bytes;      // (NPIX is a multiple of 16: every section stays aligned)
+    DevTemps t;
+    uint8_t* d_in = nullptr;
+    HIPCHK(c, t.alloc(&d_in, up));
+    std::vector<uint8_t> h_in(up);
+    memcpy(h_in.data(), img1, img);
+    memcpy(h_in.data() + img, mask1, img);
+    memcpy(h_in.data() + 2 * img, img2, img);
+    memcpy(h_in.data() + 3 * img, offsets0_px, off_bytes);
+    HIPCHK(c, hipMemcpyAsync(d_in, h_in.data(), up, hipMemcpyHostToDevice, c->stream));
+    return photo_align_masked_run(c, d_in, d_in + img, d_in + 2 * img, n, reinterpret_cast<const float*>(d_in + 3 * img), *opts, levels, out, levels_out);
 }
 
 // the Schur complement of the brightness block: info8 = A_xx - A_xc A_cc^-1 A_cx, grad8 = g_x - A_xc A_cc^-1 g_c (include/hnet_photo_refine.h marginal)

@@ -5,6 +5,7 @@
 // (cuahn_ros/homography_network/src/HomographyNet.cpp) without libtorch: weights come from an HNETW001
 // blob, the forward is a fixed sequence of HIP kernel launches on one stream over persistent buffers.
 #include "capi_internal.h"
+#include "photo_masked_dev.h"
 
 using namespace hnet;
 using namespace capi;
@@ -169,6 +170,7 @@ int create_impl(const hnet_config* cfg_in, const uint8_t* blob, size_t len, hnet
     CK(chain_init_device());
     CK(photo_init_device());
     CK(photo_align_init_device());
+    CK(photo_masked_init_device());
     if (preset_stream) { c->stream = preset_stream; c->owns_stream = false; }      // a group member: the group created its streams first, each on a priority level / hardware queue of its own
     else CK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     CK(hipEventCreate(&c->ev0));

@@ -19,9 +19,10 @@
 //
 // The start of a level is where the level above ended, whatever its flags: a gather kernel copies it, as bits (a NaN keeps its payload), from the records
 // into the contiguous array the accumulate and solve kernels read.  Levels and iterations are separate launches; nothing waits on another workgroup, and a
-// stopped pair's workgroups return at once (a workgroup-uniform branch).  pa_run_levels is the one launch sequence of both forms.
-#include "photo_robust_dev.h"
-#include "warp_dev.h"
+// stopped pair's workgroups return at once (a workgroup-uniform branch).  pa_run_levels is the one launch sequence of both forms, and of a third: the
+// robust form on the template pixels a mask admits (MaskedForm), whose accumulate kernels and mask pyramid are kernels_photo_masked.hip's.
+#include "photo_masked_dev.h"
+#include "photo_robust_kernel_dev.h"
 
 namespace hnet {
 
@@ -38,45 +39,7 @@ static_assert(offsetof(AlignSums, sr) == pa::NSYM * 8 && offsetof(AlignSums, rr)
 constexpr int PA_LDS_BYTES = NPIX + PA_WAVES * PA_ND * 8 + PA_WAVES * 4 + 9 * 4 + 4;      // 73 496: two workgroups per CU
 static_assert(NPIX % 16 == 0 && 2 * PA_LDS_BYTES <= 160 * 1024, "aligned sections; two workgroups share a CU's LDS");
 constexpr int pl_threads(int L) { return L == 1 ? 256 : (L == 2 ? 128 : 64); }  // plain, levels 1 - 3: 10, 5 and 2.5 pixels per thread and slice
-constexpr int PR_ND = pr::ND;                                                    // 78
-constexpr int pr_threads(int L) { return L <= 1 ? 256 : (L == 2 ? 128 : 64); }
-// dynamic LDS of the accumulate kernel: img2 of the level | per-wave sums [waves][78] f64 | per-wave counts [waves][2] i32 | H [9], Gf, bf, kf f32
-constexpr int pr_lds_bytes(int L) { return pa::level_pix(L) + (pr_threads(L) / 64) * (PR_ND * 8 + 8) + 12 * 4; }
-static_assert(2 * pr_lds_bytes(0) <= 160 * 1024, "two level-0 workgroups share a CU's LDS");
-static_assert(offsetof(RobustSums, tr) == pr::NSYM_T * 8 && offsetof(RobustSums, rho) == (pr::NSYM_T + pr::NT) * 8 && offsetof(RobustSums, n_valid) == PR_ND * 8 &&
-              offsetof(RobustSums, n_outliers) == PR_ND * 8 + 4, "RobustSums is 78 doubles, then the two counts");
-
-// one pixel (u, v) of level L into the thread's accumulators; i1: the level-L img1 pixel as u8 / 255
-template <int L>
-__device__ __forceinline__ void pr_pixel(const float* h, float Gf, float bf, float kf, const uint8_t* tile, int u, int v, float i1, double (&acc)[PR_ND],
-                                         int& n_valid, int& n_out) {
-    constexpr int W = pa::level_w(L);
-    const float fu = pa::level_centre(L, u), fv = pa::level_centre(L, v);
-    float ix0, iy0, Z, ix, iy;
-    pa::level_coords(h, fu, fv, WarpDiv{}, ix0, iy0, Z);
-    if (!pa::level_position(L, ix0, iy0, ix, iy)) return;                    // (false for NaN)
-    const uint8_t* p = tile + (int)floorf(iy) * W + (int)floorf(ix);
-    const float a = PixRead<uint8_t>::cvt(p[0]), b = PixRead<uint8_t>::cvt(p[1]), c = PixRead<uint8_t>::cvt(p[W]), d = PixRead<uint8_t>::cvt(p[W + 1]);
-    float r0, s[pa::NH];
-    pa::level_row(L, a, b, c, d, i1, ix, iy, ix0, iy0, Z, fu, fv, r0, s);
-    const float w = pr::sample(a, b, c, d, ix, iy);
-    float r, omega, t[pr::NT], tw[pr::NT];
-    double rho;
-    n_out += pr::residual(Gf, bf, kf, w, i1, r, omega, rho) ? 1 : 0;
-    pr::weighted_row(s, w, omega, t, tw);
-    double td[pr::NT], twd[pr::NT];
-#pragma unroll
-    for (int k = 0; k < pr::NT; k++) { td[k] = (double)t[k]; twd[k] = (double)tw[k]; }
-    const double rd = (double)r;
-#pragma unroll
-    for (int k = 0; k < pr::NT; k++) {
-#pragma unroll
-        for (int j = k; j < pr::NT; j++) acc[pr::sym_index(k, j)] += twd[k] * td[j];
-        acc[pr::NSYM_T + k] += twd[k] * rd;
-    }
-    acc[pr::NSYM_T + pr::NT] += rho;
-    n_valid++;
-}
+// (the robust kernel's threads, LDS layout and pr_pixel: photo_robust_kernel_dev.h, shared with kernels_photo_masked.hip)
 
 // The front of both solve kernels, over the 64 lanes of the workgroup: the ND sums and the two count words of the pair's 7 partials added in slice order,
 // the degenerate test of the linearisation point x, and D column by column; then a barrier.  The arrays are the calling kernel's own __shared__ arrays (an
@@ -492,6 +455,27 @@ struct RobustForm {
     }
 };
 
+// The robust form on the template pixels a mask admits: RobustForm's gather and solve, the accumulate launches of kernels_photo_masked.hip.
+// The mask, its pyramid and its counts travel in the options, which the driver hands to every launch.
+struct MaskedOpts { RobustOpts r; const uint8_t* mask0; const uint8_t* mpyr; const int32_t* n_mask; };
+struct MaskedForm {
+    using Opts = MaskedOpts; using Start = RobustStart; using Sums = RobustSums; using Work = RobustWork; using Rec = RobustRec;
+    template <class O> static auto& base(O& o) { return o.r.base; }
+    static const Start* gather(const Rec* above, const float* x0, const Opts& o, Start* start, int n, hipStream_t s) {
+        return RobustForm::gather(above, x0, o.r, start, n, s);
+    }
+    template <int L>
+    static void accumulate(const uint8_t* img1, const uint8_t* img2, const uint8_t* pyr1, const uint8_t* pyr2, int n, const Start* start, const Opts& o,
+                           const Work* work, const Rec* rec, Sums* partial, hipStream_t s) {
+        launch_photo_masked_accum(L, L == 0 ? img1 : pyr1 + pa::level_offset(L), L == 0 ? img2 : pyr2 + pa::level_offset(L),
+                                  L == 0 ? o.mask0 : o.mpyr + pa::level_offset(L), o.n_mask, L == 0 ? NPIX : PYR_BYTES, n, pr::huber_f(o.r.huber_k), start, work,
+                                  rec, partial, s);
+    }
+    static void solve(const Sums* partial, const Start* start, int it, const Opts& o, int n, Work* work, Rec* rec, hipStream_t s) {
+        RobustForm::solve(partial, start, it, o.r, n, work, rec, s);
+    }
+};
+
 // one level: max_iterations + 1 pairs of {accumulate, solve}
 template <int L, class F>
 hipError_t pa_run_level(const uint8_t* img1, const uint8_t* img2, const uint8_t* pyr1, const uint8_t* pyr2, int n, const typename F::Start* start,
@@ -551,6 +535,15 @@ hipError_t launch_photo_align_robust(const uint8_t* img1, const uint8_t* img2, i
                                      uint8_t* pyr2, RobustStart* start, RobustSums* partial, RobustWork* work, RobustRec* rec, hipStream_t s) {
     if (!start || !pr::opts_valid(opts)) return hipErrorInvalidValue;
     return pa_run_levels<RobustForm>(img1, img2, n, x0, opts, levels, pyr1, pyr2, start, partial, work, rec, s);
+}
+
+hipError_t launch_photo_align_masked(const uint8_t* img1, const uint8_t* mask1, const uint8_t* img2, int n, const float* x0, const RobustOpts& opts, int levels,
+                                     uint8_t* pyr1, uint8_t* pyr2, uint8_t* mpyr, int32_t* n_mask, RobustStart* start, RobustSums* partial, RobustWork* work,
+                                     RobustRec* rec, hipStream_t s) {
+    if (!start || !pr::opts_valid(opts)) return hipErrorInvalidValue;
+    const hipError_t e = launch_photo_mask_pyramid(mask1, n, mpyr, n_mask, s);
+    if (e != hipSuccess) return e;
+    return pa_run_levels<MaskedForm>(img1, img2, n, x0, MaskedOpts{opts, mask1, mpyr, n_mask}, levels, pyr1, pyr2, start, partial, work, rec, s);
 }
 
 }  // namespace hnet

@@ -311,6 +311,23 @@ class HnetEngine:
                                                           out.ctypes.data, lv.ctypes.data if want_levels else None))
         return (out, lv) if want_levels else out
 
+    def op_photo_align_masked(self, img1, mask1, img2, offsets0, levels=4, want_levels=False, **opts):
+        """op_photo_align_robust on the template pixels a mask admits (hnet_op_photo_align_masked): mask1 uint8 [n, 224, 320] beside img1, non-zero = the
+        pixel takes part; a mask without a zero byte gives op_photo_align_robust's records byte for byte"""
+        a = np.ascontiguousarray(img1, dtype=np.uint8).reshape(-1, IMG_H, IMG_W)
+        m = np.ascontiguousarray(mask1, dtype=np.uint8).reshape(-1, IMG_H, IMG_W)
+        b = np.ascontiguousarray(img2, dtype=np.uint8).reshape(-1, IMG_H, IMG_W)
+        n = a.shape[0]
+        if b.shape[0] != n or m.shape[0] != n:
+            raise ValueError("img1, mask1 and img2 must hold the same number of frames")
+        off = np.ascontiguousarray(offsets0, dtype=np.float32).reshape(n, 8)
+        o = _capi.photo_robust_opts(**opts)
+        out = np.zeros(n, _capi.PHOTO_ROBUST_DTYPE)
+        lv = np.zeros((n, max(int(levels), 1)), _capi.PHOTO_ROBUST_DTYPE) if want_levels else None
+        check(self._h, self._L.hnet_op_photo_align_masked(self._h, a.ctypes.data, m.ctypes.data, b.ctypes.data, n, off.ctypes.data, C.addressof(o), int(levels),
+                                                          out.ctypes.data, lv.ctypes.data if want_levels else None))
+        return (out, lv) if want_levels else out
+
     def op_photo_search(self, img1, img2, want_scores=False, **opts):
         """coarse search over integer translations between the 40 x 28 thumbnails of uint8 frames [n, 224, 320] (hnet_op_photo_search): a start for the
         alignments from up to 240 x 160 px away; opts as _capi.photo_search_opts -> records [n] of _capi.PHOTO_SEARCH_DTYPE; want_scores: (those, the
@@ -342,6 +359,23 @@ class HnetEngine:
         check(self._h, self._L.hnet_op_keyframe_render(self._h, len(ent), img.ctypes.data, ent.ctypes.data, hv.ctypes.data, C.addressof(o), out.ctypes.data,
                                                        cover.ctypes.data, rec.ctypes.data))
         return out, cover, rec
+
+    def op_keyframe_localise(self, images, entries, h_origin_pred, curr, want_images=False, **opts):
+        """a camera localised against its rendered keyframe map (hnet_op_keyframe_localise): m (1 .. 8) stored keyframes [m, 224, 320] uint8 with their
+        entries [m], the view h_origin_pred [3, 3] the chain predicts for the current frame and that frame curr [224, 320] -> record [1] of
+        _capi.KEYFRAME_LOCALISE_DTYPE; want_images: (that, template [224, 320], cover [224, 320]); opts as _capi.keyframe_localise_opts"""
+        img = np.ascontiguousarray(images, dtype=np.uint8).reshape(-1, IMG_H, IMG_W)
+        ent = np.ascontiguousarray(entries, dtype=_capi.KEYFRAME_MAP_ENTRY_DTYPE).reshape(-1)
+        if len(ent) != img.shape[0]:
+            raise ValueError("images and entries must hold the same number of keyframes")
+        hv = np.ascontiguousarray(h_origin_pred, dtype=np.float64).reshape(9)
+        cur = np.ascontiguousarray(curr, dtype=np.uint8).reshape(IMG_H, IMG_W)
+        o = _capi.keyframe_localise_opts(**opts)
+        out = np.zeros(1, _capi.KEYFRAME_LOCALISE_DTYPE)
+        tmpl, cover = np.zeros((IMG_H, IMG_W), np.uint8), np.zeros((IMG_H, IMG_W), np.uint8)
+        check(self._h, self._L.hnet_op_keyframe_localise(self._h, len(ent), img.ctypes.data, ent.ctypes.data, hv.ctypes.data, cur.ctypes.data, C.addressof(o),
+                                                         out.ctypes.data, tmpl.ctypes.data if want_images else None, cover.ctypes.data if want_images else None))
+        return (out, tmpl, cover) if want_images else out
 
     def op_keyframe_adjust_solve(self, entries, edges, edge_infos=None, **opts):
         """the solve of a keyframe map's joint adjustment alone (hnet_op_keyframe_adjust_solve): entries [m] (1 .. 8) of _capi.KEYFRAME_MAP_ENTRY_DTYPE,
@@ -813,6 +847,19 @@ class HnetSessions:
         self._check(self._L.hnet_sessions_keyframe_render(self._s, n, ids.ctypes.data, hv.ctypes.data if hv is not None else None, C.addressof(o),
                                                           out.ctypes.data, cover.ctypes.data, rec.ctypes.data))
         return out, cover, rec
+
+    def enable_keyframe_localise(self):
+        """hnet_sessions_enable_keyframe_localise: allocates the localise's templates, masks, tables and records; once, after enable_keyframe_map"""
+        self._check(self._L.hnet_sessions_enable_keyframe_localise(self._s))
+
+    def keyframe_localise(self, ids, **opts):
+        """hnet_sessions_keyframe_localise: each listed session's current frame localised against its rendered keyframe map -> records [n] of
+        _capi.KEYFRAME_LOCALISE_DTYPE; apply=1 corrects the chain of a LOCALISED session; opts as _capi.keyframe_localise_opts"""
+        ids, n = self._ids(ids)
+        o = _capi.keyframe_localise_opts(**opts)
+        out = np.zeros(n, _capi.KEYFRAME_LOCALISE_DTYPE)
+        self._check(self._L.hnet_sessions_keyframe_localise(self._s, n, ids.ctypes.data, C.addressof(o), out.ctypes.data))
+        return out
 
     def enable_keyframe_adjust(self):
         """hnet_sessions_enable_keyframe_adjust: allocates the adjustment's tables, records and pinned blocks; once, after enable_keyframe_map"""

@@ -692,6 +692,16 @@ int  hnet_op_photo_align_robust(hnet_ctx* ctx, const uint8_t* img1, const uint8_
 /* the same on the current pair of each listed session; read-only like hnet_sessions_photo_align_pyramid */
 int  hnet_sessions_photo_align_robust(hnet_sessions* s, int n, const int32_t* ids, const float* offsets0_px, const hnet_photo_robust_opts* opts, int levels,
                                       hnet_photo_robust* out, hnet_photo_robust* levels_out);
+/* hnet_op_photo_align_robust on the template pixels a mask admits (include/hnet_photo_masked.h).  mask1: u8 [n][224][320] beside img1;
+ * non-zero: the pixel takes part.  Level L of the mask is 1 where all 4^L level-0 bytes under a pixel are non-zero (an AND), so a coarse template pixel whose
+ * box mean mixes admitted and refused bytes is never used.  A refused pixel adds nothing to any sum, to n_valid or to n_outliers; img1 under it is never
+ * read into a sum.  Options, levels, the per-level min_valid (NOT scaled by the mask: a mask that admits too little stops HNET_ALIGN_FEW_PIXELS), records and
+ * flags are the robust call's; a mask without a zero byte gives its records byte for byte.  Errors are those of hnet_op_photo_align_robust, and
+ * HNET_ERR_INVALID_ARG for a null mask.  One upload {img1 | mask1 | img2 | offsets}, the mask pyramid and the launch sequence, one download, one
+ * synchronisation; hnet_last_photo_align_device_ms covers the mask pyramid and the sequence. */
+int  hnet_op_photo_align_masked(hnet_ctx* ctx, const uint8_t* img1, const uint8_t* mask1, const uint8_t* img2, int n, const float* offsets0_px,
+                                const hnet_photo_robust_opts* opts, int levels, hnet_photo_robust* out /* [n] */,
+                                hnet_photo_robust* levels_out /* NULL or [n][levels], index = level */);
 /* host only: the information matrix and gradient of the offsets with gain and bias marginalised (the Schur complement of the 2 x 2 brightness block of
  * info10): what a filter may use when brightness is a nuisance.  With the model off (rows 8, 9 of info10 all zero) it copies px.info / px.grad.
  * HNET_ERR_INVALID_ARG, nothing written, for a null argument or when the 2 x 2 block has no Cholesky factor. */
@@ -1286,6 +1296,61 @@ int  hnet_sessions_enable_keyframe_render(hnet_sessions* s, int max_width, int m
  * track saw. */
 int  hnet_sessions_keyframe_render(hnet_sessions* s, int n, const int32_t* ids, const double* h_origin_view, const hnet_keyframe_render_opts* opts,
                                    uint8_t* out_img, uint8_t* out_cover, hnet_keyframe_render_rec* out);
+
+/* ---- a camera LOCALISED against its rendered keyframe map (csrc/kernels_keyframe_localise.hip; the shared code is include/hnet_keyframe_localise.h;
+ * DESIGN 7ae).  A revisit measures against ONE stored keyframe and needs most of it in view; a camera between stored keyframes sees ground the map knows
+ * and gets HNET_RV_NO_CANDIDATE.  The localise renders the entries into the view the chain predicts for the current frame (320 x 224, `mode`), takes the
+ * cover image as the mask of hnet_op_photo_align_masked's alignment composite -> current frame from zero offsets, and judges the record: one flag, tested
+ * in the order of the enum.  On HNET_LOC_LOCALISED h_origin_curr = H(offsets) . h_origin_before and correction_px = the corners of h_origin_curr minus those
+ * of h_origin_before; otherwise h_origin_curr = h_origin_before and correction_px = 0.  When no entry took part or the cover is below min_cover nothing is
+ * aligned (the start is quiet NaNs, the alignment returns at once) and `rec` is zero.  The defaults are choices, not measurements. */
+enum { HNET_LOC_NO_MAP = 1,            /* no entry took part in the template */
+       HNET_LOC_LOW_COVER = 2,         /* n_covered / 71 680 < min_cover */
+       HNET_LOC_STOPPED = 4,           /* the record stopped SINGULAR, DEGENERATE or FEW_PIXELS */
+       HNET_LOC_MSE_ABOVE_MAX = 8,     /* max_mse > 0 and not mse <= max_mse */
+       HNET_LOC_NON_FINITE = 16,       /* an offset of the record is not finite */
+       HNET_LOC_LOW_OVERLAP = 32,      /* n_valid / 71 680 < min_overlap */
+       HNET_LOC_SHIFT_ABOVE_MAX = 64,  /* max_shift_px > 0 and the worst |offset| exceeds it */
+       HNET_LOC_CHAIN = 128,           /* H(offsets) . h_origin_before is degenerate */
+       HNET_LOC_LOCALISED = 256 };
+typedef struct hnet_keyframe_localise_opts {
+    hnet_photo_robust_opts align;
+    int32_t levels, mode;              /* 1 .. 4 (3); HNET_RENDER_* (FEWEST_LINKS) */
+    double  min_cover, min_overlap;    /* fractions of the frame (0.5, 0.4) */
+    double  max_mse, max_shift_px;     /* 0 = no limit (0, 0) */
+    int32_t apply, pad;                /* 0 / 1: hnet_sessions_keyframe_localise corrects the chain; the operator-level call has no state and ignores it */
+} hnet_keyframe_localise_opts;
+typedef struct hnet_keyframe_localise {
+    hnet_photo_robust rec;             /* level 0 of the masked alignment, byte for byte hnet_op_photo_align_masked(template, cover, curr, 0) */
+    double  h_origin_before[9], h_origin_curr[9], correction_px[8];
+    double  cover, overlap;            /* n_covered and n_valid over 71 680 */
+    int32_t used_mask, links_before, links, flags, pad[2];      /* links: 1 + the largest links in used_mask when localised */
+} hnet_keyframe_localise;
+void hnet_keyframe_localise_default_opts(hnet_keyframe_localise_opts* o);
+/* Operator level: m (1 .. 8) caller-supplied images [m][224][320] and entries [m] (every valid entry is eligible), the predicted view h_origin_pred [9]
+ * and the current frame curr [224][320]; no session is involved.  out_template / out_cover: NULL or [224][320], byte for byte hnet_op_keyframe_render's for
+ * the same view, entries and mode.  ONE upload, the launch sequence {render setup, render, start, mask pyramid + masked alignment, decide}, ONE download,
+ * one synchronisation.  HNET_ERR_INVALID_ARG, nothing written: a null argument but the last two, m outside 1 .. 8, options hnet_op_photo_align_robust
+ * would refuse, levels outside 1 .. 4, a mode outside the three, min_cover or min_overlap outside 0 .. 1, a negative or non-finite max_mse or
+ * max_shift_px, apply outside 0 / 1, a non-finite entry of h_origin_pred. */
+int  hnet_op_keyframe_localise(hnet_ctx* ctx, int m, const uint8_t* images, const hnet_keyframe_map_entry* entries, const double* h_origin_pred /* [9] */,
+                               const uint8_t* curr, const hnet_keyframe_localise_opts* opts, hnet_keyframe_localise* out, uint8_t* out_template,
+                               uint8_t* out_cover);
+/* once, after hnet_sessions_enable_keyframe_map (the render need not be enabled): templates, cover images, mask pyramids, tables and records of max_batch
+ * slots, pinned blocks and events of its own.  A sessions object that never calls it allocates, launches and returns what it did.
+ * HNET_ERR_INVALID_ARG: before the map, a second call. */
+int  hnet_sessions_enable_keyframe_localise(hnet_sessions* s);
+/* The listed sessions, each against its own map.  Eligible are the valid entries with slot != cur_slot and links < cur_links (the revisit's preference);
+ * the view is the session's current frame as its origin chain predicts it (h_origin_curr of its last track) and the current frame its latest image.
+ * links_before = cur_links.  With opts->apply = 1 a LOCALISED session's chain is corrected on the device: key_px stays,
+ * h_origin_key <- inverse(H(key_px)) . h_origin_curr (HNET_LOC_CHAIN, nothing changed, if that product is degenerate), the map entry of cur_slot follows
+ * when cur_slot >= 0, and cur_links and that entry's links become the record's links (1 + the largest links that took part: never more than before).  Age,
+ * keyframe count, images, cursor and serial stay; the next track continues from the corrected chain.  A rejected call, apply = 0 and every unlisted session
+ * change no byte of any state.  ONE upload {ids | current ring slots}, the launch sequence {render setup, eligible, render, gather + start, mask pyramid +
+ * masked alignment, decide} on the context's staging and the store's alignment scratch, ONE download of out [n], one synchronisation;
+ * hnet_sessions_last_keyframe_device_ms covers it.  Every id and ring slot is checked again on the device.  Refused before anything is enqueued, nothing
+ * changed: everything hnet_sessions_keyframe_revisit refuses (with these options' rules for its own), and a call before the enable. */
+int  hnet_sessions_keyframe_localise(hnet_sessions* s, int n, const int32_t* ids, const hnet_keyframe_localise_opts* opts, hnet_keyframe_localise* out /* [n] */);
 
 /* ---- a keyframe map ADJUSTED jointly, on the device (csrc/kernels_keyframe_adjust.hip; the shared code is include/hnet_keyframe_adjust.h).
  * A revisit re-attaches the session to one stored keyframe; every entry stored in between keeps its drifted h_origin_key.  The adjustment re-measures
