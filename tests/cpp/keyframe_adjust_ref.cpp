@@ -42,6 +42,14 @@ void keyframe_adjust_ref_judge(const void* job, const void* rec, const void* opt
 
 int keyframe_adjust_ref_homography_d(const double* d, double* h) { return ka::homography_d(d, h) ? 1 : 0; }
 
+// one edge's residual and one column of its Jacobian, as the solve calls them: G [9], di, dj, z, r and col [8]; which 0: endpoint i, 1: endpoint j
+int keyframe_adjust_ref_edge_residual(const double* G, const double* di, const double* dj, const double* z, double* r) {
+    return ka::edge_residual(G, di, dj, z, r) ? 1 : 0;
+}
+void keyframe_adjust_ref_jacobian_col(const double* G, const double* di, const double* dj, int which, int comp, double* col) {
+    ka::jacobian_col(G, di, dj, which, comp, col);
+}
+
 // the solve alone: entries [m] (rewritten with apply), edges [n_edges], infos null or [n_edges][64] -> the record, every byte written
 void keyframe_adjust_ref_solve(void* entries, int m, int n_edges, const void* edges, const double* infos, const void* opts, void* record) {
     ka::Record& rec = *static_cast<ka::Record*>(record);
