@@ -1293,8 +1293,7 @@ int hnet_filters_set_photo_refine(hnet_filters* f, int id, const hnet_photo_refi
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
     const int N = f->s->n, B = c->cfg.max_batch;
     if (!f->refine) {
-        const size_t pyr = (size_t)B * PYR_BYTES;
-        if (!c->pyr_scratch) HIPCHK(c, dalloc(&c->pyr_scratch, 2 * pyr));
+        if (const int rc = ensure_pyr_scratch(c); rc != HNET_OK) return rc;
         RefineCfg* d_cfg = nullptr;
         HIPCHK(c, dalloc(&d_cfg, (size_t)N));
         hipError_t e = hipMemsetAsync(d_cfg, 0, (size_t)N * sizeof(RefineCfg), c->stream);

@@ -211,17 +211,46 @@ struct Carver {
     }
 };
 
-// Device temporaries of the operator-level entry points: freed on every return path (HIPCHK returns early).
-struct DevTemps {
-    std::vector<void*> ptrs;
+// The owner of device and pinned host memory: its destructor frees what it handed out; a default-constructed one holds nothing.  As a local (DevTemps) it
+// holds the temporaries of an operator-level entry point, freed on every return path (HIPCHK returns early); as a member, the buffers of an object
+// that are sized once and live as long as it does (the keyframe store and its layers, keyframes_internal.h).
+struct DevMem {
+    std::vector<void*> ptrs, pinned;           // device / pinned host
+    DevMem() = default;
+    DevMem(const DevMem&) = delete;
+    DevMem& operator=(const DevMem&) = delete;
     template <typename T>
     hipError_t alloc(T** p, size_t count) {
         const hipError_t e = dalloc(p, count);
         if (e == hipSuccess) ptrs.push_back((void*)*p);
         return e;
     }
-    ~DevTemps() { for (void* q : ptrs) (void)hipFree(q); }
+    template <typename T>
+    hipError_t alloc_pinned(T** p, size_t count) {
+        const hipError_t e = hipHostMalloc((void**)p, count * sizeof(T), hipHostMallocDefault);
+        if (e == hipSuccess) pinned.push_back((void*)*p);
+        return e;
+    }
+    // what `o` owns becomes this owner's (allocate into a local, adopt on success: a failure leaves the object as it was)
+    void adopt(DevMem& o) {
+        for (void* q : o.ptrs) ptrs.push_back(q);
+        for (void* q : o.pinned) pinned.push_back(q);
+        o.ptrs.clear();
+        o.pinned.clear();
+    }
+    ~DevMem() {
+        for (void* q : ptrs) (void)hipFree(q);
+        for (void* q : pinned) (void)hipHostFree(q);
+    }
 };
+using DevTemps = DevMem;
+
+// levels 1 .. 3 of img1 [max_batch] | img2 [max_batch] of a coarse-to-fine alignment (hnet_ctx::pyr_scratch): allocated by the first call that needs them
+inline int ensure_pyr_scratch(hnet_ctx* c) {
+    const size_t pyr = (size_t)c->cfg.max_batch * hnet::PYR_BYTES;
+    if (!c->pyr_scratch) HIPCHK(c, dalloc(&c->pyr_scratch, 2 * pyr));
+    return HNET_OK;
+}
 
 bool parse_blob(const uint8_t* p, size_t len, Blob& out);                                  // capi_weights.hip
 int upload_weights(hnet_ctx* c, const Blob& b);          // weights -> device in the layouts of the context's arithmetic mode

@@ -22,21 +22,18 @@
 // keyframes_instep_* functions below, with the store's own scratch, decide on a copy of the state table and the commits deferred to the accepted attempt.
 // And the RECOVERY inside that in-step track: the launches of hnet_sessions_keyframe_track_recover on working copies of the state table and
 // of the map's entries and states (KeyInstepWork, allocated by hnet_filters_set_keyframe_recover), every image write deferred to the accepted attempt.
-// And the RENDER of a map into a view (keyframe_render_dev.h) lives in capi_keyframe_render.hip: the store only holds its pointer, frees it,
-// and hands out what the render reads (keyframes_render_hooks, keyframes_check_tracked).
-// And the joint ADJUSTMENT of a map (keyframe_adjust_dev.h) lives in capi_keyframe_adjust.hip in the same way: the store holds its pointer,
-// frees it, and hands out the map, the states and the alignment's scratch (keyframes_adjust_hooks).
-// And the LOCALISE against the rendered map (keyframe_localise_dev.h) lives in capi_keyframe_localise.hip in the same way (keyframes_localise_hooks).
+// And the RENDER of a map into a view, its joint ADJUSTMENT and the LOCALISE against the rendered map live in
+// capi_keyframe_render.hip, capi_keyframe_adjust.hip and capi_keyframe_localise.hip: the store owns each as a KeyLayer and they read the store, its map
+// and its alignment scratch directly (keyframes_internal.h, which also holds the frame every sessions call here and there runs in: begin_call, finish_call).
 // The four tracks - the two sessions calls and the in-step track with and without recovery - share ONE launch sequence (enqueue_track), as
 // the relocalisations do: what each reads and writes is its RelocTargets, the recovering part its KeyRecovery.  The host table of a track has one
 // filler (keyframes_table) and the accepted in-step attempt one commit (keyframes_instep_commit).
-#include "sessions_internal.h"
+#include "keyframes_internal.h"
 #include "keyframe_recover_dev.h"
 #include "photo_search_fine_dev.h"
 #include "filters_keyframe_dev.h"
-#include "keyframe_render_dev.h"
-#include "keyframe_adjust_dev.h"
-#include "keyframe_localise_dev.h"
+
+#include <memory>
 
 using namespace hnet;
 using namespace capi;
@@ -90,73 +87,39 @@ static_assert(sizeof(hnet_keyframe_recover) == sizeof(RecoverRec) && offsetof(hn
               sizeof(hnet_keyframe_recover_opts) == sizeof(RecoverOpts) && offsetof(hnet_keyframe_recover_opts, reloc) == offsetof(RecoverOpts, reloc) &&
               (int)HNET_KF_RECOVERED == hnet_keyframe_recovery::RECOVERED, "hnet_keyframe_recover / _opts are the layouts of include/hnet_keyframe_recover.h");
 
-// the scratch of the relocalisation (allocated by the first relocalise, oriented relocalise or track with recovery), for max_batch B and the largest map
-struct KeyReloc {
-    uint8_t* scratch = nullptr;                // device: the sections of RelocScratch
-    uint8_t *pin_in = nullptr, *pin_out = nullptr;     // pinned: the largest call's table and its records [B]
-};
+namespace capi __attribute__((visibility("hidden"))) {
 
-// the scratch of the fine relocalise (allocated by the first hnet_sessions_keyframe_relocalise_fine), for max_batch B
-struct KeyFine {
-    uint8_t* scratch = nullptr;                // device: the sections of FineScratch
-    uint8_t *pin_in = nullptr, *pin_out = nullptr;     // pinned: the call's table and its records [B]
-};
-
-// the map of a store (hnet_sessions_enable_keyframe_map): sized at its enable, for N sessions, M slots each and max_batch B
-struct KeyMap {
-    MapStore dev = {nullptr, nullptr, nullptr, 0, 0};  // device: images [N][M][NPIX], entries [N][M], states [N]; all zeroed at enable
-    uint8_t* scratch = nullptr;                // device: the sections of MapScratch
-    uint8_t *pin_in = nullptr, *pin_out = nullptr;     // pinned: a revisit's table and its records [B]
-    hipEvent_t ev[2] = {nullptr, nullptr};     // around the launch sequence of the last revisit
-};
+// the scratch of the relocalisation (allocated by the first relocalise, oriented relocalise or track with recovery), for max_batch B and the largest
+// map: the sections of RelocScratch, the largest call's table and its records
+struct KeyReloc : KeyBlocks {};
+// the scratch of the fine relocalise (allocated by the first hnet_sessions_keyframe_relocalise_fine), for max_batch B: the sections of FineScratch, the
+// call's table and its records
+struct KeyFine : KeyBlocks {};
 
 // the working copies of an in-step track with recovery: the map's entries [N][M] and states [N]; null without a map.  Allocated by whichever comes
 // second of keyframes_instep_recover_ensure and hnet_sessions_enable_keyframe_map (instep_map_alloc)
 struct KeyInstepWork {
+    DevMem mem;
     MapEntry* entry = nullptr;
     MapState* state = nullptr;
 };
 
-// the store: everything is sized at enable, for the sessions' count N and the context's max_batch B
-struct hnet_keyframes {
-    KeyMap* map = nullptr;                     // the keyframe map or null: never enabled
-    KeyReloc* reloc = nullptr;                 // the relocalisation's scratch or null: none of its calls was ever made
-    KeyFine* fine = nullptr;                   // the fine relocalise's scratch or null: the call was never made
-    KeyInstepWork* instep = nullptr;           // the in-step recovery's working copies or null: no filter ever turned it on
-    KeyRender* render = nullptr;               // the render's buffers (capi_keyframe_render.hip) or null: hnet_sessions_enable_keyframe_render was never called
-    KeyAdjust* adjust = nullptr;               // the adjustment's buffers (capi_keyframe_adjust.hip) or null: hnet_sessions_enable_keyframe_adjust was never called
-    KeyLocalise* localise = nullptr;           // the localise's buffers (capi_keyframe_localise.hip) or null: hnet_sessions_enable_keyframe_localise was never called
-    uint8_t* key = nullptr;                    // device [N][NPIX], zeroed at enable
-    KeyState* state = nullptr;                 // device [N], zeroed at enable (has_key = 0)
-    uint8_t* scratch = nullptr;                // device: the sections of KeyScratch
-    uint8_t *pin_in = nullptr, *pin_out = nullptr;     // pinned: one call's table and its records [B]
-    hipEvent_t ev[2] = {nullptr, nullptr};     // around the launch sequence of the last track: events of its own, every hnet_timing stays as it was
-    double ms = 0.0;
-    // host mirror of what the device state decides deterministically: whether the session holds a keyframe, and its image count at its previous track
-    std::vector<uint8_t> has_key;
-    std::vector<int> count_at_track;
-};
+}  // namespace capi
+
+// (hnet_destroy_sessions has set the device and drained the stream)
+hnet_keyframes::~hnet_keyframes() {
+    delete instep;
+    delete render;
+    delete adjust;
+    delete localise;
+    delete map;
+    delete reloc;
+    delete fine;
+    for (hipEvent_t e : ev)
+        if (e) (void)hipEventDestroy(e);
+}
 
 namespace {
-
-size_t table_bytes(int n) { return (size_t)n * (8 * sizeof(float) + 3 * sizeof(int32_t)); }
-
-// the sections of the scratch for max_batch B: the alignment's, as capi_filters.hip sizes them for 7o, then the call's table, start, records and copy flags
-struct KeyScratch {
-    RobustRec* rec; RobustStart* start; RobustWork* work; RobustSums* part; float* x0; uint8_t* tab; KeyTrack* out; int32_t* copy; size_t bytes;
-    KeyScratch(uint8_t* b, int B) {
-        Carver cv{b};
-        rec = cv.take<RobustRec>((size_t)HNET_ALIGN_MAX_LEVELS * B);
-        start = cv.take<RobustStart>(B);
-        work = cv.take<RobustWork>(B);
-        part = cv.take<RobustSums>((size_t)B * PHOTO_SLICES);
-        x0 = cv.take<float>((size_t)B * 8);
-        tab = cv.take(table_bytes(B));
-        out = cv.take<KeyTrack>(B);
-        copy = cv.take<int32_t>(B);
-        bytes = cv.used;
-    }
-};
 
 // the table of a call of n slots inside a block that holds it
 KeyTable table_view(const uint8_t* b, int n) {
@@ -234,90 +197,19 @@ struct FineScratch {
 // what enqueue_relocalise runs between the gather and the alignment of a fine relocalise
 struct FineStage { const FineScratch* fw; FineOpts fo; const SearchHyp* d_fine; };
 
-void fine_free(KeyFine* f) {
-    if (!f) return;
-    if (f->scratch) (void)hipFree(f->scratch);
-    if (f->pin_in) (void)hipHostFree(f->pin_in);
-    if (f->pin_out) (void)hipHostFree(f->pin_out);
-    delete f;
-}
-
-void reloc_free(KeyReloc* r) {
-    if (!r) return;
-    if (r->scratch) (void)hipFree(r->scratch);
-    if (r->pin_in) (void)hipHostFree(r->pin_in);
-    if (r->pin_out) (void)hipHostFree(r->pin_out);
-    delete r;
-}
-
-void map_free(KeyMap* m) {
-    if (!m) return;
-    if (m->dev.img) (void)hipFree(m->dev.img);
-    if (m->dev.entry) (void)hipFree(m->dev.entry);
-    if (m->dev.state) (void)hipFree(m->dev.state);
-    if (m->scratch) (void)hipFree(m->scratch);
-    if (m->pin_in) (void)hipHostFree(m->pin_in);
-    if (m->pin_out) (void)hipHostFree(m->pin_out);
-    for (hipEvent_t e : m->ev)
-        if (e) (void)hipEventDestroy(e);
-    delete m;
-}
-
-void instep_free(KeyInstepWork* w) {
-    if (!w) return;
-    if (w->entry) (void)hipFree(w->entry);
-    if (w->state) (void)hipFree(w->state);
-    delete w;
-}
-
 // the working copies of the map m for N sessions; on failure w is as it was
 hipError_t instep_map_alloc(KeyInstepWork* w, const KeyMap* m, int N) {
     if (w->entry) return hipSuccess;
+    DevMem got;
     MapEntry* en = nullptr;
     MapState* st = nullptr;
-    hipError_t e = hipMalloc((void**)&en, (size_t)N * m->dev.capacity * sizeof(MapEntry));
-    if (e == hipSuccess) e = hipMalloc((void**)&st, (size_t)N * sizeof(MapState));
-    if (e != hipSuccess) {
-        if (en) (void)hipFree(en);
-        return e;
-    }
+    hipError_t e = got.alloc(&en, (size_t)N * m->dev.capacity);
+    if (e == hipSuccess) e = got.alloc(&st, (size_t)N);
+    if (e != hipSuccess) return e;
+    w->mem.adopt(got);
     w->entry = en;
     w->state = st;
     return hipSuccess;
-}
-
-void keyframes_free(hnet_keyframes* k) {
-    if (!k) return;
-    instep_free(k->instep);
-    keyframes_render_free(k->render);
-    keyframes_adjust_free(k->adjust);
-    keyframes_localise_free(k->localise);
-    map_free(k->map);
-    reloc_free(k->reloc);
-    fine_free(k->fine);
-    if (k->key) (void)hipFree(k->key);
-    if (k->state) (void)hipFree(k->state);
-    if (k->scratch) (void)hipFree(k->scratch);
-    if (k->pin_in) (void)hipHostFree(k->pin_in);
-    if (k->pin_out) (void)hipHostFree(k->pin_out);
-    for (hipEvent_t e : k->ev)
-        if (e) (void)hipEventDestroy(e);
-    delete k;
-}
-
-// every listed session has an image; tracked: and holds a keyframe that its last track took from its latest image
-int check_listed(hnet_sessions* s, int n, const int32_t* ids, const char* who, bool tracked) {
-    hnet_ctx* c = s->ctx;
-    const hnet_keyframes* k = s->kf;
-    for (int i = 0; i < n; i++) {
-        const int id = ids[i];
-        if (s->st[id].count < 1) return fail(c, HNET_ERR_NOT_READY, std::string(who) + ": a listed session has no image");
-        if (!tracked) continue;
-        if (!k->has_key[id]) return fail(c, HNET_ERR_NOT_READY, std::string(who) + ": a listed session holds no keyframe");
-        if (s->st[id].count != k->count_at_track[id])
-            return fail(c, HNET_ERR_NOT_READY, std::string(who) + ": a listed session's latest image is not the one its last track saw (track it first)");
-    }
-    return HNET_OK;
 }
 
 // o <- *opts with its pads zeroed, or the context's error; name: what the caller calls the struct ("opts", "opts.reloc")
@@ -335,36 +227,23 @@ int reloc_check_opts(hnet_ctx* c, const hnet_keyframe_relocalise_opts* opts, con
     return HNET_OK;
 }
 
-// the relocalisation's scratch, allocated by the first call that needs it, before that call enqueues anything
-int reloc_ensure(hnet_ctx* c, hnet_keyframes* k, const char* who) {
-    if (k->reloc) return HNET_OK;
-    const int B = c->cfg.max_batch;
-    KeyReloc* r = new KeyReloc();
-    hipError_t e = hipMalloc((void**)&r->scratch, RelocScratch(nullptr, B).bytes);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&r->pin_in, recover_table_bytes(B, SEARCH_MAX_HYP), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&r->pin_out, (size_t)B * sizeof(RecoverRec), hipHostMallocDefault);
-    if (e != hipSuccess) {
-        reloc_free(r);
-        return fail(c, HNET_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-    }
-    k->reloc = r;
+// a relocalisation's scratch (KeyReloc, KeyFine), allocated by the first call that needs it, before that call enqueues anything
+template <class Blocks>
+int blocks_ensure(hnet_ctx* c, Blocks*& slot, size_t scratch_bytes, size_t in_bytes, size_t out_bytes, const char* who) {
+    if (slot) return HNET_OK;
+    auto b = std::make_unique<Blocks>();
+    const hipError_t e = b->alloc(scratch_bytes, in_bytes, out_bytes);
+    if (e != hipSuccess) return fail(c, HNET_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    slot = b.release();
     return HNET_OK;
 }
-
-// the fine relocalise's scratch, allocated by its first call, before that call enqueues anything
-int fine_ensure(hnet_ctx* c, hnet_keyframes* k, const char* who) {
-    if (k->fine) return HNET_OK;
+int reloc_ensure(hnet_ctx* c, hnet_keyframes* k, const char* who) {
     const int B = c->cfg.max_batch;
-    KeyFine* f = new KeyFine();
-    hipError_t e = hipMalloc((void**)&f->scratch, FineScratch(nullptr, B).bytes);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&f->pin_in, fine_table_bytes(B, SEARCH_MAX_HYP, FINE_MAX), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&f->pin_out, (size_t)B * sizeof(FineRelocRec), hipHostMallocDefault);
-    if (e != hipSuccess) {
-        fine_free(f);
-        return fail(c, HNET_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-    }
-    k->fine = f;
-    return HNET_OK;
+    return blocks_ensure(c, k->reloc, RelocScratch(nullptr, B).bytes, recover_table_bytes(B, SEARCH_MAX_HYP), (size_t)B * sizeof(RecoverRec), who);
+}
+int fine_ensure(hnet_ctx* c, hnet_keyframes* k, const char* who) {
+    const int B = c->cfg.max_batch;
+    return blocks_ensure(c, k->fine, FineScratch(nullptr, B).bytes, fine_table_bytes(B, SEARCH_MAX_HYP, FINE_MAX), (size_t)B * sizeof(FineRelocRec), who);
 }
 
 // what a track or a relocalisation reads and writes besides its scratch: the state table its decisions write, the map whose entries and states its notes
@@ -483,19 +362,6 @@ void table_fill(const hnet_sessions* s, int n, const int32_t* ids, const float* 
     keyframes_table(s, n, ids, nullptr, reinterpret_cast<int32_t*>(h_step + (size_t)8 * n));
 }
 
-// the end of a call whose launches began at ev[0]: the closing event, ONE download of its records, one synchronisation, the device time between the events
-int finish_call(hnet_ctx* c, hnet_keyframes* k, hipEvent_t* ev, const void* d_out, uint8_t* pin_out, void* out, size_t bytes) {
-    hipStream_t st = c->stream;
-    HIPCHK(c, hipEventRecord(ev[1], st));
-    HIPCHK(c, hipMemcpyAsync(pin_out, d_out, bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    float ms = 0;
-    HIPCHK(c, hipEventElapsedTime(&ms, ev[0], ev[1]));
-    k->ms = ms;
-    memcpy(out, pin_out, bytes);
-    return HNET_OK;
-}
-
 // ONE upload {ids | curr slot | the oriented call's table}, the launch sequence inside the store's own events, ONE download of the records [n], one
 // synchronisation.  oriented: under the table hyps [n_hyp], out [n] hnet_keyframe_relocalise_oriented; else the plain call, out [n] hnet_keyframe_relocalise.
 int relocalise(hnet_sessions* s, int n, const int32_t* ids, const hnet_keyframe_relocalise_opts* opts, bool oriented, const hnet_photo_search_hyp* hyps,
@@ -515,19 +381,14 @@ int relocalise(hnet_sessions* s, int n, const int32_t* ids, const hnet_keyframe_
     if ((rc = reloc_ensure(c, k, who)) != HNET_OK) return rc;
     KeyReloc* r = k->reloc;
     const RelocScratch rw(r->scratch, c->cfg.max_batch);
-    int32_t* h_ids = reinterpret_cast<int32_t*>(r->pin_in);
-    for (int i = 0; i < n; i++) {
-        h_ids[i] = ids[i];
-        h_ids[n + i] = 2 * ids[i] + s->st[ids[i]].curr;
-    }
+    slot_table(s, n, ids, nullptr, reinterpret_cast<int32_t*>(r->pin_in));
     const size_t head = map_table_bytes(n), tab = oriented ? (size_t)n_hyp * sizeof(SearchHyp) : 0;
     if (oriented) memcpy(r->pin_in + head, hyps, tab);                 // (8 n bytes in front: the table is aligned)
     const int32_t* d_ids = reinterpret_cast<const int32_t*>(rw.tab);
     const SearchHyp* d_hyps = oriented ? reinterpret_cast<const SearchHyp*>(rw.tab + head) : nullptr;
-    HIPCHK(c, hipMemcpyAsync(rw.tab, r->pin_in, head + tab, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipEventRecord(k->ev[0], c->stream));
+    if ((rc = begin_call(c, k, rw.tab, r->pin_in, head + tab)) != HNET_OK) return rc;
     if ((rc = enqueue_relocalise(s, reloc_targets_store(s), rw, d_ids, d_ids + n, n, nullptr, d_hyps, n_hyp, o)) != HNET_OK) return rc;
-    return finish_call(c, k, k->ev, rw.out, r->pin_out, out, (size_t)n * (oriented ? sizeof(OrientedRelocRec) : sizeof(RelocRec)));
+    return finish_call(c, k, rw.out, r->pin_out, out, (size_t)n * (oriented ? sizeof(OrientedRelocRec) : sizeof(RelocRec)));
 }
 
 // hnet_sessions_keyframe_relocalise_oriented with the fine stage on the picked candidate: ONE upload {ids | curr slot | table | fine table} into the fine
@@ -553,11 +414,7 @@ int relocalise_fine(hnet_sessions* s, int n, const int32_t* ids, const hnet_keyf
     KeyFine* f = k->fine;
     const RelocScratch rw(k->reloc->scratch, c->cfg.max_batch);
     const FineScratch fw(f->scratch, c->cfg.max_batch);
-    int32_t* h_ids = reinterpret_cast<int32_t*>(f->pin_in);
-    for (int i = 0; i < n; i++) {
-        h_ids[i] = ids[i];
-        h_ids[n + i] = 2 * ids[i] + s->st[ids[i]].curr;
-    }
+    slot_table(s, n, ids, nullptr, reinterpret_cast<int32_t*>(f->pin_in));
     const size_t head = map_table_bytes(n), tab = (size_t)n_hyp * sizeof(SearchHyp), ftab = tab * fs.fo.n_fine;      // (8 n bytes in front: the tables are aligned)
     memcpy(f->pin_in + head, hyps, tab);
     memcpy(f->pin_in + head + tab, fine, ftab);
@@ -565,11 +422,10 @@ int relocalise_fine(hnet_sessions* s, int n, const int32_t* ids, const hnet_keyf
     const SearchHyp* d_hyps = reinterpret_cast<const SearchHyp*>(fw.tab + head);
     fs.fw = &fw;
     fs.d_fine = reinterpret_cast<const SearchHyp*>(fw.tab + head + tab);
-    HIPCHK(c, hipMemcpyAsync(fw.tab, f->pin_in, head + tab + ftab, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipEventRecord(k->ev[0], c->stream));
+    if ((rc = begin_call(c, k, fw.tab, f->pin_in, head + tab + ftab)) != HNET_OK) return rc;
     if ((rc = enqueue_relocalise(s, reloc_targets_store(s), rw, d_ids, d_ids + n, n, nullptr, d_hyps, n_hyp, o, &fs)) != HNET_OK) return rc;
     HIPCHK(c, launch_reloc_fine_pack(reinterpret_cast<const OrientedRelocRec*>(rw.out), n, fw.out, c->stream));
-    return finish_call(c, k, k->ev, fw.out, f->pin_out, out, (size_t)n * sizeof(FineRelocRec));
+    return finish_call(c, k, fw.out, f->pin_out, out, (size_t)n * sizeof(FineRelocRec));
 }
 
 }  // namespace
@@ -578,8 +434,40 @@ namespace capi {
 
 // (hnet_destroy_sessions has set the device and drained the stream)
 void keyframes_destroy(hnet_sessions* s) {
-    keyframes_free(s->kf);
+    delete s->kf;
     s->kf = nullptr;
+}
+
+int check_listed(hnet_sessions* s, int n, const int32_t* ids, const char* who, bool tracked) {
+    hnet_ctx* c = s->ctx;
+    const hnet_keyframes* k = s->kf;
+    for (int i = 0; i < n; i++) {
+        const int id = ids[i];
+        if (s->st[id].count < 1) return fail(c, HNET_ERR_NOT_READY, std::string(who) + ": a listed session has no image");
+        if (!tracked) continue;
+        if (!k->has_key[id]) return fail(c, HNET_ERR_NOT_READY, std::string(who) + ": a listed session holds no keyframe");
+        if (s->st[id].count != k->count_at_track[id])
+            return fail(c, HNET_ERR_NOT_READY, std::string(who) + ": a listed session's latest image is not the one its last track saw (track it first)");
+    }
+    return HNET_OK;
+}
+
+int begin_call(hnet_ctx* c, hnet_keyframes* k, void* d_in, const void* pin_in, size_t bytes) {
+    HIPCHK(c, hipMemcpyAsync(d_in, pin_in, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipEventRecord(k->ev[0], c->stream));
+    return HNET_OK;
+}
+
+int finish_call(hnet_ctx* c, hnet_keyframes* k, const void* d_out, void* pin_out, void* out, size_t bytes) {
+    hipStream_t st = c->stream;
+    HIPCHK(c, hipEventRecord(k->ev[1], st));
+    HIPCHK(c, hipMemcpyAsync(pin_out, d_out, bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    float ms = 0;
+    HIPCHK(c, hipEventElapsedTime(&ms, k->ev[0], k->ev[1]));
+    k->ms = ms;
+    if (out) memcpy(out, pin_out, bytes);
+    return HNET_OK;
 }
 
 // the session's keyframe and origin chain are dropped: its next track is FIRST.  Stream ordered behind every enqueued track; nothing is synchronised.
@@ -600,53 +488,10 @@ int keyframes_drop(hnet_sessions* s, int id) {
 
 bool keyframes_enabled(const hnet_sessions* s) { return s->kf != nullptr; }
 
-bool keyframes_render_hooks(hnet_sessions* s, KeyRenderHooks* h) {
-    hnet_keyframes* k = s->kf;
-    if (!k || !k->map) return false;
-    const MapStore& m = k->map->dev;
-    h->src = RenderSource{m.img, m.entry, k->state, m.n_sessions, m.capacity};
-    h->render = &k->render;
-    h->ms = &k->ms;
-    return true;
-}
-
-int keyframes_check_tracked(hnet_sessions* s, int n, const int32_t* ids, const char* who) { return check_listed(s, n, ids, who, true); }
-
-bool keyframes_adjust_hooks(hnet_sessions* s, KeyAdjustHooks* h) {
-    hnet_keyframes* k = s->kf;
-    if (!k || !k->map) return false;
-    const MapStore& m = k->map->dev;
-    const KeyScratch w(k->scratch, s->ctx->cfg.max_batch);
-    h->src = AdjustSource{m.img, m.entry, k->state, m.state, m.n_sessions, m.capacity};
-    h->align = AdjustAlign{w.rec, w.start, w.work, w.part, w.x0};
-    h->adjust = &k->adjust;
-    h->ms = &k->ms;
-    return true;
-}
-
-bool keyframes_localise_hooks(hnet_sessions* s, KeyLocaliseHooks* h) {
-    hnet_keyframes* k = s->kf;
-    if (!k || !k->map) return false;
-    const MapStore& m = k->map->dev;
-    const KeyScratch w(k->scratch, s->ctx->cfg.max_batch);
-    h->src = RenderSource{m.img, m.entry, k->state, m.n_sessions, m.capacity};
-    h->state = k->state;
-    h->mstate = m.state;
-    h->entry = m.entry;
-    h->align = AdjustAlign{w.rec, w.start, w.work, w.part, w.x0};
-    h->localise = &k->localise;
-    h->ms = &k->ms;
-    return true;
-}
-
 void keyframes_table(const hnet_sessions* s, int n, const int32_t* ids, const uint8_t* on, int32_t* tab) {
     const hnet_keyframes* k = s->kf;
-    for (int i = 0; i < n; i++) {
-        const int id = ids[i];
-        tab[i] = !on || on[id] ? id : -1;
-        tab[n + i] = 2 * id + s->st[id].curr;
-        tab[2 * n + i] = k->has_key[id] && s->st[id].count != k->count_at_track[id] + 1 ? 1 : 0;
-    }
+    slot_table(s, n, ids, on, tab);
+    for (int i = 0; i < n; i++) tab[2 * n + i] = k->has_key[ids[i]] && s->st[ids[i]].count != k->count_at_track[ids[i]] + 1 ? 1 : 0;
 }
 
 // (the store's events and ms stay the last sessions call's.  A plain track has no working copy of the map: its note waits for the commit; one with
@@ -729,15 +574,12 @@ int keyframes_instep_recover_ensure(hnet_sessions* s, const char* who) {
     if (k->instep) return HNET_OK;                 // (a map enabled since then brought its working copies with it: hnet_sessions_enable_keyframe_map)
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
     if (const int rc = reloc_ensure(c, k, who); rc != HNET_OK) return rc;
-    KeyInstepWork* w = new KeyInstepWork();
+    auto w = std::make_unique<KeyInstepWork>();
     if (const KeyMap* m = k->map) {
-        const hipError_t e = instep_map_alloc(w, m, s->n);
-        if (e != hipSuccess) {
-            instep_free(w);
-            return fail(c, HNET_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-        }
+        const hipError_t e = instep_map_alloc(w.get(), m, s->n);
+        if (e != hipSuccess) return fail(c, HNET_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
     }
-    k->instep = w;
+    k->instep = w.release();
     return HNET_OK;
 }
 
@@ -759,25 +601,19 @@ int hnet_sessions_enable_keyframes(hnet_sessions* s) {
     if (s->kf) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": keyframes are already enabled");
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
     const int B = c->cfg.max_batch, N = s->n;
-    const size_t pyr = (size_t)B * PYR_BYTES;
-    if (!c->pyr_scratch) HIPCHK(c, dalloc(&c->pyr_scratch, 2 * pyr));
-    hnet_keyframes* k = new hnet_keyframes();
-    hipError_t e = hipMalloc((void**)&k->key, (size_t)N * NPIX);
-    if (e == hipSuccess) e = hipMalloc((void**)&k->state, (size_t)N * sizeof(KeyState));
-    if (e == hipSuccess) e = hipMalloc((void**)&k->scratch, KeyScratch(nullptr, B).bytes);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&k->pin_in, table_bytes(B), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&k->pin_out, (size_t)B * sizeof(KeyTrack), hipHostMallocDefault);
-    for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipEventCreate(&k->ev[i]);
+    if (const int rc = ensure_pyr_scratch(c); rc != HNET_OK) return rc;
+    auto k = std::make_unique<hnet_keyframes>();
+    hipError_t e = k->mem.alloc(&k->key, (size_t)N * NPIX);
+    if (e == hipSuccess) e = k->mem.alloc(&k->state, (size_t)N);
+    if (e == hipSuccess) e = k->alloc(KeyScratch(nullptr, B).bytes, table_bytes(B), (size_t)B * sizeof(KeyTrack));
+    for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipEventCreate(&k->ev[i]);      // (the one pair of the store and of every layer on it)
     if (e == hipSuccess) e = hipMemsetAsync(k->key, 0, (size_t)N * NPIX, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(k->state, 0, (size_t)N * sizeof(KeyState), c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
-        keyframes_free(k);
-        return fail(c, HNET_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return fail(c, HNET_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
     k->has_key.assign(N, 0);
     k->count_at_track.assign(N, -1);
-    s->kf = k;
+    s->kf = k.release();
     return HNET_OK;
 }
 
@@ -800,10 +636,9 @@ int hnet_sessions_keyframe_track(hnet_sessions* s, int n, const int32_t* ids, co
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
     const KeyScratch w(k->scratch, c->cfg.max_batch);
     table_fill(s, n, ids, step_px, k->pin_in);
-    HIPCHK(c, hipMemcpyAsync(w.tab, k->pin_in, table_bytes(n), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipEventRecord(k->ev[0], c->stream));
+    if ((rc = begin_call(c, k, w.tab, k->pin_in, table_bytes(n))) != HNET_OK) return rc;
     if ((rc = enqueue_track(s, reloc_targets_store(s), table_view(w.tab, n), n, o, nullptr)) != HNET_OK) return rc;
-    if ((rc = finish_call(c, k, k->ev, w.out, k->pin_out, out, (size_t)n * sizeof(KeyTrack))) != HNET_OK) return rc;
+    if ((rc = finish_call(c, k, w.out, k->pin_out, out, (size_t)n * sizeof(KeyTrack))) != HNET_OK) return rc;
     for (int i = 0; i < n; i++) {
         k->has_key[ids[i]] = 1;
         k->count_at_track[ids[i]] = s->st[ids[i]].count;
@@ -851,31 +686,25 @@ int hnet_sessions_enable_keyframe_map(hnet_sessions* s, int capacity) {
         if (k->has_key[id]) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": a session already holds a keyframe, which would not be in the map");
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
     const int B = c->cfg.max_batch, N = s->n, M = capacity;
-    KeyMap* m = new KeyMap();
+    auto m = std::make_unique<KeyMap>();
     m->dev.n_sessions = N;
     m->dev.capacity = M;
     const size_t img = (size_t)N * M * NPIX, ent = (size_t)N * M * sizeof(MapEntry), sta = (size_t)N * sizeof(MapState);
-    hipError_t e = hipMalloc((void**)&m->dev.img, img);
-    if (e == hipSuccess) e = hipMalloc((void**)&m->dev.entry, ent);
-    if (e == hipSuccess) e = hipMalloc((void**)&m->dev.state, sta);
-    if (e == hipSuccess) e = hipMalloc((void**)&m->scratch, MapScratch(nullptr, B).bytes);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&m->pin_in, map_table_bytes(B), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&m->pin_out, (size_t)B * sizeof(MapRevisit), hipHostMallocDefault);
-    for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipEventCreate(&m->ev[i]);
-    if (e == hipSuccess && k->instep) e = instep_map_alloc(k->instep, m, N);      // (a filter turned the in-step recovery on before the map existed)
+    hipError_t e = m->mem.alloc(&m->dev.img, img);
+    if (e == hipSuccess) e = m->mem.alloc(&m->dev.entry, (size_t)N * M);
+    if (e == hipSuccess) e = m->mem.alloc(&m->dev.state, (size_t)N);
+    if (e == hipSuccess) e = m->alloc(MapScratch(nullptr, B).bytes, map_table_bytes(B), (size_t)B * sizeof(MapRevisit));
+    if (e == hipSuccess && k->instep) e = instep_map_alloc(k->instep, m.get(), N);      // (a filter turned the in-step recovery on before the map existed)
     if (e == hipSuccess) e = hipMemsetAsync(m->dev.img, 0, img, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(m->dev.entry, 0, ent, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(m->dev.state, 0, sta, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
-        map_free(m);
-        return fail(c, HNET_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-    }
-    k->map = m;
+    if (e != hipSuccess) return fail(c, HNET_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    k->map = m.release();
     return HNET_OK;
 }
 
-// ONE upload {ids | curr slot}, the launch sequence inside the map's own events, ONE download of the records [n], one synchronisation
+// ONE upload {ids | curr slot}, the launch sequence inside the store's events, ONE download of the records [n], one synchronisation
 int hnet_sessions_keyframe_revisit(hnet_sessions* s, int n, const int32_t* ids, const hnet_keyframe_revisit_opts* opts, hnet_keyframe_revisit* out) {
     const char* who = "hnet_sessions_keyframe_revisit";
     if (!s) return HNET_ERR_INVALID_ARG;
@@ -898,23 +727,18 @@ int hnet_sessions_keyframe_revisit(hnet_sessions* s, int n, const int32_t* ids, 
     const int B = c->cfg.max_batch, N = s->n;
     const KeyScratch w(k->scratch, B);
     const MapScratch mw(m->scratch, B);
-    int32_t* h_ids = reinterpret_cast<int32_t*>(m->pin_in);
-    for (int i = 0; i < n; i++) {
-        h_ids[i] = ids[i];
-        h_ids[n + i] = 2 * ids[i] + s->st[ids[i]].curr;
-    }
+    slot_table(s, n, ids, nullptr, reinterpret_cast<int32_t*>(m->pin_in));
     const int32_t *d_ids = mw.tab, *d_slot = mw.tab + n;
     const size_t pyr = (size_t)B * PYR_BYTES;
     uint8_t *prev = (uint8_t*)c->stage_prev, *curr = (uint8_t*)c->stage_curr;
     hipStream_t st = c->stream;
-    HIPCHK(c, hipMemcpyAsync(mw.tab, m->pin_in, map_table_bytes(n), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipEventRecord(m->ev[0], st));
+    if ((rc = begin_call(c, k, mw.tab, m->pin_in, map_table_bytes(n))) != HNET_OK) return rc;
     HIPCHK(c, launch_keyframe_map_select(d_ids, n, k->state, m->dev, o.min_grid, w.x0, mw.cand, mw.out, st));
     HIPCHK(c, launch_keyframe_map_gather(d_ids, d_slot, n, mw.cand, m->dev, s->ring, 2 * N, prev, curr, st));
     HIPCHK(c, launch_photo_align_robust(prev, curr, n, w.x0, o.align, o.levels, c->pyr_scratch, c->pyr_scratch + pyr, w.start, w.part, w.work, w.rec, st));
     HIPCHK(c, launch_keyframe_map_decide(d_ids, n, w.rec, w.x0, mw.cand, o, k->state, m->dev, mw.out, mw.attach, st));
     HIPCHK(c, launch_keyframe_map_attach(d_ids, n, mw.cand, mw.attach, m->dev, k->key, st));
-    return finish_call(c, k, m->ev, mw.out, m->pin_out, out, (size_t)n * sizeof(MapRevisit));
+    return finish_call(c, k, mw.out, m->pin_out, out, (size_t)n * sizeof(MapRevisit));
 }
 
 int hnet_sessions_keyframe_map_info(hnet_sessions* s, int id, hnet_keyframe_map_entry* entries, hnet_keyframe_map_state* map_state) {
@@ -1010,10 +834,9 @@ int hnet_sessions_keyframe_track_recover(hnet_sessions* s, int n, const int32_t*
     memset(r->pin_in + table_bytes(n), 0, head - table_bytes(n));
     memcpy(r->pin_in + head, hyps, tabb);
     const KeyRecovery rec{o.reloc, reinterpret_cast<const SearchHyp*>(rw.tab + head), n_hyp, nullptr, nullptr};
-    HIPCHK(c, hipMemcpyAsync(rw.tab, r->pin_in, head + tabb, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipEventRecord(k->ev[0], c->stream));
+    if ((rc = begin_call(c, k, rw.tab, r->pin_in, head + tabb)) != HNET_OK) return rc;
     if ((rc = enqueue_track(s, reloc_targets_store(s), table_view(rw.tab, n), n, o.track, &rec)) != HNET_OK) return rc;
-    if ((rc = finish_call(c, k, k->ev, rw.rout, r->pin_out, out, (size_t)n * sizeof(RecoverRec))) != HNET_OK) return rc;
+    if ((rc = finish_call(c, k, rw.rout, r->pin_out, out, (size_t)n * sizeof(RecoverRec))) != HNET_OK) return rc;
     for (int i = 0; i < n; i++) {
         k->has_key[ids[i]] = 1;
         k->count_at_track[ids[i]] = s->st[ids[i]].count;

@@ -1,12 +1,13 @@
 // capi_keyframe_adjust.hip — hnet_keyframe_adjust_default_opts, hnet_op_keyframe_adjust_solve, hnet_op_keyframe_adjust,
 // hnet_sessions_enable_keyframe_adjust and hnet_sessions_keyframe_adjust of include/hnet.h (keyframe_adjust_dev.h, csrc/kernels_keyframe_adjust.hip;
 // DESIGN 7ad): a keyframe map adjusted jointly.  The operator-level calls own their buffers as device temporaries.  The sessions call reads the map, the
-// states, the staging arrays and the alignment scratch of the keyframe store (capi_keyframe.hip, through keyframes_adjust_hooks) and owns its tables,
-// records and pinned blocks, allocated by its enable: additive, a store whose adjustment was never enabled holds a null pointer and allocates and
+// states, the staging arrays and the alignment scratch of the keyframe store (keyframes_internal.h) and owns its tables, records and pinned blocks,
+// allocated by its enable: additive, a store whose adjustment was never enabled holds a null pointer and allocates and
 // launches nothing here.  The jobs of a call run in ROUNDS of max_batch alignments, because the alignment's scratch is sized by max_batch; the host
 // needs the job counts to size the rounds, so a call has TWO synchronisations: one after the pairs kernel, one at the end.
-#include "sessions_internal.h"
-#include "keyframe_adjust_dev.h"
+#include "keyframes_internal.h"
+
+#include <memory>
 
 using namespace hnet;
 using namespace capi;
@@ -31,35 +32,18 @@ static_assert((int)HNET_ADJ_FEW_ENTRIES == ka::ADJ_FEW_ENTRIES && (int)HNET_ADJ_
               (int)HNET_ADJ_WEIGHT_UNIT == ka::WEIGHT_UNIT && (int)HNET_ADJ_WEIGHT_INFO == ka::WEIGHT_INFO && HNET_ADJ_MAX_EDGES == ka::MAX_PAIRS &&
               HNET_ADJ_MAX_TRIALS == ka::MAX_TRIALS, "HNET_ADJ_* are the header's");
 
-namespace capi {
+namespace {
 
 // the adjustment of a store: sized at its enable for max_batch B
-struct KeyAdjust {
+struct KeyAdjust : KeyLayer {
     int32_t* d_ids = nullptr;                  // device [B]
     AdjustJobs* tab = nullptr;                 // device [B]
     double* infos = nullptr;                   // device [B][28][64]
     uint8_t* d_out = nullptr;                  // device: a call's results {records [n] | level-0 records [n][28]}, packed for ONE download
-    uint8_t *pin_in = nullptr, *pin_tab = nullptr, *pin_out = nullptr;     // pinned: the ids, the job tables, the results
-    hipEvent_t ev[2] = {nullptr, nullptr};     // around the launches of the last adjustment
+    int32_t* pin_in = nullptr;                 // pinned: the ids,
+    AdjustJobs* pin_tab = nullptr;             // the job tables,
+    uint8_t* pin_out = nullptr;                // the results
 };
-
-void keyframes_adjust_free(KeyAdjust* a) {
-    if (!a) return;
-    if (a->d_ids) (void)hipFree(a->d_ids);
-    if (a->tab) (void)hipFree(a->tab);
-    if (a->infos) (void)hipFree(a->infos);
-    if (a->d_out) (void)hipFree(a->d_out);
-    if (a->pin_in) (void)hipHostFree(a->pin_in);
-    if (a->pin_tab) (void)hipHostFree(a->pin_tab);
-    if (a->pin_out) (void)hipHostFree(a->pin_out);
-    for (hipEvent_t e : a->ev)
-        if (e) (void)hipEventDestroy(e);
-    delete a;
-}
-
-}  // namespace capi
-
-namespace {
 
 constexpr size_t INFO_DOUBLES = (size_t)ADJUST_MAX_PAIRS * ADJUST_INFO, EDGE_RECS_BYTES = (size_t)ADJUST_MAX_PAIRS * sizeof(RobustRec);
 size_t out_bytes(int n, bool edge_recs) { return (size_t)n * (sizeof(AdjustRec) + (edge_recs ? EDGE_RECS_BYTES : 0)); }
@@ -81,7 +65,7 @@ int check_opts(hnet_ctx* c, const hnet_keyframe_adjust_opts* opts, const char* w
 
 // what one adjustment runs on: the source, the call's device ids, its tables and records, the staging pair and the alignment's scratch for B pairs
 struct AdjustRun {
-    AdjustSource src; const int32_t* d_ids; int n; AdjustJobs* tab; AdjustRec* rec; double* infos; RobustRec* edge_recs; AdjustAlign al; uint8_t *prev, *curr;
+    AdjustSource src; const int32_t* d_ids; int n; AdjustJobs* tab; AdjustRec* rec; double* infos; RobustRec* edge_recs; AlignScratch al; uint8_t *prev, *curr;
     AdjustJobs* h_tab;                         // host [n]: where the job tables are downloaded to
 };
 
@@ -130,23 +114,21 @@ int hnet_op_keyframe_adjust_solve(hnet_ctx* c, int m, const hnet_keyframe_map_en
     const int rc = check_opts(c, opts, who, o);
     if (rc != HNET_OK) return rc;
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    // the upload block: the id, the entries (8-byte aligned), the record with its rows, the information matrices
-    const size_t ent_off = 8, rec_off = ent_off + (size_t)m * sizeof(MapEntry), info_off = rec_off + sizeof(AdjustRec);
-    const size_t total = info_off + (edge_infos ? INFO_DOUBLES * sizeof(double) : 0);
-    std::vector<uint8_t> h_in(total, 0);
-    memcpy(h_in.data() + ent_off, entries, (size_t)m * sizeof(MapEntry));
-    AdjustRec* seed = reinterpret_cast<AdjustRec*>(h_in.data() + rec_off);
+    const KeyUpload up(m, KeyUpload::SEED | (edge_infos ? KeyUpload::INFOS : 0));      // (the record with its rows, the information matrices)
+    std::vector<uint8_t> h_in(up.total, 0);
+    memcpy(h_in.data() + up.entry, entries, (size_t)m * sizeof(MapEntry));
+    AdjustRec* seed = reinterpret_cast<AdjustRec*>(h_in.data() + up.seed);
     seed->n_jobs = n_edges;
     if (n_edges) memcpy(seed->edge, edges, (size_t)n_edges * sizeof(AdjustEdge));
-    if (edge_infos) memcpy(h_in.data() + info_off, edge_infos, (size_t)n_edges * ADJUST_INFO * sizeof(double));
+    if (edge_infos) memcpy(h_in.data() + up.infos, edge_infos, (size_t)n_edges * ADJUST_INFO * sizeof(double));
     DevTemps t;
     uint8_t* d_in = nullptr;
-    HIPCHK(c, t.alloc(&d_in, total));
-    const AdjustSource src{nullptr, reinterpret_cast<MapEntry*>(d_in + ent_off), nullptr, nullptr, 1, m};
-    AdjustRec* d_rec = reinterpret_cast<AdjustRec*>(d_in + rec_off);
+    HIPCHK(c, t.alloc(&d_in, up.total));
+    const AdjustSource src{nullptr, reinterpret_cast<MapEntry*>(d_in + up.entry), nullptr, nullptr, 1, m};
+    AdjustRec* d_rec = reinterpret_cast<AdjustRec*>(d_in + up.seed);
     hipStream_t st = c->stream;
-    HIPCHK(c, hipMemcpyAsync(d_in, h_in.data(), total, hipMemcpyHostToDevice, st));
-    HIPCHK(c, launch_keyframe_adjust_solve(reinterpret_cast<const int32_t*>(d_in), 1, src, edge_infos ? reinterpret_cast<const double*>(d_in + info_off) : nullptr, o,
+    HIPCHK(c, hipMemcpyAsync(d_in, h_in.data(), up.total, hipMemcpyHostToDevice, st));
+    HIPCHK(c, launch_keyframe_adjust_solve(reinterpret_cast<const int32_t*>(d_in), 1, src, edge_infos ? reinterpret_cast<const double*>(d_in + up.infos) : nullptr, o,
                                            d_rec, st));
     AdjustRec h_rec;
     HIPCHK(c, hipMemcpyAsync(&h_rec, d_rec, sizeof h_rec, hipMemcpyDeviceToHost, st));
@@ -169,17 +151,16 @@ int hnet_op_keyframe_adjust(hnet_ctx* c, int m, const uint8_t* images, const hne
     o.apply = 0;                                                           // (there is no map to write: the record holds the matrices)
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
     const int B = c->cfg.max_batch;
-    const size_t pyr = (size_t)B * PYR_BYTES;
-    if (!c->pyr_scratch) HIPCHK(c, dalloc(&c->pyr_scratch, 2 * pyr));
-    const size_t ent_off = 8, img_off = (ent_off + (size_t)m * sizeof(MapEntry) + 15) & ~(size_t)15, in_total = img_off + (size_t)m * NPIX;
+    if (const int e = ensure_pyr_scratch(c); e != HNET_OK) return e;
+    const KeyUpload up(m, KeyUpload::IMAGES);
     const size_t out_total = out_bytes(1, out_edge_records != nullptr);
-    std::vector<uint8_t> h_in(in_total, 0), h_out(out_total);
-    memcpy(h_in.data() + ent_off, entries, (size_t)m * sizeof(MapEntry));
-    memcpy(h_in.data() + img_off, images, (size_t)m * NPIX);
+    std::vector<uint8_t> h_in(up.total, 0), h_out(out_total);
+    memcpy(h_in.data() + up.entry, entries, (size_t)m * sizeof(MapEntry));
+    memcpy(h_in.data() + up.images, images, (size_t)m * NPIX);
     DevTemps t;
     uint8_t *d_in = nullptr, *d_out = nullptr, *d_stage = nullptr;
     AdjustRun r{};
-    HIPCHK(c, t.alloc(&d_in, in_total));
+    HIPCHK(c, t.alloc(&d_in, up.total));
     HIPCHK(c, t.alloc(&d_out, out_total));
     HIPCHK(c, t.alloc(&d_stage, 2 * (size_t)B * NPIX));
     HIPCHK(c, t.alloc(&r.tab, 1));
@@ -190,7 +171,7 @@ int hnet_op_keyframe_adjust(hnet_ctx* c, int m, const uint8_t* images, const hne
     HIPCHK(c, t.alloc(&r.al.part, (size_t)B * PHOTO_SLICES));
     HIPCHK(c, t.alloc(&r.al.x0, (size_t)B * 8));
     AdjustJobs h_tab;
-    r.src = AdjustSource{d_in + img_off, reinterpret_cast<MapEntry*>(d_in + ent_off), nullptr, nullptr, 1, m};
+    r.src = AdjustSource{d_in + up.images, reinterpret_cast<MapEntry*>(d_in + up.entry), nullptr, nullptr, 1, m};
     r.d_ids = reinterpret_cast<const int32_t*>(d_in);
     r.n = 1;
     r.rec = reinterpret_cast<AdjustRec*>(d_out);
@@ -199,7 +180,7 @@ int hnet_op_keyframe_adjust(hnet_ctx* c, int m, const uint8_t* images, const hne
     r.curr = d_stage + (size_t)B * NPIX;
     r.h_tab = &h_tab;
     hipStream_t st = c->stream;
-    HIPCHK(c, hipMemcpyAsync(d_in, h_in.data(), in_total, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(d_in, h_in.data(), up.total, hipMemcpyHostToDevice, st));
     if (const int e = enqueue_adjust(c, r, o); e != HNET_OK) return e;
     HIPCHK(c, hipMemcpyAsync(h_out.data(), d_out, out_total, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
@@ -212,70 +193,58 @@ int hnet_sessions_enable_keyframe_adjust(hnet_sessions* s) {
     const char* who = "hnet_sessions_enable_keyframe_adjust";
     if (!s) return HNET_ERR_INVALID_ARG;
     hnet_ctx* c = s->ctx;
-    KeyAdjustHooks hk;
-    if (!keyframes_adjust_hooks(s, &hk)) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": the keyframe map is not enabled (hnet_sessions_enable_keyframe_map)");
-    if (*hk.adjust) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": the keyframe adjustment is already enabled");
+    hnet_keyframes* k = s->kf;
+    if (!k || !k->map) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": the keyframe map is not enabled (hnet_sessions_enable_keyframe_map)");
+    if (k->adjust) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": the keyframe adjustment is already enabled");
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    const int B = c->cfg.max_batch;
-    KeyAdjust* a = new KeyAdjust();
-    hipError_t e = hipMalloc((void**)&a->d_ids, (size_t)B * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&a->tab, (size_t)B * sizeof(AdjustJobs));
-    if (e == hipSuccess) e = hipMalloc((void**)&a->infos, (size_t)B * INFO_DOUBLES * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&a->d_out, out_bytes(B, true));
-    if (e == hipSuccess) e = hipHostMalloc((void**)&a->pin_in, (size_t)B * sizeof(int32_t), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&a->pin_tab, (size_t)B * sizeof(AdjustJobs), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&a->pin_out, out_bytes(B, true), hipHostMallocDefault);
-    for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipEventCreate(&a->ev[i]);
-    if (e != hipSuccess) {
-        keyframes_adjust_free(a);
-        return fail(c, HNET_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-    }
-    *hk.adjust = a;
+    const size_t B = (size_t)c->cfg.max_batch;
+    auto a = std::make_unique<KeyAdjust>();
+    hipError_t e = a->mem.alloc(&a->d_ids, B);
+    if (e == hipSuccess) e = a->mem.alloc(&a->tab, B);
+    if (e == hipSuccess) e = a->mem.alloc(&a->infos, B * INFO_DOUBLES);
+    if (e == hipSuccess) e = a->mem.alloc(&a->d_out, out_bytes((int)B, true));
+    if (e == hipSuccess) e = a->mem.alloc_pinned(&a->pin_in, B);
+    if (e == hipSuccess) e = a->mem.alloc_pinned(&a->pin_tab, B);
+    if (e == hipSuccess) e = a->mem.alloc_pinned(&a->pin_out, out_bytes((int)B, true));
+    if (e != hipSuccess) return fail(c, HNET_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    k->adjust = a.release();
     return HNET_OK;
 }
 
-// ONE upload {ids}, the launches of enqueue_adjust inside the adjustment's own events with their synchronisation, ONE download {records | level-0
+// ONE upload {ids}, the launches of enqueue_adjust inside the store's events with their synchronisation, ONE download {records | level-0
 // records}, the second synchronisation
 int hnet_sessions_keyframe_adjust(hnet_sessions* s, int n, const int32_t* ids, const hnet_keyframe_adjust_opts* opts, hnet_keyframe_adjust* out,
                                   hnet_photo_robust* out_edge_records) {
     const char* who = "hnet_sessions_keyframe_adjust";
     if (!s) return HNET_ERR_INVALID_ARG;
     hnet_ctx* c = s->ctx;
-    KeyAdjustHooks hk;
-    if (!keyframes_adjust_hooks(s, &hk) || !*hk.adjust)
+    hnet_keyframes* k = s->kf;
+    if (!k || !k->map || !k->adjust)
         return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": the keyframe adjustment is not enabled (hnet_sessions_enable_keyframe_adjust)");
-    KeyAdjust* a = *hk.adjust;
+    KeyAdjust* a = static_cast<KeyAdjust*>(k->adjust);
     if (!out) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": out");
     AdjustOpts o;
     int rc = check_opts(c, opts, who, o);
     if (rc != HNET_OK) return rc;
     if ((rc = sessions_check_ids(s, n, ids)) != HNET_OK) return rc;
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    int32_t* h_ids = reinterpret_cast<int32_t*>(a->pin_in);
-    for (int i = 0; i < n; i++) h_ids[i] = ids[i];
+    for (int i = 0; i < n; i++) a->pin_in[i] = ids[i];
     const size_t recs = (size_t)n * sizeof(AdjustRec), total = out_bytes(n, out_edge_records != nullptr);
     AdjustRun r{};
-    r.src = hk.src;
+    r.src = adjust_source(k);
     r.d_ids = a->d_ids;
     r.n = n;
     r.tab = a->tab;
     r.rec = reinterpret_cast<AdjustRec*>(a->d_out);
     r.infos = a->infos;
     r.edge_recs = out_edge_records ? reinterpret_cast<RobustRec*>(a->d_out + recs) : nullptr;
-    r.al = hk.align;
+    r.al = KeyScratch(k->scratch, c->cfg.max_batch).align();
     r.prev = (uint8_t*)c->stage_prev;
     r.curr = (uint8_t*)c->stage_curr;
-    r.h_tab = reinterpret_cast<AdjustJobs*>(a->pin_tab);
-    hipStream_t st = c->stream;
-    HIPCHK(c, hipMemcpyAsync(a->d_ids, a->pin_in, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipEventRecord(a->ev[0], st));
+    r.h_tab = a->pin_tab;
+    if ((rc = begin_call(c, k, a->d_ids, a->pin_in, (size_t)n * sizeof(int32_t))) != HNET_OK) return rc;
     if ((rc = enqueue_adjust(c, r, o)) != HNET_OK) return rc;
-    HIPCHK(c, hipEventRecord(a->ev[1], st));
-    HIPCHK(c, hipMemcpyAsync(a->pin_out, a->d_out, total, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    float ms = 0;
-    HIPCHK(c, hipEventElapsedTime(&ms, a->ev[0], a->ev[1]));
-    *hk.ms = ms;
+    if ((rc = finish_call(c, k, a->d_out, a->pin_out, nullptr, total)) != HNET_OK) return rc;
     memcpy(out, a->pin_out, recs);
     if (out_edge_records) memcpy(out_edge_records, a->pin_out + recs, (size_t)n * EDGE_RECS_BYTES);
     return HNET_OK;

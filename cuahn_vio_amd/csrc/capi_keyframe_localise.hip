@@ -1,8 +1,12 @@
 // capi_keyframe_localise.hip — hnet_keyframe_localise_default_opts and hnet_op_keyframe_localise of include/hnet.h (keyframe_localise_dev.h,
 // csrc/kernels_keyframe_localise.hip): a camera localised against its rendered keyframe map.  The operator-level call owns its buffers as
 // device temporaries and runs the unchanged render (keyframe_render_dev.h) and the masked alignment (photo_masked_dev.h) between its two small kernels.
-#include "sessions_internal.h"
+// The sessions call reads the map, the states and the alignment scratch of the keyframe store (keyframes_internal.h) and owns its templates, tables and
+// records, allocated by its enable.
+#include "keyframes_internal.h"
 #include "keyframe_localise_dev.h"
+
+#include <memory>
 
 using namespace hnet;
 using namespace capi;
@@ -21,10 +25,10 @@ static_assert((int)HNET_LOC_NO_MAP == kl::LOC_NO_MAP && (int)HNET_LOC_LOW_COVER 
               "HNET_LOC_* are the header's");
 static_assert(sizeof(LocaliseRec) % 16 == 0, "the template behind the record stays 16-byte aligned");
 
-namespace capi {
+namespace {
 
 // the localise of a store: sized at its enable for max_batch B
-struct KeyLocalise {
+struct KeyLocalise : KeyLayer {
     int32_t* d_in = nullptr;                   // device: a call's table {ids [n] | curr ring slot [n]}
     RenderTab* tab = nullptr;                  // device [B]
     RenderRec* rrec = nullptr;                 // device [B]
@@ -34,23 +38,7 @@ struct KeyLocalise {
     LocaliseRec* d_out = nullptr;              // device [B]
     int32_t* pin_in = nullptr;                 // pinned: the table
     LocaliseRec* pin_out = nullptr;            // pinned: the records
-    hipEvent_t ev[2] = {nullptr, nullptr};     // around the launch sequence of the last localise
 };
-
-void keyframes_localise_free(KeyLocalise* l) {
-    if (!l) return;
-    for (void* p : {(void*)l->d_in, (void*)l->tab, (void*)l->rrec, (void*)l->tmpl, (void*)l->cover, (void*)l->mpyr, (void*)l->n_mask, (void*)l->d_out})
-        if (p) (void)hipFree(p);
-    if (l->pin_in) (void)hipHostFree(l->pin_in);
-    if (l->pin_out) (void)hipHostFree(l->pin_out);
-    for (hipEvent_t e : l->ev)
-        if (e) (void)hipEventDestroy(e);
-    delete l;
-}
-
-}  // namespace capi
-
-namespace {
 
 // o <- *opts checked, or the context's error
 int check_opts(hnet_ctx* c, const hnet_keyframe_localise_opts* opts, const char* who, LocaliseOpts& o) {
@@ -89,16 +77,16 @@ int hnet_op_keyframe_localise(hnet_ctx* c, int m, const uint8_t* images, const h
     if (rc != HNET_OK) return rc;
     if (!all_finite(h_origin_pred, 9)) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": h_origin_pred is not finite");
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    // the upload block: {id 0, padded to 8 bytes | view [9] f64 | entries [m] | images [m], 16-byte aligned | curr}
-    const size_t view_off = 8, ent_off = view_off + 9 * sizeof(double), img_off = (ent_off + (size_t)m * sizeof(MapEntry) + 15) & ~(size_t)15;
-    const size_t curr_off = img_off + (size_t)m * NPIX, in_total = curr_off + NPIX, out_total = sizeof(LocaliseRec) + 2 * (size_t)NPIX;
-    std::vector<uint8_t> h_in(in_total, 0), h_out(out_total);
-    memcpy(h_in.data() + view_off, h_origin_pred, 9 * sizeof(double));
-    memcpy(h_in.data() + ent_off, entries, (size_t)m * sizeof(MapEntry));
-    memcpy(h_in.data() + img_off, images, (size_t)m * NPIX);
-    memcpy(h_in.data() + curr_off, curr, NPIX);
+    const KeyUpload up(m, KeyUpload::VIEW | KeyUpload::IMAGES | KeyUpload::FRAME);
+    const size_t out_total = sizeof(LocaliseRec) + 2 * (size_t)NPIX;
+    std::vector<uint8_t> h_in(up.total, 0), h_out(out_total);
+    memcpy(h_in.data() + up.view, h_origin_pred, 9 * sizeof(double));
+    memcpy(h_in.data() + up.entry, entries, (size_t)m * sizeof(MapEntry));
+    memcpy(h_in.data() + up.images, images, (size_t)m * NPIX);
+    memcpy(h_in.data() + up.frame, curr, NPIX);
     const size_t pyr = (size_t)c->cfg.max_batch * PYR_BYTES;
-    if (o.levels > 1 && !c->pyr_scratch) HIPCHK(c, dalloc(&c->pyr_scratch, 2 * pyr));
+    if (o.levels > 1)
+        if (const int e = ensure_pyr_scratch(c); e != HNET_OK) return e;
     DevTemps t;
     uint8_t *d_in = nullptr, *d_out = nullptr, *d_mpyr = nullptr;
     RenderTab* d_tab = nullptr;
@@ -109,7 +97,7 @@ int hnet_op_keyframe_localise(hnet_ctx* c, int m, const uint8_t* images, const h
     RobustWork* d_work = nullptr;
     RobustRec* d_arec = nullptr;
     RobustStart* d_start = nullptr;
-    HIPCHK(c, t.alloc(&d_in, in_total));
+    HIPCHK(c, t.alloc(&d_in, up.total));
     HIPCHK(c, t.alloc(&d_out, out_total));
     HIPCHK(c, t.alloc(&d_tab, 1));
     HIPCHK(c, t.alloc(&d_rrec, 1));
@@ -120,20 +108,20 @@ int hnet_op_keyframe_localise(hnet_ctx* c, int m, const uint8_t* images, const h
     HIPCHK(c, t.alloc(&d_work, 1));
     HIPCHK(c, t.alloc(&d_arec, (size_t)o.levels));
     HIPCHK(c, t.alloc(&d_start, 1));
-    const RenderSource src{d_in + img_off, reinterpret_cast<const MapEntry*>(d_in + ent_off), nullptr, 1, m};
+    const RenderSource src{d_in + up.images, reinterpret_cast<const MapEntry*>(d_in + up.entry), nullptr, 1, m};
     const int32_t* d_id = reinterpret_cast<const int32_t*>(d_in);
     const RenderOpts ro{IMG_W, IMG_H, o.mode, 0};
     RobustOpts ao;
     memcpy(&ao, &o.align, sizeof ao);
     uint8_t *d_tmpl = d_out + sizeof(LocaliseRec), *d_cover = d_tmpl + NPIX;
     hipStream_t st = c->stream;
-    HIPCHK(c, hipMemcpyAsync(d_in, h_in.data(), in_total, hipMemcpyHostToDevice, st));
-    HIPCHK(c, launch_keyframe_render_setup(d_id, 1, src, reinterpret_cast<const double*>(d_in + view_off), d_tab, d_rrec, st));
+    HIPCHK(c, hipMemcpyAsync(d_in, h_in.data(), up.total, hipMemcpyHostToDevice, st));
+    HIPCHK(c, launch_keyframe_render_setup(d_id, 1, src, reinterpret_cast<const double*>(d_in + up.view), d_tab, d_rrec, st));
     HIPCHK(c, launch_keyframe_render(d_id, 1, src, d_tab, ro, d_tmpl, d_cover, d_rrec, st));
     HIPCHK(c, launch_keyframe_localise_start(d_rrec, 1, o, d_x0, st));
-    HIPCHK(c, launch_photo_align_masked(d_tmpl, d_cover, d_in + curr_off, 1, d_x0, ao, o.levels, c->pyr_scratch, c->pyr_scratch ? c->pyr_scratch + pyr : nullptr, d_mpyr,
+    HIPCHK(c, launch_photo_align_masked(d_tmpl, d_cover, d_in + up.frame, 1, d_x0, ao, o.levels, c->pyr_scratch, c->pyr_scratch ? c->pyr_scratch + pyr : nullptr, d_mpyr,
                                         d_n_mask, d_start, d_part, d_work, d_arec, st));
-    const MapStore one{nullptr, const_cast<MapEntry*>(src.entry), nullptr, 1, m};                   // (no state: the decide reads the entries only)
+    const MapStore one{nullptr, reinterpret_cast<MapEntry*>(d_in + up.entry), nullptr, 1, m};                   // (no state: the decide reads the entries only)
     HIPCHK(c, launch_keyframe_localise_decide(nullptr, 1, d_rrec, d_arec, nullptr, one, o, reinterpret_cast<LocaliseRec*>(d_out), st));      // (level 0 leads [levels][1])
     HIPCHK(c, hipMemcpyAsync(h_out.data(), d_out, out_total, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
@@ -143,84 +131,71 @@ int hnet_op_keyframe_localise(hnet_ctx* c, int m, const uint8_t* images, const h
     return HNET_OK;
 }
 
-// once, after hnet_sessions_enable_keyframe_map: templates, covers, mask pyramids, tables and records for max_batch, pinned blocks and events of its own
+// once, after hnet_sessions_enable_keyframe_map: templates, covers, mask pyramids, tables and records for max_batch and pinned blocks of its own
 int hnet_sessions_enable_keyframe_localise(hnet_sessions* s) {
     const char* who = "hnet_sessions_enable_keyframe_localise";
     if (!s) return HNET_ERR_INVALID_ARG;
     hnet_ctx* c = s->ctx;
-    KeyLocaliseHooks hk;
-    if (!keyframes_localise_hooks(s, &hk)) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": the keyframe map is not enabled (hnet_sessions_enable_keyframe_map)");
-    if (*hk.localise) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": the keyframe localise is already enabled");
+    hnet_keyframes* k = s->kf;
+    if (!k || !k->map) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": the keyframe map is not enabled (hnet_sessions_enable_keyframe_map)");
+    if (k->localise) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": the keyframe localise is already enabled");
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
     const size_t B = (size_t)c->cfg.max_batch;
-    KeyLocalise* l = new KeyLocalise();
-    hipError_t e = hipMalloc((void**)&l->d_in, 2 * B * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&l->tab, B * sizeof(RenderTab));
-    if (e == hipSuccess) e = hipMalloc((void**)&l->rrec, B * sizeof(RenderRec));
-    if (e == hipSuccess) e = hipMalloc((void**)&l->tmpl, B * NPIX);
-    if (e == hipSuccess) e = hipMalloc((void**)&l->cover, B * NPIX);
-    if (e == hipSuccess) e = hipMalloc((void**)&l->mpyr, B * PYR_BYTES);
-    if (e == hipSuccess) e = hipMalloc((void**)&l->n_mask, B * N_MASK * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&l->d_out, B * sizeof(LocaliseRec));
-    if (e == hipSuccess) e = hipHostMalloc((void**)&l->pin_in, 2 * B * sizeof(int32_t), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&l->pin_out, B * sizeof(LocaliseRec), hipHostMallocDefault);
-    for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipEventCreate(&l->ev[i]);
-    if (e != hipSuccess) {
-        keyframes_localise_free(l);
-        return fail(c, HNET_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-    }
-    *hk.localise = l;
+    auto l = std::make_unique<KeyLocalise>();
+    hipError_t e = l->mem.alloc(&l->d_in, 2 * B);
+    if (e == hipSuccess) e = l->mem.alloc(&l->tab, B);
+    if (e == hipSuccess) e = l->mem.alloc(&l->rrec, B);
+    if (e == hipSuccess) e = l->mem.alloc(&l->tmpl, B * NPIX);
+    if (e == hipSuccess) e = l->mem.alloc(&l->cover, B * NPIX);
+    if (e == hipSuccess) e = l->mem.alloc(&l->mpyr, B * PYR_BYTES);
+    if (e == hipSuccess) e = l->mem.alloc(&l->n_mask, B * N_MASK);
+    if (e == hipSuccess) e = l->mem.alloc(&l->d_out, B);
+    if (e == hipSuccess) e = l->mem.alloc_pinned(&l->pin_in, 2 * B);
+    if (e == hipSuccess) e = l->mem.alloc_pinned(&l->pin_out, B);
+    if (e != hipSuccess) return fail(c, HNET_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    k->localise = l.release();
     return HNET_OK;
 }
 
-// ONE upload {ids | curr ring slot}; {render setup, eligible, render, gather + start, mask pyramid + masked alignment, decide} inside the localise's own events, on
+// ONE upload {ids | curr ring slot}; {render setup, eligible, render, gather + start, mask pyramid + masked alignment, decide} inside the store's events, on
 // the context's staging and the store's alignment scratch; ONE download of the records [n], one synchronisation
 int hnet_sessions_keyframe_localise(hnet_sessions* s, int n, const int32_t* ids, const hnet_keyframe_localise_opts* opts, hnet_keyframe_localise* out) {
     const char* who = "hnet_sessions_keyframe_localise";
     if (!s) return HNET_ERR_INVALID_ARG;
     hnet_ctx* c = s->ctx;
-    KeyLocaliseHooks hk;
-    if (!keyframes_localise_hooks(s, &hk) || !*hk.localise)
+    hnet_keyframes* k = s->kf;
+    if (!k || !k->map || !k->localise)
         return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": the keyframe localise is not enabled (hnet_sessions_enable_keyframe_localise)");
-    KeyLocalise* l = *hk.localise;
+    KeyLocalise* l = static_cast<KeyLocalise*>(k->localise);
     if (!opts || !out) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": opts / out");
     LocaliseOpts o;
     int rc = check_opts(c, opts, who, o);
     if (rc != HNET_OK) return rc;
     if ((rc = sessions_check_ids(s, n, ids)) != HNET_OK) return rc;
-    if ((rc = keyframes_check_tracked(s, n, ids, who)) != HNET_OK) return rc;
+    if ((rc = check_listed(s, n, ids, who, true)) != HNET_OK) return rc;
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
     const int B = c->cfg.max_batch;
-    for (int i = 0; i < n; i++) {
-        l->pin_in[i] = ids[i];
-        l->pin_in[n + i] = 2 * ids[i] + s->st[ids[i]].curr;
-    }
+    slot_table(s, n, ids, nullptr, l->pin_in);
     const int32_t *d_ids = l->d_in, *d_slot = l->d_in + n;
     const size_t pyr = (size_t)B * PYR_BYTES;
-    if (o.levels > 1 && !c->pyr_scratch) HIPCHK(c, dalloc(&c->pyr_scratch, 2 * pyr));
+    if (o.levels > 1 && (rc = ensure_pyr_scratch(c)) != HNET_OK) return rc;
     uint8_t* curr = (uint8_t*)c->stage_curr;
-    const MapStore map{const_cast<uint8_t*>(hk.src.img), hk.entry, hk.mstate, hk.src.n_sessions, hk.src.capacity};
+    const MapStore& map = k->map->dev;
+    const RenderSource src = render_source(k);
+    const AlignScratch al = KeyScratch(k->scratch, B).align();
     const RenderOpts ro{IMG_W, IMG_H, o.mode, 0};
     RobustOpts ao;
     memcpy(&ao, &o.align, sizeof ao);
     hipStream_t st = c->stream;
-    HIPCHK(c, hipMemcpyAsync(l->d_in, l->pin_in, 2 * (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipEventRecord(l->ev[0], st));
-    HIPCHK(c, launch_keyframe_render_setup(d_ids, n, hk.src, nullptr, l->tab, l->rrec, st));
+    if ((rc = begin_call(c, k, l->d_in, l->pin_in, 2 * (size_t)n * sizeof(int32_t))) != HNET_OK) return rc;
+    HIPCHK(c, launch_keyframe_render_setup(d_ids, n, src, nullptr, l->tab, l->rrec, st));
     HIPCHK(c, launch_keyframe_localise_eligible(d_ids, n, map, l->tab, l->rrec, st));
-    HIPCHK(c, launch_keyframe_render(d_ids, n, hk.src, l->tab, ro, l->tmpl, l->cover, l->rrec, st));
-    HIPCHK(c, launch_keyframe_localise_gather(d_slot, n, s->ring, 2 * s->n, l->rrec, o, curr, hk.align.x0, st));
-    HIPCHK(c, launch_photo_align_masked(l->tmpl, l->cover, curr, n, hk.align.x0, ao, o.levels, c->pyr_scratch, c->pyr_scratch ? c->pyr_scratch + pyr : nullptr, l->mpyr,
-                                        l->n_mask, hk.align.start, hk.align.part, hk.align.work, hk.align.rec, st));
-    HIPCHK(c, launch_keyframe_localise_decide(d_ids, n, l->rrec, hk.align.rec, hk.state, map, o, l->d_out, st));      // (level 0 leads [levels][n])
-    HIPCHK(c, hipEventRecord(l->ev[1], st));
-    HIPCHK(c, hipMemcpyAsync(l->pin_out, l->d_out, (size_t)n * sizeof(LocaliseRec), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    float ms = 0;
-    HIPCHK(c, hipEventElapsedTime(&ms, l->ev[0], l->ev[1]));
-    *hk.ms = ms;
-    memcpy(out, l->pin_out, (size_t)n * sizeof(LocaliseRec));
-    return HNET_OK;
+    HIPCHK(c, launch_keyframe_render(d_ids, n, src, l->tab, ro, l->tmpl, l->cover, l->rrec, st));
+    HIPCHK(c, launch_keyframe_localise_gather(d_slot, n, s->ring, 2 * s->n, l->rrec, o, curr, al.x0, st));
+    HIPCHK(c, launch_photo_align_masked(l->tmpl, l->cover, curr, n, al.x0, ao, o.levels, c->pyr_scratch, c->pyr_scratch ? c->pyr_scratch + pyr : nullptr, l->mpyr,
+                                        l->n_mask, al.start, al.part, al.work, al.rec, st));
+    HIPCHK(c, launch_keyframe_localise_decide(d_ids, n, l->rrec, al.rec, k->state, map, o, l->d_out, st));      // (level 0 leads [levels][n])
+    return finish_call(c, k, l->d_out, l->pin_out, out, (size_t)n * sizeof(LocaliseRec));
 }
 
 }  // extern "C"

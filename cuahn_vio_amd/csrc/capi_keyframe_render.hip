@@ -1,10 +1,11 @@
 // capi_keyframe_render.hip — hnet_keyframe_render_fit_view, hnet_op_keyframe_render, hnet_sessions_enable_keyframe_render and
 // hnet_sessions_keyframe_render of include/hnet.h (keyframe_render_dev.h, csrc/kernels_keyframe_render.hip): a keyframe map rendered into a
 // view with its cover image and seam statistics.  The operator-level call owns its buffers as device temporaries.  The sessions call reads the map and
-// the states of the keyframe store (capi_keyframe.hip, through keyframes_render_hooks) and writes only buffers of its own, allocated by its enable:
-// additive, a store whose render was never enabled holds a null pointer and allocates and launches nothing here.
-#include "sessions_internal.h"
-#include "keyframe_render_dev.h"
+// the states of the keyframe store (keyframes_internal.h) and writes only buffers of its own, allocated by its enable: additive, a store whose render
+// was never enabled holds a null pointer and allocates and launches nothing here.
+#include "keyframes_internal.h"
+
+#include <memory>
 
 using namespace hnet;
 using namespace capi;
@@ -20,36 +21,21 @@ static_assert(sizeof(hnet_keyframe_render_rec) == sizeof(RenderRec) && offsetof(
 static_assert((int)HNET_RENDER_FEWEST_LINKS == kr::FEWEST_LINKS && (int)HNET_RENDER_NEWEST == kr::NEWEST && (int)HNET_RENDER_MEAN == kr::MEAN &&
               HNET_RENDER_MAX_DIM == kr::MAX_DIM, "HNET_RENDER_* are the header's");
 
-namespace capi {
+namespace {
 
 // the render of a store: sized at its enable for max_batch B and views up to max_w x max_h
-struct KeyRender {
+struct KeyRender : KeyLayer {
     int max_w = 0, max_h = 0;
     uint8_t* d_in = nullptr;                   // device: a call's table {ids [n] i32, padded to 8 bytes | views [n][9] f64}
     RenderTab* tab = nullptr;                  // device [B]
     uint8_t* d_out = nullptr;                  // device: a call's results {records [n] | images [n][h][w] | covers [n][h][w]}, packed for ONE download
     uint8_t *pin_in = nullptr, *pin_out = nullptr;     // pinned: the same two blocks
-    hipEvent_t ev[2] = {nullptr, nullptr};     // around the two launches of the last render
 };
 
-void keyframes_render_free(KeyRender* r) {
-    if (!r) return;
-    if (r->d_in) (void)hipFree(r->d_in);
-    if (r->tab) (void)hipFree(r->tab);
-    if (r->d_out) (void)hipFree(r->d_out);
-    if (r->pin_in) (void)hipHostFree(r->pin_in);
-    if (r->pin_out) (void)hipHostFree(r->pin_out);
-    for (hipEvent_t e : r->ev)
-        if (e) (void)hipEventDestroy(e);
-    delete r;
-}
-
-}  // namespace capi
-
-namespace {
-
-size_t ids_bytes(int n) { return ((size_t)n * sizeof(int32_t) + 7) & ~(size_t)7; }
-size_t in_bytes(int n) { return ids_bytes(n) + (size_t)n * 9 * sizeof(double); }
+constexpr size_t ids_bytes(int n) { return ((size_t)n * sizeof(int32_t) + 7) & ~(size_t)7; }
+constexpr size_t in_bytes(int n) { return ids_bytes(n) + (size_t)n * 9 * sizeof(double); }
+static_assert(KeyUpload(1, KeyUpload::VIEW).view == ids_bytes(1) && KeyUpload(1, KeyUpload::VIEW).entry == in_bytes(1),
+              "the operator-level block begins with the table of a sessions call of one");
 size_t out_bytes(int n, int w, int h) { return (size_t)n * (sizeof(RenderRec) + 2 * (size_t)w * h); }
 
 // o <- *opts with its pad zeroed, or the context's error; max_w, max_h: the largest view the caller's buffers hold
@@ -83,24 +69,23 @@ int hnet_op_keyframe_render(hnet_ctx* c, int m, const uint8_t* images, const hne
     if (rc != HNET_OK) return rc;
     if (!all_finite(h_origin_view, 9)) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": h_origin_view is not finite");
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    // the upload block: the table as the sessions call lays it out, then the entries (8-byte aligned) and the images (16-byte aligned)
-    const size_t ent_off = in_bytes(1), img_off = (ent_off + (size_t)m * sizeof(MapEntry) + 15) & ~(size_t)15, in_total = img_off + (size_t)m * NPIX;
+    const KeyUpload up(m, KeyUpload::VIEW | KeyUpload::IMAGES);       // (the table as the sessions call lays it out, then the entries and the images)
     const size_t px = (size_t)o.width * o.height, out_total = out_bytes(1, o.width, o.height);
-    std::vector<uint8_t> h_in(in_total, 0), h_out(out_total);
-    memcpy(h_in.data() + ids_bytes(1), h_origin_view, 9 * sizeof(double));
-    memcpy(h_in.data() + ent_off, entries, (size_t)m * sizeof(MapEntry));
-    memcpy(h_in.data() + img_off, images, (size_t)m * NPIX);
+    std::vector<uint8_t> h_in(up.total, 0), h_out(out_total);
+    memcpy(h_in.data() + up.view, h_origin_view, 9 * sizeof(double));
+    memcpy(h_in.data() + up.entry, entries, (size_t)m * sizeof(MapEntry));
+    memcpy(h_in.data() + up.images, images, (size_t)m * NPIX);
     DevTemps t;
     uint8_t *d_in = nullptr, *d_out = nullptr;
     RenderTab* d_tab = nullptr;
-    HIPCHK(c, t.alloc(&d_in, in_total));
+    HIPCHK(c, t.alloc(&d_in, up.total));
     HIPCHK(c, t.alloc(&d_out, out_total));
     HIPCHK(c, t.alloc(&d_tab, 1));
-    const RenderSource src{d_in + img_off, reinterpret_cast<const MapEntry*>(d_in + ent_off), nullptr, 1, m};
+    const RenderSource src{d_in + up.images, reinterpret_cast<const MapEntry*>(d_in + up.entry), nullptr, 1, m};
     RenderRec* d_rec = reinterpret_cast<RenderRec*>(d_out);
     hipStream_t st = c->stream;
-    HIPCHK(c, hipMemcpyAsync(d_in, h_in.data(), in_total, hipMemcpyHostToDevice, st));
-    HIPCHK(c, launch_keyframe_render_setup(reinterpret_cast<const int32_t*>(d_in), 1, src, reinterpret_cast<const double*>(d_in + ids_bytes(1)), d_tab, d_rec, st));
+    HIPCHK(c, hipMemcpyAsync(d_in, h_in.data(), up.total, hipMemcpyHostToDevice, st));
+    HIPCHK(c, launch_keyframe_render_setup(reinterpret_cast<const int32_t*>(d_in), 1, src, reinterpret_cast<const double*>(d_in + up.view), d_tab, d_rec, st));
     HIPCHK(c, launch_keyframe_render(reinterpret_cast<const int32_t*>(d_in), 1, src, d_tab, o, d_out + sizeof(RenderRec), d_out + sizeof(RenderRec) + px, d_rec, st));
     HIPCHK(c, hipMemcpyAsync(h_out.data(), d_out, out_total, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
@@ -114,40 +99,36 @@ int hnet_sessions_enable_keyframe_render(hnet_sessions* s, int max_width, int ma
     const char* who = "hnet_sessions_enable_keyframe_render";
     if (!s) return HNET_ERR_INVALID_ARG;
     hnet_ctx* c = s->ctx;
-    KeyRenderHooks hk;
-    if (!keyframes_render_hooks(s, &hk)) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": the keyframe map is not enabled (hnet_sessions_enable_keyframe_map)");
-    if (*hk.render) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": the keyframe render is already enabled");
+    hnet_keyframes* k = s->kf;
+    if (!k || !k->map) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": the keyframe map is not enabled (hnet_sessions_enable_keyframe_map)");
+    if (k->render) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": the keyframe render is already enabled");
     if (max_width < 1 || max_width > kr::MAX_DIM || max_height < 1 || max_height > kr::MAX_DIM)
         return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": 1 <= max_width, max_height <= HNET_RENDER_MAX_DIM");
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
     const int B = c->cfg.max_batch;
-    KeyRender* r = new KeyRender();
+    auto r = std::make_unique<KeyRender>();
     r->max_w = max_width;
     r->max_h = max_height;
-    hipError_t e = hipMalloc((void**)&r->d_in, in_bytes(B));
-    if (e == hipSuccess) e = hipMalloc((void**)&r->tab, (size_t)B * sizeof(RenderTab));
-    if (e == hipSuccess) e = hipMalloc((void**)&r->d_out, out_bytes(B, max_width, max_height));
-    if (e == hipSuccess) e = hipHostMalloc((void**)&r->pin_in, in_bytes(B), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&r->pin_out, out_bytes(B, max_width, max_height), hipHostMallocDefault);
-    for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipEventCreate(&r->ev[i]);
-    if (e != hipSuccess) {
-        keyframes_render_free(r);
-        return fail(c, HNET_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-    }
-    *hk.render = r;
+    hipError_t e = r->mem.alloc(&r->d_in, in_bytes(B));
+    if (e == hipSuccess) e = r->mem.alloc(&r->tab, (size_t)B);
+    if (e == hipSuccess) e = r->mem.alloc(&r->d_out, out_bytes(B, max_width, max_height));
+    if (e == hipSuccess) e = r->mem.alloc_pinned(&r->pin_in, in_bytes(B));
+    if (e == hipSuccess) e = r->mem.alloc_pinned(&r->pin_out, out_bytes(B, max_width, max_height));
+    if (e != hipSuccess) return fail(c, HNET_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    k->render = r.release();
     return HNET_OK;
 }
 
-// ONE upload {ids | views}, the two launches inside the render's own events, ONE download {records | images | covers}, one synchronisation
+// ONE upload {ids | views}, the two launches inside the store's events, ONE download {records | images | covers}, one synchronisation
 int hnet_sessions_keyframe_render(hnet_sessions* s, int n, const int32_t* ids, const double* h_origin_view, const hnet_keyframe_render_opts* opts,
                                   uint8_t* out_img, uint8_t* out_cover, hnet_keyframe_render_rec* out) {
     const char* who = "hnet_sessions_keyframe_render";
     if (!s) return HNET_ERR_INVALID_ARG;
     hnet_ctx* c = s->ctx;
-    KeyRenderHooks hk;
-    if (!keyframes_render_hooks(s, &hk) || !*hk.render)
+    hnet_keyframes* k = s->kf;
+    if (!k || !k->map || !k->render)
         return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": the keyframe render is not enabled (hnet_sessions_enable_keyframe_render)");
-    KeyRender* r = *hk.render;
+    KeyRender* r = static_cast<KeyRender*>(k->render);
     if (!opts || !out_img || !out_cover || !out) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": opts / out_img / out_cover / out");
     RenderOpts o;
     int rc = check_opts(c, opts, r->max_w, r->max_h, who, o);
@@ -155,7 +136,7 @@ int hnet_sessions_keyframe_render(hnet_sessions* s, int n, const int32_t* ids, c
     if ((rc = sessions_check_ids(s, n, ids)) != HNET_OK) return rc;
     if (h_origin_view) {
         if (!all_finite(h_origin_view, (size_t)n * 9)) return fail(c, HNET_ERR_INVALID_ARG, std::string(who) + ": h_origin_view is not finite");
-    } else if ((rc = keyframes_check_tracked(s, n, ids, who)) != HNET_OK) {
+    } else if ((rc = check_listed(s, n, ids, who, true)) != HNET_OK) {
         return rc;
     }
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
@@ -167,17 +148,12 @@ int hnet_sessions_keyframe_render(hnet_sessions* s, int n, const int32_t* ids, c
     const size_t px = (size_t)n * o.width * o.height, recs = (size_t)n * sizeof(RenderRec), total = recs + 2 * px;
     const int32_t* d_ids = reinterpret_cast<const int32_t*>(r->d_in);
     RenderRec* d_rec = reinterpret_cast<RenderRec*>(r->d_out);
+    const RenderSource src = render_source(k);
     hipStream_t st = c->stream;
-    HIPCHK(c, hipMemcpyAsync(r->d_in, r->pin_in, up, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipEventRecord(r->ev[0], st));
-    HIPCHK(c, launch_keyframe_render_setup(d_ids, n, hk.src, h_origin_view ? reinterpret_cast<const double*>(r->d_in + head) : nullptr, r->tab, d_rec, st));
-    HIPCHK(c, launch_keyframe_render(d_ids, n, hk.src, r->tab, o, r->d_out + recs, r->d_out + recs + px, d_rec, st));
-    HIPCHK(c, hipEventRecord(r->ev[1], st));
-    HIPCHK(c, hipMemcpyAsync(r->pin_out, r->d_out, total, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    float ms = 0;
-    HIPCHK(c, hipEventElapsedTime(&ms, r->ev[0], r->ev[1]));
-    *hk.ms = ms;
+    if ((rc = begin_call(c, k, r->d_in, r->pin_in, up)) != HNET_OK) return rc;
+    HIPCHK(c, launch_keyframe_render_setup(d_ids, n, src, h_origin_view ? reinterpret_cast<const double*>(r->d_in + head) : nullptr, r->tab, d_rec, st));
+    HIPCHK(c, launch_keyframe_render(d_ids, n, src, r->tab, o, r->d_out + recs, r->d_out + recs + px, d_rec, st));
+    if ((rc = finish_call(c, k, r->d_out, r->pin_out, nullptr, total)) != HNET_OK) return rc;
     memcpy(out, r->pin_out, recs);
     memcpy(out_img, r->pin_out + recs, px);
     memcpy(out_cover, r->pin_out + recs + px, px);

@@ -35,7 +35,8 @@ int run(hnet_ctx* c, const uint8_t* d_img1, const uint8_t* d_img2, int n, const 
     Opts o;
     memcpy(&o, &opts, sizeof o);
     const size_t pyr = (size_t)c->cfg.max_batch * PYR_BYTES;
-    if (levels > 1 && !c->pyr_scratch) HIPCHK(c, dalloc(&c->pyr_scratch, 2 * pyr));
+    if (levels > 1)
+        if (const int rc = ensure_pyr_scratch(c); rc != HNET_OK) return rc;
     DevTemps t;
     Sums* d_part = nullptr;
     Work* d_work = nullptr;

@@ -55,7 +55,7 @@ hipError_t launch_filter_kfm_finish(const int32_t* ids, int n, int n_sessions, c
 
 }  // namespace hnet
 
-// ---- what capi_filters.hip reaches of the keyframe store through capi_keyframe.hip (the store's type is private to that file)
+// ---- what capi_filters.hip reaches of the keyframe store through capi_keyframe.hip (the store itself: keyframes_internal.h)
 namespace capi __attribute__((visibility("hidden"))) {
 
 // the recovering part of a track: the reloc options, the device table of the oriented search and, of a track inside a filter step, the per-session

@@ -1,5 +1,5 @@
 // keyframe_adjust_dev.h — the joint adjustment of a keyframe map (include/hnet.h hnet_op_keyframe_adjust_solve, hnet_op_keyframe_adjust,
-// hnet_sessions_keyframe_adjust): what capi_keyframe_adjust.hip, capi_keyframe.hip and kernels_keyframe_adjust.hip share.  The device compiles
+// hnet_sessions_keyframe_adjust): what capi_keyframe_adjust.hip, keyframes_internal.h and kernels_keyframe_adjust.hip share.  The device compiles
 // include/hnet_keyframe_adjust.h itself (host + device functions): pair_job, judge_edge, build, solve and finish are the functions
 // tests/test_keyframe_adjust_cpu.py pins on the host.
 #pragma once
@@ -43,17 +43,3 @@ hipError_t launch_keyframe_adjust_solve(const int32_t* ids, int n, const AdjustS
                                         hipStream_t s);
 
 }  // namespace hnet
-
-// ---- host side: what capi_keyframe_adjust.hip reads of the keyframe store of capi_keyframe.hip
-struct hnet_sessions;
-namespace capi __attribute__((visibility("hidden"))) {
-
-struct KeyAdjust;                                    // the adjustment's own buffers (capi_keyframe_adjust.hip); the store holds the pointer
-void keyframes_adjust_free(KeyAdjust* a);            // capi_keyframe_adjust.hip; called when the store is freed
-// the alignment's scratch for max_batch pairs: the store's, as a revisit uses it
-struct AdjustAlign { hnet::RobustRec* rec; hnet::RobustStart* start; hnet::RobustWork* work; hnet::RobustSums* part; float* x0; };
-// the store's map, states and alignment scratch, the place of its adjust pointer and of its last device time; false: keyframes or the map were never enabled
-struct KeyAdjustHooks { hnet::AdjustSource src; AdjustAlign align; KeyAdjust** adjust; double* ms; };
-bool keyframes_adjust_hooks(hnet_sessions* s, KeyAdjustHooks* h);
-
-}  // namespace capi

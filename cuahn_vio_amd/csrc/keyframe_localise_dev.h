@@ -3,7 +3,6 @@
 // functions): start and decide_localise are the functions tests/test_keyframe_localise_cpu.py pins on the host.
 #pragma once
 #include "keyframe_render_dev.h"
-#include "keyframe_adjust_dev.h"
 #include "photo_masked_dev.h"
 
 #pragma clang force_cuda_host_device begin
@@ -33,16 +32,3 @@ hipError_t launch_keyframe_localise_decide(const int32_t* ids, int n, const Rend
                                            const LocaliseOpts& opts, LocaliseRec* out, hipStream_t s);
 
 }  // namespace hnet
-
-// ---- host side: what capi_keyframe_localise.hip reads of the keyframe store of capi_keyframe.hip
-struct hnet_sessions;
-namespace capi __attribute__((visibility("hidden"))) {
-
-struct KeyLocalise;                                  // the localise's own buffers (capi_keyframe_localise.hip); the store holds the pointer
-void keyframes_localise_free(KeyLocalise* l);        // capi_keyframe_localise.hip; called when the store is freed
-// the store's map as the render reads it, the tables a decision rewrites, the alignment's scratch for max_batch pairs, the place of the localise pointer and of
-// the store's last device time; false: keyframes or the map were never enabled
-struct KeyLocaliseHooks { hnet::RenderSource src; hnet::KeyState* state; hnet::MapState* mstate; hnet::MapEntry* entry; AdjustAlign align; KeyLocalise** localise; double* ms; };
-bool keyframes_localise_hooks(hnet_sessions* s, KeyLocaliseHooks* h);
-
-}  // namespace capi

@@ -1,5 +1,5 @@
 // keyframe_render_dev.h — a keyframe map rendered into a view (include/hnet.h hnet_op_keyframe_render, hnet_sessions_keyframe_render): what
-// capi_keyframe_render.hip, capi_keyframe.hip and kernels_keyframe_render.hip share.  The device compiles include/hnet_keyframe_render.h itself (host +
+// capi_keyframe_render.hip, keyframes_internal.h and kernels_keyframe_render.hip share.  The device compiles include/hnet_keyframe_render.h itself (host +
 // device functions): render_setup, render_sample, render_pixel and seam_add are the functions tests/test_keyframe_render_rule.py pins on the host.
 #pragma once
 #include "keyframe_map_dev.h"
@@ -35,17 +35,3 @@ hipError_t launch_keyframe_render(const int32_t* ids, int n, const RenderSource&
                                   uint8_t* out_cover, RenderRec* rec, hipStream_t s);
 
 }  // namespace hnet
-
-// ---- host side: what capi_keyframe_render.hip reads of the keyframe store of capi_keyframe.hip
-struct hnet_sessions;
-namespace capi __attribute__((visibility("hidden"))) {
-
-struct KeyRender;                                    // the render's own buffers (capi_keyframe_render.hip); the store holds the pointer
-void keyframes_render_free(KeyRender* r);            // capi_keyframe_render.hip; called when the store is freed
-// the store's map, states, the place of its render pointer and of its last device time; false: keyframes or the map were never enabled
-struct KeyRenderHooks { hnet::RenderSource src; KeyRender** render; double* ms; };
-bool keyframes_render_hooks(hnet_sessions* s, KeyRenderHooks* h);
-// every listed session holds a keyframe that its last track took from its latest image, or HNET_ERR_NOT_READY (check_listed of capi_keyframe.hip)
-int keyframes_check_tracked(hnet_sessions* s, int n, const int32_t* ids, const char* who);
-
-}  // namespace capi
